@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- backward-warp Mpixels/s (+ RANSAC hypotheses/s) on N MI355X of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Run as that plain command with N > 1 it starts its own ranks (one process per GPU, `torch.distributed.run` on
 127.0.0.1, before anything touches the GPU in the parent); under `torch.distributed.run` (the driver's launch) it is
 a rank.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, the clock ramp and W warm-up steps, K timed steps, the
+outputs of the last step if --dump-outputs is given, the JSON line.  Everything else below (the load facts of the
+roofline, the extra keys, the CPU baseline) runs only with --full.
+--dump-outputs DIR: DIR/warp_out.npy (DIR/warp_out_rank<r>.npy at N > 1), float32, = what the last timed step left in
+the destination frames, all of it when it is small, else a fixed stratified sample (sample_index) of 8 Mi values in all.
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on):
   transformImageH-style warp of 3840x2160 RGB u8 frames with the survey's mild-perspective Hs,
@@ -14,7 +20,7 @@ Workload (BASELINE.json configs[1], the configuration the metric is quoted on):
   resident in HBM (batch source + destination = 1.5 GB > the 256 MB Infinity Cache, so the
   traffic is HBM traffic, not cache traffic).
   N > 1: every rank warps its own batch (shard by image, no collective): weak scaling (`value`).
-Extra keys of the same JSON line:
+Extra keys of the same JSON line (--full):
   warp_8k       the north_star's 8K warp: 8 distinct 7680x4320 frames per launch, same kernel, with its own kernel
                 time / achieved GB/s / fraction of the HBM roofline (N = 1);
   config5_batch_1080p  BASELINE config 5's warp: 512 distinct 1080p frames sharded by image, one launch per rank.
@@ -42,6 +48,8 @@ sys.path.insert(0, ROOT)
 H_S = np.array([[1.02, 0.01, 5.0], [0.015, 0.98, 7.0], [1e-5, 2e-5, 1.0]])
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec peak
 PREWARM_MS = 150.0     # untimed clock ramp before the warm-up steps (see run_rank)
+DUMP_VALUES = 8 << 20  # --dump-outputs: at most this many float32 values over all ranks (32 MB)
+DUMP_SEED = 20240607   # the fixed seed of the sample positions
 
 
 def parse_args(argv=None):
@@ -51,9 +59,41 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=32, help="4K frames per step (per GPU)")
     ap.add_argument("--src", default="3840x2160", help="source frame WxH (default: the BASELINE 4K configuration)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (no 8K / RANSAC / config 4 legs)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/*.npy (float32; "
+                         "bench_outputs/ is ignored by git)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the load facts, the 8K / config 5 / other-kernel / RANSAC / config 4 legs and the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only (no 8K / RANSAC / config 4 legs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def sample_index(n, count, seed=DUMP_SEED):
+    """`count` sorted distinct positions in [0, n): one uniformly drawn position in each of `count` equal strata (fixed seed),
+    so that the sample covers every frame and every part of a frame."""
+    lo = np.arange(count, dtype=np.int64) * n // count
+    hi = np.arange(1, count + 1, dtype=np.int64) * n // count
+    return lo + (np.random.default_rng(seed).random(count) * (hi - lo)).astype(np.int64)
+
+
+def dump_outputs(path, out, rank=0, world=1):
+    """Write the destination tensor of the timed launches (what the caller of the warp receives) as float32 .npy: whole when it
+    holds at most this rank's share of DUMP_VALUES, else the values at sample_index(out.numel(), share) of its flattened form."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_VALUES // world
+    flat = out.reshape(-1)
+    if flat.numel() <= share:
+        arr = out.float().cpu().numpy()
+    else:
+        idx = torch.from_numpy(sample_index(flat.numel(), share)).to(flat.device)
+        arr = flat[idx].float().cpu().numpy()
+    name = "warp_out" if world == 1 else "warp_out_rank%d" % rank
+    np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def cpu_baseline(frames_note, src_w, src_h):
@@ -414,7 +454,10 @@ def run_rank(args, backend, dist=None):
     elapsed = max_over_ranks(elapsed)
     value = world * B * out_h * out_w / 1e6 * args.steps / elapsed
     alg_bytes = B * (3 * src_h * src_w + 3 * out_h * out_w)
-    load = backend.load_facts(step) if hasattr(backend, "load_facts") else {}       # every rank: its own chip's clock and power
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, keep[1], rank, world)     # keep[1]: the destination frames of the last timed step
+    # every rank: its own chip's clock and power (1.2 s more of the same launches: --full only)
+    load = backend.load_facts(step) if args.full and hasattr(backend, "load_facts") else {}
     per_rank_load = None
     if world > 1 and load:
         t = backend.tensor([0.0] * (2 * world), "float64")
@@ -425,7 +468,7 @@ def run_rank(args, backend, dist=None):
     del keep, step
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # ---- the other kernels of the warp entry point on the same workload (informational, N = 1) ----------------
         if world == 1:
             extras["other_warp_kernels"] = backend.other_kernels_leg(src_w, src_h, min(B, 16))
@@ -489,7 +532,8 @@ def run_rank(args, backend, dist=None):
         roof["frac_8k"], roof["kernel_ms_8k"] = extras["warp_8k"]["frac"], extras["warp_8k"]["kernel_ms"]
     at_cap = bool(load.get("power_w") and load.get("power_cap_w") and load["power_w"] >= 0.97 * load["power_cap_w"])
     # what binds, from the run's own measurements + the committed counters: at the power cap with the VALU >= 90 % busy the kernel's
-    # time follows its arithmetic energy ("valu+power"); below that it is the memory system ("hbm": peak = HBM3E, the contract's roofline)
+    # time follows its arithmetic energy ("valu+power"); below that it is the memory system ("hbm": peak = HBM3E, the contract's roofline).
+    # Without --full the power is not read and the bound stays the contract's "hbm".
     roof["bound"] = "valu+power" if (at_cap and (roof.get("valu_frac_pmc") or 0) > 0.9) else "hbm"
     if load.get("power_w") and load.get("power_cap_w") and load["power_w"] >= 0.97 * load["power_cap_w"]:
         # the launches run AT the board's power cap and the chip holds a clock below its 2.4 GHz maximum: the bound that
@@ -504,14 +548,14 @@ def run_rank(args, backend, dist=None):
         "config": {"workload": "transformImageH warp %dx%d RGB u8 bilinear -> %dx%d u8, %d distinct frames per "
                                "GPU per step, Hs mild perspective" % (src_w, src_h, out_h, out_w, B),
                    "frames_per_step_per_gpu": B, "sharding": "by image, no collective",
-                   "untimed_clock_ramp_ms": PREWARM_MS},
+                   "untimed_clock_ramp_ms": PREWARM_MS, "full": args.full},
         "roofline": roof,
         "rccl": {"backend": backend.collective if world > 1 else None, "world_size_seen_by_rank": seen},
     }
     line.update(extras)
     if "ransac" in line and "all_ranks_decoded" in line["ransac"].get("K=100000", {}):
         line["rccl"]["all_ranks_agree_on_winner"] = len(set(line["ransac"]["K=100000"]["all_ranks_decoded"])) == 1
-    if not args.no_cpu and world == 1:
+    if args.full and not args.no_cpu and world == 1:
         line["cpu_baseline"] = cpu_baseline("%d-frame batch" % B, src_w, src_h)
     return line
 

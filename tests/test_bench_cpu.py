@@ -68,7 +68,7 @@ def _rank(rank, world, port, path):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    args = bench.parse_args(["--gpus", str(world), "--steps", "4", "--warmup", "1", "--frames", "2", "--src", "640x480"])
+    args = bench.parse_args(["--gpus", str(world), "--steps", "4", "--warmup", "1", "--frames", "2", "--src", "640x480", "--full"])
     bench.PREWARM_MS = 0.0
     line = bench.run_rank(args, CpuStandIn(), dist)
     assert (line is None) == (rank != 0)
@@ -104,6 +104,82 @@ def test_single_rank_line_has_the_contract_keys():
     assert line["n_gpus"] == 1 and line["config"]["workload"].startswith("transformImageH warp 640x480")
     for key in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel"):
         assert key in line["roofline"], key
+
+
+class CountingStandIn(CpuStandIn):
+    """CpuStandIn whose warp writes the number of its launch into a real destination tensor and which records every leg asked of it."""
+
+    def __init__(self):
+        super().__init__()
+        self.launches, self.calls = 0, []
+
+    def make_warp(self, frames, src_w, src_h, seed, rows_of=None):
+        self.calls.append(("make_warp", frames, src_w, src_h))
+        out_h, out_w = src_h - 100, src_w - 60
+        dst = torch.zeros((frames, out_h, out_w, 3), dtype=torch.uint8)
+
+        def step():
+            self.launches += 1
+            dst.copy_((torch.arange(dst.numel()) + self.launches).reshape(dst.shape) % 251)
+        return step, out_h, out_w, (0, out_h), "stand-in", (None, dst, None, None)
+
+    def load_facts(self, step, seconds=1.2):
+        self.calls.append(("load_facts",))
+        return {}
+
+    def make_search(self, K, b, e, settle=False):
+        self.calls.append(("make_search", K))
+        return super().make_search(K, b, e, settle)
+
+
+def test_plain_run_times_only_the_headline():
+    """Without --full the rank does set-up, warm-up, EXACTLY --steps timed launches and the line: no load facts, no other leg."""
+    bench.PREWARM_MS = 0.0
+    be = CountingStandIn()
+    line = bench.run_rank(bench.parse_args(["--steps", "7", "--warmup", "2", "--frames", "2", "--src", "640x480"]), be, None)
+    assert be.launches == 2 + 7 and be.calls == [("make_warp", 2, 640, 480)]
+    assert line["steps"] == 7 and line["ms_per_step"] > 0 and line["config"]["full"] is False
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    for key in ("warp_8k", "strong_8k", "config5_batch_1080p", "ransac", "other_warp_kernels", "config4_panorama_8k", "cpu_baseline"):
+        assert key not in line, key
+    be = CountingStandIn()
+    line = bench.run_rank(bench.parse_args(["--steps", "3", "--warmup", "1", "--frames", "2", "--src", "640x480", "--full", "--no-cpu",
+                                            "--no-extras"]), be, None)
+    assert be.calls == [("make_warp", 2, 640, 480), ("load_facts",)] and line["config"]["full"] is True    # (the legs: world 2 test)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_are_the_last_step(tmp_path):
+    """--dump-outputs writes what the LAST timed launch left in the destination, as float32; the same arguments give the same file."""
+    bench.PREWARM_MS = 0.0
+    args = ["--steps", "5", "--warmup", "2", "--frames", "2", "--src", "160x140"]
+    be = CountingStandIn()
+    bench.run_rank(bench.parse_args(args + ["--dump-outputs", str(tmp_path / "a")]), be, None)
+    got = np.load(tmp_path / "a" / "warp_out.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 40, 100, 3)                # small: the whole output, in its shape
+    assert np.array_equal(got.reshape(-1), (np.arange(got.size) + 7) % 251)       # launch 7 = 2 warm-up + 5 timed
+    bench.run_rank(bench.parse_args(args + ["--dump-outputs", str(tmp_path / "b")]), CountingStandIn(), None)
+    assert np.array_equal(np.load(tmp_path / "b" / "warp_out.npy"), got)
+
+
+def test_dump_outputs_sample_a_large_output(tmp_path, monkeypatch):
+    """A destination larger than the budget is written as a fixed stratified sample: sorted distinct positions, one per stratum, the
+    same every time; at N > 1 every rank writes its own file within its share of the budget."""
+    monkeypatch.setattr(bench, "DUMP_VALUES", 1000)
+    out = (torch.arange(3 * 50 * 70 * 3) % 256).to(torch.uint8).reshape(3, 50, 70, 3)
+    bench.dump_outputs(str(tmp_path), out)
+    bench.dump_outputs(str(tmp_path), out, rank=1, world=2)
+    idx = bench.sample_index(out.numel(), 1000)
+    assert np.array_equal(idx, bench.sample_index(out.numel(), 1000)) and (np.diff(idx) > 0).all()
+    strata = np.arange(1001) * out.numel() // 1000
+    assert ((idx >= strata[:-1]) & (idx < strata[1:])).all()
+    got = np.load(tmp_path / "warp_out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, out.reshape(-1).numpy()[idx])
+    assert np.load(tmp_path / "warp_out_rank1.npy").size == 500
+    monkeypatch.undo()
+    assert bench.DUMP_VALUES * 4 <= 64 << 20                                       # the whole dump stays within 64 MB
 
 
 def test_plain_command_self_launches():

@@ -1,5 +1,5 @@
 """Per-(kernel, grid size) statistics of a rocprofv3 --kernel-trace CSV: calls, mean / median / min / max duration (us), stddev.
-rocprofv3's own --stats folds every launch of a kernel into one row; bench.py launches the headline kernel on three workloads
+rocprofv3's own --stats folds every launch of a kernel into one row; `bench.py --full` launches the headline kernel on three workloads
 (4K x 32, 8K x 8, 512 x 1080p), so the per-grid table is what reproduces the bench line.
    python tools/kernel_stats_by_grid.py <dir with *kernel_trace.csv> > profiles/rNN_kernel_stats_by_grid.csv"""
 import collections, csv, glob, os, statistics, sys
