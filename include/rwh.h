@@ -352,6 +352,11 @@ RWH_API int rwh_host_legacy_randint(uint32_t* key, int32_t* pos, int64_t m, int6
  *   sample and every hypothesis within 32 counts of the best or of `need` get a count INTERVAL (rwh_score_interval, budgets of 16 /
  *   64 float32 ulps of natural scale) -- those whose interval is not a point AND reaches the best lower bound or `need`.
  *   'backward' / 'reproj': every flagged sample and every hypothesis within min(margin_cap, 3 + count / 16) of a decision.
+ *   The 'fwd' rule is exact under this MODEL, and assumes nothing more: (a) a sample without an always-bit (REPEATED / SINGULAR /
+ *   DEGENERATE) has the reference's count inside its interval, and K2's count too; (b) an UNFLAGGED sample has the reference's count
+ *   within 16 of K2's (the 32-count window is placed by the best count of an unflagged sample); (c) an RWH_HYP_ILLCOND sample's
+ *   count is bounded only by its interval; (d) always-bit samples carry no information.  The winner is then settled or has a point
+ *   interval.  (A NaN or Inf coordinate in pts_a: the margin rule.)
  * What remains EMPIRICAL in both: that LAPACK's float32 H lies within the budget (resp. that an unflagged K1 count is within the
  * margin) of K1's -- measured on 13 problem families and ~30 000 soak cases (profiles/r04_lab_notes.txt), not proven.
  *   pts_a, pts_b: m x 2 float32, idx: k x 4 int32 -- HOST arrays (the reference's inputs are host arrays; idx = the first

@@ -20,6 +20,7 @@
 #include <cstdio>
 #endif
 #include "rwh_common.h"
+#include "rwh_settle.h"
 
 namespace {
 // sections of the two workspaces (byte offsets, 256-byte aligned)
@@ -79,7 +80,6 @@ struct Stamps {
 #define STAMP(w) ((void)0)
 #endif
 
-inline int margin_of(int best, int cap) { const int v = 3 + (best > 0 ? best : 0) / 16; return v < cap ? v : cap; }
 }  // namespace
 
 extern "C" int rwh_ransac_run_layout(int m, int k, long long* offsets, int n_offsets) {
@@ -96,7 +96,6 @@ extern "C" int rwh_ransac_run_layout(int m, int k, long long* offsets, int n_off
 // ill-conditioned samples: 16 and 64 float32 ulps (no containment failure at 8 ulps on 13 families x 20 000 samples;
 // profiles/r04_lab_notes.txt).  'backward' / 'reproj' keep the margin rule of rounds 2-3 (an interval through the inverse is
 // too wide to be useful).
-static constexpr int IV_NEAR = 32;
 static constexpr double IV_DELTA0 = 0x1p-20, IV_DELTA1 = 0x1p-18;
 
 extern "C" int rwh_ransac_run(const float* pts_a, const float* pts_b, int m, const int32_t* idx, int k, double th, int loss,
@@ -164,15 +163,17 @@ extern "C" int rwh_ransac_run(const float* pts_a, const float* pts_b, int m, con
 
     // ---- hypotheses settled so far: position in the Hset / cnt_set / mask_set tables, -1 = not settled -------------------
     // (per-thread scratch that keeps its pages between calls: four fresh 400 KB vectors per call at k = 100 000 cost ~0.15 ms of page faults)
-    static thread_local std::vector<int> pos_tl, cnt_tl, lo_tl, hi_tl, act_tl;
-    std::vector<int>&pos = pos_tl, &cnt = cnt_tl, &lo = lo_tl, &hi = hi_tl, &act = act_tl;
+    static thread_local rwh_settle::State st_tl;
+    rwh_settle::State& sst = st_tl;
+    std::vector<int>&pos = sst.pos, &cnt = sst.cnt;
+    int& nset = sst.nset;
     pos.assign((size_t)k, -1);
     cnt.resize((size_t)k);
-    int nset = 0, rounds = 0;
-    auto settle = [&](int n_rows) -> int {      // h_rows[0..n_rows) -> H by the reference's solver, counts + masks by K2
+    nset = 0;
+    auto settle = [&](const int32_t* rows, int n_rows) -> int {      // rows[0..n_rows) -> H by the reference's solver, counts + masks by K2
         if (n_rows == 0) return RWH_OK;
         std::vector<int32_t> samples(4 * (size_t)n_rows);
-        for (int j = 0; j < n_rows; ++j) memcpy(&samples[4 * (size_t)j], idx + 4 * (size_t)h_rows[j], 16);
+        for (int j = 0; j < n_rows; ++j) memcpy(&samples[4 * (size_t)j], idx + 4 * (size_t)rows[j], 16);
         int r = rwh_host_dlt4_svd(pts_a, pts_b, m, samples.data(), n_rows, dgesdd_ilp64, threads, h_hset + 9 * (size_t)nset);
         if (r != RWH_OK) return r;
         if (hipMemcpyAsync(d_hset + 9 * (size_t)nset, h_hset + 9 * (size_t)nset, 36 * (size_t)n_rows, hipMemcpyHostToDevice, s) != hipSuccess) return RWH_E_LAUNCH;
@@ -187,10 +188,6 @@ extern "C" int rwh_ransac_run(const float* pts_a, const float* pts_b, int m, con
         if (hipMemcpyAsync(h_cntset + nset, d_cntset + nset, 4 * (size_t)n_rows, hipMemcpyDeviceToHost, s) != hipSuccess) return RWH_E_LAUNCH;
         return RWH_OK;
     };
-    auto absorb = [&](int n_rows) {             // after the stream has been synchronised
-        for (int j = 0; j < n_rows; ++j) { pos[(size_t)h_rows[j]] = nset + j; cnt[(size_t)h_rows[j]] = h_cntset[nset + j]; }
-        nset += n_rows;
-    };
 
     // ---- while the GPU searches: the samples the host already knows K1 will flag (a repeated index) -----------------------
     int n_rep = 0;
@@ -199,148 +196,51 @@ extern "C" int rwh_ransac_run(const float* pts_a, const float* pts_b, int m, con
         if ((q[0] == q[1]) | (q[0] == q[2]) | (q[0] == q[3]) | (q[1] == q[2]) | (q[1] == q[3]) | (q[2] == q[3])) h_rows[n_rep++] = i;
     }
     STAMP("vectors + repeated scan");
-    st = settle(n_rep);
+    st = settle(h_rows, n_rep);
     if (st != RWH_OK) { (void)hipStreamSynchronize(s); return st; }
     STAMP("repeated-index SVDs");
     if (hipStreamSynchronize(s) != hipSuccess) return RWH_E_LAUNCH;
     STAMP("sync 1");
     memcpy(cnt.data(), h_counts, 4 * (size_t)k);
-    absorb(n_rep);
+    for (int j = 0; j < n_rep; ++j) { pos[(size_t)h_rows[j]] = nset + j; cnt[(size_t)h_rows[j]] = h_cntset[nset + j]; }
+    nset += n_rep;
     int n_flagged = 0;
     for (int i = 0; i < k; ++i) n_flagged += h_flags[i] != 0;
 
     STAMP("counts copy + flag count");
-    // ---- 'fwd': count intervals for the candidates (see the comment above the function) ------------------------------------
+    // ---- 'fwd': count intervals for the candidates, then the settle rounds and the accept rules (rwh_settle.h) --------------
     double cscale = 1.0;
-    for (long long i = 0; i < 2ll * m; ++i) { const double v = pts_a[i] < 0 ? -(double)pts_a[i] : (double)pts_a[i]; if (v > cscale) cscale = v; }
-    const bool use_iv = loss == RWH_LOSS_FWD && cscale < 1e30;            // (an Inf / NaN coordinate: the margin rule)
-    const unsigned always_bits = use_iv ? (RWH_HYP_REPEATED | RWH_HYP_SINGULAR | RWH_HYP_DEGENERATE) : 0xFFu;
-    int n_iv = 0;
-    if (use_iv) {
-        lo.resize((size_t)k); hi.resize((size_t)k);
-        memcpy(lo.data(), cnt.data(), 4 * (size_t)k);                      // not a candidate: its count is taken as it is
-        memcpy(hi.data(), cnt.data(), 4 * (size_t)k);
-        int best0 = 0;
-        for (int i = 0; i < k; ++i) {
-            const int c = (h_flags[i] & always_bits) ? 0 : cnt[(size_t)i];
-            best0 = c > best0 ? c : best0;
-        }
-        const int near_lim = (best0 < need ? best0 : need) - IV_NEAR;      // cnt >= best0 - NEAR or cnt >= need - NEAR
-        for (int i = 0; i < k; ++i) {
-            const unsigned f = h_flags[i];
-            if (!(f & always_bits) && ((f & RWH_HYP_ILLCOND) || cnt[(size_t)i] >= near_lim) && pos[(size_t)i] < 0) h_rows[n_iv++] = i;
-        }
-        STAMP("lo/hi init + candidates");
-        if (n_iv) {
-            if (hipMemcpyAsync(d_rows, h_rows, 4 * (size_t)n_iv, hipMemcpyHostToDevice, s) != hipSuccess) return RWH_E_LAUNCH;
-            st = rwh_score_interval(d_H, d_rows, n_iv, d_flags, d_pa, d_pb, m, th, cscale, IV_DELTA0, IV_DELTA1, d_lo, d_hi, s);
-            if (st != RWH_OK) { (void)hipStreamSynchronize(s); return st; }
-            if (hipMemcpyAsync(h_lo, d_lo, 4 * (size_t)n_iv, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(h_hi, d_hi, 4 * (size_t)n_iv, hipMemcpyDeviceToHost, s) != hipSuccess) return RWH_E_LAUNCH;
-            if (hipStreamSynchronize(s) != hipSuccess) return RWH_E_LAUNCH;
-            std::vector<int32_t> rows_iv(h_rows, h_rows + n_iv);          // (h_rows is reused by the rounds below)
-            for (int j = 0; j < n_iv; ++j) { lo[(size_t)rows_iv[(size_t)j]] = h_lo[j]; hi[(size_t)rows_iv[(size_t)j]] = h_hi[j]; }
-        }
+    for (long long i = 0; i < 2ll * m; ++i) {
+        const double v = pts_a[i] < 0 ? -(double)pts_a[i] : (double)pts_a[i];
+        if (v != v) { cscale = v; break; }                                 // a NaN coordinate
+        if (v > cscale) cscale = v;
     }
-
-    STAMP("interval kernel round trip");
-    // ---- rounds: settle every hypothesis that can take part in the decision (ransac._settle_on_host, same rules) ----------
-    int end = k;
-    if (use_iv) {
-        // The same rules as the general loop below, without three passes over all k hypotheses per round.  Only a hypothesis that is
-        // not settled and either carries an always-bit or has an open interval (lo < hi) can ever be taken: the ACTIVE list, a few
-        // thousand of 100 000.  Every other one is fixed for the whole call: v[] = what it contributes to the running best (lo; 0 for
-        // an unsettled always-bit sample; the settled count once settled -- kept in lo[]), `fs` = the first hypothesis that
-        // certainly exits.
-        act.clear();
-        int fs = k;
-        for (int i = k - 1; i >= 0; --i) {
-            const bool settled = pos[(size_t)i] >= 0, always = (h_flags[i] & always_bits) != 0;
-            int v;
-            if (settled) v = cnt[(size_t)i];
-            else if (always) v = 0;
-            else v = lo[(size_t)i];
-            if ((settled || !always) && v >= need) fs = i;
-            if (!settled && (always || lo[(size_t)i] < hi[(size_t)i])) act.push_back(i);
-            lo[(size_t)i] = v;                                  // from here on lo[] is v[]
-        }
-        std::reverse(act.begin(), act.end());                   // ascending, like the general loop's h_rows
-        for (;;) {
-            end = fs < k ? fs + 1 : k;
-            int best = 0;
-            for (int i = 0; i < end; ++i) best = lo[(size_t)i] > best ? lo[(size_t)i] : best;
-            int n_rows = 0;
-            size_t keep = 0;
-            for (size_t a = 0; a < act.size(); ++a) {
-                const int i = act[a];
-                const bool take = i < end && ((h_flags[i] & always_bits) || hi[(size_t)i] >= best || hi[(size_t)i] >= need);
-                if (take) h_rows[n_rows++] = i; else act[keep++] = i;
-            }
-            act.resize(keep);
-            STAMP("round scans");
-            if (n_rows == 0) break;
-            ++rounds;
-            st = settle(n_rows);
-            if (st != RWH_OK) { (void)hipStreamSynchronize(s); return st; }
-            if (hipStreamSynchronize(s) != hipSuccess) return RWH_E_LAUNCH;
-            const int first_new = nset;
-            absorb(n_rows);
-            for (int j = 0; j < n_rows; ++j) {
-                const int i = h_rows[j], c = h_cntset[first_new + j];
-                lo[(size_t)i] = c;
-                if (c >= need && i < fs) fs = i;
-            }
-            STAMP("round settle + sync");
-        }
-    } else
-    for (;;) {
-        end = k;
-        const int m_need = margin_of(need, margin_cap);
-        for (int i = 0; i < k; ++i) {
-            bool sure;
-            if (pos[(size_t)i] >= 0) sure = cnt[(size_t)i] >= need;
-            else if (use_iv) sure = !(h_flags[i] & always_bits) && lo[(size_t)i] >= need;
-            else sure = h_flags[i] == 0 && cnt[(size_t)i] >= need + m_need;
-            if (sure) { end = i + 1; break; }
-        }
-        int best = 0;                                       // a lower bound of the best count the reference sees in the prefix
-        for (int i = 0; i < end; ++i) {
-            int v = 0;
-            if (pos[(size_t)i] >= 0) v = cnt[(size_t)i];
-            else if (use_iv) v = (h_flags[i] & always_bits) ? 0 : lo[(size_t)i];
-            else v = h_flags[i] == 0 ? cnt[(size_t)i] : 0;
-            if (v > best) best = v;
-        }
-        const int m_best = margin_of(best, margin_cap);
-        int n_rows = 0;
-        for (int i = 0; i < end; ++i) {
-            if (pos[(size_t)i] >= 0) continue;
-            bool take;
-            if (use_iv) take = (h_flags[i] & always_bits) || (lo[(size_t)i] < hi[(size_t)i] && (hi[(size_t)i] >= best || hi[(size_t)i] >= need));
-            else take = h_flags[i] != 0 || cnt[(size_t)i] >= best - m_best || cnt[(size_t)i] >= need - m_need;
-            if (take) h_rows[n_rows++] = i;
-        }
-        STAMP("round scans");
-        if (n_rows == 0) break;
-        ++rounds;
-        st = settle(n_rows);
-        if (st != RWH_OK) { (void)hipStreamSynchronize(s); return st; }
+    const bool use_iv = loss == RWH_LOSS_FWD && cscale < 1e30;            // (an Inf / NaN coordinate: the margin rule; NaN < 1e30 is false)
+    auto interval = [&](const int32_t* rows, int n_iv, int32_t* lo, int32_t* hi) -> int {
+        if (hipMemcpyAsync(d_rows, rows, 4 * (size_t)n_iv, hipMemcpyHostToDevice, s) != hipSuccess) return RWH_E_LAUNCH;
+        const int r = rwh_score_interval(d_H, d_rows, n_iv, d_flags, d_pa, d_pb, m, th, cscale, IV_DELTA0, IV_DELTA1, d_lo, d_hi, s);
+        if (r != RWH_OK) { (void)hipStreamSynchronize(s); return r; }
+        if (hipMemcpyAsync(h_lo, d_lo, 4 * (size_t)n_iv, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(h_hi, d_hi, 4 * (size_t)n_iv, hipMemcpyDeviceToHost, s) != hipSuccess) return RWH_E_LAUNCH;
         if (hipStreamSynchronize(s) != hipSuccess) return RWH_E_LAUNCH;
-        absorb(n_rows);
+        for (int j = 0; j < n_iv; ++j) { lo[(size_t)rows[j]] = h_lo[j]; hi[(size_t)rows[j]] = h_hi[j]; }
+        STAMP("interval kernel round trip");
+        return RWH_OK;
+    };
+    auto settle_round = [&](const int32_t* rows, int n_rows, int32_t* counts) -> int {
+        const int r = settle(rows, n_rows);
+        if (r != RWH_OK) { (void)hipStreamSynchronize(s); return r; }
+        if (hipStreamSynchronize(s) != hipSuccess) return RWH_E_LAUNCH;
+        for (int j = 0; j < n_rows; ++j) counts[(size_t)rows[j]] = h_cntset[nset + j];
         STAMP("round settle + sync");
-    }
-
-    // ---- the accept rules (ransac.py:186-202) over the prefix the reference looks at ------------------------------------
-    int winner = -1, early = 0;
-    for (int i = 0; i < end; ++i)
-        if (cnt[(size_t)i] >= need) { winner = i; early = 1; break; }
-    if (winner < 0) {
-        int bestc = 0;
-        for (int i = 0; i < end; ++i)
-            if (cnt[(size_t)i] > bestc) { bestc = cnt[(size_t)i]; winner = i; }       // strict >: the first index of the maximum
-    }
-    out[0] = winner; out[1] = early; out[2] = winner >= 0 ? cnt[(size_t)winner] : 0; out[3] = nset; out[4] = rounds; out[5] = n_flagged;
-    out[6] = n_iv;
+        return RWH_OK;
+    };
+    rwh_settle::Outcome dec;
+    st = rwh_settle::decide(k, h_flags, need, use_iv, margin_cap, h_rows, sst, interval, settle_round, dec);
+    if (st != RWH_OK) return st;
+    const int winner = dec.winner, early = dec.early;
+    out[0] = winner; out[1] = early; out[2] = dec.count; out[3] = nset; out[4] = dec.rounds; out[5] = n_flagged;
+    out[6] = dec.n_iv;
     if (out_keys && winner >= 0) {
         // this slice's packed keys, as K2b packs them (the payload of the one all-reduce of a sharded search): word 0 = count and
         // inverted GLOBAL index of the slice's winner, word 1 = inverted global index of its first hypothesis that reaches `need`

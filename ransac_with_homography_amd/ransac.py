@@ -271,13 +271,16 @@ def _settle_on_host(pa_dev, pb_dev, pa, pb, idx_host, counts, flags, need, th, m
         st.add(rows, H, msk)
     with np.errstate(invalid="ignore"):
         cscale = float(max(1.0, np.abs(pa).max())) if pa.size else 1.0
+        if pa.size and np.isnan(pa).any():
+            cscale = float("nan")                          # a NaN coordinate: the margin rule, like an Inf one (NaN < 1e30 is false)
     use_iv = method == "fwd" and H_dev is not None and cscale < 1e30
     n_iv = 0
     if use_iv:
         always = (flags & (_lib.RWH_HYP_REPEATED | _lib.RWH_HYP_SINGULAR | _lib.RWH_HYP_DEGENERATE)) != 0
         lo, hi = counts.copy(), counts.copy()              # not a candidate: its count is taken as it is
         free = ~always
-        best0 = int(counts[free].max()) if free.any() else 0
+        unflagged = flags == 0                            # an RWH_HYP_ILLCOND raw count places nothing: a lower best0 only widens
+        best0 = int(counts[unflagged].max()) if unflagged.any() else 0
         cand0 = np.flatnonzero(~st.done & free & (((flags & _lib.RWH_HYP_ILLCOND) != 0) | (counts >= best0 - IV_NEAR) | (counts >= need - IV_NEAR)))
         if cand0.size:
             if flags_dev is None:

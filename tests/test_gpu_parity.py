@@ -2338,3 +2338,203 @@ def test_native_and_python_run_drivers_agree(gpu, matches):
             finally:
                 rmod.FORCE_PYTHON_DRIVER = False
         assert res[0] == res[1], (seed, th, d, n, k, m, res[0][:7] if not isinstance(res[0], str) else res[0], res[1][:7] if not isinstance(res[1], str) else res[1])
+
+
+# ---- K2i soundness: [lo, hi] against the reference's float32 arithmetic at sampled points of the perturbation box --------------
+def _k2i_box(h, illcond, C, delta0, delta1):
+    """The perturbation box of rwh_score_interval (include/rwh.h), plainly in float64: entry i may move by delta x max(|h_i|, its
+    natural scale) -- s, s, s C / s, s, s C / s / C, s / C, s, with s the largest scale-free entry and C = coord_scale."""
+    a = np.abs(np.asarray(h, np.float64))
+    s = max(a[0], a[1], a[3], a[4], a[8], max(a[2], a[5]) / C, max(a[6], a[7]) * C)
+    nat = np.array([s, s, s * C, s, s, s * C, s / C, s / C, s])
+    return (delta1 if illcond else delta0) * np.maximum(a, nat)
+
+
+def _box_points(h, D, rng, n_interior=200):
+    """float32 points of the box around h (float32 [9]): the 3^6 combinations of {-1, 0, +1} in the affine entries h0..h5, each with
+    the two extreme points of the projective entries h6, h7, h8 (all low, all high), and n_interior random interior points; every
+    point rounded to float32 and kept inside the box (one step back toward h where rounding left it)."""
+    import itertools
+    aff = np.array(list(itertools.product((-1.0, 0.0, 1.0), repeat=6)))
+    S = np.concatenate([np.c_[np.repeat(aff, 2, axis=0), np.tile([[-1.0] * 3, [1.0] * 3], (len(aff), 1))],
+                        rng.uniform(-1, 1, (n_interior, 9))])
+    h32 = np.asarray(h, np.float32)
+    P = (h32.astype(np.float64) + S * D).astype(np.float32)
+    out = np.abs(P.astype(np.float64) - h32) > D
+    P = np.where(out, np.nextafter(P, np.broadcast_to(h32, P.shape)), P)
+    assert (np.abs(P.astype(np.float64) - h32) <= D).all()
+    return P
+
+
+def _inliers_over_box(h, D, X, Y, th, rng):
+    """[n_points, M] bool: the reference's inlier test (oracle.compute_loss 'fwd' < th, float32 as the reference computes it) at
+    every sampled point of the box."""
+    from oracle import rwh_oracle as orc
+    with np.errstate(all="ignore"):
+        return np.stack([orc.compute_loss(p.reshape(3, 3), X, Y, "fwd") < th for p in _box_points(h, D, rng)])
+
+
+def _k2i_edge_problems(rng, th):
+    """Problems built round one H each, with adversarial pairs: targets placed at th +- 1e-5 .. 3e-4 px from the float64 projection of
+    a source point (then rounded to float32), at the places the margin formula could be too tight.  -> [(name, A, B, H, adversarial
+    pair indices)]."""
+    eps = np.array([1e-5, 3e-5, 1e-4, 3e-4])
+    eps = np.concatenate([-eps, eps])
+    out = []
+    for name in ("cancel_1e4", "cancel_1e5", "horizon", "below2"):
+        if name.startswith("cancel"):       # h0 x + h1 y + h2 ~ 0 with terms of 1e4 / 1e5: cancellation in the numerators
+            c0 = 5e4 if name == "cancel_1e4" else 5e5
+            x0, y0 = c0 * 0.3, c0 * 0.2
+            H = np.array([[1.0, 0.5, -(x0 + 0.5 * y0)], [0.3, 1.0, -(0.3 * x0 + y0)], [1e-8, 2e-8, 1.0]])
+            A = np.c_[rng.uniform(x0 - c0 * 0.2, x0 + c0 * 0.2, 160), rng.uniform(y0 - c0 * 0.2, y0 + c0 * 0.2, 160)]
+            src = np.c_[x0 + rng.uniform(-50, 50, 12), y0 + rng.uniform(-50, 50, 12)]
+        elif name == "horizon":             # 1 + h6 x near 0: the denominator close to the horizon line x = 1052.6
+            H = np.array([[1.0, 0.02, 3.0], [0.01, 1.0, -2.0], [-9.5e-4, 0.0, 1.0]])
+            A = np.c_[rng.uniform(0, 1000, 160), rng.uniform(0, 1000, 160)]
+            src = np.c_[rng.uniform(1040, 1051, 12), rng.uniform(0, 1000, 12)]
+        else:                               # every coordinate below 2: coord_scale is clamped to 1
+            H = np.array([[0.9, 0.05, 0.1], [-0.03, 1.1, 0.05], [0.02, -0.01, 1.0]])
+            A = rng.uniform(0, 1.99, (160, 2))
+            src = rng.uniform(0, 1.99, (12, 2))
+        H32 = H.astype(np.float32).reshape(9)
+        Hq = H32.astype(np.float64).reshape(3, 3)
+
+        def proj(P):
+            q = np.c_[P, np.ones(len(P))] @ Hq.T
+            return q[:, :2] / q[:, 2:3]
+        B = proj(A) + rng.normal(0, 0.6 * th, (len(A), 2))
+        phi = rng.uniform(0, 2 * np.pi, (len(src), len(eps)))
+        tgt = proj(src)[:, None, :] + (th + eps)[None, :, None] * np.stack([np.cos(phi), np.sin(phi)], -1)
+        A = np.concatenate([A, np.repeat(src, len(eps), axis=0)]).astype(np.float32)
+        B = np.concatenate([B, tgt.reshape(-1, 2)]).astype(np.float32)
+        out.append((name, A, B, H32, np.arange(160, len(A))))
+    return out
+
+
+def test_score_interval_sound_over_the_box(gpu, matches):
+    """K2i's claim as stated (include/rwh.h, rwh_score_interval): lo counts the pairs that are inliers for EVERY H within the
+    perturbation box, hi those that are inliers for SOME.  Checked against the reference's own float32 arithmetic (the oracle's
+    compute_loss) at sampled points of the box -- the 729 affine corners x 2 projective extremes and 200 interior points, in float32,
+    inside the box -- for unflagged (delta0) and RWH_HYP_ILLCOND (delta1) rows.
+      * count level, one launch per problem: lo <= count(H') <= hi on dense-cloud, two-cluster, lattice and matchespoints problems
+        (K1's hypotheses nearest the top, the ill-conditioned ones, a few at random) and on the adversarial problems;
+      * pair level, one launch with m = 1 per adversarial pair (the full problem's coord_scale): a pair counted in lo is an inlier
+        at every sampled H', a pair excluded by hi an outlier at every one.  Adversarial pairs sit at th +- 1e-5 .. 3e-4 px where
+        h0 x + h1 y + h2 cancels at coordinates of 1e4 / 1e5, next to the horizon, and with every coordinate below 2."""
+    from ransac_with_homography_amd import _lib, kernels
+    from ransac_with_homography_amd import ransac as rmod
+    rng = np.random.default_rng(31)
+    d0, d1, th = rmod.IV_DELTA0, rmod.IV_DELTA1, 5.0
+    ILL = _lib.RWH_HYP_ILLCOND
+    always_bits = _lib.RWH_HYP_REPEATED | _lib.RWH_HYP_SINGULAR | _lib.RWH_HYP_DEGENERATE
+    HS = np.array([[1.02, 0.01, 5.0], [0.015, 0.98, 7.0], [1e-5, 2e-5, 1.0]])
+
+    def real_problem(kind):
+        if kind == "matches":
+            return matches
+        M = {"cloud": 1400, "two": 2000, "lattice": 600}[kind]
+        if kind == "cloud": G = rng.normal(500, 3, (M, 2))
+        elif kind == "two": G = np.array([[400., 450.], [620., 560.]])[rng.integers(0, 2, M)] + rng.normal(0, 5, (M, 2))
+        else: G = np.stack([rng.integers(0, 12, M) * 37.0, rng.integers(0, 9, M) * 53.0], 1)
+        P = np.c_[G, np.ones(M)] @ HS.T
+        B = P[:, :2] / P[:, 2:3] + rng.normal(0, 1.0, (M, 2))
+        o = rng.random(M) < 0.3
+        B[o] = rng.uniform(B.min(), B.max(), (int(o.sum()), 2))
+        return G.astype(np.float32), B.astype(np.float32)
+
+    checked = {"count": 0, "pair_lo": 0, "pair_hi": 0, "ill": 0}
+    for kind in ("cloud", "two", "lattice", "matches"):
+        A, B = real_problem(kind)
+        X, Y = A.T, B.T
+        K = 2000
+        idx = rng.integers(0, A.shape[0], (K, 4)).astype(np.int32)
+        pa, pb = torch.from_numpy(A).to(gpu), torch.from_numpy(B).to(gpu)
+        ws = kernels.SearchWorkspace(K, A.shape[0], gpu)
+        kernels.ransac_search(pa, pb, torch.from_numpy(idx).to(gpu), th, "fwd", 1 << 30, ws)
+        flags, counts, Hk = ws.flags.cpu().numpy(), ws.counts.cpu().numpy(), ws.H.cpu().numpy()
+        free = np.flatnonzero((flags & always_bits) == 0)
+        top = free[np.argsort(-counts[free], kind="stable")[:14]]
+        ill = free[(flags[free] & ILL) != 0][:10]
+        rows = np.unique(np.concatenate([top, ill, rng.choice(free, 4, replace=False)]))
+        C = max(1.0, float(np.abs(A).max()))
+        lo, hi = kernels.score_interval(ws.H, rows, ws.flags, pa, pb, th, C, d0, d1)
+        for j, r in enumerate(rows):
+            D = _k2i_box(Hk[r], flags[r] & ILL, C, d0, d1)
+            c = _inliers_over_box(Hk[r], D, X, Y, th, rng).sum(axis=1)
+            assert lo[j] <= c.min() and c.max() <= hi[j], (kind, int(r), int(flags[r]), int(lo[j]), int(hi[j]), int(c.min()), int(c.max()))
+            checked["count"] += 1
+            checked["ill"] += bool(flags[r] & ILL)
+
+    for name, A, B, H32, adv in _k2i_edge_problems(rng, th):
+        X, Y = A.T, B.T
+        C = max(1.0, float(np.abs(A).max()))
+        Hs = np.stack([H32, H32, np.nextafter(H32, np.float32(np.inf)), np.nextafter(H32, np.float32(-np.inf))])
+        fl = np.array([0, ILL, 0, ILL], np.uint8)
+        H_dev, fl_dev = torch.from_numpy(Hs).to(gpu), torch.from_numpy(fl).to(gpu)
+        rows = np.arange(len(Hs))
+        pa, pb = torch.from_numpy(A).to(gpu), torch.from_numpy(B).to(gpu)
+        lo, hi = kernels.score_interval(H_dev, rows, fl_dev, pa, pb, th, C, d0, d1)
+        box = [_inliers_over_box(Hs[r], _k2i_box(Hs[r], fl[r], C, d0, d1), X, Y, th, rng) for r in rows]
+        for r in rows:
+            c = box[r].sum(axis=1)
+            assert lo[r] <= c.min() and c.max() <= hi[r], (name, int(r), int(lo[r]), int(hi[r]), int(c.min()), int(c.max()))
+            checked["count"] += 1
+        for p in adv:
+            plo, phi = kernels.score_interval(H_dev, rows, fl_dev, pa[p:p + 1], pb[p:p + 1], th, C, d0, d1)
+            for r in rows:
+                if plo[r]:
+                    assert box[r][:, p].all(), (name, int(r), int(p), "counted in lo, an outlier at some H' of the box")
+                    checked["pair_lo"] += 1
+                if not phi[r]:
+                    assert not box[r][:, p].any(), (name, int(r), int(p), "excluded by hi, an inlier at some H' of the box")
+                    checked["pair_hi"] += 1
+    print("K2i soundness:", checked)
+    assert checked["ill"] > 0 and checked["pair_lo"] > 0 and checked["pair_hi"] > 0, checked
+
+
+def test_ransac_run_nan_coordinate_vs_oracle(gpu):
+    """A NaN source coordinate: the settle step takes the margin rule under 'fwd' (the interval kernel's coordinate scale cannot be
+    formed; both drivers test for the NaN explicitly).  RANSAC.run against the oracle's loop on a dense cloud with one NaN
+    coordinate: the same winner, count, inlier list and generator position -- or, where a sample holding the NaN point comes before
+    any early exit, the same LinAlgError."""
+    import ransac as rs
+    from oracle import rwh_oracle as orc
+    from ransac_with_homography_amd import ransac as rmod
+    rng = np.random.default_rng(43)
+    HS = np.array([[1.02, 0.01, 5.0], [0.015, 0.98, 7.0], [1e-5, 2e-5, 1.0]])
+    M = 1400
+    G = rng.normal(500, 3, (M, 2))
+    P = np.c_[G, np.ones(M)] @ HS.T
+    B = P[:, :2] / P[:, 2:3] + rng.normal(0, 1.0, (M, 2))
+    o = rng.random(M) < 0.3
+    B[o] = rng.uniform(B.min(), B.max(), (int(o.sum()), 2))
+    A, B = G.astype(np.float32), B.astype(np.float32)
+    A[777, 0] = np.nan
+    completed = 0
+    for d, k in ((95, 300), (5000, 60)):
+        for seed in (1, 2, 3):
+            for force in (False, True):
+                np.random.seed(seed)
+                try:
+                    with np.errstate(all="ignore"):
+                        Ho, inlo, cnto, ito = orc.ransac_run(A.T, B.T, th=5, d=d, n=4, k=k, method="fwd")
+                    ref = (int(cnto), int(ito), inlo[0].tolist())
+                except np.linalg.LinAlgError:
+                    ref = "LinAlgError"
+                nxt_o = np.random.randint(0, 1 << 30)
+                np.random.seed(seed)
+                rmod.FORCE_PYTHON_DRIVER = force
+                try:
+                    r = rs.RANSAC(rs.HomoModel(th=5, d=d, n=4), k=k)
+                    with np.errstate(all="ignore"):
+                        Hg, inlg, cntg = r.run([A.T, B.T], method="fwd")
+                    got = (int(cntg), int(r.last_run["winner"]), inlg[0].tolist())
+                except np.linalg.LinAlgError:
+                    got = "LinAlgError"
+                finally:
+                    rmod.FORCE_PYTHON_DRIVER = False
+                assert got == ref and np.random.randint(0, 1 << 30) == nxt_o, (d, k, seed, force, str(got)[:80], str(ref)[:80])
+                if ref != "LinAlgError":
+                    completed += 1
+                    assert r.last_run["intervals"] == 0, r.last_run      # the margin rule: no interval was asked for
+    assert completed >= 4, completed

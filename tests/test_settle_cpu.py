@@ -273,3 +273,51 @@ def test_native_legacy_randint_is_numpys_stream():
     nxt = np.random.randint(0, 99)
     np.random.set_state(st)
     assert none64 is None and np.array_equal(a32, np.random.randint(0, 185, (5000, 4))) and nxt == np.random.randint(0, 99)
+
+
+def test_interval_window_ignores_illcond_raw_counts(oracle_scorer, monkeypatch):
+    """The candidate window of the 'fwd' interval rule is placed by the best raw count of an UNFLAGGED hypothesis only.  An
+    RWH_HYP_ILLCOND raw count says nothing about the reference's count (the flag exists for exactly that disagreement): when it
+    placed the window (best0 over every row without an always-bit), one ill-conditioned row far above the rest pushed the near-best
+    unflagged rows out of it, they kept their raw K1 counts, and the row the reference ranks second won.  Real K1 / reference data
+    (K1 emulated, intervals emulated, the oracle as scorer): rows 25 (K1 64, reference 65) and 82 (65 / 65), 40 low unflagged rows
+    whose counts agree, and one low unflagged row re-flagged ill-conditioned with K1 count 209 and the reference H of row 25.
+    The reference's winner is 25 (the first of the two 65s); the old window returned 82."""
+    import bench
+    import interval_emulation as ive
+    from k1_emulation import RWH_HYP_ILLCOND, dlt4
+    monkeypatch.setattr(kernels, "score_interval", lambda H, rows, flags, pa, pb, th, c, d0, d1: ive.score_interval(
+        H.numpy(), rows, None if flags is None else flags.numpy(), pa.numpy(), pb.numpy(), th, c, d0, d1))
+    rng = np.random.default_rng(7000)
+    M = int(rng.integers(150, 400))
+    G = rng.normal(500, 3, (M, 2))
+    P = np.c_[G, np.ones(M)] @ bench.H_S.T
+    B = P[:, :2] / P[:, 2:3] + rng.normal(0, 1, (M, 2))
+    o = rng.random(M) < 0.35
+    B[o] = rng.uniform(B.min(), B.max(), (o.sum(), 2))
+    A, B = G.astype(np.float32), B.astype(np.float32)
+    idx = rng.integers(0, M, (1500, 4)).astype(np.int32)
+    th, X, Y = 3.0, A.T, B.T
+    H, flags = dlt4(A, B, idx)
+    Href = impl.svd_hypotheses(A, B, idx)
+
+    def count(h):
+        with np.errstate(all="ignore"):
+            return int((orc.compute_loss(h.reshape(3, 3), X, Y, "fwd") < th).sum()) if np.isfinite(h).all() else 0
+    dev = np.array([count(h) for h in H])
+    ref = np.array([count(h) for h in Href])
+    assert M == 339 and (dev[25], ref[25], dev[82], ref[82]) == (64, 65, 65, 65) and flags[25] == flags[82] == 0
+    unflagged = np.flatnonzero(flags == 0)
+    low = [int(i) for i in unflagged if dev[i] == ref[i] < 20][:40]
+    fab = [int(i) for i in unflagged if ref[i] < 20 and int(i) not in low][0]
+    rows = sorted([25, 82] + low + [fab])
+    t_H, t_flags, t_cnt = H[rows].copy(), flags[rows].copy(), dev[rows].astype(np.int32)
+    j = rows.index(fab)
+    t_flags[j], t_H[j], t_cnt[j] = RWH_HYP_ILLCOND, Href[25], 209
+    Ad, Bd = torch.from_numpy(A), torch.from_numpy(B)
+    w, early, cnt, words, _, _ = impl._settle_on_host(Ad, Bd, A, B, idx[rows], t_cnt, t_flags, 10 ** 6, th, "fwd", impl.RESCORE_MARGIN, {},
+                                                      H_dev=torch.from_numpy(t_H), flags_dev=torch.from_numpy(t_flags))
+    assert (rows[w], early, cnt) == (25, False, 65), (rows[w], early, cnt)
+    inl = np.flatnonzero(np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:M]) if words is not None else \
+        np.flatnonzero(orc.compute_loss(H[25].reshape(3, 3), X, Y, "fwd") < th)
+    assert np.array_equal(inl, np.flatnonzero(orc.compute_loss(Href[25].reshape(3, 3), X, Y, "fwd") < th))
