@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define RWH_ABI_VERSION 3   /* 3 (round 4): rwh_ransac_run takes hyp_base and returns packed keys, RWH_HYP_DEGENERATE, rwh_score_interval;
+#define RWH_ABI_VERSION 4   /* 4: rwh_stitch_panorama_ex and the element types after RWH_F64 (additive);
+                               3 (round 4): rwh_ransac_run takes hyp_base and returns packed keys, RWH_HYP_DEGENERATE, rwh_score_interval;
                                2: blend modes of rwh_stitch_panorama, RWH_BATCH_EARLY_STOP (d_counts may hold -1), rwh_lab_clock_probe, RWH_HYP_ILLCOND */
 #define RWH_API __attribute__((visibility("default")))
 
@@ -33,8 +34,9 @@ enum {
     RWH_E_LAUNCH = -3        /* HIP reported a launch / memset failure */
 };
 
-/* element types of image planes */
-enum { RWH_U8 = 0, RWH_F32 = 1, RWH_F64 = 2 };
+/* element types of image planes (the codes after RWH_F64 are taken by rwh_stitch_panorama_ex only; a bool plane is RWH_U8) */
+enum { RWH_U8 = 0, RWH_F32 = 1, RWH_F64 = 2, RWH_I8 = 3, RWH_U16 = 4, RWH_I16 = 5, RWH_I32 = 6, RWH_I64 = 7, RWH_U32 = 8,
+       RWH_U64 = 9, RWH_F16 = 10 };
 /* interpolators: reference homography.py:140 `convertfunc` keys */
 enum { RWH_NEAREST = 0, RWH_BILINEAR = 1 };
 /* RANSAC loss: reference ransac.py:84-98 `computeLoss` method */
@@ -414,6 +416,33 @@ RWH_API int rwh_stitch_panorama_rows(const void* d_img_t, int t_h, int t_w, cons
                              const double* inv_h, int grid_x0, int grid_y0, int warp_w, int warp_h,
                              int tsx, int tsy, int qsx, int qsy, int canvas_h, int canvas_w,
                              int blend, double rate, void* d_canvas, int row_begin, int row_end, unsigned flags, void* stream);
+
+/*
+ * The exact compositor on images of any numeric element type: stitchPanorama (homography.py:288-338) where imgT / imgQ are not
+ * uint8 RGB.  d_img_t: t_h x t_w x t_c elements of t_dtype (t_c 3 or 4); d_img_q: q_h x q_w x q_c elements of q_dtype (q_c 1, 3
+ * or 4); dtypes: any RWH_U8 .. RWH_F16 code, both read in their own type.  Geometry, blend and rate as rwh_stitch_panorama;
+ * canvas rows [row_begin, row_end) of a canvas_h x canvas_w x canvas_c uint8 canvas (d_canvas points at row 0).
+ * The reference's numpy conversions, operation by operation, canvas bit-identical to the reference's:
+ *   paste (blend 0): canvas_c == t_c; the texels are lerped in float64 (every integer promoted to float64), the warp is cast to
+ *     uint8 (truncation toward zero, low byte of the int32; 0 where that does not fit int32: NaN, +-inf, |v| >= 2^31); imgQ is
+ *     assigned over it, integers by their low byte, floats by the same cast; q_c == t_c, or 1 (broadcast);
+ *   blend (1..3): canvas_c == 3; addAlpha's float32 copy of imgT (integers rounded to nearest, int64 directly) is warped in
+ *     float64, imgQ's channels 0..2 enter as float32 (q_c 1 broadcasts), the float32 canvas is cast to uint8.  t_c == 3: the
+ *     alpha plane of rwh_stitch_panorama; t_c == 4: the warped channel 3 of imgT is imgT's weight (what the reference's 5-channel
+ *     warp hands its blend), and blend 1 differs from 2 and 3 only in imgQ's alpha.
+ * flags: RWH_WARP_ZERO_ORIGIN only (anything else is RWH_E_INVALID).  Paste: blanks texel (0,0) of imgT in memory, every channel,
+ * as bilinear() does to the caller's array (pass it with the first row tile only); blend: imgT is never written, texel (0,0) is
+ * read with channels 0..2 (t_c 3: and its alpha) at 0 -- the copy addAlpha made is what bilinear() blanks (pass it with every tile).
+ * RWH_E_INVALID: NULL pointer, unknown dtype code, blend outside 0..3, size <= 0, bad row range, another flag;
+ * RWH_E_UNSUPPORTED: t_c, q_c or canvas_c outside the sets above (the reference raises IndexError / ValueError there, or
+ * composites more channels than this entry point takes).  Where the reference's warp indexes past imgT it raises IndexError:
+ * rwh_warp_index_check tells, the canvas is then meaningless (the +1 taps are clamped).
+ */
+RWH_API int rwh_stitch_panorama_ex(const void* d_img_t, int t_h, int t_w, int t_c, int t_dtype,
+                                   const void* d_img_q, int q_h, int q_w, int q_c, int q_dtype,
+                                   const double* inv_h, int grid_x0, int grid_y0, int warp_w, int warp_h,
+                                   int tsx, int tsy, int qsx, int qsy, int canvas_h, int canvas_w, int canvas_c,
+                                   int blend, double rate, void* d_canvas, int row_begin, int row_end, unsigned flags, void* stream);
 
 #ifdef __cplusplus
 }

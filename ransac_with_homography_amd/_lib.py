@@ -10,8 +10,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librwh_hip.so")
 
-ABI_VERSION = 3          # RWH_ABI_VERSION of the include/rwh.h this binding was written against
+ABI_VERSION = 4          # RWH_ABI_VERSION of the include/rwh.h this binding was written against
 RWH_U8, RWH_F32, RWH_F64 = 0, 1, 2
+RWH_I8, RWH_U16, RWH_I16, RWH_I32, RWH_I64, RWH_U32, RWH_U64, RWH_F16 = 3, 4, 5, 6, 7, 8, 9, 10    # rwh_stitch_panorama_ex only
 RWH_NEAREST, RWH_BILINEAR = 0, 1
 RWH_LOSS = {"fwd": 0, "backward": 1, "reproj": 2}
 RWH_WARP_ZERO_ORIGIN = 1
@@ -26,7 +27,7 @@ RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRA
 EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_probe", "rwh_warp_backward", "rwh_warp_plan", "rwh_sample_points", "rwh_dlt4_batched",
            "rwh_score_count", "rwh_project_points", "rwh_project_points_ex", "rwh_ransac_search", "rwh_ransac_batched", "rwh_stitch_panorama",
            "rwh_host_dlt4_svd", "rwh_ransac_run", "rwh_ransac_run_layout", "rwh_warp_index_check", "rwh_score_count_inv", "rwh_host_inv3", "rwh_stitch_panorama_rows",
-           "rwh_host_legacy_randint", "rwh_score_interval")
+           "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex")
 
 
 class RwhUnavailable(RuntimeError):
@@ -82,6 +83,11 @@ def _bind(lib):
     lib.rwh_stitch_panorama_rows.restype = i32
     lib.rwh_stitch_panorama_rows.argtypes = [vp, i32, i32, vp, i32, i32, c.POINTER(f64), i32, i32, i32, i32,
                                              i32, i32, i32, i32, i32, i32, i32, f64, vp, i32, i32, u32, vp]
+    lib.rwh_stitch_panorama_ex.restype = i32
+    lib.rwh_stitch_panorama_ex.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32,    # img_t h w c dtype, img_q h w c dtype
+                                           c.POINTER(f64), i32, i32, i32, i32,               # inv_h, grid x0 y0, warp w h
+                                           i32, i32, i32, i32, i32, i32, i32,                # tsx tsy qsx qsy, canvas h w c
+                                           i32, f64, vp, i32, i32, u32, vp]                  # blend rate canvas row_begin row_end flags stream
     lib.rwh_project_points_ex.restype = i32
     lib.rwh_project_points_ex.argtypes = [vp, vp, i32, i32, vp, vp]
     lib.rwh_project_points.restype = i32

@@ -431,7 +431,9 @@ def _as_uint8_image(img, what):
         if img.dtype == torch.uint8:
             return img
         u = img.to(torch.uint8)
-        if bool((u.to(img.dtype) == img).all()):
+        # (int8 survives the round trip through uint8 for every value: a negative int8 is no uint8 value -- the blend reads it as
+        #  a negative float)
+        if bool((u.to(img.dtype) == img).all()) and not (img.dtype == torch.int8 and bool((img < 0).any())):
             return u
     else:
         a = np.asarray(img)
@@ -439,7 +441,7 @@ def _as_uint8_image(img, what):
             return img
         with np.errstate(invalid="ignore"):
             u = a.astype(np.uint8)
-            if np.array_equal(u.astype(a.dtype), a):
+            if np.array_equal(u.astype(a.dtype), a) and not (a.dtype == np.int8 and (a < 0).any()):
                 return u
     raise NotImplementedError("stitchPanorama: %s is not uint8 and holds values that are not uint8 values; the MI355X compositor takes "
                               "uint8 RGB images (the reference composites such images in numpy, homography.py:296-338)" % what)
@@ -614,17 +616,29 @@ def stitchPanorama(imgQ, imgT, H, method='bilinear', blending=False, blendrate=0
     ONE fused kernel (`rwh_stitch_panorama`): alpha plane, warp, paste / alpha blend per canvas pixel; nothing intermediate (RGBA
     float32 image, float64 warp, float32 canvas) is materialised.  `blending` False / 'Rate' / 'Gradient' / any other truthy value
     (for which the reference's addAlpha leaves the alpha plane at 0: blend mode 3) on uint8 RGB images -- or images of another
-    dtype that hold uint8 values, converted; round 4 removed the host compositor that used to take the rest.  numpy arrays in (or EXACT = True): the reference's float64 arithmetic, canvas bit-identical to the
-    reference's; torch tensors in (or EXACT = False): the staged fast warp kernel with the compositor as its epilogue,
-    canvas within 1 LSB."""
+    dtype that hold uint8 values, converted.  numpy arrays in (or EXACT = True): the reference's float64 arithmetic, canvas
+    bit-identical to the reference's; torch tensors in (or EXACT = False): the staged fast warp kernel with the compositor as its
+    epilogue, canvas within 1 LSB.
+
+    Every other input goes to the any-dtype compositor (`rwh_stitch_panorama_ex`, exact for numpy arrays and tensors alike): images
+    of any numeric dtype (bool, int8 .. int64, uint8 .. uint64, float16 / 32 / 64), imgT with 3 or 4 channels, imgQ with 1, 3 or 4
+    (paste: as many as imgT, or 1); canvas, exceptions (IndexError from the warp before a ValueError from a channel mismatch) and
+    side effects on the caller's imgT as the reference's.  imgT with 1 or 2 channels raises the reference's IndexError.  Images
+    with 5 or more channels and non-numeric dtypes (bfloat16 tensors among them: numpy has no such type) raise
+    NotImplementedError."""
     import torch
     paste = not blending                                     # homography.py:298 / 322: `if blending:`
-    if imgQ.shape[2] != 3 or imgT.shape[2] != 3:
-        raise NotImplementedError("stitchPanorama: 3-channel images (the reference pastes a %d-channel warp into its canvas only when both "
-                                  "images have 3 channels, homography.py:296-338)" % imgT.shape[2])
+    u8 = None
+    if imgQ.shape[2] == 3 and imgT.shape[2] == 3:
+        try:
+            u8 = _as_uint8_image(imgQ, "imgQ"), _as_uint8_image(imgT, "imgT")
+        except NotImplementedError:
+            pass
+    if u8 is None:                # not uint8 RGB (nor uint8 values in 3 channels): the any-dtype compositor
+        return _stitch_any(imgQ, imgT, H, blending, blendrate)
     tens = _is_tensor(imgQ) or _is_tensor(imgT)
     caller_imgT = imgT
-    imgQ, imgT = _as_uint8_image(imgQ, "imgQ"), _as_uint8_image(imgT, "imgT")
+    imgQ, imgT = u8
     if blending == 'Rate':
         print(blendrate + 1e-10)   # addAlpha prints the rate it stores (homography.py:257)
     elif blending == 'Gradient':
@@ -671,6 +685,91 @@ def stitchPanorama(imgQ, imgT, H, method='bilinear', blending=False, blendrate=0
     if not blending:
         _blank_origin(caller_imgT)     # transformImageH -> bilinear blanks the caller's texel (0,0) in the paste path
     res = _xfer.to_host(out)
+    bits = int(flag.item())
+    if bits:
+        kernels.raise_like_reference(bits, (h, w))
+    return res
+
+
+# numpy element types the any-dtype compositor reads (bool as uint8); torch's are kernels.STITCH_DTYPE
+_STITCH_NP = {np.dtype(t): np.dtype(v) for t, v in ((np.bool_, np.uint8), (np.uint8, np.uint8), (np.int8, np.int8), (np.uint16, np.uint16),
+                                                    (np.int16, np.int16), (np.int32, np.int32), (np.uint32, np.uint32), (np.int64, np.int64),
+                                                    (np.uint64, np.uint64), (np.float16, np.float16), (np.float32, np.float32),
+                                                    (np.float64, np.float64))}
+
+
+def _blank_channels(img, k):
+    """Channels 0 .. k-1 of texel (0,0) of the caller's array or tensor set to 0, any dtype (a tensor through its bytes: torch
+    has no fill for every dtype on the device)."""
+    if _is_tensor(img) and img.stride(2) == 1:
+        import torch
+        try:
+            img.view(torch.uint8)[0, 0, :k * img.element_size()] = 0
+            return
+        except RuntimeError:
+            pass
+    for c in range(k):
+        img[0, 0, c] = 0
+
+
+def _stitch_any(imgQ, imgT, H, blending, blendrate):
+    """stitchPanorama on what the uint8 compositor does not take (homography.py:288-338): any numeric dtype, imgT with 3 or 4
+    channels, imgQ with 1, 3 or 4.  The reference's sequence: addAlpha (a float32 copy; blend only), the bounds, the blanking of
+    texel (0,0) by bilinear() (on the caller's imgT in paste: IndexError there with fewer than 3 channels), the warp (IndexError
+    where it indexes past imgT), the canvas (ValueError where imgQ does not broadcast into it)."""
+    import torch
+    for img, what in ((imgT, "imgT"), (imgQ, "imgQ")):
+        known = img.dtype in kernels.STITCH_DTYPE if _is_tensor(img) else np.asarray(img).dtype in _STITCH_NP
+        if not known or img.shape[2] >= 5:
+            raise NotImplementedError("stitchPanorama: %s (%s, %d channels) is not composited here: the compositor takes numeric images "
+                                      "with 1 to 4 channels (homography.py:288-338)" % (what, img.dtype, img.shape[2]))
+    ct, cq = int(imgT.shape[2]), int(imgQ.shape[2])
+    paste = not blending
+    if blending == 'Rate':
+        print(blendrate + 1e-10)   # addAlpha prints the rate it stores (homography.py:257)
+    elif blending == 'Gradient':
+        print('not implement yet')  # homography.py:266
+    h, w = int(imgT.shape[0]), int(imgT.shape[1])
+    mx, my, wt, ht = _bounds(h, w, H, 0)
+    if wt <= 0 or ht <= 0:
+        raise ValueError("Number of samples, %d, must be non-negative." % min(wt, ht))
+    hq, wq = int(imgQ.shape[0]), int(imgQ.shape[1])
+    (tsx, tsy, tex, tey), (qsx, qsy, qex, qey), (fw, fh) = _stitch_geometry(wt, ht, wq, hq, mx, my)
+    inv_h = np.linalg.inv(np.asarray(H, dtype=np.float64))
+    cw = ct if paste else ct + 1                             # channels bilinear() sees (addAlpha appends one)
+    if cw < 3:                                               # bilinear() blanks channels 0..2: IndexError at channel cw
+        if paste:
+            _blank_channels(imgT, cw)
+        raise IndexError("index %d is out of bounds for axis 2 with size %d" % (cw, cw))
+    if paste:
+        _blank_channels(imgT, ct)                            # the caller's array, as bilinear() (the kernel blanks the device copy)
+    dev = _lib.require_gpu()
+    flag = kernels.warp_index_check((h, w), inv_h, kernels.Grid(mx, mx + wt - 1, wt, my, my + ht - 1, ht), (h, w), "bilinear", dev)
+    # the canvas assignments after the warp: imgQ into the C_T-channel canvas (paste) or imgQ[:, :, :3] into channels 0..2 (blend)
+    q_into = ct if paste else 3
+    q_from = cq if paste else min(cq, 3)
+    if (q_from != q_into and q_from != 1) or cw == 3 and not paste:
+        bits = int(flag.item())
+        if bits:
+            kernels.raise_like_reference(bits, (h, w))
+        if q_from != q_into and q_from != 1:
+            raise ValueError("could not broadcast input array from shape (%d,%d,%d) into shape (%d,%d,%d)" % (hq, wq, q_from, hq, wq, q_into))
+        raise IndexError("index 3 is out of bounds for axis 2 with size 3")      # a 2-channel imgT: the canvas has no alpha channel
+
+    def on_device(img):
+        if _is_tensor(img):
+            t = img.to(dev)
+            return (t.view(torch.uint8) if t.dtype == torch.bool else t).contiguous()
+        a = np.ascontiguousarray(img)
+        return _xfer.to_device(a.view(_STITCH_NP[a.dtype]), dev)
+    t_dev, q_dev = on_device(imgT), on_device(imgQ)
+    mode = 0 if paste else 1 if blending == 'Rate' else 2 if blending == 'Gradient' else 3
+    out = kernels.stitch_panorama_ex(t_dev, q_dev, inv_h, (mx, my), (wt, ht), (tsx, tsy), (qsx, qsy), (fh, fw), mode, blendrate,
+                                     zero_origin=True)
+    if _is_tensor(imgQ) or _is_tensor(imgT):
+        res = out
+    else:
+        res = _xfer.to_host(out)
     bits = int(flag.item())
     if bits:
         kernels.raise_like_reference(bits, (h, w))

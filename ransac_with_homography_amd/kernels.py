@@ -428,6 +428,40 @@ def stitch_panorama_rows(img_t, img_q, inv_h, grid_origin, warp_wh, t_origin, q_
                                        RWH_WARP_ZERO_ORIGIN if zero_origin else 0, _lib.stream_ptr()), "rwh_stitch_panorama_rows")
 
 
+# element type codes of rwh_stitch_panorama_ex (a bool plane is read as uint8: numpy and torch store it as one 0 / 1 byte)
+STITCH_DTYPE = {torch.uint8: RWH_U8, torch.bool: RWH_U8, torch.int8: _lib.RWH_I8, torch.uint16: _lib.RWH_U16, torch.int16: _lib.RWH_I16,
+                torch.int32: _lib.RWH_I32, torch.uint32: _lib.RWH_U32, torch.int64: _lib.RWH_I64, torch.uint64: _lib.RWH_U64,
+                torch.float16: _lib.RWH_F16, torch.float32: RWH_F32, torch.float64: RWH_F64}
+
+
+def stitch_panorama_ex(img_t, img_q, inv_h, grid_origin, warp_wh, t_origin, q_origin, canvas_hw, blend, rate, zero_origin=True,
+                       rows=None, out=None):
+    """The exact compositor on images of any element type of STITCH_DTYPE (rwh_stitch_panorama_ex): img_t [H,W,3|4], img_q
+    [H,W,1|3|4] GPU tensors -> uint8 canvas [fh, fw, 3] (blend) or [fh, fw, C_T] (paste).  rows=(r0, r1): only those canvas rows,
+    into `out` (the whole canvas tensor) when given.  zero_origin: paste blanks texel (0,0) of img_t in place (pass it with the
+    first row tile only); blend reads that texel blanked and never writes img_t (pass it with every tile)."""
+    lib = _lib.load()
+    _dev_check(img_t, img_q)
+    if img_t.dtype not in STITCH_DTYPE or img_q.dtype not in STITCH_DTYPE:
+        raise TypeError("stitch_panorama_ex: no element type code for %s / %s" % (img_t.dtype, img_q.dtype))
+    fh, fw = (int(v) for v in canvas_hw)
+    cc = 3 if blend else int(img_t.shape[2])
+    if out is None:
+        out = torch.empty((fh, fw, cc), dtype=torch.uint8, device=img_t.device)
+    else:
+        _dev_check(out)
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (fh, fw, cc)
+    r0, r1 = (0, fh) if rows is None else (int(rows[0]), int(rows[1]))
+    ih = np.ascontiguousarray(inv_h, dtype=np.float64).reshape(9)
+    check(lib.rwh_stitch_panorama_ex(_ptr(img_t), img_t.shape[0], img_t.shape[1], img_t.shape[2], STITCH_DTYPE[img_t.dtype],
+                                     _ptr(img_q), img_q.shape[0], img_q.shape[1], img_q.shape[2], STITCH_DTYPE[img_q.dtype],
+                                     ih.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(grid_origin[0]), int(grid_origin[1]),
+                                     int(warp_wh[0]), int(warp_wh[1]), int(t_origin[0]), int(t_origin[1]), int(q_origin[0]),
+                                     int(q_origin[1]), fh, fw, cc, int(blend), float(rate), _ptr(out), r0, r1,
+                                     RWH_WARP_ZERO_ORIGIN if zero_origin else 0, _lib.stream_ptr()), "rwh_stitch_panorama_ex")
+    return out
+
+
 def decode_best(best_words, k_total):
     """Unpack the two argmax words (host ints) -> (winner_index, count, early_exit).
     Word 1 (first index reaching `need`) takes precedence, like the reference's
