@@ -22,7 +22,8 @@
 extern "C" {
 #endif
 
-#define RWH_ABI_VERSION 4   /* 4: rwh_stitch_panorama_ex and the element types after RWH_F64 (additive);
+#define RWH_ABI_VERSION 5   /* 5: rwh_settle_decide and its two callback types (additive);
+                               4: rwh_stitch_panorama_ex and the element types after RWH_F64 (additive);
                                3 (round 4): rwh_ransac_run takes hyp_base and returns packed keys, RWH_HYP_DEGENERATE, rwh_score_interval;
                                2: blend modes of rwh_stitch_panorama, RWH_BATCH_EARLY_STOP (d_counts may hold -1), rwh_lab_clock_probe, RWH_HYP_ILLCOND */
 #define RWH_API __attribute__((visibility("default")))
@@ -381,6 +382,27 @@ RWH_API int rwh_ransac_run_layout(int m, int k, long long* offsets, int n_offset
 RWH_API int rwh_ransac_run(const float* pts_a, const float* pts_b, int m, const int32_t* idx, int k, double th, int loss,
                    int need, int margin_cap, void* dgesdd_ilp64, void* dgesv_ilp64, int threads, void* d_ws, void* h_ws,
                    int64_t hyp_base, int32_t* out, uint64_t* out_keys, uint64_t* out_mask, void* stream);
+
+/*
+ * HOST only (no device memory, no stream; works without a GPU): the settle step's DECISION as rwh_ransac_run takes it, with the
+ * GPU and LAPACK work handed to the caller's callbacks -- what the step-by-step drivers of the Python package run.
+ *   k hypotheses; flags [k]: K1's flags; counts [k]: K2's raw counts in (a row already settled holds its settled count), the
+ *   settled counts out; slot [k]: -1 or the settle order 0 .. nset-1 of rows the caller settled beforehand in, the settle order of
+ *   every settled row out; pts_a: m x 2 float32 (HOST), read for the coordinate scale only (largest |entry|, at least 1);
+ *   allow_iv: 'fwd' with K1's H at hand -- the interval rule runs if the coordinate scale is finite (below 1e30), else the margin
+ *   rule with margin_cap, as in rwh_ransac_run;
+ *   interval(rows, n, coord_scale, lo, hi, user): [lo, hi] of every listed row (rwh_score_interval), written at lo[row], hi[row];
+ *   solve(rows, n, counts, user): the reference's count of every listed row (host solver, then K2), written at counts[row];
+ *     the rows take the next n slots.  A callback returns 0, or a nonzero status that ends the call;
+ *   out: 5 x int32 = winner (-1: none), early exit (0 / 1), winner's count, settle rounds, hypotheses given an interval.
+ * Returns 0, RWH_E_INVALID (NULL pointer, k < 0, m < 0, margin_cap < 0, slots that are not exactly 0 .. nset-1), or the first
+ * nonzero status a callback returned -- counts, slot and out then hold the state as far as the rule got.
+ */
+typedef int (*rwh_settle_interval_fn)(const int32_t* rows, int n, double coord_scale, int32_t* lo, int32_t* hi, void* user);
+typedef int (*rwh_settle_solve_fn)(const int32_t* rows, int n, int32_t* counts, void* user);
+RWH_API int rwh_settle_decide(int k, const uint8_t* flags, int32_t* counts, int32_t* slot, const float* pts_a, int m, int need,
+                              int allow_iv, int margin_cap, rwh_settle_interval_fn interval, rwh_settle_solve_fn solve, void* user,
+                              int32_t* out);
 
 /*
  * Fused panorama compositor.  Replaces the body of stitchPanorama (homography.py:288-338) after its canvas

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librwh_hip.so")
 
-ABI_VERSION = 4          # RWH_ABI_VERSION of the include/rwh.h this binding was written against
+ABI_VERSION = 5          # RWH_ABI_VERSION of the include/rwh.h this binding was written against
 RWH_U8, RWH_F32, RWH_F64 = 0, 1, 2
 RWH_I8, RWH_U16, RWH_I16, RWH_I32, RWH_I64, RWH_U32, RWH_U64, RWH_F16 = 3, 4, 5, 6, 7, 8, 9, 10    # rwh_stitch_panorama_ex only
 RWH_NEAREST, RWH_BILINEAR = 0, 1
@@ -27,7 +27,12 @@ RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRA
 EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_probe", "rwh_warp_backward", "rwh_warp_plan", "rwh_sample_points", "rwh_dlt4_batched",
            "rwh_score_count", "rwh_project_points", "rwh_project_points_ex", "rwh_ransac_search", "rwh_ransac_batched", "rwh_stitch_panorama",
            "rwh_host_dlt4_svd", "rwh_ransac_run", "rwh_ransac_run_layout", "rwh_warp_index_check", "rwh_score_count_inv", "rwh_host_inv3", "rwh_stitch_panorama_rows",
-           "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex")
+           "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex", "rwh_settle_decide")
+
+# the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
+_I32P = ctypes.POINTER(ctypes.c_int32)
+SETTLE_INTERVAL_FN = ctypes.CFUNCTYPE(ctypes.c_int, _I32P, ctypes.c_int, ctypes.c_double, _I32P, _I32P, ctypes.c_void_p)
+SETTLE_SOLVE_FN = ctypes.CFUNCTYPE(ctypes.c_int, _I32P, ctypes.c_int, _I32P, ctypes.c_void_p)
 
 
 class RwhUnavailable(RuntimeError):
@@ -102,6 +107,8 @@ def _bind(lib):
     lib.rwh_ransac_run_layout.argtypes = [i32, i32, vp, i32]
     lib.rwh_ransac_run.restype = i32
     lib.rwh_ransac_run.argtypes = [vp, vp, i32, vp, i32, f64, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp]
+    lib.rwh_settle_decide.restype = i32
+    lib.rwh_settle_decide.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, SETTLE_INTERVAL_FN, SETTLE_SOLVE_FN, vp, vp]
     return lib
 
 

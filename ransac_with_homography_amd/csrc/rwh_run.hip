@@ -4,9 +4,9 @@
 // (rwh_ransac_search: K1 + K2 + argmax) plus the "settle" step that makes the result exact with respect to the reference's
 // solver: every sample K1 flags (repeated index, non-finite, ill-conditioned) and every hypothesis whose count is within a
 // margin of a decision gets the reference's own H -- LAPACK dgesdd, rwh_host_dlt4_svd -- and is re-scored by K2; then the
-// accept rules (first count >= need wins and stops, else the first maximum) are applied.  Rounds 2-3 drove this from
-// Python (ransac._settle_on_host: still there for the batched and sharded forms, and as this function's twin in the CPU
-// tests); here the same logic runs without the interpreter between its ~30 small steps: one upload, the repeated-index
+// accept rules (first count >= need wins and stops, else the first maximum) are applied.  Which hypotheses are settled is
+// decided by rwh_settle.h, here and in rwh_settle_decide (the same rule with C callbacks, for ransac._settle_on_host); this
+// function runs the GPU work around it without the interpreter between its ~30 small steps: one upload, the repeated-index
 // samples solved on host threads WHILE the GPU searches, one readback, usually one more solve / score / readback round.
 //
 // Buffers are the caller's (the function allocates nothing persistent): a device workspace and a page-locked host
@@ -209,13 +209,8 @@ extern "C" int rwh_ransac_run(const float* pts_a, const float* pts_b, int m, con
 
     STAMP("counts copy + flag count");
     // ---- 'fwd': count intervals for the candidates, then the settle rounds and the accept rules (rwh_settle.h) --------------
-    double cscale = 1.0;
-    for (long long i = 0; i < 2ll * m; ++i) {
-        const double v = pts_a[i] < 0 ? -(double)pts_a[i] : (double)pts_a[i];
-        if (v != v) { cscale = v; break; }                                 // a NaN coordinate
-        if (v > cscale) cscale = v;
-    }
-    const bool use_iv = loss == RWH_LOSS_FWD && cscale < 1e30;            // (an Inf / NaN coordinate: the margin rule; NaN < 1e30 is false)
+    const double cscale = rwh_settle::coord_scale(pts_a, m);
+    const bool use_iv = loss == RWH_LOSS_FWD && rwh_settle::intervals_usable(cscale);
     auto interval = [&](const int32_t* rows, int n_iv, int32_t* lo, int32_t* hi) -> int {
         if (hipMemcpyAsync(d_rows, rows, 4 * (size_t)n_iv, hipMemcpyHostToDevice, s) != hipSuccess) return RWH_E_LAUNCH;
         const int r = rwh_score_interval(d_H, d_rows, n_iv, d_flags, d_pa, d_pb, m, th, cscale, IV_DELTA0, IV_DELTA1, d_lo, d_hi, s);
@@ -259,4 +254,31 @@ extern "C" int rwh_ransac_run(const float* pts_a, const float* pts_b, int m, con
     for (int i = 0; i < k; ++i) h_cntset[i] = cnt[(size_t)i];      // (h_cntset is free again: every batch has been absorbed)
     STAMP("settled counts out");
     return RWH_OK;
+}
+
+extern "C" int rwh_settle_decide(int k, const uint8_t* flags, int32_t* counts, int32_t* slot, const float* pts_a, int m, int need,
+                                 int allow_iv, int margin_cap, rwh_settle_interval_fn interval, rwh_settle_solve_fn solve, void* user,
+                                 int32_t* out) {
+    if (k < 0 || m < 0 || margin_cap < 0 || !flags || !counts || !slot || !pts_a || !interval || !solve || !out) return RWH_E_INVALID;
+    rwh_settle::State st;
+    st.pos.assign(slot, slot + k);
+    st.cnt.assign(counts, counts + k);
+    for (int i = 0; i < k; ++i) st.nset += slot[i] >= 0;
+    std::vector<char> seen((size_t)st.nset);                             // slots must be exactly 0 .. nset-1
+    for (int i = 0; i < k; ++i) {
+        const int p = slot[i];
+        if (p < -1 || p >= st.nset || (p >= 0 && seen[(size_t)p])) return RWH_E_INVALID;
+        if (p >= 0) seen[(size_t)p] = 1;
+    }
+    const double cscale = rwh_settle::coord_scale(pts_a, m);
+    std::vector<int> rows((size_t)(k > 0 ? k : 1));
+    rwh_settle::Outcome o;
+    const int r = rwh_settle::decide(
+        k, flags, need, allow_iv && rwh_settle::intervals_usable(cscale), margin_cap, rows.data(), st,
+        [&](const int* rw, int n, int* lo, int* hi) { return interval(rw, n, cscale, lo, hi, user); },
+        [&](const int* rw, int n, int* cnt) { return solve(rw, n, cnt, user); }, o);
+    std::copy(st.cnt.begin(), st.cnt.end(), counts);
+    std::copy(st.pos.begin(), st.pos.end(), slot);
+    out[0] = o.winner; out[1] = o.early; out[2] = o.count; out[3] = o.rounds; out[4] = o.n_iv;
+    return r;
 }

@@ -1,7 +1,8 @@
 // rwh_settle.h: the DECISION part of the settle step of rwh_ransac_run (csrc/rwh_run.hip) -- which hypotheses get the reference's own
 // solver, in which rounds, and the accept rules over the result.  Host-only C++17 (no HIP include, no HIP type): the GPU work comes in
-// through two callables, so the same code runs inside the library and, driven by synthetic tables, in the CPU suite
-// (tests/cabi/settle_rule_shim.cpp, tests/test_settle_rule_cpu.py).  ransac._settle_on_host is its Python twin: same rules.
+// through two callables.  rwh_ransac_run calls `decide` directly; rwh_settle_decide (csrc/rwh_run.hip) exports it with C callbacks
+// for ransac._settle_on_host (the step-by-step Python driver, the batched and sharded forms) and for the CPU suite
+// (tests/test_settle_rule_cpu.py, on synthetic tables).  This file is the only place the rule is written.
 //
 // THE MODEL the 'fwd' interval rule is entitled to assume -- and all it assumes (stated in include/rwh.h and DESIGN.md too):
 //   * a hypothesis without an always-bit (RWH_HYP_REPEATED / SINGULAR / DEGENERATE) has its reference count inside its count
@@ -26,7 +27,24 @@ namespace rwh_settle {
 
 static constexpr int IV_NEAR = 32;
 
+// Margin around a decision count: min(cap, 3 + best / 16).  It shrinks with the count (a count of 17 cannot move by 8) and grows by
+// at most 1 per 16 counts, so best - margin_of(best) is nondecreasing: a hypothesis inside the margin of a larger best is inside the
+// margin of every smaller one -- what lets each shard of a sharded search settle on its own (sharded.gpu_score_slice).
 inline int margin_of(int best, int cap) { const int v = 3 + (best > 0 ? best : 0) / 16; return v < cap ? v : cap; }
+
+// The coordinate scale of rwh_score_interval's budget: the largest |entry| of pts_a (m x 2), at least 1; NaN if an entry is NaN.
+inline double coord_scale(const float* pts_a, int m) {
+    double c = 1.0;
+    for (long long i = 0; i < 2ll * m; ++i) {
+        const double v = pts_a[i] < 0 ? -(double)pts_a[i] : (double)pts_a[i];
+        if (v != v) return v;
+        if (v > c) c = v;
+    }
+    return c;
+}
+
+// Whether the 'fwd' interval rule may run at this scale: an Inf / NaN coordinate takes the margin rule (NaN < 1e30 is false).
+inline bool intervals_usable(double coord_scale) { return coord_scale < 1e30; }
 
 struct Outcome {
     int winner = -1, early = 0, count = 0;   // accept rules over the prefix the reference looks at; winner -1: no count above 0

@@ -24,13 +24,12 @@ index gives a rank-deficient 8 x 9 system, for which the reference still takes w
 LAPACK's SVD returns and lets it compete for the running best; an ill-conditioned sample (three collinear
 source points, equal coordinates at different indices) gives K1 and LAPACK unrelated H; and on ~2 % of
 ordinary samples the two round to neighbouring float32 H.  K1 flags the first two kinds
-(RWH_HYP_REPEATED / _SINGULAR / _ILLCOND) and `_settle_on_host` re-derives, with the reference's own
-arithmetic (float32 DLT matrix -> LAPACK dgesdd, the routine numpy.linalg.svd calls -> /h[8]: `svd_hypotheses`),
-every flagged hypothesis and every unflagged one whose count is within a margin of the best (or of the
-early-exit count), re-scores those rows with K2 (bit-exact given H) and only then applies the accept rules.
-The repeated-index samples are known before anything is launched: `presettle` solves them on the host
-while the GPU searches; the whole driver is one native call (`rwh_ransac_run`).  k = 1500 at M = 185: ~90 host solves,
-0.36-0.42 ms per run end to end.
+(RWH_HYP_REPEATED / _SINGULAR / _ILLCOND), and the settle step re-derives, with the reference's own arithmetic
+(float32 DLT matrix -> LAPACK dgesdd, the routine numpy.linalg.svd calls -> /h[8]: `svd_hypotheses`), every
+hypothesis that can decide the run (the rule: csrc/rwh_settle.h), re-scores those rows with K2 (bit-exact given H)
+and only then applies the accept rules.  The repeated-index samples are known before anything is launched: they are
+solved on the host while the GPU searches; the whole driver is one native call (`rwh_ransac_run`).  k = 1500 at
+M = 185: ~90 host solves, 0.36-0.42 ms per run end to end.
 
 Error behaviour (fixture g14, written by the unmodified reference): k = 0 raises UnboundLocalError (ransac.py:203 reads a
 variable only the loop assigns), a run in which no hypothesis has an inlier indexes with np.where(None) (an error from numpy
@@ -50,23 +49,10 @@ from . import _lapack, _lib, kernels
 from .homography import (_pair_rows, calcHomography, calcHomographyLinear, cylindericlMap,  # noqa: F401
                          stitchPanorama)
 
-# Which hypotheses need the reference's own solver (`_settle_on_host`):
-#   * every sample K1 flags: a repeated index (LAPACK's null vector of the rank-deficient system is arbitrary -- and it is what
-#     the reference uses), a non-finite result, an ill-conditioned sample (RWH_HYP_ILLCOND: collinear triples, equal
-#     coordinates at different indices, |h33| tiny; K1's elimination and LAPACK then round to different float32 H);
-#   * second line: every unflagged hypothesis whose count is within a margin of a decision (the best count, the early-exit
-#     count).  An unflagged K1 H differs from LAPACK's by float32 round-off on 1.8 % of natural samples, which moves its
-#     inlier count by <= 2 on all ~130 000 golden hypotheses and by <= 8 on the lattice / cluster stress sets of
-#     tests/golden/g12_illcond.npz (measured with a float64 emulation of K1, tools/README).  The margin shrinks with the
-#     best count (a count of 17 cannot move by 8): `_margin(best)`.
+# Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
+# in csrc/rwh_settle.h.  RESCORE_MARGIN caps the margin of the 'backward' / 'reproj' rule: an unflagged K1 count moves by <= 2
+# on all ~130 000 golden hypotheses and by <= 8 on the stress sets of tests/golden/g12_illcond.npz (tools/README).
 RESCORE_MARGIN = 8
-
-
-def _margin(best, cap):
-    """Margin around a decision count `best`: min(cap, 3 + best // 16), nondecreasing in `best` and growing by at most
-    1 per 16 counts, so `best - _margin(best)` is nondecreasing too (a hypothesis inside the margin of a larger best is
-    inside the margin of every smaller one: what lets each shard settle on its own, sharded.gpu_score_slice)."""
-    return min(int(cap), 3 + int(best) // 16)
 
 
 LVL = 0
@@ -146,7 +132,7 @@ def _host_thread_share():
 
 
 HOST_THREADS = _host_thread_share()
-FORCE_PYTHON_DRIVER = False        # tests: RANSAC.run through the Python twin of rwh_ransac_run
+FORCE_PYTHON_DRIVER = False        # tests: RANSAC.run through `_run_python_driver`, the step-by-step form of rwh_ransac_run
 
 
 def svd_hypotheses(pts_a, pts_b, idx_rows, threads=None):
@@ -187,15 +173,13 @@ def repeated_rows(idx):
 class _Settled(object):
     """Hypotheses re-derived with the reference's solver so far: index -> (H row, count, where its mask lives)."""
 
-    def __init__(self, k):
-        self.done = np.zeros(k, dtype=bool)
+    def __init__(self):
         self.batches = []          # (indices, H float32 [n, 9], mask tensor [n, words] on the device)
         self.where = {}
 
     def add(self, cand, H, masks):
         b = len(self.batches)
         self.batches.append((cand, H, masks))
-        self.done[cand] = True
         for j, i in enumerate(cand.tolist()):
             self.where[i] = (b, j)
 
@@ -234,10 +218,7 @@ def presettle(pa_dev, pb_dev, pa, pb, idx_host, rows, th, method):
     return rows, H, cnt, msk
 
 
-# 'fwd' searches (round 4): which hypotheses need the reference's own solver is decided by count INTERVALS (rwh_score_interval),
-# not by a flat margin -- the native driver's rule (csrc/rwh_run.hip), mirrored in `_settle_on_host`.
-IV_NEAR = 32                               # hypotheses within this many counts of the best / of `need` get an interval
-IV_DELTA0, IV_DELTA1 = 2.0 ** -20, 2.0 ** -18     # perturbation budgets (natural scale of an entry): unflagged / RWH_HYP_ILLCOND rows
+IV_DELTA0, IV_DELTA1 = 2.0 ** -20, 2.0 ** -18     # interval budgets (natural scale of an entry): unflagged / RWH_HYP_ILLCOND rows
 
 
 def _settle_on_host(pa_dev, pb_dev, pa, pb, idx_host, counts, flags, need, th, method, margin, stats=None, pre=None, H_dev=None,
@@ -245,87 +226,58 @@ def _settle_on_host(pa_dev, pb_dev, pa, pb, idx_host, counts, flags, need, th, m
     """Accept rules of ransac.py:186-202 over K1/K2's results, exact with respect to the reference's solver.
 
     counts / flags: host copies of K2's counts and K1's flags for the k hypotheses of `idx_host`; `pre`: what `presettle`
-    returned (its counts are read here).  Hypotheses are "settled" (H from the host SVD, count + mask from K2 on that H)
-    in rounds until every hypothesis that can take part in the decision is settled:
-      * nothing after the first hypothesis that certainly reaches `need` is ever looked at by the reference (`break`,
-        ransac.py:186-190);
-      * inside that prefix, 'fwd' with K1's H at hand (`H_dev`): the samples whose H says nothing (repeated index, non-finite,
-        RWH_HYP_DEGENERATE) and, of the candidates -- RWH_HYP_ILLCOND samples, hypotheses within IV_NEAR of the best or of
-        `need`, each with a count interval [lo, hi] from rwh_score_interval --, those whose interval is not a point and reaches
-        the best lower bound or `need`;
-      * 'backward' / 'reproj' (or no H_dev): every flagged hypothesis, every unflagged one within `_margin` of `need` or of
-        the best trustworthy count (the rule of rounds 2-3).
-    Usually ONE round beyond `pre`.  Returns (winner | None, early, count, mask_words | None, H_rows, counts): mask_words
-    is the winner's uint64 mask if the winner was settled here (None: take K2's own mask for it), H_rows maps settled
-    index -> float32[9], counts is the int64 count table with the settled entries replaced."""
+    returned (its counts are read here).  Which hypotheses are "settled" (H from the host SVD, count + mask from K2 on that H),
+    in which rounds, and the accept rules are rwh_ransac_run's rule (csrc/rwh_settle.h), called through `rwh_settle_decide`:
+    the interval rule for 'fwd' with K1's H at hand (`H_dev`), else the margin rule capped at `margin`.  This function does the
+    work it asks for (`svd_hypotheses` + `_score_settled`, `kernels.score_interval`); an exception raised there propagates.
+    Returns (winner | None, early, count, mask_words | None, H_rows, counts): mask_words is the winner's uint64 mask if the
+    winner was settled here (None: take K2's own mask for it), H_rows maps settled index -> float32[9], counts is the int64
+    count table with the settled entries replaced."""
     import torch
-    k = counts.shape[0]
-    counts = counts.astype(np.int64)
-    st = _Settled(k)
-    flags = np.asarray(flags)
-    suspect = flags != 0
-    n_rounds = 0
+    flags = np.ascontiguousarray(flags, dtype=np.uint8)
+    k = flags.shape[0]
+    cnt, slot, st = np.array(counts, dtype=np.int32), np.full(k, -1, dtype=np.int32), _Settled()
     if pre is not None:
-        rows, H, cnt, msk = pre
-        counts[rows] = cnt.cpu().numpy()
+        rows, H, c, msk = pre
+        cnt[rows], slot[rows] = c.cpu().numpy(), np.arange(len(rows))
         st.add(rows, H, msk)
-    with np.errstate(invalid="ignore"):
-        cscale = float(max(1.0, np.abs(pa).max())) if pa.size else 1.0
-        if pa.size and np.isnan(pa).any():
-            cscale = float("nan")                          # a NaN coordinate: the margin rule, like an Inf one (NaN < 1e30 is false)
-    use_iv = method == "fwd" and H_dev is not None and cscale < 1e30
-    n_iv = 0
-    if use_iv:
-        always = (flags & (_lib.RWH_HYP_REPEATED | _lib.RWH_HYP_SINGULAR | _lib.RWH_HYP_DEGENERATE)) != 0
-        lo, hi = counts.copy(), counts.copy()              # not a candidate: its count is taken as it is
-        free = ~always
-        unflagged = flags == 0                            # an RWH_HYP_ILLCOND raw count places nothing: a lower best0 only widens
-        best0 = int(counts[unflagged].max()) if unflagged.any() else 0
-        cand0 = np.flatnonzero(~st.done & free & (((flags & _lib.RWH_HYP_ILLCOND) != 0) | (counts >= best0 - IV_NEAR) | (counts >= need - IV_NEAR)))
-        if cand0.size:
-            if flags_dev is None:
-                flags_dev = torch.from_numpy(np.ascontiguousarray(flags, dtype=np.uint8)).to(H_dev.device)
-            lo[cand0], hi[cand0] = kernels.score_interval(H_dev, cand0, flags_dev, pa_dev, pb_dev, th, cscale, IV_DELTA0, IV_DELTA1)
-        n_iv = int(cand0.size)
-    while True:
-        settled = st.done
-        if use_iv:
-            sure = np.where(settled, counts >= need, ~always & (lo >= need))
-        else:
-            sure = np.where(settled, counts >= need, ~suspect & (counts >= need + _margin(need, margin)))
-        hit = np.flatnonzero(sure)
-        end = int(hit[0]) + 1 if hit.size else k
-        c = counts[:end]
-        open_ = ~settled[:end]
-        if use_iv:
-            v = np.where(settled[:end], c, np.where(always[:end], 0, lo[:end]))
-            best = int(v.max()) if v.size else 0
-            cand = np.flatnonzero(open_ & (always[:end] | ((lo[:end] < hi[:end]) & ((hi[:end] >= best) | (hi[:end] >= need)))))
-        else:
-            trusted = settled | ~suspect                  # counts that mean something: the reference's, or K1's within a margin
-            tc = c[trusted[:end]]
-            best = int(tc.max()) if tc.size else 0
-            cand = np.flatnonzero(open_ & (suspect[:end] | (c >= best - _margin(best, margin)) | (c >= need - _margin(need, margin))))
-        if cand.size == 0:
-            break
-        n_rounds += 1
-        H = svd_hypotheses(pa, pb, idx_host[cand][:, :4])
-        cnt, msk = _score_settled(H, pa_dev, pb_dev, th, method)
-        counts[cand] = cnt.cpu().numpy()
-        st.add(cand, H, msk)
+    failed = []
+
+    def callback(fn_type, body):        # an exception inside a ctypes callback would be printed and dropped: kept, raised below
+        def call(rows, n, *args):
+            try:
+                body(np.ctypeslib.as_array(rows, (n,)).astype(np.int64), *args[:-1])
+                return 0
+            except BaseException as e:
+                failed.append(e)
+                return 1
+        return fn_type(call)
+
+    def solve(rows, cnt_p):
+        H = svd_hypotheses(pa, pb, idx_host[rows][:, :4])
+        c, msk = _score_settled(H, pa_dev, pb_dev, th, method)
+        np.ctypeslib.as_array(cnt_p, (k,))[rows] = c.cpu().numpy()
+        st.add(rows, H, msk)
+
+    def interval(rows, coord_scale, lo_p, hi_p):
+        f_dev = flags_dev if flags_dev is not None else torch.from_numpy(flags).to(H_dev.device)
+        lo, hi = kernels.score_interval(H_dev, rows, f_dev, pa_dev, pb_dev, th, coord_scale, IV_DELTA0, IV_DELTA1)
+        np.ctypeslib.as_array(lo_p, (k,))[rows], np.ctypeslib.as_array(hi_p, (k,))[rows] = lo, hi
+
+    pa32 = np.ascontiguousarray(pa, dtype=np.float32)
+    out = np.zeros(5, dtype=np.int32)
+    fns = callback(_lib.SETTLE_INTERVAL_FN, interval), callback(_lib.SETTLE_SOLVE_FN, solve)     # alive until the call returns
+    rc = _lib.load().rwh_settle_decide(k, flags.ctypes.data, cnt.ctypes.data, slot.ctypes.data, pa32.ctypes.data, pa32.size // 2,
+                                       int(need), int(method == "fwd" and H_dev is not None), int(margin), *fns, None, out.ctypes.data)
+    if failed:
+        raise failed[0]
+    _lib.check(rc, "rwh_settle_decide")
+    w, early, count, rounds, n_iv = out.tolist()
     if stats is not None:
-        stats["host_settled"] = int(st.done.sum())
-        stats["host_rounds"] = n_rounds
-        stats["flagged"] = int(suspect.sum())
-        stats["intervals"] = n_iv
-    hit = np.flatnonzero(c >= need)
-    if hit.size:
-        w, early = int(hit[0]), True
-    elif end and c.max() > 0:
-        w, early = int(np.argmax(c)), False               # first index of the maximum (ransac.py:199: strict >)
-    else:
-        return None, False, 0, None, st.rows(), counts
-    return w, early, int(c[w]), st.mask_words(w), st.rows(), counts
+        stats.update(host_settled=int((slot >= 0).sum()), host_rounds=rounds, flagged=int((flags != 0).sum()), intervals=n_iv)
+    if w < 0:
+        return None, False, 0, None, st.rows(), cnt.astype(np.int64)
+    return w, bool(early), count, st.mask_words(w), st.rows(), cnt.astype(np.int64)
 
 
 class Model(object):
@@ -523,7 +475,7 @@ class RANSAC(object):
                     dgesv=gesv, want_keys=True)
             except _lib.RwhError:
                 # LAPACK refused a sample (info != 0: e.g. an Inf coordinate times 0 is a NaN in the DLT matrix): the step-by-step
-                # twin reaches numpy.linalg.svd, which raises the reference's LinAlgError for it
+                # driver reaches numpy.linalg.svd, which raises the reference's LinAlgError for it
                 ws = None
         else:
             ws = None

@@ -34,7 +34,8 @@ def gpu_score_slice(pa, pb, idx_slice, th, loss, need, hyp_base):
     every hypothesis that can decide the slice -- repeated-index samples on host threads while the GPU searches --, the accept
     rules), which returns the slice's two packed keys (round 4; rounds 2-3 ran the step-by-step Python driver here).
     A hypothesis that can decide the GLOBAL search can decide its own slice (the slice's best is not above the global best),
-    so settling needs no exchange and the path keeps its ONE collective.  Without numpy's LAPACK by address: the Python twin.
+    so settling needs no exchange and the path keeps its ONE collective.  Without numpy's LAPACK by address: the step-by-step driver
+    (`ransac._settle_on_host`, the same rule through `rwh_settle_decide`).
     Returns the keys (include/rwh.h, rwh_score_count) as a 2 x int64 tensor on the GPU."""
     import torch
     from . import _lapack, kernels

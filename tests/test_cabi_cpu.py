@@ -51,6 +51,26 @@ def test_argument_validation_without_gpu(lib):
     assert st == -1
     st = lib.rwh_warp_backward(null, 10, 10, 3, 0, 300, 1, ih, 1, 0., 1., 9., 0., 1., 9., 10, 10, 10, 10, 1, null, 0, 300, 4, 4, 0, null)
     assert st == 0
+    # rwh_settle_decide (host only): NULL pointers, k < 0, slots that are not exactly 0 .. nset-1 -> RWH_E_INVALID before any callback
+    from ransac_with_homography_amd import _lib
+    calls = []
+    iv = _lib.SETTLE_INTERVAL_FN(lambda *a: calls.append("iv") or 0)
+    solve = _lib.SETTLE_SOLVE_FN(lambda *a: calls.append("solve") or 0)
+    flags, pa, out = np.zeros(3, np.uint8), np.ones((3, 2), np.float32), np.zeros(5, np.int32)
+
+    def decide(k=3, flags=flags.ctypes.data, counts=None, slot=None, pa=pa.ctypes.data, iv=iv, solve=solve, out=out.ctypes.data):
+        cnt, sl = np.array([5, 9, 7], np.int32), np.array(slot if slot is not None else [-1, -1, -1], np.int32)
+        return lib.rwh_settle_decide(k, flags, cnt.ctypes.data if counts is None else counts, sl.ctypes.data, pa, 3, 100, 0, 8,
+                                     iv, solve, None, out)
+    assert decide(k=-1) == -1 and decide(flags=None) == -1 and decide(counts=null) == -1 and decide(pa=None) == -1
+    assert decide(iv=_lib.SETTLE_INTERVAL_FN()) == -1 and decide(solve=_lib.SETTLE_SOLVE_FN()) == -1 and decide(out=None) == -1   # (NULL callbacks)
+    assert lib.rwh_settle_decide(3, flags.ctypes.data, out.ctypes.data, None, pa.ctypes.data, 3, 100, 0, 8, iv, solve, None,
+                                 out.ctypes.data) == -1
+    for bad in ([0, 0, -1], [1, -1, -1], [0, 2, -1], [-2, -1, -1], [3, -1, -1]):
+        assert decide(slot=bad) == -1, bad
+    assert calls == []
+    # a valid call needs no GPU: the margin rule settles rows 1 and 2 in one round (the callback leaves their counts), row 1 wins
+    assert decide(slot=[-1, -1, -1]) == 0 and out.tolist() == [1, 0, 9, 1, 0] and calls == ["solve"]
 
 
 def test_round3_host_entry_points_without_gpu(lib):

@@ -14,6 +14,13 @@ from ransac_with_homography_amd import kernels
 from ransac_with_homography_amd import ransac as impl
 
 
+@pytest.fixture(scope="module", autouse=True)
+def lib():
+    """_settle_on_host takes its rule from the library (rwh_settle_decide, host code: no GPU needed)."""
+    import __graft_entry__ as g
+    g.build()
+
+
 @pytest.fixture
 def oracle_scorer(monkeypatch):
     def score_count(H, pa, pb, th, loss, need, best, **kw):

@@ -1,6 +1,7 @@
-"""The settle rule of RANSAC.run against the model it relies on, on CPU: the native rule (ransac_with_homography_amd/csrc/rwh_settle.h,
-compiled here with g++ through tests/cabi/settle_rule_shim.cpp and driven through ctypes) and its Python twin (ransac._settle_on_host,
-with the host solver, the scorer and the interval kernel replaced by table lookups) on synthetic hypothesis tables.
+"""The settle rule of RANSAC.run against the model it relies on, on CPU, on synthetic hypothesis tables: the rule
+(ransac_with_homography_amd/csrc/rwh_settle.h) through the library's host-only export rwh_settle_decide, driven through ctypes, and
+through ransac._settle_on_host -- the Python plumbing around the same export (`pre`, slots, masks, the H rows returned) -- with the host
+solver, the scorer and the interval kernel replaced by table lookups.
 
 Every table lists, per hypothesis, K1's flags, K2's raw count, a count interval [lo, hi] (what rwh_score_interval would return) and the
 reference's TRUE count.  In-model tables obey the model stated in rwh_settle.h (and include/rwh.h):
@@ -10,38 +11,25 @@ reference's TRUE count.  In-model tables obey the model stated in rwh_settle.h (
   * always-bit rows: anything.
 The oracle is the reference's accept rules (ransac.py:186-202) on the true counts of all k hypotheses.  For the margin rule
 ('backward' / 'reproj', margin cap 0 or 8) the model is |true - raw| <= min(3, cap) for unflagged rows.  Out-of-model tables
-(containment broken on purpose) have no right answer; there the two drivers must still agree."""
+(containment broken on purpose) have no right answer; there the two paths must still agree."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from ransac_with_homography_amd import kernels
+from ransac_with_homography_amd import _lib, kernels
 from ransac_with_homography_amd import ransac as impl
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REP, SING, ILL, DEG = 1, 2, 4, 8
-NEAR = 32                                     # IV_NEAR of rwh_settle.h / ransac.py
-
-IV_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                         ctypes.POINTER(ctypes.c_int), ctypes.c_void_p)
-SETTLE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_void_p)
+NEAR = 32                                     # IV_NEAR of rwh_settle.h
 
 
 @pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("settle_shim") / "settle_rule_shim.so")
-    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"),
-                    "-I", os.path.join(ROOT, "ransac_with_homography_amd", "csrc"), os.path.join(ROOT, "tests", "cabi", "settle_rule_shim.cpp"),
-                    "-o", so], check=True)
-    lib = ctypes.CDLL(so)
-    lib.settle_rule_run.restype = ctypes.c_int
-    lib.settle_rule_run.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, IV_FN,
-                                    SETTLE_FN, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    return lib
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    return _lib.load()
 
 
 class Table(object):
@@ -70,10 +58,13 @@ def oracle(t):
     return w, 0, best
 
 
-def run_native(shim, t):
+def run_native(lib, t):
+    """rwh_settle_decide on table t; like rwh_ransac_run, the RWH_HYP_REPEATED rows are settled first (through the same solve
+    callback) and handed in as slots 0 .. n_rep-1."""
     asked_iv, settled = [], []
 
-    def iv(rows, n, lo, hi, _):
+    def iv(rows, n, cscale, lo, hi, _):
+        assert cscale == 1.0                  # pts_a is all zeros: the coordinate scale is its floor
         for j in range(n):
             r = rows[j]
             asked_iv.append(r)
@@ -88,18 +79,27 @@ def run_native(shim, t):
         return 0
 
     out = np.zeros(5, np.int32)
-    slot = np.zeros(max(t.k, 1), np.int32)
-    raw = np.ascontiguousarray(t.raw, np.int32)
-    st = shim.settle_rule_run(t.k, t.flags.ctypes.data, raw.ctypes.data, t.need, int(t.use_iv), t.cap, IV_FN(iv), SETTLE_FN(settle),
-                              None, out.ctypes.data, slot.ctypes.data)
+    cnt = np.array(t.raw, np.int32)
+    slot = np.full(t.k, -1, np.int32)
+    rep = np.flatnonzero(t.flags & REP).astype(np.int32)
+    if rep.size:
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        assert settle(rep.ctypes.data_as(i32p), rep.size, cnt.ctypes.data_as(i32p), None) == 0
+        slot[rep] = np.arange(rep.size)
+    pa = np.zeros((1, 2), np.float32)
+    st = lib.rwh_settle_decide(t.k, t.flags.ctypes.data, cnt.ctypes.data, slot.ctypes.data, pa.ctypes.data, 1, t.need, int(t.use_iv),
+                               t.cap, _lib.SETTLE_INTERVAL_FN(iv), _lib.SETTLE_SOLVE_FN(settle), None, out.ctypes.data)
     assert st == 0
     assert len(settled) == len(set(settled)), ("a hypothesis settled twice", t)
-    assert set(np.flatnonzero(slot[:t.k] >= 0).tolist()) == set(settled)
+    assert set(np.flatnonzero(slot >= 0).tolist()) == set(settled)
+    assert sorted(slot[slot >= 0].tolist()) == list(range(len(settled)))
+    assert all(cnt[r] == t.true[r] for r in settled)
     return dict(res=(int(out[0]), int(out[1]), int(out[2])), settled=set(settled), asked_iv=set(asked_iv))
 
 
 class Twin(object):
-    """ransac._settle_on_host with the GPU / LAPACK work looked up in the current table: H rows carry their hypothesis index."""
+    """ransac._settle_on_host with the GPU / LAPACK work looked up in the current table: H rows and mask rows carry their hypothesis
+    index."""
 
     def __init__(self, monkeypatch):
         self.t = None
@@ -116,9 +116,10 @@ class Twin(object):
     def _score(self, H, pa_dev, pb_dev, th, method):
         r = H[:, 0].astype(np.int64)
         self.settled.extend(r.tolist())
-        return torch.from_numpy(self.t.true[r].astype(np.int32)), torch.zeros((len(r), 1), dtype=torch.int64)
+        return torch.from_numpy(self.t.true[r].astype(np.int32)), torch.from_numpy(r[:, None].copy())
 
     def _interval(self, H, rows, flags, pa, pb, th, cscale, d0, d1):
+        assert cscale == 1.0                  # pts_a is all zeros: the coordinate scale the library computed is its floor
         rows = np.asarray(rows, np.int64)
         self.asked_iv.extend(rows.tolist())
         return self.t.lo[rows].copy(), self.t.hi[rows].copy()
@@ -129,11 +130,15 @@ class Twin(object):
         pa = np.zeros((1, 2), np.float32)
         method = "fwd" if t.use_iv else "backward"
         pre = impl.presettle(None, None, pa, pa, idx, np.flatnonzero(t.flags & REP), 1.0, method)
-        w, early, cnt, words, rows, _ = impl._settle_on_host(
+        w, early, cnt, words, rows, counts = impl._settle_on_host(
             None, None, pa, pa, idx, t.raw.astype(np.int32), t.flags, t.need, 1.0, method, t.cap, {}, pre=pre,
             H_dev=torch.zeros(1) if t.use_iv else None, flags_dev=torch.from_numpy(t.flags) if t.use_iv else None)
         assert len(self.settled) == len(set(self.settled)), ("a hypothesis settled twice", t)
-        assert set(rows) == set(self.settled)
+        assert set(rows) == set(self.settled) and all(int(h[0]) == i for i, h in rows.items())
+        want = t.raw.copy()
+        want[sorted(self.settled)] = t.true[sorted(self.settled)]
+        assert counts.dtype == np.int64 and np.array_equal(counts, want)
+        assert words is None or (w is not None and int(words[0]) == w)
         return dict(res=(-1 if w is None else w, int(early), int(cnt)), settled=set(self.settled), asked_iv=set(self.asked_iv),
                     mask_settled=words is not None)
 
@@ -345,33 +350,74 @@ def _check_in_model(t, nat, twin):
         assert twin["mask_settled"] == (w in twin["settled"])
 
 
-def test_settle_rule_model_native_and_twin(shim, monkeypatch):
-    """Every in-model table: native rule and Python twin each return the oracle's (winner, early, count), settle the same rows,
+def test_settle_rule_model_native_and_twin(lib, monkeypatch):
+    """Every in-model table: the export and _settle_on_host each return the oracle's (winner, early, count), settle the same rows,
     and the winner is settled unless its interval is a point."""
     twin = Twin(monkeypatch)
     seen = {}
     for t in _tables(20261016):
-        nat, tw = run_native(shim, t), twin.run(t)
+        nat, tw = run_native(lib, t), twin.run(t)
         _check_in_model(t, nat, tw)
         seen[t.family] = seen.get(t.family, 0) + 1
     assert sum(seen.values()) >= 3000, seen
 
 
-def test_settle_rule_out_of_model_drivers_agree(shim, monkeypatch):
-    """Containment broken on purpose: there is no right answer, but the native rule and the Python twin must take the same
+def test_settle_rule_out_of_model_drivers_agree(lib, monkeypatch):
+    """Containment broken on purpose: there is no right answer, but the export and _settle_on_host must take the same
     decision and settle the same rows (ADVICE finding 3: a row that seeded the first sure exit settling below `need`)."""
     twin = Twin(monkeypatch)
     rng = np.random.default_rng(7)
     n = 0
     for t in _tables(99):
         b = break_model(rng, t)
-        nat, tw = run_native(shim, b), twin.run(b)
+        nat, tw = run_native(lib, b), twin.run(b)
         assert nat["res"] == tw["res"], (nat["res"], tw["res"], b)
         assert nat["settled"] == tw["settled"], (sorted(nat["settled"] ^ tw["settled"]), b)
         n += 1
     # the targeted case: the first sure row (lo >= need) settles below need; the next sure row decides the prefix
     need = 50
     b = Table([0, 0, 0, 0], [10, 60, 40, 55], [10, 50, 30, 55], [10, 70, 49, 55], [10, 20, 45, 55], need, family="fs_lost")
-    nat, tw = run_native(shim, b), twin.run(b)
+    nat, tw = run_native(lib, b), twin.run(b)
     assert nat["res"] == tw["res"] == (3, 1, 55), (nat, tw)
     assert nat["settled"] == tw["settled"]
+
+
+@pytest.mark.parametrize("where, exc", [("solve", np.linalg.LinAlgError("SVD did not converge")),
+                                        ("interval", RuntimeError("rwh_score_interval failed"))])
+def test_settle_callback_exception_propagates(lib, monkeypatch, where, exc):
+    """An exception raised by the work _settle_on_host does for the rule -- numpy's LinAlgError from the host solver (why RANSAC.run
+    falls back to this path), a kernel or torch error -- leaves _settle_on_host as that same exception, not as a library error; the
+    library returns the status of the callback that caught it."""
+    twin = Twin(monkeypatch)
+
+    def boom(*a, **kw):
+        raise exc
+    monkeypatch.setattr(impl, "svd_hypotheses", boom) if where == "solve" else monkeypatch.setattr(kernels, "score_interval", boom)
+    real, returned = lib.rwh_settle_decide, []
+
+    def spy(*a):
+        returned.append(real(*a))
+        return returned[-1]
+    monkeypatch.setattr(lib, "rwh_settle_decide", spy)
+    # 'fwd': all three rows get an interval, then rows 1 and 2 (open intervals reaching the best lower bound) are settled
+    t = Table([0, ILL, 0], [40, 90, 38], [40, 0, 36], [40, 95, 41], [40, 10, 39], 10 ** 6, family="raises")
+    with pytest.raises(type(exc)) as e:
+        twin.run(t)
+    assert e.value is exc and returned == [1]
+
+
+def test_settle_callback_status_is_returned(lib):
+    """A nonzero status from either callback ends rwh_settle_decide with that status, the state as far as the rule got."""
+    pa = np.zeros((1, 2), np.float32)
+    flags = np.array([0, ILL, 0], np.uint8)
+    for iv_status, solve_status, rounds in ((7, 0, 0), (0, -3, 1)):
+        def iv(rows, n, cscale, lo, hi, _):
+            for j in range(n):
+                lo[rows[j]], hi[rows[j]] = ((40, 40), (0, 95), (36, 41))[rows[j]]
+            return iv_status
+        cnt, slot, out = np.array([40, 90, 38], np.int32), np.full(3, -1, np.int32), np.zeros(5, np.int32)
+        st = lib.rwh_settle_decide(3, flags.ctypes.data, cnt.ctypes.data, slot.ctypes.data, pa.ctypes.data, 1, 10 ** 6, 1, 8,
+                                   _lib.SETTLE_INTERVAL_FN(iv), _lib.SETTLE_SOLVE_FN(lambda rows, n, c, _: solve_status), None,
+                                   out.ctypes.data)
+        assert st == (iv_status or solve_status)
+        assert out.tolist() == [-1, 0, 0, rounds, 3] and cnt.tolist() == [40, 90, 38] and slot.tolist() == [-1, -1, -1]

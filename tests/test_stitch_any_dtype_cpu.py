@@ -34,9 +34,9 @@ def lib():
     return _lib.load()
 
 
-def test_stitch_ex_exported_and_validates(lib):
+def test_stitch_ex_exported_and_validates_abi5(lib):
     from ransac_with_homography_amd import _lib
-    assert _lib.ABI_VERSION == 4 and lib.rwh_abi_version() == 4
+    assert _lib.ABI_VERSION == 5 and lib.rwh_abi_version() == 5
     assert "rwh_stitch_panorama_ex" in _lib.EXPORTS
     nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     assert " rwh_stitch_panorama_ex" in nm
