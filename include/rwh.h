@@ -35,7 +35,8 @@ enum {
     RWH_E_LAUNCH = -3        /* HIP reported a launch / memset failure */
 };
 
-/* element types of image planes (the codes after RWH_F64 are taken by rwh_stitch_panorama_ex only; a bool plane is RWH_U8) */
+/* element types of image planes (the codes after RWH_F64 are taken by rwh_stitch_panorama_ex and by the exact warps,
+   rwh_warp_backward with RWH_WARP_EXACT and rwh_sample_points; a bool plane is RWH_U8) */
 enum { RWH_U8 = 0, RWH_F32 = 1, RWH_F64 = 2, RWH_I8 = 3, RWH_U16 = 4, RWH_I16 = 5, RWH_I32 = 6, RWH_I64 = 7, RWH_U32 = 8,
        RWH_U64 = 9, RWH_F16 = 10 };
 /* interpolators: reference homography.py:140 `convertfunc` keys */
@@ -51,6 +52,9 @@ enum { RWH_LOSS_FWD = 0, RWH_LOSS_BACKWARD = 1, RWH_LOSS_REPROJ = 2 };
                                    k-order, IEEE divides, separately rounded float64 lerps): results bit-identical to
                                    numpy's; dst_dtype F64 (bilinear), U8 (bilinear, truncated) or the source dtype
                                    (nearest).  Several times slower than the default kernels. */
+
+/* channel limit of the any-dtype exact warp (rwh_warp_backward with RWH_WARP_EXACT, rwh_sample_points) */
+#define RWH_WARP_MAX_CHANNELS 64
 
 RWH_API int rwh_abi_version(void);
 RWH_API const char* rwh_strerror(int code);
@@ -114,6 +118,14 @@ RWH_API int rwh_lab_clock_probe(uint64_t* d_out, double milliseconds, void* stre
  *
  * Supported: channels 3 or 4; src_dtype U8 or F32; dst_dtype == src_dtype for
  * RWH_NEAREST; dst_dtype U8 (truncating) or F32 for RWH_BILINEAR (F64 or U8 with RWH_WARP_EXACT).
+ * With RWH_WARP_EXACT also every other source: src_dtype any code RWH_U8 .. RWH_F16, channels 1 .. RWH_WARP_MAX_CHANNELS
+ * (the any-dtype kernel takes every configuration but U8 / F32 with 3 or 4 channels, which keep their kernels).  Nearest
+ * copies texels bit for bit (dst_dtype == src_dtype); bilinear converts each tap to float64 as numpy does (int64 / uint64
+ * round to nearest) and gives F64, or U8 as numpy's astype(np.uint8) of that float64 (low byte of the truncation, 0 where it
+ * does not fit int32).  On this kernel a coordinate outside the bounds reads texel (0,0) (nearest) or is interpolated at
+ * (0, 0) (bilinear), as the reference does, instead of giving 0; RWH_WARP_ZERO_ORIGIN blanks channels 0..2 of texel (0,0),
+ * and channel 3 only when channels == 4 (homography.py:112-116).  Without RWH_WARP_EXACT these sources return
+ * RWH_E_UNSUPPORTED; rwh_warp_plan tells whether a configuration is served.
  * n_h is 1 (one homography for the whole batch) or `batch` (inv_h holds batch
  * 3x3 matrices, image b uses the b-th; any batch size -- the library launches
  * groups of images that share a kernel configuration).
@@ -135,7 +147,8 @@ RWH_API int rwh_warp_backward(const void* d_src, int src_h, int src_w, int chann
  * d_out: n x channels, element type = the image's for RWH_NEAREST (dst_dtype == src_dtype), float64 for RWH_BILINEAR
  * (dst_dtype RWH_F64) -- the reference's float64 arithmetic operation by operation, bit-identical to numpy's;
  * (bound_h, bound_w): the `h, w` arguments of the reference's call (clipped to the image); flags: RWH_WARP_ZERO_ORIGIN
- * blanks texel (0,0) of the image first, as both interpolators do to the caller's array.  The +1 taps are clamped to the
+ * blanks texel (0,0) of the image first, as both interpolators do to the caller's array.  Sources: as rwh_warp_backward with
+ * RWH_WARP_EXACT (any code RWH_U8 .. RWH_F16, channels 1 .. RWH_WARP_MAX_CHANNELS, the same kernel split).  The +1 taps are clamped to the
  * image where the reference raises IndexError (their weight is 0 there).
  */
 RWH_API int rwh_sample_points(const void* d_img, int src_h, int src_w, int channels, int src_dtype,

@@ -12,7 +12,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "librwh_hip.so")
 
 ABI_VERSION = 5          # RWH_ABI_VERSION of the include/rwh.h this binding was written against
 RWH_U8, RWH_F32, RWH_F64 = 0, 1, 2
-RWH_I8, RWH_U16, RWH_I16, RWH_I32, RWH_I64, RWH_U32, RWH_U64, RWH_F16 = 3, 4, 5, 6, 7, 8, 9, 10    # rwh_stitch_panorama_ex only
+RWH_I8, RWH_U16, RWH_I16, RWH_I32, RWH_I64, RWH_U32, RWH_U64, RWH_F16 = 3, 4, 5, 6, 7, 8, 9, 10    # stitch_ex and the exact warps
+RWH_WARP_MAX_CHANNELS = 64
 RWH_NEAREST, RWH_BILINEAR = 0, 1
 RWH_LOSS = {"fwd": 0, "backward": 1, "reproj": 2}
 RWH_WARP_ZERO_ORIGIN = 1

@@ -1,5 +1,5 @@
-// rwh_cast.h: numpy's element conversions as the reference meets them in stitchPanorama (homography.py:288-338), for the any-dtype
-// compositor (rwh_stitch_any.hip).  Compiles as plain C++ too (no HIP include): the CPU suite builds it with g++ through
+// rwh_cast.h: numpy's element conversions as the reference meets them in stitchPanorama (homography.py:288-338) and in its
+// interpolators (homography.py:123-138), for the any-dtype compositor (rwh_stitch_any.hip) and the any-dtype warp (rwh_warp.hip).  Compiles as plain C++ too (no HIP include): the CPU suite builds it with g++ through
 // tests/cabi/stitch_cast_shim.cpp and checks it against numpy (tests/test_stitch_any_dtype_cpu.py).
 //
 // numpy on x86-64 (numpy 2.x) casts a float to uint8 through a truncating conversion to int32 (cvttsd2si) and keeps the low byte;
@@ -33,5 +33,12 @@ RWH_HD inline uint8_t u8_of_u64(uint64_t v) { return (uint8_t)v; }
 RWH_HD inline float f32_of_i64(int64_t v) { return (float)v; }
 RWH_HD inline float f32_of_u64(uint64_t v) { return (float)v; }
 RWH_HD inline float f32_of_f64(double v) { return (float)v; }     // beyond float32's range: +-inf, NaN stays NaN
+
+// -> float64 (a texel times the float64 weights of bilinear(): numpy promotes every integer, bool and float to float64): exact but
+// for int64 / uint64, which round to nearest even like numpy's conversion
+template <class T> RWH_HD inline double as_f64(T v) { return (double)v; }
+#if defined(__HIPCC__)
+template <> RWH_HD inline double as_f64<_Float16>(_Float16 v) { return (double)(float)v; }   // every float16 is exact in float32
+#endif
 
 }  // namespace rwh_cast

@@ -25,6 +25,17 @@ __device__ __forceinline__ uint32_t ld4(const unsigned char* p) { uint32_t v; __
 
 extern int g_force_warp_shape, g_force_score_hpw, g_score_exact_only, g_force_warp_frames;   // rwh_api.hip (rwh_lab_tune)
 
+// bytes per element of an RWH_U8 .. RWH_F16 code; 0 for an unknown code
+inline int elem_size(int code) {
+    switch (code) {
+        case RWH_U8: case RWH_I8: return 1;
+        case RWH_U16: case RWH_I16: case RWH_F16: return 2;
+        case RWH_F32: case RWH_I32: case RWH_U32: return 4;
+        case RWH_F64: case RWH_I64: case RWH_U64: return 8;
+        default: return 0;
+    }
+}
+
 inline int check_launch() {
     return hipGetLastError() == hipSuccess ? RWH_OK : RWH_E_LAUNCH;
 }

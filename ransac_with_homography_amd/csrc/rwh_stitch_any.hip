@@ -36,8 +36,7 @@ struct AnyArgs {
 };
 
 // element conversions by source type (rwh_cast.h): -> float64 (paste lerps), -> float32 (blend's float32 copies), -> uint8
-template <class T> __device__ __forceinline__ double as_f64(T v) { return (double)v; }
-template <> __device__ __forceinline__ double as_f64<half_t>(half_t v) { return (double)(float)v; }
+using rwh_cast::as_f64;
 template <class T> __device__ __forceinline__ float as_f32(T v) { return (float)v; }
 template <> __device__ __forceinline__ float as_f32<int64_t>(int64_t v) { return rwh_cast::f32_of_i64(v); }
 template <> __device__ __forceinline__ float as_f32<uint64_t>(uint64_t v) { return rwh_cast::f32_of_u64(v); }
@@ -214,16 +213,6 @@ int launch_any(const AnyArgs& a, int t_c, dim3 grid, hipStream_t s) {
         else hipLaunchKernelGGL((stitch_any_kernel<TT, 3, false>), grid, dim3(256), 0, s, a);
     }
     return check_launch();
-}
-
-int elem_size(int code) {
-    switch (code) {
-        case RWH_U8: case RWH_I8: return 1;
-        case RWH_U16: case RWH_I16: case RWH_F16: return 2;
-        case RWH_F32: case RWH_I32: case RWH_U32: return 4;
-        case RWH_F64: case RWH_I64: case RWH_U64: return 8;
-        default: return 0;
-    }
 }
 
 }  // namespace

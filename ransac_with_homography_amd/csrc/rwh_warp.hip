@@ -15,6 +15,7 @@
 //     of output tile rows: vertically adjacent tiles share source rows in one L2;
 //   * no MFMA: there is no dense contraction in this path.
 #include "rwh_common.h"
+#include "rwh_cast.h"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -44,6 +45,7 @@ struct WarpArgs {
     int out_h, out_w;
     int row_begin, rows;   // produce rows [row_begin, row_begin+rows)
     unsigned tiles_x, tiles_y, nblocks, cpx;
+    int channels;          // warp_any only (the other kernels take it as a template argument)
 };
 
 constexpr int PX = 4;        // pixels per lane (uint8 output: 12 / 16 bytes per lane and store)
@@ -85,6 +87,17 @@ __device__ __forceinline__ void project(const WarpArgs& a, double x, double rx, 
     r = fma(fma(-W, r, 1.0), r, r);
     sx = X * r;
     sy = Y * r;
+}
+
+// The exact kernels' source coordinate of output coordinate (x, y), the reference's float64 arithmetic (see warp_exact below).
+// warp_exact, warp_any and index_check_kernel all call this one function: what the warp samples and where rwh_warp_index_check
+// finds the reference's IndexError come from the same operations.
+__device__ __forceinline__ void exact_coord(const WarpArgs& a, double x, double y, double& sx, double& sy) {
+    const double X = fma(a.ih[1], y, a.ih[0] * x) + a.ih[2];
+    const double Y = fma(a.ih[4], y, a.ih[3] * x) + a.ih[5];
+    const double W = fma(a.ih[7], y, a.ih[6] * x) + a.ih[8];
+    sx = X / W;
+    sy = Y / W;
 }
 
 __device__ __forceinline__ float ub(uint32_t v, int byte) { return (float)((v >> (8 * byte)) & 0xffu); }
@@ -243,6 +256,24 @@ __device__ __forceinline__ void load_texel_f64(const unsigned char* img, size_t 
     }
 }
 
+// Bilinear taps of an unmasked float64 source coordinate (homography.py:133-137): astype(int32) truncation, f = z - trunc(z), the +1
+// taps clamped to the image (the reference raises IndexError there, rwh_warp_index_check; their weight is 0 on the last texel).
+struct ExactTaps { int ix, iy, ix1, iy1; double fx, fy, gx, gy; };
+__device__ __forceinline__ ExactTaps exact_taps(double sx, double sy, int src_h, int src_w) {
+    ExactTaps t;
+    t.ix = (int)sx; t.iy = (int)sy;
+    t.fx = sx - (double)t.ix; t.fy = sy - (double)t.iy;
+    t.gx = 1.0 - t.fx; t.gy = 1.0 - t.fy;
+    t.ix1 = min(t.ix + 1, src_w - 1); t.iy1 = min(t.iy + 1, src_h - 1);
+    return t;
+}
+// p00*(1-fx) + p01*fx, p10*(1-fx) + p11*fx, top*(1-fy) + bot*fy: contraction is off, every product and sum rounded, like numpy
+__device__ __forceinline__ double lerp_exact(const ExactTaps& t, double p00, double p01, double p10, double p11) {
+    const double top = p00 * t.gx + p01 * t.fx;
+    const double bot = p10 * t.gx + p11 * t.fx;
+    return top * t.gy + bot * t.fy;
+}
+
 // One sample at the float64 source coordinate (sx, sy), the reference's arithmetic operation by operation (see above).
 template <typename SrcT, int C, typename DstT, int INTERP>
 __device__ __forceinline__ void sample_exact(const unsigned char* simg, size_t img_bytes, int src_h, int src_w, int bound_h, int bound_w,
@@ -266,21 +297,14 @@ __device__ __forceinline__ void sample_exact(const unsigned char* simg, size_t i
         const double bw1 = (double)(bound_w - 1), bh1 = (double)(bound_h - 1);
         const bool valid = (sx >= 0.0) & (sx <= bw1) & (sy >= 0.0) & (sy <= bh1);
         if (valid) {
-            const int ix = (int)sx, iy = (int)sy;
-            const double fx = sx - (double)ix, fy = sy - (double)iy;
-            const double gx = 1.0 - fx, gy = 1.0 - fy;
-            const int ix1 = min(ix + 1, src_w - 1), iy1 = min(iy + 1, src_h - 1);
+            const ExactTaps t = exact_taps(sx, sy, src_h, src_w);
             double p00[C], p01[C], p10[C], p11[C];
-            load_texel_f64<SrcT, C>(simg, img_bytes, src_w, iy, ix, p00);
-            load_texel_f64<SrcT, C>(simg, img_bytes, src_w, iy, ix1, p01);
-            load_texel_f64<SrcT, C>(simg, img_bytes, src_w, iy1, ix, p10);
-            load_texel_f64<SrcT, C>(simg, img_bytes, src_w, iy1, ix1, p11);
+            load_texel_f64<SrcT, C>(simg, img_bytes, src_w, t.iy, t.ix, p00);
+            load_texel_f64<SrcT, C>(simg, img_bytes, src_w, t.iy, t.ix1, p01);
+            load_texel_f64<SrcT, C>(simg, img_bytes, src_w, t.iy1, t.ix, p10);
+            load_texel_f64<SrcT, C>(simg, img_bytes, src_w, t.iy1, t.ix1, p11);
 #pragma unroll
-            for (int k = 0; k < C; ++k) {
-                const double top = p00[k] * gx + p01[k] * fx;   // contraction is off: three roundings, like numpy
-                const double bot = p10[k] * gx + p11[k] * fx;
-                o[k] = top * gy + bot * fy;
-            }
+            for (int k = 0; k < C; ++k) o[k] = lerp_exact(t, p00[k], p01[k], p10[k], p11[k]);
         } else {
 #pragma unroll
             for (int k = 0; k < C; ++k) o[k] = 0.0;
@@ -324,10 +348,8 @@ __global__ __launch_bounds__(256) void warp_exact(const WarpArgs a) {
         const int c = c0 + j;
         if (c >= a.out_w) break;
         const double x = grid_coord(c, a.out_w, a.x0, a.step_x, a.x_last);
-        const double X = fma(a.ih[1], y, a.ih[0] * x) + a.ih[2];
-        const double Y = fma(a.ih[4], y, a.ih[3] * x) + a.ih[5];
-        const double W = fma(a.ih[7], y, a.ih[6] * x) + a.ih[8];
-        const double sx = X / W, sy = Y / W;
+        double sx, sy;
+        exact_coord(a, x, y, sx, sy);
         sample_exact<SrcT, C, DstT, INTERP>(simg, img_bytes, a.src_h, a.src_w, a.bound_h, a.bound_w, sx, sy, drow + j * C);
     }
 }
@@ -341,6 +363,135 @@ int dispatch_exact(const WarpArgs& a, int interp, int dst_dtype, hipStream_t s) 
     if (dst_dtype == RWH_F64) return launch(warp_exact<SrcT, C, double, RWH_BILINEAR>, a, s, "warp_exact", tname<SrcT>(), C, "double", RWH_BILINEAR);
     if (dst_dtype == RWH_U8) return launch(warp_exact<SrcT, C, unsigned char, RWH_BILINEAR>, a, s, "warp_exact", tname<SrcT>(), C, "unsigned char", RWH_BILINEAR);
     return RWH_E_UNSUPPORTED;
+}
+
+// ================================================================================================
+// Any-dtype exact kernel (RWH_WARP_EXACT on every source warp_exact does not take: int8 .. uint64, float16, float64, bool read as
+// uint8, and uint8 / float32 with other than 3 or 4 channels).  warp_exact's coordinates (exact_coord), one lane per output
+// pixel, the channel count a runtime value (1 .. RWH_WARP_MAX_CHANNELS) walked in a loop:
+//   * nearest (homography.py:110-121): texel (yi, xi) copied as raw elements of its size (one instance per size: 1, 2, 4, 8
+//     bytes), so NaN payloads, -0.0 and bool bytes survive; a masked coordinate reads texel (0,0) as the reference's does --
+//     RWH_WARP_ZERO_ORIGIN has blanked its channels 0..2 (and 3 when C == 4), not the ones beyond;
+//   * bilinear (homography.py:131-137): each tap read in its own type and converted to float64 as numpy promotes it
+//     (rwh_cast::as_f64), warp_exact's taps and three-rounding lerp (exact_taps, lerp_exact); a masked coordinate is
+//     interpolated at (0, 0) as in the reference, so non-finite texels next to the origin reach the output as they do there;
+//     a uint8 result is numpy's astype(np.uint8) of the float64 (rwh_cast::u8_of_f64).
+// ================================================================================================
+template <typename E>
+__device__ __forceinline__ void nearest_any(const unsigned char* img, int src_w, int bound_h, int bound_w, int C, double sx, double sy,
+                                            E* out) {
+    int xi = (int)(sx + 0.5), yi = (int)(sy + 0.5);
+    const bool valid = (xi >= 0) & (xi <= bound_w - 1) & (yi >= 0) & (yi <= bound_h - 1) & (sx == sx) & (sy == sy);   // as sample_exact
+    if (!valid) xi = yi = 0;
+    const E* p = reinterpret_cast<const E*>(img) + ((size_t)yi * (size_t)src_w + (size_t)xi) * (size_t)C;
+    for (int k = 0; k < C; ++k) out[k] = p[k];
+}
+
+template <typename T, typename DstT>
+__device__ __forceinline__ void bilinear_any(const unsigned char* img, int src_h, int src_w, int bound_h, int bound_w, int C, double sx,
+                                             double sy, DstT* out) {
+    const bool valid = (sx >= 0.0) & (sx <= (double)(bound_w - 1)) & (sy >= 0.0) & (sy <= (double)(bound_h - 1));
+    if (!valid) sx = sy = 0.0;     // (a NaN coordinate too: the reference raises IndexError there, rwh_warp_index_check)
+    const ExactTaps t = exact_taps(sx, sy, src_h, src_w);
+    const T* r0 = reinterpret_cast<const T*>(img) + (size_t)t.iy * (size_t)src_w * (size_t)C;
+    const T* r1 = reinterpret_cast<const T*>(img) + (size_t)t.iy1 * (size_t)src_w * (size_t)C;
+    const size_t c0 = (size_t)t.ix * (size_t)C, c1 = (size_t)t.ix1 * (size_t)C;
+    for (int k = 0; k < C; ++k) {
+        const double o = lerp_exact(t, rwh_cast::as_f64(r0[c0 + k]), rwh_cast::as_f64(r0[c1 + k]), rwh_cast::as_f64(r1[c0 + k]),
+                                    rwh_cast::as_f64(r1[c1 + k]));
+        if constexpr (sizeof(DstT) == 1) out[k] = rwh_cast::u8_of_f64(o);
+        else out[k] = o;
+    }
+}
+
+template <typename SrcT, typename DstT, int INTERP>
+__global__ __launch_bounds__(256) void warp_any(const WarpArgs a) {
+    unsigned tx, ty, img;
+    if (!decode_tile(a, tx, ty, img)) return;
+    const int rr = (int)ty * TILE_ROWS + (int)(threadIdx.x >> 6);
+    const int c = (int)tx * RWH_WAVE + (int)(threadIdx.x & 63);
+    if (rr >= a.rows || c >= a.out_w) return;
+    const int r = a.row_begin + rr;
+    double sx, sy;
+    exact_coord(a, grid_coord(c, a.out_w, a.x0, a.step_x, a.x_last), grid_coord(r, a.out_h, a.y0, a.step_y, a.y_last), sx, sy);
+    const unsigned char* simg = a.src + (long long)img * a.src_img_stride;
+    DstT* out = reinterpret_cast<DstT*>(a.dst + (long long)img * a.dst_img_stride) +
+                ((size_t)rr * (size_t)a.out_w + (size_t)c) * (size_t)a.channels;
+    if constexpr (INTERP == RWH_NEAREST) nearest_any<SrcT>(simg, a.src_w, a.bound_h, a.bound_w, a.channels, sx, sy, out);
+    else bilinear_any<SrcT, DstT>(simg, a.src_h, a.src_w, a.bound_h, a.bound_w, a.channels, sx, sy, out);
+}
+
+// rwh_sample_points on the any-dtype sources: one thread per point
+template <typename SrcT, typename DstT, int INTERP>
+__global__ __launch_bounds__(256) void sample_points_any(const unsigned char* img, int src_h, int src_w, int bound_h, int bound_w, int C,
+                                                         const double* __restrict__ xs, const double* __restrict__ ys, long long n,
+                                                         DstT* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (INTERP == RWH_NEAREST) nearest_any<SrcT>(img, src_w, bound_h, bound_w, C, xs[i], ys[i], out + i * C);
+    else bilinear_any<SrcT, DstT>(img, src_h, src_w, bound_h, bound_w, C, xs[i], ys[i], out + i * C);
+}
+
+// f(T{}, name of T as the demangled kernel names spell it) for the element type of `code` (a bool plane is RWH_U8); false: unknown code
+template <class F> static bool with_elem(int code, F&& f) {
+    switch (code) {
+        case RWH_U8: f(uint8_t{}, "unsigned char"); return true;
+        case RWH_I8: f(int8_t{}, "signed char"); return true;
+        case RWH_U16: f(uint16_t{}, "unsigned short"); return true;
+        case RWH_I16: f(int16_t{}, "short"); return true;
+        case RWH_I32: f(int32_t{}, "int"); return true;
+        case RWH_U32: f(uint32_t{}, "unsigned int"); return true;
+        case RWH_I64: f(int64_t{}, "long"); return true;
+        case RWH_U64: f(uint64_t{}, "unsigned long"); return true;
+        case RWH_F16: f(_Float16{}, "_Float16"); return true;
+        case RWH_F32: f(float{}, "float"); return true;
+        case RWH_F64: f(double{}, "double"); return true;
+        default: return false;
+    }
+}
+
+// nearest copies elements as unsigned integers of the element size: f(E{}, name)
+template <class F> static void with_raw(int esz, F&& f) {
+    switch (esz) {
+        case 1: f(uint8_t{}, "unsigned char"); break;
+        case 2: f(uint16_t{}, "unsigned short"); break;
+        case 4: f(uint32_t{}, "unsigned int"); break;
+        default: f(uint64_t{}, "unsigned long"); break;
+    }
+}
+
+// channels of texel (0,0) the reference's interpolators blank (homography.py:112-116): 0..2, and 3 only when there are exactly 4
+static int blank_channels(int c) { return c == 4 ? 4 : c < 3 ? c : 3; }
+
+template <typename K>
+static int launch_any(K kernel, const WarpArgs& a, hipStream_t s, const char* src, const char* dst, int interp) {
+    char name[96];
+    snprintf(name, sizeof name, "rwh::warp_any<%s, %s, %d>", src, dst, interp);
+    if (plan_only("%s", name)) return RWH_OK;
+    hipLaunchKernelGGL(kernel, dim3(8u * a.cpx), dim3(256), 0, s, a);
+    return check_launch();
+}
+
+static bool retile(WarpArgs& a, int px);
+
+static int dispatch_any(const WarpArgs& a0, int src_dtype, int interp, int dst_dtype, hipStream_t s) {
+    WarpArgs a = a0;
+    if (!retile(a, 1)) return RWH_E_UNSUPPORTED;
+    int st = RWH_E_UNSUPPORTED;
+    if (interp == RWH_NEAREST) {
+        if (dst_dtype != src_dtype) return RWH_E_UNSUPPORTED;
+        with_raw(elem_size(src_dtype), [&](auto tag, const char* name) {
+            using E = decltype(tag);
+            st = launch_any(warp_any<E, E, RWH_NEAREST>, a, s, name, name, RWH_NEAREST);
+        });
+    } else if (dst_dtype == RWH_F64 || dst_dtype == RWH_U8) {
+        with_elem(src_dtype, [&](auto tag, const char* name) {
+            using T = decltype(tag);
+            st = dst_dtype == RWH_F64 ? launch_any(warp_any<T, double, RWH_BILINEAR>, a, s, name, "double", RWH_BILINEAR)
+                                      : launch_any(warp_any<T, unsigned char, RWH_BILINEAR>, a, s, name, "unsigned char", RWH_BILINEAR);
+        });
+    }
+    return st;
 }
 
 // ---- host side ---------------------------------------------------------------------------------
@@ -674,16 +825,17 @@ extern "C" int rwh_warp_backward(const void* d_src, int src_h, int src_w, int ch
     if (bound_h <= 0 || bound_w <= 0) return RWH_E_INVALID;
     if (interp != RWH_NEAREST && interp != RWH_BILINEAR) return RWH_E_INVALID;
     if (n_h != 1 && n_h != batch) return RWH_E_INVALID;
-    if (channels != 3 && channels != 4) return RWH_E_UNSUPPORTED;
-    if (src_dtype != RWH_U8 && src_dtype != RWH_F32) return RWH_E_UNSUPPORTED;
-    const size_t esz = src_dtype == RWH_U8 ? 1 : 4;
+    // uint8 / float32 with 3 or 4 channels: the kernels below; every other numeric source through the exact kernel only (warp_any)
+    const bool any = !((src_dtype == RWH_U8 || src_dtype == RWH_F32) && (channels == 3 || channels == 4));
+    const size_t esz = (size_t)elem_size(src_dtype);
+    if (any && (!(flags & RWH_WARP_EXACT) || !esz || channels < 1 || channels > RWH_WARP_MAX_CHANNELS)) return RWH_E_UNSUPPORTED;
     if ((size_t)src_h * (size_t)src_w * channels * esz >= (1ull << 32)) return RWH_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
 
     if ((flags & RWH_WARP_ZERO_ORIGIN) && !g_plan_buf) {  // one tiny launch for the whole batch (memsets cost ~4 us each)
         hipLaunchKernelGGL(zero_origin_kernel, dim3((batch + 255) / 256), dim3(256), 0, s,
                            const_cast<unsigned char*>(static_cast<const unsigned char*>(d_src)), (long long)src_image_stride,
-                           batch, (int)(channels * esz));
+                           batch, (int)(blank_channels(channels) * esz));
         if (check_launch() != RWH_OK) return RWH_E_LAUNCH;
     }
 
@@ -737,6 +889,8 @@ extern "C" int rwh_warp_backward(const void* d_src, int src_h, int src_w, int ch
     if (nb >= (1ull << 31) / 8) return RWH_E_UNSUPPORTED;
     a.nblocks = (unsigned)nb;
     a.cpx = (a.nblocks + 7u) / 8u;
+    a.channels = channels;
+    if (any) return dispatch_any(a, src_dtype, interp, dst_dtype, s);
 
     // nearest neighbour, RGB u8: one kernel for the exact and the default mode -- it is bit-exact by construction
     if (src_dtype == RWH_U8 && channels == 3 && interp == RWH_NEAREST && dst_dtype == RWH_U8 && a.out_w >= 128 &&
@@ -772,8 +926,8 @@ extern "C" int rwh_warp_plan(int src_h, int src_w, int channels, int src_dtype, 
     kernel_name[0] = 0;
     rwh::g_plan_buf = kernel_name; rwh::g_plan_len = name_len;
     static unsigned char dummy[16];   // never dereferenced: every launch site returns before touching the device
-    const int64_t src_stride = (int64_t)src_h * src_w * channels * (src_dtype == RWH_U8 ? 1 : 4);
-    const int64_t dst_stride = (int64_t)(row_end - row_begin) * out_w * channels * (dst_dtype == RWH_U8 ? 1 : dst_dtype == RWH_F32 ? 4 : 8);
+    const int64_t src_stride = (int64_t)src_h * src_w * channels * rwh::elem_size(src_dtype);
+    const int64_t dst_stride = (int64_t)(row_end - row_begin) * out_w * channels * rwh::elem_size(dst_dtype);
     const int st = rwh_warp_backward(dummy, src_h, src_w, channels, src_dtype, src_stride, batch, inv_h, n_h, x0, step_x, x_last, y0,
                                      step_y, y_last, out_h, out_w, bound_h, bound_w, interp, dummy, dst_dtype, dst_stride, row_begin,
                                      row_end, flags, nullptr);
@@ -793,10 +947,8 @@ __global__ __launch_bounds__(256) void index_check_kernel(const WarpArgs a, int 
     if (i >= (long long)a.out_h * a.out_w) return;
     const int r = (int)(i / a.out_w), c = (int)(i - (long long)r * a.out_w);
     const double y = grid_coord(r, a.out_h, a.y0, a.step_y, a.y_last), x = grid_coord(c, a.out_w, a.x0, a.step_x, a.x_last);
-    const double X = fma(a.ih[1], y, a.ih[0] * x) + a.ih[2];
-    const double Y = fma(a.ih[4], y, a.ih[3] * x) + a.ih[5];
-    const double W = fma(a.ih[7], y, a.ih[6] * x) + a.ih[8];
-    const double sx = X / W, sy = Y / W;
+    double sx, sy;
+    exact_coord(a, x, y, sx, sy);
     int bits = 0;
     if (interp == RWH_NEAREST) {                       // homography.py:110-119: the mask is on the integers, NaN -> INT_MIN is masked
         const int xi = (int)(sx + 0.5), yi = (int)(sy + 0.5);
@@ -828,6 +980,27 @@ static int sample_dispatch(const unsigned char* img, int src_h, int src_w, int b
     }
     return check_launch();
 }
+
+static int sample_dispatch_any(const unsigned char* img, int src_h, int src_w, int bound_h, int bound_w, int C, const double* xs,
+                               const double* ys, long long n, int src_dtype, int interp, void* out, int dst_dtype, hipStream_t s) {
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (interp == RWH_NEAREST) {
+        if (dst_dtype != src_dtype) return RWH_E_UNSUPPORTED;
+        with_raw(elem_size(src_dtype), [&](auto tag, const char*) {
+            using E = decltype(tag);
+            hipLaunchKernelGGL((sample_points_any<E, E, RWH_NEAREST>), grid, block, 0, s, img, src_h, src_w, bound_h, bound_w, C, xs, ys, n,
+                               static_cast<E*>(out));
+        });
+    } else {
+        if (dst_dtype != RWH_F64) return RWH_E_UNSUPPORTED;
+        with_elem(src_dtype, [&](auto tag, const char*) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL((sample_points_any<T, double, RWH_BILINEAR>), grid, block, 0, s, img, src_h, src_w, bound_h, bound_w, C, xs,
+                               ys, n, static_cast<double*>(out));
+        });
+    }
+    return check_launch();
+}
 }  // namespace rwh
 
 extern "C" int rwh_sample_points(const void* d_img, int src_h, int src_w, int channels, int src_dtype, const double* d_x, const double* d_y,
@@ -835,19 +1008,21 @@ extern "C" int rwh_sample_points(const void* d_img, int src_h, int src_w, int ch
     using namespace rwh;
     if (!d_img || !d_x || !d_y || !d_out || n < 0 || src_h < 1 || src_w < 1 || bound_h <= 0 || bound_w <= 0) return RWH_E_INVALID;
     if (interp != RWH_NEAREST && interp != RWH_BILINEAR) return RWH_E_INVALID;
-    if (channels != 3 && channels != 4) return RWH_E_UNSUPPORTED;
-    if (src_dtype != RWH_U8 && src_dtype != RWH_F32) return RWH_E_UNSUPPORTED;
+    // uint8 / float32 with 3 or 4 channels: sample_points_kernel; every other numeric source: sample_points_any
+    const bool any = !((src_dtype == RWH_U8 || src_dtype == RWH_F32) && (channels == 3 || channels == 4));
+    const size_t esz = (size_t)elem_size(src_dtype);
+    if (any && (!esz || channels < 1 || channels > RWH_WARP_MAX_CHANNELS)) return RWH_E_UNSUPPORTED;
     if (n == 0) return RWH_OK;
     if (n > (1ll << 31) * 255) return RWH_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t esz = src_dtype == RWH_U8 ? 1 : 4;
     if (flags & RWH_WARP_ZERO_ORIGIN) {
         hipLaunchKernelGGL(zero_origin_kernel, dim3(1), dim3(64), 0, s, const_cast<unsigned char*>(static_cast<const unsigned char*>(d_img)),
-                           0ll, 1, (int)(channels * esz));
+                           0ll, 1, (int)(blank_channels(channels) * esz));
         if (check_launch() != RWH_OK) return RWH_E_LAUNCH;
     }
     const unsigned char* img = static_cast<const unsigned char*>(d_img);
     const int bh = bound_h < src_h ? bound_h : src_h, bw = bound_w < src_w ? bound_w : src_w;
+    if (any) return sample_dispatch_any(img, src_h, src_w, bh, bw, channels, d_x, d_y, n, src_dtype, interp, d_out, dst_dtype, s);
     if (src_dtype == RWH_U8)
         return channels == 3 ? sample_dispatch<unsigned char, 3>(img, src_h, src_w, bh, bw, d_x, d_y, n, interp, d_out, dst_dtype, s)
                              : sample_dispatch<unsigned char, 4>(img, src_h, src_w, bh, bw, d_x, d_y, n, interp, d_out, dst_dtype, s);

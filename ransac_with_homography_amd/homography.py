@@ -23,6 +23,16 @@ Documented divergences from the reference:
     float64-derived weights (<= 1e-4 relative to the reference's float64 blend, typically 3e-7) and
     uint8 results can differ by 1 LSB where the float64 value sits within ~1e-5 of an integer; with the
     exact kernel (numpy arrays in, the default) results are bit-identical to the reference's;
+  * numpy images of every numeric dtype and 3 .. 64 channels are warped in their own dtype (uint8 / float32 with 3 or 4 channels by
+    the exact kernel above, every other one by the any-dtype exact kernel): 'nn' copies texels bit for bit, 'bilinear' converts
+    each tap to float64 as numpy does.  A NaN that the bilinear arithmetic produces (inf * 0, inf - inf) is NaN here too, but
+    with the GPU's sign and payload (x86 gives a negative NaN); every other value is bit-identical.  1 or 2 channels: the
+    reference's IndexError after channel 0 (and 1) of texel (0,0) is zeroed; non-numeric dtypes (complex, longdouble, object,
+    strings, datetimes): NotImplementedError, before anything is touched;
+  * the exact kernel of uint8 / float32 images with 3 or 4 channels returns 0 for a bilinear pixel outside the bounds, where the
+    reference interpolates at (0, 0): the two differ when a texel next to the origin is not finite (0 * inf).  Its uint8 output
+    (transformImage) converts through a saturating int32 cast: float32 values beyond int32 give 255 / 0 where numpy gives 0.
+    The any-dtype kernel does both as the reference does;
   * `cylindericlMap` / `cylindricalWarp` / `cylindericalTransform` (dead code in
     the reference, needs OpenCV) are not provided beyond an import-compatible stub.
 """
@@ -139,7 +149,7 @@ def _is_tensor(x):
 
 def _blank_origin(img):
     """Mirror homography.py:112-116 / 126-130 on the caller's HOST array (the kernel does the
-    same to the device copy): channels 0..2, and 3 when there are exactly 4."""
+    same to the device copy): channels 0..2, and 3 when there are exactly 4 (not beyond: 5+ channels keep channel 3 on)."""
     img[0, 0, 0] = 0
     img[0, 0, 1] = 0
     img[0, 0, 2] = 0
@@ -147,8 +157,9 @@ def _blank_origin(img):
         img[0, 0, 3] = 0
 
 
-def _to_device(img, host=None):
-    """-> (GPU tensor [H,W,C] uint8|float32, was_numpy, result dtype for nn)."""
+def _to_device(img, host):
+    """-> (GPU tensor [H,W,C], was_numpy, result dtype for nn).  Tensors in: uint8 | float32 (other dtypes are cast to float32);
+    numpy arrays in: `host`, what _host_src returned for this image, uploaded as it is."""
     import torch
     dev = _lib.require_gpu()
     if _is_tensor(img):
@@ -158,18 +169,47 @@ def _to_device(img, host=None):
         if t.dtype not in (torch.uint8, torch.float32):
             t = t.to(torch.float32)
         return t.contiguous(), False, None
-    src, np_dtype = host if host is not None else _host_src(img)      # (`host`: what _host_src already returned for this image)
+    src, np_dtype = host
     return _xfer.to_device(src, dev), True, np_dtype
 
 
-def _host_src(img):
-    """numpy image -> (the uint8 / float32 array the kernels read, the caller's dtype)."""
+def _host_src(img, exact):
+    """numpy image -> (the array the kernels read, the caller's dtype); no device work.
+
+    exact (the float64 kernels): uint8 / float32 images with 3 or 4 channels as they are; every other numeric dtype (bool read as
+    uint8, int8 .. int64, uint16 .. uint64, float16, float64) and channel count 3 .. RWH_WARP_MAX_CHANNELS in its own type, for the
+    any-dtype kernel.  1 or 2 channels: the reference's interpolators blank channel 0 (and 1) of the caller's texel (0,0) and then
+    raise IndexError at the next channel (homography.py:112-114 / 126-128); so does this.  Non-numeric dtypes (complex,
+    longdouble, object, ...) raise NotImplementedError before anything is touched.
+    Not exact (RWH_EXACT=0): the fast kernels' uint8 / float32 with 3 or 4 channels, other dtypes cast to float32."""
     a = np.asarray(img)
     if a.ndim != 3:
         raise ValueError("not enough values to unpack (expected 3, got %d)" % a.ndim)  # img.shape unpack
-    if a.shape[2] not in (3, 4):
-        raise IndexError("index out of bounds: the warp supports 3 or 4 channels")
-    return (a if a.dtype in (np.uint8, np.float32) else a.astype(np.float32)), a.dtype
+    if not exact:
+        if a.shape[2] not in (3, 4):
+            raise IndexError("index out of bounds: the warp supports 3 or 4 channels")
+        return (a if a.dtype in (np.uint8, np.float32) else a.astype(np.float32)), a.dtype
+    native = a.dtype.newbyteorder("=") if a.dtype.kind in "biuf" else a.dtype
+    if native not in _STITCH_NP:
+        raise NotImplementedError("warp: %s images are not warped here: the exact kernels take numeric images (bool, int8 .. int64, "
+                                  "uint8 .. uint64, float16 / 32 / 64)" % a.dtype)
+    c = a.shape[2]
+    if c < 3:
+        for k in range(c):
+            img[0, 0, k] = 0
+        raise IndexError("index %d is out of bounds for axis 2 with size %d" % (c, c))
+    if c > _lib.RWH_WARP_MAX_CHANNELS:
+        raise NotImplementedError("warp: %d channels; the exact kernels take up to %d" % (c, _lib.RWH_WARP_MAX_CHANNELS))
+    if a.dtype in (np.uint8, np.float32) and c in (3, 4):
+        return a, a.dtype
+    if native != a.dtype:
+        a = a.astype(native)
+    return a.view(_STITCH_NP[native]), a.dtype
+
+
+def _torch_dtype(np_dtype):
+    import torch
+    return torch.from_numpy(np.empty(0, np_dtype)).dtype
 
 
 def _warp(img, H, grid, bound_hw, convert, u8_out):
@@ -178,12 +218,12 @@ def _warp(img, H, grid, bound_hw, convert, u8_out):
     if convert not in kernels.INTERP:
         raise KeyError(convert)  # convertfunc[convert], homography.py:179 / 208
     inv_h = np.linalg.inv(np.asarray(H, dtype=np.float64))  # homography.py:172 / 203 (raises LinAlgError)
-    host = None
-    if not _is_tensor(img) and PIPELINE_MIN_BYTES is not None:
+    host = None if _is_tensor(img) else _host_src(img, True if EXACT is None else bool(EXACT))
+    if host is not None and PIPELINE_MIN_BYTES is not None:
         # a large host array through the exact kernels: upload, kernel by output-row tiles and download overlapped (_warp_pipelined)
-        a, np_dtype = host = _host_src(img)
+        a, np_dtype = host
         exact = True if EXACT is None else bool(EXACT)
-        t_dtype = torch.uint8 if a.dtype == np.uint8 else torch.float32
+        t_dtype = _torch_dtype(a.dtype)
         out_dtype = t_dtype if convert == "nn" else (torch.uint8 if u8_out else torch.float64 if exact else torch.float32)
         out_bytes = grid.out_h * grid.out_w * a.shape[2] * torch.empty(0, dtype=out_dtype).element_size()
         # (the result of a pipelined call is ONE page-locked block: capped like _xfer.to_host's, beyond it the plain path)
@@ -279,6 +319,7 @@ def _sample(z_t, img, h, w, mh, mw, convert):
     arithmetic, bit-identical results).  Like the reference it blanks texel (0,0) of the caller's image and, for
     'bilinear', writes 0 into the masked columns of the caller's z_t (homography.py:131-132: `z_t = z_t.T` is a view)."""
     import torch
+    host = None if _is_tensor(img) else _host_src(img, True)     # (1 or 2 channels: the reference's IndexError, before z_t is touched)
     dev = _lib.require_gpu()
     chn = img.shape[2]
     if _is_tensor(z_t):
@@ -287,7 +328,7 @@ def _sample(z_t, img, h, w, mh, mw, convert):
         z_t = np.asarray(z_t)
         zx = torch.from_numpy(np.ascontiguousarray(z_t[0], dtype=np.float64)).to(dev)
         zy = torch.from_numpy(np.ascontiguousarray(z_t[1], dtype=np.float64)).to(dev)
-    src, was_numpy, np_dtype = _to_device(img)
+    src, was_numpy, np_dtype = _to_device(img, host)
     out = kernels.sample_points(src, zx, zy, (h, w), convert, zero_origin=True).reshape(mh, mw, chn)
     if convert == 'bilinear' and not _is_tensor(z_t) and z_t.dtype.kind == 'f':
         mask = (z_t[0] > w - 1) | (z_t[0] < 0) | (z_t[1] > h - 1) | (z_t[1] < 0)
@@ -581,11 +622,11 @@ def _stitch_pipelined(imgQ, imgT, inv_h, mx, my, wt, ht, tsx, tsy, qsx, qsy, fh,
 
 def _warp_pipelined(a, inv_h, grid, bound_hw, convert, out_dtype, exact, dev):
     """One warp from a host array through `_pipeline`: output row tiles (rwh_warp_backward's row_begin / row_end), a tile as soon
-    as the source rows it samples have arrived.  a: contiguous uint8 / float32 H x W x C host array.  -> host array."""
+    as the source rows it samples have arrived.  a: contiguous H x W x C host array as _host_src returns it.  -> host array."""
     import torch
     flat = a.reshape(-1).view(np.uint8)
     h, w, c = (int(v) for v in a.shape)
-    t_dtype = torch.uint8 if a.dtype == np.uint8 else torch.float32
+    t_dtype = _torch_dtype(a.dtype)
     s_flat = torch.empty(flat.size, dtype=torch.uint8, device=dev)
     src = s_flat.view(t_dtype).view(h, w, c)
     oh, ow = grid.out_h, grid.out_w

@@ -15,6 +15,11 @@ from . import _lib
 from ._lib import (RWH_BILINEAR, RWH_F32, RWH_F64, RWH_LOSS, RWH_NEAREST, RWH_U8, RWH_WARP_EXACT, RWH_WARP_ZERO_ORIGIN, check)
 
 _DTYPE = {torch.uint8: RWH_U8, torch.float32: RWH_F32, torch.float64: RWH_F64}
+# element type codes of the exact warps (exact=True, sample_points) and rwh_stitch_panorama_ex (a bool plane is read as uint8: numpy
+# and torch store it as one 0 / 1 byte)
+STITCH_DTYPE = {torch.uint8: RWH_U8, torch.bool: RWH_U8, torch.int8: _lib.RWH_I8, torch.uint16: _lib.RWH_U16, torch.int16: _lib.RWH_I16,
+                torch.int32: _lib.RWH_I32, torch.uint32: _lib.RWH_U32, torch.int64: _lib.RWH_I64, torch.uint64: _lib.RWH_U64,
+                torch.float16: _lib.RWH_F16, torch.float32: RWH_F32, torch.float64: RWH_F64}
 INTERP = {"nn": RWH_NEAREST, "bilinear": RWH_BILINEAR}
 
 
@@ -48,18 +53,19 @@ class Grid:
 
 
 def warp_backward(src, inv_h, grid, bound_hw, interp, out_dtype, zero_origin=True, rows=None, out=None, exact=False):
-    """Launch K3.  `src`: [B,H,W,C] or [H,W,C] uint8/float32 GPU tensor.
+    """Launch K3.  `src`: [B,H,W,C] or [H,W,C] uint8/float32 GPU tensor (with exact=True: any dtype of STITCH_DTYPE, C 1..64).
     Returns a tensor [B,rows,out_w,C] (or without B) of `out_dtype` holding
     output rows `rows=(begin,end)` (default: all).  `inv_h`: inv(H) 3x3 for the whole batch, or [B,3,3] with one
     inverse per image (same output grid for all).  `exact=True` selects the float64 kernel that
-    reproduces the reference's arithmetic bit for bit (out_dtype float64 / uint8 for bilinear)."""
+    reproduces the reference's arithmetic bit for bit (out_dtype float64 / uint8 for bilinear, src.dtype for nn)."""
     lib = _lib.load()
     _dev_check(src)
     squeeze = src.dim() == 3
     if squeeze:
         src = src.unsqueeze(0)
     B, H, W, C = src.shape
-    if src.dtype not in _DTYPE or out_dtype not in _DTYPE:
+    codes = STITCH_DTYPE if exact else _DTYPE
+    if src.dtype not in codes or out_dtype not in codes:
         raise ValueError("unsupported image dtype")
     r0, r1 = (0, grid.out_h) if rows is None else rows
     if out is None:
@@ -72,18 +78,18 @@ def warp_backward(src, inv_h, grid, bound_hw, interp, out_dtype, zero_origin=Tru
     assert ih.size == 9 * n_h and n_h in (1, B), "inv_h: 3x3, or one 3x3 per image of the batch"
     ih = ih.reshape(9 * n_h)
     st = lib.rwh_warp_backward(
-        _ptr(src), H, W, C, _DTYPE[src.dtype], src.stride(0) * src.element_size(), B,
+        _ptr(src), H, W, C, codes[src.dtype], src.stride(0) * src.element_size(), B,
         ih.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n_h,
         grid.x0, grid.step_x, grid.x_last, grid.y0, grid.step_y, grid.y_last,
         grid.out_h, grid.out_w, int(bound_hw[0]), int(bound_hw[1]), INTERP[interp],
-        _ptr(out), _DTYPE[out_dtype], (r1 - r0) * grid.out_w * C * out.element_size(),
+        _ptr(out), codes[out_dtype], (r1 - r0) * grid.out_w * C * out.element_size(),
         r0, r1, (RWH_WARP_ZERO_ORIGIN if zero_origin else 0) | (RWH_WARP_EXACT if exact else 0), _lib.stream_ptr())
     check(st, "rwh_warp_backward")
     return out[0] if squeeze else out
 
 
 def sample_points(img, xs, ys, bound_hw, interp, zero_origin=True):
-    """Launch the interpolator on precomputed coordinates (rwh_sample_points): img [H,W,C] uint8|float32 GPU tensor, xs / ys
+    """Launch the interpolator on precomputed coordinates (rwh_sample_points): img [H,W,C] GPU tensor of a STITCH_DTYPE type, xs / ys
     [N] float64 GPU tensors -> [N, C] (image dtype for 'nn', float64 for 'bilinear')."""
     lib = _lib.load()
     _dev_check(img, xs, ys)
@@ -92,8 +98,8 @@ def sample_points(img, xs, ys, bound_hw, interp, zero_origin=True):
     n = xs.numel()
     out_dtype = img.dtype if interp == "nn" else torch.float64
     out = torch.empty((n, C), dtype=out_dtype, device=img.device)
-    check(lib.rwh_sample_points(_ptr(img), H, W, C, _DTYPE[img.dtype], _ptr(xs), _ptr(ys), n, int(bound_hw[0]), int(bound_hw[1]),
-                                INTERP[interp], _ptr(out), _DTYPE[out_dtype], RWH_WARP_ZERO_ORIGIN if zero_origin else 0,
+    check(lib.rwh_sample_points(_ptr(img), H, W, C, STITCH_DTYPE[img.dtype], _ptr(xs), _ptr(ys), n, int(bound_hw[0]), int(bound_hw[1]),
+                                INTERP[interp], _ptr(out), STITCH_DTYPE[out_dtype], RWH_WARP_ZERO_ORIGIN if zero_origin else 0,
                                 _lib.stream_ptr()), "rwh_sample_points")
     return out
 
@@ -129,9 +135,10 @@ def warp_plan(src_shape, src_dtype, inv_h, grid, bound_hw, interp, out_dtype, ro
     n_h = 1 if ih.size == 9 else ih.size // 9
     r0, r1 = (0, grid.out_h) if rows is None else rows
     buf = ctypes.create_string_buffer(128)
-    check(lib.rwh_warp_plan(H, W, C, _DTYPE[src_dtype], B, ih.reshape(-1).ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n_h,
+    codes = STITCH_DTYPE if exact else _DTYPE
+    check(lib.rwh_warp_plan(H, W, C, codes[src_dtype], B, ih.reshape(-1).ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n_h,
                             grid.x0, grid.step_x, grid.x_last, grid.y0, grid.step_y, grid.y_last, grid.out_h, grid.out_w,
-                            int(bound_hw[0]), int(bound_hw[1]), INTERP[interp], _DTYPE[out_dtype], r0, r1,
+                            int(bound_hw[0]), int(bound_hw[1]), INTERP[interp], codes[out_dtype], r0, r1,
                             RWH_WARP_EXACT if exact else 0, buf, 128), "rwh_warp_plan")
     return buf.value.decode()
 
@@ -427,11 +434,6 @@ def stitch_panorama_rows(img_t, img_q, inv_h, grid_origin, warp_wh, t_origin, q_
                                        int(q_origin[1]), fh, fw, int(blend), float(rate), _ptr(out), int(rows[0]), int(rows[1]),
                                        RWH_WARP_ZERO_ORIGIN if zero_origin else 0, _lib.stream_ptr()), "rwh_stitch_panorama_rows")
 
-
-# element type codes of rwh_stitch_panorama_ex (a bool plane is read as uint8: numpy and torch store it as one 0 / 1 byte)
-STITCH_DTYPE = {torch.uint8: RWH_U8, torch.bool: RWH_U8, torch.int8: _lib.RWH_I8, torch.uint16: _lib.RWH_U16, torch.int16: _lib.RWH_I16,
-                torch.int32: _lib.RWH_I32, torch.uint32: _lib.RWH_U32, torch.int64: _lib.RWH_I64, torch.uint64: _lib.RWH_U64,
-                torch.float16: _lib.RWH_F16, torch.float32: RWH_F32, torch.float64: RWH_F64}
 
 
 def stitch_panorama_ex(img_t, img_q, inv_h, grid_origin, warp_wh, t_origin, q_origin, canvas_hw, blend, rate, zero_origin=True,
