@@ -25,15 +25,51 @@ __device__ __forceinline__ uint32_t ld4(const unsigned char* p) { uint32_t v; __
 
 extern int g_force_warp_shape, g_force_score_hpw, g_score_exact_only, g_force_warp_frames;   // rwh_api.hip (rwh_lab_tune)
 
+// The element types of image planes, one row each: C++ type, its RWH_* code (rwh.h; a bool plane is RWH_U8) and the name the
+// demangled kernel names spell for it.  elem<T>, with_elem and elem_size below are all made from this one list.
+// RWH_ELSE marks the type an unknown code reads as in device code, where the code was validated on the host before the launch.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RWH_ELSE default:
+#else
+#define RWH_ELSE
+#endif
+#define RWH_ELEM_TYPES(X)                                                                                                          \
+    X(uint8_t, RWH_U8, "unsigned char", ) X(int8_t, RWH_I8, "signed char", ) X(uint16_t, RWH_U16, "unsigned short", )              \
+    X(int16_t, RWH_I16, "short", ) X(int32_t, RWH_I32, "int", ) X(uint32_t, RWH_U32, "unsigned int", ) X(int64_t, RWH_I64, "long", ) \
+    X(uint64_t, RWH_U64, "unsigned long", ) X(_Float16, RWH_F16, "_Float16", ) X(float, RWH_F32, "float", )                        \
+    X(double, RWH_F64, "double", RWH_ELSE)
+
+template <class T> struct elem;
+#define RWH_X(T, CODE, NAME, ELSE) template <> struct elem<T> { static constexpr int dtype = CODE; static constexpr const char* name = NAME; };
+RWH_ELEM_TYPES(RWH_X)
+#undef RWH_X
+
+// f(T{}, elem<T>::name) with T the element type of `code` (uniform across a launch: a scalar branch in device code).
+// false, and f not called: an unknown code, on the host.
+template <class F> __host__ __device__ __forceinline__ bool with_elem(int code, F&& f) {
+    switch (code) {
+#define RWH_X(T, CODE, NAME, ELSE) ELSE case CODE: f(T{}, NAME); return true;
+        RWH_ELEM_TYPES(RWH_X)
+#undef RWH_X
+    }
+    return false;
+}
+
+// the same for the unsigned integer of `esz` bytes (nearest neighbour copies elements as raw bits)
+template <class F> void with_raw(int esz, F&& f) {
+    switch (esz) {
+        case 1: f(uint8_t{}, elem<uint8_t>::name); break;
+        case 2: f(uint16_t{}, elem<uint16_t>::name); break;
+        case 4: f(uint32_t{}, elem<uint32_t>::name); break;
+        default: f(uint64_t{}, elem<uint64_t>::name); break;
+    }
+}
+
 // bytes per element of an RWH_U8 .. RWH_F16 code; 0 for an unknown code
 inline int elem_size(int code) {
-    switch (code) {
-        case RWH_U8: case RWH_I8: return 1;
-        case RWH_U16: case RWH_I16: case RWH_F16: return 2;
-        case RWH_F32: case RWH_I32: case RWH_U32: return 4;
-        case RWH_F64: case RWH_I64: case RWH_U64: return 8;
-        default: return 0;
-    }
+    int n = 0;
+    with_elem(code, [&](auto tag, const char*) { n = (int)sizeof(tag); });
+    return n;
 }
 
 inline int check_launch() {

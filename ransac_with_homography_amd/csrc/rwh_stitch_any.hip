@@ -7,8 +7,8 @@
 //   blend  -- addAlpha's float32 copy of imgT (C_T + 1 channels) is warped in float64; imgQ enters as float32; the float32 canvas
 //             is cast to uint8.  With C_T == 4 the weight of imgT is its own channel 3, warped (img_t[:, :, 3:4] of the 5-channel
 //             warp); bilinear() blanks channels 0..2 of texel (0,0) of the 5-channel copy, not channel 3.
-// Texels are read in their own type (one switch on the dtype code per launch: one instance per imgT type), imgQ through a
-// uniform switch per pixel.  Four canvas pixels per lane, one 12- or 16-byte store per lane, as stitch_kernel.
+// Texels are read in their own type (with_elem on the dtype code per launch: one instance per imgT type), imgQ through the
+// same switch per pixel, uniform across the launch (a scalar branch).  Four canvas pixels per lane, one 12- or 16-byte store per lane, as stitch_kernel.
 #include "rwh_common.h"
 #include "rwh_cast.h"
 
@@ -55,28 +55,11 @@ template <class T, int C> __device__ __forceinline__ Texel<T, C> ld_texel(const 
     return t;
 }
 
-// f(T{}) with T the element type of `code` (uniform across the launch: a scalar branch)
-template <class F> __device__ __forceinline__ void with_type(int code, F&& f) {
-    switch (code) {
-        case RWH_U8: f(uint8_t{}); break;
-        case RWH_I8: f(int8_t{}); break;
-        case RWH_U16: f(uint16_t{}); break;
-        case RWH_I16: f(int16_t{}); break;
-        case RWH_I32: f(int32_t{}); break;
-        case RWH_U32: f(uint32_t{}); break;
-        case RWH_I64: f(int64_t{}); break;
-        case RWH_U64: f(uint64_t{}); break;
-        case RWH_F16: f(half_t{}); break;
-        case RWH_F32: f(float{}); break;
-        default: f(double{}); break;
-    }
-}
-
 // imgQ's pixel: channel k of the canvas takes imgQ's channel k, or channel 0 when imgQ has 1 channel (numpy broadcasting)
 template <int CT>
 __device__ __forceinline__ uint32_t q_bytes(const AnyArgs& a, size_t pix) {      // paste: uint8, 0x(AA)BBGGRR
     uint32_t out = 0u;
-    with_type(a.q_dtype, [&](auto tag) {
+    with_elem(a.q_dtype, [&](auto tag, const char*) {
         using T = decltype(tag);
         const T* p = reinterpret_cast<const T*>(a.src_q) + pix * a.q_c;
 #pragma unroll
@@ -85,7 +68,7 @@ __device__ __forceinline__ uint32_t q_bytes(const AnyArgs& a, size_t pix) {     
     return out;
 }
 __device__ __forceinline__ void q_floats(const AnyArgs& a, size_t pix, float q[3]) {   // blend: imgQ[:, :, :3].astype(np.float32)
-    with_type(a.q_dtype, [&](auto tag) {
+    with_elem(a.q_dtype, [&](auto tag, const char*) {
         using T = decltype(tag);
         const T* p = reinterpret_cast<const T*>(a.src_q) + pix * a.q_c;
 #pragma unroll
@@ -252,17 +235,7 @@ extern "C" int rwh_stitch_panorama_ex(const void* d_img_t, int t_h, int t_w, int
     a.alpha_q_in = blend >= 2 ? 1.0f : (float)(1 + 1e-10 - rate);
     a.alpha_q_out = (float)1e-10;
     const dim3 grid((canvas_w + 64 * SA_PX - 1) / (64 * SA_PX), (row_end - row_begin + 3) / 4);
-    switch (t_dtype) {
-        case RWH_U8: return launch_any<uint8_t>(a, t_c, grid, s);
-        case RWH_I8: return launch_any<int8_t>(a, t_c, grid, s);
-        case RWH_U16: return launch_any<uint16_t>(a, t_c, grid, s);
-        case RWH_I16: return launch_any<int16_t>(a, t_c, grid, s);
-        case RWH_I32: return launch_any<int32_t>(a, t_c, grid, s);
-        case RWH_U32: return launch_any<uint32_t>(a, t_c, grid, s);
-        case RWH_I64: return launch_any<int64_t>(a, t_c, grid, s);
-        case RWH_U64: return launch_any<uint64_t>(a, t_c, grid, s);
-        case RWH_F16: return launch_any<half_t>(a, t_c, grid, s);
-        case RWH_F32: return launch_any<float>(a, t_c, grid, s);
-        default: return launch_any<double>(a, t_c, grid, s);
-    }
+    int st = RWH_E_INVALID;
+    with_elem(t_dtype, [&](auto tag, const char*) { st = launch_any<decltype(tag)>(a, t_c, grid, s); });
+    return st;
 }

@@ -18,6 +18,7 @@
 #include "rwh_cast.h"
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 #include "rwh_warp_rgb8.h"
 
@@ -27,12 +28,30 @@ namespace rwh {
 // would have launched (the names are the demangled kernel names rocprofv3 prints).
 static thread_local char* g_plan_buf = nullptr;
 static thread_local int g_plan_len = 0;
-static bool plan_only(const char* fmt, const char* a = "", int b = 0, const char* c = "", int d = 0) {
+static bool plan_only(const char* name) {
     if (!g_plan_buf) return false;
-    if (g_plan_buf[0] == 0) snprintf(g_plan_buf, (size_t)g_plan_len, fmt, a, b, c, d);   // the first launch = the dominant kernel
+    if (g_plan_buf[0] == 0) snprintf(g_plan_buf, (size_t)g_plan_len, "%s", name);   // the first launch = the dominant kernel
     return true;
 }
-template <typename T> constexpr const char* tname() { return sizeof(T) == 1 ? "unsigned char" : sizeof(T) == 4 ? "float" : "double"; }
+
+// A kernel instance together with its name: every dispatch below selects one of these, once, and launches (or plans) what it got.
+// The pick_* functions next to each kernel family are the only places that spell a kernel name, from the template arguments of the
+// instance they return.
+template <class... A> struct Kernel {
+    void (*fn)(A...);
+    char name[96];
+};
+template <class... A, class... P> static Kernel<A...> named(void (*fn)(A...), const char* fmt, P... p) {
+    Kernel<A...> k{fn, {}};
+    snprintf(k.name, sizeof k.name, fmt, p...);
+    return k;
+}
+// One launch on the XCD-remapped block grid (8 * cpx blocks of 256 threads); under rwh_warp_plan: the name, and no launch.
+template <class... A> static int launch(const Kernel<A...>& k, unsigned cpx, hipStream_t s, const A&... args) {
+    if (plan_only(k.name)) return RWH_OK;
+    hipLaunchKernelGGL(k.fn, dim3(8u * cpx), dim3(256), 0, s, args...);
+    return check_launch();
+}
 
 struct WarpArgs {
     const unsigned char* src;
@@ -53,10 +72,6 @@ constexpr int PX = 4;        // pixels per lane (uint8 output: 12 / 16 bytes per
 // stores 64 consecutive pixels with one instruction, and four times as many waves are there to hide the gathers
 template <typename DstT, int C> constexpr int generic_px() { return sizeof(DstT) == 1 ? PX : 1; }   // (uint8 RGBA at 1 px per lane: 23 % slower)
 constexpr int TILE_ROWS = 4; // waves per block, one output row each
-
-template <typename T> struct elem;
-template <> struct elem<unsigned char> { static constexpr int dtype = RWH_U8; };
-template <> struct elem<float> { static constexpr int dtype = RWH_F32; };
 
 // ---- block -> tile decode with XCD-contiguous remap -------------------------------------------
 __device__ __forceinline__ bool decode_tile(const WarpArgs& a, unsigned& tx, unsigned& ty, unsigned& img) {
@@ -222,7 +237,9 @@ __global__ __launch_bounds__(256) void warp_generic(const WarpArgs a) {
     if (whole) __builtin_memcpy(drow, packed, sizeof(packed));
 }
 
-template <typename K> int launch(K kernel, const WarpArgs& a, hipStream_t s, const char* family, const char* src, int c, const char* dst, int interp);
+template <typename SrcT, int C, typename DstT, int INTERP> static Kernel<WarpArgs> pick_generic() {
+    return named(warp_generic<SrcT, C, DstT, INTERP>, "rwh::warp_generic<%s, %d, %s, %d>", elem<SrcT>::name, C, elem<DstT>::name, INTERP);
+}
 
 // ================================================================================================
 // Exact kernel (flag RWH_WARP_EXACT): the reference's float64 arithmetic, operation by operation, so that
@@ -354,14 +371,18 @@ __global__ __launch_bounds__(256) void warp_exact(const WarpArgs a) {
     }
 }
 
+template <typename SrcT, int C, typename DstT, int INTERP> static Kernel<WarpArgs> pick_exact() {
+    return named(warp_exact<SrcT, C, DstT, INTERP>, "rwh::warp_exact<%s, %d, %s, %d>", elem<SrcT>::name, C, elem<DstT>::name, INTERP);
+}
+
 template <typename SrcT, int C>
 int dispatch_exact(const WarpArgs& a, int interp, int dst_dtype, hipStream_t s) {
     if (interp == RWH_NEAREST) {
         if (dst_dtype != elem<SrcT>::dtype) return RWH_E_UNSUPPORTED;
-        return launch(warp_exact<SrcT, C, SrcT, RWH_NEAREST>, a, s, "warp_exact", tname<SrcT>(), C, tname<SrcT>(), RWH_NEAREST);
+        return launch(pick_exact<SrcT, C, SrcT, RWH_NEAREST>(), a.cpx, s, a);
     }
-    if (dst_dtype == RWH_F64) return launch(warp_exact<SrcT, C, double, RWH_BILINEAR>, a, s, "warp_exact", tname<SrcT>(), C, "double", RWH_BILINEAR);
-    if (dst_dtype == RWH_U8) return launch(warp_exact<SrcT, C, unsigned char, RWH_BILINEAR>, a, s, "warp_exact", tname<SrcT>(), C, "unsigned char", RWH_BILINEAR);
+    if (dst_dtype == RWH_F64) return launch(pick_exact<SrcT, C, double, RWH_BILINEAR>(), a.cpx, s, a);
+    if (dst_dtype == RWH_U8) return launch(pick_exact<SrcT, C, unsigned char, RWH_BILINEAR>(), a.cpx, s, a);
     return RWH_E_UNSUPPORTED;
 }
 
@@ -432,113 +453,78 @@ __global__ __launch_bounds__(256) void sample_points_any(const unsigned char* im
     else bilinear_any<SrcT, DstT>(img, src_h, src_w, bound_h, bound_w, C, xs[i], ys[i], out + i * C);
 }
 
-// f(T{}, name of T as the demangled kernel names spell it) for the element type of `code` (a bool plane is RWH_U8); false: unknown code
-template <class F> static bool with_elem(int code, F&& f) {
-    switch (code) {
-        case RWH_U8: f(uint8_t{}, "unsigned char"); return true;
-        case RWH_I8: f(int8_t{}, "signed char"); return true;
-        case RWH_U16: f(uint16_t{}, "unsigned short"); return true;
-        case RWH_I16: f(int16_t{}, "short"); return true;
-        case RWH_I32: f(int32_t{}, "int"); return true;
-        case RWH_U32: f(uint32_t{}, "unsigned int"); return true;
-        case RWH_I64: f(int64_t{}, "long"); return true;
-        case RWH_U64: f(uint64_t{}, "unsigned long"); return true;
-        case RWH_F16: f(_Float16{}, "_Float16"); return true;
-        case RWH_F32: f(float{}, "float"); return true;
-        case RWH_F64: f(double{}, "double"); return true;
-        default: return false;
-    }
-}
-
-// nearest copies elements as unsigned integers of the element size: f(E{}, name)
-template <class F> static void with_raw(int esz, F&& f) {
-    switch (esz) {
-        case 1: f(uint8_t{}, "unsigned char"); break;
-        case 2: f(uint16_t{}, "unsigned short"); break;
-        case 4: f(uint32_t{}, "unsigned int"); break;
-        default: f(uint64_t{}, "unsigned long"); break;
-    }
+template <typename SrcT, typename DstT, int INTERP> static Kernel<WarpArgs> pick_any() {
+    return named(warp_any<SrcT, DstT, INTERP>, "rwh::warp_any<%s, %s, %d>", elem<SrcT>::name, elem<DstT>::name, INTERP);
 }
 
 // channels of texel (0,0) the reference's interpolators blank (homography.py:112-116): 0..2, and 3 only when there are exactly 4
 static int blank_channels(int c) { return c == 4 ? 4 : c < 3 ? c : 3; }
 
-template <typename K>
-static int launch_any(K kernel, const WarpArgs& a, hipStream_t s, const char* src, const char* dst, int interp) {
-    char name[96];
-    snprintf(name, sizeof name, "rwh::warp_any<%s, %s, %d>", src, dst, interp);
-    if (plan_only("%s", name)) return RWH_OK;
-    hipLaunchKernelGGL(kernel, dim3(8u * a.cpx), dim3(256), 0, s, a);
-    return check_launch();
+// ---- host side ---------------------------------------------------------------------------------
+// The block grid of `count` images of tiles_x x tiles_y tiles each (WarpArgs and FastArgs name these fields alike).
+// false, and `a` untouched: too many blocks for one launch.
+template <class Args> static bool set_grid(Args& a, unsigned tiles_x, unsigned tiles_y, unsigned count) {
+    const unsigned long long nb = (unsigned long long)tiles_x * tiles_y * count;
+    if (nb >= (1ull << 31) / 8) return false;
+    a.tiles_x = tiles_x; a.tiles_y = tiles_y;
+    a.nblocks = (unsigned)nb;
+    a.cpx = (a.nblocks + 7u) / 8u;
+    return true;
+}
+// the grid of the WarpArgs kernels: tiles of TILE_ROWS rows (one per wave) x 64 lanes of `px` pixels
+static bool tile_grid(WarpArgs& a, int px, int batch) {
+    return set_grid(a, (unsigned)((a.out_w + RWH_WAVE * px - 1) / (RWH_WAVE * px)), (unsigned)((a.rows + TILE_ROWS - 1) / TILE_ROWS), (unsigned)batch);
 }
 
-static bool retile(WarpArgs& a, int px);
+static WarpArgs make_warp_args(const void* src, int src_h, int src_w, long long src_img_stride, const double* ih, double x0, double step_x,
+                               double x_last, double y0, double step_y, double y_last, int out_h, int out_w, int bound_h, int bound_w,
+                               void* dst, long long dst_img_stride, int row_begin, int row_end) {
+    WarpArgs a = {};
+    a.src = static_cast<const unsigned char*>(src); a.dst = static_cast<unsigned char*>(dst);
+    a.src_img_stride = src_img_stride; a.dst_img_stride = dst_img_stride;
+    for (int i = 0; i < 9; ++i) a.ih[i] = ih[i];
+    a.x0 = x0; a.step_x = step_x; a.x_last = x_last; a.y0 = y0; a.step_y = step_y; a.y_last = y_last;
+    a.src_h = src_h; a.src_w = src_w; a.bound_h = bound_h; a.bound_w = bound_w;
+    a.out_h = out_h; a.out_w = out_w; a.row_begin = row_begin; a.rows = row_end - row_begin;
+    return a;
+}
 
-static int dispatch_any(const WarpArgs& a0, int src_dtype, int interp, int dst_dtype, hipStream_t s) {
-    WarpArgs a = a0;
-    if (!retile(a, 1)) return RWH_E_UNSUPPORTED;
+static int dispatch_any(WarpArgs a, int batch, int src_dtype, int interp, int dst_dtype, hipStream_t s) {
+    if (!tile_grid(a, 1, batch)) return RWH_E_UNSUPPORTED;
     int st = RWH_E_UNSUPPORTED;
     if (interp == RWH_NEAREST) {
         if (dst_dtype != src_dtype) return RWH_E_UNSUPPORTED;
-        with_raw(elem_size(src_dtype), [&](auto tag, const char* name) {
+        with_raw(elem_size(src_dtype), [&](auto tag, const char*) {
             using E = decltype(tag);
-            st = launch_any(warp_any<E, E, RWH_NEAREST>, a, s, name, name, RWH_NEAREST);
+            st = launch(pick_any<E, E, RWH_NEAREST>(), a.cpx, s, a);
         });
     } else if (dst_dtype == RWH_F64 || dst_dtype == RWH_U8) {
-        with_elem(src_dtype, [&](auto tag, const char* name) {
+        with_elem(src_dtype, [&](auto tag, const char*) {
             using T = decltype(tag);
-            st = dst_dtype == RWH_F64 ? launch_any(warp_any<T, double, RWH_BILINEAR>, a, s, name, "double", RWH_BILINEAR)
-                                      : launch_any(warp_any<T, unsigned char, RWH_BILINEAR>, a, s, name, "unsigned char", RWH_BILINEAR);
+            st = dst_dtype == RWH_F64 ? launch(pick_any<T, double, RWH_BILINEAR>(), a.cpx, s, a)
+                                      : launch(pick_any<T, unsigned char, RWH_BILINEAR>(), a.cpx, s, a);
         });
     }
     return st;
 }
 
-// ---- host side ---------------------------------------------------------------------------------
-template <typename K>
-int launch(K kernel, const WarpArgs& a, hipStream_t s, const char* family, const char* src, int c, const char* dst, int interp) {
-    char fmt[96];
-    snprintf(fmt, sizeof fmt, "rwh::%s<%%s, %%d, %%s, %%d>", family);
-    if (plan_only(fmt, src, c, dst, interp)) return RWH_OK;
-    const unsigned grid = 8u * a.cpx;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, a);
-    return check_launch();
-}
-
-// the block grid for `px` pixels per lane (the entry point sets it up for PX); false: too many blocks for one launch
-static bool retile(WarpArgs& a, int px) {
-    const unsigned long long per_img = (unsigned long long)a.tiles_x * a.tiles_y;
-    const unsigned long long batch = per_img ? a.nblocks / per_img : 0;
-    a.tiles_x = (unsigned)((a.out_w + RWH_WAVE * px - 1) / (RWH_WAVE * px));
-    const unsigned long long nb = (unsigned long long)a.tiles_x * a.tiles_y * batch;
-    if (nb >= (1ull << 31) / 8) return false;
-    a.nblocks = (unsigned)nb;
-    a.cpx = (a.nblocks + 7u) / 8u;
-    return true;
-}
-
+// float32 output runs at 1 px per lane (generic_px): each instance is launched on the grid of its own px
 template <typename SrcT, int C>
-int dispatch(const WarpArgs& a, int interp, int dst_dtype, hipStream_t s) {
+int dispatch(WarpArgs a, int batch, int interp, int dst_dtype, hipStream_t s) {
+    Kernel<WarpArgs> k;
+    int px;
     if (interp == RWH_NEAREST) {
         if (dst_dtype != elem<SrcT>::dtype) return RWH_E_UNSUPPORTED;
-        if constexpr (generic_px<SrcT, C>() != PX) {
-            WarpArgs b = a;
-            if (!retile(b, generic_px<SrcT, C>())) return RWH_E_UNSUPPORTED;
-            return launch(warp_generic<SrcT, C, SrcT, RWH_NEAREST>, b, s, "warp_generic", tname<SrcT>(), C, tname<SrcT>(), RWH_NEAREST);
-        }
-        return launch(warp_generic<SrcT, C, SrcT, RWH_NEAREST>, a, s, "warp_generic", tname<SrcT>(), C, tname<SrcT>(), RWH_NEAREST);
+        k = pick_generic<SrcT, C, SrcT, RWH_NEAREST>(); px = generic_px<SrcT, C>();
+    } else if (dst_dtype == RWH_F32) {
+        k = pick_generic<SrcT, C, float, RWH_BILINEAR>(); px = generic_px<float, C>();
+    } else if (dst_dtype == RWH_U8) {
+        k = pick_generic<SrcT, C, unsigned char, RWH_BILINEAR>(); px = generic_px<unsigned char, C>();
+    } else {
+        return RWH_E_UNSUPPORTED;
     }
-    if (dst_dtype == RWH_F32) {
-        WarpArgs b = a;
-        if (!retile(b, generic_px<float, C>())) return RWH_E_UNSUPPORTED;
-        return launch(warp_generic<SrcT, C, float, RWH_BILINEAR>, b, s, "warp_generic", tname<SrcT>(), C, "float", RWH_BILINEAR);
-    }
-    if (dst_dtype == RWH_U8) {
-        WarpArgs b = a;
-        if (!retile(b, generic_px<unsigned char, C>())) return RWH_E_UNSUPPORTED;
-        return launch(warp_generic<SrcT, C, unsigned char, RWH_BILINEAR>, b, s, "warp_generic", tname<SrcT>(), C, "unsigned char", RWH_BILINEAR);
-    }
-    return RWH_E_UNSUPPORTED;
+    if (!tile_grid(a, px, batch)) return RWH_E_UNSUPPORTED;
+    return launch(k, a.cpx, s, a);
 }
 
 __global__ void zero_origin_kernel(unsigned char* src, long long stride, int batch, int nbytes) {
@@ -624,167 +610,175 @@ static void fill_offsets(Coef& c, int shape, int pstr) {
     }
 }
 
-// Fast-path launch (RGB u8; bilinear u8 / float32 output, or nearest): returns RWH_E_UNSUPPORTED when the shape needs
-// the generic kernel.
-// variant: 0 = 4 px per lane (256 x 4 block tiles), 1 = 8 px per lane (128 x 16 block tiles, patch shape chosen here),
-// 3 = nearest neighbour on the 8 px kernel's tiling.  n_h = 1: one homography for the batch; n_h = batch (variants 1
-// and 3): one per image, launched TAB_N images at a time with their coefficients as a second kernel argument.
-// (variant 2 / `group` / `custom` serve tools/warp_lab.hip: an experimental kernel on the 8 px kernel's 128 x 16 block tiles.)
-int launch_fast(const WarpArgs& w, const double* ih, double x0, double step_x, double y0, double step_y,
-                int dst_dtype, int batch, hipStream_t s, int variant, int group = 1,
-                void (*custom)(const FastArgs) = nullptr, int n_h = 1, const CompArgs* comp = nullptr, int channels = 3) {
-    const bool px8 = variant >= 1, nn = variant == 3;
+// ---- the fast path: staged RGB u8 kernels (rwh_warp_rgb8.h) ------------------------------------------------------------------
+enum class FastKind {
+    Bilinear4,   // 4 px per lane, 256 x 4 block tiles (outputs narrower than 128 px)
+    Bilinear8,   // 8 px per lane, 128 x 16 block tiles, patch shape chosen here
+    Nearest8,    // nearest neighbour on the 8 px kernel's tiling
+    Custom,      // tools/warp_lab.hip: an experimental kernel of its own on the 8 px kernel's tiling
+};
+struct FastRequest {
+    FastKind kind;
+    int dst_dtype = RWH_U8;               // RWH_U8, or RWH_F32 (bilinear)
+    int batch = 1;
+    const double* ih = nullptr;           // n_h inverse homographies of 9 doubles; nullptr: the one in WarpArgs
+    int n_h = 1;                          // 1: one homography for the batch; batch: one per image, launched TAB_N images at a time
+    int channels = 3;                     // 4: uint8 RGBA
+    const CompArgs* comp = nullptr;       // the canvas compositor's paste / 'Rate' epilogue
+    void (*custom)(const FastArgs) = nullptr;   // Custom: the kernel, and the value of its free parameter FastArgs::group
+    int group = 1;
+};
+
+// f(std::integral_constant<int, shape>) for a patch shape (log2 of the patch width) 7, 6 or 5
+template <class F> static auto with_shape(int shape, F&& f) {
+    return shape == 7 ? f(std::integral_constant<int, 7>{}) : shape == 6 ? f(std::integral_constant<int, 6>{}) : f(std::integral_constant<int, 5>{});
+}
+enum class Frames { One, Wave, Block };   // frames per block: one; several, a staging window per wave (fast8m) or per block (fast8mb)
+
+// The (FastArgs) kernel of one homography.  halves: only shapes 6 and 5 exist (choose_shape).
+static Kernel<FastArgs> pick_fast(FastKind kind, bool u8, int channels, int shape, bool halves, Frames frames) {
+    if (kind == FastKind::Bilinear4)
+        return u8 ? named(warp_rgb8_fast<unsigned char>, "rwh::warp_rgb8_fast<%s>", elem<unsigned char>::name)
+                  : named(warp_rgb8_fast<float>, "rwh::warp_rgb8_fast<%s>", elem<float>::name);
+    return with_shape(shape, [&](auto lp) {
+        constexpr int S = decltype(lp)::value;
+        if (kind == FastKind::Nearest8) return named(warp_rgb8_nn<S>, "rwh::warp_rgb8_nn<%d>", S);
+        if (channels == 4) return named(warp_rgba8_fast8<S>, "rwh::warp_rgba8_fast8<%d>", S);
+        if (frames == Frames::Block) return named(warp_rgb8_fast8mb<S>, "rwh::warp_rgb8_fast8mb<%d>", S);
+        if (frames == Frames::Wave) return named(warp_rgb8_fast8m<S>, "rwh::warp_rgb8_fast8m<%d>", S);
+        if constexpr (S != 7)
+            if (halves) return named(warp_rgb8_fast8h<S>, "rwh::warp_rgb8_fast8h<%d>", S);
+        return u8 ? named(warp_rgb8_fast8<unsigned char, S>, "rwh::warp_rgb8_fast8<unsigned char, %d>", S)
+                  : named(warp_rgb8_fast8<float, S>, "rwh::warp_rgb8_fast8<float, %d>", S);
+    });
+}
+// The (FastArgs, CoefTab) kernel of a group of images with one homography each
+static Kernel<FastArgs, CoefTab> pick_tab(bool nn, bool u8, int shape, bool halves) {
+    return with_shape(shape, [&](auto lp) {
+        constexpr int S = decltype(lp)::value;
+        if constexpr (S != 7)
+            if (halves) return named(warp_rgb8_fast8h_tab<S>, "rwh::warp_rgb8_fast8h_tab<%d>", S);
+        if (nn) return named(warp_rgb8_nn_tab<S>, "rwh::warp_rgb8_nn_tab<%d>", S);
+        return u8 ? named(warp_rgb8_fast8_tab<unsigned char, S>, "rwh::warp_rgb8_fast8_tab<unsigned char, %d>", S)
+                  : named(warp_rgb8_fast8_tab<float, S>, "rwh::warp_rgb8_fast8_tab<float, %d>", S);
+    });
+}
+static Kernel<FastArgs, CompArgs> pick_comp(int shape) {
+    return with_shape(shape, [](auto lp) { return named(warp_rgb8_comp<decltype(lp)::value>, "rwh::warp_rgb8_comp<%d>", decltype(lp)::value); });
+}
+// the ragged right edge: columns [a.out_w, a.pitch_w) of `count` images, one block per 256 rows
+static int launch_strip(const FastArgs& a, bool u8, const CoefTab* tab, int count, hipStream_t s) {
+    if (g_plan_buf) return RWH_OK;         // (rwh_warp_plan names the tiled kernel only)
+    const dim3 sgrid((unsigned)((a.rows + 255) / 256), (unsigned)count);
+    if (tab) hipLaunchKernelGGL(u8 ? warp_rgb8_strip_tab<unsigned char> : warp_rgb8_strip_tab<float>, sgrid, dim3(256), 0, s, a, *tab);
+    else hipLaunchKernelGGL(u8 ? warp_rgb8_strip<unsigned char> : warp_rgb8_strip<float>, sgrid, dim3(256), 0, s, a);
+    return check_launch();
+}
+
+// Fast-path launch of the warp `w` describes (RGB u8 source; bilinear with u8 / float32 output, or nearest), as `q` asks for it.
+// Returns RWH_E_UNSUPPORTED when the configuration needs the generic kernel.
+int launch_fast(const WarpArgs& w, const FastRequest& q, hipStream_t s) {
+    const bool bil8 = q.kind == FastKind::Bilinear8, nn = q.kind == FastKind::Nearest8, px8 = q.kind != FastKind::Bilinear4;
+    const bool u8 = q.dst_dtype == RWH_U8;
+    const double* ih = q.ih ? q.ih : w.ih;
+    const int n_h = q.n_h, batch = q.batch;
+    // what may be combined: one homography per image on the 8 px bilinear and nearest kernels; RGBA or the compositor (not both) on
+    // the uint8 8 px bilinear kernel with one homography, the compositor on one image; a custom kernel if and only if Custom
+    if (n_h != 1 && !(bil8 || nn)) return RWH_E_UNSUPPORTED;
+    if ((q.channels == 4 || q.comp) && !(bil8 && u8 && n_h == 1)) return RWH_E_UNSUPPORTED;
+    if (q.comp && (q.channels == 4 || batch != 1)) return RWH_E_UNSUPPORTED;
+    if ((q.kind == FastKind::Custom) != (q.custom != nullptr)) return RWH_E_UNSUPPORTED;
     if (w.out_w < (px8 ? 128 : FP_PX) || w.bound_w > (1 << 19) || w.bound_h > (1 << 19)) return RWH_E_UNSUPPORTED;
-    if (n_h != 1 && (!px8 || custom)) return RWH_E_UNSUPPORTED;
-    // 4 channels: the uint8 RGBA form of the 8 px bilinear kernel only (one homography, no compositor)
-    if (channels == 4 && (!px8 || nn || dst_dtype != RWH_U8 || n_h != 1 || comp || custom)) return RWH_E_UNSUPPORTED;
-    const size_t dst_esz = dst_dtype == RWH_U8 ? 1 : 4;
-    if ((size_t)w.rows * (size_t)w.out_w * (size_t)channels * dst_esz >= (1ull << 32)) return RWH_E_UNSUPPORTED;  // 32-bit lane offsets
+    if ((size_t)w.rows * (size_t)w.out_w * (size_t)q.channels * (u8 ? 1 : 4) >= (1ull << 32)) return RWH_E_UNSUPPORTED;  // 32-bit lane offsets
+    // the plain RGB bilinear kernels have a form that stages a patch by halves (uint8 output only; RGBA was tried: its gathers are
+    // aligned 8-byte loads of exactly the two texels a tap pair needs, and beat the halves at every minification -- 4K x 16, 1.4x:
+    // 0.57 of the roofline gathered vs 0.48 staged), and leave a thin ragged right edge (1 .. STRIP_MAX columns past a multiple of
+    // 128) to warp_rgb8_strip (rwh_warp_rgb8.h), covering whole tiles only.  The strip is a function of out_w alone: shards,
+    // batches, tables and shapes agree.
+    const bool plain = bil8 && !q.comp && q.channels == 3;
+    const int strip = (plain && w.out_w >= 256 && w.out_w % 128 >= 1 && w.out_w % 128 <= STRIP_MAX) ? w.out_w % 128 : 0;
     FastArgs a;
     a.src = w.src; a.dst = w.dst; a.src_img_stride = w.src_img_stride; a.dst_img_stride = w.dst_img_stride;
-    a.src_h = w.src_h; a.src_w = w.src_w; a.bound_h = w.bound_h; a.bound_w = w.bound_w; a.out_w = w.out_w; a.pitch_w = w.out_w;
-    // a thin ragged right edge (1 .. STRIP_MAX columns past a multiple of 128) is left to warp_rgb8_strip (rwh_warp_rgb8.h): the
-    // bilinear 8 px kernels then cover whole tiles only.  A function of out_w alone: shards, batches, tables and shapes agree.
-    const int strip = (px8 && !nn && !custom && !comp && channels == 3 && w.out_w >= 256 && w.out_w % 128 >= 1 && w.out_w % 128 <= STRIP_MAX)
-                          ? w.out_w % 128 : 0;
-    a.out_w = w.out_w - strip;
-    auto launch_strip = [&](const CoefTab* tab, int count) -> int {
-        if (!strip || g_plan_buf) return RWH_OK;
-        const dim3 sgrid((unsigned)((w.rows + 255) / 256), (unsigned)count);
-        if (tab) {
-            if (dst_dtype == RWH_U8) hipLaunchKernelGGL(warp_rgb8_strip_tab<unsigned char>, sgrid, dim3(256), 0, s, a, *tab);
-            else hipLaunchKernelGGL(warp_rgb8_strip_tab<float>, sgrid, dim3(256), 0, s, a, *tab);
-        } else {
-            if (dst_dtype == RWH_U8) hipLaunchKernelGGL(warp_rgb8_strip<unsigned char>, sgrid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL(warp_rgb8_strip<float>, sgrid, dim3(256), 0, s, a);
-        }
-        return check_launch();
-    };
+    a.src_h = w.src_h; a.src_w = w.src_w; a.bound_h = w.bound_h; a.bound_w = w.bound_w; a.out_w = w.out_w - strip; a.pitch_w = w.out_w;
     a.row_begin = w.row_begin; a.rows = w.rows;
     a.gx0 = w.x0; a.gstep_x = w.step_x; a.gx_last = w.x_last; a.gy0 = w.y0; a.gstep_y = w.step_y; a.gy_last = w.y_last;
     a.out_h = w.out_h;
+    a.group = q.group;
     // patch shape: the host's choice per homography; with one homography per image the images are grouped by shape
     int shape = 0, shapes[16] = {};      // indexed by the shape code: 5..7, + 8 for the HALVES form
     std::vector<int> shape_of(n_h > 1 ? n_h : 0);
     if (px8) {
         for (int i = 0; i < n_h; ++i) {
-            fill_coef(a.c, ih + 9 * i, x0, step_x, y0, step_y);
-            // uint8 bilinear RGB only.  (RGBA was tried: its gathers are aligned 8-byte loads of exactly the two texels a tap
-            //  pair needs, and beat the halves at every minification -- 4K x 16, 1.4x: 0.57 of the roofline gathered vs 0.48 staged)
-            const bool halves_ok = !comp && !nn && !custom && channels == 3 && dst_dtype == RWH_U8;
-            shape = comp ? choose_shape(a, comp->tsy, comp->tsx, comp->ht, comp->wt) : choose_shape(a, 0, 0, -1, -1, halves_ok);
+            fill_coef(a.c, ih + 9 * i, w.x0, w.step_x, w.y0, w.step_y);
+            shape = q.comp ? choose_shape(a, q.comp->tsy, q.comp->tsx, q.comp->ht, q.comp->wt) : choose_shape(a, 0, 0, -1, -1, plain && u8);
             if (n_h > 1) { shape_of[i] = shape; shapes[shape] = 1; }
         }
     }
-    fill_coef(a.c, ih, x0, step_x, y0, step_y);
+    fill_coef(a.c, ih, w.x0, w.step_x, w.y0, w.step_y);
     const bool halves = px8 && (shape & 8);
     shape &= 7;
-    const int pstr = (px8 && dst_dtype != RWH_U8) ? (1 << shape) / 8 : 1;
-    if (px8) fill_offsets(a.c, shape, pstr);
+    if (px8) fill_offsets(a.c, shape, u8 ? 1 : (1 << shape) / 8);
     for (int j = 1; j <= 3; ++j) { a.dxs[j - 1][0] = j * a.c.cx[2]; a.dxs[j - 1][1] = j * a.c.cy[2]; a.dxs[j - 1][2] = j * a.c.cw[2]; }
     const double xm = MAGIC + (double)(w.bound_w - 1), ym = MAGIC + (double)(w.bound_h - 1);
     __builtin_memcpy(&a.xmax_bits, &xm, 8);
     __builtin_memcpy(&a.ymax_bits, &ym, 8);
-    a.tiles_x = (unsigned)(px8 ? (a.out_w + 127) / 128 : (a.out_w + 255) / 256);
-    a.group = group;   // free parameter of a tools/warp_lab custom kernel
-    a.tiles_y = (unsigned)(px8 ? (w.rows + 15) / 16 : (w.rows + 3) / 4);
-    const bool u8 = dst_dtype == RWH_U8;
-    const dim3 block(256);
+    const unsigned tiles_x = (unsigned)(px8 ? (a.out_w + 127) / 128 : (a.out_w + 255) / 256);
+    const unsigned tiles_y = (unsigned)(px8 ? (w.rows + 15) / 16 : (w.rows + 3) / 4);
     auto geometry = [&](int count) {
-        const unsigned long long nb = (unsigned long long)a.tiles_x * a.tiles_y * (unsigned)count;
-        if (nb >= (1ull << 31) / 8) return false;
-        a.nblocks = (unsigned)nb;
-        a.cpx = (a.nblocks + 7u) / 8u;
+        if (!set_grid(a, tiles_x, tiles_y, (unsigned)count)) return false;
 #ifdef RWH_XCD_CHUNK_LOG   // lab builds (rwh_warp_rgb8.h): the grid is a whole number of 8-chunk groups
         a.cpx = (a.cpx + (1u << RWH_XCD_CHUNK_LOG) - 1u) >> RWH_XCD_CHUNK_LOG << RWH_XCD_CHUNK_LOG;
 #endif
-        a.tiles_x_magic = div_magic(a.tiles_x, nb);
-        a.tiles_y_magic = div_magic(a.tiles_y, nb / a.tiles_x + 1);
-        return !((a.tiles_x > 1 && !a.tiles_x_magic) || (a.tiles_y > 1 && !a.tiles_y_magic));
+        a.tiles_x_magic = div_magic(tiles_x, a.nblocks);
+        a.tiles_y_magic = div_magic(tiles_y, a.nblocks / tiles_x + 1);
+        return !((tiles_x > 1 && !a.tiles_x_magic) || (tiles_y > 1 && !a.tiles_y_magic));
     };
     if (n_h == 1) {
         if (!geometry(batch)) return RWH_E_UNSUPPORTED;
-        void (*kern)(const FastArgs) = custom;
-        if (!kern) {
-            if (nn) kern = shape == 7 ? warp_rgb8_nn<7> : shape == 6 ? warp_rgb8_nn<6> : warp_rgb8_nn<5>;
-            else if (!px8) kern = u8 ? warp_rgb8_fast<unsigned char> : warp_rgb8_fast<float>;
-            else if (halves) kern = shape == 6 ? warp_rgb8_fast8h<6> : warp_rgb8_fast8h<5>;
-            else if (shape == 7) kern = u8 ? warp_rgb8_fast8<unsigned char, 7> : warp_rgb8_fast8<float, 7>;
-            else if (shape == 6) kern = u8 ? warp_rgb8_fast8<unsigned char, 6> : warp_rgb8_fast8<float, 6>;
-            else kern = u8 ? warp_rgb8_fast8<unsigned char, 5> : warp_rgb8_fast8<float, 5>;
-        }
-        if (channels == 4) {
-            if (plan_only("rwh::warp_rgba8_fast8<%.0s%d>", "", shape)) return RWH_OK;
-            kern = shape == 7 ? warp_rgba8_fast8<7> : shape == 6 ? warp_rgba8_fast8<6> : warp_rgba8_fast8<5>;
-            hipLaunchKernelGGL(kern, dim3(8u * a.cpx), block, 0, s, a);
-            return check_launch();
-        }
-        if (comp) {      // canvas compositor: the 8 px kernel with the paste / 'Rate' epilogue (uint8, one image)
-            if (!px8 || nn || !u8 || batch != 1) return RWH_E_UNSUPPORTED;
-            if (plan_only("rwh::warp_rgb8_comp<%.0s%d>", "", shape)) return RWH_OK;
-            void (*ck)(const FastArgs, const CompArgs) = shape == 7 ? warp_rgb8_comp<7> : shape == 6 ? warp_rgb8_comp<6> : warp_rgb8_comp<5>;
-            hipLaunchKernelGGL(ck, dim3(8u * a.cpx), block, 0, s, a, *comp);
-            return check_launch();
-        }
+        if (q.comp) return launch(pick_comp(shape), a.cpx, s, a, *q.comp);
+        unsigned cpx = a.cpx;
+        Frames frames = Frames::One;
         // one homography, several frames, interior geometry shared by the frames of a block (warp_rgb8_fast8m): uint8 RGB bilinear
         // whole-patch kernel only.  OFF unless rwh_lab_tune(RWH_TUNE_WARP_FRAMES, n >= 2) asks for n frames per block: the kernel
         // halves the VALU work per frame (366 -> ~185 instructions per wave and frame) and is bit-identical, but same-box A/B
         // (profiles/r04_lab_notes.txt) gives +3 % on 4K x 32, +2 % on 1080p x 512 and -3 % on 8K x 8 at its best setting (3-4
         // frames): this warp is bound by the memory system's throughput on its access pattern, not by its arithmetic.
-        if (px8 && !nn && !custom && !halves && u8 && batch >= 2 && g_force_warp_frames >= 2) {
+        if (plain && !halves && u8 && batch >= 2 && g_force_warp_frames >= 2) {
             const int want = g_force_warp_frames % 100;
-            const bool block_window = g_force_warp_frames >= 100;      // 100 + n: one staging window per block (warp_rgb8_fast8mb)
             const int F = want < batch ? want : batch;
-            const unsigned long long ntiles = (unsigned long long)a.tiles_x * a.tiles_y, groups = ((unsigned)batch + F - 1) / F;
+            const unsigned long long ntiles = (unsigned long long)tiles_x * tiles_y, groups = ((unsigned)batch + F - 1) / F;
             const unsigned long long mnb = ntiles * groups;
             const unsigned magic = div_magic((unsigned)ntiles, mnb);
             if (mnb < (1ull << 31) / 8 && (ntiles == 1 || magic)) {
                 a.mf_frames = F; a.mf_batch = batch; a.ntiles = (unsigned)ntiles; a.ntiles_magic = magic;
                 a.mf_nblocks = (unsigned)mnb; a.mf_cpx = (a.mf_nblocks + 7u) / 8u;
-                if (plan_only(block_window ? "rwh::warp_rgb8_fast8mb<%.0s%d>" : "rwh::warp_rgb8_fast8m<%.0s%d>", "", shape)) return RWH_OK;
-                void (*mk)(const FastArgs) = block_window ? (shape == 7 ? warp_rgb8_fast8mb<7> : shape == 6 ? warp_rgb8_fast8mb<6> : warp_rgb8_fast8mb<5>)
-                                                          : (shape == 7 ? warp_rgb8_fast8m<7> : shape == 6 ? warp_rgb8_fast8m<6> : warp_rgb8_fast8m<5>);
-                hipLaunchKernelGGL(mk, dim3(8u * a.mf_cpx), block, 0, s, a);
-                if (check_launch() != RWH_OK) return RWH_E_LAUNCH;
-                return launch_strip(nullptr, batch);
+                cpx = a.mf_cpx;
+                frames = g_force_warp_frames >= 100 ? Frames::Block : Frames::Wave;      // 100 + n: one staging window per block
             }
         }
-        if (custom ? false : nn ? plan_only("rwh::warp_rgb8_nn<%.0s%d>", "", shape)
-                          : !px8 ? plan_only("rwh::warp_rgb8_fast<%s>", u8 ? "unsigned char" : "float")
-                          : halves ? plan_only("rwh::warp_rgb8_fast8h<%.0s%d>", "", shape)
-                                 : plan_only("rwh::warp_rgb8_fast8<%s, %d>", u8 ? "unsigned char" : "float", shape))
-            return RWH_OK;
-        hipLaunchKernelGGL(kern, dim3(8u * a.cpx), block, 0, s, a);
-        if (check_launch() != RWH_OK) return RWH_E_LAUNCH;
-        return launch_strip(nullptr, batch);
+        const Kernel<FastArgs> k = q.custom ? Kernel<FastArgs>{q.custom, "(custom)"} : pick_fast(q.kind, u8, q.channels, shape, halves, frames);
+        if (launch(k, cpx, s, a) != RWH_OK) return RWH_E_LAUNCH;
+        return strip ? launch_strip(a, u8, nullptr, batch, s) : RWH_OK;
     }
     // one homography per image: per shape, TAB_N images per launch with their coefficients as a second kernel argument
     for (int code = 15; code >= 5; --code) {
         if (!shapes[code]) continue;
         const int sh = code & 7;
         const bool hv = code & 8;            // images whose homography minifies: patches staged by halves
-        const int ps = u8 ? 1 : (1 << sh) / 8;
-        void (*kern)(const FastArgs, const CoefTab);
-        if (hv) kern = sh == 6 ? warp_rgb8_fast8h_tab<6> : warp_rgb8_fast8h_tab<5>;
-        else if (nn) kern = sh == 7 ? warp_rgb8_nn_tab<7> : sh == 6 ? warp_rgb8_nn_tab<6> : warp_rgb8_nn_tab<5>;
-        else if (sh == 7) kern = u8 ? warp_rgb8_fast8_tab<unsigned char, 7> : warp_rgb8_fast8_tab<float, 7>;
-        else if (sh == 6) kern = u8 ? warp_rgb8_fast8_tab<unsigned char, 6> : warp_rgb8_fast8_tab<float, 6>;
-        else kern = u8 ? warp_rgb8_fast8_tab<unsigned char, 5> : warp_rgb8_fast8_tab<float, 5>;
+        const Kernel<FastArgs, CoefTab> k = pick_tab(nn, u8, sh, hv);
         CoefTab tab;
         int count = 0;
         for (int i = 0; i <= n_h; ++i) {
             if (i < n_h && shape_of[i] == code) {
-                fill_coef(tab.e[count], ih + 9 * i, x0, step_x, y0, step_y);
-                fill_offsets(tab.e[count], sh, ps);
+                fill_coef(tab.e[count], ih + 9 * i, w.x0, w.step_x, w.y0, w.step_y);
+                fill_offsets(tab.e[count], sh, u8 ? 1 : (1 << sh) / 8);
                 tab.e[count++].image = i;
             }
             if (count == TAB_N || (i == n_h && count > 0)) {
-                for (int k = count; k < TAB_N; ++k) tab.e[k] = tab.e[0];
+                for (int j = count; j < TAB_N; ++j) tab.e[j] = tab.e[0];
                 if (!geometry(count)) return RWH_E_UNSUPPORTED;
-                if (hv ? plan_only("rwh::warp_rgb8_fast8h_tab<%.0s%d>", "", sh) : nn ? plan_only("rwh::warp_rgb8_nn_tab<%.0s%d>", "", sh) : plan_only("rwh::warp_rgb8_fast8_tab<%s, %d>", u8 ? "unsigned char" : "float", sh)) { count = 0; continue; }
-                hipLaunchKernelGGL(kern, dim3(8u * a.cpx), block, 0, s, a, tab);
-                if (check_launch() != RWH_OK) return RWH_E_LAUNCH;
-                if (!nn && launch_strip(&tab, count) != RWH_OK) return RWH_E_LAUNCH;
+                if (launch(k, a.cpx, s, a, tab) != RWH_OK) return RWH_E_LAUNCH;
+                if (strip && launch_strip(a, u8, &tab, count, s) != RWH_OK) return RWH_E_LAUNCH;
                 count = 0;
             }
         }
@@ -797,15 +791,11 @@ int launch_fast(const WarpArgs& w, const double* ih, double x0, double step_x, d
 int warp_composite(const unsigned char* d_img_t, int t_h, int t_w, const double* inv_h, double x0, double y0, int canvas_h,
                    int canvas_w, unsigned char* d_canvas, const CompArgs& comp, hipStream_t s) {
     if (canvas_w < 128 || (size_t)t_h * t_w * 3 >= (1ull << 32)) return RWH_E_UNSUPPORTED;
-    WarpArgs a;
-    a.src = d_img_t; a.dst = d_canvas;
-    a.src_img_stride = 0; a.dst_img_stride = 0;
-    for (int i = 0; i < 9; ++i) a.ih[i] = inv_h[i];
-    a.x0 = x0; a.step_x = 1.0; a.x_last = x0 + (double)(canvas_w - 1);
-    a.y0 = y0; a.step_y = 1.0; a.y_last = y0 + (double)(canvas_h - 1);
-    a.src_h = t_h; a.src_w = t_w; a.bound_h = t_h; a.bound_w = t_w;
-    a.out_h = canvas_h; a.out_w = canvas_w; a.row_begin = 0; a.rows = canvas_h;
-    return launch_fast(a, inv_h, x0, 1.0, y0, 1.0, RWH_U8, 1, s, /*variant=*/1, 1, nullptr, 1, &comp);
+    const WarpArgs a = make_warp_args(d_img_t, t_h, t_w, 0, inv_h, x0, 1.0, x0 + (double)(canvas_w - 1), y0, 1.0, y0 + (double)(canvas_h - 1),
+                                      canvas_h, canvas_w, t_h, t_w, d_canvas, 0, 0, canvas_h);
+    FastRequest q{FastKind::Bilinear8};
+    q.comp = &comp;
+    return launch_fast(a, q, s);
 }
 
 }  // namespace rwh
@@ -839,6 +829,12 @@ extern "C" int rwh_warp_backward(const void* d_src, int src_h, int src_w, int ch
         if (check_launch() != RWH_OK) return RWH_E_LAUNCH;
     }
 
+    WarpArgs a = make_warp_args(d_src, src_h, src_w, src_image_stride, inv_h, x0, step_x, x_last, y0, step_y, y_last, out_h, out_w,
+                                bound_h < src_h ? bound_h : src_h, bound_w < src_w ? bound_w : src_w, d_dst, dst_image_stride, row_begin, row_end);
+    a.channels = channels;
+    FastRequest fast{FastKind::Bilinear8};
+    fast.dst_dtype = dst_dtype; fast.batch = batch;
+
     if (n_h == batch && batch > 1) {
         // one homography per image.  The staged RGB u8 kernels take a table of TAB_N coefficient sets per launch ...
         const bool fast_bil = src_dtype == RWH_U8 && channels == 3 && interp == RWH_BILINEAR && !(flags & RWH_WARP_EXACT) &&
@@ -846,16 +842,9 @@ extern "C" int rwh_warp_backward(const void* d_src, int src_h, int src_w, int ch
         const bool fast_nn = src_dtype == RWH_U8 && channels == 3 && interp == RWH_NEAREST && dst_dtype == RWH_U8 &&
                              (size_t)src_h * src_w * 3 < (1ull << 32) - 4;
         if ((fast_bil || fast_nn) && out_w >= 128) {
-            WarpArgs a;
-            a.src = static_cast<const unsigned char*>(d_src);
-            a.dst = static_cast<unsigned char*>(d_dst);
-            a.src_img_stride = src_image_stride; a.dst_img_stride = dst_image_stride;
-            a.x0 = x0; a.step_x = step_x; a.x_last = x_last; a.y0 = y0; a.step_y = step_y; a.y_last = y_last;
-            a.src_h = src_h; a.src_w = src_w;
-            a.bound_h = bound_h < src_h ? bound_h : src_h;
-            a.bound_w = bound_w < src_w ? bound_w : src_w;
-            a.out_h = out_h; a.out_w = out_w; a.row_begin = row_begin; a.rows = row_end - row_begin;
-            const int st = launch_fast(a, inv_h, x0, step_x, y0, step_y, dst_dtype, batch, s, fast_nn ? 3 : 1, 1, nullptr, batch);
+            fast.kind = fast_nn ? FastKind::Nearest8 : FastKind::Bilinear8;
+            fast.ih = inv_h; fast.n_h = batch;
+            const int st = launch_fast(a, fast, s);
             if (st != RWH_E_UNSUPPORTED) return st;
         }
         // ... every other configuration is one launch per image on the same stream
@@ -870,32 +859,14 @@ extern "C" int rwh_warp_backward(const void* d_src, int src_h, int src_w, int ch
         return RWH_OK;
     }
 
-    WarpArgs a;
-    a.src = static_cast<const unsigned char*>(d_src);
-    a.dst = static_cast<unsigned char*>(d_dst);
-    a.src_img_stride = src_image_stride;
-    a.dst_img_stride = dst_image_stride;
-    for (int i = 0; i < 9; ++i) a.ih[i] = inv_h[i];
-    a.x0 = x0; a.step_x = step_x; a.x_last = x_last;
-    a.y0 = y0; a.step_y = step_y; a.y_last = y_last;
-    a.src_h = src_h; a.src_w = src_w;
-    a.bound_h = bound_h < src_h ? bound_h : src_h;
-    a.bound_w = bound_w < src_w ? bound_w : src_w;
-    a.out_h = out_h; a.out_w = out_w;
-    a.row_begin = row_begin; a.rows = row_end - row_begin;
-    a.tiles_x = (unsigned)((out_w + RWH_WAVE * PX - 1) / (RWH_WAVE * PX));
-    a.tiles_y = (unsigned)((a.rows + TILE_ROWS - 1) / TILE_ROWS);
-    const unsigned long long nb = (unsigned long long)a.tiles_x * a.tiles_y * (unsigned)batch;
-    if (nb >= (1ull << 31) / 8) return RWH_E_UNSUPPORTED;
-    a.nblocks = (unsigned)nb;
-    a.cpx = (a.nblocks + 7u) / 8u;
-    a.channels = channels;
-    if (any) return dispatch_any(a, src_dtype, interp, dst_dtype, s);
+    if (!tile_grid(a, PX, batch)) return RWH_E_UNSUPPORTED;
+    if (any) return dispatch_any(a, batch, src_dtype, interp, dst_dtype, s);
 
     // nearest neighbour, RGB u8: one kernel for the exact and the default mode -- it is bit-exact by construction
     if (src_dtype == RWH_U8 && channels == 3 && interp == RWH_NEAREST && dst_dtype == RWH_U8 && a.out_w >= 128 &&
         (size_t)src_h * src_w * 3 < (1ull << 32) - 4) {
-        const int st = launch_fast(a, inv_h, x0, step_x, y0, step_y, dst_dtype, batch, s, /*variant=*/3);
+        fast.kind = FastKind::Nearest8;
+        const int st = launch_fast(a, fast, s);
         if (st != RWH_E_UNSUPPORTED) return st;
     }
     if (flags & RWH_WARP_EXACT) {
@@ -903,19 +874,18 @@ extern "C" int rwh_warp_backward(const void* d_src, int src_h, int src_w, int ch
                                                       : dispatch_exact<unsigned char, 4>(a, interp, dst_dtype, s);
         return channels == 3 ? dispatch_exact<float, 3>(a, interp, dst_dtype, s) : dispatch_exact<float, 4>(a, interp, dst_dtype, s);
     }
-    if (src_dtype == RWH_U8 && channels == 3 && interp == RWH_BILINEAR && (dst_dtype == RWH_U8 || dst_dtype == RWH_F32)) {
-        const int st = launch_fast(a, inv_h, x0, step_x, y0, step_y, dst_dtype, batch, s, /*variant=*/a.out_w >= 128 ? 1 : 0);
+    // bilinear, uint8 in: RGB to uint8 / float32, RGBA (8 px kernel only) to uint8
+    if (src_dtype == RWH_U8 && interp == RWH_BILINEAR && (dst_dtype == RWH_U8 || (dst_dtype == RWH_F32 && channels == 3)) &&
+        (channels == 3 || a.out_w >= 128)) {
+        fast.kind = a.out_w >= 128 ? FastKind::Bilinear8 : FastKind::Bilinear4;
+        fast.channels = channels;
+        const int st = launch_fast(a, fast, s);
         if (st != RWH_E_UNSUPPORTED) return st;  // else: shape outside the fast kernel's limits -> generic kernel
     }
 
-    if (src_dtype == RWH_U8 && channels == 4 && interp == RWH_BILINEAR && dst_dtype == RWH_U8 && a.out_w >= 128) {
-        const int st = launch_fast(a, inv_h, x0, step_x, y0, step_y, dst_dtype, batch, s, /*variant=*/1, 1, nullptr, 1, nullptr, 4);
-        if (st != RWH_E_UNSUPPORTED) return st;
-    }
-
-    if (src_dtype == RWH_U8) return channels == 3 ? dispatch<unsigned char, 3>(a, interp, dst_dtype, s)
-                                                  : dispatch<unsigned char, 4>(a, interp, dst_dtype, s);
-    return channels == 3 ? dispatch<float, 3>(a, interp, dst_dtype, s) : dispatch<float, 4>(a, interp, dst_dtype, s);
+    if (src_dtype == RWH_U8) return channels == 3 ? dispatch<unsigned char, 3>(a, batch, interp, dst_dtype, s)
+                                                  : dispatch<unsigned char, 4>(a, batch, interp, dst_dtype, s);
+    return channels == 3 ? dispatch<float, 3>(a, batch, interp, dst_dtype, s) : dispatch<float, 4>(a, batch, interp, dst_dtype, s);
 }
 
 extern "C" int rwh_warp_plan(int src_h, int src_w, int channels, int src_dtype, int batch, const double* inv_h, int n_h,
@@ -1036,11 +1006,9 @@ extern "C" int rwh_warp_index_check(int src_h, int src_w, const double* inv_h, d
     using namespace rwh;
     if (!inv_h || !d_flag || src_h <= 0 || src_w <= 0 || out_h <= 0 || out_w <= 0 || bound_h <= 0 || bound_w <= 0) return RWH_E_INVALID;
     if (interp != RWH_NEAREST && interp != RWH_BILINEAR) return RWH_E_INVALID;
-    WarpArgs a = {};
-    for (int i = 0; i < 9; ++i) a.ih[i] = inv_h[i];
-    a.x0 = x0; a.step_x = step_x; a.x_last = x_last; a.y0 = y0; a.step_y = step_y; a.y_last = y_last;
-    a.src_h = src_h; a.src_w = src_w; a.bound_h = bound_h; a.bound_w = bound_w;      // the bound is NOT clipped here: it is the reference's mask
-    a.out_h = out_h; a.out_w = out_w;
+    // (no image access; the bound is NOT clipped here: it is the reference's mask)
+    const WarpArgs a = make_warp_args(nullptr, src_h, src_w, 0, inv_h, x0, step_x, x_last, y0, step_y, y_last, out_h, out_w, bound_h, bound_w,
+                                      nullptr, 0, 0, 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (hipMemsetAsync(d_flag, 0, sizeof(int), s) != hipSuccess) return RWH_E_LAUNCH;
     const long long n = (long long)out_h * out_w;

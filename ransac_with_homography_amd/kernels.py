@@ -52,6 +52,21 @@ class Grid:
             self.y_last = self.y0
 
 
+def _warp_marshal(src_shape, src_dtype, inv_h, grid, bound_hw, interp, out_dtype, rows, exact):
+    """The arguments rwh_warp_backward and rwh_warp_plan share, marshalled once: the plan is the same call without the buffers.
+    src_shape (B, H, W, C) -> (source description, B, warp description, dst dtype code, (row_begin, row_end, flags), ih, n_h);
+    a dtype without a code in this mode is a KeyError."""
+    B, H, W, C = src_shape
+    codes = STITCH_DTYPE if exact else _DTYPE
+    ih = np.ascontiguousarray(inv_h, dtype=np.float64).reshape(-1)
+    n_h = 1 if ih.size == 9 else ih.size // 9          # one inverse for the batch, or [B,3,3]: one per image
+    r0, r1 = (0, grid.out_h) if rows is None else rows
+    warp = (ih.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n_h,
+            grid.x0, grid.step_x, grid.x_last, grid.y0, grid.step_y, grid.y_last,
+            grid.out_h, grid.out_w, int(bound_hw[0]), int(bound_hw[1]), INTERP[interp])
+    return (H, W, C, codes[src_dtype]), B, warp, codes[out_dtype], (r0, r1, RWH_WARP_EXACT if exact else 0), ih, n_h
+
+
 def warp_backward(src, inv_h, grid, bound_hw, interp, out_dtype, zero_origin=True, rows=None, out=None, exact=False):
     """Launch K3.  `src`: [B,H,W,C] or [H,W,C] uint8/float32 GPU tensor (with exact=True: any dtype of STITCH_DTYPE, C 1..64).
     Returns a tensor [B,rows,out_w,C] (or without B) of `out_dtype` holding
@@ -67,23 +82,18 @@ def warp_backward(src, inv_h, grid, bound_hw, interp, out_dtype, zero_origin=Tru
     codes = STITCH_DTYPE if exact else _DTYPE
     if src.dtype not in codes or out_dtype not in codes:
         raise ValueError("unsupported image dtype")
-    r0, r1 = (0, grid.out_h) if rows is None else rows
+    src_desc, B, warp, dst_code, (r0, r1, flags), ih, n_h = _warp_marshal(src.shape, src.dtype, inv_h, grid, bound_hw, interp, out_dtype,
+                                                                          rows, exact)
     if out is None:
         out = torch.empty((B, r1 - r0, grid.out_w, C), dtype=out_dtype, device=src.device)
     else:
         _dev_check(out)
         assert out.dtype == out_dtype and out.numel() == B * (r1 - r0) * grid.out_w * C
-    ih = np.ascontiguousarray(inv_h, dtype=np.float64)
-    n_h = 1 if ih.size == 9 else ih.size // 9          # one inverse for the batch, or [B,3,3]: one per image
     assert ih.size == 9 * n_h and n_h in (1, B), "inv_h: 3x3, or one 3x3 per image of the batch"
-    ih = ih.reshape(9 * n_h)
     st = lib.rwh_warp_backward(
-        _ptr(src), H, W, C, codes[src.dtype], src.stride(0) * src.element_size(), B,
-        ih.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n_h,
-        grid.x0, grid.step_x, grid.x_last, grid.y0, grid.step_y, grid.y_last,
-        grid.out_h, grid.out_w, int(bound_hw[0]), int(bound_hw[1]), INTERP[interp],
-        _ptr(out), codes[out_dtype], (r1 - r0) * grid.out_w * C * out.element_size(),
-        r0, r1, (RWH_WARP_ZERO_ORIGIN if zero_origin else 0) | (RWH_WARP_EXACT if exact else 0), _lib.stream_ptr())
+        _ptr(src), *src_desc, src.stride(0) * src.element_size(), B, *warp,
+        _ptr(out), dst_code, (r1 - r0) * grid.out_w * C * out.element_size(),
+        r0, r1, flags | (RWH_WARP_ZERO_ORIGIN if zero_origin else 0), _lib.stream_ptr())
     check(st, "rwh_warp_backward")
     return out[0] if squeeze else out
 
@@ -130,16 +140,10 @@ def warp_plan(src_shape, src_dtype, inv_h, grid, bound_hw, interp, out_dtype, ro
     """Name of the kernel `warp_backward` launches for this configuration (rwh_warp_plan: the library's own dispatch,
     nothing is launched and no GPU is needed).  src_shape: (B, H, W, C) or (H, W, C)."""
     lib = _lib.load()
-    B, H, W, C = (1,) + tuple(src_shape) if len(src_shape) == 3 else tuple(src_shape)
-    ih = np.ascontiguousarray(inv_h, dtype=np.float64)
-    n_h = 1 if ih.size == 9 else ih.size // 9
-    r0, r1 = (0, grid.out_h) if rows is None else rows
+    shape4 = (1,) + tuple(src_shape) if len(src_shape) == 3 else tuple(src_shape)
+    src_desc, B, warp, dst_code, (r0, r1, flags), _, _ = _warp_marshal(shape4, src_dtype, inv_h, grid, bound_hw, interp, out_dtype, rows, exact)
     buf = ctypes.create_string_buffer(128)
-    codes = STITCH_DTYPE if exact else _DTYPE
-    check(lib.rwh_warp_plan(H, W, C, codes[src_dtype], B, ih.reshape(-1).ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n_h,
-                            grid.x0, grid.step_x, grid.x_last, grid.y0, grid.step_y, grid.y_last, grid.out_h, grid.out_w,
-                            int(bound_hw[0]), int(bound_hw[1]), INTERP[interp], codes[out_dtype], r0, r1,
-                            RWH_WARP_EXACT if exact else 0, buf, 128), "rwh_warp_plan")
+    check(lib.rwh_warp_plan(*src_desc, B, *warp, dst_code, r0, r1, flags, buf, 128), "rwh_warp_plan")
     return buf.value.decode()
 
 

@@ -160,6 +160,676 @@ def test_new_entry_points_validate_and_plan(lib):
                              torch.uint8) == "rwh::warp_rgb8_fast<unsigned char>"
 
 
+def _plan_sweep_rows():
+    """(key, thunk) per configuration of the plan sweep; thunk() -> the planned kernel name, or the status the library refuses with."""
+    import torch
+    from ransac_with_homography_amd import _lib, kernels
+    SH, SW = 2160, 3840
+
+    def zoom(s, deg=0.0):            # minification s (and a rotation) about the image centre
+        t = np.deg2rad(deg)
+        c, s_, cx, cy = np.cos(t) / s, np.sin(t) / s, (SW - 1) / 2, (SH - 1) / 2
+        return np.array([[c, -s_, cx - c * cx + s_ * cy], [s_, c, cy - s_ * cx - c * cy], [0, 0, 1.0]])
+    t30 = np.deg2rad(30)
+    HOMS = {"HS": np.array([[1.02, 0.01, 5.0], [0.015, 0.98, 7.0], [1e-5, 2e-5, 1.0]]),      # bench.py's H_S
+            "rot30": np.array([[np.cos(t30), -np.sin(t30), 100.0], [np.sin(t30), np.cos(t30), -50.0], [0, 0, 1.0]]),
+            "rot90": zoom(1.0, 90.0), "min1.5": zoom(1.5), "min1.9": zoom(1.9), "min2": zoom(2.0), "min3": zoom(3.0),
+            "scale1.5": np.diag([1 / 1.5, 1 / 1.5, 1.0]), "scale2": np.diag([0.5, 0.5, 1.0]), "scale3": np.diag([1 / 3.0, 1 / 3.0, 1.0])}
+    INV = {k: np.linalg.inv(h) for k, h in HOMS.items()}
+    MIXED = ["HS", "min1.5", "rot30", "min2", "min3", "rot90"]      # a per-image batch cycles through these: several shapes
+    DT = {"u8": torch.uint8, "f32": torch.float32, "f64": torch.float64, "bool": torch.bool, "i8": torch.int8, "u16": torch.uint16,
+          "i16": torch.int16, "i32": torch.int32, "u32": torch.uint32, "i64": torch.int64, "u64": torch.uint64, "f16": torch.float16}
+    assert set(DT.values()) == set(kernels.STITCH_DTYPE)
+    WIDTHS = (100, 127, 128, 255, 256, 257, 272, 273, 3771)
+
+    def row(tag, src, c, interp, out, ow=3771, hom="HS", batch=1, per_image=None, rows=None, exact=False, tune=None):
+        key = "|".join(str(v) for v in (tag, src, c, interp, out, ow, hom, batch, per_image or "-", "shard" if rows else "-",
+                                        "exact" if exact else "-", "%s=%d" % tune if tune else "-"))
+
+        def thunk():
+            lib = _lib.load()
+            inv = INV[hom] if not per_image else np.stack([INV[MIXED[i % len(MIXED)] if per_image == "mixed" else hom] for i in range(batch)])
+            # ow columns of bench.py's 2028-row grid; ow None: the frame scaled by 1 / s on its own (SW / s) x (SH / s) grid
+            s = float(hom[5:]) if ow is None else 0.0
+            grid = kernels.Grid(5, 5 + ow - 1, ow, 7, 2034, 2028) if ow else kernels.Grid(0, int(SW / s) - 1, int(SW / s), 0, int(SH / s) - 1, int(SH / s))
+            if tune: assert lib.rwh_lab_tune(getattr(_lib, "RWH_TUNE_WARP_" + tune[0]), tune[1]) == 0
+            try:
+                return kernels.warp_plan((batch, SH, SW, c), DT[src], inv, grid, (SH, SW), interp, DT[out], rows=rows, exact=exact)
+            except _lib.RwhError as e:
+                return int(re.search(r"\((-?\d+)\)$", str(e)).group(1))
+            finally:
+                if tune: assert lib.rwh_lab_tune(getattr(_lib, "RWH_TUNE_WARP_" + tune[0]), 0) == 0
+        return key, thunk
+
+    # A: the default mode on H_S -- every width for 3 and 4 channels; channel counts only the exact mode takes are refused
+    for src in ("u8", "f32"):
+        for interp in ("nn", "bilinear"):
+            for out in ("u8", "f32", "f64"):
+                for c in (3, 4):
+                    for ow in (WIDTHS if out != "f64" else (3771,)): yield row("A", src, c, interp, out, ow)
+                for c in (1, 5, 64): yield row("A", src, c, interp, out)
+    # B: other homographies (rotations, minification: the patch shapes and the halves form)
+    for hom in ("rot30", "rot90", "min1.5", "min1.9", "min2", "min3"):
+        for c in (3, 4):
+            for interp in ("nn", "bilinear"):
+                for out in ("u8", "f32"):
+                    for ow in (257, 3771): yield row("B", "u8", c, interp, out, ow, hom)
+    for hom in ("scale1.5", "scale2", "scale3"):
+        for c, interp, out, batch, per in ((3, "bilinear", "u8", 1, None), (3, "bilinear", "f32", 1, None), (3, "nn", "u8", 1, None),
+                                           (4, "bilinear", "u8", 1, None), (3, "bilinear", "u8", 4, "same")):
+            yield row("B", "u8", c, interp, out, None, hom, batch, per)
+    # C: the exact mode, every element type and channel count (nn: the source's type out; bilinear: float64 or uint8)
+    for src in DT:
+        for c in (1, 3, 4, 5, 64):
+            yield row("C", src, c, "nn", src, exact=True)
+            yield row("C", src, c, "bilinear", "f64", exact=True)
+            yield row("C", src, c, "bilinear", "u8", exact=True)
+    for src, out in (("i16", "f64"), ("u8", "f32"), ("f32", "u8")): yield row("C", src, 3, "nn", out, exact=True)       # refused
+    for ow in (100, 128): yield row("C", "u8", 3, "nn", "u8", ow, exact=True)
+    yield row("C", "f32", 5, "bilinear", "f32", exact=True)                                                           # refused
+    # D: batches with one homography, and with one per image (the same for all; mixed: different shapes in one call)
+    for batch in (1, 4, 32):
+        for per in (None, "same", "mixed"):
+            for interp in ("nn", "bilinear"):
+                for out in ("u8", "f32"):
+                    for c, widths in ((3, (100, 257, 3771)), (4, (100, 3771))):
+                        for ow in widths: yield row("D", "u8", c, interp, out, ow, "HS", batch, per)
+            for hom in ("min1.5", "rot30"): yield row("D", "u8", 3, "bilinear", "u8", 3771, hom, batch, per)
+            yield row("D", "f32", 3, "bilinear", "f32", 3771, "HS", batch, per)
+            yield row("D", "i16", 5, "bilinear", "f64", 3771, "HS", batch, per, exact=True)
+            yield row("D", "u8", 3, "bilinear", "f64", 3771, "HS", batch, per, exact=True)
+    # E: a row shard plans what the whole grid plans
+    for hom in ("HS", "rot30", "min1.5"):
+        for interp, out in (("bilinear", "u8"), ("bilinear", "f32"), ("nn", "u8")):
+            yield row("E", "u8", 3, interp, out, 3771, hom, rows=(500, 700))
+            yield row("E", "u8", 3, interp, out, 3771, hom, 4, "mixed", rows=(500, 700))
+    yield row("E", "u8", 4, "bilinear", "u8", 3771, "HS", rows=(500, 700))
+    yield row("E", "f32", 3, "bilinear", "f32", 3771, "HS", rows=(500, 700))
+    # F: the lab knobs the GPU tests set
+    for shape in (0, 5, 6, 7, 13, 14):
+        for hom in ("HS", "min1.5"):
+            for c, interp, out, batch, per in ((3, "bilinear", "u8", 1, None), (3, "bilinear", "f32", 1, None), (3, "nn", "u8", 1, None),
+                                               (4, "bilinear", "u8", 1, None), (3, "bilinear", "u8", 4, "same"), (3, "nn", "u8", 4, "same"),
+                                               (3, "bilinear", "u8", 4, "mixed"), (3, "bilinear", "f32", 4, "same")):
+                yield row("F", "u8", c, interp, out, 3771, hom, batch, per, tune=("SHAPE", shape))
+        yield row("F", "u8", 3, "bilinear", "u8", 100, "HS", tune=("SHAPE", shape))
+    for frames in (0, 1, 4, 104):
+        for batch in (1, 4, 32):
+            for hom in ("HS", "min1.5", "min3"):
+                for c, interp, out, per in ((3, "bilinear", "u8", None), (3, "bilinear", "f32", None), (3, "nn", "u8", None),
+                                            (4, "bilinear", "u8", None), (3, "bilinear", "u8", "same")):
+                    yield row("F", "u8", c, interp, out, 3771, hom, batch, per, tune=("FRAMES", frames))
+            yield row("F", "u8", 3, "bilinear", "u8", 272, "HS", batch, tune=("FRAMES", frames))
+            yield row("F", "u8", 3, "bilinear", "u8", 100, "HS", batch, tune=("FRAMES", frames))
+
+
+_PLAN_SWEEP = {      # planned kernel name (or refusal status) -> the rows of _plan_sweep_rows() that get it
+    "rwh::warp_generic<unsigned char, 3, unsigned char, 0>": (
+        "A|u8|3|nn|u8|100|HS|1|-|-|-|- A|u8|3|nn|u8|127|HS|1|-|-|-|- D|u8|3|nn|u8|100|HS|1|-|-|-|- D|u8|3|nn|u8|100|HS|1|same|-|-|- "
+        "D|u8|3|nn|u8|100|HS|1|mixed|-|-|- D|u8|3|nn|u8|100|HS|4|-|-|-|- D|u8|3|nn|u8|100|HS|4|same|-|-|- "
+        "D|u8|3|nn|u8|100|HS|4|mixed|-|-|- D|u8|3|nn|u8|100|HS|32|-|-|-|- D|u8|3|nn|u8|100|HS|32|same|-|-|- "
+        "D|u8|3|nn|u8|100|HS|32|mixed|-|-|- "),
+    "rwh::warp_rgb8_nn<6>": (
+        "A|u8|3|nn|u8|128|HS|1|-|-|-|- A|u8|3|nn|u8|255|HS|1|-|-|-|- A|u8|3|nn|u8|256|HS|1|-|-|-|- A|u8|3|nn|u8|257|HS|1|-|-|-|- "
+        "A|u8|3|nn|u8|272|HS|1|-|-|-|- A|u8|3|nn|u8|273|HS|1|-|-|-|- A|u8|3|nn|u8|3771|HS|1|-|-|-|- "
+        "C|u8|3|nn|u8|3771|HS|1|-|-|exact|- C|bool|3|nn|bool|3771|HS|1|-|-|exact|- C|u8|3|nn|u8|128|HS|1|-|-|exact|- "
+        "D|u8|3|nn|u8|257|HS|1|-|-|-|- D|u8|3|nn|u8|3771|HS|1|-|-|-|- D|u8|3|nn|u8|257|HS|1|same|-|-|- "
+        "D|u8|3|nn|u8|3771|HS|1|same|-|-|- D|u8|3|nn|u8|257|HS|1|mixed|-|-|- D|u8|3|nn|u8|3771|HS|1|mixed|-|-|- "
+        "D|u8|3|nn|u8|257|HS|4|-|-|-|- D|u8|3|nn|u8|3771|HS|4|-|-|-|- D|u8|3|nn|u8|257|HS|32|-|-|-|- D|u8|3|nn|u8|3771|HS|32|-|-|-|- "
+        "E|u8|3|nn|u8|3771|HS|1|-|shard|-|- F|u8|3|nn|u8|3771|HS|1|-|-|-|SHAPE=0 F|u8|3|nn|u8|3771|HS|1|-|-|-|SHAPE=6 "
+        "F|u8|3|nn|u8|3771|min1.5|1|-|-|-|SHAPE=6 F|u8|3|nn|u8|3771|HS|1|-|-|-|FRAMES=0 F|u8|3|nn|u8|3771|HS|4|-|-|-|FRAMES=0 "
+        "F|u8|3|nn|u8|3771|HS|32|-|-|-|FRAMES=0 F|u8|3|nn|u8|3771|HS|1|-|-|-|FRAMES=1 F|u8|3|nn|u8|3771|HS|4|-|-|-|FRAMES=1 "
+        "F|u8|3|nn|u8|3771|HS|32|-|-|-|FRAMES=1 F|u8|3|nn|u8|3771|HS|1|-|-|-|FRAMES=4 F|u8|3|nn|u8|3771|HS|4|-|-|-|FRAMES=4 "
+        "F|u8|3|nn|u8|3771|HS|32|-|-|-|FRAMES=4 F|u8|3|nn|u8|3771|HS|1|-|-|-|FRAMES=104 F|u8|3|nn|u8|3771|HS|4|-|-|-|FRAMES=104 "
+        "F|u8|3|nn|u8|3771|HS|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_generic<unsigned char, 4, unsigned char, 0>": (
+        "A|u8|4|nn|u8|100|HS|1|-|-|-|- A|u8|4|nn|u8|127|HS|1|-|-|-|- A|u8|4|nn|u8|128|HS|1|-|-|-|- A|u8|4|nn|u8|255|HS|1|-|-|-|- "
+        "A|u8|4|nn|u8|256|HS|1|-|-|-|- A|u8|4|nn|u8|257|HS|1|-|-|-|- A|u8|4|nn|u8|272|HS|1|-|-|-|- A|u8|4|nn|u8|273|HS|1|-|-|-|- "
+        "A|u8|4|nn|u8|3771|HS|1|-|-|-|- B|u8|4|nn|u8|257|rot30|1|-|-|-|- B|u8|4|nn|u8|3771|rot30|1|-|-|-|- "
+        "B|u8|4|nn|u8|257|rot90|1|-|-|-|- B|u8|4|nn|u8|3771|rot90|1|-|-|-|- B|u8|4|nn|u8|257|min1.5|1|-|-|-|- "
+        "B|u8|4|nn|u8|3771|min1.5|1|-|-|-|- B|u8|4|nn|u8|257|min1.9|1|-|-|-|- B|u8|4|nn|u8|3771|min1.9|1|-|-|-|- "
+        "B|u8|4|nn|u8|257|min2|1|-|-|-|- B|u8|4|nn|u8|3771|min2|1|-|-|-|- B|u8|4|nn|u8|257|min3|1|-|-|-|- "
+        "B|u8|4|nn|u8|3771|min3|1|-|-|-|- D|u8|4|nn|u8|100|HS|1|-|-|-|- D|u8|4|nn|u8|3771|HS|1|-|-|-|- "
+        "D|u8|4|nn|u8|100|HS|1|same|-|-|- D|u8|4|nn|u8|3771|HS|1|same|-|-|- D|u8|4|nn|u8|100|HS|1|mixed|-|-|- "
+        "D|u8|4|nn|u8|3771|HS|1|mixed|-|-|- D|u8|4|nn|u8|100|HS|4|-|-|-|- D|u8|4|nn|u8|3771|HS|4|-|-|-|- "
+        "D|u8|4|nn|u8|100|HS|4|same|-|-|- D|u8|4|nn|u8|3771|HS|4|same|-|-|- D|u8|4|nn|u8|100|HS|4|mixed|-|-|- "
+        "D|u8|4|nn|u8|3771|HS|4|mixed|-|-|- D|u8|4|nn|u8|100|HS|32|-|-|-|- D|u8|4|nn|u8|3771|HS|32|-|-|-|- "
+        "D|u8|4|nn|u8|100|HS|32|same|-|-|- D|u8|4|nn|u8|3771|HS|32|same|-|-|- D|u8|4|nn|u8|100|HS|32|mixed|-|-|- "
+        "D|u8|4|nn|u8|3771|HS|32|mixed|-|-|- "),
+    -2: (
+        "A|u8|1|nn|u8|3771|HS|1|-|-|-|- A|u8|5|nn|u8|3771|HS|1|-|-|-|- A|u8|64|nn|u8|3771|HS|1|-|-|-|- A|u8|3|nn|f32|100|HS|1|-|-|-|- "
+        "A|u8|3|nn|f32|127|HS|1|-|-|-|- A|u8|3|nn|f32|128|HS|1|-|-|-|- A|u8|3|nn|f32|255|HS|1|-|-|-|- A|u8|3|nn|f32|256|HS|1|-|-|-|- "
+        "A|u8|3|nn|f32|257|HS|1|-|-|-|- A|u8|3|nn|f32|272|HS|1|-|-|-|- A|u8|3|nn|f32|273|HS|1|-|-|-|- A|u8|3|nn|f32|3771|HS|1|-|-|-|- "
+        "A|u8|4|nn|f32|100|HS|1|-|-|-|- A|u8|4|nn|f32|127|HS|1|-|-|-|- A|u8|4|nn|f32|128|HS|1|-|-|-|- A|u8|4|nn|f32|255|HS|1|-|-|-|- "
+        "A|u8|4|nn|f32|256|HS|1|-|-|-|- A|u8|4|nn|f32|257|HS|1|-|-|-|- A|u8|4|nn|f32|272|HS|1|-|-|-|- A|u8|4|nn|f32|273|HS|1|-|-|-|- "
+        "A|u8|4|nn|f32|3771|HS|1|-|-|-|- A|u8|1|nn|f32|3771|HS|1|-|-|-|- A|u8|5|nn|f32|3771|HS|1|-|-|-|- "
+        "A|u8|64|nn|f32|3771|HS|1|-|-|-|- A|u8|3|nn|f64|3771|HS|1|-|-|-|- A|u8|4|nn|f64|3771|HS|1|-|-|-|- "
+        "A|u8|1|nn|f64|3771|HS|1|-|-|-|- A|u8|5|nn|f64|3771|HS|1|-|-|-|- A|u8|64|nn|f64|3771|HS|1|-|-|-|- "
+        "A|u8|1|bilinear|u8|3771|HS|1|-|-|-|- A|u8|5|bilinear|u8|3771|HS|1|-|-|-|- A|u8|64|bilinear|u8|3771|HS|1|-|-|-|- "
+        "A|u8|1|bilinear|f32|3771|HS|1|-|-|-|- A|u8|5|bilinear|f32|3771|HS|1|-|-|-|- A|u8|64|bilinear|f32|3771|HS|1|-|-|-|- "
+        "A|u8|3|bilinear|f64|3771|HS|1|-|-|-|- A|u8|4|bilinear|f64|3771|HS|1|-|-|-|- A|u8|1|bilinear|f64|3771|HS|1|-|-|-|- "
+        "A|u8|5|bilinear|f64|3771|HS|1|-|-|-|- A|u8|64|bilinear|f64|3771|HS|1|-|-|-|- A|f32|3|nn|u8|100|HS|1|-|-|-|- "
+        "A|f32|3|nn|u8|127|HS|1|-|-|-|- A|f32|3|nn|u8|128|HS|1|-|-|-|- A|f32|3|nn|u8|255|HS|1|-|-|-|- A|f32|3|nn|u8|256|HS|1|-|-|-|- "
+        "A|f32|3|nn|u8|257|HS|1|-|-|-|- A|f32|3|nn|u8|272|HS|1|-|-|-|- A|f32|3|nn|u8|273|HS|1|-|-|-|- A|f32|3|nn|u8|3771|HS|1|-|-|-|- "
+        "A|f32|4|nn|u8|100|HS|1|-|-|-|- A|f32|4|nn|u8|127|HS|1|-|-|-|- A|f32|4|nn|u8|128|HS|1|-|-|-|- A|f32|4|nn|u8|255|HS|1|-|-|-|- "
+        "A|f32|4|nn|u8|256|HS|1|-|-|-|- A|f32|4|nn|u8|257|HS|1|-|-|-|- A|f32|4|nn|u8|272|HS|1|-|-|-|- A|f32|4|nn|u8|273|HS|1|-|-|-|- "
+        "A|f32|4|nn|u8|3771|HS|1|-|-|-|- A|f32|1|nn|u8|3771|HS|1|-|-|-|- A|f32|5|nn|u8|3771|HS|1|-|-|-|- "
+        "A|f32|64|nn|u8|3771|HS|1|-|-|-|- A|f32|1|nn|f32|3771|HS|1|-|-|-|- A|f32|5|nn|f32|3771|HS|1|-|-|-|- "
+        "A|f32|64|nn|f32|3771|HS|1|-|-|-|- A|f32|3|nn|f64|3771|HS|1|-|-|-|- A|f32|4|nn|f64|3771|HS|1|-|-|-|- "
+        "A|f32|1|nn|f64|3771|HS|1|-|-|-|- A|f32|5|nn|f64|3771|HS|1|-|-|-|- A|f32|64|nn|f64|3771|HS|1|-|-|-|- "
+        "A|f32|1|bilinear|u8|3771|HS|1|-|-|-|- A|f32|5|bilinear|u8|3771|HS|1|-|-|-|- A|f32|64|bilinear|u8|3771|HS|1|-|-|-|- "
+        "A|f32|1|bilinear|f32|3771|HS|1|-|-|-|- A|f32|5|bilinear|f32|3771|HS|1|-|-|-|- A|f32|64|bilinear|f32|3771|HS|1|-|-|-|- "
+        "A|f32|3|bilinear|f64|3771|HS|1|-|-|-|- A|f32|4|bilinear|f64|3771|HS|1|-|-|-|- A|f32|1|bilinear|f64|3771|HS|1|-|-|-|- "
+        "A|f32|5|bilinear|f64|3771|HS|1|-|-|-|- A|f32|64|bilinear|f64|3771|HS|1|-|-|-|- B|u8|3|nn|f32|257|rot30|1|-|-|-|- "
+        "B|u8|3|nn|f32|3771|rot30|1|-|-|-|- B|u8|4|nn|f32|257|rot30|1|-|-|-|- B|u8|4|nn|f32|3771|rot30|1|-|-|-|- "
+        "B|u8|3|nn|f32|257|rot90|1|-|-|-|- B|u8|3|nn|f32|3771|rot90|1|-|-|-|- B|u8|4|nn|f32|257|rot90|1|-|-|-|- "
+        "B|u8|4|nn|f32|3771|rot90|1|-|-|-|- B|u8|3|nn|f32|257|min1.5|1|-|-|-|- B|u8|3|nn|f32|3771|min1.5|1|-|-|-|- "
+        "B|u8|4|nn|f32|257|min1.5|1|-|-|-|- B|u8|4|nn|f32|3771|min1.5|1|-|-|-|- B|u8|3|nn|f32|257|min1.9|1|-|-|-|- "
+        "B|u8|3|nn|f32|3771|min1.9|1|-|-|-|- B|u8|4|nn|f32|257|min1.9|1|-|-|-|- B|u8|4|nn|f32|3771|min1.9|1|-|-|-|- "
+        "B|u8|3|nn|f32|257|min2|1|-|-|-|- B|u8|3|nn|f32|3771|min2|1|-|-|-|- B|u8|4|nn|f32|257|min2|1|-|-|-|- "
+        "B|u8|4|nn|f32|3771|min2|1|-|-|-|- B|u8|3|nn|f32|257|min3|1|-|-|-|- B|u8|3|nn|f32|3771|min3|1|-|-|-|- "
+        "B|u8|4|nn|f32|257|min3|1|-|-|-|- B|u8|4|nn|f32|3771|min3|1|-|-|-|- C|i16|3|nn|f64|3771|HS|1|-|-|exact|- "
+        "C|u8|3|nn|f32|3771|HS|1|-|-|exact|- C|f32|3|nn|u8|3771|HS|1|-|-|exact|- C|f32|5|bilinear|f32|3771|HS|1|-|-|exact|- "
+        "D|u8|3|nn|f32|100|HS|1|-|-|-|- D|u8|3|nn|f32|257|HS|1|-|-|-|- D|u8|3|nn|f32|3771|HS|1|-|-|-|- D|u8|4|nn|f32|100|HS|1|-|-|-|- "
+        "D|u8|4|nn|f32|3771|HS|1|-|-|-|- D|u8|3|nn|f32|100|HS|1|same|-|-|- D|u8|3|nn|f32|257|HS|1|same|-|-|- "
+        "D|u8|3|nn|f32|3771|HS|1|same|-|-|- D|u8|4|nn|f32|100|HS|1|same|-|-|- D|u8|4|nn|f32|3771|HS|1|same|-|-|- "
+        "D|u8|3|nn|f32|100|HS|1|mixed|-|-|- D|u8|3|nn|f32|257|HS|1|mixed|-|-|- D|u8|3|nn|f32|3771|HS|1|mixed|-|-|- "
+        "D|u8|4|nn|f32|100|HS|1|mixed|-|-|- D|u8|4|nn|f32|3771|HS|1|mixed|-|-|- D|u8|3|nn|f32|100|HS|4|-|-|-|- "
+        "D|u8|3|nn|f32|257|HS|4|-|-|-|- D|u8|3|nn|f32|3771|HS|4|-|-|-|- D|u8|4|nn|f32|100|HS|4|-|-|-|- "
+        "D|u8|4|nn|f32|3771|HS|4|-|-|-|- D|u8|3|nn|f32|100|HS|4|same|-|-|- D|u8|3|nn|f32|257|HS|4|same|-|-|- "
+        "D|u8|3|nn|f32|3771|HS|4|same|-|-|- D|u8|4|nn|f32|100|HS|4|same|-|-|- D|u8|4|nn|f32|3771|HS|4|same|-|-|- "
+        "D|u8|3|nn|f32|100|HS|4|mixed|-|-|- D|u8|3|nn|f32|257|HS|4|mixed|-|-|- D|u8|3|nn|f32|3771|HS|4|mixed|-|-|- "
+        "D|u8|4|nn|f32|100|HS|4|mixed|-|-|- D|u8|4|nn|f32|3771|HS|4|mixed|-|-|- D|u8|3|nn|f32|100|HS|32|-|-|-|- "
+        "D|u8|3|nn|f32|257|HS|32|-|-|-|- D|u8|3|nn|f32|3771|HS|32|-|-|-|- D|u8|4|nn|f32|100|HS|32|-|-|-|- "
+        "D|u8|4|nn|f32|3771|HS|32|-|-|-|- D|u8|3|nn|f32|100|HS|32|same|-|-|- D|u8|3|nn|f32|257|HS|32|same|-|-|- "
+        "D|u8|3|nn|f32|3771|HS|32|same|-|-|- D|u8|4|nn|f32|100|HS|32|same|-|-|- D|u8|4|nn|f32|3771|HS|32|same|-|-|- "
+        "D|u8|3|nn|f32|100|HS|32|mixed|-|-|- D|u8|3|nn|f32|257|HS|32|mixed|-|-|- D|u8|3|nn|f32|3771|HS|32|mixed|-|-|- "
+        "D|u8|4|nn|f32|100|HS|32|mixed|-|-|- D|u8|4|nn|f32|3771|HS|32|mixed|-|-|- "),
+    "rwh::warp_rgb8_fast<unsigned char>": (
+        "A|u8|3|bilinear|u8|100|HS|1|-|-|-|- A|u8|3|bilinear|u8|127|HS|1|-|-|-|- D|u8|3|bilinear|u8|100|HS|1|-|-|-|- "
+        "D|u8|3|bilinear|u8|100|HS|1|same|-|-|- D|u8|3|bilinear|u8|100|HS|1|mixed|-|-|- D|u8|3|bilinear|u8|100|HS|4|-|-|-|- "
+        "D|u8|3|bilinear|u8|100|HS|4|same|-|-|- D|u8|3|bilinear|u8|100|HS|4|mixed|-|-|- D|u8|3|bilinear|u8|100|HS|32|-|-|-|- "
+        "D|u8|3|bilinear|u8|100|HS|32|same|-|-|- D|u8|3|bilinear|u8|100|HS|32|mixed|-|-|- F|u8|3|bilinear|u8|100|HS|1|-|-|-|SHAPE=0 "
+        "F|u8|3|bilinear|u8|100|HS|1|-|-|-|SHAPE=5 F|u8|3|bilinear|u8|100|HS|1|-|-|-|SHAPE=6 "
+        "F|u8|3|bilinear|u8|100|HS|1|-|-|-|SHAPE=7 F|u8|3|bilinear|u8|100|HS|1|-|-|-|SHAPE=13 "
+        "F|u8|3|bilinear|u8|100|HS|1|-|-|-|SHAPE=14 F|u8|3|bilinear|u8|100|HS|1|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|100|HS|4|-|-|-|FRAMES=0 F|u8|3|bilinear|u8|100|HS|32|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|100|HS|1|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|100|HS|4|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|100|HS|32|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|100|HS|1|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|100|HS|4|-|-|-|FRAMES=4 F|u8|3|bilinear|u8|100|HS|32|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|100|HS|1|-|-|-|FRAMES=104 F|u8|3|bilinear|u8|100|HS|4|-|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|u8|100|HS|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast8<unsigned char, 6>": (
+        "A|u8|3|bilinear|u8|128|HS|1|-|-|-|- A|u8|3|bilinear|u8|255|HS|1|-|-|-|- A|u8|3|bilinear|u8|256|HS|1|-|-|-|- "
+        "A|u8|3|bilinear|u8|257|HS|1|-|-|-|- A|u8|3|bilinear|u8|272|HS|1|-|-|-|- A|u8|3|bilinear|u8|273|HS|1|-|-|-|- "
+        "A|u8|3|bilinear|u8|3771|HS|1|-|-|-|- D|u8|3|bilinear|u8|257|HS|1|-|-|-|- D|u8|3|bilinear|u8|3771|HS|1|-|-|-|- "
+        "D|u8|3|bilinear|u8|257|HS|1|same|-|-|- D|u8|3|bilinear|u8|3771|HS|1|same|-|-|- D|u8|3|bilinear|u8|257|HS|1|mixed|-|-|- "
+        "D|u8|3|bilinear|u8|3771|HS|1|mixed|-|-|- D|u8|3|bilinear|u8|3771|min1.5|1|mixed|-|-|- "
+        "D|u8|3|bilinear|u8|3771|rot30|1|mixed|-|-|- D|u8|3|bilinear|u8|257|HS|4|-|-|-|- D|u8|3|bilinear|u8|3771|HS|4|-|-|-|- "
+        "D|u8|3|bilinear|u8|257|HS|32|-|-|-|- D|u8|3|bilinear|u8|3771|HS|32|-|-|-|- E|u8|3|bilinear|u8|3771|HS|1|-|shard|-|- "
+        "F|u8|3|bilinear|u8|3771|HS|1|-|-|-|SHAPE=0 F|u8|3|bilinear|u8|3771|HS|1|-|-|-|SHAPE=6 "
+        "F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=6 F|u8|3|bilinear|u8|3771|HS|1|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|HS|1|same|-|-|FRAMES=0 F|u8|3|bilinear|u8|272|HS|1|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|HS|4|-|-|-|FRAMES=0 F|u8|3|bilinear|u8|272|HS|4|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|HS|32|-|-|-|FRAMES=0 F|u8|3|bilinear|u8|272|HS|32|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|HS|1|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|HS|1|same|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|272|HS|1|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|HS|4|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|272|HS|4|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|HS|32|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|272|HS|32|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|HS|1|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|HS|1|same|-|-|FRAMES=4 F|u8|3|bilinear|u8|272|HS|1|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|HS|1|-|-|-|FRAMES=104 F|u8|3|bilinear|u8|3771|HS|1|same|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|u8|272|HS|1|-|-|-|FRAMES=104 "),
+    "rwh::warp_generic<unsigned char, 4, unsigned char, 1>": (
+        "A|u8|4|bilinear|u8|100|HS|1|-|-|-|- A|u8|4|bilinear|u8|127|HS|1|-|-|-|- D|u8|4|bilinear|u8|100|HS|1|-|-|-|- "
+        "D|u8|4|bilinear|u8|100|HS|1|same|-|-|- D|u8|4|bilinear|u8|100|HS|1|mixed|-|-|- D|u8|4|bilinear|u8|100|HS|4|-|-|-|- "
+        "D|u8|4|bilinear|u8|100|HS|4|same|-|-|- D|u8|4|bilinear|u8|100|HS|4|mixed|-|-|- D|u8|4|bilinear|u8|100|HS|32|-|-|-|- "
+        "D|u8|4|bilinear|u8|100|HS|32|same|-|-|- D|u8|4|bilinear|u8|100|HS|32|mixed|-|-|- "),
+    "rwh::warp_rgba8_fast8<6>": (
+        "A|u8|4|bilinear|u8|128|HS|1|-|-|-|- A|u8|4|bilinear|u8|255|HS|1|-|-|-|- A|u8|4|bilinear|u8|256|HS|1|-|-|-|- "
+        "A|u8|4|bilinear|u8|257|HS|1|-|-|-|- A|u8|4|bilinear|u8|272|HS|1|-|-|-|- A|u8|4|bilinear|u8|273|HS|1|-|-|-|- "
+        "A|u8|4|bilinear|u8|3771|HS|1|-|-|-|- D|u8|4|bilinear|u8|3771|HS|1|-|-|-|- D|u8|4|bilinear|u8|3771|HS|1|same|-|-|- "
+        "D|u8|4|bilinear|u8|3771|HS|1|mixed|-|-|- D|u8|4|bilinear|u8|3771|HS|4|-|-|-|- D|u8|4|bilinear|u8|3771|HS|4|same|-|-|- "
+        "D|u8|4|bilinear|u8|3771|HS|4|mixed|-|-|- D|u8|4|bilinear|u8|3771|HS|32|-|-|-|- D|u8|4|bilinear|u8|3771|HS|32|same|-|-|- "
+        "D|u8|4|bilinear|u8|3771|HS|32|mixed|-|-|- E|u8|4|bilinear|u8|3771|HS|1|-|shard|-|- "
+        "F|u8|4|bilinear|u8|3771|HS|1|-|-|-|SHAPE=0 F|u8|4|bilinear|u8|3771|HS|1|-|-|-|SHAPE=6 "
+        "F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=6 F|u8|4|bilinear|u8|3771|HS|1|-|-|-|FRAMES=0 "
+        "F|u8|4|bilinear|u8|3771|HS|4|-|-|-|FRAMES=0 F|u8|4|bilinear|u8|3771|HS|32|-|-|-|FRAMES=0 "
+        "F|u8|4|bilinear|u8|3771|HS|1|-|-|-|FRAMES=1 F|u8|4|bilinear|u8|3771|HS|4|-|-|-|FRAMES=1 "
+        "F|u8|4|bilinear|u8|3771|HS|32|-|-|-|FRAMES=1 F|u8|4|bilinear|u8|3771|HS|1|-|-|-|FRAMES=4 "
+        "F|u8|4|bilinear|u8|3771|HS|4|-|-|-|FRAMES=4 F|u8|4|bilinear|u8|3771|HS|32|-|-|-|FRAMES=4 "
+        "F|u8|4|bilinear|u8|3771|HS|1|-|-|-|FRAMES=104 F|u8|4|bilinear|u8|3771|HS|4|-|-|-|FRAMES=104 "
+        "F|u8|4|bilinear|u8|3771|HS|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast<float>": (
+        "A|u8|3|bilinear|f32|100|HS|1|-|-|-|- A|u8|3|bilinear|f32|127|HS|1|-|-|-|- D|u8|3|bilinear|f32|100|HS|1|-|-|-|- "
+        "D|u8|3|bilinear|f32|100|HS|1|same|-|-|- D|u8|3|bilinear|f32|100|HS|1|mixed|-|-|- D|u8|3|bilinear|f32|100|HS|4|-|-|-|- "
+        "D|u8|3|bilinear|f32|100|HS|4|same|-|-|- D|u8|3|bilinear|f32|100|HS|4|mixed|-|-|- D|u8|3|bilinear|f32|100|HS|32|-|-|-|- "
+        "D|u8|3|bilinear|f32|100|HS|32|same|-|-|- D|u8|3|bilinear|f32|100|HS|32|mixed|-|-|- "),
+    "rwh::warp_rgb8_fast8<float, 6>": (
+        "A|u8|3|bilinear|f32|128|HS|1|-|-|-|- A|u8|3|bilinear|f32|255|HS|1|-|-|-|- A|u8|3|bilinear|f32|256|HS|1|-|-|-|- "
+        "A|u8|3|bilinear|f32|257|HS|1|-|-|-|- A|u8|3|bilinear|f32|272|HS|1|-|-|-|- A|u8|3|bilinear|f32|273|HS|1|-|-|-|- "
+        "A|u8|3|bilinear|f32|3771|HS|1|-|-|-|- D|u8|3|bilinear|f32|257|HS|1|-|-|-|- D|u8|3|bilinear|f32|3771|HS|1|-|-|-|- "
+        "D|u8|3|bilinear|f32|257|HS|1|same|-|-|- D|u8|3|bilinear|f32|3771|HS|1|same|-|-|- D|u8|3|bilinear|f32|257|HS|1|mixed|-|-|- "
+        "D|u8|3|bilinear|f32|3771|HS|1|mixed|-|-|- D|u8|3|bilinear|f32|257|HS|4|-|-|-|- D|u8|3|bilinear|f32|3771|HS|4|-|-|-|- "
+        "D|u8|3|bilinear|f32|257|HS|32|-|-|-|- D|u8|3|bilinear|f32|3771|HS|32|-|-|-|- E|u8|3|bilinear|f32|3771|HS|1|-|shard|-|- "
+        "F|u8|3|bilinear|f32|3771|HS|1|-|-|-|SHAPE=0 F|u8|3|bilinear|f32|3771|HS|1|-|-|-|SHAPE=6 "
+        "F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|SHAPE=6 F|u8|3|bilinear|f32|3771|HS|1|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|f32|3771|HS|4|-|-|-|FRAMES=0 F|u8|3|bilinear|f32|3771|HS|32|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|f32|3771|HS|1|-|-|-|FRAMES=1 F|u8|3|bilinear|f32|3771|HS|4|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|f32|3771|HS|32|-|-|-|FRAMES=1 F|u8|3|bilinear|f32|3771|HS|1|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|f32|3771|HS|4|-|-|-|FRAMES=4 F|u8|3|bilinear|f32|3771|HS|32|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|f32|3771|HS|1|-|-|-|FRAMES=104 F|u8|3|bilinear|f32|3771|HS|4|-|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|f32|3771|HS|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_generic<unsigned char, 4, float, 1>": (
+        "A|u8|4|bilinear|f32|100|HS|1|-|-|-|- A|u8|4|bilinear|f32|127|HS|1|-|-|-|- A|u8|4|bilinear|f32|128|HS|1|-|-|-|- "
+        "A|u8|4|bilinear|f32|255|HS|1|-|-|-|- A|u8|4|bilinear|f32|256|HS|1|-|-|-|- A|u8|4|bilinear|f32|257|HS|1|-|-|-|- "
+        "A|u8|4|bilinear|f32|272|HS|1|-|-|-|- A|u8|4|bilinear|f32|273|HS|1|-|-|-|- A|u8|4|bilinear|f32|3771|HS|1|-|-|-|- "
+        "B|u8|4|bilinear|f32|257|rot30|1|-|-|-|- B|u8|4|bilinear|f32|3771|rot30|1|-|-|-|- B|u8|4|bilinear|f32|257|rot90|1|-|-|-|- "
+        "B|u8|4|bilinear|f32|3771|rot90|1|-|-|-|- B|u8|4|bilinear|f32|257|min1.5|1|-|-|-|- B|u8|4|bilinear|f32|3771|min1.5|1|-|-|-|- "
+        "B|u8|4|bilinear|f32|257|min1.9|1|-|-|-|- B|u8|4|bilinear|f32|3771|min1.9|1|-|-|-|- B|u8|4|bilinear|f32|257|min2|1|-|-|-|- "
+        "B|u8|4|bilinear|f32|3771|min2|1|-|-|-|- B|u8|4|bilinear|f32|257|min3|1|-|-|-|- B|u8|4|bilinear|f32|3771|min3|1|-|-|-|- "
+        "D|u8|4|bilinear|f32|100|HS|1|-|-|-|- D|u8|4|bilinear|f32|3771|HS|1|-|-|-|- D|u8|4|bilinear|f32|100|HS|1|same|-|-|- "
+        "D|u8|4|bilinear|f32|3771|HS|1|same|-|-|- D|u8|4|bilinear|f32|100|HS|1|mixed|-|-|- D|u8|4|bilinear|f32|3771|HS|1|mixed|-|-|- "
+        "D|u8|4|bilinear|f32|100|HS|4|-|-|-|- D|u8|4|bilinear|f32|3771|HS|4|-|-|-|- D|u8|4|bilinear|f32|100|HS|4|same|-|-|- "
+        "D|u8|4|bilinear|f32|3771|HS|4|same|-|-|- D|u8|4|bilinear|f32|100|HS|4|mixed|-|-|- D|u8|4|bilinear|f32|3771|HS|4|mixed|-|-|- "
+        "D|u8|4|bilinear|f32|100|HS|32|-|-|-|- D|u8|4|bilinear|f32|3771|HS|32|-|-|-|- D|u8|4|bilinear|f32|100|HS|32|same|-|-|- "
+        "D|u8|4|bilinear|f32|3771|HS|32|same|-|-|- D|u8|4|bilinear|f32|100|HS|32|mixed|-|-|- "
+        "D|u8|4|bilinear|f32|3771|HS|32|mixed|-|-|- "),
+    "rwh::warp_generic<float, 3, float, 0>": (
+        "A|f32|3|nn|f32|100|HS|1|-|-|-|- A|f32|3|nn|f32|127|HS|1|-|-|-|- A|f32|3|nn|f32|128|HS|1|-|-|-|- "
+        "A|f32|3|nn|f32|255|HS|1|-|-|-|- A|f32|3|nn|f32|256|HS|1|-|-|-|- A|f32|3|nn|f32|257|HS|1|-|-|-|- "
+        "A|f32|3|nn|f32|272|HS|1|-|-|-|- A|f32|3|nn|f32|273|HS|1|-|-|-|- A|f32|3|nn|f32|3771|HS|1|-|-|-|- "),
+    "rwh::warp_generic<float, 4, float, 0>": (
+        "A|f32|4|nn|f32|100|HS|1|-|-|-|- A|f32|4|nn|f32|127|HS|1|-|-|-|- A|f32|4|nn|f32|128|HS|1|-|-|-|- "
+        "A|f32|4|nn|f32|255|HS|1|-|-|-|- A|f32|4|nn|f32|256|HS|1|-|-|-|- A|f32|4|nn|f32|257|HS|1|-|-|-|- "
+        "A|f32|4|nn|f32|272|HS|1|-|-|-|- A|f32|4|nn|f32|273|HS|1|-|-|-|- A|f32|4|nn|f32|3771|HS|1|-|-|-|- "),
+    "rwh::warp_generic<float, 3, unsigned char, 1>": (
+        "A|f32|3|bilinear|u8|100|HS|1|-|-|-|- A|f32|3|bilinear|u8|127|HS|1|-|-|-|- A|f32|3|bilinear|u8|128|HS|1|-|-|-|- "
+        "A|f32|3|bilinear|u8|255|HS|1|-|-|-|- A|f32|3|bilinear|u8|256|HS|1|-|-|-|- A|f32|3|bilinear|u8|257|HS|1|-|-|-|- "
+        "A|f32|3|bilinear|u8|272|HS|1|-|-|-|- A|f32|3|bilinear|u8|273|HS|1|-|-|-|- A|f32|3|bilinear|u8|3771|HS|1|-|-|-|- "),
+    "rwh::warp_generic<float, 4, unsigned char, 1>": (
+        "A|f32|4|bilinear|u8|100|HS|1|-|-|-|- A|f32|4|bilinear|u8|127|HS|1|-|-|-|- A|f32|4|bilinear|u8|128|HS|1|-|-|-|- "
+        "A|f32|4|bilinear|u8|255|HS|1|-|-|-|- A|f32|4|bilinear|u8|256|HS|1|-|-|-|- A|f32|4|bilinear|u8|257|HS|1|-|-|-|- "
+        "A|f32|4|bilinear|u8|272|HS|1|-|-|-|- A|f32|4|bilinear|u8|273|HS|1|-|-|-|- A|f32|4|bilinear|u8|3771|HS|1|-|-|-|- "),
+    "rwh::warp_generic<float, 3, float, 1>": (
+        "A|f32|3|bilinear|f32|100|HS|1|-|-|-|- A|f32|3|bilinear|f32|127|HS|1|-|-|-|- A|f32|3|bilinear|f32|128|HS|1|-|-|-|- "
+        "A|f32|3|bilinear|f32|255|HS|1|-|-|-|- A|f32|3|bilinear|f32|256|HS|1|-|-|-|- A|f32|3|bilinear|f32|257|HS|1|-|-|-|- "
+        "A|f32|3|bilinear|f32|272|HS|1|-|-|-|- A|f32|3|bilinear|f32|273|HS|1|-|-|-|- A|f32|3|bilinear|f32|3771|HS|1|-|-|-|- "
+        "D|f32|3|bilinear|f32|3771|HS|1|-|-|-|- D|f32|3|bilinear|f32|3771|HS|1|same|-|-|- D|f32|3|bilinear|f32|3771|HS|1|mixed|-|-|- "
+        "D|f32|3|bilinear|f32|3771|HS|4|-|-|-|- D|f32|3|bilinear|f32|3771|HS|4|same|-|-|- D|f32|3|bilinear|f32|3771|HS|4|mixed|-|-|- "
+        "D|f32|3|bilinear|f32|3771|HS|32|-|-|-|- D|f32|3|bilinear|f32|3771|HS|32|same|-|-|- "
+        "D|f32|3|bilinear|f32|3771|HS|32|mixed|-|-|- E|f32|3|bilinear|f32|3771|HS|1|-|shard|-|- "),
+    "rwh::warp_generic<float, 4, float, 1>": (
+        "A|f32|4|bilinear|f32|100|HS|1|-|-|-|- A|f32|4|bilinear|f32|127|HS|1|-|-|-|- A|f32|4|bilinear|f32|128|HS|1|-|-|-|- "
+        "A|f32|4|bilinear|f32|255|HS|1|-|-|-|- A|f32|4|bilinear|f32|256|HS|1|-|-|-|- A|f32|4|bilinear|f32|257|HS|1|-|-|-|- "
+        "A|f32|4|bilinear|f32|272|HS|1|-|-|-|- A|f32|4|bilinear|f32|273|HS|1|-|-|-|- A|f32|4|bilinear|f32|3771|HS|1|-|-|-|- "),
+    "rwh::warp_rgb8_nn<5>": (
+        "B|u8|3|nn|u8|257|rot30|1|-|-|-|- B|u8|3|nn|u8|3771|rot30|1|-|-|-|- B|u8|3|nn|u8|257|rot90|1|-|-|-|- "
+        "B|u8|3|nn|u8|3771|rot90|1|-|-|-|- E|u8|3|nn|u8|3771|rot30|1|-|shard|-|- F|u8|3|nn|u8|3771|HS|1|-|-|-|SHAPE=5 "
+        "F|u8|3|nn|u8|3771|min1.5|1|-|-|-|SHAPE=5 "),
+    "rwh::warp_rgb8_fast8<unsigned char, 5>": (
+        "B|u8|3|bilinear|u8|257|rot30|1|-|-|-|- B|u8|3|bilinear|u8|3771|rot30|1|-|-|-|- B|u8|3|bilinear|u8|257|rot90|1|-|-|-|- "
+        "B|u8|3|bilinear|u8|3771|rot90|1|-|-|-|- D|u8|3|bilinear|u8|3771|rot30|1|-|-|-|- D|u8|3|bilinear|u8|3771|rot30|1|same|-|-|- "
+        "D|u8|3|bilinear|u8|3771|rot30|4|-|-|-|- D|u8|3|bilinear|u8|3771|rot30|32|-|-|-|- E|u8|3|bilinear|u8|3771|rot30|1|-|shard|-|- "
+        "F|u8|3|bilinear|u8|3771|HS|1|-|-|-|SHAPE=5 F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=5 "),
+    "rwh::warp_rgb8_fast8<float, 5>": (
+        "B|u8|3|bilinear|f32|257|rot30|1|-|-|-|- B|u8|3|bilinear|f32|3771|rot30|1|-|-|-|- B|u8|3|bilinear|f32|257|rot90|1|-|-|-|- "
+        "B|u8|3|bilinear|f32|3771|rot90|1|-|-|-|- E|u8|3|bilinear|f32|3771|rot30|1|-|shard|-|- "
+        "F|u8|3|bilinear|f32|3771|HS|1|-|-|-|SHAPE=5 F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|SHAPE=5 "),
+    "rwh::warp_rgba8_fast8<5>": (
+        "B|u8|4|bilinear|u8|257|rot30|1|-|-|-|- B|u8|4|bilinear|u8|3771|rot30|1|-|-|-|- B|u8|4|bilinear|u8|257|rot90|1|-|-|-|- "
+        "B|u8|4|bilinear|u8|3771|rot90|1|-|-|-|- F|u8|4|bilinear|u8|3771|HS|1|-|-|-|SHAPE=5 "
+        "F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=5 "),
+    "rwh::warp_rgb8_nn<7>": (
+        "B|u8|3|nn|u8|257|min1.5|1|-|-|-|- B|u8|3|nn|u8|3771|min1.5|1|-|-|-|- B|u8|3|nn|u8|257|min1.9|1|-|-|-|- "
+        "B|u8|3|nn|u8|3771|min1.9|1|-|-|-|- B|u8|3|nn|u8|257|min2|1|-|-|-|- B|u8|3|nn|u8|3771|min2|1|-|-|-|- "
+        "B|u8|3|nn|u8|257|min3|1|-|-|-|- B|u8|3|nn|u8|3771|min3|1|-|-|-|- B|u8|3|nn|u8|None|scale1.5|1|-|-|-|- "
+        "B|u8|3|nn|u8|None|scale2|1|-|-|-|- B|u8|3|nn|u8|None|scale3|1|-|-|-|- E|u8|3|nn|u8|3771|min1.5|1|-|shard|-|- "
+        "F|u8|3|nn|u8|3771|min1.5|1|-|-|-|SHAPE=0 F|u8|3|nn|u8|3771|HS|1|-|-|-|SHAPE=7 F|u8|3|nn|u8|3771|min1.5|1|-|-|-|SHAPE=7 "
+        "F|u8|3|nn|u8|3771|HS|1|-|-|-|SHAPE=13 F|u8|3|nn|u8|3771|min1.5|1|-|-|-|SHAPE=13 F|u8|3|nn|u8|3771|HS|1|-|-|-|SHAPE=14 "
+        "F|u8|3|nn|u8|3771|min1.5|1|-|-|-|SHAPE=14 F|u8|3|nn|u8|3771|min1.5|1|-|-|-|FRAMES=0 F|u8|3|nn|u8|3771|min3|1|-|-|-|FRAMES=0 "
+        "F|u8|3|nn|u8|3771|min1.5|4|-|-|-|FRAMES=0 F|u8|3|nn|u8|3771|min3|4|-|-|-|FRAMES=0 F|u8|3|nn|u8|3771|min1.5|32|-|-|-|FRAMES=0 "
+        "F|u8|3|nn|u8|3771|min3|32|-|-|-|FRAMES=0 F|u8|3|nn|u8|3771|min1.5|1|-|-|-|FRAMES=1 F|u8|3|nn|u8|3771|min3|1|-|-|-|FRAMES=1 "
+        "F|u8|3|nn|u8|3771|min1.5|4|-|-|-|FRAMES=1 F|u8|3|nn|u8|3771|min3|4|-|-|-|FRAMES=1 F|u8|3|nn|u8|3771|min1.5|32|-|-|-|FRAMES=1 "
+        "F|u8|3|nn|u8|3771|min3|32|-|-|-|FRAMES=1 F|u8|3|nn|u8|3771|min1.5|1|-|-|-|FRAMES=4 F|u8|3|nn|u8|3771|min3|1|-|-|-|FRAMES=4 "
+        "F|u8|3|nn|u8|3771|min1.5|4|-|-|-|FRAMES=4 F|u8|3|nn|u8|3771|min3|4|-|-|-|FRAMES=4 F|u8|3|nn|u8|3771|min1.5|32|-|-|-|FRAMES=4 "
+        "F|u8|3|nn|u8|3771|min3|32|-|-|-|FRAMES=4 F|u8|3|nn|u8|3771|min1.5|1|-|-|-|FRAMES=104 "
+        "F|u8|3|nn|u8|3771|min3|1|-|-|-|FRAMES=104 F|u8|3|nn|u8|3771|min1.5|4|-|-|-|FRAMES=104 "
+        "F|u8|3|nn|u8|3771|min3|4|-|-|-|FRAMES=104 F|u8|3|nn|u8|3771|min1.5|32|-|-|-|FRAMES=104 "
+        "F|u8|3|nn|u8|3771|min3|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast8h<6>": (
+        "B|u8|3|bilinear|u8|257|min1.5|1|-|-|-|- B|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|- B|u8|3|bilinear|u8|None|scale1.5|1|-|-|-|- "
+        "D|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|- D|u8|3|bilinear|u8|3771|min1.5|1|same|-|-|- "
+        "D|u8|3|bilinear|u8|3771|min1.5|4|-|-|-|- D|u8|3|bilinear|u8|3771|min1.5|32|-|-|-|- "
+        "E|u8|3|bilinear|u8|3771|min1.5|1|-|shard|-|- F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=0 "
+        "F|u8|3|bilinear|u8|3771|HS|1|-|-|-|SHAPE=14 F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=14 "
+        "F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|FRAMES=0 F|u8|3|bilinear|u8|3771|min1.5|1|same|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|-|-|-|FRAMES=0 F|u8|3|bilinear|u8|3771|min1.5|32|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|min1.5|1|same|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|min1.5|32|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|FRAMES=4 F|u8|3|bilinear|u8|3771|min1.5|1|same|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|-|-|-|FRAMES=4 F|u8|3|bilinear|u8|3771|min1.5|32|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|FRAMES=104 F|u8|3|bilinear|u8|3771|min1.5|1|same|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|-|-|-|FRAMES=104 F|u8|3|bilinear|u8|3771|min1.5|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast8<float, 7>": (
+        "B|u8|3|bilinear|f32|257|min1.5|1|-|-|-|- B|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|- B|u8|3|bilinear|f32|257|min1.9|1|-|-|-|- "
+        "B|u8|3|bilinear|f32|3771|min1.9|1|-|-|-|- B|u8|3|bilinear|f32|257|min2|1|-|-|-|- B|u8|3|bilinear|f32|3771|min2|1|-|-|-|- "
+        "B|u8|3|bilinear|f32|257|min3|1|-|-|-|- B|u8|3|bilinear|f32|3771|min3|1|-|-|-|- B|u8|3|bilinear|f32|None|scale1.5|1|-|-|-|- "
+        "B|u8|3|bilinear|f32|None|scale2|1|-|-|-|- B|u8|3|bilinear|f32|None|scale3|1|-|-|-|- "
+        "E|u8|3|bilinear|f32|3771|min1.5|1|-|shard|-|- F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|SHAPE=0 "
+        "F|u8|3|bilinear|f32|3771|HS|1|-|-|-|SHAPE=7 F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|SHAPE=7 "
+        "F|u8|3|bilinear|f32|3771|HS|1|-|-|-|SHAPE=13 F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|SHAPE=13 "
+        "F|u8|3|bilinear|f32|3771|HS|1|-|-|-|SHAPE=14 F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|SHAPE=14 "
+        "F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|FRAMES=0 F|u8|3|bilinear|f32|3771|min3|1|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|f32|3771|min1.5|4|-|-|-|FRAMES=0 F|u8|3|bilinear|f32|3771|min3|4|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|f32|3771|min1.5|32|-|-|-|FRAMES=0 F|u8|3|bilinear|f32|3771|min3|32|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|FRAMES=1 F|u8|3|bilinear|f32|3771|min3|1|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|f32|3771|min1.5|4|-|-|-|FRAMES=1 F|u8|3|bilinear|f32|3771|min3|4|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|f32|3771|min1.5|32|-|-|-|FRAMES=1 F|u8|3|bilinear|f32|3771|min3|32|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|FRAMES=4 F|u8|3|bilinear|f32|3771|min3|1|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|f32|3771|min1.5|4|-|-|-|FRAMES=4 F|u8|3|bilinear|f32|3771|min3|4|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|f32|3771|min1.5|32|-|-|-|FRAMES=4 F|u8|3|bilinear|f32|3771|min3|32|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|f32|3771|min1.5|1|-|-|-|FRAMES=104 F|u8|3|bilinear|f32|3771|min3|1|-|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|f32|3771|min1.5|4|-|-|-|FRAMES=104 F|u8|3|bilinear|f32|3771|min3|4|-|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|f32|3771|min1.5|32|-|-|-|FRAMES=104 F|u8|3|bilinear|f32|3771|min3|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_rgba8_fast8<7>": (
+        "B|u8|4|bilinear|u8|257|min1.5|1|-|-|-|- B|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|- B|u8|4|bilinear|u8|257|min1.9|1|-|-|-|- "
+        "B|u8|4|bilinear|u8|3771|min1.9|1|-|-|-|- B|u8|4|bilinear|u8|257|min2|1|-|-|-|- B|u8|4|bilinear|u8|3771|min2|1|-|-|-|- "
+        "B|u8|4|bilinear|u8|257|min3|1|-|-|-|- B|u8|4|bilinear|u8|3771|min3|1|-|-|-|- B|u8|4|bilinear|u8|None|scale1.5|1|-|-|-|- "
+        "B|u8|4|bilinear|u8|None|scale2|1|-|-|-|- B|u8|4|bilinear|u8|None|scale3|1|-|-|-|- "
+        "F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=0 F|u8|4|bilinear|u8|3771|HS|1|-|-|-|SHAPE=7 "
+        "F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=7 F|u8|4|bilinear|u8|3771|HS|1|-|-|-|SHAPE=13 "
+        "F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=13 F|u8|4|bilinear|u8|3771|HS|1|-|-|-|SHAPE=14 "
+        "F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=14 F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|FRAMES=0 "
+        "F|u8|4|bilinear|u8|3771|min3|1|-|-|-|FRAMES=0 F|u8|4|bilinear|u8|3771|min1.5|4|-|-|-|FRAMES=0 "
+        "F|u8|4|bilinear|u8|3771|min3|4|-|-|-|FRAMES=0 F|u8|4|bilinear|u8|3771|min1.5|32|-|-|-|FRAMES=0 "
+        "F|u8|4|bilinear|u8|3771|min3|32|-|-|-|FRAMES=0 F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|FRAMES=1 "
+        "F|u8|4|bilinear|u8|3771|min3|1|-|-|-|FRAMES=1 F|u8|4|bilinear|u8|3771|min1.5|4|-|-|-|FRAMES=1 "
+        "F|u8|4|bilinear|u8|3771|min3|4|-|-|-|FRAMES=1 F|u8|4|bilinear|u8|3771|min1.5|32|-|-|-|FRAMES=1 "
+        "F|u8|4|bilinear|u8|3771|min3|32|-|-|-|FRAMES=1 F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|FRAMES=4 "
+        "F|u8|4|bilinear|u8|3771|min3|1|-|-|-|FRAMES=4 F|u8|4|bilinear|u8|3771|min1.5|4|-|-|-|FRAMES=4 "
+        "F|u8|4|bilinear|u8|3771|min3|4|-|-|-|FRAMES=4 F|u8|4|bilinear|u8|3771|min1.5|32|-|-|-|FRAMES=4 "
+        "F|u8|4|bilinear|u8|3771|min3|32|-|-|-|FRAMES=4 F|u8|4|bilinear|u8|3771|min1.5|1|-|-|-|FRAMES=104 "
+        "F|u8|4|bilinear|u8|3771|min3|1|-|-|-|FRAMES=104 F|u8|4|bilinear|u8|3771|min1.5|4|-|-|-|FRAMES=104 "
+        "F|u8|4|bilinear|u8|3771|min3|4|-|-|-|FRAMES=104 F|u8|4|bilinear|u8|3771|min1.5|32|-|-|-|FRAMES=104 "
+        "F|u8|4|bilinear|u8|3771|min3|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast8h<5>": (
+        "B|u8|3|bilinear|u8|257|min1.9|1|-|-|-|- B|u8|3|bilinear|u8|3771|min1.9|1|-|-|-|- B|u8|3|bilinear|u8|257|min2|1|-|-|-|- "
+        "B|u8|3|bilinear|u8|None|scale2|1|-|-|-|- F|u8|3|bilinear|u8|3771|HS|1|-|-|-|SHAPE=13 "
+        "F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=13 "),
+    "rwh::warp_rgb8_fast8<unsigned char, 7>": (
+        "B|u8|3|bilinear|u8|3771|min2|1|-|-|-|- B|u8|3|bilinear|u8|257|min3|1|-|-|-|- B|u8|3|bilinear|u8|3771|min3|1|-|-|-|- "
+        "B|u8|3|bilinear|u8|None|scale3|1|-|-|-|- F|u8|3|bilinear|u8|3771|HS|1|-|-|-|SHAPE=7 "
+        "F|u8|3|bilinear|u8|3771|min1.5|1|-|-|-|SHAPE=7 F|u8|3|bilinear|u8|3771|min3|1|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|min3|1|same|-|-|FRAMES=0 F|u8|3|bilinear|u8|3771|min3|4|-|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|min3|32|-|-|-|FRAMES=0 F|u8|3|bilinear|u8|3771|min3|1|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|3771|min3|1|same|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|min3|4|-|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|3771|min3|32|-|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|min3|1|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|min3|1|same|-|-|FRAMES=4 F|u8|3|bilinear|u8|3771|min3|1|-|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|u8|3771|min3|1|same|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast8h_tab<6>": (
+        "B|u8|3|bilinear|u8|None|scale1.5|4|same|-|-|- D|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|- "
+        "D|u8|3|bilinear|u8|257|HS|4|mixed|-|-|- D|u8|3|bilinear|u8|3771|HS|4|mixed|-|-|- "
+        "D|u8|3|bilinear|u8|3771|min1.5|4|mixed|-|-|- D|u8|3|bilinear|u8|3771|rot30|4|mixed|-|-|- "
+        "D|u8|3|bilinear|u8|3771|min1.5|32|same|-|-|- D|u8|3|bilinear|u8|257|HS|32|mixed|-|-|- "
+        "D|u8|3|bilinear|u8|3771|HS|32|mixed|-|-|- D|u8|3|bilinear|u8|3771|min1.5|32|mixed|-|-|- "
+        "D|u8|3|bilinear|u8|3771|rot30|32|mixed|-|-|- E|u8|3|bilinear|u8|3771|HS|4|mixed|shard|-|- "
+        "E|u8|3|bilinear|u8|3771|rot30|4|mixed|shard|-|- E|u8|3|bilinear|u8|3771|min1.5|4|mixed|shard|-|- "
+        "F|u8|3|bilinear|u8|3771|HS|4|mixed|-|-|SHAPE=0 F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|SHAPE=0 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|mixed|-|-|SHAPE=0 F|u8|3|bilinear|u8|3771|HS|4|same|-|-|SHAPE=14 "
+        "F|u8|3|bilinear|u8|3771|HS|4|mixed|-|-|SHAPE=14 F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|SHAPE=14 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|mixed|-|-|SHAPE=14 F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|min1.5|32|same|-|-|FRAMES=0 F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|3771|min1.5|32|same|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|min1.5|32|same|-|-|FRAMES=4 F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|u8|3771|min1.5|32|same|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast8h_tab<5>": (
+        "B|u8|3|bilinear|u8|None|scale2|4|same|-|-|- F|u8|3|bilinear|u8|3771|HS|4|same|-|-|SHAPE=13 "
+        "F|u8|3|bilinear|u8|3771|HS|4|mixed|-|-|SHAPE=13 F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|SHAPE=13 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|mixed|-|-|SHAPE=13 "),
+    "rwh::warp_rgb8_fast8_tab<unsigned char, 7>": (
+        "B|u8|3|bilinear|u8|None|scale3|4|same|-|-|- F|u8|3|bilinear|u8|3771|HS|4|same|-|-|SHAPE=7 "
+        "F|u8|3|bilinear|u8|3771|HS|4|mixed|-|-|SHAPE=7 F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|SHAPE=7 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|mixed|-|-|SHAPE=7 F|u8|3|bilinear|u8|3771|min3|4|same|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|min3|32|same|-|-|FRAMES=0 F|u8|3|bilinear|u8|3771|min3|4|same|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|3771|min3|32|same|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|min3|4|same|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|min3|32|same|-|-|FRAMES=4 F|u8|3|bilinear|u8|3771|min3|4|same|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|u8|3771|min3|32|same|-|-|FRAMES=104 "),
+    "rwh::warp_any<unsigned char, unsigned char, 0>": (
+        "C|u8|1|nn|u8|3771|HS|1|-|-|exact|- C|u8|5|nn|u8|3771|HS|1|-|-|exact|- C|u8|64|nn|u8|3771|HS|1|-|-|exact|- "
+        "C|bool|1|nn|bool|3771|HS|1|-|-|exact|- C|bool|5|nn|bool|3771|HS|1|-|-|exact|- C|bool|64|nn|bool|3771|HS|1|-|-|exact|- "
+        "C|i8|1|nn|i8|3771|HS|1|-|-|exact|- C|i8|3|nn|i8|3771|HS|1|-|-|exact|- C|i8|4|nn|i8|3771|HS|1|-|-|exact|- "
+        "C|i8|5|nn|i8|3771|HS|1|-|-|exact|- C|i8|64|nn|i8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned char, double, 1>": (
+        "C|u8|1|bilinear|f64|3771|HS|1|-|-|exact|- C|u8|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|u8|64|bilinear|f64|3771|HS|1|-|-|exact|- C|bool|1|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|bool|5|bilinear|f64|3771|HS|1|-|-|exact|- C|bool|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned char, unsigned char, 1>": (
+        "C|u8|1|bilinear|u8|3771|HS|1|-|-|exact|- C|u8|5|bilinear|u8|3771|HS|1|-|-|exact|- C|u8|64|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|bool|1|bilinear|u8|3771|HS|1|-|-|exact|- C|bool|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|bool|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<unsigned char, 3, double, 1>": (
+        "C|u8|3|bilinear|f64|3771|HS|1|-|-|exact|- C|bool|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "D|u8|3|bilinear|f64|3771|HS|1|-|-|exact|- D|u8|3|bilinear|f64|3771|HS|1|same|-|exact|- "
+        "D|u8|3|bilinear|f64|3771|HS|1|mixed|-|exact|- D|u8|3|bilinear|f64|3771|HS|4|-|-|exact|- "
+        "D|u8|3|bilinear|f64|3771|HS|4|same|-|exact|- D|u8|3|bilinear|f64|3771|HS|4|mixed|-|exact|- "
+        "D|u8|3|bilinear|f64|3771|HS|32|-|-|exact|- D|u8|3|bilinear|f64|3771|HS|32|same|-|exact|- "
+        "D|u8|3|bilinear|f64|3771|HS|32|mixed|-|exact|- "),
+    "rwh::warp_exact<unsigned char, 3, unsigned char, 1>": (
+        "C|u8|3|bilinear|u8|3771|HS|1|-|-|exact|- C|bool|3|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<unsigned char, 4, unsigned char, 0>": (
+        "C|u8|4|nn|u8|3771|HS|1|-|-|exact|- C|bool|4|nn|bool|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<unsigned char, 4, double, 1>": (
+        "C|u8|4|bilinear|f64|3771|HS|1|-|-|exact|- C|bool|4|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<unsigned char, 4, unsigned char, 1>": (
+        "C|u8|4|bilinear|u8|3771|HS|1|-|-|exact|- C|bool|4|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned int, unsigned int, 0>": (
+        "C|f32|1|nn|f32|3771|HS|1|-|-|exact|- C|f32|5|nn|f32|3771|HS|1|-|-|exact|- C|f32|64|nn|f32|3771|HS|1|-|-|exact|- "
+        "C|i32|1|nn|i32|3771|HS|1|-|-|exact|- C|i32|3|nn|i32|3771|HS|1|-|-|exact|- C|i32|4|nn|i32|3771|HS|1|-|-|exact|- "
+        "C|i32|5|nn|i32|3771|HS|1|-|-|exact|- C|i32|64|nn|i32|3771|HS|1|-|-|exact|- C|u32|1|nn|u32|3771|HS|1|-|-|exact|- "
+        "C|u32|3|nn|u32|3771|HS|1|-|-|exact|- C|u32|4|nn|u32|3771|HS|1|-|-|exact|- C|u32|5|nn|u32|3771|HS|1|-|-|exact|- "
+        "C|u32|64|nn|u32|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<float, double, 1>": (
+        "C|f32|1|bilinear|f64|3771|HS|1|-|-|exact|- C|f32|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|f32|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<float, unsigned char, 1>": (
+        "C|f32|1|bilinear|u8|3771|HS|1|-|-|exact|- C|f32|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|f32|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<float, 3, float, 0>": (
+        "C|f32|3|nn|f32|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<float, 3, double, 1>": (
+        "C|f32|3|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<float, 3, unsigned char, 1>": (
+        "C|f32|3|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<float, 4, float, 0>": (
+        "C|f32|4|nn|f32|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<float, 4, double, 1>": (
+        "C|f32|4|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<float, 4, unsigned char, 1>": (
+        "C|f32|4|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned long, unsigned long, 0>": (
+        "C|f64|1|nn|f64|3771|HS|1|-|-|exact|- C|f64|3|nn|f64|3771|HS|1|-|-|exact|- C|f64|4|nn|f64|3771|HS|1|-|-|exact|- "
+        "C|f64|5|nn|f64|3771|HS|1|-|-|exact|- C|f64|64|nn|f64|3771|HS|1|-|-|exact|- C|i64|1|nn|i64|3771|HS|1|-|-|exact|- "
+        "C|i64|3|nn|i64|3771|HS|1|-|-|exact|- C|i64|4|nn|i64|3771|HS|1|-|-|exact|- C|i64|5|nn|i64|3771|HS|1|-|-|exact|- "
+        "C|i64|64|nn|i64|3771|HS|1|-|-|exact|- C|u64|1|nn|u64|3771|HS|1|-|-|exact|- C|u64|3|nn|u64|3771|HS|1|-|-|exact|- "
+        "C|u64|4|nn|u64|3771|HS|1|-|-|exact|- C|u64|5|nn|u64|3771|HS|1|-|-|exact|- C|u64|64|nn|u64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<double, double, 1>": (
+        "C|f64|1|bilinear|f64|3771|HS|1|-|-|exact|- C|f64|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|f64|4|bilinear|f64|3771|HS|1|-|-|exact|- C|f64|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|f64|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<double, unsigned char, 1>": (
+        "C|f64|1|bilinear|u8|3771|HS|1|-|-|exact|- C|f64|3|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|f64|4|bilinear|u8|3771|HS|1|-|-|exact|- C|f64|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|f64|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<signed char, double, 1>": (
+        "C|i8|1|bilinear|f64|3771|HS|1|-|-|exact|- C|i8|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|i8|4|bilinear|f64|3771|HS|1|-|-|exact|- C|i8|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|i8|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<signed char, unsigned char, 1>": (
+        "C|i8|1|bilinear|u8|3771|HS|1|-|-|exact|- C|i8|3|bilinear|u8|3771|HS|1|-|-|exact|- C|i8|4|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|i8|5|bilinear|u8|3771|HS|1|-|-|exact|- C|i8|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned short, unsigned short, 0>": (
+        "C|u16|1|nn|u16|3771|HS|1|-|-|exact|- C|u16|3|nn|u16|3771|HS|1|-|-|exact|- C|u16|4|nn|u16|3771|HS|1|-|-|exact|- "
+        "C|u16|5|nn|u16|3771|HS|1|-|-|exact|- C|u16|64|nn|u16|3771|HS|1|-|-|exact|- C|i16|1|nn|i16|3771|HS|1|-|-|exact|- "
+        "C|i16|3|nn|i16|3771|HS|1|-|-|exact|- C|i16|4|nn|i16|3771|HS|1|-|-|exact|- C|i16|5|nn|i16|3771|HS|1|-|-|exact|- "
+        "C|i16|64|nn|i16|3771|HS|1|-|-|exact|- C|f16|1|nn|f16|3771|HS|1|-|-|exact|- C|f16|3|nn|f16|3771|HS|1|-|-|exact|- "
+        "C|f16|4|nn|f16|3771|HS|1|-|-|exact|- C|f16|5|nn|f16|3771|HS|1|-|-|exact|- C|f16|64|nn|f16|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned short, double, 1>": (
+        "C|u16|1|bilinear|f64|3771|HS|1|-|-|exact|- C|u16|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|u16|4|bilinear|f64|3771|HS|1|-|-|exact|- C|u16|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|u16|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned short, unsigned char, 1>": (
+        "C|u16|1|bilinear|u8|3771|HS|1|-|-|exact|- C|u16|3|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|u16|4|bilinear|u8|3771|HS|1|-|-|exact|- C|u16|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|u16|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<short, double, 1>": (
+        "C|i16|1|bilinear|f64|3771|HS|1|-|-|exact|- C|i16|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|i16|4|bilinear|f64|3771|HS|1|-|-|exact|- C|i16|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|i16|64|bilinear|f64|3771|HS|1|-|-|exact|- D|i16|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "D|i16|5|bilinear|f64|3771|HS|1|same|-|exact|- D|i16|5|bilinear|f64|3771|HS|1|mixed|-|exact|- "
+        "D|i16|5|bilinear|f64|3771|HS|4|-|-|exact|- D|i16|5|bilinear|f64|3771|HS|4|same|-|exact|- "
+        "D|i16|5|bilinear|f64|3771|HS|4|mixed|-|exact|- D|i16|5|bilinear|f64|3771|HS|32|-|-|exact|- "
+        "D|i16|5|bilinear|f64|3771|HS|32|same|-|exact|- D|i16|5|bilinear|f64|3771|HS|32|mixed|-|exact|- "),
+    "rwh::warp_any<short, unsigned char, 1>": (
+        "C|i16|1|bilinear|u8|3771|HS|1|-|-|exact|- C|i16|3|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|i16|4|bilinear|u8|3771|HS|1|-|-|exact|- C|i16|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|i16|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<int, double, 1>": (
+        "C|i32|1|bilinear|f64|3771|HS|1|-|-|exact|- C|i32|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|i32|4|bilinear|f64|3771|HS|1|-|-|exact|- C|i32|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|i32|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<int, unsigned char, 1>": (
+        "C|i32|1|bilinear|u8|3771|HS|1|-|-|exact|- C|i32|3|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|i32|4|bilinear|u8|3771|HS|1|-|-|exact|- C|i32|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|i32|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned int, double, 1>": (
+        "C|u32|1|bilinear|f64|3771|HS|1|-|-|exact|- C|u32|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|u32|4|bilinear|f64|3771|HS|1|-|-|exact|- C|u32|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|u32|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned int, unsigned char, 1>": (
+        "C|u32|1|bilinear|u8|3771|HS|1|-|-|exact|- C|u32|3|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|u32|4|bilinear|u8|3771|HS|1|-|-|exact|- C|u32|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|u32|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<long, double, 1>": (
+        "C|i64|1|bilinear|f64|3771|HS|1|-|-|exact|- C|i64|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|i64|4|bilinear|f64|3771|HS|1|-|-|exact|- C|i64|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|i64|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<long, unsigned char, 1>": (
+        "C|i64|1|bilinear|u8|3771|HS|1|-|-|exact|- C|i64|3|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|i64|4|bilinear|u8|3771|HS|1|-|-|exact|- C|i64|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|i64|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned long, double, 1>": (
+        "C|u64|1|bilinear|f64|3771|HS|1|-|-|exact|- C|u64|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|u64|4|bilinear|f64|3771|HS|1|-|-|exact|- C|u64|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|u64|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<unsigned long, unsigned char, 1>": (
+        "C|u64|1|bilinear|u8|3771|HS|1|-|-|exact|- C|u64|3|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|u64|4|bilinear|u8|3771|HS|1|-|-|exact|- C|u64|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|u64|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<_Float16, double, 1>": (
+        "C|f16|1|bilinear|f64|3771|HS|1|-|-|exact|- C|f16|3|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|f16|4|bilinear|f64|3771|HS|1|-|-|exact|- C|f16|5|bilinear|f64|3771|HS|1|-|-|exact|- "
+        "C|f16|64|bilinear|f64|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_any<_Float16, unsigned char, 1>": (
+        "C|f16|1|bilinear|u8|3771|HS|1|-|-|exact|- C|f16|3|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|f16|4|bilinear|u8|3771|HS|1|-|-|exact|- C|f16|5|bilinear|u8|3771|HS|1|-|-|exact|- "
+        "C|f16|64|bilinear|u8|3771|HS|1|-|-|exact|- "),
+    "rwh::warp_exact<unsigned char, 3, unsigned char, 0>": (
+        "C|u8|3|nn|u8|100|HS|1|-|-|exact|- "),
+    "rwh::warp_rgb8_nn_tab<6>": (
+        "D|u8|3|nn|u8|257|HS|4|same|-|-|- D|u8|3|nn|u8|3771|HS|4|same|-|-|- D|u8|3|nn|u8|257|HS|32|same|-|-|- "
+        "D|u8|3|nn|u8|3771|HS|32|same|-|-|- F|u8|3|nn|u8|3771|HS|4|same|-|-|SHAPE=0 F|u8|3|nn|u8|3771|HS|4|same|-|-|SHAPE=6 "
+        "F|u8|3|nn|u8|3771|min1.5|4|same|-|-|SHAPE=6 "),
+    "rwh::warp_rgb8_fast8_tab<unsigned char, 6>": (
+        "D|u8|3|bilinear|u8|257|HS|4|same|-|-|- D|u8|3|bilinear|u8|3771|HS|4|same|-|-|- D|u8|3|bilinear|u8|257|HS|32|same|-|-|- "
+        "D|u8|3|bilinear|u8|3771|HS|32|same|-|-|- F|u8|3|bilinear|u8|3771|HS|4|same|-|-|SHAPE=0 "
+        "F|u8|3|bilinear|u8|3771|HS|4|same|-|-|SHAPE=6 F|u8|3|bilinear|u8|3771|HS|4|mixed|-|-|SHAPE=6 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|SHAPE=6 F|u8|3|bilinear|u8|3771|min1.5|4|mixed|-|-|SHAPE=6 "
+        "F|u8|3|bilinear|u8|3771|HS|4|same|-|-|FRAMES=0 F|u8|3|bilinear|u8|3771|HS|32|same|-|-|FRAMES=0 "
+        "F|u8|3|bilinear|u8|3771|HS|4|same|-|-|FRAMES=1 F|u8|3|bilinear|u8|3771|HS|32|same|-|-|FRAMES=1 "
+        "F|u8|3|bilinear|u8|3771|HS|4|same|-|-|FRAMES=4 F|u8|3|bilinear|u8|3771|HS|32|same|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|HS|4|same|-|-|FRAMES=104 F|u8|3|bilinear|u8|3771|HS|32|same|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast8_tab<float, 6>": (
+        "D|u8|3|bilinear|f32|257|HS|4|same|-|-|- D|u8|3|bilinear|f32|3771|HS|4|same|-|-|- D|u8|3|bilinear|f32|257|HS|32|same|-|-|- "
+        "D|u8|3|bilinear|f32|3771|HS|32|same|-|-|- F|u8|3|bilinear|f32|3771|HS|4|same|-|-|SHAPE=0 "
+        "F|u8|3|bilinear|f32|3771|HS|4|same|-|-|SHAPE=6 F|u8|3|bilinear|f32|3771|min1.5|4|same|-|-|SHAPE=6 "),
+    "rwh::warp_rgb8_fast8_tab<unsigned char, 5>": (
+        "D|u8|3|bilinear|u8|3771|rot30|4|same|-|-|- D|u8|3|bilinear|u8|3771|rot30|32|same|-|-|- "
+        "F|u8|3|bilinear|u8|3771|HS|4|same|-|-|SHAPE=5 F|u8|3|bilinear|u8|3771|HS|4|mixed|-|-|SHAPE=5 "
+        "F|u8|3|bilinear|u8|3771|min1.5|4|same|-|-|SHAPE=5 F|u8|3|bilinear|u8|3771|min1.5|4|mixed|-|-|SHAPE=5 "),
+    "rwh::warp_rgb8_nn_tab<7>": (
+        "D|u8|3|nn|u8|257|HS|4|mixed|-|-|- D|u8|3|nn|u8|3771|HS|4|mixed|-|-|- D|u8|3|nn|u8|257|HS|32|mixed|-|-|- "
+        "D|u8|3|nn|u8|3771|HS|32|mixed|-|-|- E|u8|3|nn|u8|3771|HS|4|mixed|shard|-|- E|u8|3|nn|u8|3771|rot30|4|mixed|shard|-|- "
+        "E|u8|3|nn|u8|3771|min1.5|4|mixed|shard|-|- F|u8|3|nn|u8|3771|min1.5|4|same|-|-|SHAPE=0 "
+        "F|u8|3|nn|u8|3771|HS|4|same|-|-|SHAPE=7 F|u8|3|nn|u8|3771|min1.5|4|same|-|-|SHAPE=7 F|u8|3|nn|u8|3771|HS|4|same|-|-|SHAPE=13 "
+        "F|u8|3|nn|u8|3771|min1.5|4|same|-|-|SHAPE=13 F|u8|3|nn|u8|3771|HS|4|same|-|-|SHAPE=14 "
+        "F|u8|3|nn|u8|3771|min1.5|4|same|-|-|SHAPE=14 "),
+    "rwh::warp_rgb8_fast8_tab<float, 7>": (
+        "D|u8|3|bilinear|f32|257|HS|4|mixed|-|-|- D|u8|3|bilinear|f32|3771|HS|4|mixed|-|-|- D|u8|3|bilinear|f32|257|HS|32|mixed|-|-|- "
+        "D|u8|3|bilinear|f32|3771|HS|32|mixed|-|-|- E|u8|3|bilinear|f32|3771|HS|4|mixed|shard|-|- "
+        "E|u8|3|bilinear|f32|3771|rot30|4|mixed|shard|-|- E|u8|3|bilinear|f32|3771|min1.5|4|mixed|shard|-|- "
+        "F|u8|3|bilinear|f32|3771|min1.5|4|same|-|-|SHAPE=0 F|u8|3|bilinear|f32|3771|HS|4|same|-|-|SHAPE=7 "
+        "F|u8|3|bilinear|f32|3771|min1.5|4|same|-|-|SHAPE=7 F|u8|3|bilinear|f32|3771|HS|4|same|-|-|SHAPE=13 "
+        "F|u8|3|bilinear|f32|3771|min1.5|4|same|-|-|SHAPE=13 F|u8|3|bilinear|f32|3771|HS|4|same|-|-|SHAPE=14 "
+        "F|u8|3|bilinear|f32|3771|min1.5|4|same|-|-|SHAPE=14 "),
+    "rwh::warp_rgb8_nn_tab<5>": (
+        "F|u8|3|nn|u8|3771|HS|4|same|-|-|SHAPE=5 F|u8|3|nn|u8|3771|min1.5|4|same|-|-|SHAPE=5 "),
+    "rwh::warp_rgb8_fast8_tab<float, 5>": (
+        "F|u8|3|bilinear|f32|3771|HS|4|same|-|-|SHAPE=5 F|u8|3|bilinear|f32|3771|min1.5|4|same|-|-|SHAPE=5 "),
+    "rwh::warp_rgb8_fast8m<6>": (
+        "F|u8|3|bilinear|u8|3771|HS|4|-|-|-|FRAMES=4 F|u8|3|bilinear|u8|272|HS|4|-|-|-|FRAMES=4 "
+        "F|u8|3|bilinear|u8|3771|HS|32|-|-|-|FRAMES=4 F|u8|3|bilinear|u8|272|HS|32|-|-|-|FRAMES=4 "),
+    "rwh::warp_rgb8_fast8m<7>": (
+        "F|u8|3|bilinear|u8|3771|min3|4|-|-|-|FRAMES=4 F|u8|3|bilinear|u8|3771|min3|32|-|-|-|FRAMES=4 "),
+    "rwh::warp_rgb8_fast8mb<6>": (
+        "F|u8|3|bilinear|u8|3771|HS|4|-|-|-|FRAMES=104 F|u8|3|bilinear|u8|272|HS|4|-|-|-|FRAMES=104 "
+        "F|u8|3|bilinear|u8|3771|HS|32|-|-|-|FRAMES=104 F|u8|3|bilinear|u8|272|HS|32|-|-|-|FRAMES=104 "),
+    "rwh::warp_rgb8_fast8mb<7>": (
+        "F|u8|3|bilinear|u8|3771|min3|4|-|-|-|FRAMES=104 F|u8|3|bilinear|u8|3771|min3|32|-|-|-|FRAMES=104 "),
+}
+
+def test_warp_plan_sweep_matches_parent(lib):
+    """Every kernel name rwh_warp_plan reports over a fixed matrix of configurations equals what the library reported BEFORE the
+    warp dispatch was refactored to choose each kernel once: _PLAN_SWEEP was generated from the library of the parent commit
+    6f87344 (not from this tree), so a change of selection -- or of a single byte of a name -- fails here, without a GPU.
+    The matrix: uint8 / float32 sources and, in exact mode, every STITCH_DTYPE type; 1, 3, 4, 5 and 64 channels; nn and bilinear;
+    uint8 / float32 / float64 outputs, legal or refused (a refusal is a row: its status code); output widths around the 128 px tiles
+    and the ragged-edge strip; batches of 1, 4 and 32 with one homography and with one per image (the same, and mixed ones that choose
+    different shapes); bench.py's H_S, rotations by 30 and 90 degrees, minifications about the image centre and plain scales by
+    1 / 1.5, 1 / 2, 1 / 3 on their own grids; a row shard; RWH_TUNE_WARP_SHAPE in 0, 5, 6, 7, 13, 14 and RWH_TUNE_WARP_FRAMES in 0, 1, 4, 104.
+    Known limit: rwh_warp_plan records only the FIRST launch of a call, so the ragged-edge strip launch (warp_rgb8_strip*: out_w >= 256
+    and out_w % 128 in 1..16) and the second and later shape groups of a per-image batch do not show in it; those are covered by the
+    GPU tests test_warp_vs_oracle_1080p_and_ragged, test_warp_one_homography_per_image and test_warp_minification_halves_per_image."""
+    from ransac_with_homography_amd import _lib
+    want = {key: result for result, keys in _PLAN_SWEEP.items() for key in keys.split()}
+    assert len(want) == sum(len(keys.split()) for keys in _PLAN_SWEEP.values()) > 900
+    got = {}
+    try:
+        for key, thunk in _plan_sweep_rows():
+            assert key not in got, key
+            got[key] = thunk()
+    finally:
+        assert lib.rwh_lab_tune(_lib.RWH_TUNE_WARP_SHAPE, 0) == 0 and lib.rwh_lab_tune(_lib.RWH_TUNE_WARP_FRAMES, 0) == 0
+    assert set(got) == set(want)
+    wrong = {key: (got[key], want[key]) for key in got if got[key] != want[key]}
+    assert not wrong, wrong
+    # the matrix reaches the kernels it is meant to reach (the host's own choices on the parent, not forced ones)
+    for key, name in (("B|u8|3|bilinear|u8|None|scale1.5|1|-|-|-|-", "rwh::warp_rgb8_fast8h<6>"),
+                      ("B|u8|3|bilinear|u8|None|scale2|1|-|-|-|-", "rwh::warp_rgb8_fast8h<5>"),
+                      ("B|u8|3|bilinear|u8|None|scale3|1|-|-|-|-", "rwh::warp_rgb8_fast8<unsigned char, 7>"),
+                      ("F|u8|3|bilinear|u8|3771|HS|32|-|-|-|FRAMES=4", "rwh::warp_rgb8_fast8m<6>"),
+                      ("F|u8|3|bilinear|u8|3771|HS|32|-|-|-|FRAMES=104", "rwh::warp_rgb8_fast8mb<6>"),
+                      ("F|u8|3|bilinear|u8|3771|HS|1|-|-|-|SHAPE=13", "rwh::warp_rgb8_fast8h<5>"),
+                      ("F|u8|3|bilinear|u8|3771|HS|1|-|-|-|SHAPE=14", "rwh::warp_rgb8_fast8h<6>"),
+                      ("C|i16|5|bilinear|f64|3771|HS|1|-|-|exact|-", "rwh::warp_any<short, double, 1>"),
+                      ("C|i16|5|nn|i16|3771|HS|1|-|-|exact|-", "rwh::warp_any<unsigned short, unsigned short, 0>"),
+                      ("A|u8|3|bilinear|u8|100|HS|1|-|-|-|-", "rwh::warp_rgb8_fast<unsigned char>"),
+                      ("A|u8|3|bilinear|u8|127|HS|1|-|-|-|-", "rwh::warp_rgb8_fast<unsigned char>"),
+                      ("A|u8|3|bilinear|u8|128|HS|1|-|-|-|-", "rwh::warp_rgb8_fast8<unsigned char, 6>"),
+                      ("A|u8|3|bilinear|u8|3771|HS|1|-|-|-|-", "rwh::warp_rgb8_fast8<unsigned char, 6>"),
+                      ("A|u8|1|bilinear|u8|3771|HS|1|-|-|-|-", -2)):
+        assert want[key] == name, key
+
+
 def test_no_cpu_fallback():
     import torch
     if torch.cuda.is_available():

@@ -1,6 +1,6 @@
 // Developer microbenchmark for the warp kernels (NOT part of the product, not built by build()).
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -ffp-contract=off tools/warp_lab.hip -o tools/warp_lab
-//   gpurun -- ./tools/warp_lab [frames] [case-filter]
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -ffp-contract=off tools/warp_lab.hip ransac_with_homography_amd/csrc/rwh_api.hip -o tools/warp_lab
+//   ./tools/warp_lab [frames] [case-filter]
 // Times the RGB-u8 bilinear kernels on the BASELINE geometry (3840x2160 -> 2028x3771 auto-bounds grid and a
 // 3840x2160 fixed grid) and reports how many output bytes differ from the generic (reference-order,
 // texel-exact) kernel.
@@ -152,25 +152,28 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int g = 0; g < 2; ++g) {
         const Geo G = geo[g];
+        auto args = [&] {
+            return make_warp_args(src, SH, SW, (long long)src_bytes, ih, G.x0, 1.0, G.x0 + G.w - 1, G.y0, 1.0, G.y0 + G.h - 1, G.h, G.w, SH, SW,
+                                  dst, (long long)G.w * G.h * 3, 0, G.h);
+        };
         auto call = [&](int interp, int dst_dtype, bool generic) {
             // the C ABI picks the fast kernel; `generic` forces the generic one by going through launch()
             if (!generic)
                 return rwh_warp_backward(src, SH, SW, 3, RWH_U8, (int64_t)src_bytes, B, ih, 1, G.x0, 1.0, G.x0 + G.w - 1, G.y0, 1.0,
                                          G.y0 + G.h - 1, G.h, G.w, SH, SW, interp, dst, dst_dtype, (int64_t)G.w * G.h * 3, 0, G.h, 0, nullptr);
-            WarpArgs a;
-            a.src = src; a.dst = dst; a.src_img_stride = (long long)src_bytes; a.dst_img_stride = (long long)G.w * G.h * 3;
-            for (int i = 0; i < 9; ++i) a.ih[i] = ih[i];
-            a.x0 = G.x0; a.step_x = 1.0; a.x_last = G.x0 + G.w - 1; a.y0 = G.y0; a.step_y = 1.0; a.y_last = G.y0 + G.h - 1;
-            a.src_h = SH; a.src_w = SW; a.bound_h = SH; a.bound_w = SW; a.out_h = G.h; a.out_w = G.w; a.row_begin = 0; a.rows = G.h;
-            a.tiles_x = (G.w + 255) / 256; a.tiles_y = (G.h + 3) / 4; a.nblocks = a.tiles_x * a.tiles_y * B; a.cpx = (a.nblocks + 7) / 8;
-            return launch(warp_generic<unsigned char, 3, unsigned char, RWH_BILINEAR>, a, (hipStream_t)0);
+            WarpArgs a = args();
+            if (!tile_grid(a, PX, B)) return (int)RWH_E_UNSUPPORTED;
+            return launch(pick_generic<unsigned char, 3, unsigned char, RWH_BILINEAR>(), a.cpx, (hipStream_t)0, a);
         };
-        auto fast = [&](int variant, int group) {
-            WarpArgs a;
-            a.src = src; a.dst = dst; a.src_img_stride = (long long)src_bytes; a.dst_img_stride = (long long)G.w * G.h * 3;
-            a.src_h = SH; a.src_w = SW; a.bound_h = SH; a.bound_w = SW; a.out_h = G.h; a.out_w = G.w; a.row_begin = 0; a.rows = G.h;
-            return launch_fast(a, ih, G.x0, 1.0, G.y0, 1.0, RWH_U8, B, (hipStream_t)0, variant, group,
-                               variant == 2 ? (group == 0 ? pattern_twin<0> : group == 1 ? pattern_twin<220> : group == 2 ? pattern_twin<440> : group == 3 ? pattern_twin<0, 1> : pattern_twin<0, 2>) : nullptr);
+        // kind Custom: the memory-pattern twin number `group` on the 8 px kernel's tiling
+        auto fast = [&](FastKind kind, int group = 1) {
+            FastRequest q{kind};
+            q.batch = B;
+            if (kind == FastKind::Custom) {
+                q.group = group;
+                q.custom = group == 0 ? pattern_twin<0> : group == 1 ? pattern_twin<220> : group == 2 ? pattern_twin<440> : group == 3 ? pattern_twin<0, 1> : pattern_twin<0, 2>;
+            }
+            return launch_fast(args(), q, (hipStream_t)0);
         };
         struct Case { const char* name; std::function<int()> run; };
         std::vector<Case> cases = {
@@ -180,16 +183,16 @@ int main(int argc, char** argv) {
             {"exact u8 (float64, RWH_WARP_EXACT)", [&] {
                 return rwh_warp_backward(src, SH, SW, 3, RWH_U8, (int64_t)src_bytes, B, ih, 1, G.x0, 1.0, G.x0 + G.w - 1, G.y0, 1.0,
                                          G.y0 + G.h - 1, G.h, G.w, SH, SW, RWH_BILINEAR, dst, RWH_U8, (int64_t)G.w * G.h * 3, 0, G.h, RWH_WARP_EXACT, nullptr); }},
-            {"fast u8 px4", [&] { return fast(0, 1); }},
-            {"fast u8 px8", [&] { return fast(1, 1); }},
-            {"fast u8 px8 shape 128x4", [&] { rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 7); int r = fast(1, 1); rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 0); return r; }},
-            {"fast u8 px8 shape 64x8", [&] { rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 6); int r = fast(1, 1); rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 0); return r; }},
-            {"fast u8 px8 shape 32x16", [&] { rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 5); int r = fast(1, 1); rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 0); return r; }},
-            {"twin: px8 access pattern, no ALU", [&] { return fast(2, 0); }},
-            {"twin: px8 access pattern + 220 FMA", [&] { return fast(2, 1); }},
-            {"twin: px8 access pattern + 440 FMA", [&] { return fast(2, 2); }},
-            {"twin: loads only", [&] { return fast(2, 3); }},
-            {"twin: stores only", [&] { return fast(2, 4); }},
+            {"fast u8 px4", [&] { return fast(FastKind::Bilinear4); }},
+            {"fast u8 px8", [&] { return fast(FastKind::Bilinear8); }},
+            {"fast u8 px8 shape 128x4", [&] { rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 7); int r = fast(FastKind::Bilinear8); rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 0); return r; }},
+            {"fast u8 px8 shape 64x8", [&] { rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 6); int r = fast(FastKind::Bilinear8); rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 0); return r; }},
+            {"fast u8 px8 shape 32x16", [&] { rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 5); int r = fast(FastKind::Bilinear8); rwh_lab_tune(RWH_TUNE_WARP_SHAPE, 0); return r; }},
+            {"twin: px8 access pattern, no ALU", [&] { return fast(FastKind::Custom, 0); }},
+            {"twin: px8 access pattern + 220 FMA", [&] { return fast(FastKind::Custom, 1); }},
+            {"twin: px8 access pattern + 440 FMA", [&] { return fast(FastKind::Custom, 2); }},
+            {"twin: loads only", [&] { return fast(FastKind::Custom, 3); }},
+            {"twin: stores only", [&] { return fast(FastKind::Custom, 4); }},
         };
         const double bytes = (double)B * (src_bytes + (double)G.w * G.h * 3);
         const size_t nbytes = (size_t)G.w * G.h * 3 * B;
