@@ -313,6 +313,37 @@ RWH_API int rwh_ransac_batched(const float* d_pts_a, const float* d_pts_b, const
                        uint64_t* d_masks, uint64_t* d_best, unsigned flags, void* stream);
 
 /*
+ * The final N-point refit of the winners of rwh_ransac_batched, on the device.  Replaces, per problem,
+ *   finalModel = model.fit(X[:, inliers], Y[:, inliers], collective=True)   ransac.py:206-211
+ *   calc_correspLinearCollective + inv(A.T @ A) @ (A.T @ b)                 homography.py:48-69 / 90-105
+ * as ONE launch for P problems (one workgroup each), results left on the device.  A documented NON-PARITY mode: the reference
+ * forms and solves the normal equations in float32 through BLAS / LAPACK (an undefined summation order, and a poor solve:
+ * cond(A^T A) is 1e13 .. 1e15 on pixel coordinates); this entry point solves the SAME least-squares problem in float64 and is
+ * not the reference's float32 bits -- it is closer to the exact least-squares solution than the reference is.
+ *   Problem p's inliers are the bits set in row p of d_masks (P x mask_words uint64): bit i of word i / 64 = correspondence
+ *   d_offsets[p] + i, the layout rwh_ransac_batched writes; bits at or past the problem's size are ignored.  d_pts_a, d_pts_b,
+ *   d_offsets (P + 1 int32) as rwh_ransac_batched.  The problems' sizes live on the device, so the CALLER guarantees mask_words >=
+ *   ceil(M_p / 64) for every problem; a shorter row is never read past its end (correspondences beyond it count as outliers).
+ *   Each inlier (x, y) -> (x', y') gives the rows [x, y, 1, 0, 0, 0, -x x', -y x' | x'] and [0, 0, 0, x, y, 1, -x y', -y y' | y']
+ *   (float32 inputs converted to float64, products exact); d_h (P x 9 float64, row-major 3 x 3) = the least-squares h with
+ *   h[8] = 1, from the float64 normal equations: moments summed in a fixed order (no atomics: a rerun is bit-identical),
+ *   symmetric diagonal equilibration, Cholesky.
+ *   d_status (P int32): RWH_REFIT_OK; RWH_REFIT_FEW, fewer than 4 inliers (the reference's refit asserts, ransac.py:38);
+ *   RWH_REFIT_SINGULAR, a diagonal entry or pivot that is not a positive finite number, or a non-finite solution (the inliers do
+ *   not determine a homography).  Anything but OK: all nine entries NaN.  Problems do not affect one another.
+ * RWH_E_INVALID: NULL pointer, n_problems <= 0, mask_words <= 0.
+ *
+ * rwh_host_refit: the same operations in the same order on the HOST for one problem (no device, no stream; works without a GPU):
+ * pts_a, pts_b m x 2 float32, mask_words ceil(m / 64) uint64, out_h9 9 float64, out_status one int32.  m == 0 gives
+ * RWH_REFIT_FEW; RWH_E_INVALID: NULL pointer, m < 0.
+ */
+enum { RWH_REFIT_OK = 0, RWH_REFIT_FEW = 1, RWH_REFIT_SINGULAR = 2 };
+RWH_API int rwh_refit_batched(const float* d_pts_a, const float* d_pts_b, const int32_t* d_offsets, int n_problems,
+                      const uint64_t* d_masks, int mask_words, double* d_h, int32_t* d_status, void* stream);
+RWH_API int rwh_host_refit(const float* pts_a, const float* pts_b, int m, const uint64_t* mask_words,
+                   double* out_h9, int32_t* out_status);
+
+/*
  * HOST helper of the settle step (no device work, no stream): the reference's own 4-point solve for n samples,
  *   calc_corresp (homography.py:4-14: 8 x 9 float32 DLT matrix, float32 products) -> numpy.linalg.svd (LAPACK dgesdd,
  *   float64 inside) -> last row of V^T cast to float32 -> / its 9th element in float32   (homography.py:71-88),

@@ -22,13 +22,14 @@ RWH_STITCH_FAST = 4
 RWH_HYP_REPEATED, RWH_HYP_SINGULAR, RWH_HYP_ILLCOND, RWH_HYP_DEGENERATE = 1, 2, 4, 8
 RWH_BATCH_DEVICE_SAMPLING = 1
 RWH_BATCH_EARLY_STOP = 2
+RWH_REFIT_OK, RWH_REFIT_FEW, RWH_REFIT_SINGULAR = 0, 1, 2
 RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRAMES = 0, 1, 2, 3
 
 # every symbol include/rwh.h declares (tests check the library exports them all)
 EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_probe", "rwh_warp_backward", "rwh_warp_plan", "rwh_sample_points", "rwh_dlt4_batched",
            "rwh_score_count", "rwh_project_points", "rwh_project_points_ex", "rwh_ransac_search", "rwh_ransac_batched", "rwh_stitch_panorama",
            "rwh_host_dlt4_svd", "rwh_ransac_run", "rwh_ransac_run_layout", "rwh_warp_index_check", "rwh_score_count_inv", "rwh_host_inv3", "rwh_stitch_panorama_rows",
-           "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex", "rwh_settle_decide")
+           "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex", "rwh_settle_decide", "rwh_refit_batched", "rwh_host_refit")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -110,6 +111,10 @@ def _bind(lib):
     lib.rwh_ransac_run.argtypes = [vp, vp, i32, vp, i32, f64, i32, i32, i32, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp]
     lib.rwh_settle_decide.restype = i32
     lib.rwh_settle_decide.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, SETTLE_INTERVAL_FN, SETTLE_SOLVE_FN, vp, vp]
+    lib.rwh_refit_batched.restype = i32
+    lib.rwh_refit_batched.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp]
+    lib.rwh_host_refit.restype = i32
+    lib.rwh_host_refit.argtypes = [vp, vp, i32, vp, vp, vp]
     return lib
 
 

@@ -384,6 +384,25 @@ def ransac_batched(pts_a, pts_b, offsets, needs, th, loss, ws, seed=None, idx=No
     return ws
 
 
+def refit_batched(pts_a, pts_b, offsets, masks):
+    """The N-point refit of P problems in one launch (rwh_refit_batched, include/rwh.h): float64 normal equations over each
+    problem's inliers -- the reference's least-squares problem, NOT its float32 bits.
+
+    pts_a/pts_b: [total,2] float32, offsets: [P+1] int32, masks: [P,words] int64 (bit i of word i/64 of row p = correspondence
+    offsets[p] + i; words >= ceil(M_p/64) for every problem) -- all on the GPU.  Returns (H [P,3,3] float64, status [P] int32:
+    RWH_REFIT_OK / _FEW / _SINGULAR, H all NaN unless OK), both on the GPU, enqueued on torch's current stream."""
+    lib = _lib.load()
+    _dev_check(pts_a, pts_b, offsets, masks)
+    P = offsets.shape[0] - 1
+    assert pts_a.dtype == torch.float32 and pts_b.dtype == torch.float32 and offsets.dtype == torch.int32
+    assert masks.dtype == torch.int64 and masks.dim() == 2 and masks.shape[0] == P and tuple(pts_a.shape) == tuple(pts_b.shape)
+    H = torch.empty((P, 3, 3), dtype=torch.float64, device=pts_a.device)
+    status = torch.empty((P,), dtype=torch.int32, device=pts_a.device)
+    check(lib.rwh_refit_batched(_ptr(pts_a), _ptr(pts_b), _ptr(offsets), P, _ptr(masks), masks.shape[1], _ptr(H), _ptr(status),
+                                _lib.stream_ptr()), "rwh_refit_batched")
+    return H, status
+
+
 def project_points(h9, pts, inverse):
     """Launch the projection kernel: h9 [9] float32, pts [M,2] float32 -> [3,M] float32."""
     lib = _lib.load()

@@ -584,6 +584,13 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
     `finalModel` is None for a problem whose winner has too few inliers to refit (where `RANSAC.run` raises
     AssertionError) and with refit=False (no correspondence then visits the host at all).
 
+    refit="device": the N-point refit runs on the GPU for all problems in one launch (kernels.refit_batched); when `idx` is
+    None no correspondence visits the host (with `idx=` the host settle step still downloads them).  A documented NON-PARITY mode: it solves the same least-squares problem as the reference in
+    float64 and is not the reference's float32 bits (it is closer to the exact least-squares solution).  `finalModel` is None
+    where the refit reports anything but RWH_REFIT_OK or the winner has fewer than `n` inliers; inliers and counts are as with
+    refit=True.  `info` then also receives "H_device" ([P,3,3] float64, NaN where the status is not OK) and "refit_status"
+    ([P] int32), the device tensors, for a consumer on the GPU.  Any other value of `refit` raises ValueError.
+
     Sampling: by default on the device (Philox4x32-10 keyed by `seed`, four distinct correspondences per hypothesis):
     a documented NON-PARITY mode -- the reference draws with replacement from numpy's global legacy generator
     (ransac.py:177).  Pass `idx` (list of [k,4] integer arrays, one per problem) to supply the samples yourself; each
@@ -599,6 +606,9 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
         exit("Invalid method!")
     if n < 4:
         raise IndexError("index 3 is out of bounds for axis 0 with size %d" % n)   # as RANSAC.run (homography.py:9)
+    if not isinstance(refit, (bool, np.bool_, int, np.integer)) and refit != "device":   # truthy / falsy flags as before
+        raise ValueError("refit: True (host refit, the reference's bits), False (none) or 'device', got %r" % (refit,))
+    device_refit = isinstance(refit, str)
     dev = _lib.require_gpu()
     P = len(datas)
     if P == 0:
@@ -618,6 +628,7 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
     offsets[1:] = np.cumsum(sizes)
     needs_host = [kernels.need_count(m, d, n) for m in sizes]
     needs = torch.tensor(needs_host, dtype=torch.int32, device=dev)
+    offsets_dev = torch.from_numpy(offsets).to(dev)
     ws = kernels.BatchWorkspace(P, int(k), max(max(sizes), 1), dev)
     if idx is not None:
         if len(idx) != P:
@@ -634,12 +645,12 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
             tables.append(np.where(t < 0, t + m_, t))
         idx = tables
         table = torch.from_numpy(np.stack([t[:, :4].astype(np.int32) for t in idx])).to(dev)   # fit on the first four
-        kernels.ransac_batched(pa, pb, torch.from_numpy(offsets).to(dev), needs, _weak_threshold(th), method, ws, idx=table)
+        kernels.ransac_batched(pa, pb, offsets_dev, needs, _weak_threshold(th), method, ws, idx=table)
     else:
-        kernels.ransac_batched(pa, pb, torch.from_numpy(offsets).to(dev), needs, _weak_threshold(th), method, ws, seed=seed,
+        kernels.ransac_batched(pa, pb, offsets_dev, needs, _weak_threshold(th), method, ws, seed=seed,
                                problem_base=problem_base, early_stop=True)
     pa_host = pb_host = None
-    if idx is not None or (refit and on_device):
+    if idx is not None or (refit and on_device and not device_refit):
         pa_host, pb_host = pa.cpu().numpy(), pb.cpu().numpy()
     if idx is not None:
         # the caller's tables may hold repeated indices (numpy's sampler draws with replacement): settle every problem
@@ -658,12 +669,28 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
         winners = [kernels.decode_best(best[p], int(k)) for p in range(P)]
         host_masks = [None] * P
     rows = torch.tensor([[p, w[0] if w[0] is not None else 0] for p, w in enumerate(winners)], device=dev)
-    win_masks = ws.masks[rows[:, 0], rows[:, 1]].cpu().numpy()          # one gather, one copy for all problems
+    win_dev = ws.masks[rows[:, 0], rows[:, 1]]
+    win_masks = win_dev.cpu().numpy()                                   # one gather, one copy for all problems
     if idx is None:
         win_counts = ws.counts[rows[:, 0], rows[:, 1]].cpu().numpy()
     if info is not None:
         info["scored"] = (ws.counts >= 0).sum(dim=1).cpu().numpy()
         info["early"] = [bool(w[2]) for w in winners]
+    if device_refit:
+        # the winners' mask rows are on the device already; rows the host settle step replaced (and winners that do not exist)
+        # are overwritten by one upload
+        patch = {p: host_masks[p] for p in range(P) if host_masks[p] is not None or winners[p][0] is None}
+        if patch:
+            words = np.zeros((len(patch), ws.words), dtype=np.int64)
+            for j, w in enumerate(patch.values()):
+                if w is not None:
+                    w = np.ascontiguousarray(w).view(np.int64).ravel()
+                    words[j, :w.size] = w
+            win_dev[torch.tensor(list(patch), device=dev)] = torch.from_numpy(words).to(dev)
+        H_dev, status_dev = kernels.refit_batched(pa, pb, offsets_dev, win_dev)
+        both = torch.cat([H_dev.reshape(P, 9), status_dev.to(torch.float64)[:, None]], dim=1).cpu().numpy()   # one copy
+        if info is not None:
+            info["H_device"], info["refit_status"] = H_dev, status_dev
     out = []
     for p, (winner, _, early) in enumerate(winners):
         model = HomoModel(th=th, d=d, n=n)
@@ -674,7 +701,10 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
             bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:sizes[p]]
             inliers, total = (np.nonzero(bits)[0].astype(np.int64),), np.int64(win_counts[p])
         H = None
-        if refit:
+        if device_refit:
+            if both[p, 9] == _lib.RWH_REFIT_OK and int(total) >= n:     # fewer inliers than n: None, as the host refit
+                H = both[p, :9].reshape(3, 3).copy()
+        elif refit:
             if on_device:
                 o0 = int(offsets[p])
                 X, Y = pa_host[o0:o0 + sizes[p]].T, pb_host[o0:o0 + sizes[p]].T
