@@ -344,6 +344,53 @@ RWH_API int rwh_host_refit(const float* pts_a, const float* pts_b, int m, const 
                    double* out_h9, int32_t* out_status);
 
 /*
+ * Brute-force Hamming matcher with cross-check for P image pairs in one submission: the stage in front of rwh_ransac_batched.
+ * Replaces, per pair,
+ *   bf = cv2.BFMatcher(cv2.NORM_HAMMING, crossCheck=True); bf.match(featuresA, featuresB)     ransac.py:258-259
+ * and leaves the order of ransac.py:260-261 (sorted by distance) to the caller, who gets one record per query row.
+ * THE RULE.  A: na x nbytes uint8 binary descriptors (OpenCV's "query" side), B: nb x nbytes (the "train" side),
+ * D[i][j] = popcount(A[i] xor B[j]) over all 8 * nbytes bits.
+ *   1. For every train row j: q[j] = the query i with the smallest D[i][j], the lowest i on ties; dT[j] = D[q[j]][j].
+ *   2. For every query row i: among the j with q[j] == i, the one with the smallest dT[j], the lowest j on ties, is i's match;
+ *      if no j chose i, query i has no match.
+ *   3. The match list of the reference is the surviving (i, j, distance) ordered by (distance, i): its stable sort by distance
+ *      of a list that arrives in query order.
+ * PROVENANCE AND CAVEAT.  This is how the crossCheck=True path of OpenCV 4's BFMatcher::match reads (a 1-nearest search from
+ * the train side, turned round and reduced per query row).  It is NOT the textbook mutual nearest neighbour: a query can be
+ * matched to a train row that is not its own nearest, and only the train -> query direction needs the full distance matrix.
+ * OpenCV is not a dependency of this project and was not available where this was written: parity with OpenCV is NOT VERIFIED.
+ * The code is held to the rule above (tests/match_cases.py restates it in numpy); every quantity is an integer, so results are
+ * exact and a rerun is bit-identical.
+ *   d_desc_a / d_desc_b: the problems' descriptors concatenated, total_a x nbytes / total_b x nbytes uint8, rows contiguous, any
+ *   alignment; d_offsets_a / d_offsets_b: P + 1 int32 each, problem p owns rows d_offsets[p] .. d_offsets[p+1]-1 of its side (the
+ *   layout of rwh_ransac_batched; a problem whose range is not inside [0, total] is treated as empty);
+ *   nbytes: 1 .. RWH_MATCH_MAX_BYTES (ORB / BRIEF / LATCH 32, BRISK / FREAK 64, AKAZE 61), else RWH_E_UNSUPPORTED;
+ *   d_train_idx, d_distance: total_a int32 each, per query row of the concatenated A its match's train row (LOCAL to the problem)
+ *   and distance, -1 / -1 for no match.  A problem with na == 0 or nb == 0 is legal and has no matches;
+ *   d_workspace: workspace_bytes >= rwh_match_workspace_bytes(P, total_a, total_b) = 8 * (total_a + total_b + P + 1) bytes of
+ *   device memory, 8-byte aligned, contents irrelevant before and after.
+ * Work is split into blocks of RWH_MATCH_TILE_TRAIN train rows x RWH_MATCH_SEG_QUERY query rows (query rows staged
+ * RWH_MATCH_CHUNK_QUERY at a time) whose partial minima are combined with 64-bit integer atomic minima: the result does not
+ * depend on the split.  Four launches, whatever P.
+ * RWH_E_INVALID (before any device is touched): a NULL offsets table or workspace, a NULL descriptor / output array of a side
+ * that has rows, n_problems <= 0, a negative total, a workspace that is too small or misaligned.
+ *
+ * rwh_host_match_hamming: the same rule in plain C++ on the HOST for one pair (no device, no stream; works without a GPU):
+ * desc_a na x nbytes, desc_b nb x nbytes, train_idx / distance na int32.  RWH_E_INVALID: na < 0, nb < 0, a NULL array of a side
+ * that has rows; RWH_E_UNSUPPORTED: nbytes outside 1 .. RWH_MATCH_MAX_BYTES.
+ */
+#define RWH_MATCH_MAX_BYTES 64
+#define RWH_MATCH_TILE_TRAIN 256
+#define RWH_MATCH_CHUNK_QUERY 64
+#define RWH_MATCH_SEG_QUERY 256
+RWH_API int64_t rwh_match_workspace_bytes(int n_problems, int total_a, int total_b);
+RWH_API int rwh_match_hamming_batched(const uint8_t* d_desc_a, const uint8_t* d_desc_b, int nbytes, const int32_t* d_offsets_a,
+                              const int32_t* d_offsets_b, int n_problems, int total_a, int total_b, int32_t* d_train_idx,
+                              int32_t* d_distance, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_match_hamming(const uint8_t* desc_a, int na, const uint8_t* desc_b, int nb, int nbytes, int32_t* train_idx,
+                           int32_t* distance);
+
+/*
  * HOST helper of the settle step (no device work, no stream): the reference's own 4-point solve for n samples,
  *   calc_corresp (homography.py:4-14: 8 x 9 float32 DLT matrix, float32 products) -> numpy.linalg.svd (LAPACK dgesdd,
  *   float64 inside) -> last row of V^T cast to float32 -> / its 9th element in float32   (homography.py:71-88),

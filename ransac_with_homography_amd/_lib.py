@@ -23,13 +23,17 @@ RWH_HYP_REPEATED, RWH_HYP_SINGULAR, RWH_HYP_ILLCOND, RWH_HYP_DEGENERATE = 1, 2, 
 RWH_BATCH_DEVICE_SAMPLING = 1
 RWH_BATCH_EARLY_STOP = 2
 RWH_REFIT_OK, RWH_REFIT_FEW, RWH_REFIT_SINGULAR = 0, 1, 2
+RWH_E_INVALID, RWH_E_UNSUPPORTED, RWH_E_LAUNCH = -1, -2, -3
+RWH_MATCH_MAX_BYTES = 64
+RWH_MATCH_TILE_TRAIN, RWH_MATCH_CHUNK_QUERY, RWH_MATCH_SEG_QUERY = 256, 64, 256   # the matcher's block shape (include/rwh.h)
 RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRAMES = 0, 1, 2, 3
 
 # every symbol include/rwh.h declares (tests check the library exports them all)
 EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_probe", "rwh_warp_backward", "rwh_warp_plan", "rwh_sample_points", "rwh_dlt4_batched",
            "rwh_score_count", "rwh_project_points", "rwh_project_points_ex", "rwh_ransac_search", "rwh_ransac_batched", "rwh_stitch_panorama",
            "rwh_host_dlt4_svd", "rwh_ransac_run", "rwh_ransac_run_layout", "rwh_warp_index_check", "rwh_score_count_inv", "rwh_host_inv3", "rwh_stitch_panorama_rows",
-           "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex", "rwh_settle_decide", "rwh_refit_batched", "rwh_host_refit")
+           "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex", "rwh_settle_decide", "rwh_refit_batched", "rwh_host_refit",
+           "rwh_match_workspace_bytes", "rwh_match_hamming_batched", "rwh_host_match_hamming")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -115,6 +119,12 @@ def _bind(lib):
     lib.rwh_refit_batched.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp]
     lib.rwh_host_refit.restype = i32
     lib.rwh_host_refit.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.rwh_match_workspace_bytes.restype = i64
+    lib.rwh_match_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.rwh_match_hamming_batched.restype = i32
+    lib.rwh_match_hamming_batched.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]
+    lib.rwh_host_match_hamming.restype = i32
+    lib.rwh_host_match_hamming.argtypes = [vp, i32, vp, i32, i32, vp, vp]
     return lib
 
 

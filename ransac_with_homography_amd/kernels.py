@@ -403,6 +403,46 @@ def refit_batched(pts_a, pts_b, offsets, masks):
     return H, status
 
 
+# the matcher's block shape, for callers and tests that size problems across it: train rows per block, query rows staged in LDS at
+# a time, query rows per block (include/rwh.h)
+MATCH_TILE_TRAIN, MATCH_CHUNK_QUERY, MATCH_SEG_QUERY = _lib.RWH_MATCH_TILE_TRAIN, _lib.RWH_MATCH_CHUNK_QUERY, _lib.RWH_MATCH_SEG_QUERY
+MATCH_MAX_BYTES = _lib.RWH_MATCH_MAX_BYTES
+
+
+def match_hamming_batched(desc_a, desc_b, offsets_a, offsets_b):
+    """Brute-force Hamming matches with cross-check of P descriptor pairs in one library call (rwh_match_hamming_batched; the
+    rule, and the caveat that parity with OpenCV's BFMatcher is not verified, in include/rwh.h).
+
+    desc_a [total_a, nbytes] / desc_b [total_b, nbytes] uint8 (the problems' descriptors concatenated; query / train side),
+    offsets_a / offsets_b [P+1] int32 -- all on the GPU.  Returns (train_idx, distance), [total_a] int32 each on the GPU: per query
+    row its match's train row inside its problem and the distance, -1 / -1 for no match.  nbytes outside 1 .. MATCH_MAX_BYTES:
+    NotImplementedError."""
+    lib = _lib.load()
+    _dev_check(desc_a, desc_b, offsets_a, offsets_b)
+    if not (desc_a.dtype == torch.uint8 and desc_b.dtype == torch.uint8 and desc_a.dim() == 2 and desc_b.dim() == 2 and
+            desc_a.shape[1] == desc_b.shape[1]):
+        raise ValueError("descriptors: two uint8 [rows, nbytes] tensors of one row length, got %s %s and %s %s"
+                         % (desc_a.dtype, tuple(desc_a.shape), desc_b.dtype, tuple(desc_b.shape)))
+    if not (offsets_a.dtype == torch.int32 and offsets_b.dtype == torch.int32 and offsets_a.dim() == 1 and
+            offsets_a.shape == offsets_b.shape and offsets_a.shape[0] >= 2):
+        raise ValueError("offsets: two int32 [P + 1] tensors, P >= 1")
+    P, (total_a, nbytes), total_b = offsets_a.shape[0] - 1, desc_a.shape, desc_b.shape[0]
+    train_idx = torch.empty((total_a,), dtype=torch.int32, device=desc_a.device)
+    distance = torch.empty((total_a,), dtype=torch.int32, device=desc_a.device)
+    if nbytes == 0:         # rows without bytes have no address to hand over: the library's answer for this length, given here
+        raise NotImplementedError("match: descriptors of 0 bytes; the matcher takes 1 .. %d" % MATCH_MAX_BYTES)
+    ws_bytes = int(lib.rwh_match_workspace_bytes(P, total_a, total_b))
+    if ws_bytes < 0:
+        check(ws_bytes, "rwh_match_workspace_bytes")
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=desc_a.device)
+    status = lib.rwh_match_hamming_batched(_ptr(desc_a), _ptr(desc_b), nbytes, _ptr(offsets_a), _ptr(offsets_b), P, total_a, total_b,
+                                           _ptr(train_idx), _ptr(distance), _ptr(ws), ws_bytes, _lib.stream_ptr())
+    if status == _lib.RWH_E_UNSUPPORTED:
+        raise NotImplementedError("match: descriptors of %d bytes; the matcher takes 1 .. %d" % (nbytes, MATCH_MAX_BYTES))
+    check(status, "rwh_match_hamming_batched")
+    return train_idx, distance
+
+
 def project_points(h9, pts, inverse):
     """Launch the projection kernel: h9 [9] float32, pts [M,2] float32 -> [3,M] float32."""
     lib = _lib.load()

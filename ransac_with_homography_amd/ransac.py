@@ -718,6 +718,103 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
     return out
 
 
+def _to_device(x, dtype, dev, what):
+    """numpy array or tensor -> contiguous tensor of `dtype` on the GPU; a wrong dtype is refused, not cast."""
+    import torch
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    if t.dtype != dtype:
+        raise TypeError("%s: expected %s, got %s" % (what, dtype, t.dtype))
+    return t.to(dev).contiguous()
+
+
+def _host_rows(kps):
+    return kps.cpu().numpy() if hasattr(kps, "cpu") else np.asarray(kps)
+
+
+def match_batch(features, info=None):
+    """Brute-force Hamming matches with cross-check for MANY image pairs in one GPU submission, handed over as the
+    `DeviceProblems` that `run_batch` takes: the stage of ransac.py:258-267 (BFMatcher(NORM_HAMMING, crossCheck=True).match,
+    sorted by distance, keypoints gathered) in front of the batched search, without a visit to the host.
+
+    features: list of (kpsA float32 [Na, 2], descA uint8 [Na, nbytes], kpsB float32 [Nb, 2], descB uint8 [Nb, nbytes]) per pair,
+    numpy arrays or tensors; A is the "query" side, B the "train" side; one nbytes (1 .. 64) for the whole list.  Descriptor
+    extraction is the caller's: any binary extractor (ORB, BRIEF, BRISK, AKAZE, ...) serves.
+
+    The rule (include/rwh.h, rwh_match_hamming_batched): D[i, j] = popcount(A[i] xor B[j]); every train row j picks its nearest
+    query q[j] (lowest i on ties); every query i keeps, of the train rows that picked it, the nearest (lowest j on ties); the
+    matches are ordered by (distance, i), and problem p's correspondences are kpsA[i], kpsB[j] in that order.  This is how the
+    crossCheck path of OpenCV 4's BFMatcher reads -- NOT the textbook mutual nearest neighbour -- and parity with OpenCV is NOT
+    verified (OpenCV is not a dependency); the code is held to the rule as stated.
+
+    Returns a `DeviceProblems`.  The distances come from one library call; compaction, the ordering (one sort on a packed
+    (problem, distance, i) key) and the keypoint gather are tensor operations on the device, and the one download is the P match
+    counts that `DeviceProblems.sizes` holds.  `info`: optional dict, receives "query_idx" and "train_idx" (int32 device tensors,
+    indices inside each problem, in the order of the correspondences) and "distance".
+
+    A pair may have no matches (an empty side): its size is 0.  `run_batch` scores nothing for such a problem and returns
+    (None, no inliers, 0), as it does for a problem of fewer than four correspondences."""
+    import torch
+    dev = _lib.require_gpu()
+    P = len(features)
+    if P == 0:
+        raise ValueError("match_batch: no image pairs")
+    ka = [_to_device(f[0], torch.float32, dev, "kpsA").reshape(-1, 2) for f in features]
+    da = [_to_device(f[1], torch.uint8, dev, "descA") for f in features]
+    kb = [_to_device(f[2], torch.float32, dev, "kpsB").reshape(-1, 2) for f in features]
+    db = [_to_device(f[3], torch.uint8, dev, "descB") for f in features]
+    widths = set(int(t.shape[1]) for t in da + db if t.dim() == 2)
+    if any(t.dim() != 2 for t in da + db) or len(widths) != 1:
+        raise ValueError("match_batch: descriptors must be uint8 [rows, nbytes] with one nbytes for every pair")
+    for p in range(P):
+        if ka[p].shape[0] != da[p].shape[0] or kb[p].shape[0] != db[p].shape[0]:
+            raise ValueError("match_batch: pair %d has %d / %d keypoints for %d / %d descriptors"
+                             % (p, ka[p].shape[0], kb[p].shape[0], da[p].shape[0], db[p].shape[0]))
+    off_a = np.zeros(P + 1, dtype=np.int64)
+    off_b = np.zeros(P + 1, dtype=np.int64)
+    off_a[1:] = np.cumsum([t.shape[0] for t in da])
+    off_b[1:] = np.cumsum([t.shape[0] for t in db])
+    if off_a[-1] >= 2 ** 31 or off_b[-1] >= 2 ** 31 or P >= 2 ** 21:
+        raise ValueError("match_batch: too many rows or pairs for one submission")
+    off_a_dev = torch.from_numpy(off_a).to(dev)
+    off_b_dev = torch.from_numpy(off_b).to(dev)
+    train, dist = kernels.match_hamming_batched(torch.cat(da), torch.cat(db), off_a_dev.to(torch.int32), off_b_dev.to(torch.int32))
+    ka_all, kb_all = torch.cat(ka), torch.cat(kb)
+    total_a = int(off_a[-1])
+    row = torch.arange(total_a, device=dev)
+    prob = torch.searchsorted(off_a_dev[1:].contiguous(), row, right=True)      # the problem of every query row
+    local = row - off_a_dev[prob]
+    found = train >= 0
+    # (problem, distance, i) in one int64: i < 2^31, distance <= 512 < 2^10, problem < 2^21; rows without a match sort last
+    key = ((prob << 10) + dist.to(torch.int64).clamp(min=0) << 31) + local
+    key = torch.where(found, key, torch.full_like(key, torch.iinfo(torch.int64).max))
+    order = torch.sort(key, stable=True).indices
+    sizes = torch.bincount(prob[found], minlength=P).cpu().numpy()              # the one download
+    order = order[:int(sizes.sum())]
+    q_local, t_local, p_of = local[order], train[order].to(torch.int64), prob[order]
+    # one spare row behind the correspondences: the 4-point kernel reads row 0 of a problem that has none
+    n = order.shape[0]
+    pts_a = torch.zeros((n + 1, 2), dtype=torch.float32, device=dev)
+    pts_b = torch.zeros((n + 1, 2), dtype=torch.float32, device=dev)
+    pts_a[:n] = ka_all[order]
+    pts_b[:n] = kb_all[off_b_dev[p_of] + t_local]
+    if info is not None:
+        info["query_idx"], info["train_idx"], info["distance"] = q_local.to(torch.int32), t_local.to(torch.int32), dist[order]
+    return DeviceProblems(pts_a[:n], pts_b[:n], sizes)
+
+
+def match_descriptors(descA, descB):
+    """One pair through `match_batch`'s matcher: descA [Na, nbytes], descB [Nb, nbytes] uint8 (numpy or tensors; "query" and
+    "train" side) -> (queryIdx, trainIdx, distance), int32 numpy arrays ordered by (distance, queryIdx): the fields of
+    `sorted(bf.match(descA, descB), key=lambda m: m.distance)` (ransac.py:258-261) under the rule stated at `match_batch`
+    (parity with OpenCV not verified)."""
+    import torch
+    info = {}
+    na, nb = int(descA.shape[0]), int(descB.shape[0])
+    match_batch([(torch.zeros((na, 2), dtype=torch.float32), descA, torch.zeros((nb, 2), dtype=torch.float32), descB)], info=info)
+    both = torch.stack([info["query_idx"], info["train_idx"], info["distance"]]).cpu().numpy()
+    return both[0].copy(), both[1].copy(), both[2].copy()
+
+
 def _match_features(trainImg, queryImg):
     """ORB + brute-force Hamming matcher of ransac.py:252-267.  This is OpenCV C++ and outside the
     GPU path; it runs only when cv2 is installed."""
@@ -739,15 +836,24 @@ def _match_features(trainImg, queryImg):
 
 
 def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blending=False, blendrate=0.2,
-              mode=None, override=0, cylinderT=1, matches=None):
+              mode=None, override=0, cylinderT=1, matches=None, features=None):
     """Panorama pipeline of ransac.py:235-283: matches -> RANSAC homography -> warp + composite.
     `matches=(ptsA, ptsB)` injects precomputed correspondences so the
-    GPU path works without OpenCV; everything else keeps the reference's signature."""
+    GPU path works without OpenCV; `features=(kpsA, descA, kpsB, descB)` (keypoints float32 [N, 2], binary descriptors uint8
+    [N, nbytes], A = trainImg's) injects the extractor's output and matches it on the GPU (`match_descriptors`).  `matches` wins
+    over `features`; with neither, the OpenCV path runs.  Everything else keeps the reference's signature."""
     if override != 0:
         import cv2
         status, imgn = cv2.Stitcher_create().stitch([trainImg, queryImg])
         return imgn
-    ptsA, ptsB = matches if matches is not None else _match_features(trainImg, queryImg)
+    if matches is not None:
+        ptsA, ptsB = matches
+    elif features is not None:
+        kpsA, descA, kpsB, descB = features
+        qi, ti, _ = match_descriptors(descA, descB)
+        ptsA, ptsB = _host_rows(kpsA)[qi], _host_rows(kpsB)[ti]
+    else:
+        ptsA, ptsB = _match_features(trainImg, queryImg)
     ptsA = np.asarray(ptsA, dtype=np.float32)
     ptsB = np.asarray(ptsB, dtype=np.float32)
     if mode is None:
