@@ -391,6 +391,87 @@ RWH_API int rwh_host_match_hamming(const uint8_t* desc_a, int na, const uint8_t*
                            int32_t* distance);
 
 /*
+ * Feature extractor for a batch of images: FAST-9 corners with non-maximum suppression, intensity-centroid orientation in 12-degree
+ * bins and a steered BRIEF descriptor -- the stage in front of rwh_match_hamming_batched.  Stands where the reference calls
+ *   cv2.cvtColor(img, cv2.COLOR_RGB2GRAY); cv2.ORB_create().detectAndCompute(gray, None)      ransac.py:252-257
+ * PROVENANCE AND CAVEAT.  The rule below is taken from the ORB paper (Rublee, Rabaud, Konolige, Bradski 2011: FAST-9, intensity
+ * centroid, BRIEF steered in 12-degree steps, 5 x 5 box tests), on ONE scale.  It is NOT OpenCV's ORB: no scale pyramid, no Harris
+ * ranking, no learned test pattern as a default, no sub-pixel refinement.  OpenCV is not a dependency of this project and was not
+ * available where this was written: parity with OpenCV's ORB is NEITHER CLAIMED NOR VERIFIED.  The code is held to the rule as
+ * stated (tests/orb_cases.py restates it in numpy); every quantity is an integer, so results are exact, do not depend on the order
+ * in which the device finds keypoints, and a rerun is bit-identical.  Any binary descriptor serves the matcher.
+ * THE RULE, for one image of h rows x w columns.
+ *   1. Gray.  Pixels are uint8.  c == 1: the plane is gray already.  c == 3 (R, G, B) or c == 4 (R, G, B, alpha; alpha ignored):
+ *        g = (4899 R + 9617 G + 1868 B + 8192) >> 14        (the 8-bit fixed-point form of COLOR_RGB2GRAY)
+ *   2. Score.  The 16 circle pixels p_0 .. p_15 of pixel (x, y) sit at the offsets (dx, dy), y downwards,
+ *        (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3)
+ *      and d_i = p_i - g(x, y).  An arc is 9 circle pixels with consecutive indices modulo 16 (16 arcs).
+ *        S(x, y) = max( max over the arcs of min over the arc of d_i,  max over the arcs of min over the arc of -d_i,  0 )
+ *      for 3 <= x < w - 3 and 3 <= y < h - 3; S = 0 elsewhere (in particular outside the image).
+ *   3. Keypoints.  (x, y) is a keypoint when S(x, y) > threshold, S(x, y) > S at each of its eight neighbours, and
+ *      RWH_ORB_BORDER <= x <= w - 1 - RWH_ORB_BORDER, RWH_ORB_BORDER <= y <= h - 1 - RWH_ORB_BORDER (the patch of radius 15 plus one
+ *      pixel).  An image with a side below 2 RWH_ORB_BORDER + 1 has none.  Keypoints are ordered by (S descending, y ascending, x
+ *      ascending) -- a total order -- and the first n_features are kept.
+ *   4. Orientation.  Over the offsets with dx^2 + dy^2 <= 15^2:  m10 = sum dx g(x + dx, y + dy),  m01 = sum dy g(x + dx, y + dy).
+ *      The caller passes the bin table: RWH_ORB_BINS boundary directions b_k = (bx_k, by_k) = round(2^15 (cos, sin)((k - 1/2) 12
+ *      degrees)), int32, k = 0 .. 29, and b_30 = b_0.  With cross(b, m) = bx m01 - by m10 in 64-bit integers, the bin is the k with
+ *      cross(b_k, m) >= 0 and cross(b_(k+1), m) < 0 (exactly one k for m != 0: the 12-degree sector centred on k 12 degrees that
+ *      holds m, its lower boundary included); m == (0, 0) gives bin 0.  No atan2 anywhere.
+ *   5. Descriptor.  The caller passes the rotated patterns: int8 [RWH_ORB_BINS][nbits][4], nbits = 8 nbytes, row (k, t) = the test
+ *      (x1, y1, x2, y2) of bit t rotated by k 12 degrees and rounded to integers, every coordinate in [-RWH_ORB_TEST_RADIUS,
+ *      RWH_ORB_TEST_RADIUS] (a PRECONDITION of the device entry point, whose table lives on the device: coordinates outside are
+ *      clamped there to keep the reads inside the patch; the host twin refuses such a table).  box(u, v) = the sum of g over the 5 x 5
+ *      window centred on (u, v).  Bit t of a keypoint (x, y) with bin k is  box(x + x1, y + y1) < box(x + x2, y + y2),  stored in byte
+ *      t >> 3 at bit t & 7.
+ * rwh_orb_detect_batched: rules 1 - 3 without the order, for n_images images in one submission.
+ *   d_images: the images' bytes concatenated (images_bytes in all); d_table: n_images x 5 int64 on the device, row i = (byte offset
+ *   of image i in d_images, byte offset of its gray plane in d_gray, h, w, c), pixels interleaved, rows contiguous.  A row that does
+ *   not describe an image inside the two buffers (negative offset, h or w outside 1 .. 65536, c not 1, 3 or 4, an end past
+ *   images_bytes / gray_bytes) is treated as an image without pixels;
+ *   d_gray (gray_bytes): receives every image's gray plane (rule 1), h x w uint8, for rwh_orb_describe_batched;
+ *   d_keys: n_images x capacity uint64, d_counts: n_images int32.  Every keypoint of image i (threshold 0 .. 254) is appended to row i
+ *   of d_keys, in no particular order, as the key (255 - S) << 32 | y << 16 | x: ascending keys are the order of rule 3.  d_counts[i]
+ *   = the number of keypoints FOUND.  OVERFLOW: d_counts[i] > capacity says that only `capacity` of them, an arbitrary subset, were
+ *   stored -- nothing is written past the row; the caller repeats the call with a larger capacity (ceil((w - 32) / 2) x ceil((h -
+ *   32) / 2) always holds every keypoint, since no two keypoints are neighbours).  Unused entries of a row are RWH_ORB_KEY_NONE, above every key as signed and as unsigned words;
+ *   d_workspace: workspace_bytes >= rwh_orb_workspace_bytes(n_images) = 8 (n_images + 1) bytes of device memory, 8-byte aligned.
+ * Work: one block of 256 lanes per tile of RWH_ORB_TILE_W x RWH_ORB_TILE_H pixels, staged with a halo of 4 as gray bytes in LDS; one
+ * atomic per wave that found a keypoint.  Two launches and two memsets, whatever n_images.
+ * RWH_E_INVALID (before any device is touched): NULL pointer, n_images <= 0, capacity <= 0, negative sizes, threshold outside 0 ..
+ * 254, a workspace that is too small or misaligned.
+ * rwh_orb_describe_batched: rules 4 and 5 for the first min(d_counts[i], n_features, key_stride) keys of row i of d_keys (n_images
+ *   rows of key_stride uint64: the rows of rwh_orb_detect_batched after the caller sorted each), one wavefront per keypoint.  Slot j
+ *   of image i writes row i n_features + j of d_kps (float32 x, y), d_desc (nbytes uint8), d_score (int32 S) and d_bin (int32);
+ *   other rows are not written.  A key whose (x, y) is not inside the border of its image writes nothing.
+ *   d_bin_table: RWH_ORB_BINS x 2 int32; d_pattern: RWH_ORB_BINS x 8 nbytes x 4 int8 (rules 4 and 5), both on the device.
+ *   nbytes: 1 .. RWH_MATCH_MAX_BYTES, else RWH_E_UNSUPPORTED.  RWH_E_INVALID: NULL pointer, n_images <= 0, n_features <= 0,
+ *   key_stride <= 0, gray_bytes < 0.  One launch.
+ * rwh_host_orb_extract: the whole rule in plain C++ on the HOST for one image (no device, no stream; works without a GPU).
+ *   img: h x w x c uint8; bin_table and pattern as above, on the host; kps n_features x 2 float32, desc n_features x nbytes, score and
+ *   bin n_features int32; *out_count = the number of keypoints written (<= n_features), *out_found (may be NULL) = the number found
+ *   before the cut.  RWH_E_INVALID: NULL pointer, h or w outside 1 .. 65536, n_features < 0, threshold outside 0 .. 254, a pattern
+ *   coordinate outside +-RWH_ORB_TEST_RADIUS; RWH_E_UNSUPPORTED: c not 1, 3 or 4, nbytes outside 1 .. RWH_MATCH_MAX_BYTES.
+ */
+#define RWH_ORB_BORDER 16
+#define RWH_ORB_BINS 30
+#define RWH_ORB_PATCH_RADIUS 15
+#define RWH_ORB_TEST_RADIUS 13
+#define RWH_ORB_TILE_W 64
+#define RWH_ORB_TILE_H 16
+#define RWH_ORB_KEY_NONE 0x7F7F7F7F7F7F7F7Full
+RWH_API int64_t rwh_orb_workspace_bytes(int n_images);
+RWH_API int rwh_orb_detect_batched(const uint8_t* d_images, int64_t images_bytes, const int64_t* d_table, int n_images, int threshold,
+                           uint8_t* d_gray, int64_t gray_bytes, uint64_t* d_keys, int capacity, int32_t* d_counts,
+                           void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_orb_describe_batched(const uint8_t* d_gray, int64_t gray_bytes, const int64_t* d_table, int n_images,
+                             const uint64_t* d_keys, int key_stride, const int32_t* d_counts, int n_features,
+                             const int32_t* d_bin_table, const int8_t* d_pattern, int nbytes, float* d_kps, uint8_t* d_desc,
+                             int32_t* d_score, int32_t* d_bin, void* stream);
+RWH_API int rwh_host_orb_extract(const uint8_t* img, int h, int w, int c, int threshold, int n_features, const int32_t* bin_table,
+                         const int8_t* pattern, int nbytes, float* kps, uint8_t* desc, int32_t* score, int32_t* bin,
+                         int32_t* out_count, int32_t* out_found);
+
+/*
  * HOST helper of the settle step (no device work, no stream): the reference's own 4-point solve for n samples,
  *   calc_corresp (homography.py:4-14: 8 x 9 float32 DLT matrix, float32 products) -> numpy.linalg.svd (LAPACK dgesdd,
  *   float64 inside) -> last row of V^T cast to float32 -> / its 9th element in float32   (homography.py:71-88),

@@ -4,6 +4,7 @@
 // OpenBLAS the caller's numpy links (ransac_with_homography_amd/_lapack.py finds the symbol), called with numpy's own
 // arguments (jobz = 'A', column-major copy, workspace from a size query) -- so every H equals numpy's bit for bit
 // (tests/test_settle_cpu.py); what this file adds is the loop in native code, off the interpreter lock, on several cores.
+#include <algorithm>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
@@ -250,5 +251,86 @@ extern "C" int rwh_host_legacy_randint(uint32_t* key, int32_t* pos, int64_t m, i
         if (out64) out64[i] = (int64_t)v;
     }
     *pos = p;
+    return RWH_OK;
+}
+
+// The feature extractor's rule (include/rwh.h, rwh_orb_detect_batched / rwh_orb_describe_batched) in plain C++ for one image: whole
+// planes, no tiles, no pre-test, a sort of the keys.
+extern "C" int rwh_host_orb_extract(const uint8_t* img, int h, int w, int c, int threshold, int n_features, const int32_t* bin_table,
+                                    const int8_t* pattern, int nbytes, float* kps, uint8_t* desc, int32_t* score, int32_t* bin,
+                                    int32_t* out_count, int32_t* out_found) {
+    if (!img || !bin_table || !pattern || !out_count || h < 1 || w < 1 || h > 65536 || w > 65536 || n_features < 0 || threshold < 0 ||
+        threshold > 254 || (n_features > 0 && (!kps || !desc || !score || !bin)))
+        return RWH_E_INVALID;
+    if ((c != 1 && c != 3 && c != 4) || nbytes < 1 || nbytes > RWH_MATCH_MAX_BYTES) return RWH_E_UNSUPPORTED;
+    const int nbits = 8 * nbytes, R = RWH_ORB_TEST_RADIUS, PR = RWH_ORB_PATCH_RADIUS, B = RWH_ORB_BORDER;
+    for (long long i = 0; i < (long long)RWH_ORB_BINS * nbits * 4; ++i)
+        if (pattern[i] < -R || pattern[i] > R) return RWH_E_INVALID;
+    *out_count = 0;
+    if (out_found) *out_found = 0;
+    const size_t n = (size_t)h * (size_t)w;
+    std::vector<uint8_t> g(n), S(n, 0);
+    for (size_t i = 0; i < n; ++i) {                                        // rule 1
+        const uint8_t* q = img + i * (size_t)c;
+        g[i] = c == 1 ? q[0] : (uint8_t)((4899 * q[0] + 9617 * q[1] + 1868 * q[2] + 8192) >> 14);
+    }
+    static const int CX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
+    static const int CY[16] = {-3, -3, -2, -1, 0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3};
+    for (int y = 3; y < h - 3; ++y)                                         // rule 2
+        for (int x = 3; x < w - 3; ++x) {
+            int d[16], best = 0;
+            for (int i = 0; i < 16; ++i) d[i] = (int)g[(size_t)(y + CY[i]) * w + (x + CX[i])] - (int)g[(size_t)y * w + x];
+            for (int a = 0; a < 16; ++a) {
+                int lo = 255, hi = 255;
+                for (int j = 0; j < 9; ++j) { const int v = d[(a + j) & 15]; lo = std::min(lo, v); hi = std::min(hi, -v); }
+                best = std::max(best, std::max(lo, hi));
+            }
+            S[(size_t)y * w + x] = (uint8_t)best;
+        }
+    std::vector<uint64_t> keys;                                             // rule 3
+    for (int y = B; y <= h - 1 - B; ++y)
+        for (int x = B; x <= w - 1 - B; ++x) {
+            const int s = S[(size_t)y * w + x];
+            if (s <= threshold) continue;
+            bool top = true;
+            for (int dy = -1; dy <= 1 && top; ++dy)
+                for (int dx = -1; dx <= 1; ++dx)
+                    if ((dx || dy) && S[(size_t)(y + dy) * w + (x + dx)] >= s) { top = false; break; }
+            if (top) keys.push_back(((uint64_t)(255 - s) << 32) | ((uint64_t)y << 16) | (uint64_t)x);
+        }
+    std::sort(keys.begin(), keys.end());
+    if (out_found) *out_found = (int32_t)std::min<size_t>(keys.size(), 0x7FFFFFFF);
+    const int kept = (int)std::min<size_t>(keys.size(), (size_t)n_features);
+    for (int i = 0; i < kept; ++i) {
+        const int x = (int)(keys[i] & 0xFFFF), y = (int)((keys[i] >> 16) & 0xFFFF);
+        long long m10 = 0, m01 = 0;                                         // rule 4
+        for (int dy = -PR; dy <= PR; ++dy)
+            for (int dx = -PR; dx <= PR; ++dx)
+                if (dx * dx + dy * dy <= PR * PR) {
+                    const int v = g[(size_t)(y + dy) * w + (x + dx)];
+                    m10 += dx * v; m01 += dy * v;
+                }
+        int k = 0;
+        for (int j = 0; j < RWH_ORB_BINS; ++j) {
+            const int j1 = (j + 1) % RWH_ORB_BINS;
+            const long long c0 = (long long)bin_table[2 * j] * m01 - (long long)bin_table[2 * j + 1] * m10;
+            const long long c1 = (long long)bin_table[2 * j1] * m01 - (long long)bin_table[2 * j1 + 1] * m10;
+            if (c0 >= 0 && c1 < 0) { k = j; break; }
+        }
+        auto box = [&](int u, int v) {                                      // rule 5
+            int sum = 0;
+            for (int dy = -2; dy <= 2; ++dy)
+                for (int dx = -2; dx <= 2; ++dx) sum += g[(size_t)(v + dy) * w + (u + dx)];
+            return sum;
+        };
+        uint8_t* out = desc + (size_t)i * nbytes;
+        for (int b = 0; b < nbytes; ++b) out[b] = 0;
+        const int8_t* pat = pattern + (size_t)k * nbits * 4;
+        for (int t = 0; t < nbits; ++t)
+            if (box(x + pat[4 * t], y + pat[4 * t + 1]) < box(x + pat[4 * t + 2], y + pat[4 * t + 3])) out[t >> 3] |= (uint8_t)(1u << (t & 7));
+        kps[2 * i] = (float)x; kps[2 * i + 1] = (float)y;
+        score[i] = 255 - (int)(keys[i] >> 32); bin[i] = k;
+    }
+    *out_count = kept;
     return RWH_OK;
 }

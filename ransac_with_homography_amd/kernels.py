@@ -443,6 +443,72 @@ def match_hamming_batched(desc_a, desc_b, offsets_a, offsets_b):
     return train_idx, distance
 
 
+# the extractor's constants (include/rwh.h): border of a keypoint's centre, orientation bins, radius of the test points, the
+# detector's tile -- for callers and tests that plant corners across tile seams
+ORB_BORDER, ORB_BINS, ORB_TEST_RADIUS = _lib.RWH_ORB_BORDER, _lib.RWH_ORB_BINS, _lib.RWH_ORB_TEST_RADIUS
+ORB_TILE_W, ORB_TILE_H = _lib.RWH_ORB_TILE_W, _lib.RWH_ORB_TILE_H
+
+
+def orb_detect_batched(images, table, gray_bytes, threshold, capacity, out_keys=None):
+    """FAST-9 corners with non-maximum suppression of a batch of images in one library call (rwh_orb_detect_batched; the rule,
+    and the caveat that this is not OpenCV's ORB, in include/rwh.h).
+
+    images: uint8 [bytes], the images' pixels concatenated; table: int64 [n, 5], row i = (byte offset of image i, byte offset of
+    its gray plane, h, w, c) -- both on the GPU.  Returns (gray uint8 [gray_bytes], keys int64 [n, capacity], counts int32 [n]) on
+    the GPU: the gray planes, per image its keypoints as keys (255 - S) << 32 | y << 16 | x in no particular order (unused entries
+    0x7F7F7F7F7F7F7F7F, which sort last), and the number of keypoints found.  counts[i] > capacity: only
+    `capacity` of them were stored (overflow; call again with more room).  out_keys: an int64 [n, capacity] tensor to fill instead
+    of a new one."""
+    lib = _lib.load()
+    _dev_check(images, table)
+    if not (images.dtype == torch.uint8 and images.dim() == 1 and table.dtype == torch.int64 and table.dim() == 2 and
+            table.shape[1] == 5 and table.shape[0] >= 1):
+        raise ValueError("orb_detect_batched: images uint8 [bytes] and table int64 [n, 5], got %s %s and %s %s"
+                         % (images.dtype, tuple(images.shape), table.dtype, tuple(table.shape)))
+    n = table.shape[0]
+    gray = torch.empty((max(int(gray_bytes), 1),), dtype=torch.uint8, device=images.device)
+    keys = out_keys if out_keys is not None else torch.empty((n, int(capacity)), dtype=torch.int64, device=images.device)
+    _dev_check(keys)
+    if keys.dtype != torch.int64 or tuple(keys.shape) != (n, int(capacity)):
+        raise ValueError("orb_detect_batched: out_keys must be int64 [%d, %d]" % (n, capacity))
+    counts = torch.empty((n,), dtype=torch.int32, device=images.device)
+    ws_bytes = int(lib.rwh_orb_workspace_bytes(n))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=images.device)
+    check(lib.rwh_orb_detect_batched(_ptr(images), images.shape[0], _ptr(table), n, int(threshold), _ptr(gray), int(gray_bytes), _ptr(keys),
+                                     int(capacity), _ptr(counts), _ptr(ws), ws_bytes, _lib.stream_ptr()), "rwh_orb_detect_batched")
+    return gray, keys, counts
+
+
+def orb_describe_batched(gray, gray_bytes, table, keys, counts, n_features, bin_table, pattern):
+    """Orientation bin and steered BRIEF descriptor of the first min(counts[i], n_features) keys of every row of `keys`
+    (rwh_orb_describe_batched, include/rwh.h), one wavefront per keypoint.
+
+    gray, table: as orb_detect_batched gave / took them; keys: int64 [n, stride], every row SORTED ascending; counts: int32 [n];
+    bin_table: int32 [30, 2]; pattern: int8 [30, 8 * nbytes, 4] -- all on the GPU.  Returns (kps float32 [n, n_features, 2] as
+    (x, y), desc uint8 [n, n_features, nbytes], score int32 [n, n_features], bin int32 [n, n_features]) on the GPU; rows past an
+    image's count are zero.  nbytes outside 1 .. MATCH_MAX_BYTES: NotImplementedError."""
+    lib = _lib.load()
+    _dev_check(gray, table, keys, counts, bin_table, pattern)
+    n = table.shape[0]
+    if not (keys.dtype == torch.int64 and keys.dim() == 2 and keys.shape[0] == n and counts.dtype == torch.int32 and
+            tuple(counts.shape) == (n,) and bin_table.dtype == torch.int32 and tuple(bin_table.shape) == (ORB_BINS, 2) and
+            pattern.dtype == torch.int8 and pattern.dim() == 3 and pattern.shape[0] == ORB_BINS and pattern.shape[2] == 4 and
+            pattern.shape[1] % 8 == 0):
+        raise ValueError("orb_describe_batched: keys int64 [n, stride], counts int32 [n], bin_table int32 [30, 2], pattern int8 [30, nbits, 4]")
+    nbytes = pattern.shape[1] // 8
+    if nbytes < 1 or nbytes > MATCH_MAX_BYTES:
+        raise NotImplementedError("orb: descriptors of %d bytes; the extractor takes 1 .. %d" % (nbytes, MATCH_MAX_BYTES))
+    dev, nf = gray.device, int(n_features)
+    kps = torch.zeros((n, nf, 2), dtype=torch.float32, device=dev)
+    desc = torch.zeros((n, nf, nbytes), dtype=torch.uint8, device=dev)
+    score = torch.zeros((n, nf), dtype=torch.int32, device=dev)
+    bins = torch.zeros((n, nf), dtype=torch.int32, device=dev)
+    check(lib.rwh_orb_describe_batched(_ptr(gray), int(gray_bytes), _ptr(table), n, _ptr(keys), keys.shape[1], _ptr(counts), nf, _ptr(bin_table),
+                                       _ptr(pattern), nbytes, _ptr(kps), _ptr(desc), _ptr(score), _ptr(bins), _lib.stream_ptr()),
+          "rwh_orb_describe_batched")
+    return kps, desc, score, bins
+
+
 def project_points(h9, pts, inverse):
     """Launch the projection kernel: h9 [9] float32, pts [M,2] float32 -> [3,M] float32."""
     lib = _lib.load()

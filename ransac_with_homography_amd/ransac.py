@@ -737,8 +737,8 @@ def match_batch(features, info=None):
     sorted by distance, keypoints gathered) in front of the batched search, without a visit to the host.
 
     features: list of (kpsA float32 [Na, 2], descA uint8 [Na, nbytes], kpsB float32 [Nb, 2], descB uint8 [Nb, nbytes]) per pair,
-    numpy arrays or tensors; A is the "query" side, B the "train" side; one nbytes (1 .. 64) for the whole list.  Descriptor
-    extraction is the caller's: any binary extractor (ORB, BRIEF, BRISK, AKAZE, ...) serves.
+    numpy arrays or tensors; A is the "query" side, B the "train" side; one nbytes (1 .. 64) for the whole list.  Any binary
+    extractor (ORB, BRIEF, BRISK, AKAZE, ...) serves; `extract_batch` is the package's own.
 
     The rule (include/rwh.h, rwh_match_hamming_batched): D[i, j] = popcount(A[i] xor B[j]); every train row j picks its nearest
     query q[j] (lowest i on ties); every query i keeps, of the train rows that picked it, the nearest (lowest j on ties); the
@@ -802,6 +802,150 @@ def match_batch(features, info=None):
     return DeviceProblems(pts_a[:n], pts_b[:n], sizes)
 
 
+# ---- the feature extractor (include/rwh.h, rwh_orb_detect_batched / rwh_orb_describe_batched): its tables, made on the host ----
+ORB_BINS, ORB_BORDER, ORB_TEST_RADIUS = _lib.RWH_ORB_BINS, _lib.RWH_ORB_BORDER, _lib.RWH_ORB_TEST_RADIUS
+ORB_PATTERN_SEED = 2011
+_ORB_DEFAULT_CAPACITY = 1 << 16
+
+
+def orb_bin_table():
+    """The 30 sector boundaries of the orientation rule: int32 [30, 2], row k = round(2^15 (cos, sin)((k - 1/2) 12 degrees))."""
+    a = np.deg2rad((np.arange(ORB_BINS) - 0.5) * (360.0 / ORB_BINS))
+    return np.rint(32768.0 * np.stack([np.cos(a), np.sin(a)], axis=1)).astype(np.int32)
+
+
+def default_pattern(nbytes=32):
+    """The default BRIEF test pattern: int8 [8 * nbytes, 4], rows (x1, y1, x2, y2).  The recipe: numpy's legacy
+    RandomState(ORB_PATTERN_SEED); per test four draws normal(0, 31 / 5) rounded with rint; a test is rejected (and drawn again)
+    when a point lies outside radius 13 or the two points coincide.  The same table on every call, and a shorter pattern is a
+    prefix of a longer one.  It is NOT OpenCV's learned ORB pattern; a caller who owns that one passes it as `pattern=`."""
+    nbytes = int(nbytes)
+    if not 1 <= nbytes <= _lib.RWH_MATCH_MAX_BYTES:
+        raise NotImplementedError("orb: descriptors of %d bytes; the extractor takes 1 .. %d" % (nbytes, _lib.RWH_MATCH_MAX_BYTES))
+    rng = np.random.RandomState(ORB_PATTERN_SEED)
+    out = np.empty((8 * nbytes, 4), dtype=np.int8)
+    t = 0
+    while t < out.shape[0]:
+        x1, y1, x2, y2 = (int(v) for v in np.rint(rng.normal(0.0, 31.0 / 5.0, 4)))
+        if x1 * x1 + y1 * y1 > ORB_TEST_RADIUS ** 2 or x2 * x2 + y2 * y2 > ORB_TEST_RADIUS ** 2 or (x1, y1) == (x2, y2):
+            continue
+        out[t] = (x1, y1, x2, y2)
+        t += 1
+    return out
+
+
+def _check_pattern(pattern, nbytes):
+    pat = np.asarray(pattern)
+    if pat.dtype.kind not in "iu" or pat.ndim != 2 or pat.shape[1] != 4 or pat.shape[0] == 0 or pat.shape[0] % 8:
+        raise ValueError("orb: pattern must be an integer [8 * nbytes, 4] table of (x1, y1, x2, y2), got %s %s" % (pat.dtype, pat.shape))
+    if nbytes is not None and pat.shape[0] != 8 * int(nbytes):
+        raise ValueError("orb: pattern has %d tests, nbytes = %d needs %d" % (pat.shape[0], nbytes, 8 * int(nbytes)))
+    if pat.shape[0] // 8 > _lib.RWH_MATCH_MAX_BYTES:
+        raise NotImplementedError("orb: descriptors of %d bytes; the extractor takes 1 .. %d" % (pat.shape[0] // 8, _lib.RWH_MATCH_MAX_BYTES))
+    p = pat.astype(np.int64)
+    if ((p[:, 0] ** 2 + p[:, 1] ** 2 > ORB_TEST_RADIUS ** 2) | (p[:, 2] ** 2 + p[:, 3] ** 2 > ORB_TEST_RADIUS ** 2)).any():
+        raise ValueError("orb: a pattern point lies outside radius %d" % ORB_TEST_RADIUS)
+    return p
+
+
+def rotate_pattern(pattern):
+    """The 30 steered copies of a test pattern: int8 [30, nbits, 4], copy k = every point rotated by k 12 degrees in float64,
+    (x cos - y sin, x sin + y cos), and rounded with rint; a point within radius 13 keeps every coordinate within +-13."""
+    p = _check_pattern(pattern, None).astype(np.float64)
+    a = np.deg2rad(np.arange(ORB_BINS) * (360.0 / ORB_BINS))[:, None]
+    c, s = np.cos(a), np.sin(a)
+    out = np.empty((ORB_BINS, p.shape[0], 4), dtype=np.float64)
+    for o in (0, 2):
+        out[:, :, o] = p[None, :, o] * c - p[None, :, o + 1] * s
+        out[:, :, o + 1] = p[None, :, o] * s + p[None, :, o + 1] * c
+    out = np.rint(out)
+    assert np.abs(out).max() <= ORB_TEST_RADIUS
+    return out.astype(np.int8)
+
+
+def _orb_image(img, dev, i):
+    """numpy array or tensor -> (flat uint8 tensor on the GPU, h, w, c); uint8 [h, w], [h, w, 3] or [h, w, 4] only."""
+    import torch
+    t = img if isinstance(img, torch.Tensor) else (torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else None)
+    if t is None:
+        raise TypeError("extract_batch: image %d is a %s; numpy arrays and tensors are taken" % (i, type(img).__name__))
+    if t.dtype != torch.uint8:
+        raise TypeError("extract_batch: image %d is %s; the extractor takes uint8" % (i, t.dtype))
+    if t.dim() == 2:
+        c = 1
+    elif t.dim() == 3 and t.shape[2] in (3, 4):
+        c = int(t.shape[2])
+    else:
+        raise ValueError("extract_batch: image %d has shape %s; [h, w], [h, w, 3] or [h, w, 4]" % (i, tuple(t.shape)))
+    h, w = int(t.shape[0]), int(t.shape[1])
+    if not (1 <= h <= 65536 and 1 <= w <= 65536):
+        raise ValueError("extract_batch: image %d is %d x %d; sides of 1 .. 65536" % (i, h, w))
+    return t.to(dev).contiguous().reshape(-1), h, w, c
+
+
+def extract_batch(images, n_features=500, threshold=20, nbytes=32, pattern=None, info=None):
+    """Keypoints and binary descriptors of MANY images in one GPU submission: the stage of ransac.py:252-257
+    (cvtColor(RGB2GRAY) + ORB_create().detectAndCompute) in front of `match_batch`, by the rule stated in include/rwh.h --
+    FAST-9 corners with 3 x 3 non-maximum suppression on ONE scale, ordered by (score descending, y, x) and cut at n_features;
+    intensity-centroid orientation in 30 bins of 12 degrees; BRIEF steered by the bin, 5 x 5 box tests.  It follows the ORB paper
+    (Rublee et al. 2011), NOT OpenCV's code: no pyramid, no Harris ranking, not OpenCV's learned pattern, no sub-pixel refinement;
+    parity with OpenCV's ORB is neither claimed nor verified.  Everything is an integer: results are exact and a rerun is identical.
+
+    images: list of uint8 numpy arrays or tensors, [h, w, 3] RGB, [h, w, 4] RGBA (alpha ignored) or [h, w] gray; shapes may differ.
+    threshold: 0 .. 254; nbytes: 1 .. 64; pattern: an integer [8 * nbytes, 4] table of tests (x1, y1, x2, y2) within radius 13
+    (default: `default_pattern(nbytes)`).  Returns a list of (kps float32 [N, 2] as (x, y), desc uint8 [N, nbytes]) device tensors,
+    N <= n_features, ready to be paired into `match_batch`'s `features`.  `info`: optional dict, receives "score" and "bin" (lists
+    of int32 device tensors), "counts" (keypoints kept per image) and "found" (before the cut).
+
+    Three library launches (detect, describe and their setup) around one sort of the keys; the one download is the per-image
+    keypoint counts."""
+    import torch
+    dev = _lib.require_gpu()
+    n = len(images)
+    if n == 0:
+        raise ValueError("extract_batch: no images")
+    n_features, threshold = int(n_features), int(threshold)
+    if n_features < 1:
+        raise ValueError("extract_batch: n_features must be positive")
+    if not 0 <= threshold <= 254:
+        raise ValueError("extract_batch: threshold %d outside 0 .. 254" % threshold)
+    pat = default_pattern(nbytes) if pattern is None else _check_pattern(pattern, nbytes)
+    rot = torch.from_numpy(rotate_pattern(pat)).to(dev)
+    bins_t = torch.from_numpy(orb_bin_table()).to(dev)
+    flat, table, src_off, gray_off, full = [], [], 0, 0, 1
+    for i, img in enumerate(images):
+        t, h, w, c = _orb_image(img, dev, i)
+        flat.append(t)
+        table.append((src_off, gray_off, h, w, c))
+        src_off += h * w * c
+        gray_off += h * w
+        full = max(full, ((max(w - 2 * ORB_BORDER, 0) + 1) // 2) * ((max(h - 2 * ORB_BORDER, 0) + 1) // 2))
+    if n * n_features >= 2 ** 31:
+        raise ValueError("extract_batch: too many images x n_features for one submission")
+    src = torch.cat(flat)
+    table_dev = torch.tensor(table, dtype=torch.int64, device=dev)
+    capacity = min(full, _ORB_DEFAULT_CAPACITY)
+    gray, keys, counts = kernels.orb_detect_batched(src, table_dev, gray_off, threshold, capacity)
+    found = counts.cpu().numpy()                                               # the one download
+    if (found > capacity).any():                 # more keypoints than the usual room: once more with room for every one there can be
+        gray, keys, counts = kernels.orb_detect_batched(src, table_dev, gray_off, threshold, full)
+    keys = torch.sort(keys, dim=1).values
+    kps, desc, score, bins = kernels.orb_describe_batched(gray, gray_off, table_dev, keys, counts, n_features, bins_t, rot)
+    kept = np.minimum(found, n_features)
+    if info is not None:
+        info["score"] = [score[i, :kept[i]] for i in range(n)]
+        info["bin"] = [bins[i, :kept[i]] for i in range(n)]
+        info["counts"], info["found"] = [int(v) for v in kept], [int(v) for v in found]
+    return [(kps[i, :kept[i]], desc[i, :kept[i]]) for i in range(n)]
+
+
+def detect_and_describe(img, n_features=500, threshold=20, nbytes=32, pattern=None):
+    """One image through `extract_batch`, numpy in and out: (kps float32 [N, 2] as (x, y), desc uint8 [N, nbytes]) -- what stands
+    for `ORB_create().detectAndCompute` (ransac.py:254-257) under the rule stated at `extract_batch` (not OpenCV's ORB)."""
+    (kps, desc), = extract_batch([img], n_features=n_features, threshold=threshold, nbytes=nbytes, pattern=pattern)
+    return kps.cpu().numpy(), desc.cpu().numpy()
+
+
 def match_descriptors(descA, descB):
     """One pair through `match_batch`'s matcher: descA [Na, nbytes], descB [Nb, nbytes] uint8 (numpy or tensors; "query" and
     "train" side) -> (queryIdx, trainIdx, distance), int32 numpy arrays ordered by (distance, queryIdx): the fields of
@@ -840,8 +984,10 @@ def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blen
     """Panorama pipeline of ransac.py:235-283: matches -> RANSAC homography -> warp + composite.
     `matches=(ptsA, ptsB)` injects precomputed correspondences so the
     GPU path works without OpenCV; `features=(kpsA, descA, kpsB, descB)` (keypoints float32 [N, 2], binary descriptors uint8
-    [N, nbytes], A = trainImg's) injects the extractor's output and matches it on the GPU (`match_descriptors`).  `matches` wins
-    over `features`; with neither, the OpenCV path runs.  Everything else keeps the reference's signature."""
+    [N, nbytes], A = trainImg's) injects the extractor's output and matches it on the GPU (`match_descriptors`);
+    `features="extract"` extracts both images on the GPU first (`extract_batch` with its defaults: the rule stated there, which is
+    not OpenCV's ORB).  `matches` wins over `features`; with neither, the OpenCV path runs.  Everything else keeps the reference's
+    signature."""
     if override != 0:
         import cv2
         status, imgn = cv2.Stitcher_create().stitch([trainImg, queryImg])
@@ -849,7 +995,12 @@ def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blen
     if matches is not None:
         ptsA, ptsB = matches
     elif features is not None:
-        kpsA, descA, kpsB, descB = features
+        if isinstance(features, str):
+            if features != "extract":
+                raise ValueError("stitching: features=%r; 'extract' or (kpsA, descA, kpsB, descB)" % features)
+            (kpsA, descA), (kpsB, descB) = extract_batch([trainImg, queryImg])
+        else:
+            kpsA, descA, kpsB, descB = features
         qi, ti, _ = match_descriptors(descA, descB)
         ptsA, ptsB = _host_rows(kpsA)[qi], _host_rows(kpsB)[ti]
     else:
