@@ -66,8 +66,10 @@ RWH_API const char* rwh_strerror(int code);
  * filter and runs the two IEEE divisions for every pair (the filter only ever decides pairs that clear the threshold
  * by a proven error band, so counts and masks are the same either way); RWH_TUNE_WARP_FRAMES (round 4): frames per block of
  * the multi-frame form of the uint8 RGB bilinear kernel (one homography, batch >= 2: warp_rgb8_fast8m, a lab kernel that shares
- * a patch's coordinate / weight arithmetic between the frames of a batch) -- 0 / 1 = one frame per block (the product kernel),
- * 2..64 = that many.  Results never depend on any of them (tests/test_gpu_parity.py).
+ * a patch's coordinate / weight arithmetic between the frames of a batch) -- 0 = the library's choice (the one-frame kernel, or
+ * its batch form for 24 or more frames of at most 4K), 1 = one frame per block, forced, 2..64 = that many; 102..164 = 100 + that
+ * many with one staging window per block (warp_rgb8_fast8mb).  Results never depend on any of them (tests/test_gpu_parity.py,
+ * tests/test_warp_batch_walk_gpu.py).
  */
 enum { RWH_TUNE_WARP_SHAPE = 0, RWH_TUNE_SCORE_HPW = 1, RWH_TUNE_SCORE_EXACT = 2, RWH_TUNE_WARP_FRAMES = 3 };
 RWH_API int rwh_lab_tune(int knob, int value);

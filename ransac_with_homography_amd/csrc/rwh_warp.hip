@@ -633,9 +633,14 @@ struct FastRequest {
 template <class F> static auto with_shape(int shape, F&& f) {
     return shape == 7 ? f(std::integral_constant<int, 7>{}) : shape == 6 ? f(std::integral_constant<int, 6>{}) : f(std::integral_constant<int, 5>{});
 }
-enum class Frames { One, Wave, Block };   // frames per block: one; several, a staging window per wave (fast8m) or per block (fast8mb)
+// frames per block: one; several, a staging window per wave (fast8m) or per block (fast8mb) -- the two lab kernels; Walk: the batch
+// form of warp_rgb8_fast8, the host's own choice for large batches (launch_fast)
+enum class Frames { One, Wave, Block, Walk };
 
 // The (FastArgs) kernel of one homography.  halves: only shapes 6 and 5 exist (choose_shape).
+// The plan string names the kernel FAMILY (what rwh_warp_plan's callers and the committed plan table key on): the batch form is the
+// instantiation warp_rgb8_fast8<unsigned char, S, true> of the family "rwh::warp_rgb8_fast8<unsigned char, S>" for large
+// one-homography batches, and is reported under that name.
 static Kernel<FastArgs> pick_fast(FastKind kind, bool u8, int channels, int shape, bool halves, Frames frames) {
     if (kind == FastKind::Bilinear4)
         return u8 ? named(warp_rgb8_fast<unsigned char>, "rwh::warp_rgb8_fast<%s>", elem<unsigned char>::name)
@@ -644,6 +649,7 @@ static Kernel<FastArgs> pick_fast(FastKind kind, bool u8, int channels, int shap
         constexpr int S = decltype(lp)::value;
         if (kind == FastKind::Nearest8) return named(warp_rgb8_nn<S>, "rwh::warp_rgb8_nn<%d>", S);
         if (channels == 4) return named(warp_rgba8_fast8<S>, "rwh::warp_rgba8_fast8<%d>", S);
+        if (frames == Frames::Walk) return named(warp_rgb8_fast8<unsigned char, S, true>, "rwh::warp_rgb8_fast8<unsigned char, %d>", S);
         if (frames == Frames::Block) return named(warp_rgb8_fast8mb<S>, "rwh::warp_rgb8_fast8mb<%d>", S);
         if (frames == Frames::Wave) return named(warp_rgb8_fast8m<S>, "rwh::warp_rgb8_fast8m<%d>", S);
         if constexpr (S != 7)
@@ -674,6 +680,11 @@ static int launch_strip(const FastArgs& a, bool u8, const CoefTab* tab, int coun
     else hipLaunchKernelGGL(u8 ? warp_rgb8_strip<unsigned char> : warp_rgb8_strip<float>, sgrid, dim3(256), 0, s, a);
     return check_launch();
 }
+
+// The batch form of warp_rgb8_fast8 (rwh_warp_rgb8.h): where the host chooses it, and its frames per block (2 / 3 / 4 measured on
+// the same box: profiles/warp_batch_walk.txt)
+constexpr int WALK_FRAMES = 3, WALK_MIN_BATCH = 24;
+constexpr long long WALK_MAX_SRC_PIXELS = 3840ll * 2160ll;
 
 // Fast-path launch of the warp `w` describes (RGB u8 source; bilinear with u8 / float32 output, or nearest), as `q` asks for it.
 // Returns RWH_E_UNSUPPORTED when the configuration needs the generic kernel.
@@ -738,13 +749,24 @@ int launch_fast(const WarpArgs& w, const FastRequest& q, hipStream_t s) {
         if (q.comp) return launch(pick_comp(shape), a.cpx, s, a, *q.comp);
         unsigned cpx = a.cpx;
         Frames frames = Frames::One;
-        // one homography, several frames, interior geometry shared by the frames of a block (warp_rgb8_fast8m): uint8 RGB bilinear
-        // whole-patch kernel only.  OFF unless rwh_lab_tune(RWH_TUNE_WARP_FRAMES, n >= 2) asks for n frames per block: the kernel
-        // halves the VALU work per frame (366 -> ~185 instructions per wave and frame) and is bit-identical, but same-box A/B
-        // (profiles/r04_lab_notes.txt) gives +3 % on 4K x 32, +2 % on 1080p x 512 and -3 % on 8K x 8 at its best setting (3-4
-        // frames): this warp is bound by the memory system's throughput on its access pattern, not by its arithmetic.
-        if (plain && !halves && u8 && batch >= 2 && g_force_warp_frames >= 2) {
-            const int want = g_force_warp_frames % 100;
+        // One homography, several frames: a block can walk its tile through consecutive frames and share the interior geometry
+        // (coordinates, footprint, lane map, tap weights, slab addresses: half of a staged wave's VALU work) between them --
+        // uint8 RGB bilinear whole-patch kernels only, bit-identical to the one-frame kernel.
+        //   * The host's own choice (knob 0) is the batch form warp_rgb8_fast8<unsigned char, S, true> -- one staging window per block,
+        //     WALK_FRAMES frames per block -- inside the region where same-box A/B measured a win (profiles/r04_lab_notes.txt
+        //     sections 6 and 15, profiles/warp_batch_walk.txt): WALK_MIN_BATCH frames or more of at most WALK_MAX_SRC_PIXELS each.
+        //     Below that a block that is several frames long lengthens the launch's tail (4K x 8: -10 %), and on 8K frames the
+        //     block window loses to the waves' own (-10 %).  Not for 32 x 16 patches: the host picks them for rotations beyond
+        //     ~6 degrees, where a tile's footprint is taller than the block window and every block would fall back to the
+        //     one-frame body frame by frame (-5 %, section 6).  Not for shards of fewer than 16 rows (less than one tile row).
+        //   * rwh_lab_tune(RWH_TUNE_WARP_FRAMES, n): 1 forces the one-frame kernel (the reference of the batch form's tests and
+        //     A/B runs); 2..64 the lab kernel warp_rgb8_fast8m (a window per wave), 102..164 warp_rgb8_fast8mb (a window per
+        //     block), n % 100 frames per block, for any batch of 2 or more.
+        // When the multi-frame grid fails its guards the launch falls back to the one-frame kernel.
+        const bool walk = g_force_warp_frames == 0 && batch >= WALK_MIN_BATCH && (long long)w.src_h * w.src_w <= WALK_MAX_SRC_PIXELS &&
+                          shape >= 6 && w.rows >= 16;
+        if (plain && !halves && u8 && batch >= 2 && (walk || g_force_warp_frames >= 2)) {
+            const int want = walk ? WALK_FRAMES : g_force_warp_frames % 100;
             const int F = want < batch ? want : batch;
             const unsigned long long ntiles = (unsigned long long)tiles_x * tiles_y, groups = ((unsigned)batch + F - 1) / F;
             const unsigned long long mnb = ntiles * groups;
@@ -753,7 +775,7 @@ int launch_fast(const WarpArgs& w, const FastRequest& q, hipStream_t s) {
                 a.mf_frames = F; a.mf_batch = batch; a.ntiles = (unsigned)ntiles; a.ntiles_magic = magic;
                 a.mf_nblocks = (unsigned)mnb; a.mf_cpx = (a.mf_nblocks + 7u) / 8u;
                 cpx = a.mf_cpx;
-                frames = g_force_warp_frames >= 100 ? Frames::Block : Frames::Wave;      // 100 + n: one staging window per block
+                frames = walk ? Frames::Walk : g_force_warp_frames >= 100 ? Frames::Block : Frames::Wave;      // 100 + n: one staging window per block
             }
         }
         const Kernel<FastArgs> k = q.custom ? Kernel<FastArgs>{q.custom, "(custom)"} : pick_fast(q.kind, u8, q.channels, shape, halves, frames);

@@ -27,8 +27,12 @@
 //   * u8 output: v_cvt_pk_u8_f32 converts + packs a byte per instruction; it rounds to nearest, so the
 //     accumulator starts at -0.5 + 2^-15: exact integers (weights 0/1) land on themselves, anything else
 //     is floor(v + 3e-5), inside the float32 blend's own noise.
-// Two kernels: warp_rgb8_fast (4 px per lane, 64 x 4 patches, fixed 9 x 84-texel slab; outputs narrower than
-// 128 px) and warp_rgb8_fast8 (8 px per lane, three patch shapes, slab capacity as an area; everything else).
+// Kernels: warp_rgb8_fast (4 px per lane, 64 x 4 patches, fixed 9 x 84-texel slab; outputs narrower than 128 px) and
+// warp_rgb8_fast8 (8 px per lane, three patch shapes, a fixed staging window per shape; everything else).  warp_rgb8_fast8 has a
+// batch form, warp_rgb8_fast8<unsigned char, S, true>: for 24 or more frames of at most 4K with one homography a block walks its
+// tile through several consecutive frames, computes the per-patch geometry once and stages ONE window per block.  Its
+// relatives -- by halves (fast8h), per-image tables (_tab), RGBA, the compositor, nearest neighbour, the ragged-edge strip and
+// the two multi-frame lab kernels behind RWH_TUNE_WARP_FRAMES (fast8m, fast8mb) -- are introduced where they are defined.
 // No MFMA: there is no dense contraction on this path.
 #pragma once
 #include "rwh_common.h"
@@ -1240,8 +1244,22 @@ __device__ __forceinline__ void fast8_body(const FastArgs& a, const Coef* tab, c
     }
 }
 
-template <typename DstT, int LOG_PW>
-__global__ __launch_bounds__(256, (f8_waves<DstT, LOG_PW>())) void warp_rgb8_fast8(const FastArgs a) { fast8_body<DstT, LOG_PW>(a, nullptr); }
+// WALK = true (uint8 output): the family's BATCH FORM for large batches with one homography -- a block walks its 128 x 16 tile
+// through FastArgs::mf_frames consecutive frames, ONE staging window per block (fast8mb_body, further down; the host's
+// conditions: launch_fast).  A kernel of its own with its own register budget, on purpose: folded into the one-frame kernel behind
+// a uniform branch it would lift that kernel from 60 VGPRs to the walk's count and cost the one-frame path (8K frames, small
+// batches, one homography per image) its 8 resident waves per SIMD.
+constexpr int F8_WALK_WAVES = 4;
+template <int LOG_PW> __device__ __forceinline__ void fast8mb_body(const FastArgs& a);
+template <typename DstT, int LOG_PW, bool WALK = false>
+__global__ __launch_bounds__(256, (WALK ? F8_WALK_WAVES : f8_waves<DstT, LOG_PW>())) void warp_rgb8_fast8(const FastArgs a) {
+    if constexpr (WALK) {
+        static_assert(sizeof(DstT) == 1, "the batch form is uint8 in, uint8 out");
+        fast8mb_body<LOG_PW>(a);
+    } else {
+        fast8_body<DstT, LOG_PW>(a, nullptr);
+    }
+}
 // minification (see HALVES above): the same kernel, windows per half patch
 // (round 4, both halves' staging loads in flight at once: 86 VGPRs for 64 x 8 patches -> 5 waves per SIMD, 102 for 32 x 16 -> 4; round 3's
 //  one-half-at-a-time form ran 6 with two exposed load latencies per wave)
@@ -1591,7 +1609,8 @@ __device__ __forceinline__ void fast8m_body(const FastArgs& a) {
     }
 #endif
 }
-// ---- the same with ONE staging window per BLOCK (lab kernel, rwh_lab_tune(RWH_TUNE_WARP_FRAMES, 100 + n)) ---------------------
+// ---- the same with ONE staging window per BLOCK: the body of the batch form warp_rgb8_fast8<unsigned char, S, true>, and of the
+// lab kernel warp_rgb8_fast8mb (rwh_lab_tune(RWH_TUNE_WARP_FRAMES, 100 + n): any batch, any frames per block) -------------------
 // tools/pattern_probe.hip (the warp's memory patterns without its arithmetic, 32 x 4K frames): loads of four wave-private
 // windows + the 96-byte-segment stores 0.3147 ms -- a plain copy of the same bytes: 0.3022 --; ONE window per 128 x 16 tile
 // (132 x 18 texels for 2048 pixels instead of 4 x 66 x 10) + the same stores 0.2793 ms.  The halo is what the load path pays for.
