@@ -2341,13 +2341,7 @@ def test_native_and_python_run_drivers_agree(gpu, matches):
 
 
 # ---- K2i soundness: [lo, hi] against the reference's float32 arithmetic at sampled points of the perturbation box --------------
-def _k2i_box(h, illcond, C, delta0, delta1):
-    """The perturbation box of rwh_score_interval (include/rwh.h), plainly in float64: entry i may move by delta x max(|h_i|, its
-    natural scale) -- s, s, s C / s, s, s C / s / C, s / C, s, with s the largest scale-free entry and C = coord_scale."""
-    a = np.abs(np.asarray(h, np.float64))
-    s = max(a[0], a[1], a[3], a[4], a[8], max(a[2], a[5]) / C, max(a[6], a[7]) * C)
-    nat = np.array([s, s, s * C, s, s, s * C, s / C, s / C, s])
-    return (delta1 if illcond else delta0) * np.maximum(a, nat)
+from k1_cases import k2i_box as _k2i_box      # the box has one statement: tests/k1_cases.py
 
 
 def _box_points(h, D, rng, n_interior=200):
