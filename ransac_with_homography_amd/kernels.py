@@ -449,7 +449,7 @@ ORB_BORDER, ORB_BINS, ORB_TEST_RADIUS = _lib.RWH_ORB_BORDER, _lib.RWH_ORB_BINS, 
 ORB_TILE_W, ORB_TILE_H = _lib.RWH_ORB_TILE_W, _lib.RWH_ORB_TILE_H
 
 
-def orb_detect_batched(images, table, gray_bytes, threshold, capacity, out_keys=None):
+def orb_detect_batched(images, table, gray_bytes, threshold, capacity, out_keys=None, out_gray=None):
     """FAST-9 corners with non-maximum suppression of a batch of images in one library call (rwh_orb_detect_batched; the rule,
     and the caveat that this is not OpenCV's ORB, in include/rwh.h).
 
@@ -458,7 +458,7 @@ def orb_detect_batched(images, table, gray_bytes, threshold, capacity, out_keys=
     the GPU: the gray planes, per image its keypoints as keys (255 - S) << 32 | y << 16 | x in no particular order (unused entries
     0x7F7F7F7F7F7F7F7F, which sort last), and the number of keypoints found.  counts[i] > capacity: only
     `capacity` of them were stored (overflow; call again with more room).  out_keys: an int64 [n, capacity] tensor to fill instead
-    of a new one."""
+    of a new one; out_gray: likewise a uint8 [>= gray_bytes] tensor for the gray planes (bytes outside every plane are not written)."""
     lib = _lib.load()
     _dev_check(images, table)
     if not (images.dtype == torch.uint8 and images.dim() == 1 and table.dtype == torch.int64 and table.dim() == 2 and
@@ -466,7 +466,10 @@ def orb_detect_batched(images, table, gray_bytes, threshold, capacity, out_keys=
         raise ValueError("orb_detect_batched: images uint8 [bytes] and table int64 [n, 5], got %s %s and %s %s"
                          % (images.dtype, tuple(images.shape), table.dtype, tuple(table.shape)))
     n = table.shape[0]
-    gray = torch.empty((max(int(gray_bytes), 1),), dtype=torch.uint8, device=images.device)
+    gray = out_gray if out_gray is not None else torch.empty((max(int(gray_bytes), 1),), dtype=torch.uint8, device=images.device)
+    _dev_check(gray)
+    if gray.dtype != torch.uint8 or gray.dim() != 1 or gray.shape[0] < max(int(gray_bytes), 1):
+        raise ValueError("orb_detect_batched: out_gray must be uint8 [>= %d]" % max(int(gray_bytes), 1))
     keys = out_keys if out_keys is not None else torch.empty((n, int(capacity)), dtype=torch.int64, device=images.device)
     _dev_check(keys)
     if keys.dtype != torch.int64 or tuple(keys.shape) != (n, int(capacity)):

@@ -182,3 +182,140 @@ def cpu_cases():
              ("caller's pattern", rgb, dict(nbytes=4, pattern=caller_pattern(4))), ("foto crop", crop, {})]
     cases += [("nbytes %d" % nb, rgb, dict(nbytes=nb)) for nb in (1, 61, 64)]
     return cases
+
+
+# ---- the edge cases (test_orb_edges_cpu.py, test_orb_edges_gpu.py): built for branches that texture reaches only by chance ----
+CELL = 33                                    # the smallest image with a legal centre, (16, 16): cells of a mosaic are that size
+
+
+def _arc_cell(background, start, length, value):
+    """A 33 x 33 cell of `background` whose centre's circle pixels start .. start + length - 1 (modulo 16) hold `value`."""
+    cell = np.full((CELL, CELL), background, dtype=np.uint8)
+    for j in range(length):
+        dx, dy = CIRCLE[(start + j) % 16]
+        cell[16 + dy, 16 + dx] = value
+    return cell
+
+
+def arc_mosaic(threshold):
+    """(gray image of 8 x 12 cells = 264 x 396, must, must_not): for each polarity (brighter, darker) and each of the 16 arc starts
+    three cells -- exactly 9 consecutive circle pixels at background +- (threshold + 1): the centre is a keypoint of score
+    threshold + 1; the same at +- threshold: score == threshold, none; only 8 consecutive pixels at the largest difference a byte
+    holds: no arc of 9, none.  `must` lists (x, y, score) of the centres that are keypoints, `must_not` (x, y) of those that are
+    not.  The brighter arcs sit in the upper four cell rows on a background of min(128, 254 - threshold), the darker ones in the
+    lower four on max(128, threshold + 1): one flat 128 up to threshold 126; at threshold 254, 255 on 0 above 0 on 255."""
+    t = int(threshold)
+    assert 1 <= t <= 254
+    rows, cols = 8, 12
+    img = np.zeros((rows * CELL, cols * CELL), dtype=np.uint8)
+    must, must_not = [], []
+    n = 0
+    for sign, background in ((1, min(128, 254 - t)), (-1, max(128, t + 1))):
+        for start in range(16):
+            for kind in range(3):
+                value = background + sign * (t + 1) if kind == 0 else background + sign * t if kind == 1 else (255 if sign > 0 else 0)
+                r, c = divmod(n, cols)
+                img[r * CELL:(r + 1) * CELL, c * CELL:(c + 1) * CELL] = _arc_cell(background, start, 8 if kind == 2 else 9, value)
+                centre = (c * CELL + 16, r * CELL + 16)
+                if kind == 0:
+                    must.append(centre + (t + 1,))
+                else:
+                    must_not.append(centre)
+                n += 1
+    assert n == rows * cols == 96
+    return img, must, must_not
+
+
+def bin_wheel():
+    """(gray 165 x 198, centres): 5 x 6 cells, cell k a dot of 255 at its centre with one satellite pixel of 100 at radius 10 in
+    direction 12 k degrees (y downwards) -- moment vector 100 (dx, dy), within 3 degrees of the middle of sector k.  The 30 centres
+    are the 30 strongest keypoints, in cell order: bins 0, 1, ..., 29."""
+    rows, cols = 5, 6
+    img = np.zeros((rows * CELL, cols * CELL), dtype=np.uint8)
+    centres = []
+    for k in range(BINS):
+        r, c = divmod(k, cols)
+        x, y = c * CELL + 16, r * CELL + 16
+        a = np.deg2rad(12.0 * k)
+        img[y, x] = 255
+        img[y + int(np.rint(10 * np.sin(a))), x + int(np.rint(10 * np.cos(a)))] = 100
+        centres.append((x, y))
+    return img, centres
+
+
+WIDE_W = 65536
+_wide = {}
+
+
+def wide_image():
+    """(gray 33 x 65536, strong, weak), read-only and built once: noise of 0 .. 10 under dots of 250 at x = 16 and x = 65519 -- the
+    first and the last legal column, row 16 being the only legal row -- and, astride the tile seams at x = 64, 32768 and 65472, a
+    dot of 250 on one side with a dot of 200 as its neighbour on the other: the weaker one is suppressed through the halo.
+    x = 65519 and 65472 need all 16 bits of a key's field."""
+    if not _wide:
+        img = np.random.RandomState(77).randint(0, 11, (CELL, WIDE_W)).astype(np.uint8)
+        strong = [(16, 16), (WIDE_W - 1 - BORDER, 16), (63, 16), (32767, 16), (65472, 16)]
+        weak = [(64, 16), (32768, 16), (65471, 16)]
+        for x, y in strong:
+            img[y, x] = 250
+        for x, y in weak:
+            img[y, x] = 200
+        img.flags.writeable = False
+        _wide["v"] = (img, strong, weak)
+    return _wide["v"]
+
+
+def tall_image():
+    """The transpose of `wide_image`, 65536 x 33: the same dots at (16, y), y up to 65519, the seams between tile rows."""
+    img, strong, weak = wide_image()
+    return np.ascontiguousarray(img.T), [(y, x) for x, y in strong], [(y, x) for x, y in weak]
+
+
+def narrow(seed):
+    """One 33 x 65 image -- 2 x 3 tiles, legal centres (16 .. 48, 16): gray, RGB or RGBA by seed % 3; seeds 0 .. 2 are random texture,
+    the others noise of 0 .. 10 under one to four planted dots on the legal row, every third of them under a stronger dot in the
+    row above (no legal centre, but it suppresses)."""
+    c = (1, 3, 4)[seed % 3]
+    if seed < 3:
+        return random_image(CELL, 65, 100 + seed, channels=c)
+    rng = np.random.RandomState(1000 + seed)
+    plane = rng.randint(0, 11, (CELL, 65))
+    for j, col in enumerate(rng.permutation(9)[:1 + seed % 4]):
+        x, v = 16 + 4 * int(col), 60 + int(rng.randint(0, 160))
+        plane[16, x] = v
+        if (seed + j) % 3 == 0:
+            plane[15, x] = v + 30
+    if c == 1:
+        return plane.astype(np.uint8)
+    img = np.clip(plane[:, :, None] + rng.randint(-5, 6, (CELL, 65, c)), 0, 255)
+    if c == 4:
+        img[:, :, 3] = rng.randint(0, 256, (CELL, 65))
+    return img.astype(np.uint8)
+
+
+def strip(w, c, seed):
+    """1 x w random uint8 with c channels: too flat for a keypoint, but its gray plane is an output and its tiles are work."""
+    return random_image(1, w, seed, channels=c)
+
+
+def numbered(i):
+    """Image i of a long batch: gray, 33 .. 40 x 33 .. 48, one to three dots whose position and value are functions of i -- a batch
+    whose per-image tile counts were summed in the wrong order shows as wrong keypoints."""
+    h, w = CELL + i % 8, CELL + (5 * i) % 16
+    pts = [(16 + (3 * i + 5 * j) % (w - 32), 16 + (i + 3 * j) % (h - 32), 60 + (7 * i + 31 * j) % 190) for j in range(1 + i % 3)]
+    return dots(h, w, pts)
+
+
+def key_set(img, threshold=20):
+    """The keys (255 - S) << 32 | y << 16 | x of rule 3 for one image, as a set of ints."""
+    x, y, s = keypoints(scores(gray(img)), threshold)
+    return set(((255 - s.astype(np.int64)) << 32 | y.astype(np.int64) << 16 | x.astype(np.int64)).tolist())
+
+
+def edge_cases():
+    """(name, image, kwargs) of the edge cases that hold keypoints: the CPU module runs each through the host twin and the restatement."""
+    cases = [("arcs at threshold 20", arc_mosaic(20)[0], dict(threshold=20)), ("arcs at threshold 254", arc_mosaic(254)[0], dict(threshold=254)),
+             ("bin wheel", bin_wheel()[0], {}), ("wide", wide_image()[0], {}), ("tall", tall_image()[0], {})]
+    cases += [("narrow %d" % s, narrow(s), {}) for s in range(12)]
+    cases += [("strip %d x %d" % (w, c), strip(w, c, 40 + c), {}) for w, c in ((4097, 1), (4097, 3), (65, 4))]
+    return cases
