@@ -397,7 +397,8 @@ RWH_API int rwh_host_match_hamming(const uint8_t* desc_a, int na, const uint8_t*
  * bins and a steered BRIEF descriptor -- the stage in front of rwh_match_hamming_batched.  Stands where the reference calls
  *   cv2.cvtColor(img, cv2.COLOR_RGB2GRAY); cv2.ORB_create().detectAndCompute(gray, None)      ransac.py:252-257
  * PROVENANCE AND CAVEAT.  The rule below is taken from the ORB paper (Rublee, Rabaud, Konolige, Bradski 2011: FAST-9, intensity
- * centroid, BRIEF steered in 12-degree steps, 5 x 5 box tests), on ONE scale.  It is NOT OpenCV's ORB: no scale pyramid, no Harris
+ * centroid, BRIEF steered in 12-degree steps, 5 x 5 box tests), on ONE scale (rules 1 - 5) or on the levels of a scale pyramid
+ * (rules 6 - 8, below the entry points of the one-scale rule).  It is NOT OpenCV's ORB: not its pyramid's resampling, no Harris
  * ranking, no learned test pattern as a default, no sub-pixel refinement.  OpenCV is not a dependency of this project and was not
  * available where this was written: parity with OpenCV's ORB is NEITHER CLAIMED NOR VERIFIED.  The code is held to the rule as
  * stated (tests/orb_cases.py restates it in numpy); every quantity is an integer, so results are exact, do not depend on the order
@@ -453,6 +454,53 @@ RWH_API int rwh_host_match_hamming(const uint8_t* desc_a, int na, const uint8_t*
  *   bin n_features int32; *out_count = the number of keypoints written (<= n_features), *out_found (may be NULL) = the number found
  *   before the cut.  RWH_E_INVALID: NULL pointer, h or w outside 1 .. 65536, n_features < 0, threshold outside 0 .. 254, a pattern
  *   coordinate outside +-RWH_ORB_TEST_RADIUS; RWH_E_UNSUPPORTED: c not 1, 3 or 4, nbytes outside 1 .. RWH_MATCH_MAX_BYTES.
+ *
+ * THE SCALE PYRAMID (ORB paper, section 6.1: the rule above on every level of a pyramid), rules 6 - 8.  With n_levels == 1 they
+ * reduce to rules 1 - 5: the result is that of the one-scale entry points bit for bit.  Still not OpenCV's ORB; no parity claimed.
+ *   6. Levels.  The caller passes scales: int32 [n_levels] in Q8, scales[0] == RWH_ORB_SCALE_ONE, strictly increasing, every entry
+ *      <= RWH_ORB_SCALE_MAX, 1 <= n_levels <= RWH_ORB_LEVELS_MAX.  With s = scales[l], level l of an h x w image has
+ *        w_l = (256 w + s / 2) / s  columns and  h_l = (256 h + s / 2) / s  rows      (floor divisions);
+ *      a level with w_l == 0 or h_l == 0 has no pixels.  Level 0 is the gray plane of rule 1.  For l >= 1, pixel (X, Y) of level l is
+ *      the exact area average of level 0 over [X s, (X + 1) s) x [Y s, (Y + 1) s), source pixel j covering [256 j, 256 (j + 1)):
+ *      wx_j = the length of the overlap on x, an integer in 0 .. 256, wy_i likewise on y; a source index beyond the last column or row
+ *      reads the last one (the overshoot is at most half a footprint);
+ *        g_l(X, Y) = (sum_i sum_j wy_i wx_j g(j, i) + s^2 / 2) / s^2                   (floor division).
+ *      Every sum is below 2^31 (s^2 255 <= 1024^2 255).  No intermediate is rounded, so a SEPARABLE evaluation -- the row sums
+ *      sum_j wx_j g(j, i) first, then their column sum with wy_i, one rounding at the end -- gives the same bits; the device kernel
+ *      uses that, the host twin evaluates the double sum as written.  Every level is made from level 0, never from the level above:
+ *      the levels have no order between them and one launch makes all of them for the whole batch.
+ *   7. Per level.  Rules 2 - 5 apply to each level as if it were an image of h_l x w_l (the border of RWH_ORB_BORDER holds in level
+ *      pixels: a level with a side below 33 has no keypoints).  The caller passes quotas: int32 [n_levels], each >= 0; the first
+ *      quotas[l] keypoints of level l in rule 3's order are kept.  A shortfall on one level is not handed to another level.
+ *   8. Merge.  An image's keypoints are its levels' keypoints in level order, rule 3's order inside a level.  A keypoint (x, y) of
+ *      level l is reported at level-0 coordinates, the centre of its footprint: the float32 nearest to ((2 x + 1) s - 256) / 512, and
+ *      likewise for y (on level 0 that is x itself; the numerator is an integer below 2^27, its conversion to float32 rounds to
+ *      nearest and the division by 512 is exact).  Alongside go level (int32) and size = 31 s / 256 (float32, exact).
+ * rwh_orb_pyramid_bytes: the bytes of the planes of levels 1 .. n_levels - 1 of one h x w image, sum of h_l w_l (0 for n_levels ==
+ *   1); RWH_E_INVALID for a bad scales table (HOST pointer) or h, w outside 1 .. 65536.
+ * rwh_orb_pyramid_batched: rule 6 for n_images images in one submission.  d_images (images_bytes in all) holds the images in its
+ *   head, [0, planes_offset), and receives the level planes in its tail, [planes_offset, images_bytes): input and output are
+ *   disjoint regions of one buffer, so that ONE rwh_orb_detect_batched call (with a d_gray of its own) takes all of them as rows of
+ *   its table.  d_table: n_images x n_levels rows of 5 int64 on the device in the layout of rwh_orb_detect_batched, row i n_levels +
+ *   l = level l of image i: row i n_levels is the image itself (offset, gray offset, h, w, c), row i n_levels + l, l >= 1, is (offset
+ *   of the plane, gray offset, h_l, w_l, 1).  The gray offsets are not read here.  A level-0 row that does not describe an image
+ *   inside [0, planes_offset) (as for rwh_orb_detect_batched) leaves every level of that image unwritten; a level row whose (h, w,
+ *   c) is not (h_l, w_l, 1) of its image, or whose plane does not lie inside [planes_offset, images_bytes), is not written (a level
+ *   without pixels is any row that fails this, e.g. all zeros).  Nothing else of d_images is written.  Rule 1 is applied on read,
+ *   so level 0 needs no gray pass first.  scales: HOST pointer (the 16 ints travel as a kernel argument).
+ *   d_workspace: workspace_bytes >= rwh_orb_workspace_bytes(n_images n_levels), 8-byte aligned.
+ *   Work: one block of 256 lanes per tile of RWH_ORB_PYR_TILE_W x RWH_ORB_PYR_TILE_H output pixels over (image, level), the list
+ *   built on the device as for the detector; the source window (at most 258 x 66 at s = 1024) is staged as gray bytes in LDS, the
+ *   row sums go to a second LDS plane, a lane sums four adjacent columns and stores them as one word where the address is aligned.
+ *   Two launches (none for n_levels == 1), whatever n_images; the whole pyramid extractor is then: pyramid (2 launches), detect (2
+ *   launches, 2 memsets), the caller's sort, describe (1 launch).
+ *   RWH_E_INVALID (before any device is touched): NULL pointer, n_images <= 0, a bad scales table, planes_offset outside 0 ..
+ *   images_bytes, n_images n_levels >= 2^31, a workspace that is too small or misaligned.
+ * rwh_host_orb_pyramid: rule 6 on the HOST for one image: planes (planes_bytes >= rwh_orb_pyramid_bytes) receives levels 1 ..
+ *   n_levels - 1, concatenated in level order.  RWH_E_INVALID / RWH_E_UNSUPPORTED as rwh_host_orb_extract, and for a bad table.
+ * rwh_host_orb_extract_pyramid: rules 1 - 8 on the HOST for one image.  kps (x, y at level-0 coordinates), desc, score, bin, level
+ *   and size have room for sum(quotas) keypoints; *out_count = the number written; out_found (may be NULL): int32 [n_levels], the
+ *   keypoints found on each level before its quota.  RWH_E_INVALID also for a negative quota or sum(quotas) >= 2^31.
  */
 #define RWH_ORB_BORDER 16
 #define RWH_ORB_BINS 30
@@ -461,6 +509,11 @@ RWH_API int rwh_host_match_hamming(const uint8_t* desc_a, int na, const uint8_t*
 #define RWH_ORB_TILE_W 64
 #define RWH_ORB_TILE_H 16
 #define RWH_ORB_KEY_NONE 0x7F7F7F7F7F7F7F7Full
+#define RWH_ORB_SCALE_ONE 256
+#define RWH_ORB_SCALE_MAX 1024
+#define RWH_ORB_LEVELS_MAX 16
+#define RWH_ORB_PYR_TILE_W 64
+#define RWH_ORB_PYR_TILE_H 16
 RWH_API int64_t rwh_orb_workspace_bytes(int n_images);
 RWH_API int rwh_orb_detect_batched(const uint8_t* d_images, int64_t images_bytes, const int64_t* d_table, int n_images, int threshold,
                            uint8_t* d_gray, int64_t gray_bytes, uint64_t* d_keys, int capacity, int32_t* d_counts,
@@ -472,6 +525,15 @@ RWH_API int rwh_orb_describe_batched(const uint8_t* d_gray, int64_t gray_bytes, 
 RWH_API int rwh_host_orb_extract(const uint8_t* img, int h, int w, int c, int threshold, int n_features, const int32_t* bin_table,
                          const int8_t* pattern, int nbytes, float* kps, uint8_t* desc, int32_t* score, int32_t* bin,
                          int32_t* out_count, int32_t* out_found);
+RWH_API int64_t rwh_orb_pyramid_bytes(int h, int w, const int32_t* scales, int n_levels);
+RWH_API int rwh_orb_pyramid_batched(uint8_t* d_images, int64_t images_bytes, int64_t planes_offset, const int64_t* d_table, int n_images,
+                            const int32_t* scales, int n_levels, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_orb_pyramid(const uint8_t* img, int h, int w, int c, const int32_t* scales, int n_levels, uint8_t* planes,
+                         int64_t planes_bytes);
+RWH_API int rwh_host_orb_extract_pyramid(const uint8_t* img, int h, int w, int c, int threshold, const int32_t* scales,
+                                 const int32_t* quotas, int n_levels, const int32_t* bin_table, const int8_t* pattern, int nbytes,
+                                 float* kps, uint8_t* desc, int32_t* score, int32_t* bin, int32_t* level, float* size,
+                                 int32_t* out_count, int32_t* out_found);
 
 /*
  * HOST helper of the settle step (no device work, no stream): the reference's own 4-point solve for n samples,

@@ -29,6 +29,8 @@ RWH_MATCH_TILE_TRAIN, RWH_MATCH_CHUNK_QUERY, RWH_MATCH_SEG_QUERY = 256, 64, 256 
 # the extractor (include/rwh.h): border of a keypoint's centre, orientation bins, radius of the moment patch and of the test points,
 # the detector's tile
 RWH_ORB_BORDER, RWH_ORB_BINS, RWH_ORB_PATCH_RADIUS, RWH_ORB_TEST_RADIUS, RWH_ORB_TILE_W, RWH_ORB_TILE_H = 16, 30, 15, 13, 64, 16
+# the pyramid (rules 6 - 8): scales are Q8, 256 .. 1024, at most 16 levels; the pyramid kernel's output tile
+RWH_ORB_SCALE_ONE, RWH_ORB_SCALE_MAX, RWH_ORB_LEVELS_MAX, RWH_ORB_PYR_TILE_W, RWH_ORB_PYR_TILE_H = 256, 1024, 16, 64, 16
 RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRAMES = 0, 1, 2, 3
 
 # every symbol include/rwh.h declares (tests check the library exports them all)
@@ -37,7 +39,8 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_host_dlt4_svd", "rwh_ransac_run", "rwh_ransac_run_layout", "rwh_warp_index_check", "rwh_score_count_inv", "rwh_host_inv3", "rwh_stitch_panorama_rows",
            "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex", "rwh_settle_decide", "rwh_refit_batched", "rwh_host_refit",
            "rwh_match_workspace_bytes", "rwh_match_hamming_batched", "rwh_host_match_hamming",
-           "rwh_orb_workspace_bytes", "rwh_orb_detect_batched", "rwh_orb_describe_batched", "rwh_host_orb_extract")
+           "rwh_orb_workspace_bytes", "rwh_orb_detect_batched", "rwh_orb_describe_batched", "rwh_host_orb_extract",
+           "rwh_orb_pyramid_bytes", "rwh_orb_pyramid_batched", "rwh_host_orb_pyramid", "rwh_host_orb_extract_pyramid")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -137,6 +140,14 @@ def _bind(lib):
     lib.rwh_orb_describe_batched.argtypes = [vp, i64, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.rwh_host_orb_extract.restype = i32
     lib.rwh_host_orb_extract.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.rwh_orb_pyramid_bytes.restype = i64
+    lib.rwh_orb_pyramid_bytes.argtypes = [i32, i32, vp, i32]
+    lib.rwh_orb_pyramid_batched.restype = i32
+    lib.rwh_orb_pyramid_batched.argtypes = [vp, i64, i64, vp, i32, vp, i32, vp, i64, vp]
+    lib.rwh_host_orb_pyramid.restype = i32
+    lib.rwh_host_orb_pyramid.argtypes = [vp, i32, i32, i32, vp, i32, vp, i64]
+    lib.rwh_host_orb_extract_pyramid.restype = i32
+    lib.rwh_host_orb_extract_pyramid.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     return lib
 
 

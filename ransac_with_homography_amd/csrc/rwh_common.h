@@ -72,6 +72,17 @@ inline int elem_size(int code) {
     return n;
 }
 
+// The extractor's pyramid (include/rwh.h, rule 6): the side of level s (Q8) of an image side n, and the check of a scales table --
+// scales[0] == 256, strictly increasing, <= 1024, 1 .. 16 levels.
+__host__ __device__ __forceinline__ int orb_level_side(int n, int s) { return (int)((256u * (unsigned)n + (unsigned)s / 2u) / (unsigned)s); }
+
+inline bool orb_scales_ok(const int32_t* scales, int n_levels) {
+    if (!scales || n_levels < 1 || n_levels > RWH_ORB_LEVELS_MAX || scales[0] != RWH_ORB_SCALE_ONE) return false;
+    for (int l = 1; l < n_levels; ++l)
+        if (scales[l] <= scales[l - 1] || scales[l] > RWH_ORB_SCALE_MAX) return false;
+    return true;
+}
+
 inline int check_launch() {
     return hipGetLastError() == hipSuccess ? RWH_OK : RWH_E_LAUNCH;
 }

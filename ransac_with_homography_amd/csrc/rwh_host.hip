@@ -14,7 +14,7 @@
 #include <thread>
 #include <unistd.h>
 #include <vector>
-#include "rwh.h"
+#include "rwh_common.h"
 
 namespace {
 typedef long long lint;   // ILP64 Fortran integer (numpy >= 2 bundles scipy-openblas64)
@@ -332,5 +332,82 @@ extern "C" int rwh_host_orb_extract(const uint8_t* img, int h, int w, int c, int
         score[i] = 255 - (int)(keys[i] >> 32); bin[i] = k;
     }
     *out_count = kept;
+    return RWH_OK;
+}
+
+// Rule 6 in plain C++ for one image: the double sum as the header writes it, level by level, pixel by pixel.
+extern "C" int rwh_host_orb_pyramid(const uint8_t* img, int h, int w, int c, const int32_t* scales, int n_levels, uint8_t* planes,
+                                    int64_t planes_bytes) {
+    if (!img || h < 1 || w < 1 || h > 65536 || w > 65536 || !rwh::orb_scales_ok(scales, n_levels)) return RWH_E_INVALID;
+    if (c != 1 && c != 3 && c != 4) return RWH_E_UNSUPPORTED;
+    const int64_t need = rwh_orb_pyramid_bytes(h, w, scales, n_levels);
+    if (need < 0 || planes_bytes < need || (need > 0 && !planes)) return RWH_E_INVALID;
+    if (n_levels == 1) return RWH_OK;
+    const size_t n = (size_t)h * (size_t)w;
+    std::vector<uint8_t> g(n);
+    for (size_t i = 0; i < n; ++i) {                                        // rule 1
+        const uint8_t* q = img + i * (size_t)c;
+        g[i] = c == 1 ? q[0] : (uint8_t)((4899 * q[0] + 9617 * q[1] + 1868 * q[2] + 8192) >> 14);
+    }
+    uint8_t* out = planes;
+    for (int l = 1; l < n_levels; ++l) {
+        const long long s = scales[l];
+        const int hl = rwh::orb_level_side(h, (int)s), wl = rwh::orb_level_side(w, (int)s);
+        for (int Y = 0; Y < hl; ++Y)
+            for (int X = 0; X < wl; ++X) {
+                const long long ax = X * s, bx = ax + s, ay = Y * s, by = ay + s;
+                long long sum = 0;
+                for (long long i = ay / 256; 256 * i < by; ++i) {
+                    const long long wy = std::min(by, 256 * (i + 1)) - std::max(ay, 256 * i);
+                    const uint8_t* row = &g[(size_t)std::min<long long>(i, h - 1) * w];
+                    for (long long j = ax / 256; 256 * j < bx; ++j)
+                        sum += wy * (std::min(bx, 256 * (j + 1)) - std::max(ax, 256 * j)) * row[std::min<long long>(j, w - 1)];
+                }
+                *out++ = (uint8_t)((sum + s * s / 2) / (s * s));
+            }
+    }
+    return RWH_OK;
+}
+
+// Rules 1 - 8 for one image: every level is an image to rwh_host_orb_extract (rule 7), cut at its quota; rule 8 maps and merges.
+extern "C" int rwh_host_orb_extract_pyramid(const uint8_t* img, int h, int w, int c, int threshold, const int32_t* scales,
+                                            const int32_t* quotas, int n_levels, const int32_t* bin_table, const int8_t* pattern, int nbytes,
+                                            float* kps, uint8_t* desc, int32_t* score, int32_t* bin, int32_t* level, float* size,
+                                            int32_t* out_count, int32_t* out_found) {
+    if (!img || !quotas || !out_count || h < 1 || w < 1 || h > 65536 || w > 65536 || !rwh::orb_scales_ok(scales, n_levels)) return RWH_E_INVALID;
+    long long room = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        if (quotas[l] < 0) return RWH_E_INVALID;
+        room += quotas[l];
+    }
+    if (room >= (1ll << 31) || (room > 0 && (!kps || !desc || !score || !bin || !level || !size))) return RWH_E_INVALID;
+    if ((c != 1 && c != 3 && c != 4) || nbytes < 1 || nbytes > RWH_MATCH_MAX_BYTES) return RWH_E_UNSUPPORTED;
+    *out_count = 0;
+    std::vector<uint8_t> planes((size_t)rwh_orb_pyramid_bytes(h, w, scales, n_levels));
+    int st = rwh_host_orb_pyramid(img, h, w, c, scales, n_levels, planes.data(), (int64_t)planes.size());
+    if (st != RWH_OK) return st;
+    const uint8_t* plane = planes.data();
+    long long at = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        const int s = scales[l], hl = rwh::orb_level_side(h, s), wl = rwh::orb_level_side(w, s);
+        int32_t count = 0, found = 0;
+        if (hl >= 1 && wl >= 1) {
+            st = rwh_host_orb_extract(l == 0 ? img : plane, hl, wl, l == 0 ? c : 1, threshold, quotas[l], bin_table, pattern, nbytes,
+                                      kps ? kps + 2 * at : nullptr, desc ? desc + at * nbytes : nullptr, score ? score + at : nullptr,
+                                      bin ? bin + at : nullptr, &count, &found);
+            if (st != RWH_OK) return st;
+        }
+        if (l > 0) plane += (size_t)hl * (size_t)wl;
+        if (out_found) out_found[l] = found;
+        for (long long i = at; i < at + count; ++i) {                       // rule 8
+            const int x = (int)kps[2 * i], y = (int)kps[2 * i + 1];
+            kps[2 * i] = (float)((2 * x + 1) * s - 256) / 512.0f;
+            kps[2 * i + 1] = (float)((2 * y + 1) * s - 256) / 512.0f;
+            level[i] = l;
+            size[i] = (float)(31 * s) / 256.0f;
+        }
+        at += count;
+    }
+    *out_count = (int32_t)at;
     return RWH_OK;
 }

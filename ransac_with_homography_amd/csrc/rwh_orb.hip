@@ -18,6 +18,18 @@
 // are built separably in LDS (31 x 27 row sums, then 27 x 27 boxes: 125 byte / halfword reads per lane instead of 25 per test
 // point); lane l evaluates tests l, l + 64, ... -- two LDS reads each --, a ballot makes a 64-bit word of the descriptor and eight
 // lanes store its bytes.
+//
+// orb_pyramid_kernel (rule 6): one block of 256 lanes per tile of RWH_ORB_PYR_TILE_W x RWH_ORB_PYR_TILE_H = 64 x 16 pixels of a level
+// plane; the tile list runs over (image, level) and is built by orb_pyramid_setup_kernel as orb_setup_kernel builds the detector's:
+// a prefix sum that a fixed grid walks with a stride, all levels of all images in ONE launch.  The source window of the tile -- at
+// most 4 * 64 + 2 = 258 columns x 4 * 16 + 2 = 66 rows at the largest scale, 1024 -- is read once, a wave per row, converted to gray on
+// the way (rule 1) with indices clamped to the last column and row (the edge rule), and staged as bytes: 66 rows at a stride of 260 =
+// 17160 bytes of LDS.  The area average is evaluated separably out of LDS, which rule 6 allows because nothing is rounded before
+// the end: lane X of a wave forms the row sum sum_j wx_j g of its column for one staged row at a time (its at most five weights
+// are per-tile registers), into a plane of 66 x 68 uint32 = 17952 bytes; then a lane takes four adjacent columns of one output row,
+// sums at most five rows of row sums (one 16-byte LDS read each), divides by s^2 -- a 32-bit unsigned division by a per-level
+// constant; no 64-bit arithmetic inside the loops -- and stores the four bytes as one word where the address is a multiple of 4.
+// 35112 bytes of LDS per block in all.  The 16 scales travel by value as a kernel argument.
 #include "rwh_common.h"
 
 #define RWH_ORB_GRID_MAX 16384
@@ -243,7 +255,188 @@ __global__ __launch_bounds__(RWH_WAVE) void orb_describe_kernel(const unsigned c
     }
 }
 
+// ---- rule 6: the levels of the pyramid ----
+constexpr int PYR_TW = RWH_ORB_PYR_TILE_W, PYR_TH = RWH_ORB_PYR_TILE_H;
+constexpr int PYR_MAXQ = RWH_ORB_SCALE_MAX / RWH_ORB_SCALE_ONE;                                   // source pixels per level pixel, per axis: 4
+constexpr int PYR_WW = PYR_MAXQ * PYR_TW + 2, PYR_WH = PYR_MAXQ * PYR_TH + 2;                     // the staged window: 258 x 66
+constexpr int PYR_WS = (PYR_WW + 3) & ~3;                                                         // its row stride: 260
+constexpr int PYR_RS = PYR_TW + 4;                                                                // row stride of the row sums, in words
+constexpr int PYR_TAPS = PYR_MAXQ + 1;                                                            // source pixels a footprint can touch: 5
+static_assert(PYR_TW == RWH_WAVE && PYR_TW * PYR_TH == 4 * 256 && PYR_RS % 4 == 0, "a wave sums one staged row, a lane stores four columns");
+
+struct OrbScales { int s[RWH_ORB_LEVELS_MAX]; };
+struct OrbLevel { long long src, dst; int h, w, c, hl, wl, s; };
+
+// row `row` of the table as level row % n_levels of image row / n_levels: hl = wl = 0 (no pixels to make) for level 0, for a level
+// whose image's row does not describe an image inside [0, planes_offset), and for a row that is not that level's plane inside
+// [planes_offset, images_bytes)
+__device__ __forceinline__ OrbLevel orb_level(const int64_t* __restrict__ table, int row, int n_levels, const OrbScales& sc,
+                                              long long images_bytes, long long planes_offset) {
+    OrbLevel L;
+    L.src = L.dst = 0; L.h = L.w = 1; L.c = 1; L.hl = L.wl = 0; L.s = RWH_ORB_SCALE_ONE;
+    const int l = row % n_levels;
+    if (l == 0) return L;
+    const long long i0 = 5ll * (row - l), i = 5ll * row;
+    const long long src = table[i0], h = table[i0 + 2], w = table[i0 + 3], c = table[i0 + 4];
+    if (!(h >= 1 && w >= 1 && h <= 65536 && w <= 65536 && (c == 1 || c == 3 || c == 4) && src >= 0 && src + h * w * c <= planes_offset)) return L;
+    const int s = sc.s[l];
+    const int hl = orb_level_side((int)h, s), wl = orb_level_side((int)w, s);
+    const long long dst = table[i];
+    if (!(hl >= 1 && wl >= 1 && table[i + 2] == hl && table[i + 3] == wl && table[i + 4] == 1 && dst >= planes_offset &&
+          dst + (long long)hl * wl <= images_bytes))
+        return L;
+    L.src = src; L.dst = dst; L.h = (int)h; L.w = (int)w; L.c = (int)c; L.hl = hl; L.wl = wl; L.s = s;
+    return L;
+}
+
+__device__ __forceinline__ unsigned long long orb_level_tiles(const OrbLevel& L) {
+    return (unsigned long long)((L.wl + PYR_TW - 1) / PYR_TW) * (unsigned long long)((L.hl + PYR_TH - 1) / PYR_TH);
+}
+
+// prefix[r] = output tiles of the table rows before r, prefix[n_rows] = all (one block)
+__global__ __launch_bounds__(256) void orb_pyramid_setup_kernel(const int64_t* __restrict__ table, int n_rows, int n_levels, OrbScales sc,
+                                                                long long images_bytes, long long planes_offset,
+                                                                unsigned long long* __restrict__ prefix) {
+    __shared__ unsigned long long part[256];
+    const int per = (n_rows + 255) / 256;
+    const int i0 = (int)min((long long)n_rows, (long long)threadIdx.x * per), i1 = (int)min((long long)n_rows, (long long)i0 + per);
+    unsigned long long sum = 0;
+    for (int i = i0; i < i1; ++i) sum += orb_level_tiles(orb_level(table, i, n_levels, sc, images_bytes, planes_offset));
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long run = 0;
+        for (int t = 0; t < 256; ++t) { const unsigned long long v = part[t]; part[t] = run; run += v; }
+        prefix[n_rows] = run;
+    }
+    __syncthreads();
+    sum = part[threadIdx.x];
+    for (int i = i0; i < i1; ++i) { prefix[i] = sum; sum += orb_level_tiles(orb_level(table, i, n_levels, sc, images_bytes, planes_offset)); }
+}
+
+// the footprint [a, a + s) of a level pixel on one axis: its first source pixel and the overlap with that one and the next four
+// (0 past the footprint's end), in Q8
+__device__ __forceinline__ int orb_taps(unsigned a, unsigned s, unsigned (&wgt)[PYR_TAPS]) {
+    const unsigned b = a + s, j0 = a >> 8;
+#pragma unroll
+    for (int k = 0; k < PYR_TAPS; ++k) {
+        const unsigned lo = max(a, (j0 + k) << 8), hi = min(b, (j0 + k + 1) << 8);
+        wgt[k] = hi > lo ? hi - lo : 0u;
+    }
+    return (int)j0;
+}
+
+__global__ __launch_bounds__(256) void orb_pyramid_kernel(unsigned char* __restrict__ images, long long images_bytes, long long planes_offset,
+                                                          const int64_t* __restrict__ table, int n_rows, int n_levels, OrbScales sc,
+                                                          const unsigned long long* __restrict__ prefix) {
+    __shared__ unsigned char g[PYR_WH * PYR_WS];
+    __shared__ __attribute__((aligned(16))) unsigned rsum[PYR_WH * PYR_RS];
+    const int tid = threadIdx.x, lane = tid & (RWH_WAVE - 1), wave = tid >> 6;
+    const unsigned long long n_work = prefix[n_rows];
+    for (unsigned long long wk = blockIdx.x; wk < n_work; wk += gridDim.x) {
+        int lo = 0, hi = n_rows;                                    // the row that owns tile wk: the last r with prefix[r] <= wk
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (prefix[mid] <= wk) lo = mid; else hi = mid;
+        }
+        const OrbLevel L = orb_level(table, lo, n_levels, sc, images_bytes, planes_offset);
+        if (L.wl == 0) continue;                                    // uniform over the block; cannot happen for a tile the prefix counted
+        const unsigned tiles_x = (unsigned)((L.wl + PYR_TW - 1) / PYR_TW);
+        const unsigned long long r = wk - prefix[lo];
+        const int X0 = (int)(r % tiles_x) * PYR_TW, Y0 = (int)(r / tiles_x) * PYR_TH;
+        const int Xe = min(X0 + PYR_TW, L.wl), Ye = min(Y0 + PYR_TH, L.hl);
+        const unsigned s = (unsigned)L.s;
+        // the source window of the tile; level sides are below 2^16 and s <= 2^10, so every product is below 2^27
+        const int jb = (int)(((unsigned)X0 * s) >> 8), ib = (int)(((unsigned)Y0 * s) >> 8);
+        const int nw = min((int)(((unsigned)Xe * s - 1u) >> 8) - jb + 1, PYR_WW), nh = min((int)(((unsigned)Ye * s - 1u) >> 8) - ib + 1, PYR_WH);
+        const unsigned char* src = images + L.src;
+        __syncthreads();                                            // the tile before this one has been read by every wave
+        for (int ly = wave; ly < nh; ly += 4) {                     // a wave stages one row at a time
+            const long long row = (long long)min(ib + ly, L.h - 1) * L.w;
+            for (int lx = lane; lx < nw; lx += RWH_WAVE) {
+                const long long px = row + min(jb + lx, L.w - 1);
+                int v;
+                if (L.c == 1) v = src[px];
+                else {
+                    const unsigned char* q = src + px * L.c;
+                    v = (4899 * q[0] + 9617 * q[1] + 1868 * q[2] + 8192) >> 14;
+                }
+                g[ly * PYR_WS + lx] = (unsigned char)v;
+            }
+        }
+        unsigned wgt[PYR_TAPS];
+        {                                                           // lane X: column X0 + X of the level, the same taps for every staged row
+            const int j0 = orb_taps((unsigned)(X0 + lane) * s, s, wgt) - jb;
+            int at[PYR_TAPS];
+#pragma unroll
+            for (int k = 0; k < PYR_TAPS; ++k) at[k] = min(j0 + k, nw - 1);
+            __syncthreads();
+            if (X0 + lane < Xe)
+                for (int ly = wave; ly < nh; ly += 4) {
+                    const unsigned char* p = &g[ly * PYR_WS];
+                    unsigned sum = 0;
+#pragma unroll
+                    for (int k = 0; k < PYR_TAPS; ++k) sum += wgt[k] * p[at[k]];
+                    rsum[ly * PYR_RS + lane] = sum;
+                }
+        }
+        __syncthreads();
+        const int Y = Y0 + (tid >> 4), X = X0 + 4 * (tid & 15);      // four adjacent columns of one output row
+        if (Y < Ye && X < Xe) {
+            const int i0 = orb_taps((unsigned)Y * s, s, wgt) - ib;
+            unsigned acc[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < PYR_TAPS; ++k) {
+                const uint4 v = *reinterpret_cast<const uint4*>(&rsum[min(i0 + k, nh - 1) * PYR_RS + (X - X0)]);
+                acc[0] += wgt[k] * v.x; acc[1] += wgt[k] * v.y; acc[2] += wgt[k] * v.z; acc[3] += wgt[k] * v.w;
+            }
+            const unsigned s2 = s * s;
+            unsigned o[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = (acc[k] + s2 / 2u) / s2;
+            unsigned char* out = images + L.dst + (long long)Y * L.wl + X;
+            if (X + 3 < Xe && ((uintptr_t)out & 3u) == 0)
+                *reinterpret_cast<uint32_t*>(out) = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
+            else
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (X + k < Xe) out[k] = (unsigned char)o[k];
+        }
+    }
+}
+
 }  // namespace rwh
+
+extern "C" int64_t rwh_orb_pyramid_bytes(int h, int w, const int32_t* scales, int n_levels) {
+    if (!rwh::orb_scales_ok(scales, n_levels) || h < 1 || w < 1 || h > 65536 || w > 65536) return RWH_E_INVALID;
+    int64_t bytes = 0;
+    for (int l = 1; l < n_levels; ++l) bytes += (int64_t)rwh::orb_level_side(h, scales[l]) * rwh::orb_level_side(w, scales[l]);
+    return bytes;
+}
+
+extern "C" int rwh_orb_pyramid_batched(uint8_t* d_images, int64_t images_bytes, int64_t planes_offset, const int64_t* d_table, int n_images,
+                                       const int32_t* scales, int n_levels, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    using namespace rwh;
+    if (!d_images || !d_table || !d_workspace || n_images <= 0 || !orb_scales_ok(scales, n_levels) || planes_offset < 0 ||
+        planes_offset > images_bytes || (long long)n_images * n_levels >= (1ll << 31))
+        return RWH_E_INVALID;
+    const int n_rows = n_images * n_levels;
+    if (workspace_bytes < rwh_orb_workspace_bytes(n_rows) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
+    if (n_levels == 1) return RWH_OK;                               // level 0 is the image: nothing to make
+    OrbScales sc;
+    for (int l = 0; l < RWH_ORB_LEVELS_MAX; ++l) sc.s[l] = l < n_levels ? scales[l] : RWH_ORB_SCALE_MAX;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    unsigned long long* prefix = static_cast<unsigned long long*>(d_workspace);
+    hipLaunchKernelGGL(orb_pyramid_setup_kernel, dim3(1), dim3(256), 0, s, d_table, n_rows, n_levels, sc, (long long)images_bytes,
+                       (long long)planes_offset, prefix);
+    // the planes hold one byte per pixel inside the tail, which bounds the output pixels; a plane adds at most one partial tile per
+    // tile row and column it has -- the grid walks the tile list with a stride, so any size is correct
+    const long long want = (images_bytes - planes_offset) / (PYR_TW * PYR_TH) * 2 + n_rows;
+    const unsigned grid = (unsigned)(want < RWH_ORB_GRID_MAX ? want : RWH_ORB_GRID_MAX);
+    hipLaunchKernelGGL(orb_pyramid_kernel, dim3(grid), dim3(256), 0, s, d_images, (long long)images_bytes, (long long)planes_offset, d_table,
+                       n_rows, n_levels, sc, prefix);
+    return check_launch();
+}
 
 extern "C" int64_t rwh_orb_workspace_bytes(int n_images) {
     if (n_images <= 0) return RWH_E_INVALID;

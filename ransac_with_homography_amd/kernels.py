@@ -482,6 +482,36 @@ def orb_detect_batched(images, table, gray_bytes, threshold, capacity, out_keys=
     return gray, keys, counts
 
 
+def orb_pyramid_batched(images, planes_offset, table, scales):
+    """The level planes of a scale pyramid for a batch of images in one library call (rwh_orb_pyramid_batched; rule 6 of
+    include/rwh.h): every level an exact area average of the image's gray plane, all levels of all images in one launch.
+
+    images: uint8 [bytes] on the GPU, the images' pixels concatenated in [0, planes_offset) and room for the planes behind them;
+    table: int64 [n * n_levels, 5] on the GPU, row i * n_levels + l = level l of image i in the layout of orb_detect_batched --
+    level 0 the image itself, level l >= 1 (byte offset of its plane, gray offset, h_l, w_l, 1); scales: n_levels ints in Q8 on the
+    HOST (256 first, strictly increasing, <= 1024).  The planes are written into `images` in place (nothing else of it is), so
+    that one orb_detect_batched call takes every row; a row that does not fit its image or the tail is not written.  Returns
+    `images`."""
+    lib = _lib.load()
+    _dev_check(images, table)
+    sc = np.ascontiguousarray(np.asarray(scales, dtype=np.int32).reshape(-1))
+    n_levels = int(sc.shape[0])
+    if not (images.dtype == torch.uint8 and images.dim() == 1 and images.is_contiguous() and table.dtype == torch.int64 and table.dim() == 2 and
+            table.shape[1] == 5 and table.is_contiguous() and n_levels >= 1 and table.shape[0] >= n_levels and table.shape[0] % n_levels == 0):
+        raise ValueError("orb_pyramid_batched: images uint8 [bytes] and table int64 [n * %d, 5], got %s %s and %s %s"
+                         % (n_levels, images.dtype, tuple(images.shape), table.dtype, tuple(table.shape)))
+    rows = table.shape[0]
+    ws_bytes = int(lib.rwh_orb_workspace_bytes(rows))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=images.device)
+    status = lib.rwh_orb_pyramid_batched(_ptr(images), images.shape[0], int(planes_offset), _ptr(table), rows // n_levels, sc.ctypes.data, n_levels,
+                                         _ptr(ws), ws_bytes, _lib.stream_ptr())
+    if status == _lib.RWH_E_INVALID:
+        raise ValueError("orb_pyramid_batched: scales %s (Q8: 256 first, strictly increasing, <= 1024, at most 16) or planes_offset %d "
+                         "outside 0 .. %d" % (sc.tolist(), int(planes_offset), images.shape[0]))
+    check(status, "rwh_orb_pyramid_batched")
+    return images
+
+
 def orb_describe_batched(gray, gray_bytes, table, keys, counts, n_features, bin_table, pattern):
     """Orientation bin and steered BRIEF descriptor of the first min(counts[i], n_features) keys of every row of `keys`
     (rwh_orb_describe_batched, include/rwh.h), one wavefront per keypoint.

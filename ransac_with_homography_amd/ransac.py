@@ -814,6 +814,51 @@ def orb_bin_table():
     return np.rint(32768.0 * np.stack([np.cos(a), np.sin(a)], axis=1)).astype(np.int32)
 
 
+ORB_SCALE_ONE, ORB_SCALE_MAX, ORB_LEVELS_MAX = _lib.RWH_ORB_SCALE_ONE, _lib.RWH_ORB_SCALE_MAX, _lib.RWH_ORB_LEVELS_MAX
+
+
+def _check_scales(scales):
+    """Rule 6's table: int32 [n_levels], 1 .. 16 levels, 256 first, strictly increasing, <= 1024."""
+    sc = np.asarray(scales)
+    if sc.dtype.kind not in "iu" or sc.ndim != 1:
+        raise ValueError("orb: scales must be a list of integers in Q8 (256 = the image's own scale), got %s %s" % (sc.dtype, sc.shape))
+    if not 1 <= sc.shape[0] <= ORB_LEVELS_MAX:
+        raise ValueError("orb: %d levels; the pyramid takes 1 .. %d" % (sc.shape[0], ORB_LEVELS_MAX))
+    sc = sc.astype(np.int64)
+    if sc[0] != ORB_SCALE_ONE or (np.diff(sc) <= 0).any() or sc[-1] > ORB_SCALE_MAX:
+        raise ValueError("orb: scales %s; the table starts at %d, increases strictly and stays <= %d" % (sc.tolist(), ORB_SCALE_ONE, ORB_SCALE_MAX))
+    return sc.astype(np.int32)
+
+
+def orb_scales(n_levels=8, scale=1.2):
+    """The scales of a pyramid of n_levels levels (rule 6 of include/rwh.h): int32 [n_levels] in Q8, entry l = rint(256 scale ** l).
+    ValueError where n_levels leaves 1 .. 16 or the table leaves 256 .. 1024 or does not increase strictly (scale 1.2 reaches 8
+    levels: 256 307 369 442 531 637 764 917)."""
+    n_levels = int(n_levels)
+    if not 1 <= n_levels <= ORB_LEVELS_MAX:
+        raise ValueError("orb: %d levels; the pyramid takes 1 .. %d" % (n_levels, ORB_LEVELS_MAX))
+    with np.errstate(over="ignore"):
+        t = np.rint(ORB_SCALE_ONE * np.float64(scale) ** np.arange(n_levels))
+    if not np.isfinite(t).all() or (np.abs(t) > 2 ** 30).any():
+        raise ValueError("orb: scale %r gives a table outside %d .. %d" % (scale, ORB_SCALE_ONE, ORB_SCALE_MAX))
+    return _check_scales(t.astype(np.int64))
+
+
+def orb_level_quotas(n_features, scales):
+    """How many keypoints each level may keep (rule 7): int32 [n_levels], q_l = floor(n_features (1 / s_l) / sum_j (1 / s_j)) in exact
+    rationals, the remainder added to level 0 -- a share that falls geometrically with the level, as OpenCV's does, stated in
+    integers (no parity claimed).  Sums to n_features and never increases with the level."""
+    from fractions import Fraction
+    sc = _check_scales(scales)
+    n_features = int(n_features)
+    if n_features < 0:
+        raise ValueError("orb: n_features must not be negative")
+    total = sum(Fraction(1, int(v)) for v in sc)
+    q = [int(n_features * Fraction(1, int(v)) / total) for v in sc]           # int() of a non-negative Fraction is its floor
+    q[0] += n_features - sum(q)
+    return np.array(q, dtype=np.int32)
+
+
 def default_pattern(nbytes=32):
     """The default BRIEF test pattern: int8 [8 * nbytes, 4], rows (x1, y1, x2, y2).  The recipe: numpy's legacy
     RandomState(ORB_PATTERN_SEED); per test four draws normal(0, 31 / 5) rounded with rint; a test is rejected (and drawn again)
@@ -883,22 +928,34 @@ def _orb_image(img, dev, i):
     return t.to(dev).contiguous().reshape(-1), h, w, c
 
 
-def extract_batch(images, n_features=500, threshold=20, nbytes=32, pattern=None, info=None):
+def extract_batch(images, n_features=500, threshold=20, nbytes=32, pattern=None, info=None, n_levels=1, scale=1.2, scales=None,
+                  quotas=None):
     """Keypoints and binary descriptors of MANY images in one GPU submission: the stage of ransac.py:252-257
     (cvtColor(RGB2GRAY) + ORB_create().detectAndCompute) in front of `match_batch`, by the rule stated in include/rwh.h --
-    FAST-9 corners with 3 x 3 non-maximum suppression on ONE scale, ordered by (score descending, y, x) and cut at n_features;
-    intensity-centroid orientation in 30 bins of 12 degrees; BRIEF steered by the bin, 5 x 5 box tests.  It follows the ORB paper
-    (Rublee et al. 2011), NOT OpenCV's code: no pyramid, no Harris ranking, not OpenCV's learned pattern, no sub-pixel refinement;
-    parity with OpenCV's ORB is neither claimed nor verified.  Everything is an integer: results are exact and a rerun is identical.
+    FAST-9 corners with 3 x 3 non-maximum suppression, ordered by (score descending, y, x) and cut at n_features;
+    intensity-centroid orientation in 30 bins of 12 degrees; BRIEF steered by the bin, 5 x 5 box tests; on ONE scale by default, on
+    the levels of a scale pyramid with n_levels > 1.  It follows the ORB paper (Rublee et al. 2011), NOT OpenCV's code: not its
+    pyramid's resampling, no Harris ranking, not OpenCV's learned pattern, no sub-pixel refinement; parity with OpenCV's ORB is
+    neither claimed nor verified.  Everything is an integer: results are exact and a rerun is identical.
 
     images: list of uint8 numpy arrays or tensors, [h, w, 3] RGB, [h, w, 4] RGBA (alpha ignored) or [h, w] gray; shapes may differ.
     threshold: 0 .. 254; nbytes: 1 .. 64; pattern: an integer [8 * nbytes, 4] table of tests (x1, y1, x2, y2) within radius 13
     (default: `default_pattern(nbytes)`).  Returns a list of (kps float32 [N, 2] as (x, y), desc uint8 [N, nbytes]) device tensors,
     N <= n_features, ready to be paired into `match_batch`'s `features`.  `info`: optional dict, receives "score" and "bin" (lists
-    of int32 device tensors), "counts" (keypoints kept per image) and "found" (before the cut).
+    of int32 device tensors), "counts" (keypoints kept per image) and "found" (before the cut), "level" (int32) and "size"
+    (float32, the patch's side in image pixels: 31 on level 0) as lists of device tensors, and "found_levels" (per image, the
+    keypoints found on each level before its quota; "found" is their sum).
 
-    Three library launches (detect, describe and their setup) around one sort of the keys; the one download is the per-image
-    keypoint counts."""
+    The pyramid (rules 6 - 8 of include/rwh.h; ORB paper, section 6.1).  n_levels: 1 .. 16; level l is the image's gray plane
+    shrunk by scales[l] / 256 -- an exact area average made from level 0 -- and is searched and described as an image of its own.
+    scales: int32 [n_levels] in Q8 (default `orb_scales(n_levels, scale)`: rint(256 scale ** l)); quotas: how many keypoints each
+    level keeps (default `orb_level_quotas(n_features, scales)`; a level's shortfall is not handed to another).  An image's
+    keypoints are its levels' in level order, each at the image's own coordinates: the centre of its footprint,
+    ((2 x + 1) s - 256) / 512.  With n_levels = 1 (the default) this is the one-scale path and its bits.
+
+    One scale: three library launches (detect, describe and their setup) around one sort of the keys.  A pyramid: two more (the
+    level planes of the whole batch and their setup); detect, the sort and describe then run ONCE over n_images * n_levels rows.
+    The one download is the per-row keypoint counts."""
     import torch
     dev = _lib.require_gpu()
     n = len(images)
@@ -909,7 +966,24 @@ def extract_batch(images, n_features=500, threshold=20, nbytes=32, pattern=None,
         raise ValueError("extract_batch: n_features must be positive")
     if not 0 <= threshold <= 254:
         raise ValueError("extract_batch: threshold %d outside 0 .. 254" % threshold)
+    sc = orb_scales(n_levels, scale) if scales is None else _check_scales(scales)
+    levels = int(sc.shape[0])
+    if scales is not None and int(n_levels) not in (1, levels):
+        raise ValueError("extract_batch: n_levels = %d but %d scales" % (int(n_levels), levels))
+    if quotas is None:
+        qt = orb_level_quotas(n_features, sc)
+    else:
+        qt = np.asarray(quotas)
+        if qt.dtype.kind not in "iu" or qt.shape != (levels,) or (qt.astype(np.int64) < 0).any() or (qt.astype(np.int64) >= 2 ** 31).any():
+            raise ValueError("extract_batch: quotas must be %d non-negative integers, one per level" % levels)
+        qt = qt.astype(np.int32)
     pat = default_pattern(nbytes) if pattern is None else _check_pattern(pattern, nbytes)
+    if levels > 1:
+        return _extract_pyramid(images, sc, qt, threshold, pat, info, dev)
+    if quotas is not None:
+        n_features = int(qt[0])
+        if n_features < 1:
+            raise ValueError("extract_batch: the quota of the only level must be positive")
     rot = torch.from_numpy(rotate_pattern(pat)).to(dev)
     bins_t = torch.from_numpy(orb_bin_table()).to(dev)
     flat, table, src_off, gray_off, full = [], [], 0, 0, 1
@@ -936,13 +1010,86 @@ def extract_batch(images, n_features=500, threshold=20, nbytes=32, pattern=None,
         info["score"] = [score[i, :kept[i]] for i in range(n)]
         info["bin"] = [bins[i, :kept[i]] for i in range(n)]
         info["counts"], info["found"] = [int(v) for v in kept], [int(v) for v in found]
+        info["level"] = [torch.zeros((int(kept[i]),), dtype=torch.int32, device=dev) for i in range(n)]
+        info["size"] = [torch.full((int(kept[i]),), float(2 * _lib.RWH_ORB_PATCH_RADIUS + 1), dtype=torch.float32, device=dev) for i in range(n)]
+        info["found_levels"] = [[int(v)] for v in found]
     return [(kps[i, :kept[i]], desc[i, :kept[i]]) for i in range(n)]
 
 
-def detect_and_describe(img, n_features=500, threshold=20, nbytes=32, pattern=None):
+def _orb_level_to_image(xy, s):
+    """Rule 8: pixel coordinates on a level of scale s (Q8) -> float32 coordinates in the image, the centre of the pixel's footprint,
+    ((2 x + 1) s - 256) / 512.  xy: tensor of whole numbers, s: float64 tensor that broadcasts against it.  Every step is exact in
+    float64 (the numerator is an integer below 2^27), so the one rounding is the conversion to float32."""
+    import torch
+    return (((2.0 * xy.to(torch.float64) + 1.0) * s - 256.0) / 512.0).to(torch.float32)
+
+
+def _extract_pyramid(images, sc, qt, threshold, pat, info, dev):
+    """extract_batch with more than one level: rules 6 - 8.  The level planes go behind the images in one buffer and every level is
+    a row of the detector's table, row i * levels + l = level l of image i."""
+    import torch
+    n, levels = len(images), int(sc.shape[0])
+    nf = max(int(qt.max()), 1)
+    if n * levels * nf >= 2 ** 31:
+        raise ValueError("extract_batch: too many images x levels x quota for one submission")
+    rot = torch.from_numpy(rotate_pattern(pat)).to(dev)
+    bins_t = torch.from_numpy(orb_bin_table()).to(dev)
+    flat, shapes, src_off = [], [], 0
+    for i, img in enumerate(images):
+        t, h, w, c = _orb_image(img, dev, i)
+        flat.append(t)
+        shapes.append((src_off, h, w, c))
+        src_off += h * w * c
+    table, plane_off, gray_off, full = [], src_off, 0, 1
+    for off, h, w, c in shapes:
+        full = max(full, ((max(w - 2 * ORB_BORDER, 0) + 1) // 2) * ((max(h - 2 * ORB_BORDER, 0) + 1) // 2))   # level 0 is the largest
+        table.append((off, gray_off, h, w, c))
+        gray_off += h * w
+        for s in sc[1:].tolist():
+            hl, wl = (256 * h + s // 2) // s, (256 * w + s // 2) // s
+            if hl == 0 or wl == 0:
+                table.append((0, 0, 0, 0, 1))                                      # a level without pixels
+                continue
+            table.append((plane_off, gray_off, hl, wl, 1))
+            plane_off += hl * wl
+            gray_off += hl * wl
+    src = torch.cat(flat + [torch.empty((plane_off - src_off,), dtype=torch.uint8, device=dev)])
+    table_dev = torch.tensor(table, dtype=torch.int64, device=dev)
+    kernels.orb_pyramid_batched(src, src_off, table_dev, sc)
+    capacity = min(full, _ORB_DEFAULT_CAPACITY)
+    gray, keys, counts = kernels.orb_detect_batched(src, table_dev, gray_off, threshold, capacity)
+    found = counts.cpu().numpy()                                               # the one download
+    if (found > capacity).any():                 # more keypoints than the usual room: once more with room for every one there can be
+        gray, keys, counts = kernels.orb_detect_batched(src, table_dev, gray_off, threshold, full)
+    keys = torch.sort(keys, dim=1).values
+    quota_rows = np.tile(qt, n)
+    counts = torch.minimum(counts, torch.from_numpy(quota_rows).to(dev))        # rule 7: the describe call keeps min(count, quota) per row
+    kps, desc, score, bins = kernels.orb_describe_batched(gray, gray_off, table_dev, keys, counts, nf, bins_t, rot)
+    kept = np.minimum(found, quota_rows)
+    # rule 8: one gather of the kept slots of every row, in row order = (image, level); the map to the image's own coordinates
+    rows = np.repeat(np.arange(n * levels), kept)
+    slots = np.arange(int(kept.sum())) - np.repeat(np.cumsum(kept) - kept, kept)
+    pick = torch.from_numpy(rows.astype(np.int64) * nf + slots).to(dev)
+    s_of = torch.from_numpy(np.tile(sc, n)[rows].astype(np.float64)).to(dev)
+    xy = _orb_level_to_image(kps.reshape(-1, 2).index_select(0, pick), s_of[:, None])
+    per_image = [int(v) for v in kept.reshape(n, levels).sum(axis=1)]
+    split = lambda t: list(torch.split(t, per_image))
+    kps_l, desc_l = split(xy), split(desc.reshape(-1, desc.shape[2]).index_select(0, pick))
+    if info is not None:
+        info["score"], info["bin"] = split(score.reshape(-1).index_select(0, pick)), split(bins.reshape(-1).index_select(0, pick))
+        info["level"] = split(torch.from_numpy((rows % levels).astype(np.int32)).to(dev))
+        info["size"] = split((s_of * float(2 * _lib.RWH_ORB_PATCH_RADIUS + 1) / 256.0).to(torch.float32))
+        info["counts"] = per_image
+        info["found_levels"] = [[int(v) for v in r] for r in found.reshape(n, levels)]
+        info["found"] = [sum(r) for r in info["found_levels"]]
+    return list(zip(kps_l, desc_l))
+
+
+def detect_and_describe(img, n_features=500, threshold=20, nbytes=32, pattern=None, n_levels=1, scale=1.2, scales=None, quotas=None):
     """One image through `extract_batch`, numpy in and out: (kps float32 [N, 2] as (x, y), desc uint8 [N, nbytes]) -- what stands
     for `ORB_create().detectAndCompute` (ransac.py:254-257) under the rule stated at `extract_batch` (not OpenCV's ORB)."""
-    (kps, desc), = extract_batch([img], n_features=n_features, threshold=threshold, nbytes=nbytes, pattern=pattern)
+    (kps, desc), = extract_batch([img], n_features=n_features, threshold=threshold, nbytes=nbytes, pattern=pattern, n_levels=n_levels,
+                                 scale=scale, scales=scales, quotas=quotas)
     return kps.cpu().numpy(), desc.cpu().numpy()
 
 
@@ -985,8 +1132,9 @@ def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blen
     `matches=(ptsA, ptsB)` injects precomputed correspondences so the
     GPU path works without OpenCV; `features=(kpsA, descA, kpsB, descB)` (keypoints float32 [N, 2], binary descriptors uint8
     [N, nbytes], A = trainImg's) injects the extractor's output and matches it on the GPU (`match_descriptors`);
-    `features="extract"` extracts both images on the GPU first (`extract_batch` with its defaults: the rule stated there, which is
-    not OpenCV's ORB).  `matches` wins over `features`; with neither, the OpenCV path runs.  Everything else keeps the reference's
+    `features="extract"` extracts both images on the GPU first (`extract_batch` with its defaults: the rule stated there, on one
+    scale, which is not OpenCV's ORB); a dict does the same with its entries as `extract_batch`'s keyword arguments, e.g.
+    `features={"n_levels": 8}` for a pair whose images differ in zoom.  `matches` wins over `features`; with neither, the OpenCV path runs.  Everything else keeps the reference's
     signature."""
     if override != 0:
         import cv2
@@ -995,10 +1143,10 @@ def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blen
     if matches is not None:
         ptsA, ptsB = matches
     elif features is not None:
-        if isinstance(features, str):
-            if features != "extract":
-                raise ValueError("stitching: features=%r; 'extract' or (kpsA, descA, kpsB, descB)" % features)
-            (kpsA, descA), (kpsB, descB) = extract_batch([trainImg, queryImg])
+        if isinstance(features, (str, dict)):
+            if isinstance(features, str) and features != "extract":
+                raise ValueError("stitching: features=%r; 'extract', a dict of extract_batch's arguments or (kpsA, descA, kpsB, descB)" % features)
+            (kpsA, descA), (kpsB, descB) = extract_batch([trainImg, queryImg], **(features if isinstance(features, dict) else {}))
         else:
             kpsA, descA, kpsB, descB = features
         qi, ti, _ = match_descriptors(descA, descB)

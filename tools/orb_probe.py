@@ -9,7 +9,12 @@ is set against two numbers measured in the same run: the host twin (rwh_host_orb
 and a plain device copy of the images' bytes (torch's copy kernel: the floor for a kernel that reads every pixel once).  The
 results are checked against the host twin first.
 
-    python tools/orb_probe.py [windows] [calls]
+--levels N (default 1) times the scale pyramid (rules 6 - 8 of include/rwh.h, `extract_batch(n_levels=N)`) instead: the pyramid
+call (rwh_orb_pyramid_batched: its tile prefix and the kernel that makes levels 1 .. N - 1 of the whole batch), then detect, the
+sort and describe over the n * N rows of the table, and the whole extract_batch; the host twin is rwh_host_orb_extract_pyramid,
+and the copy set beside the pyramid call moves as many bytes as it reads and writes.
+
+    python tools/orb_probe.py [windows] [calls] [--levels N]
 """
 import os
 import sys
@@ -23,8 +28,14 @@ sys.path.insert(0, ROOT)
 from ransac_with_homography_amd import _lib, kernels        # noqa: E402
 from ransac_with_homography_amd import ransac as rs         # noqa: E402
 
-WINDOWS = int(sys.argv[1]) if len(sys.argv) > 1 else 11
-CALLS = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+ARGS = list(sys.argv[1:])
+LEVELS = 1
+if "--levels" in ARGS:
+    at = ARGS.index("--levels")
+    LEVELS = int(ARGS[at + 1])
+    del ARGS[at:at + 2]
+WINDOWS = int(ARGS[0]) if len(ARGS) > 0 else 11
+CALLS = int(ARGS[1]) if len(ARGS) > 1 else 20
 N_FEATURES, THRESHOLD, NBYTES = 500, 20, 32
 dev = _lib.require_gpu()
 lib = _lib.load()
@@ -96,6 +107,74 @@ def case(name, images):
     print("  detect reads %.1f MB and writes %.1f MB of gray: %.0f GB/s" % (src.numel() / 1e6, go / 1e6, (src.numel() + go) / t_detect[0] / 1e3))
 
 
+def pyramid_case(name, images):
+    """The same two sizes with LEVELS levels: scales and quotas are extract_batch's defaults."""
+    table, rot = rs.orb_bin_table(), np.ascontiguousarray(rs.rotate_pattern(rs.default_pattern(NBYTES)))
+    scales = rs.orb_scales(LEVELS)
+    quotas = rs.orb_level_quotas(N_FEATURES, scales)
+    room = int(quotas.sum())
+    dev_images = [torch.from_numpy(im).to(dev) for im in images]
+    extract = lambda: rs.extract_batch(dev_images, n_features=N_FEATURES, threshold=THRESHOLD, nbytes=NBYTES, n_levels=LEVELS)
+    feats = extract()
+    host_s, picks = 0.0, sorted(set((0, len(images) - 1)))
+    for i in picks:
+        im = images[i]
+        kps, desc = np.empty((room, 2), np.float32), np.empty((room, NBYTES), np.uint8)
+        score, bins, level = (np.empty(room, np.int32) for _ in range(3))
+        size, count = np.empty(room, np.float32), np.zeros(1, np.int32)
+        t = time.perf_counter()
+        st = lib.rwh_host_orb_extract_pyramid(im.ctypes.data, im.shape[0], im.shape[1], 3, THRESHOLD, scales.ctypes.data, quotas.ctypes.data,
+                                              LEVELS, table.ctypes.data, rot.ctypes.data, NBYTES, kps.ctypes.data, desc.ctypes.data,
+                                              score.ctypes.data, bins.ctypes.data, level.ctypes.data, size.ctypes.data, count.ctypes.data, None)
+        host_s += time.perf_counter() - t
+        assert st == 0
+        assert np.array_equal(feats[i][0].cpu().numpy(), kps[:count[0]]) and np.array_equal(feats[i][1].cpu().numpy(), desc[:count[0]]), "device != host twin"
+    host_per_image = host_s / len(picks)
+    # the library calls on their own, on the buffer and table extract_batch would hand them
+    rows, so, go = [], 0, 0
+    po = sum(im.size for im in images)
+    head = po
+    for im in images:
+        h, w = im.shape[:2]
+        rows.append((so, go, h, w, 3)); so += im.size; go += h * w
+        for s in scales[1:].tolist():
+            hl, wl = (256 * h + s // 2) // s, (256 * w + s // 2) // s
+            rows.append((po, go, hl, wl, 1)); po += hl * wl; go += hl * wl
+    src = torch.cat([t.reshape(-1) for t in dev_images] + [torch.empty((po - head,), dtype=torch.uint8, device=dev)])
+    tab = torch.tensor(rows, dtype=torch.int64, device=dev)
+    cap = 1 << 16
+    kernels.orb_pyramid_batched(src, head, tab, scales)
+    gray, keys, counts = kernels.orb_detect_batched(src, tab, go, THRESHOLD, cap)
+    assert int(counts.max()) <= cap
+    keys = torch.sort(keys, dim=1).values
+    clamped = torch.minimum(counts, torch.from_numpy(np.tile(quotas, len(images))).to(dev))
+    bt, pt = torch.from_numpy(table).to(dev), torch.from_numpy(rot).to(dev)
+    out_keys, nf = torch.empty_like(keys), int(quotas.max())
+    t_pyr = windows(lambda: kernels.orb_pyramid_batched(src, head, tab, scales), CALLS)
+    t_detect = windows(lambda: kernels.orb_detect_batched(src, tab, go, THRESHOLD, cap, out_keys=out_keys), CALLS)
+    t_describe = windows(lambda: kernels.orb_describe_batched(gray, go, tab, keys, clamped, nf, bt, pt), CALLS)
+    t_sort = windows(lambda: torch.sort(out_keys, dim=1), CALLS)
+    t_all = windows(extract, max(CALLS // 4, 2))
+    base_px = sum(im.shape[0] * im.shape[1] for im in images)
+    half = (po + 1) // 2                                                       # a copy of half the bytes reads and writes head + planes in all
+    a, b = torch.empty((half,), dtype=torch.uint8, device=dev), torch.empty((half,), dtype=torch.uint8, device=dev)
+    t_copy_pyr = windows(lambda: a.copy_(b), CALLS)
+    dst = torch.empty_like(src)
+    t_copy = windows(lambda: dst.copy_(src), CALLS)
+    n = len(images)
+    print("%s, %d levels: %d image(s), %.2f Mpx on level 0, %.2f Mpx on levels 1 .. (%.2fx), %d keypoints found, %d kept"
+          % (name, LEVELS, n, base_px / 1e6, (po - head) / 1e6, (po - head) / base_px, int(counts.sum()), sum(f[0].shape[0] for f in feats)))
+    for what, (med, mn) in (("pyramid call", t_pyr), ("copy moving the pyramid's bytes", t_copy_pyr), ("detect call, %d rows" % len(rows), t_detect),
+                            ("describe call", t_describe), ("sort of the keys [%d, 65536]" % len(rows), t_sort), ("extract_batch, whole", t_all),
+                            ("device copy of images + planes", t_copy)):
+        print("  %-34s median %9.1f us   min %9.1f us   (%.1f us / image)" % (what, med, mn, med / n))
+    print("  %-34s %9.1f us / image on one host core;  extract_batch is %.0fx faster per image" % ("host twin", host_per_image * 1e6, host_per_image * 1e6 / (t_all[0] / n)))
+    print("  the pyramid call reads %.1f MB and writes %.1f MB: %.0f GB/s; per output pixel %.2f ns, detect per pixel of its rows %.2f ns"
+          % (head / 1e6, (po - head) / 1e6, po / t_pyr[0] / 1e3, t_pyr[0] * 1e3 / (po - head), t_detect[0] * 1e3 / go))
+
+
+if LEVELS > 1:
+    case = pyramid_case
 z = np.load(os.path.join(ROOT, "tests", "golden", "img_foto1.npz"), allow_pickle=False)
 A, B = np.ascontiguousarray(z["A"]), np.ascontiguousarray(z["B"])
 print("orb_probe: %s, windows %d x %d calls" % (torch.cuda.get_device_name(dev), WINDOWS, CALLS))
