@@ -1249,7 +1249,9 @@ __device__ __forceinline__ void fast8_body(const FastArgs& a, const Coef* tab, c
 // conditions: launch_fast).  A kernel of its own with its own register budget, on purpose: folded into the one-frame kernel behind
 // a uniform branch it would lift that kernel from 60 VGPRs to the walk's count and cost the one-frame path (8K frames, small
 // batches, one homography per image) its 8 resident waves per SIMD.
-constexpr int F8_WALK_WAVES = 4;
+// (5: under this bound the walk takes 96 VGPRs (64 x 8 patches) / 94 (128 x 4), no scratch, and 5 waves per SIMD are resident; under a bound of 4 it
+//  takes 99 VGPRs, which leaves 4 resident waves (an earlier form of this body was 1.5-3 % slower that way on 32 x 4K frames).  The lab entry warp_rgb8_fast8mb keeps its bound of 4: 99 VGPRs, 4 waves.)
+constexpr int F8_WALK_WAVES = 5;
 template <int LOG_PW> __device__ __forceinline__ void fast8mb_body(const FastArgs& a);
 template <typename DstT, int LOG_PW, bool WALK = false>
 __global__ __launch_bounds__(256, (WALK ? F8_WALK_WAVES : f8_waves<DstT, LOG_PW>())) void warp_rgb8_fast8(const FastArgs a) {
@@ -1616,8 +1618,17 @@ __device__ __forceinline__ void fast8m_body(const FastArgs& a) {
 // (132 x 18 texels for 2048 pixels instead of 4 x 66 x 10) + the same stores 0.2793 ms.  The halo is what the load path pays for.
 // Here the block's 256 threads stage the union of the four patches' footprints into one RGBX slab (fixed lane map: slot c = thread
 // + 256 p -> row c / BCH, chunk c % BCH), the waves take their taps from it; two block barriers per frame (slab free / slab ready),
-// which the multi-frame loop can afford: its per-frame arithmetic is half the one-frame kernel's.  Blocks with a patch that is not
-// strictly interior, or whose union does not fit BROWS x BCH chunks, run the one-frame body frame by frame (all four waves).
+// which the multi-frame loop can afford: its per-frame arithmetic is half the one-frame kernel's.
+// Edge blocks walk too (profiles/warp_walk_edges.txt): nothing in the frame loop needs a block to be interior -- it reads taps at
+// precomputed slab addresses and blends with precomputed weights -- so fast8_body's border rules are applied ONCE per block, at
+// block scope: the window is the union of the boxes of the waves that are not wholly outside the source, clamped into the image
+// (bound_w / bound_h, start on a multiple of 4 texels); a pixel outside [0, bound - 1] gets four zero weights (its blend is
+// U8_BIAS, which stores 0) and every tap address is clamped into the staged window.  A block that maps wholly outside stores zeros
+// for every frame of its group and loads nothing; inside a window block, a wave of a moved last tile that owns no column and a wave
+// that maps wholly outside compute no geometry and take no taps: they stage their slots, keep the barriers, and the second stores
+// zeros per frame, as the one-frame body does for such a patch.  Only three kinds of block still run the one-frame body frame by frame (all four waves): a wave
+// with W at / across zero (the horizon), a window that does not fit BROWS x BCH chunks, and a window that reaches the last two
+// source rows (a staging chunk may read 9 bytes past its last texel).
 constexpr int BCH = 36, BROWS = 22;                     // block window: 144 texels x 22 rows
 // block barrier that orders LDS traffic only (__syncthreads' fence also waits for every outstanding global load and store:
 // the prefetched chunks of the next frame, the stores of the previous one)
@@ -1678,34 +1689,66 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
     const int y2 = (int)__builtin_amdgcn_readlane(ehy[0], 64 - LPR), y3 = (int)__builtin_amdgcn_readlane(ehy[1], 63);
     const int whxmn = smin(smin(x0, x1), smin(x2, x3)) & ~3, whxmx = smax(smax(x0, x1), smax(x2, x3));
     const int whymn = smin(smin(y0, y1), smin(y2, y3)), whymx = smax(smax(y0, y1), smax(y2, y3));
+    // a wave of the moved last tile that owns no column (fast8_body): it stages its slots and keeps the barriers, nothing else
+    const bool owns = (wave % WX + 1) * PW > tshift;          // uniform
+    bool in;                                                  // uniform: this wave owns a column and is not wholly outside the source: it blends
     {
-        const int xmn = (int)((uint32_t)smax(whxmn, 0) - MAGIC_HI), xmx = (int)((uint32_t)smax(whxmx, 0) - MAGIC_HI);
-        const int ymn = (int)((uint32_t)smax(whymn, 0) - MAGIC_HI), ymx = (int)((uint32_t)smax(whymx, 0) - MAGIC_HI);
-        const bool interior = wpos & (xmn >= 0) & (xmx < a.bound_w - 1) & (ymn >= 0) & (ymx < min(a.bound_h - 1, a.src_h - 2));
-        // ---- the block's window = the union of its four patches' footprints (through LDS; block-uniform afterwards) -------------
+        // the patch's box in texels (negative hi dwords clamped first: fast8_body) and fast8_body's wholly-outside test
+        const int bxmn = (int)((uint32_t)smax(whxmn, 0) - MAGIC_HI), bxmx = (int)((uint32_t)smax(whxmx, 0) - MAGIC_HI);
+        const int bymn = (int)((uint32_t)smax(whymn, 0) - MAGIC_HI), bymx = (int)((uint32_t)smax(whymx, 0) - MAGIC_HI);
+        const bool outside = wpos & ((bxmx < 0) | (bxmn >= a.bound_w) | (bymx < 0) | (bymn >= a.bound_h));
+        const bool interior = wpos & (bxmn >= 0) & (bxmx < a.bound_w - 1) & (bymn >= 0) & (bymx < min(a.bound_h - 1, a.src_h - 2));
+        in = owns & !outside;
+        // ---- the block's window = the union of its blending waves' boxes, each clamped into the image exactly as fast8_body's border
+        // path clamps its own (bound_w / bound_h; the start goes to a multiple of 4 texels below); a wave that does not blend writes an
+        // empty box, so the block-wide reduction is a plain min / max (through LDS; block-uniform afterwards) ---------------------------
+        const int bw1 = __builtin_amdgcn_readfirstlane(a.bound_w) - 1, bh1 = __builtin_amdgcn_readfirstlane(a.bound_h) - 1;
         int* red = reinterpret_cast<int*>(slab0);
-        if (lane == 0) { red[5 * wave] = whxmn; red[5 * wave + 1] = whxmx; red[5 * wave + 2] = whymn; red[5 * wave + 3] = whymx; red[5 * wave + 4] = interior ? 1 : 0; }
+        if (lane == 0) {
+            red[5 * wave] = in ? smin(smax(bxmn, 0), bw1) : 0x7FFFFFFF; red[5 * wave + 1] = in ? smin(smax(bxmx, 0), bw1) : -0x7FFFFFFF - 1;
+            red[5 * wave + 2] = in ? smin(smax(bymn, 0), bh1) : 0x7FFFFFFF; red[5 * wave + 3] = in ? smin(smax(bymx, 0), bh1) : -0x7FFFFFFF - 1;
+            red[5 * wave + 4] = (wpos ? 1 : 0) | ((interior | !owns) ? 2 : 0);
+        }
     }
     __syncthreads();
-    int hxmn, hxmx, hymn, hymx, all_in;
+    // Block classes (all block-uniform):
+    //   * a wave with W at / across zero (the horizon): the one-frame body, frame by frame, as before;
+    //   * no wave blends (the block maps wholly outside the source): zeros for every frame of the group, no loads, no taps;
+    //   * otherwise the clamped union holds every valid pixel's taps, by convexity.  Used when it fits BROWS x BCH chunks and stays above
+    //     the last two source rows (a chunk may read 9 bytes past its last texel); an interior block's window is what it was.  Else the
+    //     one-frame body.
+    int xmn, xmx, ymn, ymx, fl_and;
     {
         const int* red = reinterpret_cast<const int*>(slab0);
-        hxmn = min(min(red[0], red[5]), min(red[10], red[15])); hxmx = max(max(red[1], red[6]), max(red[11], red[16]));
-        hymn = min(min(red[2], red[7]), min(red[12], red[17])); hymx = max(max(red[3], red[8]), max(red[13], red[18]));
-        all_in = red[4] & red[9] & red[14] & red[19];
-        hxmn = __builtin_amdgcn_readfirstlane(hxmn); hxmx = __builtin_amdgcn_readfirstlane(hxmx);
-        hymn = __builtin_amdgcn_readfirstlane(hymn); hymx = __builtin_amdgcn_readfirstlane(hymx);
-        all_in = __builtin_amdgcn_readfirstlane(all_in);
+        xmn = min(min(red[0], red[5]), min(red[10], red[15])); xmx = max(max(red[1], red[6]), max(red[11], red[16]));
+        ymn = min(min(red[2], red[7]), min(red[12], red[17])); ymx = max(max(red[3], red[8]), max(red[13], red[18]));
+        fl_and = red[4] & red[9] & red[14] & red[19];
+        xmn = __builtin_amdgcn_readfirstlane(xmn) & ~3; xmx = __builtin_amdgcn_readfirstlane(xmx);
+        ymn = __builtin_amdgcn_readfirstlane(ymn); ymx = __builtin_amdgcn_readfirstlane(ymx);
+        fl_and = __builtin_amdgcn_readfirstlane(fl_and);
     }
     __syncthreads();                                           // (the scratch words are slab bytes: read by all before anyone stages)
-    const int xmn = (int)((uint32_t)hxmn - MAGIC_HI), xmx = (int)((uint32_t)hxmx - MAGIC_HI);          // all_in: the hi dwords are >= MAGIC_HI
-    const int ymn = (int)((uint32_t)hymn - MAGIC_HI), ymx = (int)((uint32_t)hymx - MAGIC_HI);
-    const int nrows = ymx - ymn + 2, C = (xmx - xmn + 5) >> 2;
-    if (!(all_in && nrows <= BROWS && C <= BCH)) {            // block-uniform: the one-frame body, frame by frame, every wave its patch
-        const int own_from = (int)tx * 128 - min((int)tx * 128, a.out_w - 128);
-        if ((wave % WX + 1) * PW <= own_from) return;
+    const bool any_in = ymn != 0x7FFFFFFF;                     // uniform
+    const int nrows = any_in ? ymx - ymn + 2 : 0, C = any_in ? (xmx - xmn + 5) >> 2 : 0;
+    const uint32_t doff = ((uint32_t)rr * (uint32_t)a.pitch_w + (uint32_t)c0p) * 3u;
+    const bool masked = !(fl_and & 2);                         // uniform: some owning wave is not strictly interior
+    if (!(fl_and & 1) || (any_in && !(nrows <= BROWS && C <= BCH && ymn + nrows - 1 <= a.src_h - 2))) {
+        if (!owns) return;
         for (int f = f0; f < f1; ++f)
             fast8_body<unsigned char, LOG_PW, false, 3, false, true>(a, nullptr, nullptr, (int)((unsigned)f * a.ntiles + ti), slab0 + wave * SLABW);
+        return;
+    }
+    if (!any_in) {                                             // the whole block maps outside the source
+        if (!owns) return;
+        unsigned char* drow = a.dst + (long long)f0 * a.dst_img_stride + doff;
+        for (int f = f0; f < f1; ++f) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int first = tshift - (lcol + (PW / 2) * h);
+                zero_store<unsigned char, 1, 3>(drow + 3 * (PW / 2) * h, store_any & (first <= 3), max(first, 0));
+            }
+            drow += a.dst_img_stride;
+        }
         return;
     }
 
@@ -1724,7 +1767,6 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
     }
     const unsigned char* gsrc = a.src + (long long)f0 * a.src_img_stride + (size_t)((uint32_t)ymn * pitch + (uint32_t)xmn * 3u);   // uniform
     unsigned char* gdst = a.dst + (long long)f0 * a.dst_img_stride;
-    const uint32_t doff = ((uint32_t)rr * (uint32_t)a.pitch_w + (uint32_t)c0p) * 3u;
     typedef uint32_t u3 __attribute__((ext_vector_type(3)));
     auto issue = [&](const unsigned char* gb, u3 (&v)[SLOTS]) __attribute__((always_inline)) {
 #pragma unroll
@@ -1751,10 +1793,17 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
             }
     };
 
-    // ---- geometry of the lane's 8 pixels, once (fast8m_body) ---------------------------------------------------------------
-    const uint32_t tap_c = ((uint32_t)hymn & 0xFFFFFFu) * lpitch + ((uint32_t)hxmn << 2);   // uniform; the block slab starts at LDS offset of slab0
+    // ---- geometry of the lane's 8 pixels, once (fast8m_body), with fast8_body's border rules folded in: a pixel outside
+    // [0, bound - 1] (tested on the bit patterns, as pixel_valid does) gets four zero weights -- its blend is U8_BIAS, which stores
+    // 0 --, and every pixel's tap address is kept inside the staged nrows x C chunks, whatever its coordinate is: a valid pixel
+    // lies in the window by convexity (up to a floor() that rounding moved across an integer, where the tap that could fall
+    // outside has a weight < 2^-32).  An interior block (uniform) skips both, as it always did; the frame loop does not know about them.
+    const uint32_t bx = MAGIC_HI + (uint32_t)xmn, by = MAGIC_HI + (uint32_t)ymn;                // uniform
+    const uint32_t rx_max = (uint32_t)(4 * C - 2), ry_max = (uint32_t)(nrows - 2);
+    const uint32_t tap_c = (by & 0xFFFFFFu) * lpitch + (bx << 2);                                // (interior blocks) from slab0, where the block slab starts
     float wa[F8_PX], wb[F8_PX], wc[F8_PX], wd[F8_PX];
     uint32_t lo[F8_PX];
+    if (in) {                                                  // (uniform; the other waves take no taps)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         double X[3], Y[3], W[3], rc[3];
@@ -1773,17 +1822,36 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
             hx[q] = hi32(ux); lx[q] = lo32(ux); hy[q] = hi32(uy); ly[q] = lo32(uy);
         }
         hx[3 * h] = ehx[h]; lx[3 * h] = elx[h]; hy[3 * h] = ehy[h]; ly[3 * h] = ely[h];
+        if (!masked) {
 #pragma unroll
-        for (int j = 0; j < FP_PX; ++j) {
-            const int p = 4 * h + j;
-            const float wx1 = (float)lx[j], wy1 = (float)ly[j] * WS;
-            const float w11 = wx1 * wy1;
-            const float w01 = __builtin_fmaf(wx1, WO, -w11);
-            const float w10 = __builtin_fmaf(wy1, 4294967296.0f, -w11);
-            const float w00 = __builtin_fmaf(-wx1, WO, WC) - w10;
-            wa[p] = w00; wb[p] = w01; wc[p] = w10; wd[p] = w11;
-            lo[p] = mad24_s(hy[j], lpitch, shl2_add_s(hx[j], 0u - tap_c));
+            for (int j = 0; j < FP_PX; ++j) {
+                const int p = 4 * h + j;
+                const float wx1 = (float)lx[j], wy1 = (float)ly[j] * WS;
+                const float w11 = wx1 * wy1;
+                const float w01 = __builtin_fmaf(wx1, WO, -w11);
+                const float w10 = __builtin_fmaf(wy1, 4294967296.0f, -w11);
+                const float w00 = __builtin_fmaf(-wx1, WO, WC) - w10;
+                wa[p] = w00; wb[p] = w01; wc[p] = w10; wd[p] = w11;
+                lo[p] = mad24_s(hy[j], lpitch, shl2_add_s(hx[j], 0u - tap_c));
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < FP_PX; ++j) {
+                const int p = 4 * h + j;
+                const unsigned long long ubx = ((unsigned long long)hx[j] << 32) | lx[j], uby = ((unsigned long long)hy[j] << 32) | ly[j];
+                const bool valid = (ubx >= MAGIC_BITS) & (ubx <= a.xmax_bits) & (uby >= MAGIC_BITS) & (uby <= a.ymax_bits);
+                const float ws = valid ? WS : 0.f, wo = valid ? WO : 0.f, wc1 = valid ? WC : 0.f;
+                const float wx1 = (float)lx[j], wy1 = (float)ly[j] * ws;
+                const float w11 = wx1 * wy1;
+                const float w01 = __builtin_fmaf(wx1, wo, -w11);
+                const float w10 = __builtin_fmaf(wy1, 4294967296.0f, -w11);
+                const float w00 = __builtin_fmaf(-wx1, wo, wc1) - w10;
+                wa[p] = w00; wb[p] = w01; wc[p] = w10; wd[p] = w11;
+                const uint32_t rx = min(hx[j] - bx, rx_max), ry = min(hy[j] - by, ry_max);
+                lo[p] = mad24_s(ry, lpitch, rx << 2);
+            }
         }
+    }
     }
     u3 v[SLOTS];
     issue(gsrc, v);
@@ -1794,7 +1862,8 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
     for (int f = f0; f < f1; ++f) {
         gsrc += a.src_img_stride;
         const bool more = f + 1 < f1;                         // block-uniform
-        pk3 w[2];
+        pk3 w[2];                                              // (set and stored by the waves that blend: `in`, uniform, fixed for the block)
+        if (in) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             float o[FP_PX][3];
@@ -1812,6 +1881,7 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
             }
             w[h] = pack_run_u8(o);
         }
+        }
         if (more) {
             lds_barrier();                                     // every wave has taken its taps of frame f: the slab is free
             landed(v);
@@ -1819,10 +1889,18 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
             lds_barrier();                                     // the slab holds frame f + 1
         }
         unsigned char* drow = gdst + doff;
+        if (in) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int first = tshift - (lcol + (PW / 2) * h);
-            store_run_pk(w[h], drow + 3 * (PW / 2) * h, store_any & (first <= 3), max(first, 0));
+            for (int h = 0; h < 2; ++h) {
+                const int first = tshift - (lcol + (PW / 2) * h);
+                store_run_pk(w[h], drow + 3 * (PW / 2) * h, store_any & (first <= 3), max(first, 0));
+            }
+        } else if (owns) {                                     // a wave wholly outside the source: zeros, as fast8_body stores for such a patch
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int first = tshift - (lcol + (PW / 2) * h);
+                zero_store<unsigned char, 1, 3>(drow + 3 * (PW / 2) * h, store_any & (first <= 3), max(first, 0));
+            }
         }
         gdst += a.dst_img_stride;
         if (f + 2 < f1) issue(gsrc + a.src_img_stride, v);
