@@ -702,6 +702,59 @@ RWH_API int rwh_stitch_panorama_ex(const void* d_img_t, int t_h, int t_w, int t_
                                    int tsx, int tsy, int qsx, int qsy, int canvas_h, int canvas_w, int canvas_c,
                                    int blend, double rate, void* d_canvas, int row_begin, int row_end, unsigned flags, void* stream);
 
+/*
+ * The sequence compositor: N images into ONE panorama, every image warped once into a common frame and every canvas pixel
+ * written once.  The reference has no counterpart (stitchPanorama takes two images, homography.py:288-338); this is its paste
+ * compositor generalised, held to THE SEQUENCE RULE below.  At N = 2 with blend RWH_SEQ_PASTE the canvas is, byte for byte,
+ * stitchPanorama(images[0], images[1], H) with G_1 = H.
+ *
+ * The sequence rule.
+ *   Inputs.  images[0 .. N-1]: uint8 [h_i, w_i, 3], sizes may differ, h_i, w_i >= 2.  G_i: float64 3 x 3, maps image i's pixel
+ *     coordinates into the anchor's frame.  1 <= N <= RWH_SEQ_MAX_IMAGES.
+ *   The anchor.  Exactly one image, a, is the anchor; it enters unwarped, as imgQ does in the reference.
+ *   Rectangle of a warped image.  The four corners (0,0), (w-1,0), (w-1,h-1), (0,h-1) through G_i, dehomogenised; min / max
+ *     truncated toward zero (homography.py:143-163): (mx_i, my_i, wt_i, ht_i) = (min_x, min_y, max_x - min_x + 1, max_y - min_y + 1).
+ *     The anchor's rectangle is (0, 0, w_a, h_a).
+ *   Canvas.  The union of the rectangles: origin (ox, oy) = (min mx_i, min my_i), fw = max(mx_i + wt_i) - ox, fh likewise.
+ *     Canvas pixel (cx, cy) is frame point (x, y) = (ox + cx, oy + cy).
+ *   Sample of a warped image at a frame point.  inv = numpy.linalg.inv(G_i) on the host; X = fma(inv1, y, inv0 * x) + inv2, Y
+ *     and W likewise with rows 1 and 2; sx = X / W, sy = Y / W; valid = sx >= 0 & sx <= w-1 & sy >= 0 & sy <= h-1 (a NaN is not
+ *     valid); ix, iy = sx, sy truncated; taps at ix, min(ix + 1, w-1), iy, min(iy + 1, h-1); texel (0,0) reads as 0 in all
+ *     channels; fx = sx - ix, fy = sy - iy; top = p00 * (1 - fx) + p01 * fx, bot likewise, v = top * (1 - fy) + bot * fy, all in
+ *     float64 and no operation contracted.
+ *   Coverage.  Image i covers a canvas pixel when the pixel lies in its rectangle and the sample is valid.  The anchor covers
+ *     its rectangle.
+ *   RWH_SEQ_PASTE.  `order` is a permutation of 0 .. N-1.  The pixel takes the first image in `order` that covers it: the
+ *     anchor's bytes as they are (its texel (0,0) is NOT blanked), (uint8)(int)v per channel for a warped image; 0 where nothing covers.
+ *   RWH_SEQ_FEATHER.  Every covering image contributes with weight g = min(min(sx, (w-1) - sx), min(sy, (h-1) - sy)) + 1.0; for
+ *     the anchor sx, sy are its integer pixel coordinates and v its bytes as float64.  Per channel num += g * v, den += g, both
+ *     accumulated from 0.0 in image-index order; the pixel is (uint8)(int)(num / den), 0 where nothing covers.  `order` is
+ *     validated and otherwise ignored.
+ *   The images are never written.
+ *
+ * rwh_stitch_sequence: d_images: N device pointers (a HOST array of them); hw: N x (h, w); inv_g: N x 9, inv(G_i) (the anchor's
+ * is not read); rects: N x (mx, my, wt, ht); canvas rows [row_begin, row_end) of the canvas_h x canvas_w x 3 uint8 canvas whose
+ * pixel (0, 0) is frame point (origin_x, origin_y) (d_canvas points at row 0).  d_workspace: rwh_stitch_sequence_workspace_bytes(n)
+ * bytes on the device, 8-byte aligned: the call lays the descriptor table down there (it travels in kernel arguments: nothing on
+ * the host has to outlive the call).  One pass over the canvas: a block tests its 256 x 4 tile once against the N rectangles,
+ * its pixels visit only those candidates.
+ * RWH_E_INVALID, before anything is launched: a NULL pointer (an image's among them), N outside 1 .. RWH_SEQ_MAX_IMAGES, anchor
+ * outside 0 .. N-1, an unknown blend, `order` that is not a permutation, h or w < 2, wt or ht <= 0, a rectangle that does not lie
+ * on the canvas, an anchor rectangle other than (0, 0, w_a, h_a), a non-finite inv(G_i), a canvas side outside 1 .. 65535 or a
+ * canvas above 2^31 - 1 bytes, a bad row range, a workspace too small or misaligned.
+ * rwh_host_stitch_sequence: the same arithmetic on host memory (every pointer a host pointer), no GPU involved.
+ */
+#define RWH_SEQ_MAX_IMAGES 64
+enum { RWH_SEQ_PASTE = 0, RWH_SEQ_FEATHER = 1 };
+RWH_API int64_t rwh_stitch_sequence_workspace_bytes(int n);
+RWH_API int rwh_stitch_sequence(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
+                                int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                void* stream);
+RWH_API int rwh_host_stitch_sequence(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                     int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
+                                     int origin_x, int origin_y, int row_begin, int row_end);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,8 @@ RWH_MATCH_TILE_TRAIN, RWH_MATCH_CHUNK_QUERY, RWH_MATCH_SEG_QUERY = 256, 64, 256 
 RWH_ORB_BORDER, RWH_ORB_BINS, RWH_ORB_PATCH_RADIUS, RWH_ORB_TEST_RADIUS, RWH_ORB_TILE_W, RWH_ORB_TILE_H = 16, 30, 15, 13, 64, 16
 # the pyramid (rules 6 - 8): scales are Q8, 256 .. 1024, at most 16 levels; the pyramid kernel's output tile
 RWH_ORB_SCALE_ONE, RWH_ORB_SCALE_MAX, RWH_ORB_LEVELS_MAX, RWH_ORB_PYR_TILE_W, RWH_ORB_PYR_TILE_H = 256, 1024, 16, 64, 16
+# the sequence compositor (include/rwh.h, the sequence rule): most images per call, its blend modes
+RWH_SEQ_MAX_IMAGES, RWH_SEQ_PASTE, RWH_SEQ_FEATHER = 64, 0, 1
 RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRAMES = 0, 1, 2, 3
 
 # every symbol include/rwh.h declares (tests check the library exports them all)
@@ -40,7 +42,8 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex", "rwh_settle_decide", "rwh_refit_batched", "rwh_host_refit",
            "rwh_match_workspace_bytes", "rwh_match_hamming_batched", "rwh_host_match_hamming",
            "rwh_orb_workspace_bytes", "rwh_orb_detect_batched", "rwh_orb_describe_batched", "rwh_host_orb_extract",
-           "rwh_orb_pyramid_bytes", "rwh_orb_pyramid_batched", "rwh_host_orb_pyramid", "rwh_host_orb_extract_pyramid")
+           "rwh_orb_pyramid_bytes", "rwh_orb_pyramid_batched", "rwh_host_orb_pyramid", "rwh_host_orb_extract_pyramid",
+           "rwh_stitch_sequence_workspace_bytes", "rwh_stitch_sequence", "rwh_host_stitch_sequence")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -148,6 +151,14 @@ def _bind(lib):
     lib.rwh_host_orb_pyramid.argtypes = [vp, i32, i32, i32, vp, i32, vp, i64]
     lib.rwh_host_orb_extract_pyramid.restype = i32
     lib.rwh_host_orb_extract_pyramid.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rwh_stitch_sequence_workspace_bytes.restype = i64
+    lib.rwh_stitch_sequence_workspace_bytes.argtypes = [i32]
+    lib.rwh_stitch_sequence.restype = i32
+    lib.rwh_stitch_sequence.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32,        # images hw inv_g rects n anchor order blend
+                                        vp, i32, i32, i32, i32, i32, i32,         # canvas h w origin_x origin_y row_begin row_end
+                                        vp, i64, vp]                              # workspace bytes stream
+    lib.rwh_host_stitch_sequence.restype = i32
+    lib.rwh_host_stitch_sequence.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32]
     return lib
 
 

@@ -54,7 +54,7 @@ __all__ = [
     "calc_corresp", "calc_correspLinear", "calc_correspCollective", "calc_correspLinearCollective",
     "calcHomography", "calcHomographyLinear", "calcH", "nearestNeighbor", "bilinear", "convertfunc",
     "wrapPerspective", "wrapPerspectiveScan", "perspectiveTransform", "transformImage", "transformImageH",
-    "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap",
+    "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence",
 ]
 
 
@@ -730,6 +730,114 @@ def stitchPanorama(imgQ, imgT, H, method='bilinear', blending=False, blendrate=0
     if bits:
         kernels.raise_like_reference(bits, (h, w))
     return res
+
+
+# ------------------------------------------------------------------- sequences of N images ----
+def _sequence_canvas(shapes, Gs, anchor):
+    """Rectangles, canvas and default order of the sequence rule (include/rwh.h) for given G_i: -> (rects [(mx, my, wt, ht)],
+    (ox, oy), (fh, fw), order), or the rule's ValueError."""
+    n = len(shapes)
+    rects = []
+    for i, (shape, G) in enumerate(zip(shapes, Gs)):
+        h, w = int(shape[0]), int(shape[1])
+        if h < 2 or w < 2:
+            raise ValueError("sequence: image %d is %d x %d; sides of 2 at least" % (i, h, w))
+        if i == anchor:
+            rects.append((0, 0, w, h))
+            continue
+        with np.errstate(all="ignore"):
+            p = np.asarray(G, dtype=np.float64) @ np.array([[0, w - 1, w - 1, 0], [0, 0, h - 1, h - 1], [1., 1, 1, 1]])
+            p = p[:2] / p[2]
+        if not (np.isfinite(G).all() and np.isfinite(p).all() and np.abs(p).max() < 2.0 ** 31):
+            raise ValueError("sequence: image %d has a homography or a corner in the anchor's frame that is not finite" % i)
+        mx, my, wt, ht = _bounds(h, w, G, 0)
+        if wt <= 0 or ht <= 0:
+            raise ValueError("sequence: image %d warps to an empty rectangle (%d x %d)" % (i, wt, ht))
+        rects.append((mx, my, wt, ht))
+    ox, oy = min(r[0] for r in rects), min(r[1] for r in rects)
+    fw, fh = max(r[0] + r[2] for r in rects) - ox, max(r[1] + r[3] for r in rects) - oy
+    if fw > 65535 or fh > 65535 or fw * fh * 3 > 2 ** 31 - 1:
+        raise ValueError("sequence: a %d x %d canvas; sides of at most 65535 and at most 2^31 - 1 bytes (does a horizon cross an image?)"
+                         % (fh, fw))
+    order = sorted(range(n), key=lambda i: (abs(i - anchor), i))
+    return rects, (ox, oy), (fh, fw), order
+
+
+def _check_count(n, anchor):
+    if not 1 <= n <= _lib.RWH_SEQ_MAX_IMAGES:
+        raise ValueError("sequence: %d images; 1 .. %d are taken" % (n, _lib.RWH_SEQ_MAX_IMAGES))
+    if not (isinstance(anchor, (int, np.integer)) and 0 <= anchor < n):
+        raise ValueError("sequence: anchor %r outside 0 .. %d" % (anchor, n - 1))
+
+
+def sequence_plan(shapes, Hs, anchor=0):
+    """The geometry of a sequence panorama from its pairwise homographies; pure numpy, no GPU.
+
+    shapes: N image shapes (h, w[, c]); Hs: N - 1 matrices, Hs[i] maps image i+1 into image i -- what
+    `stitching(trainImg=images[i+1], queryImg=images[i])` estimates.  C_0 = I, C_{i+1} = C_i @ Hs[i]; G_i = inv(C_a) @ C_i maps
+    image i into the anchor's frame, G_a the identity exactly.  Returns (Gs float64 [N, 3, 3], rects [(mx, my, wt, ht)] in the
+    anchor's frame, (ox, oy), (fh, fw), order): the rectangles, the canvas and the default paste order (the anchor first, then
+    increasing |i - anchor|, the lower index on ties) of the sequence rule (include/rwh.h).  ValueError: N outside 1 .. 64, a wrong
+    number of Hs, a non-finite G_i or corner, an empty rectangle, a canvas side above 65535 or a canvas above 2^31 - 1 bytes."""
+    n = len(shapes)
+    _check_count(n, anchor)
+    Hs = [np.asarray(H, dtype=np.float64) for H in Hs]
+    if len(Hs) != n - 1 or any(H.shape != (3, 3) for H in Hs):
+        raise ValueError("sequence: %d images take %d 3 x 3 homographies, got %d" % (n, n - 1, len(Hs)))
+    with np.errstate(all="ignore"):
+        C = [np.eye(3)]
+        for H in Hs:
+            C.append(C[-1] @ H)
+        if not all(np.isfinite(c).all() for c in C):
+            raise ValueError("sequence: a chained homography is not finite")
+        inv_a = np.linalg.inv(C[anchor])
+        Gs = np.stack([inv_a @ c for c in C])
+    Gs[anchor] = np.eye(3)
+    rects, origin, size, order = _sequence_canvas(shapes, Gs, anchor)
+    return Gs, rects, origin, size, order
+
+
+def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None):
+    """N images into one panorama in ONE pass over the canvas (`rwh_stitch_sequence`): every image is warped once into the
+    anchor's frame and every canvas pixel written once.  The reference has no counterpart -- its stitchPanorama takes two images,
+    and folding it over a list resamples the growing canvas once per image; this is held to the sequence rule stated in
+    include/rwh.h, the reference's paste compositor generalised.  With two images and blending=False the canvas is, byte for
+    byte, stitchPanorama(images[0], images[1], H) with Hs = [H].
+
+    images: N (1 .. 64) uint8 [h, w, 3] numpy arrays or tensors, sizes may differ; exactly one of Hs (N - 1 pairwise homographies,
+    chained by `sequence_plan`) and Gs (N maps into the anchor's frame, used as given; Gs[anchor] must be the identity).
+    blending: False -- the first image in `order` (default: the anchor, then the nearest) that covers a pixel gives it;
+    "feather" -- every covering image, weighted by its distance to its own border (`order` is ignored).  numpy arrays in -> a
+    numpy canvas; any tensor in -> a device tensor and no host copy of pixels.  The caller's images are never written.
+    ValueError: what `sequence_plan` refuses, an `order` that is not a permutation, another `blending`;
+    NotImplementedError: images that are not uint8 [h, w, 3]."""
+    n = len(images)
+    _check_count(n, anchor)
+    if (Hs is None) == (Gs is None):
+        raise ValueError("stitchSequence: exactly one of Hs and Gs")
+    if blending is not False and blending != "feather" and blending:
+        raise ValueError("stitchSequence: blending=%r; False or 'feather'" % (blending,))
+    blend = _lib.RWH_SEQ_FEATHER if blending == "feather" else _lib.RWH_SEQ_PASTE
+    for i, img in enumerate(images):
+        if len(img.shape) != 3 or img.shape[2] != 3 or str(img.dtype).replace("torch.", "") != "uint8":
+            raise NotImplementedError("stitchSequence: image %d is %s %s; uint8 [h, w, 3] images are taken" % (i, img.dtype, tuple(img.shape)))
+    shapes = [tuple(int(v) for v in img.shape) for img in images]
+    if Hs is not None:
+        Gs, rects, origin, size, default = sequence_plan(shapes, Hs, anchor)
+    else:
+        Gs = np.array([np.asarray(G, dtype=np.float64) for G in Gs])
+        if Gs.shape != (n, 3, 3) or not np.array_equal(Gs[anchor], np.eye(3)):
+            raise ValueError("stitchSequence: Gs takes %d 3 x 3 matrices with the identity at the anchor" % n)
+        rects, origin, size, default = _sequence_canvas(shapes, Gs, anchor)
+    order = default if order is None else [int(v) for v in order]
+    if sorted(order) != list(range(n)):
+        raise ValueError("stitchSequence: order %r is not a permutation of 0 .. %d" % (order, n - 1))
+    inv_g = np.stack([np.eye(3) if i == anchor else np.linalg.inv(Gs[i]) for i in range(n)])
+    dev = _lib.require_gpu()
+    tens = any(_is_tensor(img) for img in images)
+    on_dev = [img.to(dev).contiguous() if _is_tensor(img) else _xfer.to_device(img, dev) for img in images]
+    out = kernels.stitch_sequence(on_dev, inv_g, rects, anchor, order, blend, origin, size)
+    return out if tens else _xfer.to_host(out)
 
 
 # numpy element types the any-dtype compositor reads (bool as uint8); torch's are kernels.STITCH_DTYPE

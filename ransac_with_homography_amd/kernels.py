@@ -626,6 +626,53 @@ def stitch_panorama_ex(img_t, img_q, inv_h, grid_origin, warp_wh, t_origin, q_or
     return out
 
 
+SEQ_MAX_IMAGES = _lib.RWH_SEQ_MAX_IMAGES
+SEQ_BLEND = {False: _lib.RWH_SEQ_PASTE, "feather": _lib.RWH_SEQ_FEATHER}
+
+
+def sequence_tables(shapes, inv_g, rects, order):
+    """The host tables of rwh_stitch_sequence / rwh_host_stitch_sequence as contiguous arrays: (hw int32 [n, 2], inv_g float64
+    [n, 9], rects int32 [n, 4], order int32 [n])."""
+    n = len(shapes)
+    hw = np.ascontiguousarray([[int(s[0]), int(s[1])] for s in shapes], dtype=np.int32).reshape(n, 2)
+    return (hw, np.ascontiguousarray(inv_g, dtype=np.float64).reshape(n, 9), np.ascontiguousarray(rects, dtype=np.int32).reshape(n, 4),
+            np.ascontiguousarray(order, dtype=np.int32).reshape(-1))
+
+
+def stitch_sequence(images, inv_g, rects, anchor, order, blend, origin, canvas_hw, rows=None, out=None):
+    """Launch the sequence compositor (rwh_stitch_sequence; the sequence rule of include/rwh.h): images: n [h, w, 3] uint8 GPU
+    tensors; inv_g: n inv(G_i); rects: n (mx, my, wt, ht); order: a permutation of 0 .. n-1; blend: RWH_SEQ_PASTE / RWH_SEQ_FEATHER;
+    origin: (ox, oy) -> canvas [fh, fw, 3] uint8, on torch's current stream.  rows=(r0, r1): only those canvas rows, into `out`
+    (the whole canvas tensor) when given.  What the library refuses (RWH_E_INVALID) raises ValueError."""
+    lib = _lib.load()
+    _dev_check(*images)
+    n = len(images)
+    for t in images:
+        assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
+    fh, fw = (int(v) for v in canvas_hw)
+    if not (1 <= n <= SEQ_MAX_IMAGES) or len(order) != n or len(rects) != n or len(inv_g) != n:
+        raise ValueError("stitch_sequence: %d images (1 .. %d), %d rectangles, %d matrices, order of %d" % (n, SEQ_MAX_IMAGES, len(rects), len(inv_g), len(order)))
+    if not (1 <= fh <= 65535 and 1 <= fw <= 65535 and fh * fw * 3 <= 2 ** 31 - 1):
+        raise ValueError("stitch_sequence: a %d x %d canvas; sides of 1 .. 65535 and at most 2^31 - 1 bytes" % (fh, fw))
+    if out is None:
+        out = torch.empty((fh, fw, 3), dtype=torch.uint8, device=images[0].device)
+    else:
+        _dev_check(out)
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (fh, fw, 3)
+    r0, r1 = (0, fh) if rows is None else (int(rows[0]), int(rows[1]))
+    hw, ig, rc, od = sequence_tables([t.shape for t in images], inv_g, rects, order)
+    ptrs = np.array([t.data_ptr() for t in images], dtype=np.uint64)
+    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
+    status = lib.rwh_stitch_sequence(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), od.ctypes.data,
+                                     int(blend), _ptr(out), fh, fw, int(origin[0]), int(origin[1]), r0, r1, _ptr(ws),
+                                     ws.numel() * 8, _lib.stream_ptr())
+    if status == _lib.RWH_E_INVALID:
+        raise ValueError("stitch_sequence: the library refused the arguments (include/rwh.h, rwh_stitch_sequence: order, anchor, "
+                         "rectangles on the canvas, finite inv(G), row range)")
+    check(status, "rwh_stitch_sequence")
+    return out
+
+
 def decode_best(best_words, k_total):
     """Unpack the two argmax words (host ints) -> (winner_index, count, early_exit).
     Word 1 (first index reaching `need`) takes precedence, like the reference's

@@ -1,0 +1,203 @@
+"""The sequence rule (include/rwh.h, rwh_stitch_sequence) restated in numpy, the host twin's driver and the case makers that
+tests/test_sequence_cpu.py and tests/test_sequence_gpu.py share.  The restatement takes its coordinates from the oracle
+(`_source_coords`, `output_bounds`) and clamps the +1 taps where the oracle's `bilinear` raises IndexError."""
+import numpy as np
+
+from oracle import rwh_oracle as orc
+
+PASTE, FEATHER = 0, 1
+
+
+# ---- the rule ----
+def rectangles(shapes, Gs, anchor):
+    return [(0, 0, s[1], s[0]) if i == anchor else orc.output_bounds(s[0], s[1], np.asarray(G, dtype=np.float64))
+            for i, (s, G) in enumerate(zip(shapes, Gs))]
+
+
+def canvas_of(rects):
+    ox, oy = min(r[0] for r in rects), min(r[1] for r in rects)
+    return (ox, oy), (max(r[1] + r[3] for r in rects) - oy, max(r[0] + r[2] for r in rects) - ox)
+
+
+def default_order(n, anchor):
+    return sorted(range(n), key=lambda i: (abs(i - anchor), i))
+
+
+def sample(img, G, rect, is_anchor):
+    """Image over its rectangle: (v float64 [ht, wt, 3], covered bool [ht, wt], g float64 [ht, wt])."""
+    h, w, _ = img.shape
+    mx, my, wt, ht = rect
+    if is_anchor:
+        sx, sy = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+        v, valid = img.astype(np.float64), np.ones((h, w), dtype=bool)
+    else:
+        z = orc._source_coords(np.asarray(G, dtype=np.float64), mx, mx + wt - 1, wt, my, my + ht - 1, ht)
+        sx, sy = z[0].reshape(ht, wt), z[1].reshape(ht, wt)
+        with np.errstate(invalid="ignore"):
+            valid = (sx >= 0) & (sx <= w - 1) & (sy >= 0) & (sy <= h - 1)
+        sx, sy = np.where(valid, sx, 0.0), np.where(valid, sy, 0.0)
+        ix, iy = sx.astype(np.int32), sy.astype(np.int32)
+        ix1, iy1 = np.minimum(ix + 1, w - 1), np.minimum(iy + 1, h - 1)
+        src = img.astype(np.float64)
+        src[0, 0] = 0.0
+        fx, fy = (sx - ix)[:, :, None], (sy - iy)[:, :, None]
+        top = src[iy, ix] * (1 - fx) + src[iy, ix1] * fx
+        bot = src[iy1, ix] * (1 - fx) + src[iy1, ix1] * fx
+        v = top * (1 - fy) + bot * fy
+    g = np.minimum(np.minimum(sx, (w - 1) - sx), np.minimum(sy, (h - 1) - sy)) + 1.0
+    return v, valid, g
+
+
+def restate(images, Gs, anchor=0, blend=PASTE, order=None):
+    """-> (canvas uint8 [fh, fw, 3], (ox, oy))."""
+    n = len(images)
+    rects = rectangles([im.shape for im in images], Gs, anchor)
+    (ox, oy), (fh, fw) = canvas_of(rects)
+    parts = [sample(images[i], Gs[i], rects[i], i == anchor) for i in range(n)]
+    where = [(slice(r[1] - oy, r[1] - oy + r[3]), slice(r[0] - ox, r[0] - ox + r[2])) for r in rects]
+    if blend == PASTE:
+        can = np.zeros((fh, fw, 3), dtype=np.uint8)
+        for i in reversed(default_order(n, anchor) if order is None else list(order)):      # the first in `order` is written last
+            v, valid, _ = parts[i]
+            win = can[where[i]]
+            win[valid] = v[valid].astype(np.int32).astype(np.uint8)
+        return can, (ox, oy)
+    num, den = np.zeros((fh, fw, 3)), np.zeros((fh, fw))
+    for i in range(n):
+        v, valid, g = parts[i]
+        nw, dw = num[where[i]], den[where[i]]
+        nw[valid] += g[valid][:, None] * v[valid]
+        dw[valid] += g[valid]
+    can = np.zeros((fh, fw, 3), dtype=np.uint8)
+    hit = den > 0
+    can[hit] = (num[hit] / den[hit][:, None]).astype(np.int32).astype(np.uint8)
+    return can, (ox, oy)
+
+
+# ---- the library's two entry points on host tables ----
+def tables(images, Gs, anchor, order=None):
+    n = len(images)
+    rects = rectangles([im.shape for im in images], Gs, anchor)
+    (ox, oy), (fh, fw) = canvas_of(rects)
+    inv = np.stack([np.eye(3) if i == anchor else np.linalg.inv(np.asarray(Gs[i], dtype=np.float64)) for i in range(n)])
+    hw = np.array([[im.shape[0], im.shape[1]] for im in images], dtype=np.int32)
+    order = np.array(default_order(n, anchor) if order is None else order, dtype=np.int32)
+    return dict(hw=hw, inv=np.ascontiguousarray(inv.reshape(n, 9)), rects=np.array(rects, dtype=np.int32), order=order, origin=(ox, oy),
+                size=(fh, fw), n=n, anchor=anchor)
+
+
+def host_twin(lib, images, Gs, anchor=0, blend=PASTE, order=None, rows=None):
+    """rwh_host_stitch_sequence -> (status, canvas), the canvas between two 64-byte canaries that are checked here."""
+    images = [np.ascontiguousarray(im) for im in images]
+    t = tables(images, Gs, anchor, order)
+    fh, fw = t["size"]
+    buf = np.full(fh * fw * 3 + 128, 0xA5, dtype=np.uint8)
+    can = buf[64:64 + fh * fw * 3].reshape(fh, fw, 3)
+    ptrs = np.array([im.ctypes.data for im in images], dtype=np.uint64)
+    r0, r1 = (0, fh) if rows is None else rows
+    st = lib.rwh_host_stitch_sequence(ptrs.ctypes.data, t["hw"].ctypes.data, t["inv"].ctypes.data, t["rects"].ctypes.data, t["n"], anchor,
+                                      t["order"].ctypes.data, blend, can.ctypes.data, fh, fw, t["origin"][0], t["origin"][1], r0, r1)
+    assert (buf[:64] == 0xA5).all() and (buf[-64:] == 0xA5).all()
+    return st, can
+
+
+# ---- the cases ----
+def random_image(h, w, seed):
+    return np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
+
+
+def translate(tx, ty):
+    return np.array([[1.0, 0.0, tx], [0.0, 1.0, ty], [0.0, 0.0, 1.0]])
+
+
+def homography(rng, tx, ty, affine=0.03, persp=2e-4):
+    """A translation plus a small affine and perspective part (the kind of tests/g20_cases.py's fixtures)."""
+    H = np.eye(3) + np.array([[affine, affine, 0.0], [affine, affine, 0.0], [persp, persp, 0.0]]) * rng.uniform(-1, 1, (3, 3))
+    H[0, 2], H[1, 2] = tx, ty
+    return H
+
+
+def chain(Hs, anchor):
+    """G_i of the rule from pairwise Hs (Hs[i]: image i+1 -> image i)."""
+    C = [np.eye(3)]
+    for H in Hs:
+        C.append(C[-1] @ H)
+    Gs = [np.linalg.inv(C[anchor]) @ c for c in C]
+    Gs[anchor] = np.eye(3)
+    return Gs
+
+
+def general_cases():
+    """(name, images, Gs, anchor, order): every N, anchor, order and size of the CPU parity list."""
+    rng = np.random.default_rng(2024)
+    out = [("n1", [random_image(9, 11, 1)], [np.eye(3)], 0, None)]
+    two = [random_image(31, 40, 2), random_image(9, 11, 3)]          # 9 x 11: 297 bytes, the last texel takes the guarded load's byte path
+    out.append(("n2 sizes", two, [np.eye(3), homography(rng, 25.3, -4.6)], 0, None))
+    three = [random_image(30, 41, 4), random_image(27, 38, 5), random_image(33, 29, 6)]
+    hs = [homography(rng, 22.5, 3.2), homography(rng, 19.1, -5.7)]
+    out.append(("n3 anchor 0", three, chain(hs, 0), 0, None))
+    out.append(("n3 anchor 1", three, chain(hs, 1), 1, None))
+    five = [random_image(20 + 3 * i, 37 - 2 * i, 10 + i) for i in range(5)]
+    hs5 = [homography(rng, 14.0 + i, 2.5 - i) for i in range(4)]
+    out.append(("n5 order", five, chain(hs5, 2), 2, [4, 0, 2, 3, 1]))
+    out.append(("n2 last texel", [random_image(9, 11, 7), random_image(9, 11, 8)], [np.eye(3), homography(rng, 0.4, 0.3, 0.01, 1e-5)], 0, None))
+    return out
+
+
+def oracle_pairs(count=20):
+    """Seeded random (imgQ, imgT, H) on which the oracle's stitch_panorama does not raise (its bilinear indexes past the image
+    where a coordinate lies exactly on the last row or column); the seeds are fixed, the test asserts that none raises."""
+    out = []
+    for seed in range(100, 100 + count):
+        rng = np.random.default_rng(seed)
+        hq, wq, ht, wt = (int(v) for v in rng.integers(12, 48, 4))
+        H = homography(rng, float(rng.uniform(-30, 30)), float(rng.uniform(-30, 30)), 0.05, 3e-4)
+        out.append((seed, random_image(hq, wq, seed + 1000), random_image(ht, wt, seed + 2000), H))
+    return out
+
+
+def translated_strip(n, h=12, w=16, step=5):
+    """n images of h x w, image i at (step * i, (3 * i) % 7) of image 0's frame: integer translations."""
+    return [random_image(h, w, 300 + i) for i in range(n)], [translate(step * i, (3 * i) % 7) for i in range(n)]
+
+
+def edge_canvases():
+    """(fw, fh, images, Gs, order, rows): canvases of exactly fw columns for every launch edge of the kernel.  Images have two rows
+    at least, so no canvas has one: fh = 1 is ONE ROW launched (rows = (1, 2)) of a two-row canvas -- the same launch edge; every
+    other fh is the whole canvas (rows None).  The anchor and one or two integer translations span the canvas; the last image is
+    properly warped (no integer map) and first in `order`, so paste shows it too."""
+    out = []
+    for fw in (5, 255, 256, 257, 1030):
+        for fh in (1, 3, 4, 6):
+            H = max(fh, 2)
+            wa = min(fw, 520)
+            images, Gs = [random_image(H, wa, fw + fh)], [np.eye(3)]
+            wb = min(518, fw) if fw > wa else min(fw, 30)
+            images.append(random_image(H, wb, fw + fh + 1))
+            Gs.append(translate(fw - wb, 0))
+            ww = min(fw, 40)
+            images.append(random_image(H, ww, fw + fh + 2))
+            Gs.append(np.array([[0.9, 0.02, 0.3], [0.0, 0.8, 0.1], [1e-5, 0.0, 1.0]]))
+            if fw > 600:
+                images.append(random_image(H, 37, fw + fh + 3))
+                Gs.append(np.array([[0.95, 0.0, 500.4], [0.001, 0.8, 0.1], [0.0, 0.0, 1.0]]))   # across the seam of two blocks
+            rects = rectangles([im.shape for im in images], Gs, 0)
+            assert canvas_of(rects) == ((0, 0), (H, fw)), (fw, fh, rects)
+            out.append((fw, fh, images, Gs, list(range(len(images)))[::-1], (1, 2) if fh == 1 else None))
+    return out
+
+
+def scene(h=200, w=440, seed=5):
+    """An RGB scene of seeded random rectangles and discs on a mid-gray ground (the maker of the pyramid tests, in colour)."""
+    rng = np.random.RandomState(seed)
+    img = np.full((h, w, 3), 110, dtype=np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    for k in range(260):
+        x, y = int(rng.randint(0, w)), int(rng.randint(0, h))
+        v = rng.randint(1, 256, 3).astype(np.uint8)               # never black: a zero pixel on a canvas is an uncovered one
+        a, b = int(rng.randint(4, 30)), int(rng.randint(4, 30))
+        if k % 2:
+            img[max(y - b, 0):y + b, max(x - a, 0):x + a] = v
+        else:
+            img[(xx - x) ** 2 + (yy - y) ** 2 <= a * a] = v
+    return img

@@ -1,0 +1,276 @@
+"""The sequence compositor without a GPU: the host twin (rwh_host_stitch_sequence) against the numpy restatement of the sequence
+rule (tests/sequence_cases.py) and, at N = 2, against the oracle's stitch_panorama and the reference's committed digests; the
+planning (homography.sequence_plan) and every refusal.  Every comparison is exact."""
+import ctypes
+import hashlib
+
+import numpy as np
+import pytest
+
+import sequence_cases as sc
+from conftest import load_golden
+from oracle import rwh_oracle as orc
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from ransac_with_homography_amd import _lib
+    return _lib.load()
+
+
+def twin(lib, *a, **k):
+    st, can = sc.host_twin(lib, *a, **k)
+    assert st == 0
+    return can
+
+
+CASES = sc.general_cases()
+
+
+@pytest.mark.parametrize("blend", [sc.PASTE, sc.FEATHER], ids=["paste", "feather"])
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_host_twin_is_the_restatement(lib, case, blend):
+    _, images, Gs, anchor, order = case
+    want, _ = sc.restate(images, Gs, anchor, blend, order)
+    before = [im.copy() for im in images]
+    got = twin(lib, images, Gs, anchor, blend, order)
+    assert got.shape == want.shape and np.array_equal(got, want)
+    assert all(np.array_equal(a, b) for a, b in zip(images, before))         # the images are never written
+    assert want.any()
+
+
+def test_two_images_pasted_are_the_oracles_stitch_panorama(lib):
+    """N = 2, paste == oracle.stitch_panorama(images[0], images[1], H) on 20 seeded pairs, none skipped: the oracle raises on none."""
+    pairs = sc.oracle_pairs(20)
+    assert len(pairs) >= 20
+    signs = set()
+    for seed, Q, T, H in pairs:
+        want = orc.stitch_panorama(Q.copy(), T.copy(), H)                      # (an IndexError here fails the test: no pair is skipped)
+        got = twin(lib, [Q, T], [np.eye(3), H])
+        assert got.shape == want.shape and np.array_equal(got, want), seed
+        mx, my, _, _ = orc.output_bounds(T.shape[0], T.shape[1], H)
+        signs.add((mx < 0, my < 0))
+    assert len(signs) == 4                                                      # the reference's four canvas cases
+
+
+def test_two_photographs_pasted_match_the_committed_digests(lib):
+    """g8_stitch: H_notebook against the reference's own digest of its pasted canvas; H_g5, for which the fixture holds the canvas
+    shape (its digests are of the 'Rate' blend), against the oracle that test_oracle_golden.py pins to those."""
+    z = load_golden("g8_stitch")
+    f = load_golden("img_foto1")
+    A, B = f["A"], f["B"]
+    got = twin(lib, [B, A], [np.eye(3), z["H_notebook"]])
+    assert tuple(z["stitch_paste_shape"]) == got.shape == (822, 1633, 3)
+    assert np.array_equal(got.reshape(-1)[z["stitch_paste_pick"]], z["stitch_paste_vals"])
+    assert str(z["stitch_paste_sha256"]) == hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest()
+    got = twin(lib, [B, A], [np.eye(3), z["H_g5"]])
+    assert got.shape == tuple(z["stitch_g5_rate_shape"]) == (788, 1647, 3)
+    assert np.array_equal(got, orc.stitch_panorama(B.copy(), A.copy(), z["H_g5"]))
+
+
+@pytest.mark.parametrize("n", [3, 64])
+def test_integer_translations_shift_the_images_byte_for_byte(lib, n):
+    """G_i = translate(tx_i, ty_i): every warped image appears shifted, texel (0,0) as 0, its last row and column included
+    (sx == w - 1: the clamped tap) -- an expectation that needs no restatement."""
+    images, Gs = sc.translated_strip(n)
+    order = list(range(n))[::-1]                      # the last image on top ... the anchor at the bottom
+    got = twin(lib, images, Gs, 0, sc.PASTE, order)
+    want = np.zeros_like(got)
+    for i in range(n):                                # painted bottom to top
+        im = images[i].copy()
+        if i:
+            im[0, 0] = 0
+        x, y = int(Gs[i][0, 2]), int(Gs[i][1, 2])
+        want[y:y + 12, x:x + 16] = im
+    assert got.shape == (12 + max((3 * i) % 7 for i in range(n)), 16 + 5 * (n - 1), 3)
+    assert np.array_equal(got, want)
+    # default order (the anchor on top, then the nearest): painted in reverse
+    got = twin(lib, images, Gs, 0, sc.PASTE)
+    want = np.zeros_like(got)
+    for i in range(n)[::-1]:
+        im = images[i].copy()
+        if i:
+            im[0, 0] = 0
+        x, y = int(Gs[i][0, 2]), int(Gs[i][1, 2])
+        want[y:y + 12, x:x + 16] = im
+    assert np.array_equal(got, want)
+    # feather of exact copies: where one image alone covers, its bytes
+    fe = twin(lib, images, Gs, 0, sc.FEATHER)
+    assert np.array_equal(fe[:12, :5], images[0][:, :5]) and np.array_equal(fe, sc.restate(images, Gs, 0, sc.FEATHER)[0])
+
+
+def test_hidden_image_and_gap(lib):
+    a, b, c, d = (sc.random_image(14, 18, 40 + i) for i in range(4))
+    hidden = sc.random_image(6, 7, 50)
+    # image 2 lies wholly inside image 1, which is before it in `order`: it shows nowhere
+    images, Gs = [a, b, hidden], [np.eye(3), sc.translate(10, 2), sc.translate(15, 5)]
+    got = twin(lib, images, Gs, 0, sc.PASTE, [0, 1, 2])
+    assert np.array_equal(got, twin(lib, [a, b], Gs[:2], 0, sc.PASTE, [0, 1]))
+    assert not np.array_equal(got, twin(lib, images, Gs, 0, sc.PASTE, [2, 0, 1]))
+    # an image whose rectangle touches no other: zeros between
+    images, Gs = [a, c, d], [np.eye(3), sc.translate(30, 20), sc.homography(np.random.default_rng(3), 60.5, 1.5)]
+    for blend in (sc.PASTE, sc.FEATHER):
+        got = twin(lib, images, Gs, 0, blend)
+        assert np.array_equal(got, sc.restate(images, Gs, 0, blend)[0])
+        assert not got[14:20, :30].any() and not got[:14, 18:30].any()          # nothing covers: zeros
+        shifted = c.copy()
+        shifted[0, 0] = 0
+        assert np.array_equal(got[:14, :18], a) and np.array_equal(got[20:34, 30:48], shifted)
+
+
+def test_row_tiles_equal_the_whole_canvas(lib):
+    _, images, Gs, anchor, order = CASES[4]
+    for blend in (sc.PASTE, sc.FEATHER):
+        whole = twin(lib, images, Gs, anchor, blend, order)
+        fh = whole.shape[0]
+        bounds = [0, 5, fh - 7, fh]
+        assert 0 < bounds[1] < bounds[2] < fh
+        tiled = np.zeros_like(whole)
+        for r0, r1 in zip(bounds[:-1], bounds[1:]):
+            part = twin(lib, images, Gs, anchor, blend, order, rows=(r0, r1))
+            assert (part[:r0] == 0xA5).all() and (part[r1:] == 0xA5).all()      # a tile writes its own rows only
+            tiled[r0:r1] = part[r0:r1]
+        assert np.array_equal(tiled, whole)
+
+
+# ---- the planning ----
+def test_sequence_plan_chains_the_pairs():
+    from ransac_with_homography_amd import homography as hg
+    rng = np.random.default_rng(9)
+    shapes = [(30, 41, 3), (27, 38, 3), (33, 29, 3), (25, 36, 3)]
+    Hs = [sc.homography(rng, 20.0 + i, 2.0 - i) for i in range(3)]
+    C = [np.eye(3)]
+    for H in Hs:
+        C.append(C[-1] @ H)
+    Gs, rects, origin, size, order = hg.sequence_plan(shapes, Hs)
+    assert Gs.dtype == np.float64 and all(np.array_equal(Gs[i], C[i]) for i in range(4))       # anchor 0: G_i == C_i
+    assert order == [0, 1, 2, 3]
+    for a in range(4):
+        Gs, rects, origin, size, order = hg.sequence_plan(shapes, Hs, anchor=a)
+        assert np.array_equal(Gs[a], np.eye(3))                                                  # exactly the identity
+        want = sc.chain(Hs, a)
+        assert all(np.array_equal(Gs[i], want[i]) for i in range(4))
+        want_rects = sc.rectangles(shapes, want, a)
+        assert [tuple(r) for r in rects] == [tuple(r) for r in want_rects] and rects[a] == (0, 0, shapes[a][1], shapes[a][0])
+        assert (origin, size) == sc.canvas_of(want_rects)
+        assert order == sc.default_order(4, a)
+    assert hg.sequence_plan(shapes, Hs, anchor=2)[4] == [2, 1, 3, 0]                               # the lower index on ties
+    Gs, rects, origin, size, order = hg.sequence_plan([(9, 11, 3)], [])
+    assert np.array_equal(Gs, np.eye(3)[None]) and rects == [(0, 0, 11, 9)] and (origin, size, order) == ((0, 0), (9, 11), [0])
+
+
+def test_sequence_plan_refusals():
+    from ransac_with_homography_amd import homography as hg
+    s = (20, 30, 3)
+    T = sc.translate(10, 0)
+    with pytest.raises(ValueError):
+        hg.sequence_plan([], [])                                                # N = 0
+    with pytest.raises(ValueError):
+        hg.sequence_plan([s] * 65, [T] * 64)                                    # N = 65
+    assert len(hg.sequence_plan([s] * 64, [T] * 63)[1]) == 64
+    with pytest.raises(ValueError):
+        hg.sequence_plan([s, s], [T, T])                                        # a wrong number of pairs
+    with pytest.raises(ValueError):
+        hg.sequence_plan([s, s], [T], anchor=2)
+    for bad in (np.nan, np.inf):
+        H = T.copy()
+        H[0, 1] = bad
+        with pytest.raises(ValueError):
+            hg.sequence_plan([s, s], [H])                                       # a non-finite G_i
+    H = np.array([[1.0, 0, 0], [0, 1.0, 0], [-1.0 / 29, 0, 1.0]])               # W = 0 at the corner (29, 0): a non-finite bound
+    with pytest.raises(ValueError):
+        hg.sequence_plan([s, s], [H])
+    H = np.array([[1.0, 0, 0], [0, 1.0, 0], [-(1 - 1e-6) / 29, 0, 1.0]])       # the horizon next to a corner: a side of 29 million
+    with pytest.raises(ValueError):
+        hg.sequence_plan([s, s], [H])
+    with pytest.raises(ValueError):
+        hg.sequence_plan([s, s], [sc.translate(70000, 0)])                      # a canvas side above 65535
+    with pytest.raises(ValueError):
+        hg.sequence_plan([s, s], [sc.translate(40000, 40000)])                  # above 2^31 - 1 bytes
+    with pytest.raises(ValueError):
+        hg.sequence_plan([s, (1, 30, 3)], [T])                                  # h < 2
+
+
+def test_stitch_sequence_refuses_before_the_gpu():
+    """What stitchSequence checks comes before it asks for a GPU: these raise here, where there is none."""
+    from ransac_with_homography_amd import homography as hg
+    a, b = sc.random_image(12, 16, 1), sc.random_image(12, 16, 2)
+    T = sc.translate(8, 0)
+    with pytest.raises(ValueError):
+        hg.stitchSequence([a, b], Hs=[T], order=[0, 0])
+    with pytest.raises(ValueError):
+        hg.stitchSequence([a, b], Hs=[T], order=[0, 1, 2])
+    with pytest.raises(ValueError):
+        hg.stitchSequence([a, b])
+    with pytest.raises(ValueError):
+        hg.stitchSequence([a, b], Hs=[T], Gs=[np.eye(3), T])
+    with pytest.raises(ValueError):
+        hg.stitchSequence([a, b], Gs=[T, T])                                    # Gs[anchor] is not the identity
+    with pytest.raises(ValueError):
+        hg.stitchSequence([a, b], Hs=[T], blending="Rate")
+    with pytest.raises(ValueError):
+        hg.stitchSequence([], Hs=[])
+    with pytest.raises(NotImplementedError):
+        hg.stitchSequence([a, b.astype(np.float32)], Hs=[T])
+    with pytest.raises(NotImplementedError):
+        hg.stitchSequence([a, np.zeros((12, 16, 4), np.uint8)], Hs=[T])
+    import homography
+    import ransac
+    assert homography.stitchSequence is hg.stitchSequence and homography.sequence_plan is hg.sequence_plan
+    assert callable(ransac.stitch_sequence)
+
+
+# ---- the C interface ----
+def test_c_level_refusals(lib):
+    images, Gs = sc.translated_strip(3)
+    images = [np.ascontiguousarray(im) for im in images]
+    t = sc.tables(images, Gs, 0)
+    fh, fw = t["size"]
+    can = np.zeros((fh, fw, 3), np.uint8)
+    ptrs = np.array([im.ctypes.data for im in images], dtype=np.uint64)
+
+    def call(fn=lib.rwh_host_stitch_sequence, ptrs=ptrs.ctypes.data, hw=t["hw"].ctypes.data, inv=t["inv"].ctypes.data, rects=t["rects"].ctypes.data,
+             n=3, anchor=0, order=t["order"], blend=0, canvas=can.ctypes.data, fh=fh, fw=fw, origin=t["origin"], rows=(0, fh), tail=()):
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.int32)
+        return fn(ptrs, hw, inv, rects, n, anchor, None if order is None else order.ctypes.data, blend, canvas, fh, fw, origin[0], origin[1],
+                  rows[0], rows[1], *tail)
+    assert call() == 0 and can.any()
+    for k in ("ptrs", "hw", "inv", "rects", "order", "canvas"):
+        assert call(**{k: None}) == -1, k
+    holed = ptrs.copy()
+    holed[1] = 0
+    assert call(ptrs=holed.ctypes.data) == -1                                   # one image's pointer is NULL
+    assert call(n=0) == -1 and call(n=65) == -1 and call(n=-1) == -1
+    assert call(anchor=3) == -1 and call(anchor=-1) == -1 and call(blend=2) == -1
+    for bad in ([0, 0, 1], [0, 1, 3], [-1, 0, 1]):
+        assert call(order=bad) == -1, bad
+    for rows in ((-1, 2), (0, fh + 1), (3, 2)):
+        assert call(rows=rows) == -1, rows
+    assert call(rows=(2, 2)) == 0
+    assert call(fw=fw - 1) == -1 and call(fh=0) == -1 and call(fw=65536) == -1  # a rectangle off the canvas, bad canvas sides
+    assert call(origin=(1, 0)) == -1
+    r = t["rects"].copy()
+    r[2, 2] = 0
+    assert call(rects=r.ctypes.data) == -1                                      # wt <= 0
+    r = t["rects"].copy()
+    r[0, 2] -= 1
+    assert call(rects=r.ctypes.data) == -1                                      # the anchor's rectangle is not its image
+    hw = t["hw"].copy()
+    hw[1, 0] = 1
+    assert call(hw=hw.ctypes.data) == -1                                        # h < 2
+    inv = t["inv"].copy()
+    inv[2, 4] = np.nan
+    assert call(inv=inv.ctypes.data) == -1
+    # the device entry point refuses the same before it touches a device (no GPU here), and a missing or short workspace
+    dev = lib.rwh_stitch_sequence
+    one = ctypes.c_void_p(8)
+    assert lib.rwh_stitch_sequence_workspace_bytes(0) == -1 and lib.rwh_stitch_sequence_workspace_bytes(65) == -1
+    need = lib.rwh_stitch_sequence_workspace_bytes(3)
+    assert need >= 3 * 104 and lib.rwh_stitch_sequence_workspace_bytes(64) >= 64 * 104
+    for kw in (dict(n=0), dict(n=65), dict(order=[0, 0, 1]), dict(rows=(3, 2)), dict(ptrs=None), dict(canvas=None)):
+        assert call(fn=dev, tail=(one, need, None), **kw) == -1, kw
+    assert call(fn=dev, tail=(None, need, None)) == -1 and call(fn=dev, tail=(one, need - 1, None)) == -1
+    assert call(fn=dev, tail=(ctypes.c_void_p(4), need, None)) == -1            # misaligned
+    assert call(fn=dev, rows=(2, 2), tail=(one, need, None)) == 0               # an empty row range launches nothing
