@@ -751,7 +751,10 @@ __device__ __forceinline__ void fast8_body(const FastArgs& a, const Coef* tab, c
     const unsigned img_mem = tab ? (unsigned)co.image : img;   // where the image lives in the batch
     const int pwave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // physical wave: owns LDS slab pwave
     const int wave = ovr_wave >= 0 ? ovr_wave : pwave;                                   // which patch of the tile
-    const int lane = threadIdx.x & 63;
+    int lane = threadIdx.x & 63;
+    // (the multi-frame kernels call this body in a loop over frames: the lane's staging map, store offsets and masks stay inside the
+    //  loop -- hoisted, they cost the batch form, whose register budget is set by its own frame loop, VGPR spills to scratch)
+    if constexpr (EXT_SLAB) asm volatile("" : "+v"(lane));
     const int prow = lane / LPR, pq = lane % LPR;             // patch row, 4-pixel column group within a half row
     const int wave_x = (wave % WX) * PW, wave_y = (wave / WX) * PH;   // patch origin inside the 128 x 16 tile
 
@@ -1238,6 +1241,8 @@ __device__ __forceinline__ void fast8_body(const FastArgs& a, const Coef* tab, c
                 b0[j] = simg[o01] | (simg[o01 + 1] << 8) | (simg[o01 + 2] << 16);
                 a1[j] = simg[o10] | (simg[o10 + 1] << 8) | (simg[o10 + 2] << 16);
                 b1[j] = simg[o11] | (simg[o11 + 1] << 8) | (simg[o11 + 2] << 16);
+                // (inside the batch form the scheduler otherwise puts all 48 byte loads in flight at once: two VGPRs over its budget)
+                if constexpr (EXT_SLAB) __builtin_amdgcn_sched_barrier(0);
             }
         }
         finish_masked_run(h, vbits);
@@ -1249,8 +1254,10 @@ __device__ __forceinline__ void fast8_body(const FastArgs& a, const Coef* tab, c
 // conditions: launch_fast).  A kernel of its own with its own register budget, on purpose: folded into the one-frame kernel behind
 // a uniform branch it would lift that kernel from 60 VGPRs to the walk's count and cost the one-frame path (8K frames, small
 // batches, one homography per image) its 8 resident waves per SIMD.
-// (5: under this bound the walk takes 96 VGPRs (64 x 8 patches) / 94 (128 x 4), no scratch, and 5 waves per SIMD are resident; under a bound of 4 it
-//  takes 99 VGPRs, which leaves 4 resident waves (an earlier form of this body was 1.5-3 % slower that way on 32 x 4K frames).  The lab entry warp_rgb8_fast8mb keeps its bound of 4: 99 VGPRs, 4 waves.)
+// (5: under this bound the walk takes 93 VGPRs (64 x 8 patches) / 92 (128 x 4), no scratch, no SGPR spilled into VGPR lanes, and 5 waves per SIMD are
+//  resident -- as long as its one-frame fallback reads FastArgs by a route of its own, see kernarg_fastargs(); with the kernel's copy live across the
+//  window path it was 96 VGPRs and 115 / 120 spilled SGPRs.  Under a bound of 6 (80 VGPRs) it spills 11 VGPRs to scratch and is slower,
+//  profiles/warp_batch_slim.txt.  The lab entry warp_rgb8_fast8mb keeps its bound of 4 and comes to the same 93 / 92 VGPRs.)
 constexpr int F8_WALK_WAVES = 5;
 template <int LOG_PW> __device__ __forceinline__ void fast8mb_body(const FastArgs& a);
 template <typename DstT, int LOG_PW, bool WALK = false>
@@ -1633,6 +1640,19 @@ constexpr int BCH = 36, BROWS = 22;                     // block window: 144 tex
 // block barrier that orders LDS traffic only (__syncthreads' fence also waits for every outstanding global load and store:
 // the prefetched chunks of the next frame, the stores of the previous one)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory"); }
+// The kernel's FastArgs, read again from the kernarg segment (the kernels that use this body take FastArgs as their only argument, at
+// offset 0): scalar loads through a constant-address-space pointer that the compiler cannot trace back to the kernel's argument.  For the
+// blocks that run the one-frame body frame by frame (29 of the 32 x 4K headline's 3810 tiles).  Handed the kernel's own `a`, that body's
+// three dozen argument fields are loaded at kernel entry and stay live across the window path of EVERY block: 115 SGPRs spilled into VGPR
+// lanes, ~150 v_writelane / v_readlane per wave in front of the frame loop and 8 v_readlane per frame inside it
+// (profiles/warp_batch_slim.txt).  The pointer is laundered inside the frame loop of the fallback, so nothing it loads is hoisted out of it
+// either.  (Constant address space on purpose: a laundered generic pointer makes the compiler keep a private copy of the struct in scratch.)
+__device__ __forceinline__ const FastArgs& kernarg_fastargs() {
+    typedef const FastArgs __attribute__((address_space(4))) kFastArgs;
+    kFastArgs* p = (kFastArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const FastArgs*)p;
+}
 template <int LOG_PW>
 __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
     constexpr int PW = 1 << LOG_PW, PH = 512 / PW, LPR = PW / 8, WX = 128 / PW;
@@ -1734,8 +1754,10 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
     const bool masked = !(fl_and & 2);                         // uniform: some owning wave is not strictly interior
     if (!(fl_and & 1) || (any_in && !(nrows <= BROWS && C <= BCH && ymn + nrows - 1 <= a.src_h - 2))) {
         if (!owns) return;
-        for (int f = f0; f < f1; ++f)
-            fast8_body<unsigned char, LOG_PW, false, 3, false, true>(a, nullptr, nullptr, (int)((unsigned)f * a.ntiles + ti), slab0 + wave * SLABW);
+        for (int f = f0; f < f1; ++f) {
+            const FastArgs& ka = kernarg_fastargs();
+            fast8_body<unsigned char, LOG_PW, false, 3, false, true>(ka, nullptr, nullptr, (int)((unsigned)f * ka.ntiles + ti), slab0 + wave * SLABW);
+        }
         return;
     }
     if (!any_in) {                                             // the whole block maps outside the source
