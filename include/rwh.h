@@ -755,6 +755,65 @@ RWH_API int rwh_host_stitch_sequence(const void* const* images, const int32_t* h
                                      int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
                                      int origin_x, int origin_y, int row_begin, int row_end);
 
+/*
+ * Exposure gain compensation for the sequence compositor (Brown & Lowe 2007, section 6; what OpenCV's GainCompensator does): one
+ * gain per image, solved from pairwise overlap statistics, applied while compositing.  The reference has no counterpart; this is
+ * held to THE GAIN RULE below.  Everything not restated is the sequence rule's: rectangles, canvas, sampling recipe, coverage, and
+ * texel (0,0) of a warped image reading as 0.
+ *
+ * The gain rule.
+ *   Overlap statistics.  Inputs: those of the sequence rule plus `stride`, 1 <= stride <= 255.  The sample set is the canvas pixels
+ *     with cx % stride == 0 and cy % stride == 0.  At a sample, C is the set of images that cover it (the sequence rule's Coverage).
+ *     The bytes of image i at the sample are the bytes paste would write: the anchor's own bytes for the anchor, (uint8)(int)v_k per
+ *     channel for a warped image.  L_i is the sum of the three bytes, 0 <= L_i <= 765.  For every ordered pair (i, j) with i in C and
+ *     j in C, i = j included: count[i][j] += 1 and sum[i][j] += L_i.  Both tables are uint64 [n][n], row-major; a call writes them
+ *     whole (the caller need not zero them), pairs that never meet are 0.  count is symmetric, sum is not.  The statistics are
+ *     integers: they do not depend on the order in which they are added.  They are always taken on the uncompensated bytes.
+ *   Gains.  Inputs: count, sum, sigma_n (default 10.0) and sigma_g (default 0.1), both finite and > 0.  alpha = 1 / sigma_n^2,
+ *     beta = 1 / sigma_g^2.  N_ij = (double)count[i][j]; I_ij = (double)sum[i][j] / (3.0 * N_ij) where count > 0, else 0.0: the
+ *     mean intensity of i where it meets j, on the 0 .. 255 scale.  A (n x n) and b (n) are built from zero in this order: for each
+ *     i with count[i][i] == 0, A_ii = 1 and b_i = 1, the rest of row i stays 0; for each other i, j = 0 .. n-1 in turn:
+ *     A_ii += beta * N_ij and b_i += beta * N_ij, and if j != i: A_ii += 2 * alpha * I_ij * I_ij * N_ij and
+ *     A_ij -= 2 * alpha * I_ij * I_ji * N_ij (products left to right).  This is the normal equation of
+ *     e = 1/2 sum_i sum_j N_ij [alpha (g_i I_ij - g_j I_ji)^2 + beta (1 - g_i)^2], the diagonal N_ii counted in the prior: A is
+ *     symmetric positive definite, and an image that meets nobody gets gain 1 exactly.  The gains are the float64 solution of
+ *     A g = b by Cholesky, in its square-root-free form A = L D L^T on the lower triangle.  A non-positive pivot or a non-finite
+ *     result is refused (RWH_E_INVALID).
+ *   Applying gains.  gains: N float64 values, each finite and > 0 (otherwise RWH_E_INVALID before any launch).  Wherever the
+ *     sequence rule uses a sample value v_k of image i -- the anchor's bytes as float64 included -- it uses min(v_k * g_i, 255.0)
+ *     instead, in paste and in feather; the product is rounded on its own, not contracted.  The anchor under paste is therefore
+ *     (uint8)(int)min((double)b * g_a, 255.0), no longer its bytes as they are.  Feather weights and coverage do not change.  With
+ *     every g_i = 1.0 the canvas is byte for byte the one without gains.
+ *
+ * rwh_sequence_overlap_stats: images, hw, inv_g, rects, n, anchor, canvas and origin as rwh_stitch_sequence's; d_count, d_sum: device,
+ * uint64 [n][n], 8-byte aligned, written whole by every call; d_workspace: rwh_sequence_overlap_stats_workspace_bytes(n,
+ * canvas_h, canvas_w, stride) bytes on the device, 8-byte aligned (the descriptor table and 64 copies of the two tables, zeroed on
+ * the stream by every call).  One pass over the SAMPLE grid: a block takes 256 x 4 samples, tests their footprint once against the
+ * N rectangles, reduces its pairs in LDS and adds each non-zero pair once with a 64-bit integer atomic into one of the copies; a
+ * second kernel sums the copies into d_count and d_sum.  RWH_E_INVALID, before anything is launched: what rwh_stitch_sequence refuses (no order, canvas buffer or row
+ * range here), a stride outside 1 .. 255, a NULL or misaligned table.
+ * rwh_host_sequence_overlap_stats: the same per-sample arithmetic on host memory, no GPU involved.
+ * rwh_host_sequence_gains: the Gains step (host only, plain C++; no LAPACK).  RWH_E_INVALID: a NULL pointer, n outside
+ * 1 .. RWH_SEQ_MAX_IMAGES, a sigma that is not finite and > 0, a non-positive pivot, a non-finite gain.
+ * rwh_stitch_sequence_ex / rwh_host_stitch_sequence_ex: rwh_stitch_sequence / rwh_host_stitch_sequence with `gains` (a HOST array of
+ * N; they travel in the kernel arguments).  gains == NULL is the call without _ex; the gain-free kernels are the code they were.
+ */
+RWH_API int64_t rwh_sequence_overlap_stats_workspace_bytes(int n, int canvas_h, int canvas_w, int stride);
+RWH_API int rwh_sequence_overlap_stats(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                       int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
+                                       uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_sequence_overlap_stats(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                            int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
+                                            uint64_t* count, uint64_t* sum);
+RWH_API int rwh_host_sequence_gains(const uint64_t* count, const uint64_t* sum, int n, double sigma_n, double sigma_g, double* gains);
+RWH_API int rwh_stitch_sequence_ex(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                   int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
+                                   int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                   void* stream, const double* gains);
+RWH_API int rwh_host_stitch_sequence_ex(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                        int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
+                                        int origin_x, int origin_y, int row_begin, int row_end, const double* gains);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,4 +4,4 @@ from ransac_with_homography_amd.ransac import (DEBUG, LVL, HomoModel, Model, RAN
                                                match_descriptors, match_batch, extract_batch, detect_and_describe, default_pattern,
                                                rotate_pattern, orb_bin_table, orb_scales, orb_level_quotas,
                                                calcHomography, calcHomographyLinear, cylindericlMap,
-                                               stitchPanorama, stitch_sequence, stitchSequence, sequence_plan)
+                                               stitchPanorama, stitch_sequence, stitchSequence, sequence_plan, sequence_gains)

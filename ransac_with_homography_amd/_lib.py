@@ -31,8 +31,9 @@ RWH_MATCH_TILE_TRAIN, RWH_MATCH_CHUNK_QUERY, RWH_MATCH_SEG_QUERY = 256, 64, 256 
 RWH_ORB_BORDER, RWH_ORB_BINS, RWH_ORB_PATCH_RADIUS, RWH_ORB_TEST_RADIUS, RWH_ORB_TILE_W, RWH_ORB_TILE_H = 16, 30, 15, 13, 64, 16
 # the pyramid (rules 6 - 8): scales are Q8, 256 .. 1024, at most 16 levels; the pyramid kernel's output tile
 RWH_ORB_SCALE_ONE, RWH_ORB_SCALE_MAX, RWH_ORB_LEVELS_MAX, RWH_ORB_PYR_TILE_W, RWH_ORB_PYR_TILE_H = 256, 1024, 16, 64, 16
-# the sequence compositor (include/rwh.h, the sequence rule): most images per call, its blend modes
+# the sequence compositor (include/rwh.h, the sequence rule): most images per call, its blend modes; the gain rule's largest stride
 RWH_SEQ_MAX_IMAGES, RWH_SEQ_PASTE, RWH_SEQ_FEATHER = 64, 0, 1
+RWH_SEQ_MAX_STRIDE = 255
 RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRAMES = 0, 1, 2, 3
 
 # every symbol include/rwh.h declares (tests check the library exports them all)
@@ -43,7 +44,9 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_match_workspace_bytes", "rwh_match_hamming_batched", "rwh_host_match_hamming",
            "rwh_orb_workspace_bytes", "rwh_orb_detect_batched", "rwh_orb_describe_batched", "rwh_host_orb_extract",
            "rwh_orb_pyramid_bytes", "rwh_orb_pyramid_batched", "rwh_host_orb_pyramid", "rwh_host_orb_extract_pyramid",
-           "rwh_stitch_sequence_workspace_bytes", "rwh_stitch_sequence", "rwh_host_stitch_sequence")
+           "rwh_stitch_sequence_workspace_bytes", "rwh_stitch_sequence", "rwh_host_stitch_sequence",
+           "rwh_sequence_overlap_stats_workspace_bytes", "rwh_sequence_overlap_stats", "rwh_host_sequence_overlap_stats",
+           "rwh_host_sequence_gains", "rwh_stitch_sequence_ex", "rwh_host_stitch_sequence_ex")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -159,6 +162,21 @@ def _bind(lib):
                                         vp, i64, vp]                              # workspace bytes stream
     lib.rwh_host_stitch_sequence.restype = i32
     lib.rwh_host_stitch_sequence.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32]
+    # the gain rule: overlap statistics, the gains, the compositor with gains (the plain calls' arguments, then gains)
+    lib.rwh_sequence_overlap_stats_workspace_bytes.restype = i64
+    lib.rwh_sequence_overlap_stats_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.rwh_sequence_overlap_stats.restype = i32
+    lib.rwh_sequence_overlap_stats.argtypes = [vp, vp, vp, vp, i32, i32,                  # images hw inv_g rects n anchor
+                                               i32, i32, i32, i32, i32,                  # canvas h w origin_x origin_y stride
+                                               vp, vp, vp, i64, vp]                      # count sum workspace bytes stream
+    lib.rwh_host_sequence_overlap_stats.restype = i32
+    lib.rwh_host_sequence_overlap_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.rwh_host_sequence_gains.restype = i32
+    lib.rwh_host_sequence_gains.argtypes = [vp, vp, i32, f64, f64, vp]
+    lib.rwh_stitch_sequence_ex.restype = i32
+    lib.rwh_stitch_sequence_ex.argtypes = lib.rwh_stitch_sequence.argtypes + [vp]
+    lib.rwh_host_stitch_sequence_ex.restype = i32
+    lib.rwh_host_stitch_sequence_ex.argtypes = lib.rwh_host_stitch_sequence.argtypes + [vp]
     return lib
 
 

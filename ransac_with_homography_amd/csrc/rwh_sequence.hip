@@ -38,9 +38,11 @@ __host__ __device__ __forceinline__ double seq_chan(uint32_t texel, int k) { ret
 __host__ __device__ __forceinline__ double seq_min(double a, double b) { return a < b ? a : b; }
 
 // Image d at frame point (fx, fy): false where it does not cover the point; else its value v (float64 per channel) and, for the
-// feather blend, its weight g.  The anchor enters unwarped: its own bytes, texel (0,0) included.
-template <bool FEATHER>
-__host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_anchor, int fx, int fy, double v[3], double& g) {
+// feather blend, its weight g.  The anchor enters unwarped: its own bytes, texel (0,0) included.  GAIN (the gain rule): v is
+// min(v * gain, 255.0), the product rounded on its own; without GAIN `gain` is not read.
+template <bool FEATHER, bool GAIN = false>
+__host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_anchor, int fx, int fy, double v[3], double& g,
+                                                    double gain = 1.0) {
     const int tx = fx - d.mx, ty = fy - d.my;
     if (!((tx >= 0) & (tx < d.wt) & (ty >= 0) & (ty < d.ht))) return false;
     const size_t bytes = (size_t)d.h * d.w * 3;
@@ -74,20 +76,27 @@ __host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_an
             v[k] = top * gy + bot * fy_;
         }
     }
+    if constexpr (GAIN) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = seq_min(v[k] * gain, 255.0);
+    }
     if constexpr (FEATHER) g = seq_min(seq_min(sx, (double)(d.w - 1) - sx), seq_min(sy, (double)(d.h - 1) - sy)) + 1.0;
     return true;
 }
 
 // One canvas pixel as 0x00BBGGRR.  cand: bit k set = image order[k] may cover the pixel (its rectangle meets the pixel's tile).
-template <bool FEATHER>
-__host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy) {
+// gains: the N gains of the gain rule, read with GAIN only.
+template <bool FEATHER, bool GAIN = false>
+__host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains = nullptr) {
     const int fx = a.ox + cx, fy = a.oy + cy;
     double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
     bool covered = false;
     for (uint64_t m = cand; m; m &= m - 1) {
         const int i = a.order[__builtin_ctzll(m)];
         double v[3], g = 0.0;
-        if (!seq_sample<FEATHER>(a.desc[i], i == a.anchor, fx, fy, v, g)) continue;
+        double gain = 1.0;
+        if constexpr (GAIN) gain = gains[i];
+        if (!seq_sample<FEATHER, GAIN>(a.desc[i], i == a.anchor, fx, fy, v, g, gain)) continue;
         if constexpr (!FEATHER) {       // paste: the first image in `order` that covers the pixel
             uint32_t out = 0u;
 #pragma unroll
@@ -123,8 +132,16 @@ __host__ __device__ __forceinline__ uint64_t seq_tile_mask(const SeqArgs& a, int
 // A block's 256 x 4 tile is tested once against the n rectangles; blockIdx and the descriptor indices are wave-uniform, so the
 // test and the descriptor reads of the pixel loop stay on the scalar side.
 constexpr int SEQ_PX = 4;
-template <bool FEATHER>
-__global__ __launch_bounds__(256) void seq_kernel(const SeqArgs a) {
+// The arguments of one launch: SeqArgs, and with GAIN the N gains behind it (512 B: the arguments stay under 4 KB).
+template <bool GAIN> struct SeqLaunch { SeqArgs a; };
+template <> struct SeqLaunch<true> { SeqArgs a; double gains[RWH_SEQ_MAX_IMAGES]; };
+template <bool GAIN> __host__ __device__ __forceinline__ const double* seq_gains(const SeqLaunch<GAIN>& l) {
+    if constexpr (GAIN) return l.gains; else return nullptr;
+}
+
+template <bool FEATHER, bool GAIN = false>
+__global__ __launch_bounds__(256) void seq_kernel(const SeqLaunch<GAIN> l) {
+    const SeqArgs& a = l.a;
     const int bx0 = blockIdx.x * 64 * SEQ_PX, by0 = a.row_begin + blockIdx.y * 4;
     const uint64_t cand = seq_tile_mask(a, bx0, bx0 + 64 * SEQ_PX, by0, by0 + 4);
     const int cx0 = bx0 + (threadIdx.x & 63) * SEQ_PX;
@@ -133,7 +150,7 @@ __global__ __launch_bounds__(256) void seq_kernel(const SeqArgs a) {
     unsigned char* out = a.dst + ((size_t)cy * a.fw + cx0) * 3;
     uint32_t px[SEQ_PX];
 #pragma unroll
-    for (int j = 0; j < SEQ_PX; ++j) px[j] = cx0 + j < a.fw ? seq_pixel<FEATHER>(a, cand, cx0 + j, cy) : 0u;
+    for (int j = 0; j < SEQ_PX; ++j) px[j] = cx0 + j < a.fw ? seq_pixel<FEATHER, GAIN>(a, cand, cx0 + j, cy, seq_gains(l)) : 0u;
     if (cx0 + SEQ_PX <= a.fw) {
         pk3 w;
         w.a = px[0] | (px[1] << 24);
@@ -190,15 +207,184 @@ static int seq_prepare(const void* const* images, const int32_t* hw, const doubl
     return RWH_OK;
 }
 
-template <bool FEATHER>
-static void seq_host_rows(const SeqArgs& a) {
+// The gains of the gain rule: N values, each finite and > 0.
+static bool seq_gains_ok(const double* gains, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!(isfinite(gains[i]) && gains[i] > 0.0)) return false;
+    return true;
+}
+
+// Lays the n descriptors down at `table` (device), SEQ_PUT per launch.
+static void seq_put_table(const SeqDesc* descs, int n, uint64_t* table, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += SEQ_PUT) {
+        const int cnt = n - i0 < SEQ_PUT ? n - i0 : SEQ_PUT;
+        SeqPut c;
+        memset(&c, 0, sizeof(c));
+        memcpy(c.w, descs + i0, (size_t)cnt * sizeof(SeqDesc));
+        hipLaunchKernelGGL(seq_put_kernel, dim3(1), dim3(256), 0, s, c, table + (size_t)i0 * SEQ_DESC_WORDS, cnt * SEQ_DESC_WORDS);
+    }
+}
+
+template <bool FEATHER, bool GAIN>
+static void seq_launch(const SeqArgs& a, const double* gains, dim3 grid, hipStream_t s) {
+    SeqLaunch<GAIN> l;
+    l.a = a;
+    if constexpr (GAIN) {
+        memset(l.gains, 0, sizeof(l.gains));
+        memcpy(l.gains, gains, (size_t)a.n * sizeof(double));
+    }
+    hipLaunchKernelGGL((seq_kernel<FEATHER, GAIN>), grid, dim3(256), 0, s, l);
+}
+
+template <bool FEATHER, bool GAIN = false>
+static void seq_host_rows(const SeqArgs& a, const double* gains = nullptr) {
     const uint64_t all = a.n == 64 ? ~0ull : (1ull << a.n) - 1;
     for (int cy = a.row_begin; cy < a.row_end; ++cy)
         for (int cx = 0; cx < a.fw; ++cx) {
-            const uint32_t p = seq_pixel<FEATHER>(a, all, cx, cy);
+            const uint32_t p = seq_pixel<FEATHER, GAIN>(a, all, cx, cy, gains);
             unsigned char* out = a.dst + ((size_t)cy * a.fw + cx) * 3;
             out[0] = (unsigned char)p; out[1] = (unsigned char)(p >> 8); out[2] = (unsigned char)(p >> 16);
         }
+}
+
+// ---- the gain rule's overlap statistics (include/rwh.h) ----
+// The images that cover canvas pixel (cx, cy), bit i = image i (cand: bits of image indices), by the sequence rule's Coverage:
+// seq_sample's own test, its taps unused.
+__host__ __device__ __forceinline__ uint64_t seq_cover(const SeqArgs& a, uint64_t cand, int cx, int cy) {
+    const int fx = a.ox + cx, fy = a.oy + cy;
+    uint64_t cov = 0;
+    for (uint64_t m = cand; m; m &= m - 1) {
+        const int i = __builtin_ctzll(m);
+        double v[3], g = 0.0;
+        if (seq_sample<false>(a.desc[i], i == a.anchor, fx, fy, v, g)) cov |= 1ull << i;
+    }
+    return cov;
+}
+
+// L_i of the gain rule: the sum of the three bytes paste would write for image i at a canvas pixel that it covers.
+__host__ __device__ __forceinline__ uint32_t seq_byte_sum(const SeqArgs& a, int i, int cx, int cy) {
+    double v[3], g = 0.0;
+    if (!seq_sample<false>(a.desc[i], i == a.anchor, a.ox + cx, a.oy + cy, v, g)) return 0u;
+    return (uint32_t)(unsigned char)(int)v[0] + (uint32_t)(unsigned char)(int)v[1] + (uint32_t)(unsigned char)(int)v[2];
+}
+
+struct StatArgs {
+    SeqArgs a;                  // order: 0 .. n-1 (candidate bits are image indices); dst, row_begin, row_end unused
+    int stride, nsx, nsy;       // the sample grid: nsx x nsy samples, sample (u, v) is canvas pixel (u * stride, v * stride)
+    unsigned long long* slabs;  // STAT_SLABS slabs of slab_words words, zeroed on the stream before the launch: count [n][n], then sum [n][n]
+    int slab_words;
+};
+// Every block adds its pairs into ONE of STAT_SLABS copies of the two tables (a whole number of 128-byte lines each), and a second
+// kernel sums the copies into the caller's tables: with one copy, the atomics of thousands of blocks queue on the one cache line
+// that holds count[0][0] and sum[0][0] of a two-image strip.
+constexpr int STAT_SLABS = 64;
+__host__ __device__ __forceinline__ int seq_slab_words(int n) { return (2 * n * n + 15) & ~15; }
+
+// The candidates of the samples [u0, u1) x [v0, v1): the images whose rectangles meet the canvas pixels between the first and the
+// last of them.
+__host__ __device__ __forceinline__ uint64_t seq_stat_mask(const StatArgs& s, int u0, int u1, int v0, int v1) {
+    return seq_tile_mask(s.a, u0 * s.stride, (u1 - 1) * s.stride + 1, v0 * s.stride, (v1 - 1) * s.stride + 1);
+}
+
+__device__ __forceinline__ uint32_t seq_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = RWH_WAVE / 2; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// A block takes 256 x 4 samples (64 lanes x 4 consecutive samples, one wave per sample row) and tests their footprint once against
+// the n rectangles.  Pass 1: every lane's coverage masks.  Pass 2, over the candidate pairs (block-uniform, so the loops stay on the
+// scalar side): the lanes' L_i and one wave sum per live pair of (count << 20 | sum), added into 32-bit LDS accumulators of the same
+// packing, indexed by candidate rank -- a block has 1024 samples: count <= 2^10 and sum <= 1024 * 765 < 2^20 -- then one 64-bit
+// integer atomic add per non-zero count and sum per block, into the block's slab.  Integer adds commute: the tables do not depend
+// on the order.
+constexpr int STAT_W = 256, STAT_H = 4;
+__global__ __launch_bounds__(256) void seq_stats_kernel(const StatArgs s) {
+    static_assert(STAT_W * STAT_H * 765 < (1 << 20) && STAT_W * STAT_H < (1 << 12), "count << 20 | sum in 32 bits");
+    __shared__ uint32_t acc[RWH_SEQ_MAX_IMAGES * RWH_SEQ_MAX_IMAGES];
+    __shared__ unsigned char ids[RWH_SEQ_MAX_IMAGES];
+    const SeqArgs& a = s.a;
+    const int u0 = blockIdx.x * STAT_W, v0 = blockIdx.y * STAT_H;
+    const int u1 = u0 + STAT_W < s.nsx ? u0 + STAT_W : s.nsx, v1 = v0 + STAT_H < s.nsy ? v0 + STAT_H : s.nsy;
+    const uint64_t cand = seq_stat_mask(s, u0, u1, v0, v1);
+    const int nc = __builtin_popcountll(cand);
+    if (nc == 0) return;                                   // (block-uniform)
+    for (int t = threadIdx.x; t < nc * nc; t += 256) acc[t] = 0u;
+    if (threadIdx.x < RWH_SEQ_MAX_IMAGES && (cand >> threadIdx.x & 1))
+        ids[__builtin_popcountll(cand & ((1ull << threadIdx.x) - 1))] = (unsigned char)threadIdx.x;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int u = u0 + lane * SEQ_PX, v = v0 + (threadIdx.x >> 6);
+    const int cy = v * s.stride;
+    uint64_t cov[SEQ_PX];
+#pragma unroll
+    for (int k = 0; k < SEQ_PX; ++k) cov[k] = (u + k < s.nsx && v < s.nsy) ? seq_cover(a, cand, (u + k) * s.stride, cy) : 0ull;
+    int ri = 0;
+    for (uint64_t mi = cand; mi; mi &= mi - 1, ++ri) {
+        const int i = __builtin_ctzll(mi);
+        uint32_t L[SEQ_PX];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < SEQ_PX; ++k) {
+            const bool c = cov[k] >> i & 1;
+            L[k] = c ? seq_byte_sum(a, i, (u + k) * s.stride, cy) : 0u;
+            any |= c;
+        }
+        if (!__any(any)) continue;                         // (wave-uniform)
+        int rj = 0;
+        for (uint64_t mj = cand; mj; mj &= mj - 1, ++rj) {
+            const int j = __builtin_ctzll(mj);
+            uint32_t p = 0u;
+#pragma unroll
+            for (int k = 0; k < SEQ_PX; ++k)
+                if ((cov[k] >> i) & (cov[k] >> j) & 1) p += (1u << 20) + L[k];
+            if (!__any(p != 0u)) continue;                 // (wave-uniform: i and j meet at none of the wave's samples)
+            p = seq_wave_sum(p);
+            if (lane == 0 && p) atomicAdd(&acc[ri * nc + rj], p);
+        }
+    }
+    __syncthreads();
+    unsigned long long* slab = s.slabs + (size_t)((blockIdx.y * gridDim.x + blockIdx.x) % STAT_SLABS) * s.slab_words;
+    for (int t = threadIdx.x; t < nc * nc; t += 256) {
+        const uint32_t c = acc[t] >> 20, l = acc[t] & 0xfffffu;
+        if (!c) continue;
+        const size_t at = (size_t)ids[t / nc] * a.n + ids[t % nc];
+        atomicAdd(&slab[at], (unsigned long long)c);
+        if (l) atomicAdd(&slab[(size_t)a.n * a.n + at], (unsigned long long)l);
+    }
+}
+
+// count and sum (nn words each) = the sum of the slabs: writes both tables whole.
+__global__ __launch_bounds__(256) void seq_stats_sum_kernel(const unsigned long long* slabs, int slab_words, int nn,
+                                                            unsigned long long* count, unsigned long long* sum) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= 2 * nn) return;
+    unsigned long long total = 0;
+    for (int r = 0; r < STAT_SLABS; ++r) total += slabs[(size_t)r * slab_words + t];
+    if (t < nn) count[t] = total; else sum[t - nn] = total;
+}
+
+// the descriptor table at the head of the statistics workspace, a whole number of 128-byte lines
+static int64_t seq_stat_table_bytes(int n) { return ((int64_t)n * (int64_t)sizeof(SeqDesc) + 127) & ~(int64_t)127; }
+
+// What both statistics entry points check, and their arguments: rwh_stitch_sequence's checks (with the index order, no canvas
+// buffer and all rows) plus the stride range.
+static int seq_stat_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
+                            int canvas_h, int canvas_w, int origin_x, int origin_y, int stride, uint64_t* count, uint64_t* sum,
+                            SeqDesc* descs, StatArgs& s) {
+    if (!count || !sum || stride < 1 || stride > 255 || n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;
+    int32_t order[RWH_SEQ_MAX_IMAGES];
+    for (int k = 0; k < n; ++k) order[k] = k;
+    const int st = seq_prepare(images, hw, inv_g, rects, n, anchor, order, RWH_SEQ_FEATHER, count, canvas_h, canvas_w, origin_x, origin_y,
+                               0, canvas_h, descs, s.a);
+    if (st != RWH_OK) return st;
+    s.a.dst = nullptr;
+    s.stride = stride;
+    s.nsx = (canvas_w + stride - 1) / stride;
+    s.nsy = (canvas_h + stride - 1) / stride;
+    s.slabs = nullptr;
+    s.slab_words = seq_slab_words(n);
+    return RWH_OK;
 }
 
 }  // namespace rwh
@@ -208,10 +394,10 @@ extern "C" int64_t rwh_stitch_sequence_workspace_bytes(int n) {
     return (int64_t)n * (int64_t)sizeof(rwh::SeqDesc);
 }
 
-extern "C" int rwh_stitch_sequence(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
-                                   int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
-                                   int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
-                                   void* stream) {
+extern "C" int rwh_stitch_sequence_ex(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                      int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
+                                      int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                      void* stream, const double* gains) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SeqArgs a;
@@ -219,33 +405,167 @@ extern "C" int rwh_stitch_sequence(const void* const* d_images, const int32_t* h
                                row_begin, row_end, descs, a);
     if (st != RWH_OK) return st;
     if (!d_workspace || workspace_bytes < rwh_stitch_sequence_workspace_bytes(n) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
+    if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
     if (row_begin == row_end) return RWH_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint64_t* table = static_cast<uint64_t*>(d_workspace);
-    for (int i0 = 0; i0 < n; i0 += SEQ_PUT) {
-        const int cnt = n - i0 < SEQ_PUT ? n - i0 : SEQ_PUT;
-        SeqPut c;
-        memset(&c, 0, sizeof(c));
-        memcpy(c.w, descs + i0, (size_t)cnt * sizeof(SeqDesc));
-        hipLaunchKernelGGL(seq_put_kernel, dim3(1), dim3(256), 0, s, c, table + (size_t)i0 * SEQ_DESC_WORDS, cnt * SEQ_DESC_WORDS);
-    }
+    seq_put_table(descs, n, table, s);
     a.desc = reinterpret_cast<const SeqDesc*>(table);
-    const dim3 grid((canvas_w + 64 * SEQ_PX - 1) / (64 * SEQ_PX), (row_end - row_begin + 3) / 4), block(256);
-    if (blend == RWH_SEQ_FEATHER) hipLaunchKernelGGL(seq_kernel<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(seq_kernel<false>, grid, block, 0, s, a);
+    const dim3 grid((canvas_w + 64 * SEQ_PX - 1) / (64 * SEQ_PX), (row_end - row_begin + 3) / 4);
+    if (gains) {
+        if (blend == RWH_SEQ_FEATHER) seq_launch<true, true>(a, gains, grid, s);
+        else seq_launch<false, true>(a, gains, grid, s);
+    } else {
+        if (blend == RWH_SEQ_FEATHER) seq_launch<true, false>(a, nullptr, grid, s);
+        else seq_launch<false, false>(a, nullptr, grid, s);
+    }
     return check_launch();
 }
 
-extern "C" int rwh_host_stitch_sequence(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
-                                        int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
-                                        int origin_x, int origin_y, int row_begin, int row_end) {
+extern "C" int rwh_stitch_sequence(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                   int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
+                                   int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                   void* stream) {
+    return rwh_stitch_sequence_ex(d_images, hw, inv_g, rects, n, anchor, order, blend, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
+                                  row_begin, row_end, d_workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int rwh_host_stitch_sequence_ex(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                           int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
+                                           int origin_x, int origin_y, int row_begin, int row_end, const double* gains) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SeqArgs a;
     const int st = seq_prepare(images, hw, inv_g, rects, n, anchor, order, blend, canvas, canvas_h, canvas_w, origin_x, origin_y,
                                row_begin, row_end, descs, a);
     if (st != RWH_OK) return st;
-    if (blend == RWH_SEQ_FEATHER) seq_host_rows<true>(a);
-    else seq_host_rows<false>(a);
+    if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
+    if (gains) {
+        if (blend == RWH_SEQ_FEATHER) seq_host_rows<true, true>(a, gains);
+        else seq_host_rows<false, true>(a, gains);
+    } else {
+        if (blend == RWH_SEQ_FEATHER) seq_host_rows<true>(a);
+        else seq_host_rows<false>(a);
+    }
+    return RWH_OK;
+}
+
+extern "C" int rwh_host_stitch_sequence(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                        int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
+                                        int origin_x, int origin_y, int row_begin, int row_end) {
+    return rwh_host_stitch_sequence_ex(images, hw, inv_g, rects, n, anchor, order, blend, canvas, canvas_h, canvas_w, origin_x, origin_y,
+                                       row_begin, row_end, nullptr);
+}
+
+extern "C" int64_t rwh_sequence_overlap_stats_workspace_bytes(int n, int canvas_h, int canvas_w, int stride) {
+    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || stride < 1 || stride > 255) return RWH_E_INVALID;
+    if (canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535 || (int64_t)canvas_h * canvas_w * 3 > INT32_MAX) return RWH_E_INVALID;
+    return rwh::seq_stat_table_bytes(n) + (int64_t)rwh::STAT_SLABS * rwh::seq_slab_words(n) * (int64_t)sizeof(uint64_t);
+}
+
+extern "C" int rwh_sequence_overlap_stats(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                          int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
+                                          uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    using namespace rwh;
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    StatArgs a;
+    const int st = seq_stat_prepare(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, d_count, d_sum,
+                                    descs, a);
+    if (st != RWH_OK) return st;
+    if (!d_workspace || workspace_bytes < rwh_sequence_overlap_stats_workspace_bytes(n, canvas_h, canvas_w, stride) ||
+        ((uintptr_t)d_workspace & 7u) || ((uintptr_t)d_count & 7u) || ((uintptr_t)d_sum & 7u)) return RWH_E_INVALID;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint64_t* table = static_cast<uint64_t*>(d_workspace);
+    a.slabs = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_workspace) + seq_stat_table_bytes(n));
+    if (hipMemsetAsync(a.slabs, 0, (size_t)STAT_SLABS * a.slab_words * sizeof(uint64_t), s) != hipSuccess) return RWH_E_LAUNCH;
+    seq_put_table(descs, n, table, s);
+    a.a.desc = reinterpret_cast<const SeqDesc*>(table);
+    const dim3 grid((a.nsx + STAT_W - 1) / STAT_W, (a.nsy + STAT_H - 1) / STAT_H);
+    hipLaunchKernelGGL(seq_stats_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(seq_stats_sum_kernel, dim3((2 * n * n + 255) / 256), dim3(256), 0, s, a.slabs, a.slab_words, n * n,
+                       reinterpret_cast<unsigned long long*>(d_count), reinterpret_cast<unsigned long long*>(d_sum));
+    return check_launch();
+}
+
+extern "C" int rwh_host_sequence_overlap_stats(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                               int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
+                                               uint64_t* count, uint64_t* sum) {
+    using namespace rwh;
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    StatArgs a;
+    const int st = seq_stat_prepare(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, count, sum, descs, a);
+    if (st != RWH_OK) return st;
+    uint64_t* cnt = count;
+    uint64_t* sm = sum;
+    memset(cnt, 0, (size_t)n * n * sizeof(uint64_t));
+    memset(sm, 0, (size_t)n * n * sizeof(uint64_t));
+    const uint64_t all = n == 64 ? ~0ull : (1ull << n) - 1;
+    for (int v = 0; v < a.nsy; ++v)
+        for (int u = 0; u < a.nsx; ++u) {
+            const int cx = u * stride, cy = v * stride;
+            const uint64_t cov = seq_cover(a.a, all, cx, cy);
+            for (uint64_t mi = cov; mi; mi &= mi - 1) {
+                const int i = __builtin_ctzll(mi);
+                const uint64_t l = seq_byte_sum(a.a, i, cx, cy);
+                for (uint64_t mj = cov; mj; mj &= mj - 1) {
+                    const int j = __builtin_ctzll(mj);
+                    cnt[(size_t)i * n + j] += 1;
+                    sm[(size_t)i * n + j] += l;
+                }
+            }
+        }
+    return RWH_OK;
+}
+
+// The gains of the gain rule from the two tables: A and b built in the rule's order, the square-root-free Cholesky
+// A = L D L^T on the lower triangle, forward and back substitution.  Host only, float64, no LAPACK.
+extern "C" int rwh_host_sequence_gains(const uint64_t* count, const uint64_t* sum, int n, double sigma_n, double sigma_g, double* gains) {
+    if (!count || !sum || !gains || n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;
+    if (!(isfinite(sigma_n) && sigma_n > 0.0 && isfinite(sigma_g) && sigma_g > 0.0)) return RWH_E_INVALID;
+    const uint64_t* cnt = count;
+    const uint64_t* sm = sum;
+    const double alpha = 1.0 / (sigma_n * sigma_n), beta = 1.0 / (sigma_g * sigma_g);
+    static_assert(RWH_SEQ_MAX_IMAGES == 64, "A, b and y live on the stack");
+    double A[64 * 64], b[64], y[64];
+    memset(A, 0, sizeof(A));
+    memset(b, 0, sizeof(b));
+    auto N = [&](int i, int j) { return (double)cnt[(size_t)i * n + j]; };
+    auto I = [&](int i, int j) { return cnt[(size_t)i * n + j] ? (double)sm[(size_t)i * n + j] / (3.0 * N(i, j)) : 0.0; };
+    for (int i = 0; i < n; ++i) {
+        if (cnt[(size_t)i * n + i] == 0) { A[i * n + i] = 1.0; b[i] = 1.0; continue; }
+        for (int j = 0; j < n; ++j) {
+            A[i * n + i] += beta * N(i, j);
+            b[i] += beta * N(i, j);
+            if (j != i) {
+                A[i * n + i] += 2.0 * alpha * I(i, j) * I(i, j) * N(i, j);
+                A[i * n + j] -= 2.0 * alpha * I(i, j) * I(j, i) * N(i, j);
+            }
+        }
+    }
+    // A = L D L^T, L unit lower (kept below A's diagonal), D on the diagonal: a row that meets nobody (zeros off its diagonal,
+    // b_i == A_ii) comes out as b_i / A_ii = 1.0 exactly.
+    for (int j = 0; j < n; ++j) {
+        double d = A[j * n + j];
+        for (int k = 0; k < j; ++k) d -= A[j * n + k] * A[j * n + k] * A[k * n + k];
+        if (!(d > 0.0) || !isfinite(d)) return RWH_E_INVALID;
+        A[j * n + j] = d;
+        for (int i = j + 1; i < n; ++i) {
+            double t = A[i * n + j];
+            for (int k = 0; k < j; ++k) t -= A[i * n + k] * A[j * n + k] * A[k * n + k];
+            A[i * n + j] = t / d;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        double t = b[i];
+        for (int k = 0; k < i; ++k) t -= A[i * n + k] * y[k];
+        y[i] = t;
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double t = y[i] / A[i * n + i];
+        for (int k = i + 1; k < n; ++k) t -= A[k * n + i] * gains[k];
+        gains[i] = t;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!isfinite(gains[i])) return RWH_E_INVALID;
     return RWH_OK;
 }

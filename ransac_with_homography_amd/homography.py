@@ -54,7 +54,7 @@ __all__ = [
     "calc_corresp", "calc_correspLinear", "calc_correspCollective", "calc_correspLinearCollective",
     "calcHomography", "calcHomographyLinear", "calcH", "nearestNeighbor", "bilinear", "convertfunc",
     "wrapPerspective", "wrapPerspectiveScan", "perspectiveTransform", "transformImage", "transformImageH",
-    "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence",
+    "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence", "sequence_gains",
 ]
 
 
@@ -797,7 +797,71 @@ def sequence_plan(shapes, Hs, anchor=0):
     return Gs, rects, origin, size, order
 
 
-def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None):
+def _sequence_inputs(who, images, Hs, Gs, anchor):
+    """What stitchSequence and sequence_gains check of their images and geometry, before any GPU use: -> (rects, origin, size,
+    default order, inv_g float64 [N, 3, 3])."""
+    n = len(images)
+    _check_count(n, anchor)
+    if (Hs is None) == (Gs is None):
+        raise ValueError("%s: exactly one of Hs and Gs" % who)
+    for i, img in enumerate(images):
+        if len(img.shape) != 3 or img.shape[2] != 3 or str(img.dtype).replace("torch.", "") != "uint8":
+            raise NotImplementedError("%s: image %d is %s %s; uint8 [h, w, 3] images are taken" % (who, i, img.dtype, tuple(img.shape)))
+    shapes = [tuple(int(v) for v in img.shape) for img in images]
+    if Hs is not None:
+        Gs, rects, origin, size, default = sequence_plan(shapes, Hs, anchor)
+    else:
+        Gs = np.array([np.asarray(G, dtype=np.float64) for G in Gs])
+        if Gs.shape != (n, 3, 3) or not np.array_equal(Gs[anchor], np.eye(3)):
+            raise ValueError("%s: Gs takes %d 3 x 3 matrices with the identity at the anchor" % (who, n))
+        rects, origin, size, default = _sequence_canvas(shapes, Gs, anchor)
+    inv_g = np.stack([np.eye(3) if i == anchor else np.linalg.inv(Gs[i]) for i in range(n)])
+    return rects, origin, size, default, inv_g
+
+
+def _sequence_upload(images):
+    dev = _lib.require_gpu()
+    return [img.to(dev).contiguous() if _is_tensor(img) else _xfer.to_device(img, dev) for img in images]
+
+
+def _check_gain_options(who, stride, sigma_n, sigma_g):
+    if not (isinstance(stride, (int, np.integer)) and not isinstance(stride, bool) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
+        raise ValueError("%s: stride %r; an integer of 1 .. %d" % (who, stride, _lib.RWH_SEQ_MAX_STRIDE))
+    for name, v in (("sigma_n", sigma_n), ("sigma_g", sigma_g)):
+        if not (isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v) and v > 0):
+            raise ValueError("%s: %s = %r; finite and > 0" % (who, name, v))
+
+
+def _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info):
+    """One statistics launch, one download of the two n x n tables, one call of rwh_host_sequence_gains -> float64 [N]."""
+    n = len(on_dev)
+    tabs = kernels.sequence_overlap_tables(on_dev, inv_g, rects, anchor, origin, size, int(stride)).cpu().numpy().view(np.uint64)
+    gains = np.empty(n, dtype=np.float64)
+    status = _lib.load().rwh_host_sequence_gains(tabs[0].ctypes.data, tabs[1].ctypes.data, n, float(sigma_n), float(sigma_g), gains.ctypes.data)
+    if status == _lib.RWH_E_INVALID:
+        raise ValueError("sequence_gains: the gain system has a non-positive pivot or a non-finite solution")
+    _lib.check(status, "rwh_host_sequence_gains")
+    if info is not None:
+        info["count"], info["sum"] = tabs[0].copy(), tabs[1].copy()
+    return gains
+
+
+def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, sigma_g=0.1, info=None):
+    """One exposure gain per image of a sequence (the gain rule of include/rwh.h; Brown & Lowe 2007, section 6): the overlap
+    statistics of the images, warped as `stitchSequence` warps them, are reduced on the GPU in one pass over every stride-th canvas
+    pixel each way (`rwh_sequence_overlap_stats`), the two N x N integer tables come down in one copy, and the N x N system is
+    solved on the host (`rwh_host_sequence_gains`).  -> float64 [N]; `stitchSequence(..., gains=...)` applies them.
+
+    images, Hs, Gs, anchor: as `stitchSequence`'s, and refused as there.  sigma_n (10.0): the standard deviation of the intensity
+    error, on the 0 .. 255 scale; sigma_g (0.1): that of the gain about 1.  stride=4 is a convention -- a sixteenth of the samples
+    moves the gains of the test scenes in the third decimal -- not a measured optimum.  `info`: optional dict, receives "count" and
+    "sum" (uint64 [N, N]).  ValueError: a stride outside 1 .. 255, a sigma that is not finite and > 0, before the GPU is touched."""
+    rects, origin, size, _, inv_g = _sequence_inputs("sequence_gains", images, Hs, Gs, anchor)
+    _check_gain_options("sequence_gains", stride, sigma_n, sigma_g)
+    return _gains_on_device(_sequence_upload(images), inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info)
+
+
+def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None, gains=None, info=None):
     """N images into one panorama in ONE pass over the canvas (`rwh_stitch_sequence`): every image is warped once into the
     anchor's frame and every canvas pixel written once.  The reference has no counterpart -- its stitchPanorama takes two images,
     and folding it over a list resamples the growing canvas once per image; this is held to the sequence rule stated in
@@ -807,36 +871,34 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     images: N (1 .. 64) uint8 [h, w, 3] numpy arrays or tensors, sizes may differ; exactly one of Hs (N - 1 pairwise homographies,
     chained by `sequence_plan`) and Gs (N maps into the anchor's frame, used as given; Gs[anchor] must be the identity).
     blending: False -- the first image in `order` (default: the anchor, then the nearest) that covers a pixel gives it;
-    "feather" -- every covering image, weighted by its distance to its own border (`order` is ignored).  numpy arrays in -> a
+    "feather" -- every covering image, weighted by its distance to its own border (`order` is ignored).  gains: None -- the images
+    as they are; N exposure gains (the gain rule of include/rwh.h: every sample value v of image i enters as min(v * g_i, 255.0));
+    "auto" -- `sequence_gains` with its defaults on the same images and geometry, the images uploaded once.  `info`: optional dict,
+    receives "gains" (the gains used, float64 [N], or None).  numpy arrays in -> a
     numpy canvas; any tensor in -> a device tensor and no host copy of pixels.  The caller's images are never written.
-    ValueError: what `sequence_plan` refuses, an `order` that is not a permutation, another `blending`;
-    NotImplementedError: images that are not uint8 [h, w, 3]."""
+    ValueError: what `sequence_plan` refuses, an `order` that is not a permutation, another `blending`, gains of another length,
+    not finite or <= 0, or another string; NotImplementedError: images that are not uint8 [h, w, 3]."""
     n = len(images)
     _check_count(n, anchor)
-    if (Hs is None) == (Gs is None):
-        raise ValueError("stitchSequence: exactly one of Hs and Gs")
     if blending is not False and blending != "feather" and blending:
         raise ValueError("stitchSequence: blending=%r; False or 'feather'" % (blending,))
     blend = _lib.RWH_SEQ_FEATHER if blending == "feather" else _lib.RWH_SEQ_PASTE
-    for i, img in enumerate(images):
-        if len(img.shape) != 3 or img.shape[2] != 3 or str(img.dtype).replace("torch.", "") != "uint8":
-            raise NotImplementedError("stitchSequence: image %d is %s %s; uint8 [h, w, 3] images are taken" % (i, img.dtype, tuple(img.shape)))
-    shapes = [tuple(int(v) for v in img.shape) for img in images]
-    if Hs is not None:
-        Gs, rects, origin, size, default = sequence_plan(shapes, Hs, anchor)
-    else:
-        Gs = np.array([np.asarray(G, dtype=np.float64) for G in Gs])
-        if Gs.shape != (n, 3, 3) or not np.array_equal(Gs[anchor], np.eye(3)):
-            raise ValueError("stitchSequence: Gs takes %d 3 x 3 matrices with the identity at the anchor" % n)
-        rects, origin, size, default = _sequence_canvas(shapes, Gs, anchor)
+    rects, origin, size, default, inv_g = _sequence_inputs("stitchSequence", images, Hs, Gs, anchor)
     order = default if order is None else [int(v) for v in order]
     if sorted(order) != list(range(n)):
         raise ValueError("stitchSequence: order %r is not a permutation of 0 .. %d" % (order, n - 1))
-    inv_g = np.stack([np.eye(3) if i == anchor else np.linalg.inv(Gs[i]) for i in range(n)])
-    dev = _lib.require_gpu()
+    if isinstance(gains, str):
+        if gains != "auto":
+            raise ValueError("stitchSequence: gains=%r; None, N gains or 'auto'" % (gains,))
+    elif gains is not None:
+        gains = kernels.sequence_gains_array(gains, n, "stitchSequence")
     tens = any(_is_tensor(img) for img in images)
-    on_dev = [img.to(dev).contiguous() if _is_tensor(img) else _xfer.to_device(img, dev) for img in images]
-    out = kernels.stitch_sequence(on_dev, inv_g, rects, anchor, order, blend, origin, size)
+    on_dev = _sequence_upload(images)
+    if isinstance(gains, str):
+        gains = _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, 4, 10.0, 0.1, None)
+    if info is not None:
+        info["gains"] = gains
+    out = kernels.stitch_sequence(on_dev, inv_g, rects, anchor, order, blend, origin, size, gains=gains)
     return out if tens else _xfer.to_host(out)
 
 

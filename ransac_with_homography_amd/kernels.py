@@ -639,12 +639,61 @@ def sequence_tables(shapes, inv_g, rects, order):
             np.ascontiguousarray(order, dtype=np.int32).reshape(-1))
 
 
-def stitch_sequence(images, inv_g, rects, anchor, order, blend, origin, canvas_hw, rows=None, out=None):
+def sequence_gains_array(gains, n, who="stitch_sequence"):
+    """`gains` of the gain rule as a contiguous float64 [n] array; ValueError for another length, a non-finite value or one <= 0."""
+    g = np.ascontiguousarray(gains.detach().cpu().numpy() if isinstance(gains, torch.Tensor) else gains, dtype=np.float64)
+    if g.shape != (n,) or not (np.isfinite(g).all() and (g > 0).all()):
+        raise ValueError("%s: gains takes %d finite values > 0, got %r" % (who, n, g.tolist() if g.size <= 64 else g.shape))
+    return g
+
+
+def sequence_overlap_tables(images, inv_g, rects, anchor, origin, canvas_hw, stride):
+    """`sequence_overlap_stats` with both tables in ONE int64 [2, n, n] tensor (count, sum): one copy brings them down."""
+    lib = _lib.load()
+    _dev_check(*images)
+    n = len(images)
+    for t in images:
+        assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
+    fh, fw = (int(v) for v in canvas_hw)
+    if not (1 <= n <= SEQ_MAX_IMAGES) or len(rects) != n or len(inv_g) != n:
+        raise ValueError("sequence_overlap_stats: %d images (1 .. %d), %d rectangles, %d matrices" % (n, SEQ_MAX_IMAGES, len(rects), len(inv_g)))
+    if not (isinstance(stride, (int, np.integer)) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
+        raise ValueError("sequence_overlap_stats: stride %r; 1 .. %d" % (stride, _lib.RWH_SEQ_MAX_STRIDE))
+    if not (1 <= fh <= 65535 and 1 <= fw <= 65535 and fh * fw * 3 <= 2 ** 31 - 1):
+        raise ValueError("sequence_overlap_stats: a %d x %d canvas; sides of 1 .. 65535 and at most 2^31 - 1 bytes" % (fh, fw))
+    hw, ig, rc, _ = sequence_tables([t.shape for t in images], inv_g, rects, list(range(n)))
+    ptrs = np.array([t.data_ptr() for t in images], dtype=np.uint64)
+    dev = images[0].device
+    tabs = torch.empty((2, n, n), dtype=torch.int64, device=dev)
+    ws = torch.empty((int(lib.rwh_sequence_overlap_stats_workspace_bytes(n, fh, fw, int(stride))) // 8,), dtype=torch.int64, device=dev)
+    status = lib.rwh_sequence_overlap_stats(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), fh, fw,
+                                            int(origin[0]), int(origin[1]), int(stride), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(ws),
+                                            ws.numel() * 8, _lib.stream_ptr())
+    if status == _lib.RWH_E_INVALID:
+        raise ValueError("sequence_overlap_stats: the library refused the arguments (include/rwh.h, rwh_sequence_overlap_stats: anchor, "
+                         "rectangles on the canvas, finite inv(G), stride)")
+    check(status, "rwh_sequence_overlap_stats")
+    return tabs
+
+
+def sequence_overlap_stats(images, inv_g, rects, anchor, origin, canvas_hw, stride):
+    """Launch the overlap statistics of the gain rule (rwh_sequence_overlap_stats; include/rwh.h): images, inv_g, rects, anchor,
+    origin, canvas_hw as `stitch_sequence`'s; stride: 1 .. 255, every stride-th canvas pixel each way is a sample ->
+    (count, sum), int64 [n, n] GPU tensors (the library's uint64 tables: count[i][j] samples where i and j both cover, sum[i][j]
+    the byte sums of i there), on torch's current stream.  What the library refuses (RWH_E_INVALID) raises ValueError."""
+    tabs = sequence_overlap_tables(images, inv_g, rects, anchor, origin, canvas_hw, stride)
+    return tabs[0], tabs[1]
+
+
+def stitch_sequence(images, inv_g, rects, anchor, order, blend, origin, canvas_hw, rows=None, out=None, gains=None):
     """Launch the sequence compositor (rwh_stitch_sequence; the sequence rule of include/rwh.h): images: n [h, w, 3] uint8 GPU
     tensors; inv_g: n inv(G_i); rects: n (mx, my, wt, ht); order: a permutation of 0 .. n-1; blend: RWH_SEQ_PASTE / RWH_SEQ_FEATHER;
     origin: (ox, oy) -> canvas [fh, fw, 3] uint8, on torch's current stream.  rows=(r0, r1): only those canvas rows, into `out`
-    (the whole canvas tensor) when given.  What the library refuses (RWH_E_INVALID) raises ValueError."""
+    (the whole canvas tensor) when given.  gains: None, or n gains of the gain rule (rwh_stitch_sequence_ex: every sample value v of
+    image i enters as min(v * gains[i], 255.0)).  What the library refuses (RWH_E_INVALID) raises ValueError."""
     lib = _lib.load()
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images))
     _dev_check(*images)
     n = len(images)
     for t in images:
@@ -663,9 +712,9 @@ def stitch_sequence(images, inv_g, rects, anchor, order, blend, origin, canvas_h
     hw, ig, rc, od = sequence_tables([t.shape for t in images], inv_g, rects, order)
     ptrs = np.array([t.data_ptr() for t in images], dtype=np.uint64)
     ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_sequence(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), od.ctypes.data,
-                                     int(blend), _ptr(out), fh, fw, int(origin[0]), int(origin[1]), r0, r1, _ptr(ws),
-                                     ws.numel() * 8, _lib.stream_ptr())
+    args = (ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), od.ctypes.data, int(blend), _ptr(out), fh, fw,
+            int(origin[0]), int(origin[1]), r0, r1, _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
+    status = lib.rwh_stitch_sequence(*args) if gains is None else lib.rwh_stitch_sequence_ex(*args, gains.ctypes.data)
     if status == _lib.RWH_E_INVALID:
         raise ValueError("stitch_sequence: the library refused the arguments (include/rwh.h, rwh_stitch_sequence: order, anchor, "
                          "rectangles on the canvas, finite inv(G), row range)")

@@ -47,7 +47,7 @@ import numpy as np
 
 from . import _lapack, _lib, kernels
 from .homography import (_pair_rows, calcHomography, calcHomographyLinear, cylindericlMap,  # noqa: F401
-                         sequence_plan, stitchPanorama, stitchSequence)
+                         sequence_gains, sequence_plan, stitchPanorama, stitchSequence)
 
 # Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
 # in csrc/rwh_settle.h.  RESCORE_MARGIN caps the margin of the 'backward' / 'reproj' rule: an unflagged K1 count moves by <= 2
@@ -1164,7 +1164,7 @@ def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blen
     return stitchPanorama(queryImg, trainImg, H=H, blending=blending, blendrate=blendrate)
 
 
-def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, blending=False, features=None, info=None):
+def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, blending=False, features=None, info=None, gains=None):
     """Pixels -> panorama for a SEQUENCE of N overlapping images (images[i+1] overlaps images[i]), every stage batched: one
     `extract_batch` over the N images, one `match_batch` over the N - 1 adjacent pairs, one `run_batch(refit="device")`, one download
     of the [N - 1, 3, 3] homographies -- the only geometry that visits the host, because the canvas must be allocated -- and one
@@ -1172,14 +1172,20 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     stitches two images per call (ransac.py:235-283); this goes beyond it, under the rules stated for each stage in include/rwh.h.
 
     th, d, k, ransacMet, seed: as `run_batch`'s (device sampling, the float64 device refit: a NON-PARITY mode);
-    features: a dict of `extract_batch`'s keyword arguments; anchor, blending: as `stitchSequence`'s.  numpy arrays in -> a numpy
-    canvas, tensors in -> a device tensor.  `info`: optional dict, receives "Hs" (float64 [N - 1, 3, 3], Hs[i] maps image i+1
-    into image i), "Gs", "origin" ((ox, oy) of the canvas in the anchor's frame), "sizes" (matches per pair) and "inliers"
-    (per pair).  ValueError: a pair without a homography (too few matches or inliers, a singular refit), naming the pair and its
+    features: a dict of `extract_batch`'s keyword arguments; anchor, blending, gains: as `stitchSequence`'s (gains="auto": exposure
+    gains from the overlaps, `sequence_gains` with its defaults).  numpy arrays in -> a numpy canvas, tensors in -> a device
+    tensor.  `info`: optional dict, receives "Hs" (float64 [N - 1, 3, 3], Hs[i] maps image i+1 into image i), "Gs", "origin"
+    ((ox, oy) of the canvas in the anchor's frame), "sizes" (matches per pair), "inliers" (per pair) and "gains" (the gains used,
+    float64 [N], or None).  ValueError: a pair without a homography (too few matches or inliers, a singular refit), naming the pair and its
     match count; whatever `stitchSequence` refuses."""
     n = len(images)
     if not 1 <= n <= _lib.RWH_SEQ_MAX_IMAGES:
         raise ValueError("stitch_sequence: %d images; 1 .. %d are taken" % (n, _lib.RWH_SEQ_MAX_IMAGES))
+    if isinstance(gains, str):
+        if gains != "auto":
+            raise ValueError("stitch_sequence: gains=%r; None, N gains or 'auto'" % (gains,))
+    elif gains is not None:
+        gains = kernels.sequence_gains_array(gains, n, "stitch_sequence")
     Hs, sizes, inliers = np.zeros((0, 3, 3)), [], []
     if n > 1:
         feats = extract_batch(images, **(features or {}))
@@ -1197,4 +1203,8 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     Gs, _, origin, _, _ = sequence_plan(shapes, Hs, anchor)
     if info is not None:
         info["Hs"], info["Gs"], info["origin"], info["sizes"], info["inliers"] = Hs, Gs, origin, sizes, inliers
-    return stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending)
+    used = {}
+    out = stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending, gains=gains, info=used)
+    if info is not None:
+        info["gains"] = used["gains"]
+    return out

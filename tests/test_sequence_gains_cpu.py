@@ -1,0 +1,321 @@
+"""The gain rule without a GPU: the host twins (rwh_host_sequence_overlap_stats, rwh_host_sequence_gains,
+rwh_host_stitch_sequence_ex) against the numpy restatement of tests/gain_cases.py, the structure of the tables, the properties of
+the gains, and every refusal at the C and the Python level.  Tables and canvases are compared exactly; gains by the backward-error
+bound of a Cholesky solve."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import gain_cases as gc
+import sequence_cases as sc
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from ransac_with_homography_amd import _lib
+    return _lib.load()
+
+
+def hstats(lib, *a, **k):
+    st, count, total = gc.host_stats(lib, *a, **k)
+    assert st == 0
+    return count, total
+
+
+def hgains(lib, *a, **k):
+    st, g = gc.host_gains(lib, *a, **k)
+    assert st == 0
+    return g
+
+
+def twin_ex(lib, *a, **k):
+    st, can = gc.host_twin_ex(lib, *a, **k)
+    assert st == 0
+    return can
+
+
+CASES = sc.general_cases()
+STATS_INPUTS = [(c[0], c[1], c[2], c[3]) for c in CASES] + [("strip64",) + sc.translated_strip(64) + (0,), ("forty",) + gc.forty_in_one_tile() + (0,)]
+
+
+@pytest.fixture(scope="module")
+def restated():
+    """The numpy planes of every statistics input, computed once: name -> (cover, L)."""
+    return {name: gc.planes(images, Gs, anchor)[3:] for name, images, Gs, anchor in STATS_INPUTS}
+
+
+def strided(cover, L, stride):
+    cover, L = cover[:, ::stride, ::stride], L[:, ::stride, ::stride]
+    n = len(cover)
+    count, total = np.zeros((n, n), dtype=np.uint64), np.zeros((n, n), dtype=np.uint64)
+    for i in range(n):
+        both = cover[i][None] & cover                          # [n, h, w]
+        count[i] = both.sum(axis=(1, 2))
+        total[i] = (both * L[i][None]).sum(axis=(1, 2))
+    return count, total
+
+
+# ---- statistics ----
+@pytest.mark.parametrize("stride", [1, 3, 7])
+@pytest.mark.parametrize("case", STATS_INPUTS, ids=[c[0] for c in STATS_INPUTS])
+def test_host_stats_are_the_restatement(lib, restated, case, stride):
+    name, images, Gs, anchor = case
+    before = [im.copy() for im in images]
+    count, total = hstats(lib, images, Gs, anchor, stride)
+    want_count, want_total = strided(*restated[name], stride)
+    assert count.dtype == np.uint64 and np.array_equal(count, want_count) and np.array_equal(total, want_total)
+    assert all(np.array_equal(a, b) for a, b in zip(images, before))         # the images are never written
+    assert count.any()
+
+
+def test_the_two_restatements_agree():
+    """gain_cases.stats (pair by pair) and this file's vectorised form of it."""
+    _, images, Gs, anchor, _ = CASES[4]
+    for stride in (1, 3):
+        a = gc.stats(images, Gs, anchor, stride)
+        b = strided(*gc.planes(images, Gs, anchor)[3:], stride)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+def test_structure_of_the_tables(lib):
+    images, Gs = sc.translated_strip(64)
+    rects = sc.rectangles([im.shape for im in images], Gs, 0)
+    for stride in (1, 3):
+        count, total = hstats(lib, images, Gs, 0, stride)
+        _, _, _, cover, _ = gc.planes(images, Gs, 0)
+        assert np.array_equal(count, count.T) and not np.array_equal(total, total.T)
+        assert np.array_equal(np.diag(count), cover[:, ::stride, ::stride].sum(axis=(1, 2)).astype(np.uint64))
+        disjoint = 0
+        for i in range(64):
+            for j in range(64):
+                a, b = rects[i], rects[j]
+                if a[0] + a[2] <= b[0] or b[0] + b[2] <= a[0] or a[1] + a[3] <= b[1] or b[1] + b[3] <= a[1]:
+                    assert count[i, j] == 0 and total[i, j] == 0
+                    disjoint += 1
+        assert disjoint > 3000 and (count > 0).sum() > 64
+        assert (total <= count * np.uint64(765)).all()
+
+
+def test_an_image_between_the_samples_gets_gain_one(lib):
+    images, Gs = gc.between_samples()
+    count, total = hstats(lib, images, Gs, 0, 7)
+    assert count[1, 1] == 0 and count[0, 0] == 4 and not count[1].any() and not count[:, 1].any() and not total[1].any()
+    assert hstats(lib, images, Gs, 0, 1)[0][1, 1] == 4                         # at stride 1 it is covered: 2 x 2 pixels
+    g = hgains(lib, count, total)
+    assert g[1] == 1.0 and g[0] == 1.0                                          # the anchor meets nobody either
+
+
+# ---- gains ----
+def test_gains_solve_the_restated_system(lib):
+    for name, images, Gs, anchor in STATS_INPUTS:
+        for stride in (1, 3):
+            count, total = hstats(lib, images, Gs, anchor, stride)
+            A, b, I = gc.system(count, total)
+            g = hgains(lib, count, total)
+            res, bound = np.abs(A @ g - b).max(), gc.residual_bound(A, g)
+            assert res <= bound, (name, stride, res, bound)
+            ref = np.linalg.solve(A, b)
+            assert np.abs(A @ ref - b).max() <= gc.residual_bound(A, ref)
+            assert np.isfinite(g).all() and (g > 0).all()
+            ones = np.ones(len(g))
+            assert gc.mismatch(count, I, g) <= gc.mismatch(count, I, ones), (name, stride)
+    # other sigmas enter as the rule says
+    count, total = hstats(lib, *gc.exposure_fixture(), 0, 4)
+    for sn, sg in ((5.0, 0.1), (10.0, 0.5), (2.5, 0.02)):
+        A, b, _ = gc.system(count, total, sn, sg)
+        g = hgains(lib, count, total, sn, sg)
+        assert np.abs(A @ g - b).max() <= gc.residual_bound(A, g)
+
+
+def test_identical_images_get_gain_one(lib):
+    images, Gs = gc.identical_overlaps()
+    for stride in (1, 3):
+        count, total = hstats(lib, images, Gs, 0, stride)
+        assert count[0, 1] > 0 and count[1, 2] > 0 and count[0, 2] > 0
+        assert np.array_equal(total, total.T)                                   # where two meet, their bytes are equal
+        A, _, _ = gc.system(count, total)
+        g = hgains(lib, count, total)
+        assert np.abs(g - 1.0).max() <= gc.residual_bound(A, g)
+
+
+def test_one_image_gets_gain_one(lib):
+    img = sc.random_image(9, 11, 1)
+    count, total = hstats(lib, [img], [np.eye(3)], 0, 1)
+    assert count.tolist() == [[99]] and total.tolist() == [[int(img.astype(np.int64).sum())]]
+    assert hgains(lib, count, total).tolist() == [1.0]
+
+
+def test_exposure_fixture(lib):
+    """Three crops of one scene exposed at 0.7 / 1.0 / 1.3: the darkest gets the largest gain, and the mismatch falls."""
+    images, Gs = gc.exposure_fixture()
+    for stride in (1, 4):
+        count, total = hstats(lib, images, Gs, 0, stride)
+        _, _, I = gc.system(count, total)
+        g = hgains(lib, count, total)
+        before, after = gc.mismatch(count, I, np.ones(3)), gc.mismatch(count, I, g)
+        print("stride %d: gains %s, mismatch %.4g -> %.4g" % (stride, np.round(g, 4).tolist(), before, after))
+        assert after < before
+        assert g[0] > g[1] > g[2]
+
+
+# ---- the compositor with gains ----
+@pytest.mark.parametrize("blend", [sc.PASTE, sc.FEATHER], ids=["paste", "feather"])
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_host_twin_with_gains_is_the_restatement(lib, case, blend):
+    _, images, Gs, anchor, order = case
+    gains = gc.mixed_gains(len(images))
+    before = [im.copy() for im in images]
+    want = gc.restate(images, Gs, anchor, blend, order, gains)
+    got = twin_ex(lib, images, Gs, anchor, blend, order, gains=gains)
+    assert got.shape == want.shape and np.array_equal(got, want)
+    assert all(np.array_equal(a, b) for a, b in zip(images, before))
+    plain = twin_ex(lib, images, Gs, anchor, blend, order)
+    assert ((got == 255) & (plain < 255)).any()                                 # the clip at 255 occurs
+    assert not np.array_equal(got, plain)
+
+
+@pytest.mark.parametrize("blend", [sc.PASTE, sc.FEATHER], ids=["paste", "feather"])
+def test_unit_gains_and_null_are_the_plain_call(lib, blend):
+    for _, images, Gs, anchor, order in CASES:
+        st, plain = sc.host_twin(lib, images, Gs, anchor, blend, order)
+        assert st == 0
+        assert np.array_equal(plain, sc.restate(images, Gs, anchor, blend, order)[0])
+        assert np.array_equal(twin_ex(lib, images, Gs, anchor, blend, order, gains=np.ones(len(images))), plain)
+        assert np.array_equal(twin_ex(lib, images, Gs, anchor, blend, order, gains=None), plain)
+        assert np.array_equal(gc.restate(images, Gs, anchor, blend, order), plain)
+
+
+def test_row_tiles_with_gains_equal_the_whole_canvas(lib):
+    _, images, Gs, anchor, order = CASES[4]
+    gains = gc.mixed_gains(5)
+    for blend in (sc.PASTE, sc.FEATHER):
+        whole = twin_ex(lib, images, Gs, anchor, blend, order, gains=gains)
+        fh = whole.shape[0]
+        bounds = [0, 5, fh - 7, fh]
+        tiled = np.zeros_like(whole)
+        for r0, r1 in zip(bounds[:-1], bounds[1:]):
+            part = twin_ex(lib, images, Gs, anchor, blend, order, rows=(r0, r1), gains=gains)
+            assert (part[:r0] == 0xA5).all() and (part[r1:] == 0xA5).all()
+            tiled[r0:r1] = part[r0:r1]
+        assert np.array_equal(tiled, whole)
+
+
+# ---- refusals ----
+BAD_GAINS = ([1.0, np.nan, 1.0], [1.0, np.inf, 1.0], [1.0, 0.0, 1.0], [1.0, -0.5, 1.0])
+
+
+def test_c_level_refusals(lib):
+    images, Gs = sc.translated_strip(3)
+    images = [np.ascontiguousarray(im) for im in images]
+    t = sc.tables(images, Gs, 0)
+    fh, fw = t["size"]
+    ptrs = np.array([im.ctypes.data for im in images], dtype=np.uint64)
+    count, total = np.zeros((3, 3), np.uint64), np.zeros((3, 3), np.uint64)
+
+    def stats(fn=lib.rwh_host_sequence_overlap_stats, ptrs=ptrs.ctypes.data, hw=t["hw"].ctypes.data, inv=t["inv"].ctypes.data,
+              rects=t["rects"].ctypes.data, n=3, anchor=0, fh=fh, fw=fw, origin=t["origin"], stride=1, count=count.ctypes.data,
+              total=total.ctypes.data, tail=()):
+        return fn(ptrs, hw, inv, rects, n, anchor, fh, fw, origin[0], origin[1], stride, count, total, *tail)
+    assert stats() == 0 and count.any()
+    for stride in (0, 256, -1):
+        assert stats(stride=stride) == -1, stride
+    assert stats(stride=255) == 0
+    for k in ("ptrs", "hw", "inv", "rects", "count", "total"):
+        assert stats(**{k: None}) == -1, k
+    assert stats(n=0) == -1 and stats(n=65) == -1 and stats(anchor=3) == -1 and stats(fw=fw - 1) == -1 and stats(origin=(1, 0)) == -1
+    inv = t["inv"].copy()
+    inv[2, 4] = np.nan
+    assert stats(inv=inv.ctypes.data) == -1
+    # the device entry point refuses the same before it touches a device (no GPU here), and a missing, short or misaligned workspace
+    dev, one = lib.rwh_sequence_overlap_stats, ctypes.c_void_p(8)
+    wsb = lib.rwh_sequence_overlap_stats_workspace_bytes
+    need = wsb(3, fh, fw, 1)
+    assert need > 0 and wsb(0, fh, fw, 1) == -1 and wsb(65, fh, fw, 1) == -1 and wsb(3, fh, fw, 0) == -1 and wsb(3, fh, fw, 256) == -1
+    assert wsb(3, 0, fw, 1) == -1 and wsb(3, fh, 65536, 1) == -1
+    for kw in (dict(stride=0), dict(stride=256), dict(n=0), dict(ptrs=None), dict(count=None), dict(total=None), dict(anchor=-1)):
+        assert stats(fn=dev, count=kw.pop("count", one), total=kw.pop("total", one), tail=(one, need, None), **kw) == -1, kw
+    assert stats(fn=dev, count=one, total=one, tail=(None, need, None)) == -1
+    assert stats(fn=dev, count=one, total=one, tail=(one, need - 1, None)) == -1
+    assert stats(fn=dev, count=one, total=one, tail=(ctypes.c_void_p(4), need, None)) == -1
+    assert stats(fn=dev, count=ctypes.c_void_p(4), total=one, tail=(one, need, None)) == -1
+
+    # the gains
+    good_count, good_total = count.copy(), total.copy()
+    assert gc.host_gains(lib, good_count, good_total)[0] == 0
+    for sn, sg in ((0.0, 0.1), (-1.0, 0.1), (10.0, 0.0), (10.0, -0.1), (np.nan, 0.1), (10.0, np.inf)):
+        assert gc.host_gains(lib, good_count, good_total, sn, sg)[0] == -1, (sn, sg)
+    out = np.zeros(3)
+    assert lib.rwh_host_sequence_gains(None, good_total.ctypes.data, 3, 10.0, 0.1, out.ctypes.data) == -1
+    assert lib.rwh_host_sequence_gains(good_count.ctypes.data, None, 3, 10.0, 0.1, out.ctypes.data) == -1
+    assert lib.rwh_host_sequence_gains(good_count.ctypes.data, good_total.ctypes.data, 3, 10.0, 0.1, None) == -1
+    assert lib.rwh_host_sequence_gains(good_count.ctypes.data, good_total.ctypes.data, 0, 10.0, 0.1, out.ctypes.data) == -1
+    assert lib.rwh_host_sequence_gains(good_count.ctypes.data, good_total.ctypes.data, 65, 10.0, 0.1, out.ctypes.data) == -1
+    # tables no overlap produces (count is not symmetric: A_10 far outweighs A_00): a non-positive pivot is refused, not solved
+    c2 = np.array([[1, 1], [10 ** 6, 1]], dtype=np.uint64)
+    s2 = np.array([[3, 765], [765 * 10 ** 6, 3]], dtype=np.uint64)
+    assert gc.host_gains(lib, c2, s2)[0] == -1
+
+    # the compositor with gains
+    can = np.zeros((fh, fw, 3), np.uint8)
+
+    def stitch(fn=lib.rwh_host_stitch_sequence_ex, gains=None, tail=(), n=3):
+        g = None if gains is None else np.ascontiguousarray(gains, dtype=np.float64)
+        return fn(ptrs.ctypes.data, t["hw"].ctypes.data, t["inv"].ctypes.data, t["rects"].ctypes.data, n, 0, t["order"].ctypes.data, 0,
+                  can.ctypes.data, fh, fw, t["origin"][0], t["origin"][1], 0, fh, *tail, None if g is None else g.ctypes.data)
+    assert stitch() == 0 and stitch(gains=[0.5, 1.0, 1.9]) == 0
+    sneed = lib.rwh_stitch_sequence_workspace_bytes(3)
+    for bad in BAD_GAINS:
+        assert stitch(gains=bad) == -1, bad
+        assert stitch(fn=lib.rwh_stitch_sequence_ex, gains=bad, tail=(one, sneed, None)) == -1, bad
+    assert stitch(gains=[1.0, 1.0, 1.0], n=65) == -1
+    assert lib.rwh_stitch_sequence_workspace_bytes(3) == 3 * 104 and lib.rwh_stitch_sequence_workspace_bytes(64) == 64 * 104     # as before
+    assert all(np.array_equal(a, b) for a, b in zip(images, sc.translated_strip(3)[0]))
+
+
+def test_python_level_refusals_come_before_the_gpu():
+    """Everything here raises ValueError where there is no GPU: the checks come before the device is asked for."""
+    import homography
+    import ransac
+    from ransac_with_homography_amd import homography as hg, kernels
+    from ransac_with_homography_amd import ransac as rs
+    a, b, c = (sc.random_image(12, 16, i) for i in (1, 2, 3))
+    T = sc.translate(8, 0)
+    for bad in BAD_GAINS:
+        with pytest.raises(ValueError):
+            hg.stitchSequence([a, b, c], Hs=[T, T], gains=bad)
+        with pytest.raises(ValueError):
+            rs.stitch_sequence([a, b, c], gains=bad)
+    for bad in ([1.0, 1.0], [1.0, 1.0, 1.0, 1.0], np.ones((3, 1)), "Auto", "gain", ""):
+        with pytest.raises(ValueError):
+            hg.stitchSequence([a, b, c], Hs=[T, T], gains=bad)
+        with pytest.raises(ValueError):
+            rs.stitch_sequence([a, b, c], gains=bad)
+    for stride in (0, 256, -4, 2.5, None):
+        with pytest.raises(ValueError):
+            hg.sequence_gains([a, b], Hs=[T], stride=stride)
+    for kw in (dict(sigma_n=0.0), dict(sigma_n=-1.0), dict(sigma_g=0.0), dict(sigma_g=-0.1), dict(sigma_n=np.nan), dict(sigma_g=np.inf)):
+        with pytest.raises(ValueError):
+            hg.sequence_gains([a, b], Hs=[T], **kw)
+    # the same validation of images and geometry as stitchSequence
+    with pytest.raises(ValueError):
+        hg.sequence_gains([a, b])
+    with pytest.raises(ValueError):
+        hg.sequence_gains([a, b], Hs=[T], Gs=[np.eye(3), T])
+    with pytest.raises(ValueError):
+        hg.sequence_gains([a, b], Gs=[T, T])
+    with pytest.raises(ValueError):
+        hg.sequence_gains([], Hs=[])
+    with pytest.raises(ValueError):
+        hg.sequence_gains([a, b], Hs=[T], anchor=2)
+    with pytest.raises(NotImplementedError):
+        hg.sequence_gains([a, b.astype(np.float32)], Hs=[T])
+    assert np.array_equal(kernels.sequence_gains_array([0.5, 2], 2), np.array([0.5, 2.0]))
+    assert homography.sequence_gains is hg.sequence_gains and ransac.sequence_gains is hg.sequence_gains
+    assert "sequence_gains" in homography.__all__
+    import inspect
+    assert inspect.signature(hg.sequence_gains).parameters["stride"].default == 4
+    assert inspect.signature(hg.stitchSequence).parameters["gains"].default is None
+    assert inspect.signature(rs.stitch_sequence).parameters["gains"].default is None
