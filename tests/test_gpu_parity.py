@@ -59,6 +59,8 @@ def release_lab_overrides():
     yield
     _force_shape(None)
     _force_frames(0)
+    from ransac_with_homography_amd import _lib
+    assert _lib.load().rwh_lab_tune(_lib.RWH_TUNE_SCORE_HPW, 0) == 0 and _lib.load().rwh_lab_tune(_lib.RWH_TUNE_SCORE_EXACT, 0) == 0
 
 
 def close(gpu_img, ref):
