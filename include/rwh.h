@@ -814,6 +814,70 @@ RWH_API int rwh_host_stitch_sequence_ex(const void* const* images, const int32_t
                                         int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
                                         int origin_x, int origin_y, int row_begin, int row_end, const double* gains);
 
+/*
+ * Multi-band blending for the sequence compositor (Burt & Adelson 1983, as Brown & Lowe 2007, section 7, and OpenCV's stitcher use
+ * it): low frequencies are blended over a wide region, so no exposure step remains, and high frequencies come from one image, so
+ * a misregistration of a pixel or two does not ghost.  The reference has no counterpart; this is held to THE MULTI-BAND RULE below.
+ * Everything not restated is the sequence rule's: rectangles, canvas, the sampling recipe, Coverage, the feather weight g, and texel
+ * (0,0) of a warped image reading as 0.  From the planes onward everything is integer arithmetic, so the result does not depend on
+ * the order of the additions: device, host twin and a restatement agree exactly.
+ *
+ * The multi-band rule.
+ *   Inputs.  Those of the sequence rule, without `order` and without a row range; bands = K, 1 <= K <= RWH_SEQ_MAX_BANDS; optional
+ *     gains, as in the gain rule.
+ *   Padded canvas.  PW = fw rounded up to a multiple of 2^K, PH likewise.  Level l (0 .. K) is a (PH >> l) x (PW >> l) plane;
+ *     everything beyond a plane's edge reads as 0.
+ *   Bytes of image i at a canvas pixel it covers: what paste would write -- the anchor's own bytes for the anchor, (uint8)(int)v_k
+ *     for a warped image; with gains (uint8)(int)min(v_k * g_i, 255.0) for both.
+ *   Winner.  At a canvas pixel covered by at least one image, the covering image with the greatest feather weight g (float64, as
+ *     the sequence rule computes it); on equal weights the lowest index.  P is the winner's bytes there, 0 where nothing covers and
+ *     0 in the padding.
+ *   Planes of image i, over the whole padded canvas.  I_i: image i's bytes where i covers, P elsewhere (an image has no black
+ *     surround).  W_i: 16384 where i is the winner, 0 elsewhere.
+ *   Reduce (values and weights alike, all non-negative).  down(S)[y][x] = (sum_{ky,kx = -2..2} w[ky] w[kx] S[2y+ky][2x+kx] + 128) >> 8,
+ *     w = 1 4 6 4 1.  G_i^0 = I_i, G_i^{l+1} = down(G_i^l) per channel; W_i^{l+1} = down(W_i^l).
+ *   Expand.  up(S)[y][x] = floor((sum w[ky] w[kx] S[(y+ky)/2][(x+kx)/2] + 32) / 64), the sum over the ky, kx in -2..2 for which
+ *     y+ky and x+kx are both even; floor division also for negative sums (an arithmetic shift); the output has twice the size each way.
+ *   Bands.  L_i^l = G_i^l - up(G_i^{l+1}) for l < K, L_i^K = G_i^K.  |L| <= 255.
+ *   Accumulate, per level and channel.  num^l = sum_i L_i^l W_i^l, den^l = sum_i W_i^l; both fit int32.
+ *   Normalise.  B^l = 0 where den^l == 0, elsewhere sign(num) ((|num| + den / 2) / den), `/` truncating: a single contributor
+ *     gives L back exactly.
+ *   Collapse.  R^K = B^K, R^l = B^l + up(R^{l+1}).  |R| <= 255 (K + 1): int16.
+ *   Canvas.  clamp(R^0, 0, 255) per channel where at least one image covers the pixel, 0 elsewhere.  The images are never written.
+ *   Consequences.  With N = 1 the canvas is paste's.  Where all covering images agree in their bytes the canvas is paste's.  With
+ *     every g_i = 1.0 the canvas is the one without gains.
+ *   Working in windows.  Image i contributes only where W_i^l > 0, so an implementation may hold, per image and level, a window of
+ *     the plane instead of the plane.  Per axis, with [a, b) the rectangle's canvas coordinates: D_0 = [a, b) and
+ *     D_{l+1} = [floor((a_l - 1) / 2), floor((b_l + 1) / 2)] hold every non-zero W^l (the reduce taps 2x - 2 .. 2x + 2 that meet D_l);
+ *     the bands read G^l on E_l = D_l united, for l >= 1, with the expand taps of D_{l-1}, [floor(a_{l-1} / 2) - 1,
+ *     floor((b_{l-1} - 1) / 2) + 1]; G^l has to be the rule's on N_K = E_K and N_l = E_l united with the reduce taps of N_{l+1},
+ *     [2 lo - 2, 2 hi + 2].  The window of level l is N_l clipped to the plane.  By induction from level 0, which is exact everywhere,
+ *     every value stored in a window is the rule's, and what lies outside a window is either never read with a non-zero weight or
+ *     beyond the plane and 0.  D_l and E_l stay within 4 pixels of the rectangle scaled by 2^-l, so the margin obeys
+ *     m_l = 2 m_{l+1} + 2, m_K <= 4: the level-0 window reaches less than 6 * 2^K + 2 pixels beyond the rectangle.
+ *
+ * rwh_stitch_multiband_workspace_bytes: the bytes rwh_stitch_multiband needs for these rectangles, canvas and bands (the two tables,
+ * the P / winner plane, the R planes of levels 1 .. K and every image's windows, four int16 per pixel); <= 0 for arguments the
+ * main call would refuse.
+ * rwh_stitch_multiband: images, hw, inv_g, rects, n, anchor, canvas and origin as rwh_stitch_sequence's; gains: a HOST array of N,
+ * or NULL; d_workspace: that many bytes on the device, 8-byte aligned -- the call writes everything it reads there, it does not
+ * depend on what the workspace held.  Writes the whole canvas.  Launches: the winner pass over the padded canvas, level 0 of all
+ * images (one launch), K reduce launches (all images each; the 5 x 5 stencil from LDS tiles), K + 1 blend-and-collapse passes over
+ * the canvas planes from level K down.  num and den are summed in registers by the pixel that owns them: no atomics.
+ * RWH_E_INVALID, before anything is launched: everything rwh_stitch_sequence_ex refuses (no order or row range here), bands outside
+ * 1 .. RWH_SEQ_MAX_BANDS, a workspace too small or misaligned.
+ * rwh_host_stitch_multiband: the same arithmetic on host memory, no workspace (it allocates its own), no GPU involved.
+ */
+#define RWH_SEQ_MAX_BANDS 8
+RWH_API int64_t rwh_stitch_multiband_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y,
+                                                     int bands);
+RWH_API int rwh_stitch_multiband(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                 int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
+                                 int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_stitch_multiband(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                      int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
+                                      int origin_x, int origin_y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ RWH_ORB_SCALE_ONE, RWH_ORB_SCALE_MAX, RWH_ORB_LEVELS_MAX, RWH_ORB_PYR_TILE_W, RW
 # the sequence compositor (include/rwh.h, the sequence rule): most images per call, its blend modes; the gain rule's largest stride
 RWH_SEQ_MAX_IMAGES, RWH_SEQ_PASTE, RWH_SEQ_FEATHER = 64, 0, 1
 RWH_SEQ_MAX_STRIDE = 255
+RWH_SEQ_MAX_BANDS = 8         # the multi-band rule: most bands
 RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRAMES = 0, 1, 2, 3
 
 # every symbol include/rwh.h declares (tests check the library exports them all)
@@ -46,7 +47,8 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_orb_pyramid_bytes", "rwh_orb_pyramid_batched", "rwh_host_orb_pyramid", "rwh_host_orb_extract_pyramid",
            "rwh_stitch_sequence_workspace_bytes", "rwh_stitch_sequence", "rwh_host_stitch_sequence",
            "rwh_sequence_overlap_stats_workspace_bytes", "rwh_sequence_overlap_stats", "rwh_host_sequence_overlap_stats",
-           "rwh_host_sequence_gains", "rwh_stitch_sequence_ex", "rwh_host_stitch_sequence_ex")
+           "rwh_host_sequence_gains", "rwh_stitch_sequence_ex", "rwh_host_stitch_sequence_ex",
+           "rwh_stitch_multiband_workspace_bytes", "rwh_stitch_multiband", "rwh_host_stitch_multiband")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -177,6 +179,14 @@ def _bind(lib):
     lib.rwh_stitch_sequence_ex.argtypes = lib.rwh_stitch_sequence.argtypes + [vp]
     lib.rwh_host_stitch_sequence_ex.restype = i32
     lib.rwh_host_stitch_sequence_ex.argtypes = lib.rwh_host_stitch_sequence.argtypes + [vp]
+    # the multi-band rule
+    lib.rwh_stitch_multiband_workspace_bytes.restype = i64
+    lib.rwh_stitch_multiband_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32]       # rects n canvas h w origin_x origin_y bands
+    lib.rwh_stitch_multiband.restype = i32
+    lib.rwh_stitch_multiband.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp,                      # images hw inv_g rects n anchor bands gains
+                                         vp, i32, i32, i32, i32, vp, i64, vp]                    # canvas h w origin_x origin_y workspace bytes stream
+    lib.rwh_host_stitch_multiband.restype = i32
+    lib.rwh_host_stitch_multiband.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32]
     return lib
 
 

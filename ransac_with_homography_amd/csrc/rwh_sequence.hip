@@ -3,130 +3,9 @@
 // this is its paste compositor generalised to N images, plus a feather blend, and at N = 2 / paste it produces stitchPanorama's bytes.
 // The sampling recipe is stitch_pixel's (rwh_stitch.hip), restated here: float64, dgemm k-order, IEEE divides, separately rounded
 // lerps.  The pixel function is compiled for the device and for the host (rwh_host_stitch_sequence), so the two run one arithmetic.
-#include <math.h>
-#include <string.h>
-#include "rwh_common.h"
+#include "rwh_sequence.h"
 
 namespace rwh {
-
-// One image of the sequence, 13 eight-byte words: the kernels read it from a device table with wave-uniform indices.
-struct SeqDesc {
-    const unsigned char* src;   // h x w x 3 uint8
-    double ih[9];               // inv(G): frame point -> source coordinates
-    int h, w;
-    int mx, my, wt, ht;         // its rectangle in the anchor's frame
-};
-constexpr int SEQ_DESC_WORDS = 13;
-static_assert(sizeof(SeqDesc) == 8 * SEQ_DESC_WORDS, "SeqDesc is copied as 8-byte words");
-
-struct SeqArgs {
-    const SeqDesc* desc;        // n descriptors (device table; host array in the host twin)
-    unsigned char* dst;         // canvas fh x fw x 3 uint8
-    int n, anchor;
-    int ox, oy;                 // canvas pixel (cx, cy) is frame point (ox + cx, oy + cy)
-    int fh, fw;
-    int row_begin, row_end;     // canvas rows this call produces
-    unsigned char order[RWH_SEQ_MAX_IMAGES];   // paste: priority order; feather: 0 .. n-1
-};
-
-// One RGB texel as a dword: an unaligned 4-byte load (3 bytes used) unless that would step past the image's last byte.
-__host__ __device__ __forceinline__ uint32_t seq_rgb_at(const unsigned char* base, size_t off, size_t img_bytes) {
-    if (off + 4 <= img_bytes) { uint32_t v; __builtin_memcpy(&v, base + off, 4); return v; }
-    return (uint32_t)base[off] | ((uint32_t)base[off + 1] << 8) | ((uint32_t)base[off + 2] << 16);
-}
-__host__ __device__ __forceinline__ double seq_chan(uint32_t texel, int k) { return (double)((texel >> (8 * k)) & 0xffu); }
-__host__ __device__ __forceinline__ double seq_min(double a, double b) { return a < b ? a : b; }
-
-// Image d at frame point (fx, fy): false where it does not cover the point; else its value v (float64 per channel) and, for the
-// feather blend, its weight g.  The anchor enters unwarped: its own bytes, texel (0,0) included.  GAIN (the gain rule): v is
-// min(v * gain, 255.0), the product rounded on its own; without GAIN `gain` is not read.
-template <bool FEATHER, bool GAIN = false>
-__host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_anchor, int fx, int fy, double v[3], double& g,
-                                                    double gain = 1.0) {
-    const int tx = fx - d.mx, ty = fy - d.my;
-    if (!((tx >= 0) & (tx < d.wt) & (ty >= 0) & (ty < d.ht))) return false;
-    const size_t bytes = (size_t)d.h * d.w * 3;
-    double sx, sy;
-    if (is_anchor) {            // (its rectangle is (0, 0, w, h): checked before the launch)
-        const uint32_t p = seq_rgb_at(d.src, ((size_t)ty * d.w + tx) * 3, bytes);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = seq_chan(p, k);
-        sx = (double)tx; sy = (double)ty;
-    } else {
-        const double x = (double)fx, y = (double)fy;
-        const double X = fma(d.ih[1], y, d.ih[0] * x) + d.ih[2];
-        const double Y = fma(d.ih[4], y, d.ih[3] * x) + d.ih[5];
-        const double W = fma(d.ih[7], y, d.ih[6] * x) + d.ih[8];
-        sx = X / W; sy = Y / W;
-        const bool valid = (sx >= 0.0) & (sx <= (double)(d.w - 1)) & (sy >= 0.0) & (sy <= (double)(d.h - 1));   // a NaN is not valid
-        if (!valid) return false;
-        const int ix = (int)sx, iy = (int)sy;
-        const double fx_ = sx - (double)ix, fy_ = sy - (double)iy;
-        const double gx = 1.0 - fx_, gy = 1.0 - fy_;
-        const int ix1 = ix + 1 < d.w ? ix + 1 : d.w - 1, iy1 = iy + 1 < d.h ? iy + 1 : d.h - 1;
-        // texel (0,0) reads as 0: the caller's image is never written
-        const uint32_t p00 = (ix | iy) ? seq_rgb_at(d.src, ((size_t)iy * d.w + ix) * 3, bytes) : 0u;
-        const uint32_t p01 = (ix1 | iy) ? seq_rgb_at(d.src, ((size_t)iy * d.w + ix1) * 3, bytes) : 0u;
-        const uint32_t p10 = (ix | iy1) ? seq_rgb_at(d.src, ((size_t)iy1 * d.w + ix) * 3, bytes) : 0u;
-        const uint32_t p11 = seq_rgb_at(d.src, ((size_t)iy1 * d.w + ix1) * 3, bytes);      // (h, w >= 2: never texel (0,0))
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double top = seq_chan(p00, k) * gx + seq_chan(p01, k) * fx_;
-            const double bot = seq_chan(p10, k) * gx + seq_chan(p11, k) * fx_;
-            v[k] = top * gy + bot * fy_;
-        }
-    }
-    if constexpr (GAIN) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = seq_min(v[k] * gain, 255.0);
-    }
-    if constexpr (FEATHER) g = seq_min(seq_min(sx, (double)(d.w - 1) - sx), seq_min(sy, (double)(d.h - 1) - sy)) + 1.0;
-    return true;
-}
-
-// One canvas pixel as 0x00BBGGRR.  cand: bit k set = image order[k] may cover the pixel (its rectangle meets the pixel's tile).
-// gains: the N gains of the gain rule, read with GAIN only.
-template <bool FEATHER, bool GAIN = false>
-__host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains = nullptr) {
-    const int fx = a.ox + cx, fy = a.oy + cy;
-    double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
-    bool covered = false;
-    for (uint64_t m = cand; m; m &= m - 1) {
-        const int i = a.order[__builtin_ctzll(m)];
-        double v[3], g = 0.0;
-        double gain = 1.0;
-        if constexpr (GAIN) gain = gains[i];
-        if (!seq_sample<FEATHER, GAIN>(a.desc[i], i == a.anchor, fx, fy, v, g, gain)) continue;
-        if constexpr (!FEATHER) {       // paste: the first image in `order` that covers the pixel
-            uint32_t out = 0u;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) out |= (uint32_t)(unsigned char)(int)v[k] << (8 * k);
-            return out;
-        } else {
-            covered = true;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) num[k] += g * v[k];
-            den += g;
-        }
-    }
-    uint32_t out = 0u;
-    if (FEATHER && covered) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out |= (uint32_t)(unsigned char)(int)(num[k] / den) << (8 * k);
-    }
-    return out;
-}
-
-// The images whose rectangles meet canvas columns [x0, x1) and rows [y0, y1), as bits in `order`'s numbering.
-__host__ __device__ __forceinline__ uint64_t seq_tile_mask(const SeqArgs& a, int x0, int x1, int y0, int y1) {
-    uint64_t m = 0;
-    for (int k = 0; k < a.n; ++k) {
-        const SeqDesc& d = a.desc[a.order[k]];
-        const int rx = d.mx - a.ox, ry = d.my - a.oy;
-        if ((rx < x1) & (rx + d.wt > x0) & (ry < y1) & (ry + d.ht > y0)) m |= 1ull << k;
-    }
-    return m;
-}
 
 // stitch_kernel's shape (rwh_stitch.hip): 256 lanes as 64 x 4, four consecutive pixels per lane, the 12 output bytes in one store.
 // A block's 256 x 4 tile is tested once against the n rectangles; blockIdx and the descriptor indices are wave-uniform, so the
@@ -168,50 +47,6 @@ constexpr int SEQ_PUT = 32;
 struct SeqPut { uint64_t w[SEQ_PUT * SEQ_DESC_WORDS]; };
 __global__ __launch_bounds__(256) void seq_put_kernel(const SeqPut c, uint64_t* out, int words) {
     for (int t = threadIdx.x; t < words; t += 256) out[t] = c.w[t];
-}
-
-// Everything both entry points check, and the descriptors / arguments they share.  descs: room for RWH_SEQ_MAX_IMAGES.
-static int seq_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
-                       const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                       int row_begin, int row_end, SeqDesc* descs, SeqArgs& a) {
-    if (!images || !hw || !inv_g || !rects || !order || !canvas) return RWH_E_INVALID;
-    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || anchor < 0 || anchor >= n || (blend != RWH_SEQ_PASTE && blend != RWH_SEQ_FEATHER)) return RWH_E_INVALID;
-    if (canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535 || (int64_t)canvas_h * canvas_w * 3 > INT32_MAX) return RWH_E_INVALID;
-    if (row_begin < 0 || row_end > canvas_h || row_begin > row_end) return RWH_E_INVALID;
-    uint64_t seen = 0;
-    for (int k = 0; k < n; ++k) {
-        if (order[k] < 0 || order[k] >= n || (seen >> order[k] & 1)) return RWH_E_INVALID;
-        seen |= 1ull << order[k];
-    }
-    for (int i = 0; i < n; ++i) {
-        SeqDesc& d = descs[i];
-        d.src = static_cast<const unsigned char*>(images[i]);
-        d.h = hw[2 * i]; d.w = hw[2 * i + 1];
-        d.mx = rects[4 * i]; d.my = rects[4 * i + 1]; d.wt = rects[4 * i + 2]; d.ht = rects[4 * i + 3];
-        if (!d.src || d.h < 2 || d.w < 2 || d.wt <= 0 || d.ht <= 0) return RWH_E_INVALID;
-        // the rectangle lies on the canvas (so no frame coordinate leaves int32), the anchor's is its own image
-        const int64_t rx = (int64_t)d.mx - origin_x, ry = (int64_t)d.my - origin_y;
-        if (rx < 0 || ry < 0 || rx + d.wt > canvas_w || ry + d.ht > canvas_h) return RWH_E_INVALID;
-        if (i == anchor && (d.mx != 0 || d.my != 0 || d.wt != d.w || d.ht != d.h)) return RWH_E_INVALID;
-        for (int j = 0; j < 9; ++j) {
-            d.ih[j] = inv_g[9 * i + j];
-            if (i != anchor && !isfinite(d.ih[j])) return RWH_E_INVALID;
-        }
-    }
-    a.desc = descs;
-    a.dst = static_cast<unsigned char*>(canvas);
-    a.n = n; a.anchor = anchor; a.ox = origin_x; a.oy = origin_y; a.fh = canvas_h; a.fw = canvas_w;
-    a.row_begin = row_begin; a.row_end = row_end;
-    memset(a.order, 0, sizeof(a.order));
-    for (int k = 0; k < n; ++k) a.order[k] = (unsigned char)(blend == RWH_SEQ_FEATHER ? k : order[k]);   // feather: index order
-    return RWH_OK;
-}
-
-// The gains of the gain rule: N values, each finite and > 0.
-static bool seq_gains_ok(const double* gains, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!(isfinite(gains[i]) && gains[i] > 0.0)) return false;
-    return true;
 }
 
 // Lays the n descriptors down at `table` (device), SEQ_PUT per launch.

@@ -861,7 +861,12 @@ def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, s
     return _gains_on_device(_sequence_upload(images), inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info)
 
 
-def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None, gains=None, info=None):
+def _check_bands(who, bands):
+    if not (isinstance(bands, (int, np.integer)) and not isinstance(bands, bool) and 1 <= bands <= _lib.RWH_SEQ_MAX_BANDS):
+        raise ValueError("%s: bands %r; an integer of 1 .. %d" % (who, bands, _lib.RWH_SEQ_MAX_BANDS))
+
+
+def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None, gains=None, info=None, bands=5):
     """N images into one panorama in ONE pass over the canvas (`rwh_stitch_sequence`): every image is warped once into the
     anchor's frame and every canvas pixel written once.  The reference has no counterpart -- its stitchPanorama takes two images,
     and folding it over a list resamples the growing canvas once per image; this is held to the sequence rule stated in
@@ -871,7 +876,12 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     images: N (1 .. 64) uint8 [h, w, 3] numpy arrays or tensors, sizes may differ; exactly one of Hs (N - 1 pairwise homographies,
     chained by `sequence_plan`) and Gs (N maps into the anchor's frame, used as given; Gs[anchor] must be the identity).
     blending: False -- the first image in `order` (default: the anchor, then the nearest) that covers a pixel gives it;
-    "feather" -- every covering image, weighted by its distance to its own border (`order` is ignored).  gains: None -- the images
+    "feather" -- every covering image, weighted by its distance to its own border (`order` is ignored); "multiband" -- multi-band
+    blending (the multi-band rule of include/rwh.h; Burt & Adelson pyramids as Brown & Lowe 2007, section 7, use them): low
+    frequencies are blended over a wide region, high frequencies come from the image with the greatest feather weight, so neither an
+    exposure step nor ghosting remains (`order` is validated and otherwise ignored).  bands (5): the pyramid levels of "multiband",
+    an integer of 1 .. 8, ignored by the other blends; 5 is OpenCV's convention, not a measured optimum, and it wants overlaps several
+    times 2^(bands+2) pixels wide -- 170-pixel overlaps were visibly too narrow for 5.  gains: None -- the images
     as they are; N exposure gains (the gain rule of include/rwh.h: every sample value v of image i enters as min(v * g_i, 255.0));
     "auto" -- `sequence_gains` with its defaults on the same images and geometry, the images uploaded once.  `info`: optional dict,
     receives "gains" (the gains used, float64 [N], or None).  numpy arrays in -> a
@@ -880,8 +890,10 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     not finite or <= 0, or another string; NotImplementedError: images that are not uint8 [h, w, 3]."""
     n = len(images)
     _check_count(n, anchor)
-    if blending is not False and blending != "feather" and blending:
-        raise ValueError("stitchSequence: blending=%r; False or 'feather'" % (blending,))
+    if blending is not False and blending != "feather" and blending != "multiband" and blending:
+        raise ValueError("stitchSequence: blending=%r; False, 'feather' or 'multiband'" % (blending,))
+    if blending == "multiband":
+        _check_bands("stitchSequence", bands)
     blend = _lib.RWH_SEQ_FEATHER if blending == "feather" else _lib.RWH_SEQ_PASTE
     rects, origin, size, default, inv_g = _sequence_inputs("stitchSequence", images, Hs, Gs, anchor)
     order = default if order is None else [int(v) for v in order]
@@ -898,7 +910,10 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
         gains = _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, 4, 10.0, 0.1, None)
     if info is not None:
         info["gains"] = gains
-    out = kernels.stitch_sequence(on_dev, inv_g, rects, anchor, order, blend, origin, size, gains=gains)
+    if blending == "multiband":
+        out = kernels.stitch_sequence_multiband(on_dev, inv_g, rects, anchor, origin, size, int(bands), gains=gains)
+    else:
+        out = kernels.stitch_sequence(on_dev, inv_g, rects, anchor, order, blend, origin, size, gains=gains)
     return out if tens else _xfer.to_host(out)
 
 

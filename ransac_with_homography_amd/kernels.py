@@ -722,6 +722,47 @@ def stitch_sequence(images, inv_g, rects, anchor, order, blend, origin, canvas_h
     return out
 
 
+def stitch_sequence_multiband(images, inv_g, rects, anchor, origin, canvas_hw, bands, gains=None, out=None):
+    """Launch the multi-band compositor (rwh_stitch_multiband; the multi-band rule of include/rwh.h): images, inv_g, rects, anchor,
+    origin, canvas_hw as `stitch_sequence`'s; bands: 1 .. 8 pyramid levels below the top; gains: None, or n gains of the gain rule
+    -> canvas [fh, fw, 3] uint8 (`out` when given), on torch's current stream.  The workspace is allocated here, of
+    rwh_stitch_multiband_workspace_bytes bytes.  What the library refuses (RWH_E_INVALID) raises ValueError."""
+    lib = _lib.load()
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), "stitch_sequence_multiband")
+    _dev_check(*images)
+    n = len(images)
+    for t in images:
+        assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
+    fh, fw = (int(v) for v in canvas_hw)
+    if not (1 <= n <= SEQ_MAX_IMAGES) or len(rects) != n or len(inv_g) != n:
+        raise ValueError("stitch_sequence_multiband: %d images (1 .. %d), %d rectangles, %d matrices" % (n, SEQ_MAX_IMAGES, len(rects), len(inv_g)))
+    if not (isinstance(bands, (int, np.integer)) and not isinstance(bands, bool) and 1 <= bands <= _lib.RWH_SEQ_MAX_BANDS):
+        raise ValueError("stitch_sequence_multiband: bands %r; an integer of 1 .. %d" % (bands, _lib.RWH_SEQ_MAX_BANDS))
+    if not (1 <= fh <= 65535 and 1 <= fw <= 65535 and fh * fw * 3 <= 2 ** 31 - 1):
+        raise ValueError("stitch_sequence_multiband: a %d x %d canvas; sides of 1 .. 65535 and at most 2^31 - 1 bytes" % (fh, fw))
+    if out is None:
+        out = torch.empty((fh, fw, 3), dtype=torch.uint8, device=images[0].device)
+    else:
+        _dev_check(out)
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (fh, fw, 3)
+    hw, ig, rc, _ = sequence_tables([t.shape for t in images], inv_g, rects, list(range(n)))
+    ptrs = np.array([t.data_ptr() for t in images], dtype=np.uint64)
+    refused = ValueError("stitch_sequence_multiband: the library refused the arguments (include/rwh.h, rwh_stitch_multiband: anchor, "
+                         "rectangles on the canvas, finite inv(G), bands)")
+    need = int(lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1]), int(bands)))
+    if need <= 0:
+        raise refused
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
+    status = lib.rwh_stitch_multiband(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), int(bands),
+                                      None if gains is None else gains.ctypes.data, _ptr(out), fh, fw, int(origin[0]), int(origin[1]),
+                                      _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
+    if status == _lib.RWH_E_INVALID:
+        raise refused
+    check(status, "rwh_stitch_multiband")
+    return out
+
+
 def decode_best(best_words, k_total):
     """Unpack the two argmax words (host ints) -> (winner_index, count, early_exit).
     Word 1 (first index reaching `need`) takes precedence, like the reference's

@@ -46,7 +46,7 @@ import os
 import numpy as np
 
 from . import _lapack, _lib, kernels
-from .homography import (_pair_rows, calcHomography, calcHomographyLinear, cylindericlMap,  # noqa: F401
+from .homography import (_check_bands, _pair_rows, calcHomography, calcHomographyLinear, cylindericlMap,  # noqa: F401
                          sequence_gains, sequence_plan, stitchPanorama, stitchSequence)
 
 # Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
@@ -1164,7 +1164,7 @@ def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blen
     return stitchPanorama(queryImg, trainImg, H=H, blending=blending, blendrate=blendrate)
 
 
-def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, blending=False, features=None, info=None, gains=None):
+def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, blending=False, features=None, info=None, gains=None, bands=5):
     """Pixels -> panorama for a SEQUENCE of N overlapping images (images[i+1] overlaps images[i]), every stage batched: one
     `extract_batch` over the N images, one `match_batch` over the N - 1 adjacent pairs, one `run_batch(refit="device")`, one download
     of the [N - 1, 3, 3] homographies -- the only geometry that visits the host, because the canvas must be allocated -- and one
@@ -1172,7 +1172,8 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     stitches two images per call (ransac.py:235-283); this goes beyond it, under the rules stated for each stage in include/rwh.h.
 
     th, d, k, ransacMet, seed: as `run_batch`'s (device sampling, the float64 device refit: a NON-PARITY mode);
-    features: a dict of `extract_batch`'s keyword arguments; anchor, blending, gains: as `stitchSequence`'s (gains="auto": exposure
+    features: a dict of `extract_batch`'s keyword arguments; anchor, blending, bands, gains: as `stitchSequence`'s
+    (blending="multiband": multi-band blending with `bands` pyramid levels, checked before any GPU work; gains="auto": exposure
     gains from the overlaps, `sequence_gains` with its defaults).  numpy arrays in -> a numpy canvas, tensors in -> a device
     tensor.  `info`: optional dict, receives "Hs" (float64 [N - 1, 3, 3], Hs[i] maps image i+1 into image i), "Gs", "origin"
     ((ox, oy) of the canvas in the anchor's frame), "sizes" (matches per pair), "inliers" (per pair) and "gains" (the gains used,
@@ -1186,6 +1187,8 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
             raise ValueError("stitch_sequence: gains=%r; None, N gains or 'auto'" % (gains,))
     elif gains is not None:
         gains = kernels.sequence_gains_array(gains, n, "stitch_sequence")
+    if blending == "multiband":
+        _check_bands("stitch_sequence", bands)
     Hs, sizes, inliers = np.zeros((0, 3, 3)), [], []
     if n > 1:
         feats = extract_batch(images, **(features or {}))
@@ -1204,7 +1207,7 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     if info is not None:
         info["Hs"], info["Gs"], info["origin"], info["sizes"], info["inliers"] = Hs, Gs, origin, sizes, inliers
     used = {}
-    out = stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending, gains=gains, info=used)
+    out = stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands)
     if info is not None:
         info["gains"] = used["gains"]
     return out

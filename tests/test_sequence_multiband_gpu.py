@@ -1,0 +1,178 @@
+"""The multi-band rule on the GPU: rwh_stitch_multiband against its host twin (which tests/test_sequence_multiband_cpu.py holds
+to the numpy restatement) on canvases and windows that cross every launch and tile edge, into dirty workspaces and on a second
+stream, the Python layers above it, and the pipeline entry ransac.stitch_sequence(blending="multiband").  Every comparison is
+exact, and every device canvas lies between canaries."""
+import numpy as np
+import pytest
+
+import gain_cases as gc
+import multiband_cases as mc
+import sequence_cases as sc
+
+pytestmark = pytest.mark.gpu
+
+TH = 5
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from ransac_with_homography_amd import _lib
+    _lib.require_gpu()
+    return _lib.load()
+
+
+EDGES = sc.edge_canvases()
+GENERAL = sc.general_cases()
+TILES = mc.tile_edge_cases()
+
+
+# ---- launch and plane edges ----
+@pytest.mark.parametrize("case", EDGES, ids=["fw%d-fh%d" % (c[0], c[1]) for c in EDGES])
+def test_device_is_the_host_twin_across_launch_edges(lib, case):
+    """Padding, fw that is no multiple of 2^K, planes of one row; with and without gains."""
+    _, _, images, Gs, _, _ = case
+    dev = mc.upload(images)
+    for bands in (1, 2):
+        for gains in (None, gc.mixed_gains(len(images))):
+            assert np.array_equal(mc.device(lib, images, Gs, 0, bands, gains, on=dev), mc.host(lib, images, Gs, 0, bands, gains)), (bands, gains)
+
+
+@pytest.mark.parametrize("level", range(mc.TILE_BANDS + 1))
+def test_device_is_the_host_twin_where_windows_meet_tile_edges(lib, level):
+    """A 3-band run in which one image's window at `level` is a tile width (31 .. 33, 63 .. 65) or height (3 .. 5, 7 .. 9) wide."""
+    keys = sorted(k for k in TILES if k[1] == level)
+    assert keys
+    for key in keys:
+        images, Gs = TILES[key]
+        assert np.array_equal(mc.device(lib, images, Gs, 0, mc.TILE_BANDS), mc.host(lib, images, Gs, 0, mc.TILE_BANDS)), key
+
+
+def test_device_is_the_host_twin_on_canvases_of_a_tile_plus_minus_one(lib):
+    for fw, fh, images, Gs in mc.plane_edge_cases():
+        for bands in (1, 3):
+            assert np.array_equal(mc.device(lib, images, Gs, 0, bands), mc.host(lib, images, Gs, 0, bands)), (fw, fh, bands)
+
+
+# ---- other cases ----
+def test_a_top_level_of_one_pixel(lib):
+    images, Gs = mc.one_by_one_top()
+    got = mc.device(lib, images, Gs, 0, 4)
+    assert np.array_equal(got, mc.host(lib, images, Gs, 0, 4)) and np.array_equal(got, images[0])
+
+
+@pytest.mark.parametrize("case", GENERAL, ids=[c[0].replace(" ", "-") for c in GENERAL])
+def test_device_is_the_host_twin_on_general_cases(lib, case):
+    _, images, Gs, anchor, _ = case
+    assert np.array_equal(mc.device(lib, images, Gs, anchor, 3), mc.host(lib, images, Gs, anchor, 3))
+    g = gc.mixed_gains(len(images))
+    assert np.array_equal(mc.device(lib, images, Gs, anchor, 3, g), mc.host(lib, images, Gs, anchor, 3, g))
+
+
+def test_the_call_does_not_depend_on_what_the_workspace_held(lib):
+    """The strip of 64 twice into one workspace, another case's planes left in it in between."""
+    import torch
+    images, Gs = sc.translated_strip(64)
+    _, other, oG, oa, _ = GENERAL[4]
+    want = mc.host(lib, images, Gs, 0, 2)
+    need = max(mc.workspace_bytes(lib, sc.tables(images, Gs, 0), 2), mc.workspace_bytes(lib, sc.tables(other, oG, oa), 3))
+    ws = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
+    dev = mc.upload(images)
+    assert np.array_equal(mc.device(lib, images, Gs, 0, 2, on=dev, workspace=ws), want)
+    assert np.array_equal(mc.device(lib, other, oG, oa, 3, workspace=ws), mc.host(lib, other, oG, oa, 3))
+    assert np.array_equal(mc.device(lib, images, Gs, 0, 2, on=dev, workspace=ws), want)
+    assert (ws[need:].cpu().numpy() == 0xA5).all(), "a byte beyond the workspace's stated size was written"
+
+
+def test_on_a_second_stream(lib):
+    import torch
+    images, Gs = sc.translated_strip(64)
+    got = mc.device(lib, images, Gs, 0, 2, stream=torch.cuda.Stream())
+    assert np.array_equal(got, mc.host(lib, images, Gs, 0, 2))
+
+
+def test_forty_candidates_in_one_tile(lib):
+    images, Gs = gc.forty_in_one_tile()
+    assert np.array_equal(mc.device(lib, images, Gs, 0, 1), mc.host(lib, images, Gs, 0, 1))
+
+
+def test_a_workspace_too_small_or_misaligned_is_refused(lib):
+    import torch
+    images, Gs = sc.translated_strip(3)
+    t = sc.tables(images, Gs, 0)
+    fh, fw = t["size"]
+    dev = mc.upload(images)
+    ptrs = np.array([d.data_ptr() for d in dev], dtype=np.uint64)
+    need = mc.workspace_bytes(lib, t, 2)
+    ws = torch.zeros((need + 8,), dtype=torch.uint8, device="cuda")
+    can = torch.full((fh, fw, 3), 0xA5, dtype=torch.uint8, device="cuda")
+
+    def call(wp, wb, bands=2):
+        return lib.rwh_stitch_multiband(ptrs.ctypes.data, t["hw"].ctypes.data, t["inv"].ctypes.data, t["rects"].ctypes.data, 3, 0, bands, None,
+                                        can.data_ptr(), fh, fw, 0, 0, wp, wb, torch.cuda.current_stream().cuda_stream)
+    assert call(ws.data_ptr(), need - 1) == -1 and call(ws.data_ptr() + 4, need) == -1 and call(None, need) == -1
+    assert call(ws.data_ptr(), need, bands=0) == -1 and call(ws.data_ptr(), need, bands=9) == -1
+    torch.cuda.synchronize()
+    assert (can.cpu().numpy() == 0xA5).all(), "a refused call wrote the canvas"
+    assert call(ws.data_ptr(), need) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(can.cpu().numpy(), mc.host(lib, images, Gs, 0, 2))
+
+
+# ---- the Python layers ----
+def test_kernels_entry(lib):
+    import torch
+    from ransac_with_homography_amd import kernels
+    _, images, Gs, anchor, _ = GENERAL[3]
+    t = sc.tables(images, Gs, anchor)
+    dev = mc.upload(images)
+    g = gc.mixed_gains(len(images))
+    out = kernels.stitch_sequence_multiband(dev, t["inv"], t["rects"], anchor, t["origin"], t["size"], 3, gains=g)
+    assert out.dtype == torch.uint8 and out.is_cuda and np.array_equal(out.cpu().numpy(), mc.host(lib, images, Gs, anchor, 3, g))
+    into = torch.zeros_like(out)
+    assert kernels.stitch_sequence_multiband(dev, t["inv"], t["rects"], anchor, t["origin"], t["size"], 3, out=into) is into
+    assert np.array_equal(into.cpu().numpy(), mc.host(lib, images, Gs, anchor, 3))
+    with pytest.raises(ValueError):
+        kernels.stitch_sequence_multiband(dev, t["inv"], t["rects"], anchor, t["origin"], t["size"], 9)
+    with pytest.raises(ValueError):
+        kernels.stitch_sequence_multiband(dev, t["inv"], t["rects"], 7, t["origin"], t["size"], 3)
+
+
+def test_stitch_sequence_entry_numpy_and_tensors(lib):
+    import torch
+    import homography as hg
+    _, images, Gs, anchor, _ = GENERAL[2]
+    before = [im.copy() for im in images]
+    want = mc.host(lib, images, Gs, anchor, 3)
+    got = hg.stitchSequence(images, Gs=Gs, anchor=anchor, blending="multiband", bands=3, order=[2, 0, 1])
+    assert isinstance(got, np.ndarray) and got.dtype == np.uint8 and np.array_equal(got, want)
+    assert all(np.array_equal(a, b) for a, b in zip(images, before))
+    dev = mc.upload(images)
+    keep = [d.clone() for d in dev]
+    out = hg.stitchSequence(dev, Gs=Gs, anchor=anchor, blending="multiband", bands=3)
+    assert isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev[0].device and np.array_equal(out.cpu().numpy(), want)
+    assert all(torch.equal(a, b) for a, b in zip(dev, keep))
+    assert np.array_equal(hg.stitchSequence(images, Gs=Gs, anchor=anchor, blending="multiband"), mc.host(lib, images, Gs, anchor, 5))
+
+
+def test_auto_gains_are_the_gains_given(lib):
+    import homography as hg
+    images, Gs = gc.exposure_fixture()
+    info = {}
+    auto = hg.stitchSequence(images, Gs=Gs, blending="multiband", bands=3, gains="auto", info=info)
+    g = hg.sequence_gains(images, Gs=Gs)
+    assert np.array_equal(info["gains"], g) and not np.array_equal(g, np.ones(3))
+    assert np.array_equal(auto, hg.stitchSequence(images, Gs=Gs, blending="multiband", bands=3, gains=g))
+    assert np.array_equal(auto, mc.host(lib, images, Gs, 0, 3, g))
+
+
+def test_pipeline_on_three_crops_of_one_scene(lib):
+    import homography as hg
+    import ransac as rs
+    scene = sc.scene()
+    crops = [np.ascontiguousarray(scene[:, x:x + 260]) for x in (0, 90, 180)]
+    info = {}
+    can = rs.stitch_sequence(crops, th=TH, blending="multiband", bands=3, info=info)
+    assert isinstance(can, np.ndarray) and info["Hs"].shape == (2, 3, 3)
+    assert np.array_equal(can, hg.stitchSequence(crops, Hs=info["Hs"], blending="multiband", bands=3))
