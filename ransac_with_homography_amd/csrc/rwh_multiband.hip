@@ -206,34 +206,28 @@ __host__ __device__ __forceinline__ uint64_t mb_window_mask(const MbArgs& m, int
 }
 
 // ---- the kernels ----
-template <bool GAIN> struct MbLaunch { MbArgs m; };
-template <> struct MbLaunch<true> { MbArgs m; double gains[RWH_SEQ_MAX_IMAGES]; };
-template <bool GAIN> __host__ __device__ __forceinline__ const double* mb_gains(const MbLaunch<GAIN>& l) {
-    if constexpr (GAIN) return l.gains; else return nullptr;
-}
-
 // 256 lanes as 64 x 4, one pixel of the padded canvas each; the tile is tested once against the n rectangles (block-uniform).
 template <bool GAIN>
-__global__ __launch_bounds__(256) void mb_winner_kernel(const MbLaunch<GAIN> l) {
-    const MbArgs& m = l.m;
+__global__ __launch_bounds__(256) void mb_winner_kernel(const SeqWith<MbArgs, GAIN> l) {
+    const MbArgs& m = l.a;
     const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
     const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
     const int x = bx0 + (threadIdx.x & 63), y = by0 + (threadIdx.x >> 6);
     if (x >= m.PW || y >= m.PH) return;
     const bool on = x < m.a.fw && y < m.a.fh;
-    m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<GAIN>(m.a, cand, x, y, mb_gains(l)) : MB_NONE << 24;
+    m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<GAIN>(m.a, cand, x, y, seq_gains(l)) : MB_NONE << 24;
 }
 
 // blockIdx.z is the image; a block takes 64 x 4 pixels of its level-0 window (blocks beyond the window leave at once).
 template <bool GAIN>
-__global__ __launch_bounds__(256) void mb_level0_kernel(const MbLaunch<GAIN> l) {
-    const MbArgs& m = l.m;
+__global__ __launch_bounds__(256) void mb_level0_kernel(const SeqWith<MbArgs, GAIN> l) {
+    const MbArgs& m = l.a;
     const int i = blockIdx.z;
     const MbWin w = m.win[(size_t)i * (m.K + 1)];
     const int lx = blockIdx.x * 64 + (threadIdx.x & 63), ly = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (lx >= w.w || ly >= w.h) return;
     const int x = w.x0 + lx, y = w.y0 + ly;
-    m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, mb_gains(l));
+    m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l));
 }
 
 // The reduce from level l to l + 1 of image blockIdx.z.  A block makes MB_TW x MB_TH outputs from a (2 MB_TW + 3) x (2 MB_TH + 3)
@@ -282,23 +276,6 @@ __global__ __launch_bounds__(256) void mb_collapse_kernel(const MbArgs m, int l)
     mb_store(m, l, x, y, R);
 }
 
-// Host tables travel in kernel arguments, MB_PUT words per launch, and this kernel lays them down in the workspace (stream-ordered:
-// nothing on the host has to outlive the call), as rwh_stitch_sequence does with its descriptors.
-constexpr int MB_PUT = 416;
-struct MbPut { uint64_t w[MB_PUT]; };
-__global__ __launch_bounds__(256) void mb_put_kernel(const MbPut c, uint64_t* out, int words) {
-    for (int t = threadIdx.x; t < words; t += 256) out[t] = c.w[t];
-}
-static void mb_put(const void* host, size_t words, uint64_t* dev, hipStream_t s) {
-    for (size_t at = 0; at < words; at += MB_PUT) {
-        const int cnt = (int)(words - at < (size_t)MB_PUT ? words - at : (size_t)MB_PUT);
-        MbPut c;
-        memset(&c, 0, sizeof(c));
-        memcpy(c.w, static_cast<const uint64_t*>(host) + at, (size_t)cnt * 8);
-        hipLaunchKernelGGL(mb_put_kernel, dim3(1), dim3(256), 0, s, c, dev + at, cnt);
-    }
-}
-
 // ---- the plan: windows and workspace layout (include/rwh.h, "Working in windows") ----
 struct MbPlan {
     int K, PW, PH;
@@ -342,7 +319,7 @@ static int64_t mb_align(int64_t v) { return (v + 127) & ~(int64_t)127; }
 // What the size function and both entry points check of the geometry, and the plan.
 static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y, int bands, MbPlan& p) {
     if (!rects || n < 1 || n > RWH_SEQ_MAX_IMAGES || bands < 1 || bands > RWH_SEQ_MAX_BANDS) return RWH_E_INVALID;
-    if (canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535 || (int64_t)canvas_h * canvas_w * 3 > INT32_MAX) return RWH_E_INVALID;
+    if (!seq_canvas_ok(canvas_h, canvas_w)) return RWH_E_INVALID;
     const int K = bands, mask = (1 << K) - 1;
     p.K = K; p.PW = (canvas_w + mask) & ~mask; p.PH = (canvas_h + mask) & ~mask;
     for (int l = 0; l <= K; ++l) p.maxw[l] = p.maxh[l] = 0;
@@ -378,11 +355,7 @@ static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int 
 static int mb_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor, int bands,
                       const double* gains, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, MbArgs& m,
                       MbPlan& p) {
-    if (bands < 1 || bands > RWH_SEQ_MAX_BANDS || n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;
-    int32_t order[RWH_SEQ_MAX_IMAGES];
-    for (int k = 0; k < n; ++k) order[k] = k;
-    int st = seq_prepare(images, hw, inv_g, rects, n, anchor, order, RWH_SEQ_FEATHER, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                         0, canvas_h, descs, m.a);
+    int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m.a);
     if (st != RWH_OK) return st;
     if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
     st = mb_plan(rects, n, canvas_h, canvas_w, origin_x, origin_y, bands, p);
@@ -403,12 +376,7 @@ static void mb_bind(MbArgs& m, const MbPlan& p, char* base) {
 
 template <bool GAIN>
 static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains, hipStream_t s) {
-    MbLaunch<GAIN> l;
-    l.m = m;
-    if constexpr (GAIN) {
-        memset(l.gains, 0, sizeof(l.gains));
-        memcpy(l.gains, gains, (size_t)m.a.n * sizeof(double));
-    }
+    const SeqWith<MbArgs, GAIN> l = seq_with<GAIN>(m, gains, m.a.n);
     hipLaunchKernelGGL((mb_winner_kernel<GAIN>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
     hipLaunchKernelGGL((mb_level0_kernel<GAIN>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
 }
@@ -416,7 +384,7 @@ static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains
 template <bool GAIN>
 static void mb_host_run(const MbArgs& m, const MbPlan& p, const double* gains) {
     const int n = m.a.n, K = p.K;
-    const uint64_t all = n == 64 ? ~0ull : (1ull << n) - 1;
+    const uint64_t all = seq_all(n);
     for (int y = 0; y < p.PH; ++y)
         for (int x = 0; x < p.PW; ++x)
             m.pw[(int64_t)y * p.PW + x] = (x < m.a.fw && y < m.a.fh) ? mb_winner_pixel<GAIN>(m.a, all, x, y, gains) : MB_NONE << 24;
@@ -463,8 +431,8 @@ extern "C" int rwh_stitch_multiband(const void* const* d_images, const int32_t* 
     if (!d_workspace || workspace_bytes < p.bytes || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(d_workspace);
-    mb_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
-    mb_put(p.win, (size_t)n * (p.K + 1) * (sizeof(MbWin) / 8), reinterpret_cast<uint64_t*>(base + p.win_at), s);
+    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
+    seq_put(p.win, (size_t)n * (p.K + 1) * (sizeof(MbWin) / 8), reinterpret_cast<uint64_t*>(base + p.win_at), s);
     mb_bind(m, p, base);
     if (gains) mb_launch_head<true>(m, p, gains, s); else mb_launch_head<false>(m, p, nullptr, s);
     for (int l = 0; l < p.K; ++l)

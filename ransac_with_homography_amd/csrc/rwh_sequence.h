@@ -5,6 +5,7 @@
 #define RWH_SEQUENCE_H
 #include <math.h>
 #include <string.h>
+#include <type_traits>
 #include "rwh_common.h"
 
 namespace rwh {
@@ -28,6 +29,22 @@ struct SeqArgs {
     int row_begin, row_end;     // canvas rows this call produces
     unsigned char order[RWH_SEQ_MAX_IMAGES];   // paste: priority order; feather: 0 .. n-1
 };
+
+// The arguments of one launch: A, and with GAIN the N gains of the gain rule behind it (512 B: the arguments stay under 4 KB).
+template <class A, bool GAIN> struct SeqWith { A a; };
+template <class A> struct SeqWith<A, true> { A a; double gains[RWH_SEQ_MAX_IMAGES]; };
+template <class A, bool GAIN> __host__ __device__ __forceinline__ const double* seq_gains(const SeqWith<A, GAIN>& l) {
+    if constexpr (GAIN) return l.gains; else return nullptr;
+}
+template <bool GAIN, class A> static SeqWith<A, GAIN> seq_with(const A& a, const double* gains, int n) {
+    SeqWith<A, GAIN> l;
+    l.a = a;
+    if constexpr (GAIN) {
+        memset(l.gains, 0, sizeof(l.gains));
+        memcpy(l.gains, gains, (size_t)n * sizeof(double));
+    }
+    return l;
+}
 
 // One RGB texel as a dword: an unaligned 4-byte load (3 bytes used) unless that would step past the image's last byte.
 __host__ __device__ __forceinline__ uint32_t seq_rgb_at(const unsigned char* base, size_t off, size_t img_bytes) {
@@ -128,13 +145,22 @@ __host__ __device__ __forceinline__ uint64_t seq_tile_mask(const SeqArgs& a, int
     return m;
 }
 
+// "All n images" as candidate bits.
+static uint64_t seq_all(int n) { return n == 64 ? ~0ull : (1ull << n) - 1; }
+
+// The canvas every rule of the family takes: sides of 1 .. 65535, byte offsets within int32.
+static bool seq_canvas_ok(int h, int w) { return h >= 1 && w >= 1 && h <= 65535 && w <= 65535 && (int64_t)h * w * 3 <= INT32_MAX; }
+
+// Lays `words` eight-byte words of a host table down at `dev` on the stream (rwh_sequence.hip).
+void seq_put(const void* host, size_t words, uint64_t* dev, hipStream_t s);
+
 // Everything both entry points check, and the descriptors / arguments they share.  descs: room for RWH_SEQ_MAX_IMAGES.
 static int seq_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
                        const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
                        int row_begin, int row_end, SeqDesc* descs, SeqArgs& a) {
     if (!images || !hw || !inv_g || !rects || !order || !canvas) return RWH_E_INVALID;
     if (n < 1 || n > RWH_SEQ_MAX_IMAGES || anchor < 0 || anchor >= n || (blend != RWH_SEQ_PASTE && blend != RWH_SEQ_FEATHER)) return RWH_E_INVALID;
-    if (canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535 || (int64_t)canvas_h * canvas_w * 3 > INT32_MAX) return RWH_E_INVALID;
+    if (!seq_canvas_ok(canvas_h, canvas_w)) return RWH_E_INVALID;
     if (row_begin < 0 || row_end > canvas_h || row_begin > row_end) return RWH_E_INVALID;
     uint64_t seen = 0;
     for (int k = 0; k < n; ++k) {
@@ -163,6 +189,22 @@ static int seq_prepare(const void* const* images, const int32_t* hw, const doubl
     memset(a.order, 0, sizeof(a.order));
     for (int k = 0; k < n; ++k) a.order[k] = (unsigned char)(blend == RWH_SEQ_FEATHER ? k : order[k]);   // feather: index order
     return RWH_OK;
+}
+
+// seq_prepare for the rules that take the images in index order over the whole canvas: the identity order, feather, all rows.
+static int seq_prepare_indexed(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
+                               void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, SeqArgs& a) {
+    if (n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;     // (before order[] is filled)
+    int32_t order[RWH_SEQ_MAX_IMAGES];
+    for (int k = 0; k < n; ++k) order[k] = k;
+    return seq_prepare(images, hw, inv_g, rects, n, anchor, order, RWH_SEQ_FEATHER, canvas, canvas_h, canvas_w, origin_x, origin_y,
+                       0, canvas_h, descs, a);
+}
+
+// f(feather, gain), the two flags as std::true_type / std::false_type: the four forms of the compositor, device and host.
+template <class F> static void seq_dispatch(bool feather, bool gain, const F& f) {
+    if (gain) { if (feather) f(std::true_type{}, std::true_type{}); else f(std::false_type{}, std::true_type{}); }
+    else { if (feather) f(std::true_type{}, std::false_type{}); else f(std::false_type{}, std::false_type{}); }
 }
 
 // The gains of the gain rule: N values, each finite and > 0.

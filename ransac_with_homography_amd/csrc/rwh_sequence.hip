@@ -11,15 +11,9 @@ namespace rwh {
 // A block's 256 x 4 tile is tested once against the n rectangles; blockIdx and the descriptor indices are wave-uniform, so the
 // test and the descriptor reads of the pixel loop stay on the scalar side.
 constexpr int SEQ_PX = 4;
-// The arguments of one launch: SeqArgs, and with GAIN the N gains behind it (512 B: the arguments stay under 4 KB).
-template <bool GAIN> struct SeqLaunch { SeqArgs a; };
-template <> struct SeqLaunch<true> { SeqArgs a; double gains[RWH_SEQ_MAX_IMAGES]; };
-template <bool GAIN> __host__ __device__ __forceinline__ const double* seq_gains(const SeqLaunch<GAIN>& l) {
-    if constexpr (GAIN) return l.gains; else return nullptr;
-}
 
 template <bool FEATHER, bool GAIN = false>
-__global__ __launch_bounds__(256) void seq_kernel(const SeqLaunch<GAIN> l) {
+__global__ __launch_bounds__(256) void seq_kernel(const SeqWith<SeqArgs, GAIN> l) {
     const SeqArgs& a = l.a;
     const int bx0 = blockIdx.x * 64 * SEQ_PX, by0 = a.row_begin + blockIdx.y * 4;
     const uint64_t cand = seq_tile_mask(a, bx0, bx0 + 64 * SEQ_PX, by0, by0 + 4);
@@ -41,39 +35,27 @@ __global__ __launch_bounds__(256) void seq_kernel(const SeqLaunch<GAIN> l) {
     }
 }
 
-// The descriptor table travels in kernel arguments, SEQ_PUT descriptors per launch (64 of them are 6.5 KB: more than one launch's
-// 4 KB of arguments), and this kernel lays them down in the workspace: stream-ordered, no host buffer that has to outlive the call.
-constexpr int SEQ_PUT = 32;
-struct SeqPut { uint64_t w[SEQ_PUT * SEQ_DESC_WORDS]; };
+// A host table of the family (descriptors, the multi-band windows) travels in kernel arguments, SEQ_PUT_WORDS eight-byte words per
+// launch (64 descriptors are 6.5 KB: more than one launch's 4 KB of arguments), and this kernel lays them down in the workspace:
+// stream-ordered, no host buffer that has to outlive the call.
+constexpr int SEQ_PUT_WORDS = 32 * SEQ_DESC_WORDS;
+struct SeqPut { uint64_t w[SEQ_PUT_WORDS]; };
 __global__ __launch_bounds__(256) void seq_put_kernel(const SeqPut c, uint64_t* out, int words) {
     for (int t = threadIdx.x; t < words; t += 256) out[t] = c.w[t];
 }
-
-// Lays the n descriptors down at `table` (device), SEQ_PUT per launch.
-static void seq_put_table(const SeqDesc* descs, int n, uint64_t* table, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += SEQ_PUT) {
-        const int cnt = n - i0 < SEQ_PUT ? n - i0 : SEQ_PUT;
+void seq_put(const void* host, size_t words, uint64_t* dev, hipStream_t s) {
+    for (size_t at = 0; at < words; at += SEQ_PUT_WORDS) {
+        const int cnt = (int)(words - at < (size_t)SEQ_PUT_WORDS ? words - at : (size_t)SEQ_PUT_WORDS);
         SeqPut c;
         memset(&c, 0, sizeof(c));
-        memcpy(c.w, descs + i0, (size_t)cnt * sizeof(SeqDesc));
-        hipLaunchKernelGGL(seq_put_kernel, dim3(1), dim3(256), 0, s, c, table + (size_t)i0 * SEQ_DESC_WORDS, cnt * SEQ_DESC_WORDS);
+        memcpy(c.w, static_cast<const uint64_t*>(host) + at, (size_t)cnt * 8);
+        hipLaunchKernelGGL(seq_put_kernel, dim3(1), dim3(256), 0, s, c, dev + at, cnt);
     }
 }
 
 template <bool FEATHER, bool GAIN>
-static void seq_launch(const SeqArgs& a, const double* gains, dim3 grid, hipStream_t s) {
-    SeqLaunch<GAIN> l;
-    l.a = a;
-    if constexpr (GAIN) {
-        memset(l.gains, 0, sizeof(l.gains));
-        memcpy(l.gains, gains, (size_t)a.n * sizeof(double));
-    }
-    hipLaunchKernelGGL((seq_kernel<FEATHER, GAIN>), grid, dim3(256), 0, s, l);
-}
-
-template <bool FEATHER, bool GAIN = false>
-static void seq_host_rows(const SeqArgs& a, const double* gains = nullptr) {
-    const uint64_t all = a.n == 64 ? ~0ull : (1ull << a.n) - 1;
+static void seq_host_rows(const SeqArgs& a, const double* gains) {
+    const uint64_t all = seq_all(a.n);
     for (int cy = a.row_begin; cy < a.row_end; ++cy)
         for (int cx = 0; cx < a.fw; ++cx) {
             const uint32_t p = seq_pixel<FEATHER, GAIN>(a, all, cx, cy, gains);
@@ -207,11 +189,8 @@ static int64_t seq_stat_table_bytes(int n) { return ((int64_t)n * (int64_t)sizeo
 static int seq_stat_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
                             int canvas_h, int canvas_w, int origin_x, int origin_y, int stride, uint64_t* count, uint64_t* sum,
                             SeqDesc* descs, StatArgs& s) {
-    if (!count || !sum || stride < 1 || stride > 255 || n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;
-    int32_t order[RWH_SEQ_MAX_IMAGES];
-    for (int k = 0; k < n; ++k) order[k] = k;
-    const int st = seq_prepare(images, hw, inv_g, rects, n, anchor, order, RWH_SEQ_FEATHER, count, canvas_h, canvas_w, origin_x, origin_y,
-                               0, canvas_h, descs, s.a);
+    if (!count || !sum || stride < 1 || stride > 255) return RWH_E_INVALID;
+    const int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, count, canvas_h, canvas_w, origin_x, origin_y, descs, s.a);
     if (st != RWH_OK) return st;
     s.a.dst = nullptr;
     s.stride = stride;
@@ -244,16 +223,13 @@ extern "C" int rwh_stitch_sequence_ex(const void* const* d_images, const int32_t
     if (row_begin == row_end) return RWH_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint64_t* table = static_cast<uint64_t*>(d_workspace);
-    seq_put_table(descs, n, table, s);
+    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
     a.desc = reinterpret_cast<const SeqDesc*>(table);
     const dim3 grid((canvas_w + 64 * SEQ_PX - 1) / (64 * SEQ_PX), (row_end - row_begin + 3) / 4);
-    if (gains) {
-        if (blend == RWH_SEQ_FEATHER) seq_launch<true, true>(a, gains, grid, s);
-        else seq_launch<false, true>(a, gains, grid, s);
-    } else {
-        if (blend == RWH_SEQ_FEATHER) seq_launch<true, false>(a, nullptr, grid, s);
-        else seq_launch<false, false>(a, nullptr, grid, s);
-    }
+    seq_dispatch(blend == RWH_SEQ_FEATHER, gains != nullptr, [&](auto feather, auto gain) {
+        hipLaunchKernelGGL((seq_kernel<decltype(feather)::value, decltype(gain)::value>), grid, dim3(256), 0, s,
+                           seq_with<decltype(gain)::value>(a, gains, n));
+    });
     return check_launch();
 }
 
@@ -275,13 +251,8 @@ extern "C" int rwh_host_stitch_sequence_ex(const void* const* images, const int3
                                row_begin, row_end, descs, a);
     if (st != RWH_OK) return st;
     if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
-    if (gains) {
-        if (blend == RWH_SEQ_FEATHER) seq_host_rows<true, true>(a, gains);
-        else seq_host_rows<false, true>(a, gains);
-    } else {
-        if (blend == RWH_SEQ_FEATHER) seq_host_rows<true>(a);
-        else seq_host_rows<false>(a);
-    }
+    seq_dispatch(blend == RWH_SEQ_FEATHER, gains != nullptr,
+                 [&](auto feather, auto gain) { seq_host_rows<decltype(feather)::value, decltype(gain)::value>(a, gains); });
     return RWH_OK;
 }
 
@@ -294,7 +265,7 @@ extern "C" int rwh_host_stitch_sequence(const void* const* images, const int32_t
 
 extern "C" int64_t rwh_sequence_overlap_stats_workspace_bytes(int n, int canvas_h, int canvas_w, int stride) {
     if (n < 1 || n > RWH_SEQ_MAX_IMAGES || stride < 1 || stride > 255) return RWH_E_INVALID;
-    if (canvas_h < 1 || canvas_w < 1 || canvas_h > 65535 || canvas_w > 65535 || (int64_t)canvas_h * canvas_w * 3 > INT32_MAX) return RWH_E_INVALID;
+    if (!rwh::seq_canvas_ok(canvas_h, canvas_w)) return RWH_E_INVALID;
     return rwh::seq_stat_table_bytes(n) + (int64_t)rwh::STAT_SLABS * rwh::seq_slab_words(n) * (int64_t)sizeof(uint64_t);
 }
 
@@ -313,7 +284,7 @@ extern "C" int rwh_sequence_overlap_stats(const void* const* d_images, const int
     uint64_t* table = static_cast<uint64_t*>(d_workspace);
     a.slabs = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_workspace) + seq_stat_table_bytes(n));
     if (hipMemsetAsync(a.slabs, 0, (size_t)STAT_SLABS * a.slab_words * sizeof(uint64_t), s) != hipSuccess) return RWH_E_LAUNCH;
-    seq_put_table(descs, n, table, s);
+    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
     a.a.desc = reinterpret_cast<const SeqDesc*>(table);
     const dim3 grid((a.nsx + STAT_W - 1) / STAT_W, (a.nsy + STAT_H - 1) / STAT_H);
     hipLaunchKernelGGL(seq_stats_kernel, grid, dim3(256), 0, s, a);
@@ -334,7 +305,7 @@ extern "C" int rwh_host_sequence_overlap_stats(const void* const* images, const 
     uint64_t* sm = sum;
     memset(cnt, 0, (size_t)n * n * sizeof(uint64_t));
     memset(sm, 0, (size_t)n * n * sizeof(uint64_t));
-    const uint64_t all = n == 64 ? ~0ull : (1ull << n) - 1;
+    const uint64_t all = seq_all(n);
     for (int v = 0; v < a.nsy; ++v)
         for (int u = 0; u < a.nsx; ++u) {
             const int cx = u * stride, cy = v * stride;

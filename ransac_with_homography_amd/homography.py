@@ -862,8 +862,7 @@ def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, s
 
 
 def _check_bands(who, bands):
-    if not (isinstance(bands, (int, np.integer)) and not isinstance(bands, bool) and 1 <= bands <= _lib.RWH_SEQ_MAX_BANDS):
-        raise ValueError("%s: bands %r; an integer of 1 .. %d" % (who, bands, _lib.RWH_SEQ_MAX_BANDS))
+    kernels.sequence_bands_check(who, bands)
 
 
 def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None, gains=None, info=None, bands=5):

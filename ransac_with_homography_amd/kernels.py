@@ -647,32 +647,64 @@ def sequence_gains_array(gains, n, who="stitch_sequence"):
     return g
 
 
-def sequence_overlap_tables(images, inv_g, rects, anchor, origin, canvas_hw, stride):
-    """`sequence_overlap_stats` with both tables in ONE int64 [2, n, n] tensor (count, sum): one copy brings them down."""
-    lib = _lib.load()
+def sequence_bands_check(who, bands):
+    """ValueError unless `bands` of the multi-band rule is an integer of 1 .. 8."""
+    if not (isinstance(bands, (int, np.integer)) and not isinstance(bands, bool) and 1 <= bands <= _lib.RWH_SEQ_MAX_BANDS):
+        raise ValueError("%s: bands %r; an integer of 1 .. %d" % (who, bands, _lib.RWH_SEQ_MAX_BANDS))
+
+
+def _sequence_marshal(who, images, inv_g, rects, canvas_hw, order=None, own=None):
+    """What every launcher of the sequence family checks and lays out -> (n, fh, fw, ptrs, hw, inv_g, rects, order), `order` the
+    index order when none is given.  own(): the launcher's own refusals, which come before the canvas's.  The library gets raw
+    addresses: the caller holds the arrays until its call has returned."""
     _dev_check(*images)
     n = len(images)
     for t in images:
         assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
     fh, fw = (int(v) for v in canvas_hw)
-    if not (1 <= n <= SEQ_MAX_IMAGES) or len(rects) != n or len(inv_g) != n:
-        raise ValueError("sequence_overlap_stats: %d images (1 .. %d), %d rectangles, %d matrices" % (n, SEQ_MAX_IMAGES, len(rects), len(inv_g)))
-    if not (isinstance(stride, (int, np.integer)) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
-        raise ValueError("sequence_overlap_stats: stride %r; 1 .. %d" % (stride, _lib.RWH_SEQ_MAX_STRIDE))
+    if not (1 <= n <= SEQ_MAX_IMAGES) or (order is not None and len(order) != n) or len(rects) != n or len(inv_g) != n:
+        raise ValueError("%s: %d images (1 .. %d), %d rectangles, %d matrices%s"
+                         % (who, n, SEQ_MAX_IMAGES, len(rects), len(inv_g), "" if order is None else ", order of %d" % len(order)))
+    if own is not None:
+        own()
     if not (1 <= fh <= 65535 and 1 <= fw <= 65535 and fh * fw * 3 <= 2 ** 31 - 1):
-        raise ValueError("sequence_overlap_stats: a %d x %d canvas; sides of 1 .. 65535 and at most 2^31 - 1 bytes" % (fh, fw))
-    hw, ig, rc, _ = sequence_tables([t.shape for t in images], inv_g, rects, list(range(n)))
-    ptrs = np.array([t.data_ptr() for t in images], dtype=np.uint64)
+        raise ValueError("%s: a %d x %d canvas; sides of 1 .. 65535 and at most 2^31 - 1 bytes" % (who, fh, fw))
+    hw, ig, rc, od = sequence_tables([t.shape for t in images], inv_g, rects, list(range(n)) if order is None else order)
+    return n, fh, fw, np.array([t.data_ptr() for t in images], dtype=np.uint64), hw, ig, rc, od
+
+
+def _sequence_canvas(images, fh, fw, out):
+    """`out` when given, else a new tensor: uint8 [fh, fw, 3] on the device."""
+    if out is None:
+        return torch.empty((fh, fw, 3), dtype=torch.uint8, device=images[0].device)
+    _dev_check(out)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (fh, fw, 3)
+    return out
+
+
+def _sequence_status(status, what, refused):
+    """RWH_E_INVALID -> ValueError(refused); any other status through `check`."""
+    if status == _lib.RWH_E_INVALID:
+        raise ValueError(refused)
+    check(status, what)
+
+
+def sequence_overlap_tables(images, inv_g, rects, anchor, origin, canvas_hw, stride):
+    """`sequence_overlap_stats` with both tables in ONE int64 [2, n, n] tensor (count, sum): one copy brings them down."""
+    lib = _lib.load()
+
+    def own():
+        if not (isinstance(stride, (int, np.integer)) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
+            raise ValueError("sequence_overlap_stats: stride %r; 1 .. %d" % (stride, _lib.RWH_SEQ_MAX_STRIDE))
+    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal("sequence_overlap_stats", images, inv_g, rects, canvas_hw, own=own)
     dev = images[0].device
     tabs = torch.empty((2, n, n), dtype=torch.int64, device=dev)
     ws = torch.empty((int(lib.rwh_sequence_overlap_stats_workspace_bytes(n, fh, fw, int(stride))) // 8,), dtype=torch.int64, device=dev)
     status = lib.rwh_sequence_overlap_stats(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), fh, fw,
                                             int(origin[0]), int(origin[1]), int(stride), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(ws),
                                             ws.numel() * 8, _lib.stream_ptr())
-    if status == _lib.RWH_E_INVALID:
-        raise ValueError("sequence_overlap_stats: the library refused the arguments (include/rwh.h, rwh_sequence_overlap_stats: anchor, "
-                         "rectangles on the canvas, finite inv(G), stride)")
-    check(status, "rwh_sequence_overlap_stats")
+    _sequence_status(status, "rwh_sequence_overlap_stats", "sequence_overlap_stats: the library refused the arguments (include/rwh.h, "
+                     "rwh_sequence_overlap_stats: anchor, rectangles on the canvas, finite inv(G), stride)")
     return tabs
 
 
@@ -694,31 +726,15 @@ def stitch_sequence(images, inv_g, rects, anchor, order, blend, origin, canvas_h
     lib = _lib.load()
     if gains is not None:
         gains = sequence_gains_array(gains, len(images))
-    _dev_check(*images)
-    n = len(images)
-    for t in images:
-        assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
-    fh, fw = (int(v) for v in canvas_hw)
-    if not (1 <= n <= SEQ_MAX_IMAGES) or len(order) != n or len(rects) != n or len(inv_g) != n:
-        raise ValueError("stitch_sequence: %d images (1 .. %d), %d rectangles, %d matrices, order of %d" % (n, SEQ_MAX_IMAGES, len(rects), len(inv_g), len(order)))
-    if not (1 <= fh <= 65535 and 1 <= fw <= 65535 and fh * fw * 3 <= 2 ** 31 - 1):
-        raise ValueError("stitch_sequence: a %d x %d canvas; sides of 1 .. 65535 and at most 2^31 - 1 bytes" % (fh, fw))
-    if out is None:
-        out = torch.empty((fh, fw, 3), dtype=torch.uint8, device=images[0].device)
-    else:
-        _dev_check(out)
-        assert out.dtype == torch.uint8 and tuple(out.shape) == (fh, fw, 3)
+    n, fh, fw, ptrs, hw, ig, rc, od = _sequence_marshal("stitch_sequence", images, inv_g, rects, canvas_hw, order)
+    out = _sequence_canvas(images, fh, fw, out)
     r0, r1 = (0, fh) if rows is None else (int(rows[0]), int(rows[1]))
-    hw, ig, rc, od = sequence_tables([t.shape for t in images], inv_g, rects, order)
-    ptrs = np.array([t.data_ptr() for t in images], dtype=np.uint64)
     ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
     args = (ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), od.ctypes.data, int(blend), _ptr(out), fh, fw,
             int(origin[0]), int(origin[1]), r0, r1, _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
     status = lib.rwh_stitch_sequence(*args) if gains is None else lib.rwh_stitch_sequence_ex(*args, gains.ctypes.data)
-    if status == _lib.RWH_E_INVALID:
-        raise ValueError("stitch_sequence: the library refused the arguments (include/rwh.h, rwh_stitch_sequence: order, anchor, "
-                         "rectangles on the canvas, finite inv(G), row range)")
-    check(status, "rwh_stitch_sequence")
+    _sequence_status(status, "rwh_stitch_sequence", "stitch_sequence: the library refused the arguments (include/rwh.h, "
+                     "rwh_stitch_sequence: order, anchor, rectangles on the canvas, finite inv(G), row range)")
     return out
 
 
@@ -728,38 +744,21 @@ def stitch_sequence_multiband(images, inv_g, rects, anchor, origin, canvas_hw, b
     -> canvas [fh, fw, 3] uint8 (`out` when given), on torch's current stream.  The workspace is allocated here, of
     rwh_stitch_multiband_workspace_bytes bytes.  What the library refuses (RWH_E_INVALID) raises ValueError."""
     lib = _lib.load()
+    who = "stitch_sequence_multiband"
     if gains is not None:
-        gains = sequence_gains_array(gains, len(images), "stitch_sequence_multiband")
-    _dev_check(*images)
-    n = len(images)
-    for t in images:
-        assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
-    fh, fw = (int(v) for v in canvas_hw)
-    if not (1 <= n <= SEQ_MAX_IMAGES) or len(rects) != n or len(inv_g) != n:
-        raise ValueError("stitch_sequence_multiband: %d images (1 .. %d), %d rectangles, %d matrices" % (n, SEQ_MAX_IMAGES, len(rects), len(inv_g)))
-    if not (isinstance(bands, (int, np.integer)) and not isinstance(bands, bool) and 1 <= bands <= _lib.RWH_SEQ_MAX_BANDS):
-        raise ValueError("stitch_sequence_multiband: bands %r; an integer of 1 .. %d" % (bands, _lib.RWH_SEQ_MAX_BANDS))
-    if not (1 <= fh <= 65535 and 1 <= fw <= 65535 and fh * fw * 3 <= 2 ** 31 - 1):
-        raise ValueError("stitch_sequence_multiband: a %d x %d canvas; sides of 1 .. 65535 and at most 2^31 - 1 bytes" % (fh, fw))
-    if out is None:
-        out = torch.empty((fh, fw, 3), dtype=torch.uint8, device=images[0].device)
-    else:
-        _dev_check(out)
-        assert out.dtype == torch.uint8 and tuple(out.shape) == (fh, fw, 3)
-    hw, ig, rc, _ = sequence_tables([t.shape for t in images], inv_g, rects, list(range(n)))
-    ptrs = np.array([t.data_ptr() for t in images], dtype=np.uint64)
-    refused = ValueError("stitch_sequence_multiband: the library refused the arguments (include/rwh.h, rwh_stitch_multiband: anchor, "
-                         "rectangles on the canvas, finite inv(G), bands)")
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal(who, images, inv_g, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
+    out = _sequence_canvas(images, fh, fw, out)
+    refused = ("stitch_sequence_multiband: the library refused the arguments (include/rwh.h, rwh_stitch_multiband: anchor, "
+               "rectangles on the canvas, finite inv(G), bands)")
     need = int(lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1]), int(bands)))
     if need <= 0:
-        raise refused
+        raise ValueError(refused)
     ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
     status = lib.rwh_stitch_multiband(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), int(bands),
                                       None if gains is None else gains.ctypes.data, _ptr(out), fh, fw, int(origin[0]), int(origin[1]),
                                       _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    if status == _lib.RWH_E_INVALID:
-        raise refused
-    check(status, "rwh_stitch_multiband")
+    _sequence_status(status, "rwh_stitch_multiband", refused)
     return out
 
 

@@ -1,6 +1,6 @@
-"""The gain rule (include/rwh.h: overlap statistics, gains, the compositor with gains) restated in numpy on top of
-tests/sequence_cases.py, the ctypes drivers of its host twins, and the fixtures that tests/test_sequence_gains_cpu.py and
-tests/test_sequence_gains_gpu.py share."""
+"""The gain rule (include/rwh.h: overlap statistics, gains) restated in numpy on top of tests/sequence_cases.py (which restates
+the compositor with gains and drives it), the ctypes drivers of the statistics' and the solver's host twins, and the fixtures that
+tests/test_sequence_gains_cpu.py and tests/test_sequence_gains_gpu.py share."""
 import numpy as np
 
 import sequence_cases as sc
@@ -76,35 +76,6 @@ def mismatch(count, I, g):
     return sum(float(count[i, j]) * (g[i] * I[i, j] - g[j] * I[j, i]) ** 2 for i in range(n) for j in range(n) if i != j)
 
 
-def restate(images, Gs, anchor=0, blend=sc.PASTE, order=None, gains=None):
-    """sequence_cases.restate with every sample value v of image i entering as min(v * g_i, 255.0) -> canvas uint8 [fh, fw, 3]."""
-    n = len(images)
-    gains = np.ones(n) if gains is None else np.asarray(gains, dtype=np.float64)
-    rects = sc.rectangles([im.shape for im in images], Gs, anchor)
-    (ox, oy), (fh, fw) = sc.canvas_of(rects)
-    parts = []
-    for i in range(n):
-        v, valid, g = sc.sample(images[i], Gs[i], rects[i], i == anchor)
-        parts.append((np.minimum(v * gains[i], 255.0), valid, g))
-    where = [(slice(r[1] - oy, r[1] - oy + r[3]), slice(r[0] - ox, r[0] - ox + r[2])) for r in rects]
-    can = np.zeros((fh, fw, 3), dtype=np.uint8)
-    if blend == sc.PASTE:
-        for i in reversed(sc.default_order(n, anchor) if order is None else list(order)):
-            v, valid, _ = parts[i]
-            win = can[where[i]]
-            win[valid] = v[valid].astype(np.int32).astype(np.uint8)
-        return can
-    num, den = np.zeros((fh, fw, 3)), np.zeros((fh, fw))
-    for i in range(n):
-        v, valid, g = parts[i]
-        nw, dw = num[where[i]], den[where[i]]
-        nw[valid] += g[valid][:, None] * v[valid]
-        dw[valid] += g[valid]
-    hit = den > 0
-    can[hit] = (num[hit] / den[hit][:, None]).astype(np.int32).astype(np.uint8)
-    return can
-
-
 # ---- the host twins ----
 def guarded_tables(n):
     """Two uint64 [n, n] tables pre-filled with 0xA5 bytes, each between two 64-byte canaries: -> (buffer uint8, count, sum, check)."""
@@ -142,21 +113,10 @@ def host_gains(lib, count, total, sigma_n=10.0, sigma_g=0.1):
     return st, buf[8:8 + n].copy()
 
 
-def host_twin_ex(lib, images, Gs, anchor=0, blend=sc.PASTE, order=None, rows=None, gains=None):
-    """rwh_host_stitch_sequence_ex -> (status, canvas), as sequence_cases.host_twin; gains None passes NULL."""
-    images = [np.ascontiguousarray(im) for im in images]
-    t = sc.tables(images, Gs, anchor, order)
-    fh, fw = t["size"]
-    buf = np.full(fh * fw * 3 + 128, 0xA5, dtype=np.uint8)
-    can = buf[64:64 + fh * fw * 3].reshape(fh, fw, 3)
-    ptrs = np.array([im.ctypes.data for im in images], dtype=np.uint64)
-    r0, r1 = (0, fh) if rows is None else rows
-    g = None if gains is None else np.ascontiguousarray(gains, dtype=np.float64)
-    st = lib.rwh_host_stitch_sequence_ex(ptrs.ctypes.data, t["hw"].ctypes.data, t["inv"].ctypes.data, t["rects"].ctypes.data, t["n"], anchor,
-                                         t["order"].ctypes.data, blend, can.ctypes.data, fh, fw, t["origin"][0], t["origin"][1], r0, r1,
-                                         None if g is None else g.ctypes.data)
-    assert (buf[:64] == 0xA5).all() and (buf[-64:] == 0xA5).all()
-    return st, can
+def hstats(lib, *a, **k):
+    st, count, total = host_stats(lib, *a, **k)
+    assert st == 0
+    return count, total
 
 
 # ---- the cases ----

@@ -103,15 +103,14 @@ def host_twin(lib, images, Gs, anchor=0, bands=5, gains=None, tweak=None):
     images = [np.ascontiguousarray(im) for im in images]
     t = sc.tables(images, Gs, anchor)
     fh, fw = t["size"]
-    buf = np.full(fh * fw * 3 + 128, 0xA5, dtype=np.uint8)
-    can = buf[64:64 + fh * fw * 3].reshape(fh, fw, 3)
+    can, check = sc.guarded_canvas(fh, fw)
     ptrs = np.array([im.ctypes.data for im in images], dtype=np.uint64)
     if tweak is not None:
         tweak(t, ptrs)
     g, gp = _gains_ptr(gains)
     st = lib.rwh_host_stitch_multiband(ptrs.ctypes.data, t["hw"].ctypes.data, t["inv"].ctypes.data, t["rects"].ctypes.data, t["n"], t["anchor"],
                                        bands, gp, can.ctypes.data, fh, fw, t["origin"][0], t["origin"][1])
-    assert (buf[:64] == 0xA5).all() and (buf[-64:] == 0xA5).all()
+    check()
     return st, can
 
 
@@ -119,11 +118,6 @@ def host(lib, *a, **k):
     st, can = host_twin(lib, *a, **k)
     assert st == 0
     return can
-
-
-def upload(images):
-    import torch
-    return [torch.from_numpy(np.ascontiguousarray(im)).cuda() for im in images]
 
 
 def workspace_bytes(lib, t, bands):
@@ -138,7 +132,7 @@ def device(lib, images, Gs, anchor=0, bands=5, gains=None, on=None, workspace=No
     import torch
     t = sc.tables(images, Gs, anchor)
     fh, fw = t["size"]
-    dev = upload(images) if on is None else on
+    dev = sc.upload(images) if on is None else on
     ptrs = np.array([d.data_ptr() for d in dev], dtype=np.uint64)
     need = workspace_bytes(lib, t, bands)
     assert need > 0
@@ -149,15 +143,13 @@ def device(lib, images, Gs, anchor=0, bands=5, gains=None, on=None, workspace=No
     g, gp = _gains_ptr(gains)
     torch.cuda.synchronize()                    # (the uploads and the workspace fill ran on the current stream)
     with torch.cuda.stream(s):
-        buf = torch.full((fh * fw * 3 + 128,), 0xA5, dtype=torch.uint8, device="cuda")
+        can, fetch = sc.guarded_device_canvas(fh, fw)
         st = lib.rwh_stitch_multiband(ptrs.ctypes.data, t["hw"].ctypes.data, t["inv"].ctypes.data, t["rects"].ctypes.data, t["n"], anchor, bands, gp,
-                                      buf.data_ptr() + 64, fh, fw, t["origin"][0], t["origin"][1], workspace.data_ptr(), workspace.numel(),
+                                      can.data_ptr(), fh, fw, t["origin"][0], t["origin"][1], workspace.data_ptr(), workspace.numel(),
                                       s.cuda_stream)
         assert st == 0, st
         s.synchronize()
-        flat = buf.cpu().numpy()
-    assert (flat[:64] == 0xA5).all() and (flat[-64:] == 0xA5).all(), "a byte outside the canvas was written"
-    return flat[64:-64].reshape(fh, fw, 3)
+        return fetch()
 
 
 # ---- the cases ----

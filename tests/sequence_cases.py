@@ -1,5 +1,5 @@
-"""The sequence rule (include/rwh.h, rwh_stitch_sequence) restated in numpy, the host twin's driver and the case makers that
-tests/test_sequence_cpu.py and tests/test_sequence_gpu.py share.  The restatement takes its coordinates from the oracle
+"""The sequence rule (include/rwh.h, rwh_stitch_sequence; with gains, the gain rule's compositor) restated in numpy, the drivers of
+the host twin and of the device call, the guarded canvases and the case makers that the tests/test_sequence*.py files share.  The restatement takes its coordinates from the oracle
 (`_source_coords`, `output_bounds`) and clamps the +1 taps where the oracle's `bilinear` raises IndexError."""
 import numpy as np
 
@@ -48,12 +48,14 @@ def sample(img, G, rect, is_anchor):
     return v, valid, g
 
 
-def restate(images, Gs, anchor=0, blend=PASTE, order=None):
-    """-> (canvas uint8 [fh, fw, 3], (ox, oy))."""
+def restate(images, Gs, anchor=0, blend=PASTE, order=None, gains=None):
+    """-> (canvas uint8 [fh, fw, 3], (ox, oy)).  gains: every sample value v of image i enters as min(v * g_i, 255.0); None: as it is."""
     n = len(images)
     rects = rectangles([im.shape for im in images], Gs, anchor)
     (ox, oy), (fh, fw) = canvas_of(rects)
     parts = [sample(images[i], Gs[i], rects[i], i == anchor) for i in range(n)]
+    if gains is not None:
+        parts = [(np.minimum(v * g, 255.0), valid, w) for (v, valid, w), g in zip(parts, np.asarray(gains, dtype=np.float64))]
     where = [(slice(r[1] - oy, r[1] - oy + r[3]), slice(r[0] - ox, r[0] - ox + r[2])) for r in rects]
     if blend == PASTE:
         can = np.zeros((fh, fw, 3), dtype=np.uint8)
@@ -86,19 +88,78 @@ def tables(images, Gs, anchor, order=None):
                 size=(fh, fw), n=n, anchor=anchor)
 
 
-def host_twin(lib, images, Gs, anchor=0, blend=PASTE, order=None, rows=None):
-    """rwh_host_stitch_sequence -> (status, canvas), the canvas between two 64-byte canaries that are checked here."""
+def library(gpu=False):
+    """The library, built and loaded: the body of every file's `lib` fixture.  gpu: the process has to see the GPU."""
+    import __graft_entry__ as g
+    g.build()
+    from ransac_with_homography_amd import _lib
+    if gpu:
+        _lib.require_gpu()
+    return _lib.load()
+
+
+def guarded_canvas(fh, fw):
+    """A host canvas uint8 [fh, fw, 3] of 0xA5 bytes between two 64-byte canaries -> (canvas, check); check() asserts the canaries."""
+    buf = np.full(fh * fw * 3 + 128, 0xA5, dtype=np.uint8)
+
+    def check():
+        assert (buf[:64] == 0xA5).all() and (buf[-64:] == 0xA5).all(), "a byte outside the canvas was written"
+    return buf[64:-64].reshape(fh, fw, 3), check
+
+
+def guarded_device_canvas(fh, fw):
+    """The same on the device -> (canvas tensor, fetch); fetch() brings the buffer down, asserts the canaries -> the canvas in numpy."""
+    import torch
+    buf = torch.full((fh * fw * 3 + 128,), 0xA5, dtype=torch.uint8, device="cuda")
+
+    def fetch():
+        flat = buf.cpu().numpy()
+        assert (flat[:64] == 0xA5).all() and (flat[-64:] == 0xA5).all(), "a byte outside the canvas was written"
+        return flat[64:-64].reshape(fh, fw, 3)
+    return buf[64:-64].view(fh, fw, 3), fetch
+
+
+def upload(images):
+    import torch
+    return [torch.from_numpy(np.ascontiguousarray(im)).cuda() for im in images]
+
+
+def host_twin(lib, images, Gs, anchor=0, blend=PASTE, order=None, rows=None, gains=None, ex=False):
+    """rwh_host_stitch_sequence, or with `ex` rwh_host_stitch_sequence_ex (gains None passes NULL) -> (status, canvas), the canvas
+    guarded."""
+    assert ex or gains is None
     images = [np.ascontiguousarray(im) for im in images]
     t = tables(images, Gs, anchor, order)
     fh, fw = t["size"]
-    buf = np.full(fh * fw * 3 + 128, 0xA5, dtype=np.uint8)
-    can = buf[64:64 + fh * fw * 3].reshape(fh, fw, 3)
+    can, check = guarded_canvas(fh, fw)
     ptrs = np.array([im.ctypes.data for im in images], dtype=np.uint64)
     r0, r1 = (0, fh) if rows is None else rows
-    st = lib.rwh_host_stitch_sequence(ptrs.ctypes.data, t["hw"].ctypes.data, t["inv"].ctypes.data, t["rects"].ctypes.data, t["n"], anchor,
-                                      t["order"].ctypes.data, blend, can.ctypes.data, fh, fw, t["origin"][0], t["origin"][1], r0, r1)
-    assert (buf[:64] == 0xA5).all() and (buf[-64:] == 0xA5).all()
+    args = (ptrs.ctypes.data, t["hw"].ctypes.data, t["inv"].ctypes.data, t["rects"].ctypes.data, t["n"], anchor, t["order"].ctypes.data, blend,
+            can.ctypes.data, fh, fw, t["origin"][0], t["origin"][1], r0, r1)
+    g = None if gains is None else np.ascontiguousarray(gains, dtype=np.float64)
+    st = lib.rwh_host_stitch_sequence_ex(*args, None if g is None else g.ctypes.data) if ex else lib.rwh_host_stitch_sequence(*args)
+    check()
     return st, can
+
+
+def host(lib, *a, **k):
+    st, can = host_twin(lib, *a, **k)
+    assert st == 0
+    return can
+
+
+def host_ex(lib, *a, **k):
+    return host(lib, *a, ex=True, **k)
+
+
+def device(images, Gs, anchor=0, blend=PASTE, order=None, rows=None, on=None, gains=None):
+    """kernels.stitch_sequence (gains=...) into a guarded device canvas -> the canvas in numpy."""
+    from ransac_with_homography_amd import kernels
+    t = tables(images, Gs, anchor, order)
+    can, fetch = guarded_device_canvas(*t["size"])
+    kernels.stitch_sequence(upload(images) if on is None else on, t["inv"], t["rects"], anchor, t["order"], blend, t["origin"], t["size"],
+                            rows=rows, out=can, gains=gains)
+    return fetch()
 
 
 # ---- the cases ----

@@ -14,16 +14,10 @@ from oracle import rwh_oracle as orc
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from ransac_with_homography_amd import _lib
-    return _lib.load()
+    return sc.library()
 
 
-def twin(lib, *a, **k):
-    st, can = sc.host_twin(lib, *a, **k)
-    assert st == 0
-    return can
+twin = sc.host
 
 
 CASES = sc.general_cases()

@@ -1,5 +1,5 @@
 """The gain rule without a GPU: the host twins (rwh_host_sequence_overlap_stats, rwh_host_sequence_gains,
-rwh_host_stitch_sequence_ex) against the numpy restatement of tests/gain_cases.py, the structure of the tables, the properties of
+rwh_host_stitch_sequence_ex) against the numpy restatements of tests/gain_cases.py and tests/sequence_cases.py, the structure of the tables, the properties of
 the gains, and every refusal at the C and the Python level.  Tables and canvases are compared exactly; gains by the backward-error
 bound of a Cholesky solve."""
 import ctypes
@@ -13,28 +13,16 @@ import sequence_cases as sc
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from ransac_with_homography_amd import _lib
-    return _lib.load()
+    return sc.library()
 
 
-def hstats(lib, *a, **k):
-    st, count, total = gc.host_stats(lib, *a, **k)
-    assert st == 0
-    return count, total
+hstats, twin_ex = gc.hstats, sc.host_ex
 
 
 def hgains(lib, *a, **k):
     st, g = gc.host_gains(lib, *a, **k)
     assert st == 0
     return g
-
-
-def twin_ex(lib, *a, **k):
-    st, can = gc.host_twin_ex(lib, *a, **k)
-    assert st == 0
-    return can
 
 
 CASES = sc.general_cases()
@@ -168,7 +156,7 @@ def test_host_twin_with_gains_is_the_restatement(lib, case, blend):
     _, images, Gs, anchor, order = case
     gains = gc.mixed_gains(len(images))
     before = [im.copy() for im in images]
-    want = gc.restate(images, Gs, anchor, blend, order, gains)
+    want = sc.restate(images, Gs, anchor, blend, order, gains)[0]
     got = twin_ex(lib, images, Gs, anchor, blend, order, gains=gains)
     assert got.shape == want.shape and np.array_equal(got, want)
     assert all(np.array_equal(a, b) for a, b in zip(images, before))
@@ -185,7 +173,7 @@ def test_unit_gains_and_null_are_the_plain_call(lib, blend):
         assert np.array_equal(plain, sc.restate(images, Gs, anchor, blend, order)[0])
         assert np.array_equal(twin_ex(lib, images, Gs, anchor, blend, order, gains=np.ones(len(images))), plain)
         assert np.array_equal(twin_ex(lib, images, Gs, anchor, blend, order, gains=None), plain)
-        assert np.array_equal(gc.restate(images, Gs, anchor, blend, order), plain)
+        assert np.array_equal(sc.restate(images, Gs, anchor, blend, order, np.ones(len(images)))[0], plain)
 
 
 def test_row_tiles_with_gains_equal_the_whole_canvas(lib):

@@ -12,28 +12,10 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from ransac_with_homography_amd import _lib
-    _lib.require_gpu()
-    return _lib.load()
+    return sc.library(gpu=True)
 
 
-def hstats(lib, *a, **k):
-    st, count, total = gc.host_stats(lib, *a, **k)
-    assert st == 0
-    return count, total
-
-
-def host_ex(lib, *a, **k):
-    st, can = gc.host_twin_ex(lib, *a, **k)
-    assert st == 0
-    return can
-
-
-def upload(images):
-    import torch
-    return [torch.from_numpy(np.ascontiguousarray(im)).cuda() for im in images]
+hstats, host_ex, upload, device_ex = gc.hstats, sc.host_ex, sc.upload, sc.device
 
 
 class DeviceTables(object):
@@ -72,21 +54,6 @@ class DeviceTables(object):
 
 def device_stats(lib, images, Gs, anchor=0, stride=1):
     return DeviceTables(len(images)).call(lib, images, Gs, anchor, stride)
-
-
-def device_ex(images, Gs, anchor=0, blend=sc.PASTE, order=None, gains=None, on=None, rows=None):
-    """kernels.stitch_sequence(gains=...) into a canvas between two 64-byte canaries -> numpy (canaries checked)."""
-    import torch
-    from ransac_with_homography_amd import kernels
-    t = sc.tables(images, Gs, anchor, order)
-    fh, fw = t["size"]
-    buf = torch.full((fh * fw * 3 + 128,), 0xA5, dtype=torch.uint8, device="cuda")
-    can = buf[64:64 + fh * fw * 3].view(fh, fw, 3)
-    kernels.stitch_sequence(upload(images) if on is None else on, t["inv"], t["rects"], anchor, t["order"], blend, t["origin"], (fh, fw), rows=rows,
-                            out=can, gains=gains)
-    flat = buf.cpu().numpy()
-    assert (flat[:64] == 0xA5).all() and (flat[-64:] == 0xA5).all(), "a byte outside the canvas was written"
-    return flat[64:-64].reshape(fh, fw, 3)
 
 
 EDGES = sc.edge_canvases()

@@ -15,32 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from ransac_with_homography_amd import _lib
-    _lib.require_gpu()
-    return _lib.load()
+    return sc.library(gpu=True)
 
 
-def host(lib, *a, **k):
-    st, can = sc.host_twin(lib, *a, **k)
-    assert st == 0
-    return can
-
-
-def device(images, Gs, anchor=0, blend=sc.PASTE, order=None, rows=None, on=None):
-    """kernels.stitch_sequence into a canvas between two 64-byte canaries -> the canvas as a numpy array (canaries checked)."""
-    import torch
-    from ransac_with_homography_amd import kernels
-    t = sc.tables(images, Gs, anchor, order)
-    fh, fw = t["size"]
-    buf = torch.full((fh * fw * 3 + 128,), 0xA5, dtype=torch.uint8, device="cuda")
-    can = buf[64:64 + fh * fw * 3].view(fh, fw, 3)
-    dev = [torch.from_numpy(np.ascontiguousarray(im)).cuda() for im in images] if on is None else on
-    kernels.stitch_sequence(dev, t["inv"], t["rects"], anchor, t["order"], blend, t["origin"], (fh, fw), rows=rows, out=can)
-    flat = buf.cpu().numpy()
-    assert (flat[:64] == 0xA5).all() and (flat[-64:] == 0xA5).all(), "a byte outside the canvas was written"
-    return flat[64:-64].reshape(fh, fw, 3)
+host, device = sc.host, sc.device
 
 
 EDGES = sc.edge_canvases()
@@ -96,7 +74,7 @@ def test_row_tiles_and_a_second_stream(lib):
             assert (part[:r0] == 0xA5).all() and (part[r1:] == 0xA5).all()
             tiled[r0:r1] = part[r0:r1]
         assert np.array_equal(tiled, whole)
-        on = [torch.from_numpy(np.ascontiguousarray(im)).cuda() for im in images]
+        on = sc.upload(images)
         torch.cuda.synchronize()
         side = torch.cuda.Stream()
         with torch.cuda.stream(side):

@@ -13,16 +13,11 @@ import sequence_cases as sc
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from ransac_with_homography_amd import _lib
-    return _lib.load()
+    return sc.library()
 
 
 def paste(lib, images, Gs, anchor=0, gains=None):
-    st, can = gc.host_twin_ex(lib, images, Gs, anchor, sc.PASTE, gains=gains)
-    assert st == 0
-    return can
+    return sc.host_ex(lib, images, Gs, anchor, sc.PASTE, gains=gains)
 
 
 GENERAL = sc.general_cases()

@@ -16,11 +16,7 @@ TH = 5
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    g.build()
-    from ransac_with_homography_amd import _lib
-    _lib.require_gpu()
-    return _lib.load()
+    return sc.library(gpu=True)
 
 
 EDGES = sc.edge_canvases()
@@ -33,7 +29,7 @@ TILES = mc.tile_edge_cases()
 def test_device_is_the_host_twin_across_launch_edges(lib, case):
     """Padding, fw that is no multiple of 2^K, planes of one row; with and without gains."""
     _, _, images, Gs, _, _ = case
-    dev = mc.upload(images)
+    dev = sc.upload(images)
     for bands in (1, 2):
         for gains in (None, gc.mixed_gains(len(images))):
             assert np.array_equal(mc.device(lib, images, Gs, 0, bands, gains, on=dev), mc.host(lib, images, Gs, 0, bands, gains)), (bands, gains)
@@ -78,7 +74,7 @@ def test_the_call_does_not_depend_on_what_the_workspace_held(lib):
     want = mc.host(lib, images, Gs, 0, 2)
     need = max(mc.workspace_bytes(lib, sc.tables(images, Gs, 0), 2), mc.workspace_bytes(lib, sc.tables(other, oG, oa), 3))
     ws = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
-    dev = mc.upload(images)
+    dev = sc.upload(images)
     assert np.array_equal(mc.device(lib, images, Gs, 0, 2, on=dev, workspace=ws), want)
     assert np.array_equal(mc.device(lib, other, oG, oa, 3, workspace=ws), mc.host(lib, other, oG, oa, 3))
     assert np.array_equal(mc.device(lib, images, Gs, 0, 2, on=dev, workspace=ws), want)
@@ -102,7 +98,7 @@ def test_a_workspace_too_small_or_misaligned_is_refused(lib):
     images, Gs = sc.translated_strip(3)
     t = sc.tables(images, Gs, 0)
     fh, fw = t["size"]
-    dev = mc.upload(images)
+    dev = sc.upload(images)
     ptrs = np.array([d.data_ptr() for d in dev], dtype=np.uint64)
     need = mc.workspace_bytes(lib, t, 2)
     ws = torch.zeros((need + 8,), dtype=torch.uint8, device="cuda")
@@ -126,7 +122,7 @@ def test_kernels_entry(lib):
     from ransac_with_homography_amd import kernels
     _, images, Gs, anchor, _ = GENERAL[3]
     t = sc.tables(images, Gs, anchor)
-    dev = mc.upload(images)
+    dev = sc.upload(images)
     g = gc.mixed_gains(len(images))
     out = kernels.stitch_sequence_multiband(dev, t["inv"], t["rects"], anchor, t["origin"], t["size"], 3, gains=g)
     assert out.dtype == torch.uint8 and out.is_cuda and np.array_equal(out.cpu().numpy(), mc.host(lib, images, Gs, anchor, 3, g))
@@ -148,7 +144,7 @@ def test_stitch_sequence_entry_numpy_and_tensors(lib):
     got = hg.stitchSequence(images, Gs=Gs, anchor=anchor, blending="multiband", bands=3, order=[2, 0, 1])
     assert isinstance(got, np.ndarray) and got.dtype == np.uint8 and np.array_equal(got, want)
     assert all(np.array_equal(a, b) for a, b in zip(images, before))
-    dev = mc.upload(images)
+    dev = sc.upload(images)
     keep = [d.clone() for d in dev]
     out = hg.stitchSequence(dev, Gs=Gs, anchor=anchor, blending="multiband", bands=3)
     assert isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev[0].device and np.array_equal(out.cpu().numpy(), want)
