@@ -1254,10 +1254,11 @@ __device__ __forceinline__ void fast8_body(const FastArgs& a, const Coef* tab, c
 // conditions: launch_fast).  A kernel of its own with its own register budget, on purpose: folded into the one-frame kernel behind
 // a uniform branch it would lift that kernel from 60 VGPRs to the walk's count and cost the one-frame path (8K frames, small
 // batches, one homography per image) its 8 resident waves per SIMD.
-// (5: under this bound the walk takes 93 VGPRs (64 x 8 patches) / 92 (128 x 4), no scratch, no SGPR spilled into VGPR lanes, and 5 waves per SIMD are
-//  resident -- as long as its one-frame fallback reads FastArgs by a route of its own, see kernarg_fastargs(); with the kernel's copy live across the
-//  window path it was 96 VGPRs and 115 / 120 spilled SGPRs.  Under a bound of 6 (80 VGPRs) it spills 11 VGPRs to scratch and is slower,
-//  profiles/warp_batch_slim.txt.  The lab entry warp_rgb8_fast8mb keeps its bound of 4 and comes to the same 93 / 92 VGPRs.)
+// (5: under this bound the walk takes 88 VGPRs (64 x 8 patches) / 87 (128 x 4) with its three staging slots (93 / 92 with four), no scratch, no SGPR
+//  spilled into VGPR lanes, and 5 waves per SIMD are resident -- as long as its one-frame fallback reads FastArgs by a route of its own, see
+//  kernarg_fastargs(); with the kernel's copy live across the window path it was 96 VGPRs and 115 / 120 spilled SGPRs.  Under a bound of 6 (80 VGPRs) it
+//  still spills to scratch and is slower, profiles/warp_batch_slim.txt.  The lab entry warp_rgb8_fast8mb keeps its bound of 4 and comes to the same
+//  88 / 87 VGPRs and the same code.)
 constexpr int F8_WALK_WAVES = 5;
 template <int LOG_PW> __device__ __forceinline__ void fast8mb_body(const FastArgs& a);
 template <typename DstT, int LOG_PW, bool WALK = false>
@@ -1636,7 +1637,10 @@ __device__ __forceinline__ void fast8m_body(const FastArgs& a) {
 // zeros per frame, as the one-frame body does for such a patch.  Only three kinds of block still run the one-frame body frame by frame (all four waves): a wave
 // with W at / across zero (the horizon), a window that does not fit BROWS x BCH chunks, and a window that reaches the last two
 // source rows (a staging chunk may read 9 bytes past its last texel).
-constexpr int BCH = 36, BROWS = 22;                     // block window: 144 texels x 22 rows
+// block window: 144 texels x 21 rows = 756 chunks <= 768: THREE staging slots per thread.  With 22 rows a fourth slot served row 21 alone; no window
+// of the bench grids has more than 20 rows (tests/warp_window_rule.py), yet the slot cost a load with its exec toggles, an expand branch and
+// 5 VGPRs on every frame (profiles/warp_batch_prologue.txt).
+constexpr int BCH = 36, BROWS = 21;
 // block barrier that orders LDS traffic only (__syncthreads' fence also waits for every outstanding global load and store:
 // the prefetched chunks of the next frame, the stores of the previous one)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory"); }
@@ -1799,8 +1803,8 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
         }
     };
     auto landed = [&](u3 (&v)[SLOTS]) __attribute__((always_inline)) {
-        static_assert(SLOTS == 4, "operand list below");
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : : "memory");
+        static_assert(SLOTS == 3, "operand list below");
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]) : : "memory");
     };
     auto expand = [&](const u3 (&v)[SLOTS]) __attribute__((always_inline)) {
 #pragma unroll
@@ -1825,6 +1829,12 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
     const uint32_t tap_c = (by & 0xFFFFFFu) * lpitch + (bx << 2);                                // (interior blocks) from slab0, where the block slab starts
     float wa[F8_PX], wb[F8_PX], wc[F8_PX], wd[F8_PX];
     uint32_t lo[F8_PX];
+    // Frame f0's window is requested HERE, in front of the geometry (about 450 instructions, 200 of them float64, none of which needs
+    // the loads), not behind it: from the second frame on a window is requested a whole frame period before it is needed, the first one
+    // would be requested and waited for in the same breath otherwise.  Behind both early returns above: a block that leaves has nothing
+    // in flight.  (profiles/warp_batch_prologue.txt)
+    u3 v[SLOTS];
+    issue(gsrc, v);
     if (in) {                                                  // (uniform; the other waves take no taps)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -1875,9 +1885,7 @@ __device__ __forceinline__ void fast8mb_body(const FastArgs& a) {
         }
     }
     }
-    u3 v[SLOTS];
-    issue(gsrc, v);
-    landed(v);
+    landed(v);                                                 // (waves that are not `in` skipped the geometry and simply wait)
     expand(v);
     lds_barrier();                                             // the slab holds frame f0
     if (f0 + 1 < f1) issue(gsrc + a.src_img_stride, v);
