@@ -1,4 +1,4 @@
-"""Helpers of the extractor's tests (test_orb_cpu.py, test_orb_gpu.py) -- not a test module.
+"""Helpers of the extractor's tests (test_orb_cpu.py, test_orb_gpu.py, the edge and pyramid files) -- not a test module.
 
 `restate` restates the rule of include/rwh.h (rwh_orb_detect_batched / rwh_orb_describe_batched) in numpy, written from that text:
 whole planes, shifted views for the circle and the neighbours, a lexsort for the order, fancy indexing for the patches, an integral
@@ -118,6 +118,29 @@ def host_extract(lib, img, n_features=500, threshold=20, nbytes=32, pattern=None
 def same(a, b):
     return (a["found"] == b["found"] and all(a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and np.array_equal(a[k], b[k])
                                              for k in ("kps", "desc", "score", "bin")))
+
+
+def gpu_torch():
+    """torch, with the GPU in sight and the package built: the body of every GPU file's `gpu` fixture."""
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    import __graft_entry__ as g
+    g.build()
+    return torch
+
+
+def extract(images, per_level=False, **kw):
+    """extract_batch on the GPU -> one dict per image as `restate` gives it, with level and size besides (what
+    orb_pyramid_cases.restate_pyramid adds); found is the image's total, with per_level the list of its levels' counts."""
+    import ransac as rs
+    info = {}
+    feats = rs.extract_batch(images, info=info, **kw)
+    assert all(k.is_cuda and d.is_cuda and k.shape[0] == d.shape[0] == c for (k, d), c in zip(feats, info["counts"]))
+    assert info["found"] == [sum(f) for f in info["found_levels"]]
+    return [dict(kps=k.cpu().numpy(), desc=d.cpu().numpy(), score=s.cpu().numpy(), bin=b.cpu().numpy(), level=l.cpu().numpy(),
+                 size=z.cpu().numpy(), found=f)
+            for (k, d), s, b, l, z, f in zip(feats, info["score"], info["bin"], info["level"], info["size"],
+                                             info["found_levels" if per_level else "found"])]
 
 
 # ---- the cases ----

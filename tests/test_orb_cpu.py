@@ -137,7 +137,7 @@ def test_argument_validation_without_gpu(lib):
 def test_pattern_check_and_bin_table():
     """The table helpers and the pattern check of extract_batch need no device."""
     import ransac as rs
-    from ransac_with_homography_amd import ransac as impl
+    from ransac_with_homography_amd import features as impl
     with pytest.raises(ValueError):
         impl._check_pattern(rs.default_pattern(4), 32)       # 32 tests for 32 bytes
     with pytest.raises(ValueError):

@@ -16,20 +16,7 @@ FILL = 0xEE
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    import __graft_entry__ as g
-    g.build()
-    return torch
-
-
-def _extract(images, **kw):
-    import ransac as rs
-    info = {}
-    feats = rs.extract_batch(images, info=info, **kw)
-    assert all(k.is_cuda and d.is_cuda and k.shape[0] == d.shape[0] == c for (k, d), c in zip(feats, info["counts"]))
-    return [dict(kps=k.cpu().numpy(), desc=d.cpu().numpy(), score=s.cpu().numpy(), bin=b.cpu().numpy(), found=f)
-            for (k, d), s, b, f in zip(feats, info["score"], info["bin"], info["found"])]
+    return oc.gpu_torch()
 
 
 def _host(img, **kw):
@@ -75,13 +62,13 @@ def test_strided_walk_small(gpu):
     images = strips + narrows
     tiles, blocks = _sizing(images)
     assert (tiles, blocks) == (1480, 334) and tiles >= 4 * blocks
-    first = _extract(images)
+    first = oc.extract(images)
     assert [r["found"] for r in first[:20]] == [0] * 20
     for s, (img, got) in enumerate(zip(narrows, first[20:])):
         assert oc.same(got, oc.restate(img)) and oc.same(got, _host(img)), s
     assert sum(r["found"] for r in first[20:]) > 40
     assert _gray_planes_equal(gpu, images, [r["found"] for r in first])
-    again = _extract(images)
+    again = oc.extract(images)
     assert all(oc.same(a, b) for a, b in zip(again, first))
 
 
@@ -94,7 +81,7 @@ def test_strided_walk_capped_grid(gpu):
     images = strips + rest
     tiles, blocks = _sizing(images)
     assert blocks == 16384 and tiles >= 4 * blocks
-    first = _extract(images)
+    first = oc.extract(images)
     assert [r["found"] for r in first[:130]] == [0] * 130
     for i, (img, got) in enumerate(zip(rest, first[130:])):
         assert oc.same(got, oc.restate(img)) and oc.same(got, _host(img)), i
@@ -108,13 +95,13 @@ def test_strided_walk_capped_grid(gpu):
 def test_more_than_256_images(gpu, n):
     """orb_setup_kernel gives each of its 256 lanes ceil(n / 256) = 2 or 3 images; every image of the batch is numbered."""
     images = [oc.numbered(i) for i in range(n)]
-    got = _extract(images)
+    got = oc.extract(images)
     for i, (img, r) in enumerate(zip(images, got)):
         x, y, s = oc.keypoints(oc.scores(img), 20)
         assert r["found"] == len(x) >= 1 and np.array_equal(r["kps"], np.stack([x, y], axis=1).astype(np.float32)), i
         assert np.array_equal(r["score"], s.astype(np.int32)), i
     for i in sorted({0, 1, 64, 127, n // 2, 254, 255, 256, n - 2, n - 1}):
-        alone, = _extract([images[i]])
+        alone, = oc.extract([images[i]])
         assert oc.same(alone, got[i]) and oc.same(alone, oc.restate(images[i])), i
 
 
@@ -201,7 +188,7 @@ def test_arcs_and_bins_on_the_device(gpu):
     (m20, must20, not20), (m254, must254, not254), (wheel, centres) = oc.arc_mosaic(20), oc.arc_mosaic(254), oc.bin_wheel()
     images = [m20, m254, wheel]
     for threshold, k, must, must_not in ((20, 0, must20, not20), (254, 1, must254, not254)):
-        got = _extract(images, threshold=threshold)
+        got = oc.extract(images, threshold=threshold)
         for i, (img, r) in enumerate(zip(images, got)):
             assert oc.same(r, oc.restate(img, threshold=threshold)) and oc.same(r, _host(img, threshold=threshold)), (threshold, i)
         at = {(int(x), int(y)): int(s) for (x, y), s in zip(got[k]["kps"], got[k]["score"])}

@@ -1,4 +1,4 @@
-"""The extractor on the MI355X: ransac.extract_batch (rwh_orb_detect_batched -> one sort -> rwh_orb_describe_batched) against the host
+"""The extractor on the MI355X: features.extract_batch (rwh_orb_detect_batched -> one sort -> rwh_orb_describe_batched) against the host
 twin and the numpy restatement of tests/orb_cases.py -- exact equality, everything is an integer -- on one batch that holds every
 image of the CPU suite plus one that spans several tiles with corners planted on the seams; the parameter variants; the overflow
 status; determinism; alone == in the batch; tensors in == numpy in; descriptors independent of n_features; displaced crops through
@@ -15,11 +15,7 @@ KEY_NONE = 0x7F7F7F7F7F7F7F7F
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    import __graft_entry__ as g
-    g.build()
-    return torch
+    return oc.gpu_torch()
 
 
 def _seams_image():
@@ -40,24 +36,11 @@ def _seams_image():
     return img, strong, weak
 
 
-def _as_dicts(feats, info):
-    return [dict(kps=k.cpu().numpy(), desc=d.cpu().numpy(), score=s.cpu().numpy(), bin=b.cpu().numpy(), found=f)
-            for (k, d), s, b, f in zip(feats, info["score"], info["bin"], info["found"])]
-
-
-def _extract(images, **kw):
-    import ransac as rs
-    info = {}
-    feats = rs.extract_batch(images, info=info, **kw)
-    assert all(k.is_cuda and d.is_cuda and k.shape[0] == d.shape[0] == c for (k, d), c in zip(feats, info["counts"]))
-    return _as_dicts(feats, info)
-
-
 @pytest.fixture(scope="module")
 def batch(gpu):
     """Every image of the CPU cases and the seams image in one call with the default parameters; restatement computed once."""
     images = [img for _, img, _ in oc.cpu_cases()[:13]] + [_seams_image()[0]]
-    return dict(images=images, want=[oc.restate(img) for img in images], first=_extract(images))
+    return dict(images=images, want=[oc.restate(img) for img in images], first=oc.extract(images))
 
 
 def test_batch_equals_host_twin_and_restatement(batch):
@@ -81,24 +64,24 @@ def test_parameter_variants(gpu):
     variants = [(name, img, kw) for name, img, kw in oc.cpu_cases() if kw]
     assert len(variants) == 7
     for name, img, kw in variants:
-        got, = _extract([img], **kw)
+        got, = oc.extract([img], **kw)
         assert oc.same(got, oc.restate(img, **kw)) and oc.same(got, oc.host_extract(lib, img, **kw)[1]), name
 
 
 def test_second_call_is_bit_identical(batch):
-    again = _extract(batch["images"])
+    again = oc.extract(batch["images"])
     assert all(oc.same(a, b) for a, b in zip(again, batch["first"]))
 
 
 def test_alone_equals_in_the_batch(batch):
     for i in (0, 3, 4, 12, 13):
-        alone, = _extract([batch["images"][i]])
+        alone, = oc.extract([batch["images"][i]])
         assert oc.same(alone, batch["first"][i]), i
 
 
 def test_tensors_in_equal_numpy_in(gpu, batch):
     pick = [0, 1, 2, 13]
-    got = _extract([gpu.from_numpy(batch["images"][i]).cuda() if i % 2 else gpu.from_numpy(batch["images"][i]) for i in pick])
+    got = oc.extract([gpu.from_numpy(batch["images"][i]).cuda() if i % 2 else gpu.from_numpy(batch["images"][i]) for i in pick])
     assert all(oc.same(g, batch["first"][i]) for g, i in zip(got, pick))
     import ransac as rs
     kps, desc = rs.detect_and_describe(batch["images"][12])
@@ -116,7 +99,7 @@ def test_tensors_in_equal_numpy_in(gpu, batch):
 
 def test_descriptors_do_not_depend_on_n_features(batch):
     crop, full = batch["images"][12], batch["first"][12]
-    few, = _extract([crop], n_features=40)
+    few, = oc.extract([crop], n_features=40)
     assert full["found"] > 40 and few["found"] == full["found"] and len(few["score"]) == 40
     assert all(np.array_equal(few[k], full[k][:40]) for k in ("kps", "desc", "score", "bin"))
 
@@ -126,7 +109,7 @@ def test_overflow_status_and_nothing_past_the_list(gpu, batch, monkeypatch):
     behind the buffer are untouched; extract_batch meets the same status and repeats the call with room for all."""
     torch = gpu
     from ransac_with_homography_amd import kernels
-    from ransac_with_homography_amd import ransac as impl
+    from ransac_with_homography_amd import features as impl
     tie, _ = oc.tie_image()
     one = oc.dots(33, 33, [(16, 16, 255)])
     src = torch.from_numpy(np.concatenate([tie.reshape(-1), one.reshape(-1)])).cuda()
@@ -141,7 +124,7 @@ def test_overflow_status_and_nothing_past_the_list(gpu, batch, monkeypatch):
     assert g[4:8].tolist() == [16 << 16 | 16, KEY_NONE, KEY_NONE, KEY_NONE] and (g[8:] == -12345).all()
     assert np.array_equal(gray.cpu().numpy(), np.concatenate([tie.reshape(-1), one.reshape(-1)]))
     monkeypatch.setattr(impl, "_ORB_DEFAULT_CAPACITY", 4)
-    got = _extract([tie, batch["images"][12], one])
+    got = oc.extract([tie, batch["images"][12], one])
     assert got[1]["found"] > 4 and oc.same(got[1], batch["first"][12]) and oc.same(got[0], oc.restate(tie)) and got[2]["found"] == 1
 
 

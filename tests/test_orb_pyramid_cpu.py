@@ -166,11 +166,11 @@ def test_back_map(lib):
     """Rule 8: the reported coordinate is np.float32(Fraction((2 x + 1) s - 256, 512)).  The host twin is asked through noise at
     threshold 0, where the first two legal columns, x = 16 and 17, hold keypoints on every level; the widest coordinate, 65519,
     exists only on level 0 (no level of a 65536-wide image is that wide), where the twin is asked through orb_cases.wide_image;
-    the package's own map (ransac._orb_level_to_image, which extract_batch applies on the device) is asked for all three columns
+    the package's own map (features._orb_level_to_image, which extract_batch applies on the device) is asked for all three columns
     and every default scale on CPU tensors."""
     import torch
     import ransac as rs
-    from ransac_with_homography_amd import ransac as impl
+    from ransac_with_homography_amd import features as impl
     scales = rs.orb_scales(8)
     exact = lambda x, s: np.float32(Fraction((2 * int(x) + 1) * int(s) - 256, 512))
     img = oc.random_image(200, 200, 41, channels=1)
@@ -227,6 +227,53 @@ def test_table_helpers_and_their_errors():
             rs.orb_level_quotas(10, bad)
     with pytest.raises(ValueError):
         rs.orb_level_quotas(-1, [256, 300])
+
+
+def test_layout_equals_the_restatement():
+    """features.orb_layout -- the buffer and table extract_batch and tools/orb_probe.py hand to the library -- against
+    orb_pyramid_cases.layout, which was written from include/rwh.h on its own: the table, where the planes start and where they end;
+    gray_bytes is the sum of every level's area.  One level, four, and the caller's table with its level of scale 1024; a 1 x 40
+    image whose level at 1024 has no rows, (256 + 512) // 1024 = 0."""
+    import ransac as rs
+    from ransac_with_homography_amd import features
+    shape = lambda im: (im.shape[0], im.shape[1], 1 if im.ndim == 2 else im.shape[2])
+    thin = oc.random_image(1, 40, 51, channels=1)
+    batch = [img for _, img in pc.plane_images()] + pc.gpu_images() + [thin]
+    cases = [(batch, sc) for sc in (np.array([256], dtype=np.int32), rs.orb_scales(4), pc.CALLER_SCALES)]
+    cases.append(([thin], np.array([256, 1024], dtype=np.int32)))
+    for images, scales in cases:
+        table, planes_offset, images_bytes, gray_bytes, full = features.orb_layout([shape(im) for im in images], scales)
+        head, want, off, end, _ = pc.layout(images, scales, gap=0)
+        assert table.dtype == want.dtype == np.int64 and table.shape == (len(images) * len(scales), 5) and np.array_equal(table, want)
+        assert planes_offset == off == head.size and images_bytes == end
+        assert gray_bytes == sum(pc.level_side(im.shape[0], s) * pc.level_side(im.shape[1], s) for im in images for s in scales.tolist())
+    assert table.tolist() == [[0, 0, 1, 40, 1], [0, 0, 0, 0, 1]] and (planes_offset, images_bytes, gray_bytes, full) == (40, 40, 40, 1)
+
+
+def test_layout_full_is_a_bound(lib):
+    """`full`, the room of the overflow retry, holds every keypoint there can be: no image of the CPU cases finds more, and an image
+    without a legal centre (32 x 32) still gets room for one."""
+    from ransac_with_homography_amd import features
+    one = np.array([256], dtype=np.int32)
+    for name, img, kw in oc.cpu_cases():
+        st, got = oc.host_extract(lib, img, **kw)
+        full = features.orb_layout([(img.shape[0], img.shape[1], 1 if img.ndim == 2 else img.shape[2])], one)[4]
+        assert st == 0 and 0 <= got["found"] <= full, name
+    assert features.orb_layout([(32, 32, 3)], one)[4] == 1 and features.orb_layout([(32, 32, 3), (33, 35, 1)], one)[4] == 2
+
+
+def test_import_surface():
+    """Every name of the top-level `ransac` module comes from ransac_with_homography_amd.ransac; the names that live in features.py
+    are the same objects there, the hand-off type among them."""
+    import ransac as shim
+    from ransac_with_homography_amd import features
+    from ransac_with_homography_amd import ransac as impl
+    names = [n for n in vars(shim) if not n.startswith("__")]
+    assert len(names) == 25 and all(getattr(shim, n) is getattr(impl, n) for n in names)
+    moved = {"DeviceProblems", "match_descriptors", "match_batch", "extract_batch", "detect_and_describe", "default_pattern",
+             "rotate_pattern", "orb_bin_table", "orb_scales", "orb_level_quotas"}
+    assert moved <= set(names) and all(getattr(impl, n) is getattr(features, n) for n in moved)
+    assert impl.DeviceProblems is features.DeviceProblems and impl.run_batch.__module__ == impl.__name__
 
 
 def test_entry_points_refuse_bad_arguments(lib):

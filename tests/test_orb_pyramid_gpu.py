@@ -1,5 +1,5 @@
 """The scale pyramid of the extractor on the MI355X (rules 6 - 8 of include/rwh.h): rwh_orb_pyramid_batched against the host twin
-rwh_host_orb_pyramid, byte for byte, with canaries around the planes; ransac.extract_batch(n_levels=...) against
+rwh_host_orb_pyramid, byte for byte, with canaries around the planes; features.extract_batch(n_levels=...) against
 rwh_host_orb_extract_pyramid -- keypoints, descriptors, levels, sizes, scores, bins, exact equality -- with and without the capacity
 retry; n_levels = 1 against the call without the argument; batches of 70 images (210 and 280 table rows, most without keypoints);
 malformed table rows; stitching(features={"n_levels": 8}) on a pair that differs in zoom by 1.5."""
@@ -15,11 +15,7 @@ CANARY = 0xCD
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    import __graft_entry__ as g
-    g.build()
-    return torch
+    return oc.gpu_torch()
 
 
 @pytest.fixture(scope="module")
@@ -63,32 +59,17 @@ def test_planes_equal_host_twin_and_nothing_else_is_written(gpu, lib, which):
         assert spans[2][0][1] < 33 and spans[0][0][1:] == (125, 169)
 
 
-def _as_dicts(feats, info):
-    return [dict(kps=k.cpu().numpy(), desc=d.cpu().numpy(), score=s.cpu().numpy(), bin=b.cpu().numpy(), level=l.cpu().numpy(),
-                 size=z.cpu().numpy(), found=f)
-            for (k, d), s, b, l, z, f in zip(feats, info["score"], info["bin"], info["level"], info["size"], info["found_levels"])]
-
-
-def _extract(images, **kw):
-    import ransac as rs
-    info = {}
-    feats = rs.extract_batch(images, info=info, **kw)
-    assert all(k.is_cuda and d.is_cuda and k.shape[0] == d.shape[0] == c for (k, d), c in zip(feats, info["counts"]))
-    assert info["found"] == [sum(f) for f in info["found_levels"]]
-    return _as_dicts(feats, info)
-
-
 @pytest.mark.parametrize("threshold", [0, 20])
 def test_extract_batch_equals_host_twin(gpu, lib, monkeypatch, threshold):
     """threshold 0 on noise finds thousands of keypoints per level; with the usual room cut to 64 the overflow retry runs with levels."""
     import ransac as rs
-    from ransac_with_homography_amd import ransac as impl
+    from ransac_with_homography_amd import features as impl
     if threshold == 0:
         monkeypatch.setattr(impl, "_ORB_DEFAULT_CAPACITY", 64)
     images = pc.gpu_images()
     scales = rs.orb_scales(4)
     quotas = rs.orb_level_quotas(500, scales)
-    got = _extract(images, n_levels=4, threshold=threshold)
+    got = oc.extract(images, per_level=True, n_levels=4, threshold=threshold)
     total = 0
     for img, g in zip(images, got):
         st, want = pc.host_extract_pyramid(lib, img, scales, quotas, threshold=threshold)
@@ -98,17 +79,24 @@ def test_extract_batch_equals_host_twin(gpu, lib, monkeypatch, threshold):
     if threshold == 0:
         assert max(got[0]["found"]) > 64
     # the caller's table and quotas, one of them zero
-    mine = _extract(images[:2], scales=pc.CALLER_SCALES, quotas=[40, 0, 7], threshold=threshold)
+    mine = oc.extract(images[:2], per_level=True, scales=pc.CALLER_SCALES, quotas=[40, 0, 7], threshold=threshold)
     for img, g in zip(images, mine):
         st, want = pc.host_extract_pyramid(lib, img, pc.CALLER_SCALES, [40, 0, 7], threshold=threshold)
         assert st == 0 and pc.same(g, want), img.shape
 
 
-def test_one_level_is_the_call_without_the_argument(gpu):
+@pytest.fixture(scope="module")
+def one_level(gpu):
+    """The batch of the one-level tests and its extraction with the defaults: (images, features, info)."""
     import ransac as rs
     images = pc.gpu_images() + [oc.foto("A")[200:400, 300:600]]
-    ia, ib = {}, {}
-    a = rs.extract_batch(images, info=ia)
+    info = {}
+    return images, rs.extract_batch(images, info=info), info
+
+
+def test_one_level_is_the_call_without_the_argument(gpu, one_level):
+    import ransac as rs
+    (images, a, ia), ib = one_level, {}
     b = rs.extract_batch(images, n_levels=1, info=ib)
     c = rs.extract_batch(images, scales=[256], quotas=[500])
     for (ka, da), (kb, db), (kc, dc) in zip(a, b, c):
@@ -116,6 +104,40 @@ def test_one_level_is_the_call_without_the_argument(gpu):
     assert ia["found"] == ib["found"] and ia["counts"] == ib["counts"] and sum(ia["counts"]) > 500
     assert all(gpu.equal(x, y) for k in ("score", "bin", "level", "size") for x, y in zip(ia[k], ib[k]))
     assert all(int(l.sum()) == 0 and (z == 31).all() for l, z in zip(ib["level"], ib["size"]))
+
+
+def _same_call(torch, a, ia, b, ib):
+    """Every returned tensor and every `info` entry of two extract_batch calls: dtype, shape and bits."""
+    same = lambda x, y: x.dtype == y.dtype and x.is_cuda and y.is_cuda and torch.equal(x, y)
+    assert len(a) == len(b) and all(same(ka, kb) and same(da, db) for (ka, da), (kb, db) in zip(a, b))
+    assert sorted(ia) == sorted(ib) == ["bin", "counts", "found", "found_levels", "level", "score", "size"]
+    assert all(len(ia[k]) == len(ib[k]) == len(a) and all(same(x, y) for x, y in zip(ia[k], ib[k])) for k in ("score", "bin", "level", "size"))
+    assert all(ia[k] == ib[k] and len(ia[k]) == len(a) for k in ("counts", "found", "found_levels"))
+
+
+def test_one_level_quota_is_n_features(gpu, one_level):
+    """quotas=[40] on the only level is n_features=40, for an image that finds more and for one that finds fewer."""
+    import ransac as rs
+    images, _, first = one_level
+    assert max(first["found"]) > 40 > min(first["found"]) > 0
+    ia, ib = {}, {}
+    a = rs.extract_batch(images, quotas=[40], info=ia)
+    b = rs.extract_batch(images, n_features=40, info=ib)
+    _same_call(gpu, a, ia, b, ib)
+    assert ia["counts"] == [min(f, 40) for f in first["found"]] and ia["found"] == first["found"]
+
+
+def test_one_level_overflow_retry(gpu, one_level, monkeypatch):
+    """The usual room cut to 64 with one level: images that find more meet the overflow status, the detect call is repeated with
+    room for all, and the result is the call's with the usual room."""
+    import ransac as rs
+    from ransac_with_homography_amd import features as impl
+    images, want, iw = one_level
+    assert max(iw["found"]) > 64
+    monkeypatch.setattr(impl, "_ORB_DEFAULT_CAPACITY", 64)
+    info = {}
+    got = rs.extract_batch(images, info=info)
+    _same_call(gpu, got, info, want, iw)
 
 
 @pytest.mark.parametrize("levels", [3, 4])
@@ -126,7 +148,7 @@ def test_seventy_images(gpu, lib, levels):
     images = [oc.random_image(40, 40, 300 + i, channels=(1, 3)[i % 2]) if i % 3 else oc.random_image(33, 64, 300 + i, channels=1) for i in range(70)]
     scales = rs.orb_scales(levels)
     quotas = rs.orb_level_quotas(60, scales)
-    got = _extract(images, n_levels=levels, n_features=60)
+    got = oc.extract(images, per_level=True, n_levels=levels, n_features=60)
     on_level = np.zeros(levels, dtype=int)
     for i, (img, g) in enumerate(zip(images, got)):
         st, want = pc.host_extract_pyramid(lib, img, scales, quotas)

@@ -1,18 +1,18 @@
-"""The feature extractor (ransac.extract_batch: rwh_orb_detect_batched -> one sort -> rwh_orb_describe_batched) at the two sizes
+"""The feature extractor (features.extract_batch: rwh_orb_detect_batched -> one sort -> rwh_orb_describe_batched) at the two sizes
 profiles/extract_orb.txt records: one 683 x 1024 RGB image (tests/golden/img_foto1.npz A), and a batch of 64 (A and B alternating,
 each shifted by a few rows so that no two are the same), threshold 20, n_features 500, 32-byte descriptors.
 
 Per case, by device events over windows of CALLS back-to-back calls after warm-up, median and minimum of WINDOWS windows: the
 detect call (two memsets, the tile prefix, the tiled kernel), the describe call (one launch) and the whole extract_batch (upload of
 nothing -- the images are device tensors --, both calls, the sort, and the one download of the counts, which synchronises).  Each
-is set against two numbers measured in the same run: the host twin (rwh_host_orb_extract, one core, per image) on the same input,
-and a plain device copy of the images' bytes (torch's copy kernel: the floor for a kernel that reads every pixel once).  The
+is set against two numbers measured in the same run: the host twin (rwh_host_orb_extract_pyramid, one core, per image) on the same
+input, and a plain device copy of the buffer's bytes (torch's copy kernel: the floor for a kernel that reads every pixel once).  The
 results are checked against the host twin first.
 
---levels N (default 1) times the scale pyramid (rules 6 - 8 of include/rwh.h, `extract_batch(n_levels=N)`) instead: the pyramid
-call (rwh_orb_pyramid_batched: its tile prefix and the kernel that makes levels 1 .. N - 1 of the whole batch), then detect, the
-sort and describe over the n * N rows of the table, and the whole extract_batch; the host twin is rwh_host_orb_extract_pyramid,
-and the copy set beside the pyramid call moves as many bytes as it reads and writes.
+--levels N (default 1): the scale pyramid (rules 6 - 8 of include/rwh.h, `extract_batch(n_levels=N)`).  With N > 1 the pyramid call
+(rwh_orb_pyramid_batched: its tile prefix and the kernel that makes levels 1 .. N - 1 of the whole batch) is timed too, detect, the
+sort and describe run over the n * N rows of the table, and the copy set beside the pyramid call moves as many bytes as it reads
+and writes.  The buffer and the table of the separate calls are features.orb_layout's, as extract_batch's are.
 
     python tools/orb_probe.py [windows] [calls] [--levels N]
 """
@@ -26,7 +26,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from ransac_with_homography_amd import _lib, kernels        # noqa: E402
-from ransac_with_homography_amd import ransac as rs         # noqa: E402
+from ransac_with_homography_amd import features as ft       # noqa: E402
 
 ARGS = list(sys.argv[1:])
 LEVELS = 1
@@ -57,64 +57,14 @@ def windows(fn, calls):
     return float(np.median(ts)), float(np.min(ts))
 
 
-def host_twin(img, table, rot):
-    kps = np.empty((N_FEATURES, 2), np.float32)
-    desc = np.empty((N_FEATURES, NBYTES), np.uint8)
-    score, bins, count = np.empty(N_FEATURES, np.int32), np.empty(N_FEATURES, np.int32), np.zeros(1, np.int32)
-    t = time.perf_counter()
-    st = lib.rwh_host_orb_extract(img.ctypes.data, img.shape[0], img.shape[1], 3, THRESHOLD, N_FEATURES, table.ctypes.data, rot.ctypes.data,
-                                  NBYTES, kps.ctypes.data, desc.ctypes.data, score.ctypes.data, bins.ctypes.data, count.ctypes.data, None)
-    dt = time.perf_counter() - t
-    assert st == 0
-    return dt, kps[:count[0]].copy(), desc[:count[0]].copy()
-
-
 def case(name, images):
-    table, rot = rs.orb_bin_table(), np.ascontiguousarray(rs.rotate_pattern(rs.default_pattern(NBYTES)))
-    dev_images = [torch.from_numpy(im).to(dev) for im in images]
-    feats = rs.extract_batch(dev_images, n_features=N_FEATURES, threshold=THRESHOLD, nbytes=NBYTES)
-    host_s = 0.0
-    for i in sorted(set((0, len(images) - 1))):
-        dt, kps, desc = host_twin(images[i], table, rot)
-        host_s += dt
-        assert np.array_equal(feats[i][0].cpu().numpy(), kps) and np.array_equal(feats[i][1].cpu().numpy(), desc), "device != host twin"
-    host_per_image = host_s / len(set((0, len(images) - 1)))
-    # the two library calls on their own, on the tensors extract_batch would hand them
-    src = torch.cat([t.reshape(-1) for t in dev_images])
-    rows, so, go = [], 0, 0
-    for im in images:
-        rows.append((so, go, im.shape[0], im.shape[1], 3)); so += im.size; go += im.shape[0] * im.shape[1]
-    tab = torch.tensor(rows, dtype=torch.int64, device=dev)
-    cap = 1 << 16
-    gray, keys, counts = kernels.orb_detect_batched(src, tab, go, THRESHOLD, cap)
-    assert int(counts.max()) <= cap
-    keys = torch.sort(keys, dim=1).values
-    bt, pt = torch.from_numpy(table).to(dev), torch.from_numpy(rot).to(dev)
-    out_keys = torch.empty_like(keys)
-    t_detect = windows(lambda: kernels.orb_detect_batched(src, tab, go, THRESHOLD, cap, out_keys=out_keys), CALLS)
-    t_describe = windows(lambda: kernels.orb_describe_batched(gray, go, tab, keys, counts, N_FEATURES, bt, pt), CALLS)
-    t_sort = windows(lambda: torch.sort(out_keys, dim=1), CALLS)
-    t_all = windows(lambda: rs.extract_batch(dev_images, n_features=N_FEATURES, threshold=THRESHOLD, nbytes=NBYTES), max(CALLS // 4, 2))
-    dst = torch.empty_like(src)
-    t_copy = windows(lambda: dst.copy_(src), CALLS)
-    n, px = len(images), go
-    print("%s: %d image(s), %.2f Mpx, %d keypoints found, %d kept" % (name, n, px / 1e6, int(counts.sum()), sum(f[0].shape[0] for f in feats)))
-    for what, (med, mn) in (("detect call", t_detect), ("describe call", t_describe), ("sort of the keys [n, 65536]", t_sort),
-                            ("extract_batch, whole", t_all), ("device copy of the image bytes", t_copy)):
-        print("  %-34s median %9.1f us   min %9.1f us   (%.1f us / image)" % (what, med, mn, med / n))
-    print("  %-34s %9.1f us / image on one host core;  extract_batch is %.0fx faster per image, detect is %.1fx the copy"
-          % ("host twin", host_per_image * 1e6, host_per_image * 1e6 / (t_all[0] / n), t_detect[0] / t_copy[0]))
-    print("  detect reads %.1f MB and writes %.1f MB of gray: %.0f GB/s" % (src.numel() / 1e6, go / 1e6, (src.numel() + go) / t_detect[0] / 1e3))
-
-
-def pyramid_case(name, images):
-    """The same two sizes with LEVELS levels: scales and quotas are extract_batch's defaults."""
-    table, rot = rs.orb_bin_table(), np.ascontiguousarray(rs.rotate_pattern(rs.default_pattern(NBYTES)))
-    scales = rs.orb_scales(LEVELS)
-    quotas = rs.orb_level_quotas(N_FEATURES, scales)
+    """One of the two sizes with LEVELS levels: scales and quotas are extract_batch's defaults, buffer and table features.orb_layout's."""
+    table, rot = ft.orb_bin_table(), np.ascontiguousarray(ft.rotate_pattern(ft.default_pattern(NBYTES)))
+    scales = ft.orb_scales(LEVELS)
+    quotas = ft.orb_level_quotas(N_FEATURES, scales)
     room = int(quotas.sum())
     dev_images = [torch.from_numpy(im).to(dev) for im in images]
-    extract = lambda: rs.extract_batch(dev_images, n_features=N_FEATURES, threshold=THRESHOLD, nbytes=NBYTES, n_levels=LEVELS)
+    extract = lambda: ft.extract_batch(dev_images, n_features=N_FEATURES, threshold=THRESHOLD, nbytes=NBYTES, n_levels=LEVELS)
     feats = extract()
     host_s, picks = 0.0, sorted(set((0, len(images) - 1)))
     for i in picks:
@@ -129,52 +79,53 @@ def pyramid_case(name, images):
         host_s += time.perf_counter() - t
         assert st == 0
         assert np.array_equal(feats[i][0].cpu().numpy(), kps[:count[0]]) and np.array_equal(feats[i][1].cpu().numpy(), desc[:count[0]]), "device != host twin"
-    host_per_image = host_s / len(picks)
     # the library calls on their own, on the buffer and table extract_batch would hand them
-    rows, so, go = [], 0, 0
-    po = sum(im.size for im in images)
-    head = po
-    for im in images:
-        h, w = im.shape[:2]
-        rows.append((so, go, h, w, 3)); so += im.size; go += h * w
-        for s in scales[1:].tolist():
-            hl, wl = (256 * h + s // 2) // s, (256 * w + s // 2) // s
-            rows.append((po, go, hl, wl, 1)); po += hl * wl; go += hl * wl
+    rows, head, po, go, _ = ft.orb_layout([im.shape for im in images], scales)
     src = torch.cat([t.reshape(-1) for t in dev_images] + [torch.empty((po - head,), dtype=torch.uint8, device=dev)])
-    tab = torch.tensor(rows, dtype=torch.int64, device=dev)
+    tab = torch.from_numpy(rows).to(dev)
     cap = 1 << 16
-    kernels.orb_pyramid_batched(src, head, tab, scales)
+    if LEVELS > 1:
+        kernels.orb_pyramid_batched(src, head, tab, scales)
     gray, keys, counts = kernels.orb_detect_batched(src, tab, go, THRESHOLD, cap)
     assert int(counts.max()) <= cap
     keys = torch.sort(keys, dim=1).values
     clamped = torch.minimum(counts, torch.from_numpy(np.tile(quotas, len(images))).to(dev))
     bt, pt = torch.from_numpy(table).to(dev), torch.from_numpy(rot).to(dev)
     out_keys, nf = torch.empty_like(keys), int(quotas.max())
-    t_pyr = windows(lambda: kernels.orb_pyramid_batched(src, head, tab, scales), CALLS)
+    if LEVELS > 1:
+        t_pyr = windows(lambda: kernels.orb_pyramid_batched(src, head, tab, scales), CALLS)
     t_detect = windows(lambda: kernels.orb_detect_batched(src, tab, go, THRESHOLD, cap, out_keys=out_keys), CALLS)
     t_describe = windows(lambda: kernels.orb_describe_batched(gray, go, tab, keys, clamped, nf, bt, pt), CALLS)
     t_sort = windows(lambda: torch.sort(out_keys, dim=1), CALLS)
     t_all = windows(extract, max(CALLS // 4, 2))
-    base_px = sum(im.shape[0] * im.shape[1] for im in images)
-    half = (po + 1) // 2                                                       # a copy of half the bytes reads and writes head + planes in all
-    a, b = torch.empty((half,), dtype=torch.uint8, device=dev), torch.empty((half,), dtype=torch.uint8, device=dev)
-    t_copy_pyr = windows(lambda: a.copy_(b), CALLS)
+    if LEVELS > 1:
+        half = (po + 1) // 2                                                   # a copy of half the bytes reads and writes head + planes in all
+        a, b = torch.empty((half,), dtype=torch.uint8, device=dev), torch.empty((half,), dtype=torch.uint8, device=dev)
+        t_copy_pyr = windows(lambda: a.copy_(b), CALLS)
     dst = torch.empty_like(src)
     t_copy = windows(lambda: dst.copy_(src), CALLS)
-    n = len(images)
-    print("%s, %d levels: %d image(s), %.2f Mpx on level 0, %.2f Mpx on levels 1 .. (%.2fx), %d keypoints found, %d kept"
-          % (name, LEVELS, n, base_px / 1e6, (po - head) / 1e6, (po - head) / base_px, int(counts.sum()), sum(f[0].shape[0] for f in feats)))
-    for what, (med, mn) in (("pyramid call", t_pyr), ("copy moving the pyramid's bytes", t_copy_pyr), ("detect call, %d rows" % len(rows), t_detect),
-                            ("describe call", t_describe), ("sort of the keys [%d, 65536]" % len(rows), t_sort), ("extract_batch, whole", t_all),
-                            ("device copy of images + planes", t_copy)):
+    n, base_px, kept = len(images), sum(im.shape[0] * im.shape[1] for im in images), sum(f[0].shape[0] for f in feats)
+    host_us, pyr = host_s / len(picks) * 1e6, LEVELS > 1
+    if pyr:
+        print("%s, %d levels: %d image(s), %.2f Mpx on level 0, %.2f Mpx on levels 1 .. (%.2fx), %d keypoints found, %d kept"
+              % (name, LEVELS, n, base_px / 1e6, (po - head) / 1e6, (po - head) / base_px, int(counts.sum()), kept))
+    else:
+        print("%s: %d image(s), %.2f Mpx, %d keypoints found, %d kept" % (name, n, base_px / 1e6, int(counts.sum()), kept))
+    lines = [("pyramid call", t_pyr), ("copy moving the pyramid's bytes", t_copy_pyr)] if pyr else []
+    lines += [("detect call, %d rows" % len(rows) if pyr else "detect call", t_detect), ("describe call", t_describe),
+              ("sort of the keys [%s, 65536]" % (len(rows) if pyr else "n"), t_sort), ("extract_batch, whole", t_all),
+              ("device copy of images + planes" if pyr else "device copy of the image bytes", t_copy)]
+    for what, (med, mn) in lines:
         print("  %-34s median %9.1f us   min %9.1f us   (%.1f us / image)" % (what, med, mn, med / n))
-    print("  %-34s %9.1f us / image on one host core;  extract_batch is %.0fx faster per image" % ("host twin", host_per_image * 1e6, host_per_image * 1e6 / (t_all[0] / n)))
-    print("  the pyramid call reads %.1f MB and writes %.1f MB: %.0f GB/s; per output pixel %.2f ns, detect per pixel of its rows %.2f ns"
-          % (head / 1e6, (po - head) / 1e6, po / t_pyr[0] / 1e3, t_pyr[0] * 1e3 / (po - head), t_detect[0] * 1e3 / go))
+    print("  %-34s %9.1f us / image on one host core;  extract_batch is %.0fx faster per image" % ("host twin", host_us, host_us / (t_all[0] / n))
+          + ("" if pyr else ", detect is %.1fx the copy" % (t_detect[0] / t_copy[0])))
+    if pyr:
+        print("  the pyramid call reads %.1f MB and writes %.1f MB: %.0f GB/s; per output pixel %.2f ns, detect per pixel of its rows %.2f ns"
+              % (head / 1e6, (po - head) / 1e6, po / t_pyr[0] / 1e3, t_pyr[0] * 1e3 / (po - head), t_detect[0] * 1e3 / go))
+    else:
+        print("  detect reads %.1f MB and writes %.1f MB of gray: %.0f GB/s" % (src.numel() / 1e6, go / 1e6, (src.numel() + go) / t_detect[0] / 1e3))
 
 
-if LEVELS > 1:
-    case = pyramid_case
 z = np.load(os.path.join(ROOT, "tests", "golden", "img_foto1.npz"), allow_pickle=False)
 A, B = np.ascontiguousarray(z["A"]), np.ascontiguousarray(z["B"])
 print("orb_probe: %s, windows %d x %d calls" % (torch.cuda.get_device_name(dev), WINDOWS, CALLS))
