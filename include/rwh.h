@@ -878,6 +878,67 @@ RWH_API int rwh_host_stitch_multiband(const void* const* images, const int32_t* 
                                       int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
                                       int origin_x, int origin_y);
 
+/*
+ * Cylindrical and spherical canvases for the sequence compositor.  The sequence rule projects every image onto the anchor's image
+ * plane, which suits a narrow sweep only: the plane grows with tan of the angle and ends at 90 degrees, beyond which an image lands
+ * mirrored.  Panorama stitchers therefore composite onto a cylinder or a sphere about the camera (Szeliski & Shum 1997).  The
+ * reference's cylindericlMap is a stub and has no compositor behind it; this is held to THE PROJECTION RULE below.  Everything not
+ * restated is the sequence rule's.
+ *
+ * The projection rule.
+ *   Inputs.  Those of the sequence rule; focal = f, finite and > 0, in pixels; the kind of surface, cylinder or sphere.
+ *     K = [[f, 0, (w_a - 1) / 2], [0, f, (h_a - 1) / 2], [0, 0, 1]] from the anchor's shape.  Every G_i is multiplied by
+ *     sign(det G_i); a zero or non-finite determinant is refused.
+ *   Surface and canvas.  A ray r = (r0, r1, r2) in the anchor's camera has theta = atan2(r0, r2) and t = r1 / hypot(r0, r2) on the
+ *     cylinder, t = atan2(r1, hypot(r0, r2)) on the sphere; its surface point is (u, s) = (f theta, f t).  Canvas pixel (cx, cy) is
+ *     surface point (ox + cx, oy + cy), ox and oy integers.
+ *   Ray tables.  The compositor knows nothing of sin or cos: it takes two float64 tables made on the host with numpy,
+ *     col[cx] = (sin(u / f), cos(u / f)), and row[cy] = (s / f, 1.0) on the cylinder, (sin(s / f), cos(s / f)) on the sphere.  The ray
+ *     of a pixel is r0 = col[cx][0] * row[cy][1], r1 = row[cy][0], r2 = col[cx][1] * row[cy][1].  Device, host twin and a numpy
+ *     restatement read the same numbers and agree exactly; none of them calls a transcendental function.
+ *   Sample.  M_i = numpy.linalg.inv(G_i) @ K in float64 on the host; the anchor's M is K exactly.  X = fma(m2, r2, fma(m1, r1,
+ *     m0 * r0)), Y and W likewise with rows 1 and 2 of M_i; no other contraction.  valid = W > 0 and the sequence rule's bounds test on
+ *     sx = X / W, sy = Y / W.  W <= 0 is a ray behind image i's camera: what the plane would show mirrored.  From sx, sy on, the
+ *     taps, texel (0,0) reading as 0, the lerps, the feather weight g and the gain are the sequence rule's recipe for a warped
+ *     image.  EVERY image is sampled this way, the anchor included: on a curved canvas no image enters unwarped.
+ *   Rectangles, in surface pixels.  The surface points of all perimeter pixels of image i, whose rays are inv(K) G_i (x, y, 1),
+ *     not dehomogenised; the rectangle runs from floor(min) - 1 to ceil(max) + 1 on each axis.  Refused: a non-finite point; two
+ *     consecutive perimeter points whose theta differ by pi or more (the image straddles the seam behind the anchor); a perimeter
+ *     whose wrapped theta differences do not sum to 0 (the image contains a pole).  The canvas is the union of the rectangles,
+ *     under the sequence rule's size limits.  The library takes the rectangles in CANVAS coordinates (origin subtracted).
+ *   Coverage.  Inside the rectangle and valid.  The rectangle only has to contain every valid pixel.
+ *   Paste order, feather, the gain rule, the overlap statistics and the multi-band rule are unchanged on this Sample and Coverage.
+ *
+ * rwh_stitch_sequence_proj, rwh_sequence_overlap_stats_proj, rwh_stitch_multiband_proj: arguments as rwh_stitch_sequence_ex's,
+ * rwh_sequence_overlap_stats's and rwh_stitch_multiband's, except: m (N x 9, the M_i) stands in place of inv_g; d_col and d_row are
+ * the two tables on the device, exactly canvas_w x 2 and canvas_h x 2 doubles, 16-byte aligned, read only at indices inside the
+ * canvas (a lane's pair is one 16-byte load, a wave's row entry a scalar load); rects are in canvas coordinates; there is no anchor
+ * and no origin; gains may be NULL.  Workspaces: the sizes of rwh_stitch_sequence_workspace_bytes,
+ * rwh_sequence_overlap_stats_workspace_bytes and rwh_stitch_multiband_workspace_bytes (with origin (0, 0)).  The reduce and collapse
+ * passes of the multi-band call work on canvas planes and are the planar call's.  RWH_E_INVALID, before anything is launched:
+ * everything the planar siblings refuse, a NULL or misaligned table, a non-finite M (no image is exempt).
+ * rwh_host_*_proj: the same arithmetic on host memory (the tables 8-byte aligned), no GPU involved.
+ */
+RWH_API int rwh_stitch_sequence_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                     const int32_t* order, int blend, const double* d_col, const double* d_row, void* d_canvas,
+                                     int canvas_h, int canvas_w, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                     void* stream, const double* gains);
+RWH_API int rwh_host_stitch_sequence_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                          const int32_t* order, int blend, const double* col, const double* row, void* canvas,
+                                          int canvas_h, int canvas_w, int row_begin, int row_end, const double* gains);
+RWH_API int rwh_sequence_overlap_stats_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                            const double* d_col, const double* d_row, int canvas_h, int canvas_w, int stride,
+                                            uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_sequence_overlap_stats_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                 const double* col, const double* row, int canvas_h, int canvas_w, int stride,
+                                                 uint64_t* count, uint64_t* sum);
+RWH_API int rwh_stitch_multiband_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                      int bands, const double* gains, const double* d_col, const double* d_row, void* d_canvas,
+                                      int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_stitch_multiband_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                           int bands, const double* gains, const double* col, const double* row, void* canvas,
+                                           int canvas_h, int canvas_w);
+
 #ifdef __cplusplus
 }
 #endif

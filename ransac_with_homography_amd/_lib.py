@@ -48,7 +48,9 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_stitch_sequence_workspace_bytes", "rwh_stitch_sequence", "rwh_host_stitch_sequence",
            "rwh_sequence_overlap_stats_workspace_bytes", "rwh_sequence_overlap_stats", "rwh_host_sequence_overlap_stats",
            "rwh_host_sequence_gains", "rwh_stitch_sequence_ex", "rwh_host_stitch_sequence_ex",
-           "rwh_stitch_multiband_workspace_bytes", "rwh_stitch_multiband", "rwh_host_stitch_multiband")
+           "rwh_stitch_multiband_workspace_bytes", "rwh_stitch_multiband", "rwh_host_stitch_multiband",
+           "rwh_stitch_sequence_proj", "rwh_host_stitch_sequence_proj", "rwh_sequence_overlap_stats_proj",
+           "rwh_host_sequence_overlap_stats_proj", "rwh_stitch_multiband_proj", "rwh_host_stitch_multiband_proj")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -187,6 +189,24 @@ def _bind(lib):
                                          vp, i32, i32, i32, i32, vp, i64, vp]                    # canvas h w origin_x origin_y workspace bytes stream
     lib.rwh_host_stitch_multiband.restype = i32
     lib.rwh_host_stitch_multiband.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32]
+    # the projection rule: m in place of inv_g, the two ray tables, rectangles on the canvas, no anchor and no origin
+    lib.rwh_stitch_sequence_proj.restype = i32
+    lib.rwh_stitch_sequence_proj.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp,      # images hw m rects n order blend col row
+                                             vp, i32, i32, i32, i32,                    # canvas h w row_begin row_end
+                                             vp, i64, vp, vp]                           # workspace bytes stream gains
+    lib.rwh_host_stitch_sequence_proj.restype = i32
+    lib.rwh_host_stitch_sequence_proj.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.rwh_sequence_overlap_stats_proj.restype = i32
+    lib.rwh_sequence_overlap_stats_proj.argtypes = [vp, vp, vp, vp, i32, vp, vp,        # images hw m rects n col row
+                                                    i32, i32, i32,                      # canvas h w stride
+                                                    vp, vp, vp, i64, vp]                # count sum workspace bytes stream
+    lib.rwh_host_sequence_overlap_stats_proj.restype = i32
+    lib.rwh_host_sequence_overlap_stats_proj.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp]
+    lib.rwh_stitch_multiband_proj.restype = i32
+    lib.rwh_stitch_multiband_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp,     # images hw m rects n bands gains col row
+                                              vp, i32, i32, vp, i64, vp]                # canvas h w workspace bytes stream
+    lib.rwh_host_stitch_multiband_proj.restype = i32
+    lib.rwh_host_stitch_multiband_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32]
     return lib
 
 

@@ -42,16 +42,20 @@ struct MbArgs {
 // ---- the per-pixel functions ----
 // P and the winner at canvas pixel (cx, cy): the covering image with the greatest feather weight g, the lowest index on equal
 // weights (candidates are visited in index order and only a greater g replaces the best; g >= 1 wherever an image covers).
-template <bool GAIN>
-__host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains) {
+// rays: the ray tables of the projection rule, read with PROJ only.
+template <bool GAIN, bool PROJ = false>
+__host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains,
+                                                             SeqRays rays = SeqRays{nullptr, nullptr}) {
     const int fx = a.ox + cx, fy = a.oy + cy;
+    SeqRay ray;
+    if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
     double best = 0.0;
     uint32_t out = MB_NONE << 24;
     for (uint64_t m = cand; m; m &= m - 1) {
         const int i = __builtin_ctzll(m);
         double v[3], g = 0.0, gain = 1.0;
         if constexpr (GAIN) gain = gains[i];
-        if (!seq_sample<true, GAIN>(a.desc[i], i == a.anchor, fx, fy, v, g, gain)) continue;
+        if (!seq_sample<true, GAIN, PROJ>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray)) continue;
         if (g > best) {
             best = g;
             out = (uint32_t)i << 24;
@@ -63,8 +67,9 @@ __host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, u
 }
 
 // (I_i, W_i) at plane pixel (x, y) of level 0: image i's bytes where it covers, P elsewhere; MB_ONE where i is the winner.
-template <bool GAIN>
-__host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i, uint32_t pwv, int x, int y, const double* gains) {
+template <bool GAIN, bool PROJ = false>
+__host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i, uint32_t pwv, int x, int y, const double* gains,
+                                                         SeqRays rays = SeqRays{nullptr, nullptr}) {
     MbPx o;
 #pragma unroll
     for (int k = 0; k < 3; ++k) o.c[k] = (int16_t)((pwv >> (8 * k)) & 0xffu);
@@ -72,7 +77,9 @@ __host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i
     if (x < a.fw && y < a.fh) {
         double v[3], g = 0.0, gain = 1.0;
         if constexpr (GAIN) gain = gains[i];
-        if (seq_sample<false, GAIN>(a.desc[i], i == a.anchor, a.ox + x, a.oy + y, v, g, gain)) {
+        SeqRay ray;
+        if constexpr (PROJ) ray = seq_ray(rays, x, y);
+        if (seq_sample<false, GAIN, PROJ>(a.desc[i], i == a.anchor, a.ox + x, a.oy + y, v, g, gain, &ray)) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) o.c[k] = (int16_t)(unsigned char)(int)v[k];
         }
@@ -207,27 +214,27 @@ __host__ __device__ __forceinline__ uint64_t mb_window_mask(const MbArgs& m, int
 
 // ---- the kernels ----
 // 256 lanes as 64 x 4, one pixel of the padded canvas each; the tile is tested once against the n rectangles (block-uniform).
-template <bool GAIN>
-__global__ __launch_bounds__(256) void mb_winner_kernel(const SeqWith<MbArgs, GAIN> l) {
+template <bool GAIN, bool PROJ = false>
+__global__ __launch_bounds__(256) void mb_winner_kernel(const SeqWith<MbArgs, GAIN, PROJ> l) {
     const MbArgs& m = l.a;
     const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
     const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
-    const int x = bx0 + (threadIdx.x & 63), y = by0 + (threadIdx.x >> 6);
+    const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
     if (x >= m.PW || y >= m.PH) return;
     const bool on = x < m.a.fw && y < m.a.fh;
-    m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<GAIN>(m.a, cand, x, y, seq_gains(l)) : MB_NONE << 24;
+    m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<GAIN, PROJ>(m.a, cand, x, y, seq_gains(l), seq_rays(l)) : MB_NONE << 24;
 }
 
 // blockIdx.z is the image; a block takes 64 x 4 pixels of its level-0 window (blocks beyond the window leave at once).
-template <bool GAIN>
-__global__ __launch_bounds__(256) void mb_level0_kernel(const SeqWith<MbArgs, GAIN> l) {
+template <bool GAIN, bool PROJ = false>
+__global__ __launch_bounds__(256) void mb_level0_kernel(const SeqWith<MbArgs, GAIN, PROJ> l) {
     const MbArgs& m = l.a;
     const int i = blockIdx.z;
     const MbWin w = m.win[(size_t)i * (m.K + 1)];
-    const int lx = blockIdx.x * 64 + (threadIdx.x & 63), ly = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int lx = blockIdx.x * 64 + (threadIdx.x & 63), ly = blockIdx.y * 4 + seq_wave_row<PROJ>(threadIdx.x >> 6);
     if (lx >= w.w || ly >= w.h) return;
     const int x = w.x0 + lx, y = w.y0 + ly;
-    m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l));
+    m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN, PROJ>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l), seq_rays(l));
 }
 
 // The reduce from level l to l + 1 of image blockIdx.z.  A block makes MB_TW x MB_TH outputs from a (2 MB_TW + 3) x (2 MB_TH + 3)
@@ -354,8 +361,8 @@ static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int 
 // Everything both entry points check, the descriptors and the plan.
 static int mb_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor, int bands,
                       const double* gains, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, MbArgs& m,
-                      MbPlan& p) {
-    int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m.a);
+                      MbPlan& p, bool proj = false) {
+    int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m.a, proj);
     if (st != RWH_OK) return st;
     if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
     st = mb_plan(rects, n, canvas_h, canvas_w, origin_x, origin_y, bands, p);
@@ -374,25 +381,25 @@ static void mb_bind(MbArgs& m, const MbPlan& p, char* base) {
     for (int l = 1; l < MB_LEVELS; ++l) m.r[l] = l <= p.K ? reinterpret_cast<MbPx*>(base + p.r_at[l]) : nullptr;
 }
 
-template <bool GAIN>
-static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains, hipStream_t s) {
-    const SeqWith<MbArgs, GAIN> l = seq_with<GAIN>(m, gains, m.a.n);
-    hipLaunchKernelGGL((mb_winner_kernel<GAIN>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
-    hipLaunchKernelGGL((mb_level0_kernel<GAIN>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
+template <bool GAIN, bool PROJ>
+static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays, hipStream_t s) {
+    const SeqWith<MbArgs, GAIN, PROJ> l = seq_with<GAIN, PROJ>(m, gains, m.a.n, rays);
+    hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
+    hipLaunchKernelGGL((mb_level0_kernel<GAIN, PROJ>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
 }
 
-template <bool GAIN>
-static void mb_host_run(const MbArgs& m, const MbPlan& p, const double* gains) {
+template <bool GAIN, bool PROJ>
+static void mb_host_run(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays) {
     const int n = m.a.n, K = p.K;
     const uint64_t all = seq_all(n);
     for (int y = 0; y < p.PH; ++y)
         for (int x = 0; x < p.PW; ++x)
-            m.pw[(int64_t)y * p.PW + x] = (x < m.a.fw && y < m.a.fh) ? mb_winner_pixel<GAIN>(m.a, all, x, y, gains) : MB_NONE << 24;
+            m.pw[(int64_t)y * p.PW + x] = (x < m.a.fw && y < m.a.fh) ? mb_winner_pixel<GAIN, PROJ>(m.a, all, x, y, gains, rays) : MB_NONE << 24;
     for (int i = 0; i < n; ++i) {
         const MbWin& w = m.win[i * (K + 1)];
         for (int ly = 0; ly < w.h; ++ly)
             for (int lx = 0; lx < w.w; ++lx)
-                m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN>(m.a, i, m.pw[(int64_t)(w.y0 + ly) * p.PW + w.x0 + lx], w.x0 + lx, w.y0 + ly, gains);
+                m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN, PROJ>(m.a, i, m.pw[(int64_t)(w.y0 + ly) * p.PW + w.x0 + lx], w.x0 + lx, w.y0 + ly, gains, rays);
         for (int l = 0; l < K; ++l) {
             const MbWin& src = m.win[i * (K + 1) + l];
             const MbWin& dst = m.win[i * (K + 1) + l + 1];
@@ -419,22 +426,26 @@ extern "C" int64_t rwh_stitch_multiband_workspace_bytes(const int32_t* rects, in
     return st == RWH_OK ? p.bytes : (int64_t)st;
 }
 
-extern "C" int rwh_stitch_multiband(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
-                                    int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
-                                    int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream) {
+// The device call behind rwh_stitch_multiband (PROJ false: rays unused) and rwh_stitch_multiband_proj (PROJ true: mats holds the
+// M_i, no anchor, origin (0, 0)).  The reduce and collapse passes work on canvas planes and are the same for both.
+template <bool PROJ>
+static int mb_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
+                     int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
+                     int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
     MbPlan p;
-    const int st = mb_prepare(d_images, hw, inv_g, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p);
+    const int st = mb_prepare(d_images, hw, mats, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ);
     if (st != RWH_OK) return st;
     if (!d_workspace || workspace_bytes < p.bytes || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
+    if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(d_workspace);
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
     seq_put(p.win, (size_t)n * (p.K + 1) * (sizeof(MbWin) / 8), reinterpret_cast<uint64_t*>(base + p.win_at), s);
     mb_bind(m, p, base);
-    if (gains) mb_launch_head<true>(m, p, gains, s); else mb_launch_head<false>(m, p, nullptr, s);
+    if (gains) mb_launch_head<true, PROJ>(m, p, gains, rays, s); else mb_launch_head<false, PROJ>(m, p, nullptr, rays, s);
     for (int l = 0; l < p.K; ++l)
         hipLaunchKernelGGL(mb_down_kernel, dim3((p.maxw[l + 1] + MB_TW - 1) / MB_TW, (p.maxh[l + 1] + MB_TH - 1) / MB_TH, n), dim3(256), 0, s, m, l);
     for (int l = p.K; l >= 0; --l)
@@ -442,21 +453,51 @@ extern "C" int rwh_stitch_multiband(const void* const* d_images, const int32_t* 
     return check_launch();
 }
 
-extern "C" int rwh_host_stitch_multiband(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
-                                         int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
-                                         int origin_x, int origin_y) {
+extern "C" int rwh_stitch_multiband(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                    int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
+                                    int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    return mb_device<false>(d_images, hw, inv_g, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
+                            d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr});
+}
+
+extern "C" int rwh_stitch_multiband_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                         int bands, const double* gains, const double* d_col, const double* d_row, void* d_canvas,
+                                         int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    return mb_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, d_canvas, canvas_h, canvas_w, 0, 0,
+                           d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
+}
+
+template <bool PROJ>
+static int mb_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
+                   int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
+                   int origin_x, int origin_y, rwh::SeqRays rays) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
     MbPlan p;
-    const int st = mb_prepare(images, hw, inv_g, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p);
+    const int st = mb_prepare(images, hw, mats, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ);
     if (st != RWH_OK) return st;
+    if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
     char* base = static_cast<char*>(malloc((size_t)p.bytes));
     if (!base) return RWH_E_LAUNCH;
     memcpy(base + p.desc_at, descs, (size_t)n * sizeof(SeqDesc));
     memcpy(base + p.win_at, p.win, (size_t)n * (p.K + 1) * sizeof(MbWin));
     mb_bind(m, p, base);
-    if (gains) mb_host_run<true>(m, p, gains); else mb_host_run<false>(m, p, nullptr);
+    if (gains) mb_host_run<true, PROJ>(m, p, gains, rays); else mb_host_run<false, PROJ>(m, p, nullptr, rays);
     free(base);
     return RWH_OK;
+}
+
+extern "C" int rwh_host_stitch_multiband(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                         int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
+                                         int origin_x, int origin_y) {
+    return mb_host<false>(images, hw, inv_g, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y,
+                          rwh::SeqRays{nullptr, nullptr});
+}
+
+extern "C" int rwh_host_stitch_multiband_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                              int bands, const double* gains, const double* col, const double* row, void* canvas,
+                                              int canvas_h, int canvas_w) {
+    return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
+                         rwh::SeqRays{col, row});
 }

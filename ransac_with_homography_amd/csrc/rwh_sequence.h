@@ -30,20 +30,53 @@ struct SeqArgs {
     unsigned char order[RWH_SEQ_MAX_IMAGES];   // paste: priority order; feather: 0 .. n-1
 };
 
-// The arguments of one launch: A, and with GAIN the N gains of the gain rule behind it (512 B: the arguments stay under 4 KB).
-template <class A, bool GAIN> struct SeqWith { A a; };
-template <class A> struct SeqWith<A, true> { A a; double gains[RWH_SEQ_MAX_IMAGES]; };
-template <class A, bool GAIN> __host__ __device__ __forceinline__ const double* seq_gains(const SeqWith<A, GAIN>& l) {
+// The ray tables of the projection rule (include/rwh.h): col[cx] = (sin, cos) of the canvas column's angle, fw pairs; row[cy] = the
+// canvas row's pair, fh pairs; float64, 16-byte aligned on the device.  Both null in the planar forms.
+struct SeqRays { const double* col; const double* row; };
+
+// The arguments of one launch: A, with GAIN the N gains of the gain rule behind it (512 B: the arguments stay under 4 KB), and with
+// PROJ the ray tables of the projection rule last.  The forms without PROJ are laid out as they were before there was one.
+template <class A, bool GAIN, bool PROJ = false> struct SeqWith { A a; };
+template <class A> struct SeqWith<A, true, false> { A a; double gains[RWH_SEQ_MAX_IMAGES]; };
+template <class A> struct SeqWith<A, false, true> { A a; SeqRays rays; };
+template <class A> struct SeqWith<A, true, true> { A a; double gains[RWH_SEQ_MAX_IMAGES]; SeqRays rays; };
+template <class A, bool GAIN, bool PROJ> __host__ __device__ __forceinline__ const double* seq_gains(const SeqWith<A, GAIN, PROJ>& l) {
     if constexpr (GAIN) return l.gains; else return nullptr;
 }
-template <bool GAIN, class A> static SeqWith<A, GAIN> seq_with(const A& a, const double* gains, int n) {
-    SeqWith<A, GAIN> l;
+template <class A, bool GAIN, bool PROJ> __host__ __device__ __forceinline__ SeqRays seq_rays(const SeqWith<A, GAIN, PROJ>& l) {
+    if constexpr (PROJ) return l.rays; else return SeqRays{nullptr, nullptr};
+}
+template <bool GAIN, bool PROJ = false, class A> static SeqWith<A, GAIN, PROJ> seq_with(const A& a, const double* gains, int n,
+                                                                                        SeqRays rays = SeqRays{nullptr, nullptr}) {
+    SeqWith<A, GAIN, PROJ> l;
     l.a = a;
     if constexpr (GAIN) {
         memset(l.gains, 0, sizeof(l.gains));
         memcpy(l.gains, gains, (size_t)n * sizeof(double));
     }
+    if constexpr (PROJ) l.rays = rays;
     return l;
+}
+
+// The ray of canvas pixel (cx, cy) on the curved canvas: three products of table entries, no transcendental function.  Both
+// indices lie inside the canvas (the callers' bounds tests come first).  The column pair is one 16-byte load per lane; cy is
+// wave-uniform in every kernel, so the row pair is a scalar load.
+struct SeqRay { double r0, r1, r2; };
+__host__ __device__ __forceinline__ SeqRay seq_ray(const SeqRays& t, int cx, int cy) {
+#ifdef __HIP_DEVICE_COMPILE__
+    struct __attribute__((aligned(16))) Pair { double s, c; };     // (checked before the launch)
+#else
+    struct Pair { double s, c; };
+#endif
+    const Pair col = reinterpret_cast<const Pair*>(t.col)[cx], row = reinterpret_cast<const Pair*>(t.row)[cy];
+    return SeqRay{col.s * row.c, row.s, col.c * row.c};
+}
+
+// A wave's row (threadIdx.x >> 6 in every kernel of the family), which the compiler cannot see to be wave-uniform: told so in the
+// projected forms, whose row entry of the ray tables then comes by a scalar load.  The planar forms keep the expression, and the
+// code, they had.
+template <bool PROJ> __device__ __forceinline__ int seq_wave_row(int row) {
+    if constexpr (PROJ) return __builtin_amdgcn_readfirstlane(row); else return row;
 }
 
 // One RGB texel as a dword: an unaligned 4-byte load (3 bytes used) unless that would step past the image's last byte.
@@ -57,25 +90,35 @@ __host__ __device__ __forceinline__ double seq_min(double a, double b) { return 
 // Image d at frame point (fx, fy): false where it does not cover the point; else its value v (float64 per channel) and, for the
 // feather blend, its weight g.  The anchor enters unwarped: its own bytes, texel (0,0) included.  GAIN (the gain rule): v is
 // min(v * gain, 255.0), the product rounded on its own; without GAIN `gain` is not read.
-template <bool FEATHER, bool GAIN = false>
+// PROJ (the projection rule): (fx, fy) is the canvas pixel, `ray` its ray and d.ih the image's M; X, Y and W are M's rows on the
+// ray, a ray behind the camera (W <= 0) is not valid, and no image enters unwarped (is_anchor is not read).
+template <bool FEATHER, bool GAIN = false, bool PROJ = false>
 __host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_anchor, int fx, int fy, double v[3], double& g,
-                                                    double gain = 1.0) {
+                                                    double gain = 1.0, const SeqRay* ray = nullptr) {
     const int tx = fx - d.mx, ty = fy - d.my;
     if (!((tx >= 0) & (tx < d.wt) & (ty >= 0) & (ty < d.ht))) return false;
     const size_t bytes = (size_t)d.h * d.w * 3;
     double sx, sy;
-    if (is_anchor) {            // (its rectangle is (0, 0, w, h): checked before the launch)
+    if (!PROJ && is_anchor) {   // (its rectangle is (0, 0, w, h): checked before the launch)
         const uint32_t p = seq_rgb_at(d.src, ((size_t)ty * d.w + tx) * 3, bytes);
 #pragma unroll
         for (int k = 0; k < 3; ++k) v[k] = seq_chan(p, k);
         sx = (double)tx; sy = (double)ty;
     } else {
-        const double x = (double)fx, y = (double)fy;
-        const double X = fma(d.ih[1], y, d.ih[0] * x) + d.ih[2];
-        const double Y = fma(d.ih[4], y, d.ih[3] * x) + d.ih[5];
-        const double W = fma(d.ih[7], y, d.ih[6] * x) + d.ih[8];
+        double X, Y, W;
+        if constexpr (PROJ) {
+            X = fma(d.ih[2], ray->r2, fma(d.ih[1], ray->r1, d.ih[0] * ray->r0));
+            Y = fma(d.ih[5], ray->r2, fma(d.ih[4], ray->r1, d.ih[3] * ray->r0));
+            W = fma(d.ih[8], ray->r2, fma(d.ih[7], ray->r1, d.ih[6] * ray->r0));
+        } else {
+            const double x = (double)fx, y = (double)fy;
+            X = fma(d.ih[1], y, d.ih[0] * x) + d.ih[2];
+            Y = fma(d.ih[4], y, d.ih[3] * x) + d.ih[5];
+            W = fma(d.ih[7], y, d.ih[6] * x) + d.ih[8];
+        }
         sx = X / W; sy = Y / W;
-        const bool valid = (sx >= 0.0) & (sx <= (double)(d.w - 1)) & (sy >= 0.0) & (sy <= (double)(d.h - 1));   // a NaN is not valid
+        bool valid = (sx >= 0.0) & (sx <= (double)(d.w - 1)) & (sy >= 0.0) & (sy <= (double)(d.h - 1));   // a NaN is not valid
+        if constexpr (PROJ) valid &= W > 0.0;
         if (!valid) return false;
         const int ix = (int)sx, iy = (int)sy;
         const double fx_ = sx - (double)ix, fy_ = sy - (double)iy;
@@ -102,10 +145,13 @@ __host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_an
 }
 
 // One canvas pixel as 0x00BBGGRR.  cand: bit k set = image order[k] may cover the pixel (its rectangle meets the pixel's tile).
-// gains: the N gains of the gain rule, read with GAIN only.
-template <bool FEATHER, bool GAIN = false>
-__host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains = nullptr) {
+// gains: the N gains of the gain rule, read with GAIN only.  rays: the ray tables, read with PROJ only (then ox = oy = 0).
+template <bool FEATHER, bool GAIN = false, bool PROJ = false>
+__host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains = nullptr,
+                                                       SeqRays rays = SeqRays{nullptr, nullptr}) {
     const int fx = a.ox + cx, fy = a.oy + cy;
+    SeqRay ray;
+    if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
     double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
     bool covered = false;
     for (uint64_t m = cand; m; m &= m - 1) {
@@ -113,7 +159,7 @@ __host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_
         double v[3], g = 0.0;
         double gain = 1.0;
         if constexpr (GAIN) gain = gains[i];
-        if (!seq_sample<FEATHER, GAIN>(a.desc[i], i == a.anchor, fx, fy, v, g, gain)) continue;
+        if (!seq_sample<FEATHER, GAIN, PROJ>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray)) continue;
         if constexpr (!FEATHER) {       // paste: the first image in `order` that covers the pixel
             uint32_t out = 0u;
 #pragma unroll
@@ -154,12 +200,23 @@ static bool seq_canvas_ok(int h, int w) { return h >= 1 && w >= 1 && h <= 65535 
 // Lays `words` eight-byte words of a host table down at `dev` on the stream (rwh_sequence.hip).
 void seq_put(const void* host, size_t words, uint64_t* dev, hipStream_t s);
 
+// The projected forms have no anchor: every image is warped, every matrix checked, and the frame is the canvas (origin (0, 0)).
+constexpr int SEQ_NO_ANCHOR = -1;
+
+// The ray tables of a projected call: both given, 16-byte aligned where the device loads a pair at once.
+static bool seq_rays_ok(const double* col, const double* row, bool device) {
+    const uintptr_t mask = device ? 15u : 7u;
+    return col && row && !((uintptr_t)col & mask) && !((uintptr_t)row & mask);
+}
+
 // Everything both entry points check, and the descriptors / arguments they share.  descs: room for RWH_SEQ_MAX_IMAGES.
+// proj: a projected call -- inv_g holds the M_i, anchor is SEQ_NO_ANCHOR and the origin (0, 0).
 static int seq_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
                        const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                       int row_begin, int row_end, SeqDesc* descs, SeqArgs& a) {
+                       int row_begin, int row_end, SeqDesc* descs, SeqArgs& a, bool proj = false) {
     if (!images || !hw || !inv_g || !rects || !order || !canvas) return RWH_E_INVALID;
-    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || anchor < 0 || anchor >= n || (blend != RWH_SEQ_PASTE && blend != RWH_SEQ_FEATHER)) return RWH_E_INVALID;
+    if (proj ? (anchor != SEQ_NO_ANCHOR || origin_x || origin_y) : (anchor < 0 || anchor >= n)) return RWH_E_INVALID;
+    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || (blend != RWH_SEQ_PASTE && blend != RWH_SEQ_FEATHER)) return RWH_E_INVALID;
     if (!seq_canvas_ok(canvas_h, canvas_w)) return RWH_E_INVALID;
     if (row_begin < 0 || row_end > canvas_h || row_begin > row_end) return RWH_E_INVALID;
     uint64_t seen = 0;
@@ -193,12 +250,13 @@ static int seq_prepare(const void* const* images, const int32_t* hw, const doubl
 
 // seq_prepare for the rules that take the images in index order over the whole canvas: the identity order, feather, all rows.
 static int seq_prepare_indexed(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
-                               void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, SeqArgs& a) {
+                               void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, SeqArgs& a,
+                               bool proj = false) {
     if (n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;     // (before order[] is filled)
     int32_t order[RWH_SEQ_MAX_IMAGES];
     for (int k = 0; k < n; ++k) order[k] = k;
     return seq_prepare(images, hw, inv_g, rects, n, anchor, order, RWH_SEQ_FEATHER, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                       0, canvas_h, descs, a);
+                       0, canvas_h, descs, a, proj);
 }
 
 // f(feather, gain), the two flags as std::true_type / std::false_type: the four forms of the compositor, device and host.

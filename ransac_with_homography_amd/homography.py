@@ -55,6 +55,7 @@ __all__ = [
     "calcHomography", "calcHomographyLinear", "calcH", "nearestNeighbor", "bilinear", "convertfunc",
     "wrapPerspective", "wrapPerspectiveScan", "perspectiveTransform", "transformImage", "transformImageH",
     "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence", "sequence_gains",
+    "sequence_ray_tables", "sequence_focal",
 ]
 
 
@@ -770,7 +771,141 @@ def _check_count(n, anchor):
         raise ValueError("sequence: anchor %r outside 0 .. %d" % (anchor, n - 1))
 
 
-def sequence_plan(shapes, Hs, anchor=0):
+PROJECTIONS = ("cylindrical", "spherical")
+
+
+def _check_projection(who, projection, focal):
+    """ValueError unless (projection, focal) is (None, None) or a known surface with a finite focal > 0."""
+    if projection is None:
+        if focal is not None:
+            raise ValueError("%s: focal=%r without a projection" % (who, focal))
+        return
+    if not (isinstance(projection, str) and projection in PROJECTIONS):
+        raise ValueError("%s: projection=%r; None, 'cylindrical' or 'spherical'" % (who, projection))
+    if focal is None:
+        raise ValueError("%s: projection=%r takes a focal length in pixels" % (who, projection))
+    if isinstance(focal, (bool, str)) or not isinstance(focal, (int, float, np.integer, np.floating)) or not (np.isfinite(focal) and focal > 0):
+        raise ValueError("%s: focal=%r; finite and > 0" % (who, focal))
+
+
+def _camera(shape, focal):
+    """K of the projection rule: the focal length and the centre of the anchor's image."""
+    return np.array([[float(focal), 0.0, (int(shape[1]) - 1) / 2.0], [0.0, float(focal), (int(shape[0]) - 1) / 2.0], [0.0, 0.0, 1.0]])
+
+
+def _surface(rays, projection, focal):
+    """Surface points (u, s) of rays [3, n] by the projection rule."""
+    theta = np.arctan2(rays[0], rays[2])
+    hyp = np.hypot(rays[0], rays[2])
+    t = rays[1] / hyp if projection == "cylindrical" else np.arctan2(rays[1], hyp)
+    return focal * theta, focal * t
+
+
+def _perimeter(h, w):
+    """The perimeter pixels of an h x w image in order, [3, n] homogeneous; the loop closes from the last to the first."""
+    xs, ys = np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64)
+    x = np.concatenate([xs[:-1], np.full(h - 1, w - 1.0), xs[:0:-1], np.zeros(h - 1)])
+    y = np.concatenate([np.zeros(w - 1), ys[:-1], np.full(w - 1, h - 1.0), ys[:0:-1]])
+    return np.stack([x, y, np.ones_like(x)])
+
+
+def _oriented(Gs):
+    """G_i * sign(det G_i) of the projection rule; ValueError for a zero or non-finite determinant."""
+    out = []
+    for i, G in enumerate(Gs):
+        G = np.asarray(G, dtype=np.float64)
+        with np.errstate(all="ignore"):
+            det = np.linalg.det(G) if np.isfinite(G).all() else np.nan
+        if not np.isfinite(det) or det == 0.0:
+            raise ValueError("sequence: image %d has a homography whose determinant is zero or not finite" % i)
+        out.append(G if det > 0 else -G)
+    return np.stack(out)
+
+
+def _projected_canvas(shapes, Gs, anchor, projection, focal):
+    """Rectangles (in surface pixels), canvas and default order of the projection rule (include/rwh.h) for oriented G_i: ->
+    (rects, (ox, oy), (fh, fw), order), or the rule's ValueError."""
+    n = len(shapes)
+    kinv = np.linalg.inv(_camera(shapes[anchor], focal))
+    rects = []
+    for i, (shape, G) in enumerate(zip(shapes, Gs)):
+        h, w = int(shape[0]), int(shape[1])
+        if h < 2 or w < 2:
+            raise ValueError("sequence: image %d is %d x %d; sides of 2 at least" % (i, h, w))
+        with np.errstate(all="ignore"):
+            rays = kinv @ (G @ _perimeter(h, w))
+            u, v = _surface(rays, projection, float(focal))
+            theta = u / float(focal)
+        if not (np.isfinite(u).all() and np.isfinite(v).all() and max(np.abs(u).max(), np.abs(v).max()) < 2.0 ** 30):
+            raise ValueError("sequence: image %d has a perimeter point on the %s surface that is not finite" % (i, projection))
+        step = np.diff(np.append(theta, theta[0]))
+        wrapped = (step + np.pi) % (2.0 * np.pi) - np.pi
+        if int(np.rint(wrapped.sum() / (2.0 * np.pi))) != 0:
+            raise ValueError("sequence: image %d contains a pole of the %s surface" % (i, projection))
+        if (np.abs(step) >= np.pi).any():
+            raise ValueError("sequence: image %d straddles the seam behind the anchor (360-degree wrap-around is not taken)" % i)
+        mx, my = int(np.floor(u.min())) - 1, int(np.floor(v.min())) - 1
+        rects.append((mx, my, int(np.ceil(u.max())) + 1 - mx + 1, int(np.ceil(v.max())) + 1 - my + 1))
+    ox, oy = min(r[0] for r in rects), min(r[1] for r in rects)
+    fw, fh = max(r[0] + r[2] for r in rects) - ox, max(r[1] + r[3] for r in rects) - oy
+    if fw > 65535 or fh > 65535 or fw * fh * 3 > 2 ** 31 - 1:
+        raise ValueError("sequence: a %d x %d canvas; sides of at most 65535 and at most 2^31 - 1 bytes" % (fh, fw))
+    order = sorted(range(n), key=lambda i: (abs(i - anchor), i))
+    return rects, (ox, oy), (fh, fw), order
+
+
+def sequence_ray_tables(projection, focal, origin, size):
+    """The two ray tables of the projection rule (include/rwh.h) for a canvas of size (fh, fw) whose pixel (0, 0) is surface point
+    origin = (ox, oy): -> (col float64 [fw, 2], row float64 [fh, 2]); col[cx] = (sin(u / f), cos(u / f)) with u = ox + cx,
+    row[cy] = (s / f, 1.0) on the cylinder and (sin(s / f), cos(s / f)) on the sphere with s = oy + cy.  Pure numpy: the compositor,
+    its host twin and a restatement all read these numbers, none of them calls a transcendental function."""
+    _check_projection("sequence_ray_tables", projection, focal)
+    if projection is None:
+        raise ValueError("sequence_ray_tables: projection=None has no tables")
+    f = float(focal)
+    u = (int(origin[0]) + np.arange(int(size[1]), dtype=np.float64)) / f
+    t = (int(origin[1]) + np.arange(int(size[0]), dtype=np.float64)) / f
+    col = np.stack([np.sin(u), np.cos(u)], axis=1)
+    row = np.stack([t, np.ones_like(t)], axis=1) if projection == "cylindrical" else np.stack([np.sin(t), np.cos(t)], axis=1)
+    return np.ascontiguousarray(col), np.ascontiguousarray(row)
+
+
+def sequence_focal(shapes, Hs):
+    """A focal length in pixels from the pairwise homographies of a rotating camera, for `projection=`; pure numpy.
+
+    shapes: N image shapes; Hs: N - 1 matrices as `sequence_plan`'s.  With the principal points moved to the image centres,
+    Hc = inv(C_i) @ H @ C_{i+1} (entries h0 .. h8) is K_i R inv(K_{i+1}) up to scale, and the orthonormality of R's rows and
+    columns (Szeliski & Shum 1997; what OpenCV's stitcher uses) gives f0^2 as one of -h2 h5 / (h0 h3 + h1 h4) and
+    (h5^2 - h2^2) / (h0^2 + h1^2 - h3^2 - h4^2), f1^2 as one of -(h0 h1 + h3 h4) / (h6 h7) and
+    (h0^2 + h3^2 - h1^2 - h4^2) / (h7^2 - h6^2), in each case the candidate whose denominator is larger in magnitude.  A pair
+    counts when both are finite and > 0 and gives sqrt(f0 f1) (the root of the product of the two focal lengths); the result is
+    the median over the pairs.  ValueError: a wrong number of Hs, no pair that counts."""
+    n = len(shapes)
+    Hs = [np.asarray(H, dtype=np.float64) for H in Hs]
+    if n < 1 or len(Hs) != n - 1 or any(H.shape != (3, 3) for H in Hs):
+        raise ValueError("sequence_focal: %d images take %d 3 x 3 homographies, got %d" % (n, n - 1, len(Hs)))
+
+    def centre(shape, sign):
+        return np.array([[1.0, 0.0, sign * (int(shape[1]) - 1) / 2.0], [0.0, 1.0, sign * (int(shape[0]) - 1) / 2.0], [0.0, 0.0, 1.0]])
+
+    def pick(cands):
+        num, den = max(cands, key=lambda c: abs(c[1]))
+        return num / den
+
+    found = []
+    for i, H in enumerate(Hs):
+        with np.errstate(all="ignore"):
+            h = (centre(shapes[i], -1.0) @ H @ centre(shapes[i + 1], 1.0)).reshape(9)
+            f0 = pick([(-h[2] * h[5], h[0] * h[3] + h[1] * h[4]), (h[5] ** 2 - h[2] ** 2, h[0] ** 2 + h[1] ** 2 - h[3] ** 2 - h[4] ** 2)])
+            f1 = pick([(-(h[0] * h[1] + h[3] * h[4]), h[6] * h[7]), (h[0] ** 2 + h[3] ** 2 - h[1] ** 2 - h[4] ** 2, h[7] ** 2 - h[6] ** 2)])
+        if np.isfinite(f0) and np.isfinite(f1) and f0 > 0 and f1 > 0:
+            found.append(float(np.sqrt(np.sqrt(f0) * np.sqrt(f1))))
+    if not found:
+        raise ValueError("sequence_focal: no pair of images gives a focal length (%d pairs)" % len(Hs))
+    return float(np.median(found))
+
+
+def sequence_plan(shapes, Hs, anchor=0, projection=None, focal=None):
     """The geometry of a sequence panorama from its pairwise homographies; pure numpy, no GPU.
 
     shapes: N image shapes (h, w[, c]); Hs: N - 1 matrices, Hs[i] maps image i+1 into image i -- what
@@ -778,9 +913,16 @@ def sequence_plan(shapes, Hs, anchor=0):
     image i into the anchor's frame, G_a the identity exactly.  Returns (Gs float64 [N, 3, 3], rects [(mx, my, wt, ht)] in the
     anchor's frame, (ox, oy), (fh, fw), order): the rectangles, the canvas and the default paste order (the anchor first, then
     increasing |i - anchor|, the lower index on ties) of the sequence rule (include/rwh.h).  ValueError: N outside 1 .. 64, a wrong
-    number of Hs, a non-finite G_i or corner, an empty rectangle, a canvas side above 65535 or a canvas above 2^31 - 1 bytes."""
+    number of Hs, a non-finite G_i or corner, an empty rectangle, a canvas side above 65535 or a canvas above 2^31 - 1 bytes.
+
+    projection: None -- the anchor's image plane, as above; "cylindrical" or "spherical" -- the canvas is that surface about the
+    anchor's camera, with `focal` (pixels, finite and > 0) its radius (the projection rule of include/rwh.h).  The 5-tuple is the
+    same, with Gs each multiplied by the sign of its determinant and rectangles and origin in SURFACE pixels.  ValueError in
+    addition: an unknown projection, one without the other of projection and focal, a determinant that is zero or not finite, a
+    perimeter point that is not finite, an image that straddles the seam behind the anchor or contains a pole."""
     n = len(shapes)
     _check_count(n, anchor)
+    _check_projection("sequence_plan", projection, focal)
     Hs = [np.asarray(H, dtype=np.float64) for H in Hs]
     if len(Hs) != n - 1 or any(H.shape != (3, 3) for H in Hs):
         raise ValueError("sequence: %d images take %d 3 x 3 homographies, got %d" % (n, n - 1, len(Hs)))
@@ -793,15 +935,21 @@ def sequence_plan(shapes, Hs, anchor=0):
         inv_a = np.linalg.inv(C[anchor])
         Gs = np.stack([inv_a @ c for c in C])
     Gs[anchor] = np.eye(3)
+    if projection is not None:
+        Gs = _oriented(Gs)
+        rects, origin, size, order = _projected_canvas(shapes, Gs, anchor, projection, focal)
+        return Gs, rects, origin, size, order
     rects, origin, size, order = _sequence_canvas(shapes, Gs, anchor)
     return Gs, rects, origin, size, order
 
 
-def _sequence_inputs(who, images, Hs, Gs, anchor):
+def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None):
     """What stitchSequence and sequence_gains check of their images and geometry, before any GPU use: -> (rects, origin, size,
-    default order, inv_g float64 [N, 3, 3])."""
+    default order, inv_g float64 [N, 3, 3], rays).  rays is None on the anchor's plane.  With a projection it is the two ray tables
+    (numpy), the rectangles are in canvas coordinates and the matrices are the M_i = inv(G_i) @ K of the projection rule."""
     n = len(images)
     _check_count(n, anchor)
+    _check_projection(who, projection, focal)
     if (Hs is None) == (Gs is None):
         raise ValueError("%s: exactly one of Hs and Gs" % who)
     for i, img in enumerate(images):
@@ -809,14 +957,26 @@ def _sequence_inputs(who, images, Hs, Gs, anchor):
             raise NotImplementedError("%s: image %d is %s %s; uint8 [h, w, 3] images are taken" % (who, i, img.dtype, tuple(img.shape)))
     shapes = [tuple(int(v) for v in img.shape) for img in images]
     if Hs is not None:
-        Gs, rects, origin, size, default = sequence_plan(shapes, Hs, anchor)
+        Gs, rects, origin, size, default = sequence_plan(shapes, Hs, anchor, projection, focal)
     else:
         Gs = np.array([np.asarray(G, dtype=np.float64) for G in Gs])
         if Gs.shape != (n, 3, 3) or not np.array_equal(Gs[anchor], np.eye(3)):
             raise ValueError("%s: Gs takes %d 3 x 3 matrices with the identity at the anchor" % (who, n))
-        rects, origin, size, default = _sequence_canvas(shapes, Gs, anchor)
+        if projection is not None:
+            Gs = _oriented(Gs)
+            rects, origin, size, default = _projected_canvas(shapes, Gs, anchor, projection, focal)
+        else:
+            rects, origin, size, default = _sequence_canvas(shapes, Gs, anchor)
+    if projection is not None:
+        K = _camera(shapes[anchor], focal)
+        with np.errstate(all="ignore"):
+            m = np.stack([K if i == anchor else np.linalg.inv(Gs[i]) @ K for i in range(n)])
+        if not np.isfinite(m).all():
+            raise ValueError("%s: an inverse homography is not finite" % who)
+        rects = [(r[0] - origin[0], r[1] - origin[1], r[2], r[3]) for r in rects]
+        return rects, origin, size, default, m, sequence_ray_tables(projection, focal, origin, size)
     inv_g = np.stack([np.eye(3) if i == anchor else np.linalg.inv(Gs[i]) for i in range(n)])
-    return rects, origin, size, default, inv_g
+    return rects, origin, size, default, inv_g, None
 
 
 def _sequence_upload(images):
@@ -832,10 +992,20 @@ def _check_gain_options(who, stride, sigma_n, sigma_g):
             raise ValueError("%s: %s = %r; finite and > 0" % (who, name, v))
 
 
-def _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info):
-    """One statistics launch, one download of the two n x n tables, one call of rwh_host_sequence_gains -> float64 [N]."""
+def _rays_upload(rays, dev):
+    """The ray tables of a projected call on the device (None stays None)."""
+    return None if rays is None else tuple(_xfer.to_device(t, dev) for t in rays)
+
+
+def _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info, rays=None):
+    """One statistics launch, one download of the two n x n tables, one call of rwh_host_sequence_gains -> float64 [N].
+    rays: the device ray tables of a projected call (inv_g then holds the M_i and the rectangles are the canvas's)."""
     n = len(on_dev)
-    tabs = kernels.sequence_overlap_tables(on_dev, inv_g, rects, anchor, origin, size, int(stride)).cpu().numpy().view(np.uint64)
+    if rays is None:
+        tabs = kernels.sequence_overlap_tables(on_dev, inv_g, rects, anchor, origin, size, int(stride))
+    else:
+        tabs = kernels.sequence_overlap_tables_proj(on_dev, inv_g, rects, rays[0], rays[1], size, int(stride))
+    tabs = tabs.cpu().numpy().view(np.uint64)
     gains = np.empty(n, dtype=np.float64)
     status = _lib.load().rwh_host_sequence_gains(tabs[0].ctypes.data, tabs[1].ctypes.data, n, float(sigma_n), float(sigma_g), gains.ctypes.data)
     if status == _lib.RWH_E_INVALID:
@@ -846,7 +1016,7 @@ def _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n
     return gains
 
 
-def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, sigma_g=0.1, info=None):
+def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, sigma_g=0.1, info=None, projection=None, focal=None):
     """One exposure gain per image of a sequence (the gain rule of include/rwh.h; Brown & Lowe 2007, section 6): the overlap
     statistics of the images, warped as `stitchSequence` warps them, are reduced on the GPU in one pass over every stride-th canvas
     pixel each way (`rwh_sequence_overlap_stats`), the two N x N integer tables come down in one copy, and the N x N system is
@@ -855,17 +1025,20 @@ def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, s
     images, Hs, Gs, anchor: as `stitchSequence`'s, and refused as there.  sigma_n (10.0): the standard deviation of the intensity
     error, on the 0 .. 255 scale; sigma_g (0.1): that of the gain about 1.  stride=4 is a convention -- a sixteenth of the samples
     moves the gains of the test scenes in the third decimal -- not a measured optimum.  `info`: optional dict, receives "count" and
-    "sum" (uint64 [N, N]).  ValueError: a stride outside 1 .. 255, a sigma that is not finite and > 0, before the GPU is touched."""
-    rects, origin, size, _, inv_g = _sequence_inputs("sequence_gains", images, Hs, Gs, anchor)
+    "sum" (uint64 [N, N]).  projection, focal: as `stitchSequence`'s -- the statistics are taken on that canvas.  ValueError: a
+    stride outside 1 .. 255, a sigma that is not finite and > 0, before the GPU is touched."""
+    rects, origin, size, _, inv_g, rays = _sequence_inputs("sequence_gains", images, Hs, Gs, anchor, projection, focal)
     _check_gain_options("sequence_gains", stride, sigma_n, sigma_g)
-    return _gains_on_device(_sequence_upload(images), inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info)
+    on_dev = _sequence_upload(images)
+    return _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info, _rays_upload(rays, on_dev[0].device))
 
 
 def _check_bands(who, bands):
     kernels.sequence_bands_check(who, bands)
 
 
-def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None, gains=None, info=None, bands=5):
+def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None, gains=None, info=None, projection=None, focal=None,
+                   bands=5):
     """N images into one panorama in ONE pass over the canvas (`rwh_stitch_sequence`): every image is warped once into the
     anchor's frame and every canvas pixel written once.  The reference has no counterpart -- its stitchPanorama takes two images,
     and folding it over a list resamples the growing canvas once per image; this is held to the sequence rule stated in
@@ -885,6 +1058,10 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     "auto" -- `sequence_gains` with its defaults on the same images and geometry, the images uploaded once.  `info`: optional dict,
     receives "gains" (the gains used, float64 [N], or None).  numpy arrays in -> a
     numpy canvas; any tensor in -> a device tensor and no host copy of pixels.  The caller's images are never written.
+    projection: None -- the canvas is the anchor's image plane, which suits a narrow sweep (at 100 degrees off the anchor the plane
+    is behind the camera); "cylindrical" or "spherical" -- the canvas is that surface about the anchor's camera with radius `focal`
+    (pixels; `sequence_focal` estimates one from Hs), held to the projection rule of include/rwh.h: every image is warped, the
+    anchor included, and all blends, gains and bands work on it as on the plane.  A sweep that closes the circle is refused.
     ValueError: what `sequence_plan` refuses, an `order` that is not a permutation, another `blending`, gains of another length,
     not finite or <= 0, or another string; NotImplementedError: images that are not uint8 [h, w, 3]."""
     n = len(images)
@@ -894,7 +1071,7 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     if blending == "multiband":
         _check_bands("stitchSequence", bands)
     blend = _lib.RWH_SEQ_FEATHER if blending == "feather" else _lib.RWH_SEQ_PASTE
-    rects, origin, size, default, inv_g = _sequence_inputs("stitchSequence", images, Hs, Gs, anchor)
+    rects, origin, size, default, inv_g, rays = _sequence_inputs("stitchSequence", images, Hs, Gs, anchor, projection, focal)
     order = default if order is None else [int(v) for v in order]
     if sorted(order) != list(range(n)):
         raise ValueError("stitchSequence: order %r is not a permutation of 0 .. %d" % (order, n - 1))
@@ -905,11 +1082,17 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
         gains = kernels.sequence_gains_array(gains, n, "stitchSequence")
     tens = any(_is_tensor(img) for img in images)
     on_dev = _sequence_upload(images)
+    rays = _rays_upload(rays, on_dev[0].device)
     if isinstance(gains, str):
-        gains = _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, 4, 10.0, 0.1, None)
+        gains = _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, 4, 10.0, 0.1, None, rays)
     if info is not None:
         info["gains"] = gains
-    if blending == "multiband":
+    if rays is not None:
+        if blending == "multiband":
+            out = kernels.stitch_sequence_multiband_proj(on_dev, inv_g, rects, rays[0], rays[1], size, int(bands), gains=gains)
+        else:
+            out = kernels.stitch_sequence_proj(on_dev, inv_g, rects, rays[0], rays[1], order, blend, size, gains=gains)
+    elif blending == "multiband":
         out = kernels.stitch_sequence_multiband(on_dev, inv_g, rects, anchor, origin, size, int(bands), gains=gains)
     else:
         out = kernels.stitch_sequence(on_dev, inv_g, rects, anchor, order, blend, origin, size, gains=gains)

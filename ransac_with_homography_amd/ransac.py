@@ -52,8 +52,8 @@ import numpy as np
 from . import _lapack, _lib, kernels
 from .features import (DeviceProblems, _host_rows, default_pattern, detect_and_describe, extract_batch, match_batch,  # noqa: F401
                        match_descriptors, orb_bin_table, orb_layout, orb_level_quotas, orb_scales, rotate_pattern)
-from .homography import (_check_bands, _pair_rows, calcHomography, calcHomographyLinear, cylindericlMap,  # noqa: F401
-                         sequence_gains, sequence_plan, stitchPanorama, stitchSequence)
+from .homography import (_check_bands, _check_projection, _pair_rows, calcHomography, calcHomographyLinear, cylindericlMap,  # noqa: F401
+                         sequence_focal, sequence_gains, sequence_plan, stitchPanorama, stitchSequence)
 
 # Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
 # in csrc/rwh_settle.h.  RESCORE_MARGIN caps the margin of the 'backward' / 'reproj' rule: an unflagged K1 count moves by <= 2
@@ -766,7 +766,8 @@ def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blen
     return stitchPanorama(queryImg, trainImg, H=H, blending=blending, blendrate=blendrate)
 
 
-def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, blending=False, features=None, info=None, gains=None, bands=5):
+def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, blending=False, features=None, info=None, gains=None,
+                    projection=None, focal=None, bands=5):
     """Pixels -> panorama for a SEQUENCE of N overlapping images (images[i+1] overlaps images[i]), every stage batched: one
     `extract_batch` over the N images, one `match_batch` over the N - 1 adjacent pairs, one `run_batch(refit="device")`, one download
     of the [N - 1, 3, 3] homographies -- the only geometry that visits the host, because the canvas must be allocated -- and one
@@ -779,7 +780,9 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     gains from the overlaps, `sequence_gains` with its defaults).  numpy arrays in -> a numpy canvas, tensors in -> a device
     tensor.  `info`: optional dict, receives "Hs" (float64 [N - 1, 3, 3], Hs[i] maps image i+1 into image i), "Gs", "origin"
     ((ox, oy) of the canvas in the anchor's frame), "sizes" (matches per pair), "inliers" (per pair) and "gains" (the gains used,
-    float64 [N], or None).  ValueError: a pair without a homography (too few matches or inliers, a singular refit), naming the pair and its
+    float64 [N], or None).  projection, focal: as `stitchSequence`'s (a cylindrical or spherical canvas, for sweeps too wide for the
+    anchor's plane; "origin" is then in surface pixels); focal="auto" calls `sequence_focal` on the estimated homographies, and
+    `info` receives "focal" (the focal used, or None).  ValueError: a pair without a homography (too few matches or inliers, a singular refit), naming the pair and its
     match count; whatever `stitchSequence` refuses."""
     n = len(images)
     if not 1 <= n <= _lib.RWH_SEQ_MAX_IMAGES:
@@ -791,6 +794,8 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
         gains = kernels.sequence_gains_array(gains, n, "stitch_sequence")
     if blending == "multiband":
         _check_bands("stitch_sequence", bands)
+    auto_focal = isinstance(focal, str) and focal == "auto" and projection is not None
+    _check_projection("stitch_sequence", projection, 1.0 if auto_focal else focal)
     Hs, sizes, inliers = np.zeros((0, 3, 3)), [], []
     if n > 1:
         feats = extract_batch(images, **(features or {}))
@@ -805,11 +810,15 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
                                  % (p, p, p + 1, sizes[p], inliers[p]))
         Hs = np.stack([r[0] for r in res])
     shapes = [tuple(int(v) for v in img.shape) for img in images]
-    Gs, _, origin, _, _ = sequence_plan(shapes, Hs, anchor)
+    if auto_focal:
+        focal = sequence_focal(shapes, Hs)
+    Gs, _, origin, _, _ = sequence_plan(shapes, Hs, anchor, projection, focal)
     if info is not None:
         info["Hs"], info["Gs"], info["origin"], info["sizes"], info["inliers"] = Hs, Gs, origin, sizes, inliers
+        info["focal"] = focal
     used = {}
-    out = stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands)
+    out = stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands, projection=projection,
+                         focal=focal)
     if info is not None:
         info["gains"] = used["gains"]
     return out
