@@ -939,6 +939,74 @@ RWH_API int rwh_host_stitch_multiband_proj(const void* const* images, const int3
                                            int bands, const double* gains, const double* col, const double* row, void* canvas,
                                            int canvas_h, int canvas_w);
 
+/*
+ * Registration of a sequence over a pair graph: the maps G_i of the sequence rule refined jointly over the inliers of every verified
+ * pair (bundle adjustment, Brown & Lowe 2007, section 4; Triggs et al. 1999), instead of chained from N - 1 adjacent pairs.  The
+ * reference has no counterpart; this is held to THE BUNDLE RULE below.  The per-edge normal-equation blocks are summed on the
+ * device, the small dense system is solved on the host, as for the gain rule.
+ *
+ * The bundle rule.
+ *   Geometry.  G_i: float64 3 x 3, maps image i into the anchor's frame, as in the sequence rule; G_anchor is the identity exactly
+ *     and is never updated.  1 <= N <= RWH_SEQ_MAX_IMAGES.  An edge e = (s, d), s != d, has M_e >= 0 correspondences, a in image s
+ *     and b in image d, float32 rows (x, y); 1 <= E <= RWH_BUNDLE_MAX_EDGES (2016 = 64 * 63 / 2).  Its transfer is
+ *     T_e = inv(G_d) G_s, made on the HOST in float64 (numpy.linalg.inv, then the product) and divided by its largest |entry|.  The
+ *     library takes T_e as input and inverts nothing.
+ *   Parameterisation.  The update is local, on the image side: G_i <- G_i (I + D(delta_i)), D(delta) the 3 x 3 matrix with
+ *     delta_0 .. delta_7 in row-major order and D[2][2] = 0.  G[2][2] is not fixed to 1, so the system stays well conditioned where
+ *     G[2][2] passes through zero (a sweep of 90 degrees on a cylinder or a sphere).  To first order T_e becomes
+ *     (I - D(delta_d)) T_e (I + D(delta_s)).
+ *   Per correspondence, all in float64, nothing contracted except the two fma written out:
+ *     x, y, bx, by: the float32 inputs converted.  a~ = (x, y, 1).
+ *     p_i = fma(T[i][1], y, T[i][0] * x) + T[i][2], i = 0, 1, 2  (rounded multiply, fma, then the fma with w = 1, which is an
+ *       addition: the k-order of rwh_project_points_ex).
+ *     q0 = p0 / p2, q1 = p1 / p2.  r0 = q0 - bx, r1 = q1 - by.
+ *     Valid iff p2 is finite and > 0 and q0 and q1 are finite.  An inlier that is not valid contributes nothing and sets its
+ *       edge's status to RWH_BUNDLE_BEHIND.
+ *     J is 2 x 16: columns 0 .. 7 for delta_s, 8 .. 15 for delta_d.  For k = 3 rho + c, k < 8:
+ *       delta_s: dp = a~[c] * T[:, rho], three rounded products (for c = 2 the entries of T themselves);
+ *       delta_d: dp = -p[c] e_rho (one non-zero component, an exact negation);
+ *       J[0][.] = (dp0 - q0 * dp2) / p2, J[1][.] = (dp1 - q1 * dp2) / p2: the product, the difference and the quotient each
+ *       rounded.  With an exactly zero dp2 (or dp0, dp1) the operations on it may be left out: x - q * 0 = x and 0 - q * 0 = +0
+ *       for finite q.
+ *   Per edge.  A block of RWH_BUNDLE_BLOCK = 153 float64 -- the 136 entries of the upper triangle of S = sum J^T J (row-major:
+ *     S[0][0..15], S[1][1..15], ...), the 16 entries of g = sum J^T r, and c = sum r.r -- an int32 count of the rows summed and an
+ *     int32 status, RWH_BUNDLE_OK or RWH_BUNDLE_BEHIND.  The sums run over the rows whose bit is set in the edge's mask row (the
+ *     layout of rwh_refit_batched: bit i of word i / 64 = correspondence d_offsets[e] + i; never read past mask_words, rows beyond
+ *     it are no inliers) and that are valid.  An edge without such rows gives an all-zero block, count 0, status OK.
+ *   Summation order, part of the rule.  Four partial sums P0 .. P3 per entry, Pw over the rows with index = w (mod 4) in
+ *     increasing index (the index inside the edge, counting every row, masked or not), each from +0.0; one step is
+ *     acc = acc + (u0 * v0 + u1 * v1), both products rounded, then their sum, then the addition: (u, v) = (J[.][a], J[.][b]) for
+ *     S[a][b], (J[.][k], r) for g[k], (r, r) for c.  The entry is (P0 + P1) + (P2 + P3).  Rows that contribute nothing are skipped.
+ *     No atomics: a rerun gives the same bits, and device, host twin and a numpy restatement agree exactly.
+ *   The step (host).  A (8N x 8N) and g (8N) are built from zero by adding the blocks in edge order, columns 0 .. 7 of a block at
+ *     parameters 8 s .. 8 s + 7 and 8 .. 15 at 8 d .. 8 d + 7; the anchor's eight rows and columns are dropped; lambda * A_ii is
+ *     added to every diagonal entry (Marquardt scaling); A delta = -g is solved by Cholesky, A = L L^T.  A pivot that is not a
+ *     positive finite number (an image that no edge touches) or a non-finite delta gives RWH_BUNDLE_SINGULAR and delta = 0.
+ *     The anchor's delta is 0.
+ *
+ * rwh_bundle_blocks: one launch for all edges, one workgroup of 256 lanes per edge.  d_pts_a, d_pts_b (total x 2 float32), d_offsets
+ * (E + 1 int32), d_masks (E x mask_words uint64) as rwh_refit_batched's; d_transfers: E x 9 float64; d_blocks: E x 153 float64;
+ * d_count, d_status: E int32 -- all written whole.  The rows of an edge are staged 128 at a time in LDS (34 values each, a lane
+ * per row); then each of the four waves owns one partial and each of its lanes up to three of the 153 accumulators, walking the
+ * staged rows in the stated order.  RWH_E_INVALID, before anything is launched: a NULL pointer, n_edges outside
+ * 1 .. RWH_BUNDLE_MAX_EDGES, mask_words <= 0.
+ * rwh_host_bundle_blocks: the same operations in the same order on HOST memory; no device, works without a GPU.
+ * rwh_host_bundle_step: the step (host only, plain C++; no LAPACK).  edges: n_edges x (s, d) int32; blocks: n_edges x 153; lambda
+ * finite and >= 0; out_delta: 8 n float64, always written; *out_status: RWH_BUNDLE_OK or RWH_BUNDLE_SINGULAR.  RWH_E_INVALID: a NULL
+ * pointer, n outside 1 .. RWH_SEQ_MAX_IMAGES, anchor outside 0 .. n - 1, n_edges outside 1 .. RWH_BUNDLE_MAX_EDGES, an edge with an
+ * end outside 0 .. n - 1 or with s == d, a lambda that is not finite or < 0.
+ */
+#define RWH_BUNDLE_BLOCK 153
+#define RWH_BUNDLE_MAX_EDGES 2016
+enum { RWH_BUNDLE_OK = 0, RWH_BUNDLE_BEHIND = 1, RWH_BUNDLE_SINGULAR = 2 };
+RWH_API int rwh_bundle_blocks(const float* d_pts_a, const float* d_pts_b, const int32_t* d_offsets, int n_edges, const uint64_t* d_masks,
+                              int mask_words, const double* d_transfers, double* d_blocks, int32_t* d_count, int32_t* d_status,
+                              void* stream);
+RWH_API int rwh_host_bundle_blocks(const float* pts_a, const float* pts_b, const int32_t* offsets, int n_edges, const uint64_t* masks,
+                                   int mask_words, const double* transfers, double* blocks, int32_t* count, int32_t* status);
+RWH_API int rwh_host_bundle_step(int n, int anchor, const int32_t* edges, int n_edges, const double* blocks, double lambda,
+                                 double* out_delta, int32_t* out_status);
+
 #ifdef __cplusplus
 }
 #endif

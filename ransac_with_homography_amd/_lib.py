@@ -35,6 +35,9 @@ RWH_ORB_SCALE_ONE, RWH_ORB_SCALE_MAX, RWH_ORB_LEVELS_MAX, RWH_ORB_PYR_TILE_W, RW
 RWH_SEQ_MAX_IMAGES, RWH_SEQ_PASTE, RWH_SEQ_FEATHER = 64, 0, 1
 RWH_SEQ_MAX_STRIDE = 255
 RWH_SEQ_MAX_BANDS = 8         # the multi-band rule: most bands
+# the bundle rule: float64 values per edge block, most edges (64 * 63 / 2), the statuses of an edge and of a step
+RWH_BUNDLE_BLOCK, RWH_BUNDLE_MAX_EDGES = 153, 2016
+RWH_BUNDLE_OK, RWH_BUNDLE_BEHIND, RWH_BUNDLE_SINGULAR = 0, 1, 2
 RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRAMES = 0, 1, 2, 3
 
 # every symbol include/rwh.h declares (tests check the library exports them all)
@@ -50,7 +53,8 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_host_sequence_gains", "rwh_stitch_sequence_ex", "rwh_host_stitch_sequence_ex",
            "rwh_stitch_multiband_workspace_bytes", "rwh_stitch_multiband", "rwh_host_stitch_multiband",
            "rwh_stitch_sequence_proj", "rwh_host_stitch_sequence_proj", "rwh_sequence_overlap_stats_proj",
-           "rwh_host_sequence_overlap_stats_proj", "rwh_stitch_multiband_proj", "rwh_host_stitch_multiband_proj")
+           "rwh_host_sequence_overlap_stats_proj", "rwh_stitch_multiband_proj", "rwh_host_stitch_multiband_proj",
+           "rwh_bundle_blocks", "rwh_host_bundle_blocks", "rwh_host_bundle_step")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -207,6 +211,13 @@ def _bind(lib):
                                               vp, i32, i32, vp, i64, vp]                # canvas h w workspace bytes stream
     lib.rwh_host_stitch_multiband_proj.restype = i32
     lib.rwh_host_stitch_multiband_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32]
+    # the bundle rule: the edge blocks (device and host twin) and the damped step
+    lib.rwh_bundle_blocks.restype = i32
+    lib.rwh_bundle_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]     # pts_a pts_b offsets n_edges masks words T blocks count status stream
+    lib.rwh_host_bundle_blocks.restype = i32
+    lib.rwh_host_bundle_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    lib.rwh_host_bundle_step.restype = i32
+    lib.rwh_host_bundle_step.argtypes = [i32, i32, vp, i32, vp, f64, vp, vp]            # n anchor edges n_edges blocks lambda delta status
     return lib
 
 

@@ -55,7 +55,7 @@ __all__ = [
     "calcHomography", "calcHomographyLinear", "calcH", "nearestNeighbor", "bilinear", "convertfunc",
     "wrapPerspective", "wrapPerspectiveScan", "perspectiveTransform", "transformImage", "transformImageH",
     "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence", "sequence_gains",
-    "sequence_ray_tables", "sequence_focal",
+    "sequence_ray_tables", "sequence_focal", "sequence_graph", "sequence_adjust",
 ]
 
 
@@ -870,10 +870,11 @@ def sequence_ray_tables(projection, focal, origin, size):
     return np.ascontiguousarray(col), np.ascontiguousarray(row)
 
 
-def sequence_focal(shapes, Hs):
+def sequence_focal(shapes, Hs, pairs=None):
     """A focal length in pixels from the pairwise homographies of a rotating camera, for `projection=`; pure numpy.
 
-    shapes: N image shapes; Hs: N - 1 matrices as `sequence_plan`'s.  With the principal points moved to the image centres,
+    shapes: N image shapes; Hs: N - 1 matrices as `sequence_plan`'s; or, with pairs = [(s, d), ...] (the edges of a pair graph,
+    as `sequence_graph`'s), one matrix per pair, Hs[e] mapping image s into image d -- pairs=None is [(i + 1, i)].  With the principal points moved to the image centres,
     Hc = inv(C_i) @ H @ C_{i+1} (entries h0 .. h8) is K_i R inv(K_{i+1}) up to scale, and the orthonormality of R's rows and
     columns (Szeliski & Shum 1997; what OpenCV's stitcher uses) gives f0^2 as one of -h2 h5 / (h0 h3 + h1 h4) and
     (h5^2 - h2^2) / (h0^2 + h1^2 - h3^2 - h4^2), f1^2 as one of -(h0 h1 + h3 h4) / (h6 h7) and
@@ -882,8 +883,14 @@ def sequence_focal(shapes, Hs):
     the median over the pairs.  ValueError: a wrong number of Hs, no pair that counts."""
     n = len(shapes)
     Hs = [np.asarray(H, dtype=np.float64) for H in Hs]
-    if n < 1 or len(Hs) != n - 1 or any(H.shape != (3, 3) for H in Hs):
-        raise ValueError("sequence_focal: %d images take %d 3 x 3 homographies, got %d" % (n, n - 1, len(Hs)))
+    if pairs is None:
+        if n < 1 or len(Hs) != n - 1 or any(H.shape != (3, 3) for H in Hs):
+            raise ValueError("sequence_focal: %d images take %d 3 x 3 homographies, got %d" % (n, n - 1, len(Hs)))
+        pairs = [(i + 1, i) for i in range(n - 1)]
+    else:
+        pairs = _check_pairs("sequence_focal", n, pairs)
+        if len(Hs) != len(pairs) or any(H.shape != (3, 3) for H in Hs):
+            raise ValueError("sequence_focal: %d pairs take %d 3 x 3 homographies, got %d" % (len(pairs), len(pairs), len(Hs)))
 
     def centre(shape, sign):
         return np.array([[1.0, 0.0, sign * (int(shape[1]) - 1) / 2.0], [0.0, 1.0, sign * (int(shape[0]) - 1) / 2.0], [0.0, 0.0, 1.0]])
@@ -893,9 +900,9 @@ def sequence_focal(shapes, Hs):
         return num / den
 
     found = []
-    for i, H in enumerate(Hs):
+    for (src, dst), H in zip(pairs, Hs):
         with np.errstate(all="ignore"):
-            h = (centre(shapes[i], -1.0) @ H @ centre(shapes[i + 1], 1.0)).reshape(9)
+            h = (centre(shapes[dst], -1.0) @ H @ centre(shapes[src], 1.0)).reshape(9)
             f0 = pick([(-h[2] * h[5], h[0] * h[3] + h[1] * h[4]), (h[5] ** 2 - h[2] ** 2, h[0] ** 2 + h[1] ** 2 - h[3] ** 2 - h[4] ** 2)])
             f1 = pick([(-(h[0] * h[1] + h[3] * h[4]), h[6] * h[7]), (h[0] ** 2 + h[3] ** 2 - h[1] ** 2 - h[4] ** 2, h[7] ** 2 - h[6] ** 2)])
         if np.isfinite(f0) and np.isfinite(f1) and f0 > 0 and f1 > 0:
@@ -941,6 +948,216 @@ def sequence_plan(shapes, Hs, anchor=0, projection=None, focal=None):
         return Gs, rects, origin, size, order
     rects, origin, size, order = _sequence_canvas(shapes, Gs, anchor)
     return Gs, rects, origin, size, order
+
+
+# ------------------------------------------------------ registration over a pair graph (the bundle rule) ----
+# Conventions, not measured optima: the acceptance test of Brown & Lowe 2007, eq. 13 (an edge counts when its inliers exceed
+# alpha + beta * matches); Levenberg-Marquardt starting at lambda = 1e-3, a factor of 10 down on an accepted step and up on a
+# rejected one, given up above 1e12, ended by an accepted step that lowers the cost by less than 1e-12 of it.
+GRAPH_ALPHA, GRAPH_BETA = 8.0, 0.3
+ADJUST_LAMBDA0, ADJUST_LAMBDA_MAX, ADJUST_LAMBDA_FACTOR, ADJUST_REL_STOP = 1e-3, 1e12, 10.0, 1e-12
+
+
+def _check_pairs(who, n, pairs):
+    """[(s, d)] as ints, or ValueError: an end outside 0 .. n - 1, s == d, a pair that is not two integers, too many pairs."""
+    out = []
+    try:
+        for pr in pairs:
+            s, d = pr
+            if isinstance(s, (bool, np.bool_)) or isinstance(d, (bool, np.bool_)) or int(s) != s or int(d) != d:
+                raise TypeError
+            out.append((int(s), int(d)))
+    except (TypeError, ValueError):
+        raise ValueError("%s: pairs=%r; a list of (s, d) image indices" % (who, pairs)) from None
+    for s, d in out:
+        if not (0 <= s < n and 0 <= d < n) or s == d:
+            raise ValueError("%s: pair (%d, %d); two different images of 0 .. %d" % (who, s, d, n - 1))
+    if len(out) > _lib.RWH_BUNDLE_MAX_EDGES:
+        raise ValueError("%s: %d pairs; at most %d" % (who, len(out), _lib.RWH_BUNDLE_MAX_EDGES))
+    return out
+
+
+def sequence_graph(n, pairs, Hs, sizes, inliers, anchor=0):
+    """The pair graph of a sequence and its initialisation along a spanning tree; pure numpy, no GPU.
+
+    n: images; pairs: E edges (s, d); Hs[e]: 3 x 3, maps image s into image d (what `run_batch` estimates for the correspondences
+    `match_batch` makes of (features of s, features of d)), or None; sizes[e], inliers[e]: matches and RANSAC inliers of the edge.
+    An edge is ACCEPTED when inliers > 8 + 0.3 * sizes (Brown & Lowe 2007, eq. 13: alpha = 8 and beta = 0.3 are the paper's
+    conventions, not measured here) and its H is finite.  The tree grows from the anchor: of the accepted edges that join an
+    image of the tree to one outside it, the one with the most inliers is taken, on ties the lower (s, d); the new image's map is
+    G_child = G_parent @ H when the child is s, G_parent @ inv(H) when it is d.  G_anchor is the identity exactly.
+
+    Returns (Gs float64 [n, 3, 3], accepted bool [E], tree [(parent, child, e)] in the order taken).  With anchor 0 and
+    pairs = [(i + 1, i)], all accepted, Gs is `sequence_plan`'s bit for bit.  ValueError: n or anchor as `sequence_plan`'s, a bad
+    pair, lists of other lengths, an H of another shape, an image the accepted edges do not connect to the anchor (named)."""
+    _check_count(n, anchor)
+    pairs = _check_pairs("sequence_graph", n, pairs)
+    E = len(pairs)
+    if not (len(Hs) == len(sizes) == len(inliers) == E):
+        raise ValueError("sequence_graph: %d pairs take %d homographies, sizes and inlier counts" % (E, E))
+    mats, accepted = [], np.zeros(E, dtype=bool)
+    for e, H in enumerate(Hs):
+        H = None if H is None else np.asarray(H, dtype=np.float64)
+        if H is not None and H.shape != (3, 3):
+            raise ValueError("sequence_graph: pair %d has a homography of shape %s" % (e, H.shape))
+        mats.append(H)
+        accepted[e] = H is not None and bool(np.isfinite(H).all()) and float(inliers[e]) > GRAPH_ALPHA + GRAPH_BETA * float(sizes[e])
+    Gs = np.zeros((n, 3, 3))
+    Gs[anchor] = np.eye(3)
+    inside, tree = {anchor}, []
+    while len(inside) < n:
+        best = None
+        for e, (s, d) in enumerate(pairs):
+            if accepted[e] and ((s in inside) != (d in inside)):
+                key = (-int(inliers[e]), s, d, e)
+                if best is None or key < best:
+                    best = key
+        if best is None:
+            missing = [i for i in range(n) if i not in inside]
+            raise ValueError("sequence_graph: image %d is not connected to the anchor (%d) by accepted pairs%s"
+                             % (missing[0], anchor, "" if len(missing) == 1 else "; nor are %s" % missing[1:]))
+        e = best[3]
+        s, d = pairs[e]
+        with np.errstate(all="ignore"):
+            if d in inside:
+                parent, child, G = d, s, Gs[d] @ mats[e]
+            else:
+                parent, child, G = s, d, Gs[s] @ np.linalg.inv(mats[e])
+        if not np.isfinite(G).all():
+            raise ValueError("sequence_graph: image %d gets a map that is not finite (pair %d)" % (child, e))
+        Gs[child] = G
+        inside.add(child)
+        tree.append((parent, child, e))
+    return Gs, accepted, tree
+
+
+def _bundle_transfers(Gs, pairs):
+    """T_e = inv(G_d) @ G_s, divided by its largest |entry| (the bundle rule): float64 [E, 3, 3]."""
+    inv = np.linalg.inv(Gs)
+    T = np.stack([inv[d] @ Gs[s] for s, d in pairs])
+    return T / np.abs(T).reshape(len(pairs), 9).max(axis=1)[:, None, None]
+
+
+def _delta_matrix(delta):
+    """I + D(delta): delta_0 .. delta_7 in row-major order, D[2][2] = 0."""
+    return np.eye(3) + np.append(delta, 0.0).reshape(3, 3)
+
+
+def sequence_adjust(Gs, pairs, matches, masks=None, anchor=0, max_iters=20, on="device", info=None):
+    """Bundle adjustment of a sequence over its pair graph (the bundle rule of include/rwh.h): all G_i refined jointly, by
+    Levenberg-Marquardt, over the inlier correspondences of every edge, so that the error of a chain no longer accumulates.
+
+    Gs: N maps into the anchor's frame (`sequence_graph`'s or `sequence_plan`'s; Gs[anchor] the identity); pairs: E edges (s, d);
+    matches: a `DeviceProblems` with one problem per edge (a in image s, b in image d), or a list of (ptsA [M, 2], ptsB [M, 2]);
+    masks: the edges' inlier words, [E, words] (numpy uint64 / int64, or an int64 tensor on the GPU, e.g. `run_batch`'s
+    info["mask_device"]; an all-zero row leaves an edge out), default: every correspondence is an inlier.
+    on="device": the edge blocks come from `kernels.bundle_blocks` -- per evaluation one upload of E x 9 doubles, one launch, one
+    download; on="host": from the host twin, no GPU needed.  Both give the same bits.
+
+    An iteration: the blocks at the current Gs (those of the last accepted candidate), `rwh_host_bundle_step` at the current
+    lambda, the candidate G_i @ (I + D(delta_i)), each divided by its largest |entry| (the anchor stays the identity), the
+    candidate's blocks.  The step is accepted iff the candidate's cost (the sum of the edges' c) is strictly lower, no edge
+    reports RWH_BUNDLE_BEHIND and every determinant is finite with the sign it had; then lambda <- lambda / 10, else lambda <-
+    10 lambda.  Conventions, not measured optima: lambda starts at 1e-3; the loop ends after `max_iters` accepted steps, at
+    lambda > 1e12, or on an accepted step that lowers the cost by less than 1e-12 of it.
+    `info`: optional dict, receives "cost" (the start and every accepted step), "iters" (accepted steps) and "lambda".
+    Returns Gs float64 [N, 3, 3], Gs[anchor] the identity.  ValueError: bad n, anchor, pairs, on or max_iters, matches or masks that
+    do not fit the pairs, Gs that are not finite or invertible, a correspondence that is behind its camera at the start, an image
+    that no edge with inliers touches."""
+    Gs = np.array([np.asarray(G, dtype=np.float64) for G in Gs])
+    n = len(Gs)
+    _check_count(n, anchor)
+    pairs = _check_pairs("sequence_adjust", n, pairs)
+    E = len(pairs)
+    if on not in ("device", "host"):
+        raise ValueError("sequence_adjust: on=%r; 'device' or 'host'" % (on,))
+    if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 0:
+        raise ValueError("sequence_adjust: max_iters=%r; an integer >= 0" % (max_iters,))
+    if Gs.shape != (n, 3, 3) or not np.array_equal(Gs[anchor], np.eye(3)):
+        raise ValueError("sequence_adjust: Gs takes %d 3 x 3 matrices with the identity at the anchor" % n)
+    with np.errstate(all="ignore"):
+        dets = np.linalg.det(Gs) if np.isfinite(Gs).all() else np.full(n, np.nan)
+    if not (np.isfinite(dets) & (dets != 0.0)).all():
+        raise ValueError("sequence_adjust: a map that is not finite or not invertible")
+    if E < 1:
+        raise ValueError("sequence_adjust: no pairs")
+    from .features import DeviceProblems
+    on_dev = isinstance(matches, DeviceProblems)
+    sizes = list(matches.sizes) if on_dev else [int(np.asarray(a).reshape(-1, 2).shape[0]) for a, _ in matches]
+    if len(sizes) != E:
+        raise ValueError("sequence_adjust: %d pairs take %d sets of matches, got %d" % (E, E, len(sizes)))
+    offsets = np.zeros(E + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(sizes)
+    words = max((max(sizes) + 63) // 64, 1)
+    tensor_masks = masks is not None and _is_tensor(masks)
+    if masks is None:
+        masks = np.full((E, words), -1, dtype=np.int64)
+    elif not tensor_masks:
+        masks = np.ascontiguousarray(masks)
+        if masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)) or masks.ndim != 2:
+            raise ValueError("sequence_adjust: masks takes [E, words] uint64 or int64 words")
+        masks = masks.view(np.int64)
+    if tuple(masks.shape)[0] != E or len(masks.shape) != 2 or masks.shape[1] < 1:
+        raise ValueError("sequence_adjust: masks of shape %s for %d pairs" % (tuple(masks.shape), E))
+    if on == "device":
+        import torch
+        dev = _lib.require_gpu()
+        if on_dev:
+            pa, pb = matches.pts_a, matches.pts_b
+        else:
+            pa = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])).to(dev)
+            pb = torch.from_numpy(np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])).to(dev)
+        off_dev = torch.from_numpy(offsets).to(dev)
+        m_dev = (masks if tensor_masks else torch.from_numpy(masks)).to(dev).to(torch.int64).contiguous()
+
+        def evaluate(G):
+            return kernels.bundle_split(kernels.bundle_blocks(pa, pb, off_dev, m_dev, _bundle_transfers(G, pairs)).cpu().numpy())
+    else:
+        if on_dev:
+            pa, pb = matches.pts_a.cpu().numpy(), matches.pts_b.cpu().numpy()
+        else:
+            pa = np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])
+            pb = np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])
+        m_host = masks.cpu().numpy() if tensor_masks else masks
+
+        def evaluate(G):
+            return kernels.host_bundle_blocks(pa, pb, offsets, m_host, _bundle_transfers(G, pairs))
+
+    blocks, _, status = evaluate(Gs)
+    if (status != _lib.RWH_BUNDLE_OK).any():
+        e = int(np.nonzero(status != _lib.RWH_BUNDLE_OK)[0][0])
+        raise ValueError("sequence_adjust: pair %d (images %d and %d) has an inlier behind the camera at the start" % ((e,) + pairs[e]))
+    cost = float(blocks[:, -1].sum())
+    history, lam, iters = [cost], ADJUST_LAMBDA0, 0
+    signs = np.sign(dets)
+    while iters < max_iters and lam <= ADJUST_LAMBDA_MAX:
+        delta, st = kernels.host_bundle_step(n, anchor, pairs, blocks, lam)
+        if st != _lib.RWH_BUNDLE_OK:
+            raise ValueError("sequence_adjust: the step's system is singular (an image that no edge with inliers touches?)")
+        with np.errstate(all="ignore"):
+            cand = np.stack([Gs[i] if i == anchor else Gs[i] @ _delta_matrix(delta[i]) for i in range(n)])
+            scale = np.abs(cand).reshape(n, 9).max(axis=1)
+            scale[anchor] = 1.0
+            cand = cand / scale[:, None, None]
+            cdet = np.linalg.det(cand) if np.isfinite(cand).all() else np.full(n, np.nan)
+        accept = bool((np.isfinite(cdet) & (np.sign(cdet) == signs)).all())
+        if accept:
+            cblocks, _, cstatus = evaluate(cand)
+            ccost = float(cblocks[:, -1].sum())
+            accept = bool((cstatus == _lib.RWH_BUNDLE_OK).all()) and ccost < cost
+        if not accept:
+            lam *= ADJUST_LAMBDA_FACTOR
+            continue
+        small = cost - ccost < ADJUST_REL_STOP * cost
+        Gs, blocks, cost = cand, cblocks, ccost
+        history.append(cost)
+        iters += 1
+        lam /= ADJUST_LAMBDA_FACTOR
+        if small:
+            break
+    if info is not None:
+        info["cost"], info["iters"], info["lambda"] = history, iters, lam
+    return Gs
 
 
 def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None):

@@ -403,6 +403,79 @@ def refit_batched(pts_a, pts_b, offsets, masks):
     return H, status
 
 
+BUNDLE_BLOCK, BUNDLE_MAX_EDGES = _lib.RWH_BUNDLE_BLOCK, _lib.RWH_BUNDLE_MAX_EDGES
+
+
+def _bundle_transfers(transfers, n_edges):
+    t = np.ascontiguousarray(transfers, dtype=np.float64).reshape(-1, 9)
+    if t.shape[0] != n_edges or not 1 <= n_edges <= BUNDLE_MAX_EDGES:
+        raise ValueError("bundle_blocks: %d transfers for %d edges; 1 .. %d edges, a 3 x 3 transfer each" % (t.shape[0], n_edges, BUNDLE_MAX_EDGES))
+    return t
+
+
+def bundle_blocks(pts_a, pts_b, offsets, masks, transfers, out=None):
+    """The normal-equation blocks of every edge of a pair graph in one launch (rwh_bundle_blocks; the bundle rule of include/rwh.h).
+
+    pts_a/pts_b: [total, 2] float32, offsets: [E+1] int32, masks: [E, words] int64 (the layout of `refit_batched`) -- on the GPU;
+    transfers: [E, 3, 3] float64 on the HOST (one upload of E x 9 doubles).  Returns one [E, 155] float64 tensor on the GPU: the
+    153 values of each block, then the edge's count and status as float64 -- so that ONE download brings everything to the host
+    (`bundle_split` takes it apart).  out: optionally the three tensors the library writes -- blocks [E, 153] float64, count [E]
+    and status [E] int32, contiguous, on the GPU -- instead of fresh ones.  Enqueued on torch's current stream."""
+    lib = _lib.load()
+    _dev_check(pts_a, pts_b, offsets, masks)
+    E = offsets.shape[0] - 1
+    assert pts_a.dtype == torch.float32 and pts_b.dtype == torch.float32 and offsets.dtype == torch.int32
+    assert masks.dtype == torch.int64 and masks.dim() == 2 and masks.shape[0] == E and tuple(pts_a.shape) == tuple(pts_b.shape)
+    t_dev = torch.from_numpy(_bundle_transfers(transfers, E)).to(pts_a.device)
+    if out is None:
+        blocks = torch.empty((E, BUNDLE_BLOCK), dtype=torch.float64, device=pts_a.device)
+        count, status = torch.empty((2, E), dtype=torch.int32, device=pts_a.device)
+    else:
+        blocks, count, status = out
+        _dev_check(blocks, count, status)
+        assert blocks.dtype == torch.float64 and tuple(blocks.shape) == (E, BUNDLE_BLOCK)
+        assert count.dtype == torch.int32 and status.dtype == torch.int32 and tuple(count.shape) == (E,) and tuple(status.shape) == (E,)
+    check(lib.rwh_bundle_blocks(_ptr(pts_a), _ptr(pts_b), _ptr(offsets), E, _ptr(masks), masks.shape[1], _ptr(t_dev), _ptr(blocks),
+                                _ptr(count), _ptr(status), _lib.stream_ptr()), "rwh_bundle_blocks")
+    return torch.cat([blocks, count.to(torch.float64)[:, None], status.to(torch.float64)[:, None]], dim=1)
+
+
+def bundle_split(packed):
+    """(blocks float64 [E, 153], count int32 [E], status int32 [E]) of a downloaded `bundle_blocks` result (numpy)."""
+    packed = np.asarray(packed)
+    return (np.ascontiguousarray(packed[:, :BUNDLE_BLOCK]), packed[:, BUNDLE_BLOCK].astype(np.int32),
+            packed[:, BUNDLE_BLOCK + 1].astype(np.int32))
+
+
+def host_bundle_blocks(pts_a, pts_b, offsets, masks, transfers):
+    """The host twin of `bundle_blocks` (rwh_host_bundle_blocks): numpy arrays in, (blocks, count, status) numpy out, the same
+    operations in the same order.  Uses no device and works without a GPU."""
+    lib = _lib.load()
+    pts_a, pts_b = np.ascontiguousarray(pts_a, dtype=np.float32).reshape(-1, 2), np.ascontiguousarray(pts_b, dtype=np.float32).reshape(-1, 2)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    E = offsets.shape[0] - 1
+    masks = np.ascontiguousarray(masks).view(np.uint64).reshape(E, -1)
+    t = _bundle_transfers(transfers, E)
+    if pts_a.shape != pts_b.shape or E < 1 or int(offsets[0]) != 0 or int(offsets[-1]) != pts_a.shape[0] or (np.diff(offsets) < 0).any():
+        raise ValueError("host_bundle_blocks: offsets must run from 0 to the %d correspondences without decreasing" % pts_a.shape[0])
+    blocks = np.empty((E, BUNDLE_BLOCK), dtype=np.float64)
+    count, status = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
+    check(lib.rwh_host_bundle_blocks(pts_a.ctypes.data, pts_b.ctypes.data, offsets.ctypes.data, E, masks.ctypes.data, masks.shape[1],
+                                     t.ctypes.data, blocks.ctypes.data, count.ctypes.data, status.ctypes.data), "rwh_host_bundle_blocks")
+    return blocks, count, status
+
+
+def host_bundle_step(n, anchor, edges, blocks, lam):
+    """One damped step from the edge blocks (rwh_host_bundle_step, host only): -> (delta float64 [n, 8], status)."""
+    lib = _lib.load()
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    blocks = np.ascontiguousarray(blocks, dtype=np.float64).reshape(len(edges), BUNDLE_BLOCK)
+    delta, status = np.empty((int(n), 8), dtype=np.float64), np.zeros(1, dtype=np.int32)
+    check(lib.rwh_host_bundle_step(int(n), int(anchor), edges.ctypes.data, len(edges), blocks.ctypes.data, float(lam), delta.ctypes.data,
+                                   status.ctypes.data), "rwh_host_bundle_step")
+    return delta, int(status[0])
+
+
 # the matcher's block shape, for callers and tests that size problems across it: train rows per block, query rows staged in LDS at
 # a time, query rows per block (include/rwh.h)
 MATCH_TILE_TRAIN, MATCH_CHUNK_QUERY, MATCH_SEG_QUERY = _lib.RWH_MATCH_TILE_TRAIN, _lib.RWH_MATCH_CHUNK_QUERY, _lib.RWH_MATCH_SEG_QUERY

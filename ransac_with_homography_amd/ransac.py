@@ -52,8 +52,9 @@ import numpy as np
 from . import _lapack, _lib, kernels
 from .features import (DeviceProblems, _host_rows, default_pattern, detect_and_describe, extract_batch, match_batch,  # noqa: F401
                        match_descriptors, orb_bin_table, orb_layout, orb_level_quotas, orb_scales, rotate_pattern)
-from .homography import (_check_bands, _check_projection, _pair_rows, calcHomography, calcHomographyLinear, cylindericlMap,  # noqa: F401
-                         sequence_focal, sequence_gains, sequence_plan, stitchPanorama, stitchSequence)
+from .homography import (_check_bands, _check_pairs, _check_projection, _oriented, _pair_rows, _sequence_inputs, calcHomography,  # noqa: F401
+                         calcHomographyLinear, cylindericlMap, sequence_adjust, sequence_focal, sequence_gains, sequence_graph,
+                         sequence_plan, stitchPanorama, stitchSequence)
 
 # Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
 # in csrc/rwh_settle.h.  RESCORE_MARGIN caps the margin of the 'backward' / 'reproj' rule: an unflagged K1 count moves by <= 2
@@ -579,7 +580,9 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
     float64 and is not the reference's float32 bits (it is closer to the exact least-squares solution).  `finalModel` is None
     where the refit reports anything but RWH_REFIT_OK or the winner has fewer than `n` inliers; inliers and counts are as with
     refit=True.  `info` then also receives "H_device" ([P,3,3] float64, NaN where the status is not OK) and "refit_status"
-    ([P] int32), the device tensors, for a consumer on the GPU.  Any other value of `refit` raises ValueError.
+    ([P] int32), the device tensors, for a consumer on the GPU, and with them "mask_device" ([P, words] int64: the winners' inlier
+    mask rows, the layout `kernels.refit_batched` takes) and "offsets_device" ([P + 1] int32) -- what `sequence_adjust` reads
+    without a visit to the host.  Any other value of `refit` raises ValueError.
 
     Sampling: by default on the device (Philox4x32-10 keyed by `seed`, four distinct correspondences per hypothesis):
     a documented NON-PARITY mode -- the reference draws with replacement from numpy's global legacy generator
@@ -681,6 +684,7 @@ def run_batch(datas, th=5, d=50, n=4, k=1000, method="reproj", seed=0, idx=None,
         both = torch.cat([H_dev.reshape(P, 9), status_dev.to(torch.float64)[:, None]], dim=1).cpu().numpy()   # one copy
         if info is not None:
             info["H_device"], info["refit_status"] = H_dev, status_dev
+            info["mask_device"], info["offsets_device"] = win_dev, offsets_dev
     out = []
     for p, (winner, _, early) in enumerate(winners):
         model = HomoModel(th=th, d=d, n=n)
@@ -767,7 +771,7 @@ def stitching(trainImg, queryImg, ransacMet="fwd", th=5, d=70, n=4, k=1000, blen
 
 
 def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, blending=False, features=None, info=None, gains=None,
-                    projection=None, focal=None, bands=5):
+                    projection=None, focal=None, pairs="adjacent", adjust=False, bands=5):
     """Pixels -> panorama for a SEQUENCE of N overlapping images (images[i+1] overlaps images[i]), every stage batched: one
     `extract_batch` over the N images, one `match_batch` over the N - 1 adjacent pairs, one `run_batch(refit="device")`, one download
     of the [N - 1, 3, 3] homographies -- the only geometry that visits the host, because the canvas must be allocated -- and one
@@ -783,10 +787,30 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     float64 [N], or None).  projection, focal: as `stitchSequence`'s (a cylindrical or spherical canvas, for sweeps too wide for the
     anchor's plane; "origin" is then in surface pixels); focal="auto" calls `sequence_focal` on the estimated homographies, and
     `info` receives "focal" (the focal used, or None).  ValueError: a pair without a homography (too few matches or inliers, a singular refit), naming the pair and its
-    match count; whatever `stitchSequence` refuses."""
+    match count; whatever `stitchSequence` refuses.
+
+    pairs, adjust: registration over a pair graph (the bundle rule of include/rwh.h).  pairs="adjacent" (default): the N - 1 pairs
+    (i + 1, i), chained.  pairs="all" or a list of (s, d): those pairs are matched and searched in one `match_batch` and one
+    `run_batch(refit="device")` (features of s against features of d, H maps s into d), `sequence_graph` accepts the verified
+    ones and initialises every G_i along a maximum spanning tree from the anchor, so the images need not come in order.
+    adjust=True: `sequence_adjust` then refines all G_i jointly over the inliers of the accepted pairs, correspondences and masks
+    staying on the device.  The canvas comes from `stitchSequence(images, Gs=...)`.  `info` then receives "pairs", "accepted"
+    (bool per pair), "tree" and "adjust" (`sequence_adjust`'s info, or None); "Hs" is set only with pairs="adjacent".  The
+    defaults make the calls and give the results they always did.  `bands` stays the last parameter: pass it, and everything
+    behind `focal`, by name.  ValueError, before the GPU is asked for: another `pairs` or `adjust`."""
     n = len(images)
     if not 1 <= n <= _lib.RWH_SEQ_MAX_IMAGES:
         raise ValueError("stitch_sequence: %d images; 1 .. %d are taken" % (n, _lib.RWH_SEQ_MAX_IMAGES))
+    if not isinstance(adjust, (bool, np.bool_)):
+        raise ValueError("stitch_sequence: adjust=%r; True or False" % (adjust,))
+    if isinstance(pairs, str):
+        if pairs not in ("adjacent", "all"):
+            raise ValueError("stitch_sequence: pairs=%r; 'adjacent', 'all' or a list of (s, d)" % (pairs,))
+    else:
+        pairs = _check_pairs("stitch_sequence", n, pairs)
+        if len(set(pairs)) != len(pairs):
+            raise ValueError("stitch_sequence: pairs=%r names a pair twice" % (pairs,))
+    graph = adjust or pairs != "adjacent"
     if isinstance(gains, str):
         if gains != "auto":
             raise ValueError("stitch_sequence: gains=%r; None, N gains or 'auto'" % (gains,))
@@ -796,6 +820,9 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
         _check_bands("stitch_sequence", bands)
     auto_focal = isinstance(focal, str) and focal == "auto" and projection is not None
     _check_projection("stitch_sequence", projection, 1.0 if auto_focal else focal)
+    if graph:
+        return _stitch_sequence_graph(images, anchor, dict(th=th, d=d, n=4, k=k, method=ransacMet, seed=seed), blending, features, info, gains,
+                                      projection, focal, auto_focal, bands, pairs, adjust)
     Hs, sizes, inliers = np.zeros((0, 3, 3)), [], []
     if n > 1:
         feats = extract_batch(images, **(features or {}))
@@ -818,6 +845,47 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
         info["focal"] = focal
     used = {}
     out = stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands, projection=projection,
+                         focal=focal)
+    if info is not None:
+        info["gains"] = used["gains"]
+    return out
+
+
+def _stitch_sequence_graph(images, anchor, search, blending, features, info, gains, projection, focal, auto_focal, bands, pairs, adjust):
+    """`stitch_sequence` over a pair graph: one extract, one match and one search over the listed pairs, `sequence_graph`, with
+    adjust=True `sequence_adjust` on the device, then `stitchSequence(Gs=...)`."""
+    n = len(images)
+    adjacent = isinstance(pairs, str) and pairs == "adjacent"
+    if isinstance(pairs, str):
+        pairs = [(i + 1, i) for i in range(n - 1)] if adjacent else [(s, d) for d in range(n) for s in range(d + 1, n)]
+    Hs, sizes, inliers, masks, problems = [], [], [], None, None
+    if pairs:
+        feats = extract_batch(images, **(features or {}))
+        problems = match_batch([(feats[s][0], feats[s][1], feats[d][0], feats[d][1]) for s, d in pairs])
+        sizes = [int(m) for m in problems.sizes]
+        found = {}
+        res = run_batch(problems, refit="device", info=found, **search)
+        Hs, inliers, masks = [r[0] for r in res], [int(r[2]) for r in res], found["mask_device"]
+    Gs, accepted, tree = sequence_graph(n, pairs, Hs, sizes, inliers, anchor)
+    adjusted = None
+    if adjust and pairs:
+        import torch
+        adjusted = {}
+        masks = masks.clone()
+        masks[torch.from_numpy(~accepted).to(masks.device)] = 0      # an edge that is not accepted has no inliers: a zero block
+        Gs = sequence_adjust(Gs, pairs, problems, masks=masks, anchor=anchor, on="device", info=adjusted)
+    shapes = [tuple(int(v) for v in img.shape) for img in images]
+    if auto_focal:
+        focal = sequence_focal(shapes, [H for H, ok in zip(Hs, accepted) if ok], pairs=[pr for pr, ok in zip(pairs, accepted) if ok])
+    if info is not None:
+        _, origin, _, _, _, _ = _sequence_inputs("stitch_sequence", images, None, Gs, anchor, projection, focal)
+        info["Gs"], info["origin"] = (Gs if projection is None else _oriented(Gs)), origin
+        info["sizes"], info["inliers"], info["focal"] = sizes, inliers, focal
+        info["pairs"], info["accepted"], info["tree"], info["adjust"] = pairs, accepted, tree, adjusted
+        if adjacent:        # every pair of a chain is accepted, or sequence_graph has raised
+            info["Hs"] = np.stack(Hs) if Hs else np.zeros((0, 3, 3))
+    used = {}
+    out = stitchSequence(images, Gs=Gs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands, projection=projection,
                          focal=focal)
     if info is not None:
         info["gains"] = used["gains"]
