@@ -1062,8 +1062,9 @@ def sequence_adjust(Gs, pairs, matches, masks=None, anchor=0, max_iters=20, on="
     lambda > 1e12, or on an accepted step that lowers the cost by less than 1e-12 of it.
     `info`: optional dict, receives "cost" (the start and every accepted step), "iters" (accepted steps) and "lambda".
     Returns Gs float64 [N, 3, 3], Gs[anchor] the identity.  ValueError: bad n, anchor, pairs, on or max_iters, matches or masks that
-    do not fit the pairs, Gs that are not finite or invertible, a correspondence that is behind its camera at the start, an image
-    that no edge with inliers touches."""
+    do not fit the pairs, Gs that are not finite or invertible, a correspondence that is behind its camera at the start, a pair whose
+    cost is not finite at the start (a NaN or infinite coordinate in its b, or residuals beyond float64; the pair is named), an
+    image that no edge with inliers touches."""
     Gs = np.array([np.asarray(G, dtype=np.float64) for G in Gs])
     n = len(Gs)
     _check_count(n, anchor)
@@ -1127,6 +1128,10 @@ def sequence_adjust(Gs, pairs, matches, masks=None, anchor=0, max_iters=20, on="
     if (status != _lib.RWH_BUNDLE_OK).any():
         e = int(np.nonzero(status != _lib.RWH_BUNDLE_OK)[0][0])
         raise ValueError("sequence_adjust: pair %d (images %d and %d) has an inlier behind the camera at the start" % ((e,) + pairs[e]))
+    if not np.isfinite(blocks[:, -1]).all():
+        e = int(np.nonzero(~np.isfinite(blocks[:, -1]))[0][0])
+        raise ValueError("sequence_adjust: pair %d (images %d and %d) has a cost that is not finite at the start (a correspondence "
+                         "that is not finite?)" % ((e,) + pairs[e]))
     cost = float(blocks[:, -1].sum())
     history, lam, iters = [cost], ADJUST_LAMBDA0, 0
     signs = np.sign(dets)

@@ -420,13 +420,18 @@ def bundle_blocks(pts_a, pts_b, offsets, masks, transfers, out=None):
     transfers: [E, 3, 3] float64 on the HOST (one upload of E x 9 doubles).  Returns one [E, 155] float64 tensor on the GPU: the
     153 values of each block, then the edge's count and status as float64 -- so that ONE download brings everything to the host
     (`bundle_split` takes it apart).  out: optionally the three tensors the library writes -- blocks [E, 153] float64, count [E]
-    and status [E] int32, contiguous, on the GPU -- instead of fresh ones.  Enqueued on torch's current stream."""
+    and status [E] int32, contiguous, on the GPU -- instead of fresh ones.  Edges without any correspondence ([0, 2] points) give
+    zero blocks, as the host twin's.  Enqueued on torch's current stream."""
     lib = _lib.load()
     _dev_check(pts_a, pts_b, offsets, masks)
     E = offsets.shape[0] - 1
     assert pts_a.dtype == torch.float32 and pts_b.dtype == torch.float32 and offsets.dtype == torch.int32
     assert masks.dtype == torch.int64 and masks.dim() == 2 and masks.shape[0] == E and tuple(pts_a.shape) == tuple(pts_b.shape)
     t_dev = torch.from_numpy(_bundle_transfers(transfers, E)).to(pts_a.device)
+    if pts_a.shape[0] == 0:
+        # edges without a single correspondence: an empty tensor has no address and the library refuses a null pointer, where the
+        # host twin gives zero blocks.  One row that no edge's offsets reach stands in; nothing of it is read.
+        pts_a = pts_b = torch.zeros((1, 2), dtype=torch.float32, device=pts_a.device)
     if out is None:
         blocks = torch.empty((E, BUNDLE_BLOCK), dtype=torch.float64, device=pts_a.device)
         count, status = torch.empty((2, E), dtype=torch.int32, device=pts_a.device)

@@ -2,7 +2,9 @@
 loop over the rows in the stated order, vectorised over the 153 entries of a block --, the exact-rational model of one
 correspondence with the forward rounding bound of the stated operation sequence, the generators (random edges, the GRID scene)
 and the ctypes drivers of the host twin and the solver that tests/test_sequence_bundle_cpu.py and tests/test_sequence_bundle_gpu.py
-share."""
+share; for tests/test_bundle_loop_cpu.py and tests/test_bundle_loop_gpu.py the whole problem stated independently (the cost from the
+geometry, its minimum by a plain numpy optimiser in another parameterisation), the far starts, the validity cases, the largest
+launch and three warped views of one scene."""
 from fractions import Fraction
 
 import numpy as np
@@ -18,8 +20,23 @@ SIZES = [0, 1, 3, 4, 5, 63, 64, 65, 127, 128, 129, 257, 600]
 
 # ---- the rule ----
 def fma(a, b, c):
-    """a * b + c rounded once, through exact rationals (finite operands)."""
-    return float(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
+    """a * b + c rounded once, through exact rationals.  With an operand that is not finite it is the plain float expression (the
+    result is NaN or an infinity either way, no rounding is involved); where the exact result lies beyond the largest float64 it
+    is the infinity of its sign, as IEEE 754 rounds it."""
+    a, b, c = float(a), float(b), float(c)
+    if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(c)):
+        with np.errstate(all="ignore"):
+            return float(np.float64(a) * np.float64(b) + np.float64(c))
+    exact = Fraction(a) * Fraction(b) + Fraction(c)
+    if exact == 0:
+        # the sign of a zero result: a zero product and a zero c of one sign keep it, everything else (an exact cancellation
+        # included) is +0 in round-to-nearest; a rational has no -0, so this is stated here
+        negative = (a == 0.0 or b == 0.0) and np.signbit(a) != np.signbit(b) and np.signbit(c)
+        return -0.0 if negative else 0.0
+    try:
+        return float(exact)
+    except OverflowError:
+        return float("inf") if exact > 0 else float("-inf")
 
 
 def entries():
@@ -34,8 +51,8 @@ def row_values(T, a, b):
     components for each of the 16 columns, zeros included."""
     T = np.asarray(T, dtype=np.float64).reshape(3, 3)
     at = np.array([np.float64(a[0]), np.float64(a[1]), 1.0])
-    p = np.array([np.float64(fma(T[i, 1], at[1], T[i, 0] * at[0])) + T[i, 2] for i in range(3)])
     with np.errstate(all="ignore"):
+        p = np.array([np.float64(fma(T[i, 1], at[1], T[i, 0] * at[0])) + T[i, 2] for i in range(3)])
         q = p[:2] / p[2]
     if not (np.isfinite(p[2]) and p[2] > 0 and np.isfinite(q).all()):
         return None
@@ -51,6 +68,13 @@ def row_values(T, a, b):
     row[16:32] = (dp[1] - q[1] * dp[2]) / p[2]
     row[32], row[33] = q[0] - np.float64(b[0]), q[1] - np.float64(b[1])
     return row
+
+
+def row_p2(T, a):
+    """p2 of one correspondence as the rule computes it (the third component of `row_values`' p)."""
+    T = np.asarray(T, dtype=np.float64).reshape(3, 3)
+    with np.errstate(all="ignore"):
+        return np.float64(fma(T[2, 1], np.float64(a[1]), T[2, 0] * np.float64(a[0]))) + T[2, 2]
 
 
 def mask_bit(words, i):
@@ -326,6 +350,29 @@ def host_blocks(lib, pa, pb, offsets, masks, T):
             bufs[2][64:-64].view(np.int32).copy())
 
 
+def _same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+
+
+def device_blocks(pa, pb, offsets, masks, T):
+    """kernels.bundle_blocks into outputs that sit between guard words -> (blocks, count, status) in numpy; the guards are checked
+    and the packed result is checked against the three outputs."""
+    import torch
+    from ransac_with_homography_amd import kernels
+    E = len(offsets) - 1
+    blocks_buf = torch.full((E * BLOCK + 16,), -7.0, dtype=torch.float64, device="cuda")
+    tail_buf = torch.full((2, E + 32), -7, dtype=torch.int32, device="cuda")
+    out = (blocks_buf[8:-8].view(E, BLOCK), tail_buf[0, 16:-16], tail_buf[1, 16:-16])
+    packed = kernels.bundle_blocks(torch.from_numpy(pa).cuda(), torch.from_numpy(pb).cuda(), torch.from_numpy(offsets).cuda(),
+                                   torch.from_numpy(np.ascontiguousarray(masks).view(np.int64)).cuda(), T, out=out)
+    flat, tail = blocks_buf.cpu().numpy(), tail_buf.cpu().numpy()
+    assert (flat[:8] == -7.0).all() and (flat[-8:] == -7.0).all(), "a value outside the blocks was written"
+    assert (tail[:, :16] == -7).all() and (tail[:, -16:] == -7).all(), "a word outside count or status was written"
+    blocks, count, status = kernels.bundle_split(packed.cpu().numpy())
+    assert _same_bits(blocks, flat[8:-8].reshape(E, BLOCK)) and np.array_equal(count, tail[0, 16:-16]) and np.array_equal(status, tail[1, 16:-16])
+    return blocks, count, status
+
+
 def host_step(lib, n, anchor, pairs, blocks, lam):
     """rwh_host_bundle_step -> (status of the call, delta [n, 8], step status), delta between canaries."""
     edges = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
@@ -355,3 +402,202 @@ def solve_bound(A, x):
     """The backward-error bound of a Cholesky solve, as tests/gain_cases.residual_bound: 4 n^2 u |A|_inf |x|_inf."""
     n = len(x)
     return 4 * n * n * U * np.abs(A).sum(axis=1).max() * np.abs(x).max()
+
+
+# ---- the whole problem stated independently: the cost from the geometry, its minimum by a plain optimiser ----
+def _inlier_rows(matches, masks):
+    """[(a, b)] in float64, each edge's rows cut down to those whose mask bit is set (masks None: every row)."""
+    out = []
+    words = None if masks is None else np.ascontiguousarray(masks).view(np.uint64)
+    for e, (a, b) in enumerate(matches):
+        a, b = np.asarray(a, dtype=np.float64).reshape(-1, 2), np.asarray(b, dtype=np.float64).reshape(-1, 2)
+        if words is not None:
+            keep = np.array([mask_bit(words[e], i) for i in range(len(a))], dtype=bool)
+            a, b = a[keep], b[keep]
+        out.append((a, b))
+    return out
+
+
+def _residuals(Gs, pairs, rows):
+    """Every r = dehomogenised(inv(G_d) G_s a~) - b of the kept rows, one flat vector."""
+    inv = np.linalg.inv(Gs)
+    return np.concatenate([(project(inv[d] @ Gs[s], a) - b).ravel() for (s, d), (a, b) in zip(pairs, rows)])
+
+
+def reference_cost(Gs, pairs, matches, masks=None):
+    """The bundle cost at Gs from the geometry alone, float64 numpy: T = inv(G_d) @ G_s, a projected, b subtracted, the squares
+    summed over the rows whose mask bit is set.  No J, no blocks, no scaling of T (the projection does not see it)."""
+    r = _residuals(np.asarray(Gs, dtype=np.float64), pairs, _inlier_rows(matches, masks))
+    return float(np.sum(r * r))
+
+
+def reference_optimum(Gs0, pairs, matches, anchor, masks=None):
+    """The minimum of `reference_cost` by Levenberg-Marquardt in plain numpy -> (Gs, cost).  Another parameterisation than the
+    library's: the 8 entries of every G_i / G_i[2][2] but the anchor's, global, not the local I + D(delta); the Jacobian by
+    forward differences of the residual vector (step 1e-7 of the entry's size, floored at 1e-7, 1e-11 on the perspective row).
+    The optimiser only has to FIND the minimum; what it returns is judged by `reference_cost`."""
+    rows = _inlier_rows(matches, masks)
+    Gs0 = np.asarray(Gs0, dtype=np.float64)
+    n = len(Gs0)
+    free = [i for i in range(n) if i != anchor]
+    floor = np.tile([1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1e-4, 1e-4], len(free))
+
+    def unpack_x(x):
+        Gs = np.empty((n, 3, 3))
+        Gs[anchor] = np.eye(3)
+        for j, i in enumerate(free):
+            Gs[i] = np.append(x[8 * j:8 * j + 8], 1.0).reshape(3, 3)
+        return Gs
+
+    def res(x):
+        return _residuals(unpack_x(x), pairs, rows)
+
+    x = np.concatenate([(Gs0[i] / Gs0[i, 2, 2]).reshape(9)[:8] for i in free])
+    r = res(x)
+    cost, lam = float(r @ r), 1e-3
+    for _ in range(100):
+        J = np.empty((len(r), len(x)))
+        for k in range(len(x)):
+            h = 1e-7 * max(abs(x[k]), floor[k])
+            xh = x.copy()
+            xh[k] += h
+            J[:, k] = (res(xh) - r) / (xh[k] - x[k])
+        A, g = J.T @ J, J.T @ r
+        took = None
+        while lam <= 1e15 and took is None:
+            try:
+                step = np.linalg.solve(A + lam * np.diag(np.diag(A)), -g)
+            except np.linalg.LinAlgError:
+                step = None
+            if step is not None:
+                with np.errstate(all="ignore"):
+                    r2 = res(x + step)
+                c2 = float(r2 @ r2)
+                if np.isfinite(c2) and c2 < cost:
+                    took = (x + step, r2, c2)
+            if took is None:
+                lam *= 10.0
+        if took is None:
+            break
+        gain = cost - took[2]
+        x, r, cost = took
+        lam = max(lam / 10.0, 1e-9)
+        if gain <= 1e-15 * cost:
+            break
+    Gs = unpack_x(x)
+    return Gs, reference_cost(Gs, pairs, matches, masks)
+
+
+# The far starts of the loop tests: (seed, persp) of `far_start`, with what the host loop does from each of them on GRID from the
+# chain start (steps tried, steps accepted), counted where this was written; tests/test_bundle_loop_cpu.py asserts the counts.
+FAR_ONE_REJECT = dict(seed=3, persp=0.003, tried=8, accepted=7)
+FAR_MANY_REJECTS = dict(seed=35, persp=0.0025, tried=27, accepted=6)
+
+
+def far_start(start, seed, persp):
+    """`start` with every map but the first multiplied from the right by I + [[.1, .1, 20], [.1, .1, 20], [persp, persp, 0]] *
+    uniform(-1, 1): far enough that Levenberg-Marquardt rejects steps on the way back."""
+    rng = np.random.default_rng(seed)
+    spread = np.array([[0.1, 0.1, 20.0], [0.1, 0.1, 20.0], [persp, persp, 0.0]])
+    out = [np.array(start[0], dtype=np.float64)]
+    for G in start[1:]:
+        out.append(np.asarray(G, dtype=np.float64) @ (np.eye(3) + spread * rng.uniform(-1, 1, (3, 3))))
+    return np.stack(out)
+
+
+def reframed(Gs, anchor):
+    """The same maps expressed in image `anchor`'s frame: inv(G_anchor) @ G_i, the anchor's the identity exactly."""
+    Gs = np.asarray(Gs, dtype=np.float64)
+    out = np.stack([np.linalg.inv(Gs[anchor]) @ G for G in Gs])
+    out[anchor] = np.eye(3)
+    return out
+
+
+# ---- the validity test from every side ----
+VALIDITY_ROW = 130          # of edge 1 (200 rows): past the first staged chunk, row 2 of the second, so wave 2's partial
+
+
+def validity_cases():
+    """Three edges of 70, 200 and 9 rows, every row an inlier; row 130 of edge 1 made invalid in eight ways -> (c, masks, cleared,
+    [(name, pa, T)]): c the undisturbed case, `cleared` the masks without that row's bit.  Coordinate cases keep c's transfers:
+    T[1][2][0] < 0 (asserted), so the float32-huge x gives a large negative p2.  Transfer cases give edge 1 the transfer
+    [[1, 0, 1/2], [0, 1, -1/4], [1/512, 1/16, t]]: p2 = x / 512 + y / 16 + t is positive on every other row (x, y >= 0, not both
+    0: asserted), and at the row's (x, y) = (-512, 16) both products are exact and cancel, so p2 = t exactly."""
+    c = size_list_case(seed=21, sizes=[70, 200, 9])
+    at = int(c["offsets"][1]) + VALIDITY_ROW
+    masks = mask_sets(c["sizes"])["ones"]
+    cleared = masks.copy()
+    cleared[1, VALIDITY_ROW >> 6] &= ~np.int64(1 << (VALIDITY_ROW & 63))
+    assert c["T"][1][2, 0] < 0
+    others = np.delete(c["pa"][c["offsets"][1]:c["offsets"][2]], VALIDITY_ROW, axis=0)
+    assert (others >= 0).all() and (others.sum(axis=1) > 0).all()
+
+    def transfer(t):
+        return np.array([[1.0, 0.0, 0.5], [0.0, 1.0, -0.25], [1.0 / 512.0, 1.0 / 16.0, t]])
+
+    listed = [("x nan", (np.nan, None), None), ("x +inf", (np.inf, None), None), ("y -inf", (None, -np.inf), None),
+              ("x 3e38", (np.float32(3e38), None), None),
+              ("p2 +0", (-512.0, 16.0), transfer(0.0)),                    # (+1) + (-1) = +0, + 0 = +0
+              ("p2 -0", (-0.0, -0.0), transfer(-0.0)),                     # (-0) + (-0) = -0 twice: every term is a negative zero
+              ("p2 negative", (-512.0, 8.0), transfer(0.0)),               # -1 + 1/2
+              ("p2 denormal", (-512.0, 16.0), transfer(2.0 ** -1070))]     # p2 = 2^-1070 > 0 and p0 = -511.5: q0 overflows
+    cases = []
+    for name, (x, y), T1 in listed:
+        pa, T = c["pa"].copy(), c["T"].copy()
+        if x is not None:
+            pa[at, 0] = x
+        if y is not None:
+            pa[at, 1] = y
+        if T1 is not None:
+            T[1] = T1
+        cases.append((name, pa, T))
+    return c, masks, cleared, cases
+
+
+# ---- the launch's two ends ----
+LAUNCH_SIZES = [(0, 1, 2, 3, 4, 5, 7, 64, 65)[e % 9] for e in range(2016)]
+
+
+def launch_case():
+    """The largest launch: 2016 edges (every pair of 64 images), 33 824 rows, the "random" masks -> (c, masks)."""
+    c = size_list_case(seed=5, n=64, sizes=LAUNCH_SIZES)
+    return c, mask_sets(c["sizes"])["random"]
+
+
+def single_edge(c, masks, e):
+    """Edge e of a case as a launch of its own: its rows, offsets from 0, its mask row, its transfer."""
+    o0, o1 = int(c["offsets"][e]), int(c["offsets"][e + 1])
+    return (np.ascontiguousarray(c["pa"][o0:o1]), np.ascontiguousarray(c["pb"][o0:o1]), np.array([0, o1 - o0], dtype=np.int32),
+            np.ascontiguousarray(masks[e:e + 1]), c["T"][e:e + 1])
+
+
+# ---- three views with real residuals ----
+VIEW_SHAPE, VIEW_SHIFTS = (180, 290), [(3.3, 9.6), (48.7, 7.3), (139.2, 11.8)]
+
+
+def warped_views(seed=12):
+    """Three views of sequence_cases.scene() that are no integer shifts of it: view i shows the scene under M_i =
+    sc.homography(rng, tx, ty, affine=0.01, persp=2e-5) (view pixel -> scene pixel; views 45.4 and 90.5 px apart, so that the outer
+    pair still shares half a view: with 90 px twice it has too few matches to be accepted), sampled bilinearly in float64 and
+    rounded to uint8; every view lies inside the scene (asserted) -> (views, Gs): Gs[i] = inv(M_0) @ M_i, the ground truth maps
+    into view 0's frame.  On the host twins of the extractor and the matcher the pairs (1, 0), (2, 0), (2, 1) have 109, 100 and 104
+    matches, 87, 59 and 77 of them within 5 px of the truth; acceptance needs more than 40.7, 38.0 and 39.2."""
+    import sequence_cases as sc
+    scene = sc.scene().astype(np.float64)
+    rng = np.random.default_rng(seed)
+    h, w = VIEW_SHAPE
+    yy, xx = np.mgrid[0:h, 0:w]
+    views, Ms = [], []
+    for tx, ty in VIEW_SHIFTS:
+        M = sc.homography(rng, tx, ty, affine=0.01, persp=2e-5)
+        z = M @ np.stack([xx.ravel(), yy.ravel(), np.ones(h * w)]).astype(np.float64)
+        x, y = z[0] / z[2], z[1] / z[2]
+        assert x.min() >= 0 and y.min() >= 0 and x.max() <= scene.shape[1] - 1 and y.max() <= scene.shape[0] - 1
+        x0, y0 = np.minimum(np.floor(x).astype(int), scene.shape[1] - 2), np.minimum(np.floor(y).astype(int), scene.shape[0] - 2)
+        fx, fy = (x - x0)[:, None], (y - y0)[:, None]
+        img = ((scene[y0, x0] * (1 - fx) + scene[y0, x0 + 1] * fx) * (1 - fy) + (scene[y0 + 1, x0] * (1 - fx) + scene[y0 + 1, x0 + 1] * fx) * fy)
+        views.append(np.ascontiguousarray(np.rint(img).astype(np.uint8).reshape(h, w, 3)))
+        Ms.append(M)
+    Gs = np.stack([np.linalg.inv(Ms[0]) @ M for M in Ms])
+    Gs[0] = np.eye(3)
+    return views, Gs

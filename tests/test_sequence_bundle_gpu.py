@@ -31,23 +31,7 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
 
 
-def device_blocks(pa, pb, offsets, masks, T):
-    """kernels.bundle_blocks into outputs that sit between guard words -> (blocks, count, status) in numpy; the guards are checked
-    and the packed result is checked against the three outputs."""
-    import torch
-    from ransac_with_homography_amd import kernels
-    E = len(offsets) - 1
-    blocks_buf = torch.full((E * bc.BLOCK + 16,), -7.0, dtype=torch.float64, device="cuda")
-    tail_buf = torch.full((2, E + 32), -7, dtype=torch.int32, device="cuda")
-    out = (blocks_buf[8:-8].view(E, bc.BLOCK), tail_buf[0, 16:-16], tail_buf[1, 16:-16])
-    packed = kernels.bundle_blocks(torch.from_numpy(pa).cuda(), torch.from_numpy(pb).cuda(), torch.from_numpy(offsets).cuda(),
-                                   torch.from_numpy(np.ascontiguousarray(masks).view(np.int64)).cuda(), T, out=out)
-    flat, tail = blocks_buf.cpu().numpy(), tail_buf.cpu().numpy()
-    assert (flat[:8] == -7.0).all() and (flat[-8:] == -7.0).all(), "a value outside the blocks was written"
-    assert (tail[:, :16] == -7).all() and (tail[:, -16:] == -7).all(), "a word outside count or status was written"
-    blocks, count, status = kernels.bundle_split(packed.cpu().numpy())
-    assert same_bits(blocks, flat[8:-8].reshape(E, bc.BLOCK)) and np.array_equal(count, tail[0, 16:-16]) and np.array_equal(status, tail[1, 16:-16])
-    return blocks, count, status
+device_blocks = bc.device_blocks
 
 
 @pytest.mark.parametrize("which", ["ones", "random", "short"])
