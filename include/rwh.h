@@ -393,6 +393,65 @@ RWH_API int rwh_host_match_hamming(const uint8_t* desc_a, int na, const uint8_t*
                            int32_t* distance);
 
 /*
+ * Hamming matcher with the 2-nearest RATIO TEST over a PAIR GRAPH: the matcher in front of a pair graph (rwh_bundle_*), where
+ * most proposed pairs do not overlap.  The cross-check rule above gives nearly every train row a partner whether the images overlap
+ * or not (two unrelated sets of 300 random 32-byte rows: 192 "matches" in tests/test_match_ratio_cpu.py), and an acceptance rule of the form
+ * inliers > 8 + 0.3 matches (Brown & Lowe 2007, eq. 13) pays for that ballast.  Images 0 .. N-1 each own a block of rows of ONE
+ * descriptor array, and a pair (s, d) names its query and its train image: no descriptor is copied per pair.
+ * THE RATIO RULE.  Pair p = (s, d): A = the na rows of image s (query side), B = the nb rows of image d (train side),
+ * D[i][j] = popcount(A[i] xor B[j]); parameters: integers 0 < num <= den <= RWH_MATCH2_RATIO_MAX.
+ *   1. For every query i: d1[i] = min_j D[i][j], j1[i] a row that attains it, d2[i] = the smallest D[i][j] over j != j1[i] (so
+ *      d2 == d1 when two rows tie).  With nb < 2 there is no d2 and no query of the pair is a candidate.
+ *   2. Query i is a CANDIDATE iff den d1[i] < num d2[i] -- on integers, strict.  A tie for the nearest row is therefore never a
+ *      candidate, whatever the ratio, and which of the tied rows is called j1 cannot show.
+ *   3. One query per train row: among the candidates with the same j1 the one with the smallest d1 survives, the lowest i on ties;
+ *      the others have no match.
+ *   4. The pair's match list is the survivors (i, j1, d1) ordered by (d1, i) -- left to the caller, who gets one record per query
+ *      row; the correspondences are keypoint i of image s, keypoint j1 of image d, in that order (H maps s into d).
+ * PROVENANCE.  Rules 1 and 2 are Lowe's ratio test (Lowe 2004, section 7.1), the usual matcher in front of a pair graph (OpenCV's
+ * stitcher is remembered to use d1 < (1 - match_conf) d2 with match_conf 0.3 for ORB: a convention quoted from memory, parity is
+ * NOT claimed); rule 3 is added so that the search sees one-to-one correspondences.  The code is held to the statement above
+ * (tests/match_ratio_cases.py restates it in numpy), not to OpenCV; every quantity is an integer, so results are exact, do not
+ * depend on how the work is split, and a rerun is bit-identical.
+ *   d_desc: total_rows x nbytes uint8, rows contiguous, any alignment; d_image_offsets: n_images + 1 int32, image k owns rows
+ *   d_image_offsets[k] .. d_image_offsets[k+1]-1 (an image whose range is not inside [0, total_rows] has no rows);
+ *   d_pairs: n_pairs x 2 int32 (s, d).  s == d, a pair listed twice, both (s, d) and (d, s) and an image without rows are legal; a
+ *   pair that names an image outside 0 .. n_images-1 reads nothing and has no matches;
+ *   total_query = sum_p na(s_p), total_train = sum_p nb(d_p) (the caller knows the row counts; no download is needed);
+ *   d_train_idx, d_distance, d_second: total_query int32 each; the row of (pair p, query i) is sum_{q<p} na(s_q) + i and holds
+ *   (j1 LOCAL to image d, d1, d2) for a survivor and -1 / -1 / -1 otherwise.  Rows at or beyond total_query are never written;
+ *   a pair whose rows would pass total_query or total_train (totals smaller than the tables say) has no matches;
+ *   nbytes: 1 .. RWH_MATCH_MAX_BYTES, else RWH_E_UNSUPPORTED;
+ *   d_workspace: workspace_bytes >= rwh_match_ratio_workspace_bytes(P, total_query, total_train, max_train_rows) bytes of device
+ *   memory, 8-byte aligned, contents irrelevant before and after; max_train_rows = the largest nb.  The size is
+ *   8 * (total_train + 4 (P + 1) + total_query * ceil(max(max_train_rows, 1) / RWH_MATCH2_SEG_TRAIN)).  The call itself cannot know
+ *   max_train_rows without a download: it refuses a workspace below the size for max_train_rows = 1, and a pair whose partial
+ *   results would not fit into the workspace given has no matches -- never a write outside it.
+ * Work is split into blocks of RWH_MATCH2_TILE_QUERY query rows x RWH_MATCH2_SEG_TRAIN train rows (train rows staged
+ * RWH_MATCH2_CHUNK_TRAIN at a time); a block leaves its two nearest per query row, a second kernel merges them (the (distance, row)
+ * keys of one query are distinct, so the merge is commutative and associative), applies rule 2 and claims the train row of rule 3
+ * with a 64-bit integer atomic minimum.  Four launches, whatever P.
+ * RWH_E_INVALID (before any device is touched): a NULL table or workspace, a NULL descriptor array with total_rows > 0, a NULL output
+ * array with total_query > 0, n_images <= 0, n_pairs <= 0, a negative total, num / den outside the bounds above, a workspace that is
+ * too small or misaligned.
+ *
+ * rwh_host_match_ratio: the same rule in plain C++ on the HOST for one pair (no device, no stream; works without a GPU): desc_a
+ * na x nbytes, desc_b nb x nbytes, train_idx / distance / second na int32.  RWH_E_INVALID: na < 0, nb < 0, a NULL array of a side
+ * that has rows, num / den outside the bounds; RWH_E_UNSUPPORTED: nbytes outside 1 .. RWH_MATCH_MAX_BYTES.
+ */
+#define RWH_MATCH2_TILE_QUERY 256   /* query rows per block, one per lane            */
+#define RWH_MATCH2_CHUNK_TRAIN 64   /* train rows staged in LDS at a time            */
+#define RWH_MATCH2_SEG_TRAIN  256   /* train rows per block                          */
+#define RWH_MATCH2_RATIO_MAX 1024   /* the largest denominator of the ratio          */
+RWH_API int64_t rwh_match_ratio_workspace_bytes(int n_pairs, int total_query, int total_train, int max_train_rows);
+RWH_API int rwh_match_ratio_graph(const uint8_t* d_desc, int nbytes, const int32_t* d_image_offsets, int n_images, int total_rows,
+                          const int32_t* d_pairs, int n_pairs, int total_query, int total_train, int ratio_num, int ratio_den,
+                          int32_t* d_train_idx, int32_t* d_distance, int32_t* d_second, void* d_workspace, int64_t workspace_bytes,
+                          void* stream);
+RWH_API int rwh_host_match_ratio(const uint8_t* desc_a, int na, const uint8_t* desc_b, int nb, int nbytes, int ratio_num, int ratio_den,
+                         int32_t* train_idx, int32_t* distance, int32_t* second);
+
+/*
  * Feature extractor for a batch of images: FAST-9 corners with non-maximum suppression, intensity-centroid orientation in 12-degree
  * bins and a steered BRIEF descriptor -- the stage in front of rwh_match_hamming_batched.  Stands where the reference calls
  *   cv2.cvtColor(img, cv2.COLOR_RGB2GRAY); cv2.ORB_create().detectAndCompute(gray, None)      ransac.py:252-257

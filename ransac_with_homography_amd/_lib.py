@@ -26,6 +26,9 @@ RWH_REFIT_OK, RWH_REFIT_FEW, RWH_REFIT_SINGULAR = 0, 1, 2
 RWH_E_INVALID, RWH_E_UNSUPPORTED, RWH_E_LAUNCH = -1, -2, -3
 RWH_MATCH_MAX_BYTES = 64
 RWH_MATCH_TILE_TRAIN, RWH_MATCH_CHUNK_QUERY, RWH_MATCH_SEG_QUERY = 256, 64, 256   # the matcher's block shape (include/rwh.h)
+# the ratio matcher over a pair graph (include/rwh.h, the ratio rule): query rows per block, train rows staged at a time, train rows
+# per block; the largest denominator of the ratio
+RWH_MATCH2_TILE_QUERY, RWH_MATCH2_CHUNK_TRAIN, RWH_MATCH2_SEG_TRAIN, RWH_MATCH2_RATIO_MAX = 256, 64, 256, 1024
 # the extractor (include/rwh.h): border of a keypoint's centre, orientation bins, radius of the moment patch and of the test points,
 # the detector's tile
 RWH_ORB_BORDER, RWH_ORB_BINS, RWH_ORB_PATCH_RADIUS, RWH_ORB_TEST_RADIUS, RWH_ORB_TILE_W, RWH_ORB_TILE_H = 16, 30, 15, 13, 64, 16
@@ -46,6 +49,7 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_host_dlt4_svd", "rwh_ransac_run", "rwh_ransac_run_layout", "rwh_warp_index_check", "rwh_score_count_inv", "rwh_host_inv3", "rwh_stitch_panorama_rows",
            "rwh_host_legacy_randint", "rwh_score_interval", "rwh_stitch_panorama_ex", "rwh_settle_decide", "rwh_refit_batched", "rwh_host_refit",
            "rwh_match_workspace_bytes", "rwh_match_hamming_batched", "rwh_host_match_hamming",
+           "rwh_match_ratio_workspace_bytes", "rwh_match_ratio_graph", "rwh_host_match_ratio",
            "rwh_orb_workspace_bytes", "rwh_orb_detect_batched", "rwh_orb_describe_batched", "rwh_host_orb_extract",
            "rwh_orb_pyramid_bytes", "rwh_orb_pyramid_batched", "rwh_host_orb_pyramid", "rwh_host_orb_extract_pyramid",
            "rwh_stitch_sequence_workspace_bytes", "rwh_stitch_sequence", "rwh_host_stitch_sequence",
@@ -146,6 +150,12 @@ def _bind(lib):
     lib.rwh_match_hamming_batched.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]
     lib.rwh_host_match_hamming.restype = i32
     lib.rwh_host_match_hamming.argtypes = [vp, i32, vp, i32, i32, vp, vp]
+    lib.rwh_match_ratio_workspace_bytes.restype = i64
+    lib.rwh_match_ratio_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.rwh_match_ratio_graph.restype = i32
+    lib.rwh_match_ratio_graph.argtypes = [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]
+    lib.rwh_host_match_ratio.restype = i32
+    lib.rwh_host_match_ratio.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.rwh_orb_workspace_bytes.restype = i64
     lib.rwh_orb_workspace_bytes.argtypes = [i32]
     lib.rwh_orb_detect_batched.restype = i32

@@ -12,36 +12,13 @@
 // atomic minimum on distance << 32 | query index: partial minima of different segments combine to the same value in any order.
 // The block list is built on the device (the problems' sizes live there): a prefix sum of blocks per problem, which a fixed
 // grid walks with a stride.
-#include "rwh_common.h"
+#include "rwh_match.h"            // desc_dword, match_range, MATCH_NONE: shared with rwh_match_ratio.hip
 
 #define RWH_MATCH_GRID_MAX 2048     /* 256 CUs x 8 blocks of 4 waves */
 
 namespace rwh {
 
 static_assert(RWH_MATCH_SEG_QUERY % RWH_MATCH_CHUNK_QUERY == 0 && RWH_MATCH_SEG_QUERY <= 65536, "the row in its segment takes 16 bits");
-static_assert(8 * RWH_MATCH_MAX_BYTES < 65536, "the distance takes the other 16 bits of the 32-bit key");
-
-constexpr unsigned long long MATCH_NONE = ~0ull;
-
-// dword k of descriptor `row` (rows of nbytes bytes, any alignment); bytes past the row's end read as 0 on both sides, so they
-// add nothing to a distance
-__device__ __forceinline__ uint32_t desc_dword(const unsigned char* __restrict__ desc, long long row, int nbytes, int k) {
-    const unsigned char* p = desc + row * nbytes + 4 * k;
-    const int left = nbytes - 4 * k;
-    if (left >= 4) return ld4(p);
-    uint32_t v = 0;
-    for (int b = 0; b < left; ++b) v |= (uint32_t)p[b] << (8 * b);
-    return v;
-}
-
-// rows of problem p on one side, or 0 rows where the offsets table does not describe a range inside [0, total]
-__device__ __forceinline__ void match_range(const int32_t* __restrict__ offsets, int p, int total, long long& base, int& n) {
-    const long long o0 = offsets[p], o1 = offsets[p + 1];
-    const bool ok = o0 >= 0 && o1 >= o0 && o1 <= total;
-    base = ok ? o0 : 0;
-    n = ok ? (int)(o1 - o0) : 0;
-}
-
 // resets the two key arrays and (block 0) writes prefix[p] = blocks of the problems before p, prefix[P] = all
 __global__ __launch_bounds__(256) void match_setup_kernel(const int32_t* __restrict__ offsets_a, const int32_t* __restrict__ offsets_b,
                                                           int n_problems, int total_a, int total_b,

@@ -5,6 +5,8 @@ on both images, BFMatcher(NORM_HAMMING, crossCheck=True).match) in front of the 
                      rwh_orb_pyramid_batched (more than one level only) -> rwh_orb_detect_batched -> one sort -> rwh_orb_describe_batched
     match_batch      brute-force Hamming matches with cross-check (rwh_match_hamming_batched), handed over as `DeviceProblems`,
                      the correspondences `ransac.run_batch` takes without a visit to the host
+    match_graph      Hamming matches under the 2-nearest ratio test for the pairs of a pair graph (rwh_match_ratio_graph), every
+                     image's descriptors held once; the same hand-off
 
 `orb_layout` is the one statement of the extractor's buffer and table; `orb_bin_table`, `orb_scales`, `orb_level_quotas`,
 `default_pattern` and `rotate_pattern` make the library calls' tables on the host; `detect_and_describe` and `match_descriptors`
@@ -94,10 +96,22 @@ def match_batch(features, info=None):
     off_b_dev = torch.from_numpy(off_b).to(dev)
     train, dist = kernels.match_hamming_batched(torch.cat(da), torch.cat(db), off_a_dev.to(torch.int32), off_b_dev.to(torch.int32))
     ka_all, kb_all = torch.cat(ka), torch.cat(kb)
-    total_a = int(off_a[-1])
-    row = torch.arange(total_a, device=dev)
-    prob = torch.searchsorted(off_a_dev[1:].contiguous(), row, right=True)      # the problem of every query row
-    local = row - off_a_dev[prob]
+    order, q_local, t_local, p_of, sizes = _ordered_matches(train, dist, off_a_dev, int(off_a[-1]), P)
+    if info is not None:
+        info["query_idx"], info["train_idx"], info["distance"] = q_local.to(torch.int32), t_local.to(torch.int32), dist[order]
+    return _device_problems(ka_all[order], kb_all[off_b_dev[p_of] + t_local], sizes)
+
+
+def _ordered_matches(train, dist, off_q_dev, total_q, P):
+    """The tail both matchers share: the library's per-query records (train, dist: int32 [total_q], -1 for no match; problem p owns
+    rows off_q_dev[p] .. off_q_dev[p + 1] - 1, int64 [P + 1] on the device) -> the match lists in the rules' order.  Returns
+    (order, q_local, t_local, p_of, sizes): the rows of the records that hold a match, ordered by (problem, distance, i) with ONE
+    sort on a packed key; the query and train index inside the problem and the problem of each; matches per problem (numpy; the
+    one download)."""
+    import torch
+    row = torch.arange(total_q, device=train.device)
+    prob = torch.searchsorted(off_q_dev[1:].contiguous(), row, right=True)      # the problem of every query row
+    local = row - off_q_dev[prob]
     found = train >= 0
     # (problem, distance, i) in one int64: i < 2^31, distance <= 512 < 2^10, problem < 2^21; rows without a match sort last
     key = ((prob << 10) + dist.to(torch.int64).clamp(min=0) << 31) + local
@@ -105,16 +119,116 @@ def match_batch(features, info=None):
     order = torch.sort(key, stable=True).indices
     sizes = torch.bincount(prob[found], minlength=P).cpu().numpy()              # the one download
     order = order[:int(sizes.sum())]
-    q_local, t_local, p_of = local[order], train[order].to(torch.int64), prob[order]
-    # one spare row behind the correspondences: the 4-point kernel reads row 0 of a problem that has none
-    n = order.shape[0]
-    pts_a = torch.zeros((n + 1, 2), dtype=torch.float32, device=dev)
-    pts_b = torch.zeros((n + 1, 2), dtype=torch.float32, device=dev)
-    pts_a[:n] = ka_all[order]
-    pts_b[:n] = kb_all[off_b_dev[p_of] + t_local]
-    if info is not None:
-        info["query_idx"], info["train_idx"], info["distance"] = q_local.to(torch.int32), t_local.to(torch.int32), dist[order]
+    return order, local[order], train[order].to(torch.int64), prob[order], sizes
+
+
+def _device_problems(rows_a, rows_b, sizes):
+    """The gathered keypoints of the ordered matches -> `DeviceProblems`, with one spare row behind the correspondences: the
+    4-point kernel reads row 0 of a problem that has none."""
+    import torch
+    n = rows_a.shape[0]
+    pts_a = torch.zeros((n + 1, 2), dtype=torch.float32, device=rows_a.device)
+    pts_b = torch.zeros((n + 1, 2), dtype=torch.float32, device=rows_a.device)
+    pts_a[:n] = rows_a
+    pts_b[:n] = rows_b
     return DeviceProblems(pts_a[:n], pts_b[:n], sizes)
+
+
+def match_ratio(ratio, who="match_graph"):
+    """`ratio` of the ratio rule -> integers (num, den), 0 < num <= den <= 1024.  A float in (0, 1] is taken as
+    Fraction(ratio).limit_denominator(1024), so 0.7 is 7 / 10; a pair of integers (num, den) is taken as it stands.  ValueError for
+    anything else.  No GPU is needed."""
+    from fractions import Fraction
+    top = _lib.RWH_MATCH2_RATIO_MAX
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if isinstance(ratio, (float, np.floating)) and 0.0 < float(ratio) <= 1.0:      # (a NaN fails both comparisons)
+        f = Fraction(float(ratio)).limit_denominator(top)
+        if f > 0:
+            return f.numerator, f.denominator
+    elif isinstance(ratio, (tuple, list)) and len(ratio) == 2 and is_int(ratio[0]) and is_int(ratio[1]) and 0 < ratio[0] <= ratio[1] <= top:
+        return int(ratio[0]), int(ratio[1])
+    raise ValueError("%s: ratio=%r; a float in (0, 1] that is at least 1 / %d, or integers (num, den) with 0 < num <= den <= %d"
+                     % (who, ratio, 2 * top, top))
+
+
+def _check_graph_pairs(pairs, n, who):
+    """`match_graph`'s pair list -> int32 [P, 2] of (s, d), both inside 0 .. n - 1; s == d and repeats are allowed here."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    try:
+        rows = [tuple(pr) for pr in pairs]
+    except TypeError:
+        rows = None
+    if not rows or any(len(pr) != 2 or not is_int(pr[0]) or not is_int(pr[1]) for pr in rows):
+        raise ValueError("%s: pairs=%r; a non-empty list of (s, d)" % (who, pairs))
+    if any(not (0 <= s < n and 0 <= d < n) for s, d in rows):
+        raise ValueError("%s: pairs=%r names an image outside 0 .. %d" % (who, pairs, n - 1))
+    if len(rows) >= 2 ** 21:
+        raise ValueError("%s: too many pairs for one submission" % who)
+    return np.array(rows, dtype=np.int32).reshape(-1, 2)
+
+
+def match_graph(features, pairs, ratio=0.7, info=None):
+    """Hamming matches under Lowe's 2-nearest ratio test for the pairs of a PAIR GRAPH in one GPU submission, handed over as the
+    `DeviceProblems` that `run_batch` takes: the matcher in front of `sequence_graph`, where most proposed pairs do not overlap.
+    `match_batch`'s cross-check gives nearly every train row a partner, overlap or not, and `sequence_graph`'s
+    inliers > 8 + 0.3 matches pays for that ballast; the ratio test leaves the matches that have support.
+
+    features: the list `extract_batch` returns, one (kps float32 [N_k, 2], desc uint8 [N_k, nbytes]) per IMAGE, numpy arrays or
+    tensors, one nbytes (1 .. 64) throughout.  pairs: a list of (s, d): image s is the query side, image d the train side, H will
+    map s into d; s == d and repeats are allowed.  ratio: a float in (0, 1], taken as Fraction(ratio).limit_denominator(1024) (0.7
+    is 7 / 10), or integers (num, den) (`match_ratio`).  ValueError for another ratio or pair list, before the GPU is asked for.
+
+    The ratio rule (include/rwh.h, rwh_match_ratio_graph): D[i, j] = popcount(A[i] xor B[j]); d1[i], j1[i] the nearest train row of
+    query i and d2[i] the nearest of the others; i is a candidate iff den d1 < num d2 (integers, strict: a tie for the nearest is
+    never a candidate); of the candidates of one train row the one with the smallest d1 survives (lowest i on ties); the matches
+    are ordered by (d1, i).  Lowe's ratio test plus a uniqueness step; held to this statement, NOT to OpenCV.
+
+    The descriptors are concatenated ONCE PER IMAGE and every pair reads them in place (`match_batch` copies them per pair).
+    Ordering, compaction and the keypoint gather are `match_batch`'s tensor operations, and the one download is the P match counts.
+    `info`: optional dict, receives "query_idx", "train_idx" (int32 device tensors, indices inside the pair's images, in the order of
+    the correspondences), "distance" and "second" (d1 and d2)."""
+    num, den = match_ratio(ratio)
+    n = len(features)
+    if n == 0:
+        raise ValueError("match_graph: no images")
+    pr = _check_graph_pairs(pairs, n, "match_graph")
+    import torch
+    dev = _lib.require_gpu()
+    kps = [_to_device(f[0], torch.float32, dev, "kps").reshape(-1, 2) for f in features]
+    desc = [_to_device(f[1], torch.uint8, dev, "desc") for f in features]
+    if any(t.dim() != 2 for t in desc) or len(set(int(t.shape[1]) for t in desc)) != 1:
+        raise ValueError("match_graph: descriptors must be uint8 [rows, nbytes] with one nbytes for every image")
+    for k in range(n):
+        if kps[k].shape[0] != desc[k].shape[0]:
+            raise ValueError("match_graph: image %d has %d keypoints for %d descriptors" % (k, kps[k].shape[0], desc[k].shape[0]))
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum([t.shape[0] for t in desc])
+    P = pr.shape[0]
+    off_q = np.zeros(P + 1, dtype=np.int64)
+    off_q[1:] = np.cumsum((off[1:] - off[:-1])[pr[:, 0]])
+    if off[-1] >= 2 ** 31 or off_q[-1] >= 2 ** 31:
+        raise ValueError("match_graph: too many rows for one submission")
+    train, dist, second = kernels.match_ratio_graph(torch.cat(desc), off.astype(np.int32), pr, (num, den))
+    order, q_local, t_local, p_of, sizes = _ordered_matches(train, dist, torch.from_numpy(off_q).to(dev), int(off_q[-1]), P)
+    kps_all = torch.cat(kps)
+    first = torch.from_numpy(off[:-1][pr.astype(np.int64)]).to(dev)            # [P, 2]: the first row of the pair's images
+    if info is not None:
+        info["query_idx"], info["train_idx"] = q_local.to(torch.int32), t_local.to(torch.int32)
+        info["distance"], info["second"] = dist[order], second[order]
+    return _device_problems(kps_all[first[p_of, 0] + q_local], kps_all[first[p_of, 1] + t_local], sizes)
+
+
+def match_descriptors_ratio(descA, descB, ratio=0.7):
+    """One pair through `match_graph`'s matcher: descA [Na, nbytes], descB [Nb, nbytes] uint8 (numpy or tensors; query and train
+    side) -> (queryIdx, trainIdx, distance, second), int32 numpy arrays ordered by (distance, queryIdx), under the ratio rule stated
+    at `match_graph`."""
+    import torch
+    info = {}
+    na, nb = int(descA.shape[0]), int(descB.shape[0])
+    match_graph([(torch.zeros((na, 2), dtype=torch.float32), descA), (torch.zeros((nb, 2), dtype=torch.float32), descB)], [(0, 1)],
+                ratio=ratio, info=info)
+    both = torch.stack([info["query_idx"], info["train_idx"], info["distance"], info["second"]]).cpu().numpy()
+    return both[0].copy(), both[1].copy(), both[2].copy(), both[3].copy()
 
 
 def match_descriptors(descA, descB):

@@ -521,6 +521,79 @@ def match_hamming_batched(desc_a, desc_b, offsets_a, offsets_b):
     return train_idx, distance
 
 
+# the ratio matcher's block shape (include/rwh.h, the ratio rule): query rows per block, train rows staged in LDS at a time, train
+# rows per block
+MATCH2_TILE_QUERY, MATCH2_CHUNK_TRAIN, MATCH2_SEG_TRAIN = _lib.RWH_MATCH2_TILE_QUERY, _lib.RWH_MATCH2_CHUNK_TRAIN, _lib.RWH_MATCH2_SEG_TRAIN
+MATCH2_RATIO_MAX = _lib.RWH_MATCH2_RATIO_MAX
+
+
+def match_ratio_rows(image_offsets, pairs, total_rows):
+    """The rows of every pair of a graph, on the host, as rwh_match_ratio_graph counts them: image_offsets int [N + 1], pairs int
+    [P, 2] of (s, d) -> (na, nb), int64 [P] each.  An image outside 0 .. N - 1, or one whose range is not inside [0, total_rows], has
+    no rows."""
+    off = np.asarray(image_offsets, dtype=np.int64)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n = off.shape[0] - 1
+    o0, o1 = off[:-1], off[1:]
+    rows = np.where((o0 >= 0) & (o1 >= o0) & (o1 <= total_rows), o1 - o0, 0)
+    inside = (pr >= 0) & (pr < n)
+    both = np.where(inside, rows[np.clip(pr, 0, n - 1)], 0)
+    return both[:, 0], both[:, 1]
+
+
+def match_ratio_graph(desc, image_offsets, pairs, ratio=(7, 10)):
+    """Hamming matches under the 2-nearest ratio test for the P pairs of a pair graph in one library call (rwh_match_ratio_graph;
+    the ratio rule and its provenance in include/rwh.h).  Every image's descriptors are read where they lie: nothing is copied per pair.
+
+    desc [total_rows, nbytes] uint8 on the GPU (the images' descriptors concatenated); image_offsets [N + 1] int32, image k owns rows
+    image_offsets[k] .. image_offsets[k + 1] - 1; pairs [P, 2] int32 of (s, d): query image, train image.  The two tables are numpy
+    arrays or tensors; the output's length is counted from them on the host, so tables that live on the GPU are downloaded for
+    that.  ratio = (num, den), integers with 0 < num <= den <= MATCH2_RATIO_MAX.  Returns (train_idx, distance, second), int32
+    [sum of the pairs' query rows] each on the GPU: per (pair, query row), in pair order, its match's row inside image d, the
+    distance and the second-nearest distance, -1 / -1 / -1 for no match.  nbytes outside 1 .. MATCH_MAX_BYTES: NotImplementedError."""
+    lib = _lib.load()
+    _dev_check(desc)
+    if not (desc.dtype == torch.uint8 and desc.dim() == 2):
+        raise ValueError("descriptors: a uint8 [rows, nbytes] tensor, got %s %s" % (desc.dtype, tuple(desc.shape)))
+    tables = []
+    for t, what in ((image_offsets, "image_offsets"), (pairs, "pairs")):
+        t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))
+        if t.dtype != torch.int32:
+            raise ValueError("%s: an int32 table, got %s" % (what, t.dtype))
+        tables.append(t)
+    off, pr = tables
+    if not (off.dim() == 1 and off.shape[0] >= 2 and pr.dim() == 2 and pr.shape[1] == 2 and pr.shape[0] >= 1):
+        raise ValueError("image_offsets: int32 [N + 1], N >= 1; pairs: int32 [P, 2], P >= 1; got %s and %s" % (tuple(off.shape), tuple(pr.shape)))
+    try:
+        num, den = (int(v) for v in ratio)
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in ratio) and 0 < num <= den <= MATCH2_RATIO_MAX
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("ratio=%r; two integers (num, den) with 0 < num <= den <= %d" % (ratio, MATCH2_RATIO_MAX))
+    total_rows, nbytes = desc.shape
+    if nbytes == 0:         # rows without bytes have no address to hand over: the library's answer for this length, given here
+        raise NotImplementedError("match: descriptors of 0 bytes; the matcher takes 1 .. %d" % MATCH_MAX_BYTES)
+    na, nb = match_ratio_rows(off.cpu().numpy(), pr.cpu().numpy(), total_rows)
+    total_query, total_train, max_train = int(na.sum()), int(nb.sum()), int(nb.max())
+    if total_query >= 2 ** 31 or total_train >= 2 ** 31:
+        raise ValueError("match: too many rows for one submission")
+    dev = desc.device
+    off, pr = off.to(dev).contiguous(), pr.to(dev).contiguous()
+    n_images, n_pairs = off.shape[0] - 1, pr.shape[0]
+    out = [torch.empty((total_query,), dtype=torch.int32, device=dev) for _ in range(3)]
+    ws_bytes = int(lib.rwh_match_ratio_workspace_bytes(n_pairs, total_query, total_train, max_train))
+    if ws_bytes < 0:
+        check(ws_bytes, "rwh_match_ratio_workspace_bytes")
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
+    status = lib.rwh_match_ratio_graph(_ptr(desc), nbytes, _ptr(off), n_images, total_rows, _ptr(pr), n_pairs, total_query, total_train,
+                                       num, den, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws_bytes, _lib.stream_ptr())
+    if status == _lib.RWH_E_UNSUPPORTED:
+        raise NotImplementedError("match: descriptors of %d bytes; the matcher takes 1 .. %d" % (nbytes, MATCH_MAX_BYTES))
+    check(status, "rwh_match_ratio_graph")
+    return tuple(out)
+
+
 # the extractor's constants (include/rwh.h): border of a keypoint's centre, orientation bins, radius of the test points, the
 # detector's tile -- for callers and tests that plant corners across tile seams
 ORB_BORDER, ORB_BINS, ORB_TEST_RADIUS = _lib.RWH_ORB_BORDER, _lib.RWH_ORB_BINS, _lib.RWH_ORB_TEST_RADIUS

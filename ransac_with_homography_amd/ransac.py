@@ -38,8 +38,8 @@ unless an earlier one took the early exit, a winner with fewer inliers than the 
 each with numpy's generator left where the reference leaves it.
 
 `run_batch` is the same search for MANY pairs in one submission; `stitching` and `stitch_sequence` are the pipelines around it.
-The stage in front of the search -- the feature extractor and the Hamming matcher (`extract_batch`, `match_batch`, their tables, the
-hand-off type `DeviceProblems`) -- lives in `features.py`; its public names are imported here: this module stays the call surface.
+The stage in front of the search -- the feature extractor and the Hamming matchers (`extract_batch`, `match_batch` with cross-check,
+`match_graph` with the ratio test over a pair graph, their tables, the hand-off type `DeviceProblems`) -- lives in `features.py`; its public names are imported here: this module stays the call surface.
 
 There is no CPU implementation of the loop here: without librwh_hip.so and a GPU
 `RANSAC.run` raises `RwhUnavailable`.
@@ -51,7 +51,8 @@ import numpy as np
 
 from . import _lapack, _lib, kernels
 from .features import (DeviceProblems, _host_rows, default_pattern, detect_and_describe, extract_batch, match_batch,  # noqa: F401
-                       match_descriptors, orb_bin_table, orb_layout, orb_level_quotas, orb_scales, rotate_pattern)
+                       match_descriptors, match_descriptors_ratio, match_graph, match_ratio, orb_bin_table, orb_layout,
+                       orb_level_quotas, orb_scales, rotate_pattern)
 from .homography import (_check_bands, _check_pairs, _check_projection, _oriented, _pair_rows, _sequence_inputs, calcHomography,  # noqa: F401
                          calcHomographyLinear, cylindericlMap, sequence_adjust, sequence_focal, sequence_gains, sequence_graph,
                          sequence_plan, stitchPanorama, stitchSequence)
@@ -797,8 +798,18 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     staying on the device.  The canvas comes from `stitchSequence(images, Gs=...)`.  `info` then receives "pairs", "accepted"
     (bool per pair), "tree" and "adjust" (`sequence_adjust`'s info, or None); "Hs" is set only with pairs="adjacent".  The
     defaults make the calls and give the results they always did.  `bands` stays the last parameter: pass it, and everything
-    behind `focal`, by name.  ValueError, before the GPU is asked for: another `pairs` or `adjust`."""
+    behind `focal`, by name.  ValueError, before the GPU is asked for: another `pairs` or `adjust`.
+
+    The matcher.  A key "ratio" in the `features` dict (features={"ratio": 0.7, "n_levels": 4}) is taken out before the rest goes to
+    `extract_batch`: the pairs -- adjacent or of the graph -- are then matched by `match_graph(feats, pairs, ratio)`, Lowe's ratio
+    test with every image's descriptors held once, in place of `match_batch`'s cross-check.  With pairs="all" that is the matcher to
+    use: cross-check's unsupported matches raise the bar of `sequence_graph`'s acceptance rule and can cost a true overlap.
+    Without the key every call and result is what it was.  ValueError, before any GPU work: a ratio `match_ratio` refuses."""
     n = len(images)
+    ratio = None
+    if isinstance(features, dict) and "ratio" in features:
+        features = dict(features)
+        ratio = match_ratio(features.pop("ratio"), "stitch_sequence")
     if not 1 <= n <= _lib.RWH_SEQ_MAX_IMAGES:
         raise ValueError("stitch_sequence: %d images; 1 .. %d are taken" % (n, _lib.RWH_SEQ_MAX_IMAGES))
     if not isinstance(adjust, (bool, np.bool_)):
@@ -822,11 +833,14 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     _check_projection("stitch_sequence", projection, 1.0 if auto_focal else focal)
     if graph:
         return _stitch_sequence_graph(images, anchor, dict(th=th, d=d, n=4, k=k, method=ransacMet, seed=seed), blending, features, info, gains,
-                                      projection, focal, auto_focal, bands, pairs, adjust)
+                                      projection, focal, auto_focal, bands, pairs, adjust, ratio)
     Hs, sizes, inliers = np.zeros((0, 3, 3)), [], []
     if n > 1:
         feats = extract_batch(images, **(features or {}))
-        pairs = match_batch([(feats[i + 1][0], feats[i + 1][1], feats[i][0], feats[i][1]) for i in range(n - 1)])
+        if ratio is None:
+            pairs = match_batch([(feats[i + 1][0], feats[i + 1][1], feats[i][0], feats[i][1]) for i in range(n - 1)])
+        else:
+            pairs = match_graph(feats, [(i + 1, i) for i in range(n - 1)], ratio)
         sizes = [int(m) for m in pairs.sizes]
         # (run_batch brings the [N - 1, 3, 3] homographies and their refit status down in ONE copy; a pair without one gives None)
         res = run_batch(pairs, th=th, d=d, n=4, k=k, method=ransacMet, seed=seed, refit="device")
@@ -851,9 +865,10 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     return out
 
 
-def _stitch_sequence_graph(images, anchor, search, blending, features, info, gains, projection, focal, auto_focal, bands, pairs, adjust):
-    """`stitch_sequence` over a pair graph: one extract, one match and one search over the listed pairs, `sequence_graph`, with
-    adjust=True `sequence_adjust` on the device, then `stitchSequence(Gs=...)`."""
+def _stitch_sequence_graph(images, anchor, search, blending, features, info, gains, projection, focal, auto_focal, bands, pairs, adjust,
+                           ratio=None):
+    """`stitch_sequence` over a pair graph: one extract, one match (`match_batch`, or `match_graph` with a ratio) and one search over
+    the listed pairs, `sequence_graph`, with adjust=True `sequence_adjust` on the device, then `stitchSequence(Gs=...)`."""
     n = len(images)
     adjacent = isinstance(pairs, str) and pairs == "adjacent"
     if isinstance(pairs, str):
@@ -861,7 +876,10 @@ def _stitch_sequence_graph(images, anchor, search, blending, features, info, gai
     Hs, sizes, inliers, masks, problems = [], [], [], None, None
     if pairs:
         feats = extract_batch(images, **(features or {}))
-        problems = match_batch([(feats[s][0], feats[s][1], feats[d][0], feats[d][1]) for s, d in pairs])
+        if ratio is None:
+            problems = match_batch([(feats[s][0], feats[s][1], feats[d][0], feats[d][1]) for s, d in pairs])
+        else:
+            problems = match_graph(feats, pairs, ratio)
         sizes = [int(m) for m in problems.sizes]
         found = {}
         res = run_batch(problems, refit="device", info=found, **search)

@@ -1,0 +1,231 @@
+"""The ratio rule (include/rwh.h, rwh_match_ratio_graph) without a GPU: rwh_host_match_ratio against the numpy restatement of
+tests/match_ratio_cases.py -- exact equality -- on every shape, descriptor length and ratio of the suite and on hand-made cases;
+what the rule is for (unrelated sets, planted partners among distractors, the three crops of the sequence tests); the error codes
+of the two entry points and the Python layer's argument handling that is reached before the GPU."""
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import match_cases as mc
+import match_ratio_cases as rc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from ransac_with_homography_amd import _lib
+    return _lib.load()
+
+
+def _same(lib, A, B, num=7, den=10):
+    got = rc.host_match(lib, A, B, num, den)
+    want = rc.per_query(A, B, num, den)
+    assert got[0] == 0 and all(np.array_equal(g, w) and g.dtype == np.int32 for g, w in zip(got[1:], want)), (A.shape, B.shape, num, den)
+    return got[1:]
+
+
+@pytest.mark.parametrize("nbytes", mc.NBYTES)
+@pytest.mark.parametrize("na,nb", mc.SHAPES)
+def test_host_twin_equals_restatement(lib, na, nb, nbytes):
+    A, B = mc.random_pair(na, nb, nbytes, seed=1000 * na + nb + nbytes)
+    for num, den in rc.RATIOS:
+        _same(lib, A, B, num, den)
+    if min(na, nb) >= 63 and nbytes in (1, 32, 61):         # no branch of the rule is left out: each is taken on these inputs
+        cand, ties, dropped = rc.candidates(A, B, 7, 10)
+        assert cand > 0 and ties > 0 and dropped > 0, (cand, ties, dropped)
+
+
+def _pair_with_distances(d_first, d_second, nbytes=32):
+    """Query 0 at d_first from train row 0 and d_second from train row 1; query 1 far from both."""
+    rng = np.random.RandomState(8)
+    a0 = rng.randint(0, 256, nbytes).astype(np.uint8)
+    A = np.stack([a0, ~a0])
+    B = np.stack([mc.flip(a0, range(d_first)), mc.flip(a0, range(100, 100 + d_second))])
+    assert mc.distances(A, B)[0].tolist() == [d_first, d_second]
+    return A, B
+
+
+def test_hand_made_cases(lib):
+    rng = np.random.RandomState(2)
+    A = rng.randint(0, 256, (5, 32)).astype(np.uint8)
+    for nb in (0, 1):                                       # no second distance: no match, whatever the ratio
+        for num, den in rc.RATIOS:
+            t, d, s = _same(lib, A, A[:nb], num, den)
+            assert t.tolist() == d.tolist() == s.tolist() == [-1] * 5
+    assert all(o.size == 0 for o in _same(lib, A[:0], A))   # no query rows is legal
+    # den d1 == num d2 exactly is rejected (strict); one more bit on the runner-up is kept
+    t, d, s = _same(lib, *_pair_with_distances(7, 10))
+    assert t.tolist() == [-1, -1]
+    t, d, s = _same(lib, *_pair_with_distances(7, 11))
+    assert (t[0], d[0], s[0]) == (0, 7, 11) and t[1] == -1
+    t, d, s = _same(lib, *_pair_with_distances(7, 10), num=1, den=1)
+    assert (t[0], d[0], s[0]) == (0, 7, 10)
+    # d1 == d2 == 0: a tie, never a candidate
+    for num, den in rc.RATIOS:
+        t, _, _ = _same(lib, A[:1], np.stack([A[0], A[0]]), num, den)
+        assert t.tolist() == [-1]
+    # two identical queries over one near train row: the lower index keeps it
+    Q = np.stack([A[1], A[0], A[0]])
+    B = np.stack([mc.flip(A[0], [3]), A[4]])
+    t, d, s = _same(lib, Q, B)
+    assert t.tolist() == [-1, 0, -1] and d[1] == 1 and s[1] == int(mc.distances(Q, B)[1, 1])
+    # ... and the smaller d1 wins over the lower index
+    Q = np.stack([mc.flip(A[0], [3, 4, 5]), A[0]])
+    t, d, s = _same(lib, Q, B)
+    assert t.tolist() == [-1, 0] and d[1] == 1
+
+
+def test_unrelated_sets_give_next_to_nothing(lib):
+    A, B = rc.unrelated_sets()
+    cross = int((mc.per_query(A, B)[0] >= 0).sum())
+    ratio = int((_same(lib, A, B)[0] >= 0).sum())
+    print("unrelated 300 x 300 x 32 bytes: cross-check %d matches, ratio 7/10 %d" % (cross, ratio))
+    assert cross > 100 and 10 * ratio < cross
+
+
+def test_planted_partners_among_distractors(lib, matches):
+    _, desc_a, _, desc_b, truth = rc.planted_features(matches)
+    assert desc_a.shape == desc_b.shape == (300, 32) and len(truth) == 185
+    t, d, s = _same(lib, desc_a, desc_b)
+    got = set((int(i), int(t[i])) for i in np.nonzero(t >= 0)[0])
+    ci, cj, _ = mc.oracle(desc_a, desc_b)
+    cross = set(zip(ci.tolist(), cj.tolist()))
+    print("185 planted among 115 distractors a side: ratio 7/10 %d matches (%d planted); cross-check %d (%d false)"
+          % (len(got), len(got & truth), len(cross), len(cross - truth)))
+    assert got == truth and int(d.max()) <= 19
+    assert truth <= cross and len(cross) > len(truth)       # cross-check keeps the planted set and adds unsupported matches
+
+
+def test_three_crops(lib):
+    """The crops of the sequence tests through the host extractor: the ratio rule keeps the true matches and drops the ballast, and
+    the 80-pixel overlap (2, 0) passes the acceptance rule true > 8 + 0.3 matches that it fails under cross-check."""
+    import orb_cases as oc
+    feats = []
+    for img in rc.crops():
+        st, f = oc.host_extract(lib, img)
+        assert st == 0 and len(f["kps"]) > 50
+        feats.append((f["kps"], f["desc"]))
+    counts = rc.crop_counts(feats)
+    for pair in rc.CROP_PAIRS:
+        (cm, ct), (rm, rt) = counts[pair]["cross"], counts[pair]["ratio"]
+        print("crops %s: cross-check %d matches / %d true, ratio 7/10 %d / %d" % (pair, cm, ct, rm, rt))
+        assert 10 * rt >= 9 * rm and 10 * rt >= 9 * ct
+    (cm, ct), (rm, rt) = counts[(2, 0)]["cross"], counts[(2, 0)]["ratio"]
+    assert rt > 8 + 0.3 * rm and not ct > 8 + 0.3 * cm
+
+
+def test_error_codes(lib):
+    """RWH_E_INVALID / RWH_E_UNSUPPORTED before any device is touched (this runs without one)."""
+    A = np.zeros((4, 32), dtype=np.uint8)
+    out = np.zeros(4, dtype=np.int32)
+    good = [A.ctypes.data, 4, A.ctypes.data, 4, 32, 7, 10, out.ctypes.data, out.ctypes.data, out.ctypes.data]
+    assert lib.rwh_host_match_ratio(*good) == 0
+    for i, v in [(k, mc.null) for k in (0, 2, 7, 8, 9)] + [(1, -1), (3, -1), (5, 0), (5, -1), (5, 11), (6, 1025), (6, 0)]:
+        bad = list(good)
+        bad[i] = v
+        assert lib.rwh_host_match_ratio(*bad) == -1, (i, v)
+    for nbytes in (0, 65, -1):
+        bad = list(good)
+        bad[4] = nbytes
+        assert lib.rwh_host_match_ratio(*bad) == -2
+    assert lib.rwh_host_match_ratio(A.ctypes.data, 4, A.ctypes.data, 4, 32, 1024, 1024, *good[7:]) == 0
+    # workspace: owner[total_train], four tables of P + 1, one partial per query row and segment of the longest train side
+    need = lib.rwh_match_ratio_workspace_bytes(2, 10, 600, 300)
+    assert need == 8 * (600 + 4 * 3 + 10 * 2)
+    assert lib.rwh_match_ratio_workspace_bytes(2, 10, 600, 0) == lib.rwh_match_ratio_workspace_bytes(2, 10, 600, 256) == 8 * (600 + 12 + 10)
+    for bad in ((0, 1, 1, 1), (-1, 1, 1, 1), (1, -1, 1, 1), (1, 1, -1, 1), (1, 1, 1, -1)):
+        assert lib.rwh_match_ratio_workspace_bytes(*bad) == -1
+    one = 8                 # non-NULL, 8-byte aligned, never dereferenced: validation comes first
+    good = [one, 32, one, 3, 900, one, 2, 10, 600, 7, 10, one, one, one, one, need, mc.null]
+    for i in (0, 2, 5, 11, 12, 13, 14):
+        bad = list(good)
+        bad[i] = mc.null
+        assert lib.rwh_match_ratio_graph(*bad) == -1, i
+    small = 8 * (600 + 12 + 10) - 1
+    for i, v in ((3, 0), (3, -1), (4, -1), (6, 0), (6, -1), (7, -1), (8, -1), (9, 0), (9, 11), (10, 1025), (15, small), (14, 12)):
+        bad = list(good)
+        bad[i] = v
+        assert lib.rwh_match_ratio_graph(*bad) == -1, (i, v)
+    for nbytes in (0, 65, -1):
+        bad = list(good)
+        bad[1] = nbytes
+        assert lib.rwh_match_ratio_graph(*bad) == -2
+    # no query rows: nothing to do and no device is touched
+    assert lib.rwh_match_ratio_graph(one, 32, one, 3, 900, one, 2, 0, 600, 7, 10, mc.null, mc.null, mc.null, one, 1 << 20, mc.null) == 0
+
+
+def test_python_constants_match_the_header(lib):
+    from ransac_with_homography_amd import _lib, kernels
+    hdr = open(os.path.join(ROOT, "include", "rwh.h")).read()
+    for name in ("RWH_MATCH2_TILE_QUERY", "RWH_MATCH2_CHUNK_TRAIN", "RWH_MATCH2_SEG_TRAIN", "RWH_MATCH2_RATIO_MAX"):
+        assert int(re.search(r"#define %s\s+(\d+)" % name, hdr).group(1)) == getattr(_lib, name)
+    assert (kernels.MATCH2_TILE_QUERY, kernels.MATCH2_CHUNK_TRAIN, kernels.MATCH2_SEG_TRAIN) == \
+        (_lib.RWH_MATCH2_TILE_QUERY, _lib.RWH_MATCH2_CHUNK_TRAIN, _lib.RWH_MATCH2_SEG_TRAIN)
+    assert kernels.MATCH2_SEG_TRAIN % kernels.MATCH2_CHUNK_TRAIN == 0
+    assert lib.rwh_abi_version() == 5
+    na, nb = kernels.match_ratio_rows([0, 3, 3, 10, 99], [(0, 2), (2, 0), (1, 1), (4, 0), (0, -1), (3, 0)], 10)
+    assert na.tolist() == [3, 7, 0, 0, 3, 0] and nb.tolist() == [7, 3, 0, 3, 0, 3]
+
+
+def test_ratio_is_taken_as_a_fraction():
+    from ransac_with_homography_amd import ransac as rs
+    assert rs.match_ratio(0.7) == (7, 10) and rs.match_ratio(np.float32(0.5)) == (1, 2) and rs.match_ratio(1.0) == (1, 1)
+    assert rs.match_ratio(0.8) == (4, 5) and rs.match_ratio(1.0 / 3.0) == (1, 3) and rs.match_ratio(0.001) == (1, 1000)
+    assert rs.match_ratio((7, 10)) == (7, 10) and rs.match_ratio([3, 3]) == (3, 3) and rs.match_ratio((1, 1024)) == (1, 1024)
+    num, den = rs.match_ratio(0.123456789)
+    assert 0 < num <= den <= 1024 and abs(num / den - 0.123456789) < 1.0 / 1024
+    for bad in (0.0, -0.5, 1.5, float("nan"), 1e-9, 1, True, "0.7", None, (0, 10), (11, 10), (7, 1025), (7.0, 10), (7, 10, 1), (True, 1)):
+        with pytest.raises(ValueError):
+            rs.match_ratio(bad)
+
+
+def test_value_errors_come_before_the_gpu():
+    """These raise ValueError on a machine without a GPU, where everything behind the argument checks raises RwhUnavailable."""
+    from ransac_with_homography_amd import ransac as rs
+    A = np.zeros((4, 32), dtype=np.uint8)
+    feats = [(np.zeros((4, 2), np.float32), A)] * 3
+    for bad in (1.5, (11, 10), "x"):
+        with pytest.raises(ValueError):
+            rs.match_graph(feats, [(1, 0)], ratio=bad)
+        with pytest.raises(ValueError):
+            rs.match_descriptors_ratio(A, A, ratio=bad)
+    for bad in ([], [(0, 3)], [(-1, 0)], [(0,)], [(0.0, 1)], 7, None, [(0, 1, 2)]):
+        with pytest.raises(ValueError):
+            rs.match_graph(feats, bad)
+    with pytest.raises(ValueError):
+        rs.match_graph([], [(0, 0)])
+    imgs = [np.zeros((40, 40, 3), dtype=np.uint8)] * 3
+    for bad in (0.0, 2.0, (7, 5), "0.7", None):
+        for kw in (dict(), dict(pairs="all"), dict(adjust=True)):
+            with pytest.raises(ValueError, match="ratio"):
+                rs.stitch_sequence(imgs, features={"ratio": bad, "n_levels": 2}, **kw)
+    given = {"ratio": 1.5, "n_levels": 2}
+    with pytest.raises(ValueError):
+        rs.stitch_sequence(imgs, features=given)
+    assert given == {"ratio": 1.5, "n_levels": 2}            # the caller's dict is not touched
+
+
+def test_entry_points_need_a_gpu():
+    import torch
+    if torch.cuda.is_available():
+        return              # with a GPU these calls succeed: tests/test_match_ratio_gpu.py
+    from ransac_with_homography_amd import ransac as rs
+    from ransac_with_homography_amd import RwhUnavailable
+    A = np.zeros((4, 32), dtype=np.uint8)
+    with pytest.raises(RwhUnavailable):
+        rs.match_descriptors_ratio(A, A)
+    with pytest.raises(RwhUnavailable):
+        rs.match_graph([(np.zeros((4, 2), np.float32), A)], [(0, 0)], ratio=(7, 10))
+
+
+def test_stitch_sequence_keeps_its_parameters():
+    from ransac_with_homography_amd import ransac as rs
+    assert list(inspect.signature(rs.stitch_sequence).parameters) == [
+        "images", "anchor", "th", "d", "k", "ransacMet", "seed", "blending", "features", "info", "gains", "projection", "focal", "pairs",
+        "adjust", "bands"]
