@@ -1066,6 +1066,77 @@ RWH_API int rwh_host_bundle_blocks(const float* pts_a, const float* pts_b, const
 RWH_API int rwh_host_bundle_step(int n, int anchor, const int32_t* edges, int n_edges, const double* blocks, double lambda,
                                  double* out_delta, int32_t* out_status);
 
+/*
+ * Registration over rotations and focal lengths: the second model beside the bundle rule.  A camera that turns about its centre
+ * has three free parameters and a focal length where the bundle rule gives an image eight; here G_i = K_a R_i inv(K_i) with an
+ * actual rotation R_i, and the focal length is refined over every inlier (Brown & Lowe 2007, section 4; Szeliski 2006, section
+ * 5.1).  The reference has no counterpart; this is held to THE CAMERA RULE below.  The blocks are summed on the device, the small
+ * dense system is solved on the host, as for the bundle rule.
+ *
+ * The camera rule.
+ *   Geometry.  Image i has K_i = [[f_i, 0, cx_i], [0, f_i, cy_i], [0, 0, 1]] with (cx_i, cy_i) = ((w_i - 1) / 2, (h_i - 1) / 2), fixed
+ *     (the convention of the projection rule), and a rotation R_i; R_anchor is the identity exactly and is never updated.
+ *     G_i = K_a R_i inv(K_i) maps image i into the anchor's frame.  N, E and the edges as in the bundle rule.  An edge (s, d) carries
+ *     its EDGE RECORD of RWH_CAMERA_RECORD = 15 float64, made on the HOST: R = R_d^T R_s (row-major), then f_s, cx_s, cy_s, f_d,
+ *     cx_d, cy_d.  The library inverts nothing.
+ *   Parameterisation.  Four per image, a local update: R_i <- R_i exp([omega_i]x), f_i <- f_i (1 + phi_i).  To first order R_i
+ *     becomes R_i (I + [omega_i]x), which is all the blocks need; the exponential is the caller's.
+ *   Per correspondence a = (x, y) in s, b = (bx, by) in d, all in float64, nothing contracted except the fma written out:
+ *     x, y, bx, by: the float32 inputs converted.
+ *     u = (x - cx_s, y - cy_s, f_s).
+ *     v_i = fma(R[i][2], u2, fma(R[i][1], u1, R[i][0] * u0)), i = 0, 1, 2.
+ *     m0 = v0 / v2, m1 = v1 / v2.  q0 = fma(f_d, m0, cx_d), q1 = fma(f_d, m1, cy_d).  r0 = q0 - bx, r1 = q1 - by.
+ *     Valid iff v2 is finite and > 0 and q0 and q1 are finite.  An inlier that is not valid contributes nothing and sets its
+ *       edge's status to RWH_BUNDLE_BEHIND (the bundle rule's enum serves both rules).
+ *     J is 2 x 8: columns 0 .. 2 for omega_s, 3 for phi_s, 4 .. 6 for omega_d, 7 for phi_d.  Each column but the last has a dv:
+ *       omega_s,0: dv = R (e_0 x u): dv_i = fma(R[i][2], u1, R[i][1] * -u2)
+ *       omega_s,1: dv = R (e_1 x u): dv_i = fma(R[i][2], -u0, R[i][0] * u2)
+ *       omega_s,2: dv = R (e_2 x u): dv_i = fma(R[i][1], u0, R[i][0] * -u1)     (negations are exact; one rounded product, one fma)
+ *       phi_s:     dv = f_s R[:, 2]: dv_i = R[i][2] * u2
+ *       omega_d,0: dv = v x e_0 = (0, v2, -v1);  omega_d,1: dv = v x e_1 = (-v2, 0, v0);  omega_d,2: dv = v x e_2 = (v1, -v0, 0)
+ *       J[0][k] = (f_d * (dv0 - m0 * dv2)) / v2, J[1][k] = (f_d * (dv1 - m1 * dv2)) / v2: the product m dv2, the difference, the
+ *       product with f_d and the quotient, each rounded, in this order.  A zero component of dv is the operand +0.0; the
+ *       operations on it may as well be left out (x - m * 0 = x, 0 - t = -t), which changes at most the sign of a zero J entry,
+ *       and no block entry sees that: every accumulator starts from +0.0.
+ *       phi_d: J[0][7] = f_d * m0, J[1][7] = f_d * m1.
+ *   Per edge.  A block of RWH_CAMERA_BLOCK = 45 float64 -- the 36 entries of the upper triangle of S = sum J^T J (row-major:
+ *     S[0][0..7], S[1][1..7], ...), the 8 entries of g = sum J^T r, and c = sum r.r -- an int32 count of the rows summed and an int32
+ *     status, RWH_BUNDLE_OK or RWH_BUNDLE_BEHIND.  Masks, offsets, the rows that count and the empty edge: as the bundle rule's.
+ *   Summation order, part of the rule: the bundle rule's.  Four partial sums P0 .. P3 per entry, Pw over the rows with index = w
+ *     (mod 4) in increasing index (the index inside the edge, counting every row, masked or not), each from +0.0; one step is
+ *     acc = acc + (u0 * v0 + u1 * v1), both products rounded, then their sum, then the addition; the entry is
+ *     (P0 + P1) + (P2 + P3).  Rows that contribute nothing are skipped.  No atomics: a rerun gives the same bits, and device, host
+ *     twin and a numpy restatement agree exactly.
+ *   The step (host).  The unknowns are omega of every image but the anchor, 3 (N - 1) in image order, then the focal unknowns:
+ *     N of them, image i's at 3 (N - 1) + i (RWH_CAMERA_FOCAL_PER_IMAGE; the anchor's included), or one
+ *     (RWH_CAMERA_FOCAL_SHARED), to which the phi column of every image maps; the contributions add, so the cross term S[3][7] of
+ *     an edge then enters that diagonal entry twice.  A and g are built from zero by adding the blocks in edge order; the anchor's
+ *     omega rows and columns are dropped; lambda * A_ii is added to every diagonal entry (Marquardt scaling); A delta = -g is
+ *     solved by Cholesky, A = L L^T.  A pivot that is not a positive finite number (an image that no edge touches) or a non-finite
+ *     delta gives RWH_BUNDLE_SINGULAR and delta = 0.  delta is 4 N float64, (omega_0, omega_1, omega_2, phi) per image: the anchor's
+ *     omega is 0, and with one focal for all every image's phi holds the common value.
+ *
+ * rwh_camera_blocks: one launch for all edges, one workgroup of 256 lanes per edge.  Arguments as rwh_bundle_blocks', with
+ * d_records (E x 15 float64) in place of d_transfers and d_blocks E x 45 float64 -- all outputs written whole.  The rows of an edge
+ * are staged 128 at a time in LDS (18 values each, 19 doubles apart, a lane per row); then each of the four waves owns one partial
+ * and 45 of its 64 lanes one accumulator each, walking the staged rows in the stated order.  RWH_E_INVALID, before anything is
+ * launched: a NULL pointer, n_edges outside 1 .. RWH_BUNDLE_MAX_EDGES, mask_words <= 0.
+ * rwh_host_camera_blocks: the same operations in the same order on HOST memory; no device, works without a GPU.
+ * rwh_host_camera_step: the step (host only, plain C++; no LAPACK).  focals: RWH_CAMERA_FOCAL_SHARED or _PER_IMAGE; edges: n_edges x
+ * (s, d) int32; blocks: n_edges x 45; lambda finite and >= 0; out_delta: 4 n float64, always written; *out_status: RWH_BUNDLE_OK or
+ * RWH_BUNDLE_SINGULAR.  RWH_E_INVALID: what rwh_host_bundle_step refuses, or another value of focals.
+ */
+#define RWH_CAMERA_BLOCK 45
+#define RWH_CAMERA_RECORD 15
+enum { RWH_CAMERA_FOCAL_SHARED = 0, RWH_CAMERA_FOCAL_PER_IMAGE = 1 };
+RWH_API int rwh_camera_blocks(const float* d_pts_a, const float* d_pts_b, const int32_t* d_offsets, int n_edges, const uint64_t* d_masks,
+                              int mask_words, const double* d_records, double* d_blocks, int32_t* d_count, int32_t* d_status,
+                              void* stream);
+RWH_API int rwh_host_camera_blocks(const float* pts_a, const float* pts_b, const int32_t* offsets, int n_edges, const uint64_t* masks,
+                                   int mask_words, const double* records, double* blocks, int32_t* count, int32_t* status);
+RWH_API int rwh_host_camera_step(int n, int anchor, int focals, const int32_t* edges, int n_edges, const double* blocks, double lambda,
+                                 double* out_delta, int32_t* out_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,9 @@ RWH_SEQ_MAX_BANDS = 8         # the multi-band rule: most bands
 # the bundle rule: float64 values per edge block, most edges (64 * 63 / 2), the statuses of an edge and of a step
 RWH_BUNDLE_BLOCK, RWH_BUNDLE_MAX_EDGES = 153, 2016
 RWH_BUNDLE_OK, RWH_BUNDLE_BEHIND, RWH_BUNDLE_SINGULAR = 0, 1, 2
+# the camera rule: float64 values per edge block and per edge record, the two focal models of its step
+RWH_CAMERA_BLOCK, RWH_CAMERA_RECORD = 45, 15
+RWH_CAMERA_FOCAL_SHARED, RWH_CAMERA_FOCAL_PER_IMAGE = 0, 1
 RWH_TUNE_WARP_SHAPE, RWH_TUNE_SCORE_HPW, RWH_TUNE_SCORE_EXACT, RWH_TUNE_WARP_FRAMES = 0, 1, 2, 3
 
 # every symbol include/rwh.h declares (tests check the library exports them all)
@@ -58,7 +61,8 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_stitch_multiband_workspace_bytes", "rwh_stitch_multiband", "rwh_host_stitch_multiband",
            "rwh_stitch_sequence_proj", "rwh_host_stitch_sequence_proj", "rwh_sequence_overlap_stats_proj",
            "rwh_host_sequence_overlap_stats_proj", "rwh_stitch_multiband_proj", "rwh_host_stitch_multiband_proj",
-           "rwh_bundle_blocks", "rwh_host_bundle_blocks", "rwh_host_bundle_step")
+           "rwh_bundle_blocks", "rwh_host_bundle_blocks", "rwh_host_bundle_step",
+           "rwh_camera_blocks", "rwh_host_camera_blocks", "rwh_host_camera_step")
 
 # the two callbacks of rwh_settle_decide: interval(rows, n, coord_scale, lo, hi, user) and solve(rows, n, counts, user) -> status
 _I32P = ctypes.POINTER(ctypes.c_int32)
@@ -228,6 +232,13 @@ def _bind(lib):
     lib.rwh_host_bundle_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
     lib.rwh_host_bundle_step.restype = i32
     lib.rwh_host_bundle_step.argtypes = [i32, i32, vp, i32, vp, f64, vp, vp]            # n anchor edges n_edges blocks lambda delta status
+    # the camera rule: the same three calls over rotations and focal lengths
+    lib.rwh_camera_blocks.restype = i32
+    lib.rwh_camera_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]     # pts_a pts_b offsets n_edges masks words records blocks count status stream
+    lib.rwh_host_camera_blocks.restype = i32
+    lib.rwh_host_camera_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    lib.rwh_host_camera_step.restype = i32
+    lib.rwh_host_camera_step.argtypes = [i32, i32, i32, vp, i32, vp, f64, vp, vp]       # n anchor focals edges n_edges blocks lambda delta status
     return lib
 
 

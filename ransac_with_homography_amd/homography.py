@@ -56,6 +56,7 @@ __all__ = [
     "wrapPerspective", "wrapPerspectiveScan", "perspectiveTransform", "transformImage", "transformImageH",
     "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence", "sequence_gains",
     "sequence_ray_tables", "sequence_focal", "sequence_graph", "sequence_adjust",
+    "sequence_cameras", "sequence_camera_maps", "sequence_adjust_cameras",
 ]
 
 
@@ -1163,6 +1164,221 @@ def sequence_adjust(Gs, pairs, matches, masks=None, anchor=0, max_iters=20, on="
     if info is not None:
         info["cost"], info["iters"], info["lambda"] = history, iters, lam
     return Gs
+
+
+# ------------------------------------------- registration over rotations and focal lengths (the camera rule) ----
+def _nearest_rotation(A):
+    """U V^T of the SVD of A, the nearest rotation in the Frobenius norm (A has a positive determinant where this is called)."""
+    U, _, Vt = np.linalg.svd(A)
+    R = U @ Vt
+    if np.linalg.det(R) < 0:
+        R = U @ np.diag([1.0, 1.0, -1.0]) @ Vt
+    return R
+
+
+def _check_focal(who, focal):
+    if isinstance(focal, (bool, str)) or not isinstance(focal, (int, float, np.integer, np.floating)) or not (np.isfinite(focal) and focal > 0):
+        raise ValueError("%s: focal=%r; finite and > 0" % (who, focal))
+    return float(focal)
+
+
+def sequence_cameras(shapes, Gs, focal, anchor=0):
+    """Rotations and focal lengths from the maps of a sequence (the geometry of the camera rule, include/rwh.h); pure numpy.
+
+    shapes: N image shapes; Gs: N maps into the anchor's frame; focal: one focal length in pixels for every image.  With
+    K_i = `_camera(shapes[i], focal)`, A = inv(K_a) @ (G_i * sign(det G_i)) @ K_i is scaled to determinant 1 and R_i is the
+    rotation nearest to it (U V^T of its SVD); R_anchor is the identity exactly.  For maps that are K_a R_i inv(K_i) with this
+    focal the R_i come back to rounding.  Returns (Rs float64 [N, 3, 3], fs float64 [N], every entry `focal`).  ValueError: N or
+    anchor as `sequence_plan`'s, Gs of another shape, a determinant that is zero or not finite, a focal that is not finite and > 0."""
+    n = len(shapes)
+    _check_count(n, anchor)
+    f = _check_focal("sequence_cameras", focal)
+    mats = [np.asarray(G, dtype=np.float64) for G in Gs]
+    if len(mats) != n or any(G.shape != (3, 3) for G in mats):
+        raise ValueError("sequence_cameras: Gs takes %d 3 x 3 matrices" % n)
+    Gs = _oriented(mats)
+    kinv_a = np.linalg.inv(_camera(shapes[anchor], f))
+    Rs = np.empty((n, 3, 3))
+    for i in range(n):
+        A = kinv_a @ Gs[i] @ _camera(shapes[i], f)
+        with np.errstate(all="ignore"):
+            det = np.linalg.det(A)
+            A = A / np.cbrt(det)
+        if not (np.isfinite(A).all() and det > 0):
+            raise ValueError("sequence_cameras: image %d has a map without a rotation (focal %r)" % (i, f))
+        Rs[i] = _nearest_rotation(A)
+    Rs[anchor] = np.eye(3)
+    return Rs, np.full(n, f)
+
+
+def _check_cameras(who, shapes, Rs, fs, anchor):
+    n = len(shapes)
+    _check_count(n, anchor)
+    Rs = np.array([np.asarray(R, dtype=np.float64) for R in Rs])
+    fs = np.array(fs, dtype=np.float64).reshape(-1)
+    if Rs.shape != (n, 3, 3) or not np.array_equal(Rs[anchor], np.eye(3)):
+        raise ValueError("%s: Rs takes %d 3 x 3 rotations with the identity at the anchor" % (who, n))
+    if not np.isfinite(Rs).all():
+        raise ValueError("%s: a rotation that is not finite" % who)
+    if fs.shape != (n,) or not (np.isfinite(fs) & (fs > 0)).all():
+        raise ValueError("%s: fs takes %d focal lengths, finite and > 0" % (who, n))
+    return Rs, fs
+
+
+def sequence_camera_maps(shapes, Rs, fs, anchor=0):
+    """G_i = K_a R_i inv(K_i) (the geometry of the camera rule): the maps `stitchSequence(Gs=...)` takes, from rotations and focal
+    lengths; pure numpy.  Gs[anchor] is the identity exactly.  ValueError: N or anchor as `sequence_plan`'s, Rs that are not N
+    finite 3 x 3 matrices with the identity at the anchor, fs that are not N finite focal lengths > 0."""
+    Rs, fs = _check_cameras("sequence_camera_maps", shapes, Rs, fs, anchor)
+    Ka = _camera(shapes[anchor], fs[anchor])
+    Gs = np.stack([Ka @ R @ np.linalg.inv(_camera(shape, f)) for shape, R, f in zip(shapes, Rs, fs)])
+    Gs[anchor] = np.eye(3)
+    return Gs
+
+
+def _camera_records(shapes, Rs, fs, pairs):
+    """The edge records of the camera rule: R_d^T R_s row-major, then f_s, cx_s, cy_s, f_d, cx_d, cy_d: float64 [E, 15]."""
+    centre = [((int(shape[1]) - 1) / 2.0, (int(shape[0]) - 1) / 2.0) for shape in shapes]
+    return np.array([np.concatenate([(Rs[d].T @ Rs[s]).reshape(9), [fs[s], centre[s][0], centre[s][1], fs[d], centre[d][0], centre[d][1]]])
+                     for s, d in pairs])
+
+
+def _rodrigues(omega):
+    """exp([omega]x) by Rodrigues' formula; below 1e-8 rad the series I + K + K K / 2, which is exact to rounding there."""
+    theta = float(np.sqrt(omega @ omega))
+    K = np.array([[0.0, -omega[2], omega[1]], [omega[2], 0.0, -omega[0]], [-omega[1], omega[0], 0.0]])
+    if theta < 1e-8:
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (np.sin(theta) / theta) * K + ((1.0 - np.cos(theta)) / (theta * theta)) * (K @ K)
+
+
+def sequence_adjust_cameras(shapes, Rs, fs, pairs, matches, masks=None, anchor=0, focals="shared", max_iters=20, on="device", info=None):
+    """Bundle adjustment of a sequence over rotations and focal lengths (the camera rule of include/rwh.h): every R_i and the focal
+    length -- one for all images, or one per image -- refined jointly, by Levenberg-Marquardt, over the inlier correspondences of every
+    edge.  Four parameters per image where `sequence_adjust` has eight, and the maps stay those of a camera that turns about its
+    centre: G_i = K_a R_i inv(K_i) (`sequence_camera_maps`).
+
+    shapes: N image shapes; Rs, fs: N rotations (Rs[anchor] the identity) and N focal lengths, e.g. `sequence_cameras`'; pairs,
+    matches, masks, on: as `sequence_adjust`'s.  focals="shared": one focal unknown, every fs equal at the start and at the end;
+    focals="per-image": one per image, the anchor's included.  on="device": the edge blocks come from `kernels.camera_blocks` -- per
+    evaluation one upload of E x 15 doubles, one launch, one download; on="host": from the host twin, no GPU needed.  Both give
+    the same bits.
+
+    The loop is `sequence_adjust`'s, with its constants: the blocks at the current cameras, `rwh_host_camera_step` at the current
+    lambda, the candidate R_i exp([omega_i]x) (Rodrigues' formula, then U V^T of its SVD, so that it stays a rotation; the anchor
+    stays the identity) and f_i (1 + phi_i), the candidate's blocks.  The step is accepted iff every candidate focal is finite and
+    > 0, the candidate's cost (the sum of the edges' c) is strictly lower and no edge reports RWH_BUNDLE_BEHIND; then lambda <-
+    lambda / 10, else lambda <- 10 lambda.  It ends after `max_iters` accepted steps, at lambda > 1e12, or on an accepted step that
+    lowers the cost by less than 1e-12 of it.  A step whose system is singular raises on the first step tried (an image that no
+    edge touches is singular at every lambda); later it counts as a rejected step -- where the data leave the focal length open
+    (images that are translations of each other) the damping is all that keeps the system definite, and it shrinks with every
+    accepted step.  `info`: optional dict, receives "cost" (the start and every accepted step), "iters"
+    and "lambda".  Returns (Rs float64 [N, 3, 3], fs float64 [N]).  ValueError: bad n, anchor, pairs, on, focals or max_iters, Rs or
+    fs that `sequence_camera_maps` refuses, focals="shared" with fs that differ, matches or masks that do not fit the pairs, a
+    correspondence that is behind its camera at the start, a pair whose cost is not finite at the start (the pair is named), an
+    image that no edge with inliers touches."""
+    who = "sequence_adjust_cameras"
+    Rs, fs = _check_cameras(who, shapes, Rs, fs, anchor)
+    n = len(Rs)
+    pairs = _check_pairs(who, n, pairs)
+    E = len(pairs)
+    if on not in ("device", "host"):
+        raise ValueError("%s: on=%r; 'device' or 'host'" % (who, on))
+    if not (isinstance(focals, str) and focals in kernels.CAMERA_FOCALS):
+        raise ValueError("%s: focals=%r; 'shared' or 'per-image'" % (who, focals))
+    if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 0:
+        raise ValueError("%s: max_iters=%r; an integer >= 0" % (who, max_iters))
+    if focals == "shared" and not (fs == fs[0]).all():
+        raise ValueError("%s: focals='shared' takes equal focal lengths, got %r" % (who, fs.tolist()))
+    for i, shape in enumerate(shapes):
+        if len(shape) < 2:
+            raise ValueError("%s: shape %r of image %d; (h, w[, c])" % (who, shape, i))
+    if E < 1:
+        raise ValueError("%s: no pairs" % who)
+    from .features import DeviceProblems
+    on_dev = isinstance(matches, DeviceProblems)
+    sizes = list(matches.sizes) if on_dev else [int(np.asarray(a).reshape(-1, 2).shape[0]) for a, _ in matches]
+    if len(sizes) != E:
+        raise ValueError("%s: %d pairs take %d sets of matches, got %d" % (who, E, E, len(sizes)))
+    offsets = np.zeros(E + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(sizes)
+    words = max((max(sizes) + 63) // 64, 1)
+    tensor_masks = masks is not None and _is_tensor(masks)
+    if masks is None:
+        masks = np.full((E, words), -1, dtype=np.int64)
+    elif not tensor_masks:
+        masks = np.ascontiguousarray(masks)
+        if masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)) or masks.ndim != 2:
+            raise ValueError("%s: masks takes [E, words] uint64 or int64 words" % who)
+        masks = masks.view(np.int64)
+    if tuple(masks.shape)[0] != E or len(masks.shape) != 2 or masks.shape[1] < 1:
+        raise ValueError("%s: masks of shape %s for %d pairs" % (who, tuple(masks.shape), E))
+    if on == "device":
+        import torch
+        dev = _lib.require_gpu()
+        if on_dev:
+            pa, pb = matches.pts_a, matches.pts_b
+        else:
+            pa = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])).to(dev)
+            pb = torch.from_numpy(np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])).to(dev)
+        off_dev = torch.from_numpy(offsets).to(dev)
+        m_dev = (masks if tensor_masks else torch.from_numpy(masks)).to(dev).to(torch.int64).contiguous()
+
+        def evaluate(R, f):
+            return kernels.camera_split(kernels.camera_blocks(pa, pb, off_dev, m_dev, _camera_records(shapes, R, f, pairs)).cpu().numpy())
+    else:
+        if on_dev:
+            pa, pb = matches.pts_a.cpu().numpy(), matches.pts_b.cpu().numpy()
+        else:
+            pa = np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])
+            pb = np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])
+        m_host = masks.cpu().numpy() if tensor_masks else masks
+
+        def evaluate(R, f):
+            return kernels.host_camera_blocks(pa, pb, offsets, m_host, _camera_records(shapes, R, f, pairs))
+
+    blocks, _, status = evaluate(Rs, fs)
+    if (status != _lib.RWH_BUNDLE_OK).any():
+        e = int(np.nonzero(status != _lib.RWH_BUNDLE_OK)[0][0])
+        raise ValueError("%s: pair %d (images %d and %d) has an inlier behind the camera at the start" % ((who, e) + pairs[e]))
+    if not np.isfinite(blocks[:, -1]).all():
+        e = int(np.nonzero(~np.isfinite(blocks[:, -1]))[0][0])
+        raise ValueError("%s: pair %d (images %d and %d) has a cost that is not finite at the start (a correspondence that is not "
+                         "finite?)" % ((who, e) + pairs[e]))
+    cost = float(blocks[:, -1].sum())
+    history, lam, iters, tried = [cost], ADJUST_LAMBDA0, 0, 0
+    while iters < max_iters and lam <= ADJUST_LAMBDA_MAX:
+        delta, st = kernels.host_camera_step(n, anchor, pairs, blocks, lam, focals)
+        tried += 1
+        if st != _lib.RWH_BUNDLE_OK:
+            if tried == 1:
+                raise ValueError("%s: the step's system is singular (an image that no edge with inliers touches?)" % who)
+            # Later on it is the damping that has become too small for a direction the data do not determine (the focal length of
+            # images that are translations of each other): a rejected step, lambda goes up again.
+            lam *= ADJUST_LAMBDA_FACTOR
+            continue
+        with np.errstate(all="ignore"):
+            cf = fs * (1.0 + delta[:, 3])
+            accept = bool((np.isfinite(cf) & (cf > 0)).all()) and bool(np.isfinite(delta).all())
+            if accept:
+                cR = np.stack([Rs[i] if i == anchor else _nearest_rotation(Rs[i] @ _rodrigues(delta[i, :3])) for i in range(n)])
+        if accept:
+            cblocks, _, cstatus = evaluate(cR, cf)
+            ccost = float(cblocks[:, -1].sum())
+            accept = bool((cstatus == _lib.RWH_BUNDLE_OK).all()) and ccost < cost
+        if not accept:
+            lam *= ADJUST_LAMBDA_FACTOR
+            continue
+        small = cost - ccost < ADJUST_REL_STOP * cost
+        Rs, fs, blocks, cost = cR, cf, cblocks, ccost
+        history.append(cost)
+        iters += 1
+        lam /= ADJUST_LAMBDA_FACTOR
+        if small:
+            break
+    if info is not None:
+        info["cost"], info["iters"], info["lambda"] = history, iters, lam
+    return Rs, fs
 
 
 def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None):

@@ -481,6 +481,88 @@ def host_bundle_step(n, anchor, edges, blocks, lam):
     return delta, int(status[0])
 
 
+CAMERA_BLOCK, CAMERA_RECORD = _lib.RWH_CAMERA_BLOCK, _lib.RWH_CAMERA_RECORD
+CAMERA_FOCALS = {"shared": _lib.RWH_CAMERA_FOCAL_SHARED, "per-image": _lib.RWH_CAMERA_FOCAL_PER_IMAGE}
+
+
+def _camera_records(records, n_edges):
+    r = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, CAMERA_RECORD)
+    if r.shape[0] != n_edges or not 1 <= n_edges <= BUNDLE_MAX_EDGES:
+        raise ValueError("camera_blocks: %d records for %d edges; 1 .. %d edges, a record of %d doubles each"
+                         % (r.shape[0], n_edges, BUNDLE_MAX_EDGES, CAMERA_RECORD))
+    return r
+
+
+def camera_blocks(pts_a, pts_b, offsets, masks, records, out=None):
+    """The normal-equation blocks of every edge over rotations and focal lengths in one launch (rwh_camera_blocks; the camera rule of
+    include/rwh.h).
+
+    pts_a/pts_b, offsets, masks: as `bundle_blocks`', on the GPU; records: [E, 15] float64 on the HOST -- R_d^T R_s row-major, then
+    f_s, cx_s, cy_s, f_d, cx_d, cy_d (one upload of E x 15 doubles).  Returns one [E, 47] float64 tensor on the GPU: the 45 values of
+    each block, then the edge's count and status as float64, for ONE download (`camera_split` takes it apart).  out: optionally the
+    three tensors the library writes -- blocks [E, 45] float64, count [E] and status [E] int32, contiguous, on the GPU.  Edges
+    without any correspondence give zero blocks, as the host twin's.  Enqueued on torch's current stream."""
+    lib = _lib.load()
+    _dev_check(pts_a, pts_b, offsets, masks)
+    E = offsets.shape[0] - 1
+    assert pts_a.dtype == torch.float32 and pts_b.dtype == torch.float32 and offsets.dtype == torch.int32
+    assert masks.dtype == torch.int64 and masks.dim() == 2 and masks.shape[0] == E and tuple(pts_a.shape) == tuple(pts_b.shape)
+    r_dev = torch.from_numpy(_camera_records(records, E)).to(pts_a.device)
+    if pts_a.shape[0] == 0:
+        # as in bundle_blocks: one row that no edge's offsets reach stands in for tensors without an address
+        pts_a = pts_b = torch.zeros((1, 2), dtype=torch.float32, device=pts_a.device)
+    if out is None:
+        blocks = torch.empty((E, CAMERA_BLOCK), dtype=torch.float64, device=pts_a.device)
+        count, status = torch.empty((2, E), dtype=torch.int32, device=pts_a.device)
+    else:
+        blocks, count, status = out
+        _dev_check(blocks, count, status)
+        assert blocks.dtype == torch.float64 and tuple(blocks.shape) == (E, CAMERA_BLOCK)
+        assert count.dtype == torch.int32 and status.dtype == torch.int32 and tuple(count.shape) == (E,) and tuple(status.shape) == (E,)
+    check(lib.rwh_camera_blocks(_ptr(pts_a), _ptr(pts_b), _ptr(offsets), E, _ptr(masks), masks.shape[1], _ptr(r_dev), _ptr(blocks),
+                                _ptr(count), _ptr(status), _lib.stream_ptr()), "rwh_camera_blocks")
+    return torch.cat([blocks, count.to(torch.float64)[:, None], status.to(torch.float64)[:, None]], dim=1)
+
+
+def camera_split(packed):
+    """(blocks float64 [E, 45], count int32 [E], status int32 [E]) of a downloaded `camera_blocks` result (numpy)."""
+    packed = np.asarray(packed)
+    return (np.ascontiguousarray(packed[:, :CAMERA_BLOCK]), packed[:, CAMERA_BLOCK].astype(np.int32),
+            packed[:, CAMERA_BLOCK + 1].astype(np.int32))
+
+
+def host_camera_blocks(pts_a, pts_b, offsets, masks, records):
+    """The host twin of `camera_blocks` (rwh_host_camera_blocks): numpy arrays in, (blocks, count, status) numpy out, the same
+    operations in the same order.  Uses no device and works without a GPU."""
+    lib = _lib.load()
+    pts_a, pts_b = np.ascontiguousarray(pts_a, dtype=np.float32).reshape(-1, 2), np.ascontiguousarray(pts_b, dtype=np.float32).reshape(-1, 2)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    E = offsets.shape[0] - 1
+    masks = np.ascontiguousarray(masks).view(np.uint64).reshape(E, -1)
+    r = _camera_records(records, E)
+    if pts_a.shape != pts_b.shape or E < 1 or int(offsets[0]) != 0 or int(offsets[-1]) != pts_a.shape[0] or (np.diff(offsets) < 0).any():
+        raise ValueError("host_camera_blocks: offsets must run from 0 to the %d correspondences without decreasing" % pts_a.shape[0])
+    blocks = np.empty((E, CAMERA_BLOCK), dtype=np.float64)
+    count, status = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
+    check(lib.rwh_host_camera_blocks(pts_a.ctypes.data, pts_b.ctypes.data, offsets.ctypes.data, E, masks.ctypes.data, masks.shape[1],
+                                     r.ctypes.data, blocks.ctypes.data, count.ctypes.data, status.ctypes.data), "rwh_host_camera_blocks")
+    return blocks, count, status
+
+
+def host_camera_step(n, anchor, edges, blocks, lam, focals="shared"):
+    """One damped step from the edge blocks (rwh_host_camera_step, host only): -> (delta float64 [n, 4], status); a row of delta is
+    (omega_0, omega_1, omega_2, phi).  focals: "shared" (one focal unknown for all images) or "per-image"."""
+    lib = _lib.load()
+    if not (isinstance(focals, str) and focals in CAMERA_FOCALS):
+        raise ValueError("host_camera_step: focals=%r; 'shared' or 'per-image'" % (focals,))
+    edges = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    blocks = np.ascontiguousarray(blocks, dtype=np.float64).reshape(len(edges), CAMERA_BLOCK)
+    delta, status = np.empty((int(n), 4), dtype=np.float64), np.zeros(1, dtype=np.int32)
+    check(lib.rwh_host_camera_step(int(n), int(anchor), CAMERA_FOCALS[focals], edges.ctypes.data, len(edges), blocks.ctypes.data, float(lam),
+                                   delta.ctypes.data, status.ctypes.data), "rwh_host_camera_step")
+    return delta, int(status[0])
+
+
 # the matcher's block shape, for callers and tests that size problems across it: train rows per block, query rows staged in LDS at
 # a time, query rows per block (include/rwh.h)
 MATCH_TILE_TRAIN, MATCH_CHUNK_QUERY, MATCH_SEG_QUERY = _lib.RWH_MATCH_TILE_TRAIN, _lib.RWH_MATCH_CHUNK_QUERY, _lib.RWH_MATCH_SEG_QUERY

@@ -53,9 +53,10 @@ from . import _lapack, _lib, kernels
 from .features import (DeviceProblems, _host_rows, default_pattern, detect_and_describe, extract_batch, match_batch,  # noqa: F401
                        match_descriptors, match_descriptors_ratio, match_graph, match_ratio, orb_bin_table, orb_layout,
                        orb_level_quotas, orb_scales, rotate_pattern)
-from .homography import (_check_bands, _check_pairs, _check_projection, _oriented, _pair_rows, _sequence_inputs, calcHomography,  # noqa: F401
-                         calcHomographyLinear, cylindericlMap, sequence_adjust, sequence_focal, sequence_gains, sequence_graph,
-                         sequence_plan, stitchPanorama, stitchSequence)
+from .homography import (_check_bands, _check_focal, _check_pairs, _check_projection, _oriented, _pair_rows, _sequence_inputs,  # noqa: F401
+                         calcHomography, calcHomographyLinear, cylindericlMap, sequence_adjust, sequence_adjust_cameras,
+                         sequence_camera_maps, sequence_cameras, sequence_focal, sequence_gains, sequence_graph, sequence_plan,
+                         stitchPanorama, stitchSequence)
 
 # Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
 # in csrc/rwh_settle.h.  RESCORE_MARGIN caps the margin of the 'backward' / 'reproj' rule: an unflagged K1 count moves by <= 2
@@ -800,6 +801,15 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     defaults make the calls and give the results they always did.  `bands` stays the last parameter: pass it, and everything
     behind `focal`, by name.  ValueError, before the GPU is asked for: another `pairs` or `adjust`.
 
+    adjust="cameras" or "cameras-per-image": the adjustment runs over rotations and focal lengths instead (the camera rule of
+    include/rwh.h), four parameters per image in place of eight, with one focal length for all images or one per image.  After
+    `sequence_graph` the starting focal is the numeric `focal=` where one was given (here also without a projection), else
+    `sequence_focal` over the accepted pairs -- or, where no pair gives one (images that are translations of each other), the mean
+    of h + w, the stand-in OpenCV's stitcher uses; then `sequence_cameras`, `sequence_adjust_cameras` with the matches and masks on
+    the device, and `sequence_camera_maps`, whose G_i = K_a R_i inv(K_i) go to `stitchSequence`.  With a projection and
+    focal="auto" the canvas takes the adjusted focal of the anchor.  info["adjust"] also receives "Rs" and "focals"; info["focal"]
+    stays the focal of the canvas (None without a projection).
+
     The matcher.  A key "ratio" in the `features` dict (features={"ratio": 0.7, "n_levels": 4}) is taken out before the rest goes to
     `extract_batch`: the pairs -- adjacent or of the graph -- are then matched by `match_graph(feats, pairs, ratio)`, Lowe's ratio
     test with every image's descriptors held once, in place of `match_batch`'s cross-check.  With pairs="all" that is the matcher to
@@ -812,8 +822,9 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
         ratio = match_ratio(features.pop("ratio"), "stitch_sequence")
     if not 1 <= n <= _lib.RWH_SEQ_MAX_IMAGES:
         raise ValueError("stitch_sequence: %d images; 1 .. %d are taken" % (n, _lib.RWH_SEQ_MAX_IMAGES))
-    if not isinstance(adjust, (bool, np.bool_)):
-        raise ValueError("stitch_sequence: adjust=%r; True or False" % (adjust,))
+    cameras = isinstance(adjust, str) and adjust in ("cameras", "cameras-per-image")
+    if not isinstance(adjust, (bool, np.bool_)) and not cameras:
+        raise ValueError("stitch_sequence: adjust=%r; True or False, 'cameras' or 'cameras-per-image'" % (adjust,))
     if isinstance(pairs, str):
         if pairs not in ("adjacent", "all"):
             raise ValueError("stitch_sequence: pairs=%r; 'adjacent', 'all' or a list of (s, d)" % (pairs,))
@@ -830,7 +841,11 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     if blending == "multiband":
         _check_bands("stitch_sequence", bands)
     auto_focal = isinstance(focal, str) and focal == "auto" and projection is not None
-    _check_projection("stitch_sequence", projection, 1.0 if auto_focal else focal)
+    if cameras and projection is None:      # the camera model takes a starting focal of its own, with or without a surface
+        if focal is not None and not (isinstance(focal, str) and focal == "auto"):
+            _check_focal("stitch_sequence", focal)
+    else:
+        _check_projection("stitch_sequence", projection, 1.0 if auto_focal else focal)
     if graph:
         return _stitch_sequence_graph(images, anchor, dict(th=th, d=d, n=4, k=k, method=ransacMet, seed=seed), blending, features, info, gains,
                                       projection, focal, auto_focal, bands, pairs, adjust, ratio)
@@ -868,7 +883,9 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
 def _stitch_sequence_graph(images, anchor, search, blending, features, info, gains, projection, focal, auto_focal, bands, pairs, adjust,
                            ratio=None):
     """`stitch_sequence` over a pair graph: one extract, one match (`match_batch`, or `match_graph` with a ratio) and one search over
-    the listed pairs, `sequence_graph`, with adjust=True `sequence_adjust` on the device, then `stitchSequence(Gs=...)`."""
+    the listed pairs, `sequence_graph`, with adjust=True `sequence_adjust` on the device -- with adjust="cameras" or
+    "cameras-per-image" `sequence_cameras`, `sequence_adjust_cameras` on the device and `sequence_camera_maps` --, then
+    `stitchSequence(Gs=...)`."""
     n = len(images)
     adjacent = isinstance(pairs, str) and pairs == "adjacent"
     if isinstance(pairs, str):
@@ -886,15 +903,44 @@ def _stitch_sequence_graph(images, anchor, search, blending, features, info, gai
         Hs, inliers, masks = [r[0] for r in res], [int(r[2]) for r in res], found["mask_device"]
     Gs, accepted, tree = sequence_graph(n, pairs, Hs, sizes, inliers, anchor)
     adjusted = None
-    if adjust and pairs:
+    shapes = [tuple(int(v) for v in img.shape) for img in images]
+    cameras = isinstance(adjust, str)
+
+    def estimate():
+        return sequence_focal(shapes, [H for H, ok in zip(Hs, accepted) if ok], pairs=[pr for pr, ok in zip(pairs, accepted) if ok])
+
+    if cameras and pairs:
+        import torch
+        adjusted = {}
+        masks = masks.clone()
+        masks[torch.from_numpy(~accepted).to(masks.device)] = 0
+        if focal is None or isinstance(focal, str):
+            try:
+                start = estimate()
+            except ValueError:
+                # no pair gives a focal length (images that are translations of each other): the stand-in of OpenCV's stitcher
+                start = float(np.mean([shape[0] + shape[1] for shape in shapes]))
+        else:
+            start = float(focal)
+        Rs, fs = sequence_cameras(shapes, Gs, start, anchor)
+        Rs, fs = sequence_adjust_cameras(shapes, Rs, fs, pairs, problems, masks=masks, anchor=anchor, on="device", info=adjusted,
+                                         focals="shared" if adjust == "cameras" else "per-image")
+        adjusted["Rs"], adjusted["focals"] = Rs, fs
+        Gs = sequence_camera_maps(shapes, Rs, fs, anchor)
+        if projection is None:
+            focal = None
+        elif auto_focal:
+            focal = float(fs[anchor])
+    elif cameras:
+        focal = None if projection is None else focal
+    elif adjust and pairs:
         import torch
         adjusted = {}
         masks = masks.clone()
         masks[torch.from_numpy(~accepted).to(masks.device)] = 0      # an edge that is not accepted has no inliers: a zero block
         Gs = sequence_adjust(Gs, pairs, problems, masks=masks, anchor=anchor, on="device", info=adjusted)
-    shapes = [tuple(int(v) for v in img.shape) for img in images]
-    if auto_focal:
-        focal = sequence_focal(shapes, [H for H, ok in zip(Hs, accepted) if ok], pairs=[pr for pr, ok in zip(pairs, accepted) if ok])
+    if auto_focal and isinstance(focal, str):
+        focal = estimate()
     if info is not None:
         _, origin, _, _, _, _ = _sequence_inputs("stitch_sequence", images, None, Gs, anchor, projection, focal)
         info["Gs"], info["origin"] = (Gs if projection is None else _oriented(Gs)), origin
