@@ -999,6 +999,73 @@ RWH_API int rwh_host_stitch_multiband_proj(const void* const* images, const int3
                                            int canvas_h, int canvas_w);
 
 /*
+ * Full-circle panoramas.  The projection rule refuses an image across the seam behind the anchor, and with it every sweep that
+ * closes the circle.  The compositor knows nothing of sin or cos -- it reads two ray tables -- so a canvas that wraps around is a
+ * matter of index arithmetic only: which columns a rectangle covers, which candidates a tile has, where a multi-band window sits,
+ * where a pyramid tap lands.  That arithmetic is THE RING RULE below.  Everything not restated is the projection rule's.
+ *
+ * The ring rule.
+ *   Inputs.  Those of the projection rule, and a period P: a positive multiple of 256, P <= 65280.  The default is
+ *     P = 256 * max(1, rint(2 pi f / 256)) with numpy's rint; the caller may give another multiple of 256.  The radius is
+ *     rho = P / (2.0 * pi) in float64.
+ *   The camera keeps f.  K is the projection rule's K with the focal f, M_i = inv(G_i) @ K, the anchor's M is K exactly.  f is not
+ *     snapped to the period: the camera model would be wrong and the loop would not close.
+ *   The surface takes rho.  (u, s) = (rho theta, rho t).  The ray tables are the projection rule's with rho for f:
+ *     col[cx] = (sin, cos)((ox + cx) / rho), row[cy] from (oy + cy) / rho.
+ *   Canvas.  fw = P exactly, ox = -P / 2: the seam lies at +-pi, behind the anchor.  oy and fh come from the union of the
+ *     rectangles' rows; the size limits are the sequence rule's.  A multiple of 256 makes every level of a pyramid of up to
+ *     RWH_SEQ_MAX_BANDS bands periodic with the integer period P >> l, and keeps the kernels' 256 x 4 tiles from straddling the seam
+ *     or hanging over the canvas's edge.
+ *   Rectangles.  The perimeter rays and theta are the projection rule's.  The column extent is taken on the UNWRAPPED angle:
+ *     theta_u[0] = theta[0], theta_u[k+1] = theta_u[k] + wrapped(theta[k+1] - theta[k]), wrapped(x) = (x + pi) mod 2 pi - pi;
+ *     lo = floor(min rho theta_u) - 1, hi = ceil(max rho theta_u) + 1, wt = min(hi - lo + 1, P).  In canvas coordinates
+ *     mx = (lo - ox) mod P, and mx = 0 when wt == P.  The rows are the projection rule's, with rho.  Still refused: a non-finite
+ *     perimeter point; a perimeter whose wrapped differences do not sum to 0 (a pole inside the image).  No longer refused: an
+ *     image across the seam.
+ *   Coverage.  ((cx - mx) mod P) < wt, the modulo non-negative, and my <= cy < my + ht, and the projection rule's valid, W > 0
+ *     included.
+ *   Paste, feather, gains and the overlap statistics are unchanged on this Coverage.
+ *   Multi-band.  The multi-band rule with PW = P, and every plane of level l periodic in x with period P >> l: the reduce and
+ *     expand taps read column x mod (P >> l).  Above and below the plane they read 0, as before.
+ *   Working in windows.  A window is an interval [x0, x0 + w) of the unwrapped column axis with w <= P >> l; x0 may be negative,
+ *     or x0 + w may pass the period.  Plane column x belongs to the window iff ((x - x0) mod (P >> l)) < w.  An interval that
+ *     would reach the period is the whole ring: x0 = 0, w = P >> l.  The recursion D_l, E_l, N_l of the multi-band rule is
+ *     unchanged apart from dropping the clip in x.
+ *   Consequences.  (a) With f == P / (2 pi) as a float64 and no image across the seam, paste and feather give, on the columns and
+ *     rows of the projection rule's canvas, that canvas byte for byte: the table entries are the same numbers.  (b) Rolling the
+ *     column table by s columns and every mx to (mx + s) mod P rolls the canvas by s, exactly: for every s under paste and feather,
+ *     for s a multiple of stride in the statistics, for s a multiple of 2^bands under multi-band.
+ *
+ * rwh_stitch_sequence_ring, rwh_sequence_overlap_stats_ring, rwh_stitch_multiband_ring: arguments as the _proj siblings', with
+ * canvas_w the period.  Rectangles are in canvas coordinates with 0 <= mx < canvas_w and 1 <= wt <= canvas_w; mx + wt may pass the
+ * edge.  Workspaces: rwh_stitch_sequence_workspace_bytes, rwh_sequence_overlap_stats_workspace_bytes and
+ * rwh_stitch_multiband_ring_workspace_bytes (the ring's windows are not the plane's).  RWH_E_INVALID, before anything is launched:
+ * everything the _proj calls refuse, a canvas_w that is not a multiple of 256, mx outside [0, canvas_w), wt > canvas_w.  The _proj and
+ * planar entry points go on refusing a rectangle that leaves the canvas.
+ * rwh_host_*_ring: the same arithmetic on host memory (the tables 8-byte aligned), no GPU involved.
+ */
+RWH_API int rwh_stitch_sequence_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                     const int32_t* order, int blend, const double* d_col, const double* d_row, void* d_canvas,
+                                     int canvas_h, int canvas_w, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                     void* stream, const double* gains);
+RWH_API int rwh_host_stitch_sequence_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                          const int32_t* order, int blend, const double* col, const double* row, void* canvas,
+                                          int canvas_h, int canvas_w, int row_begin, int row_end, const double* gains);
+RWH_API int rwh_sequence_overlap_stats_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                            const double* d_col, const double* d_row, int canvas_h, int canvas_w, int stride,
+                                            uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_sequence_overlap_stats_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                 const double* col, const double* row, int canvas_h, int canvas_w, int stride,
+                                                 uint64_t* count, uint64_t* sum);
+RWH_API int64_t rwh_stitch_multiband_ring_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int bands);
+RWH_API int rwh_stitch_multiband_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                      int bands, const double* gains, const double* d_col, const double* d_row, void* d_canvas,
+                                      int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_stitch_multiband_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                           int bands, const double* gains, const double* col, const double* row, void* canvas,
+                                           int canvas_h, int canvas_w);
+
+/*
  * Registration of a sequence over a pair graph: the maps G_i of the sequence rule refined jointly over the inliers of every verified
  * pair (bundle adjustment, Brown & Lowe 2007, section 4; Triggs et al. 1999), instead of chained from N - 1 adjacent pairs.  The
  * reference has no counterpart; this is held to THE BUNDLE RULE below.  The per-edge normal-equation blocks are summed on the

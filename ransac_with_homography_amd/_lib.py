@@ -61,6 +61,9 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_stitch_multiband_workspace_bytes", "rwh_stitch_multiband", "rwh_host_stitch_multiband",
            "rwh_stitch_sequence_proj", "rwh_host_stitch_sequence_proj", "rwh_sequence_overlap_stats_proj",
            "rwh_host_sequence_overlap_stats_proj", "rwh_stitch_multiband_proj", "rwh_host_stitch_multiband_proj",
+           "rwh_stitch_sequence_ring", "rwh_host_stitch_sequence_ring", "rwh_sequence_overlap_stats_ring",
+           "rwh_host_sequence_overlap_stats_ring", "rwh_stitch_multiband_ring_workspace_bytes", "rwh_stitch_multiband_ring",
+           "rwh_host_stitch_multiband_ring",
            "rwh_bundle_blocks", "rwh_host_bundle_blocks", "rwh_host_bundle_step",
            "rwh_camera_blocks", "rwh_host_camera_blocks", "rwh_host_camera_step")
 
@@ -225,6 +228,15 @@ def _bind(lib):
                                               vp, i32, i32, vp, i64, vp]                # canvas h w workspace bytes stream
     lib.rwh_host_stitch_multiband_proj.restype = i32
     lib.rwh_host_stitch_multiband_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32]
+    # the ring rule: the projected calls' arguments, canvas_w the period; the multi-band workspace has its own size function
+    for ring, proj in (("rwh_stitch_sequence_ring", lib.rwh_stitch_sequence_proj), ("rwh_host_stitch_sequence_ring", lib.rwh_host_stitch_sequence_proj),
+                       ("rwh_sequence_overlap_stats_ring", lib.rwh_sequence_overlap_stats_proj),
+                       ("rwh_host_sequence_overlap_stats_ring", lib.rwh_host_sequence_overlap_stats_proj),
+                       ("rwh_stitch_multiband_ring", lib.rwh_stitch_multiband_proj), ("rwh_host_stitch_multiband_ring", lib.rwh_host_stitch_multiband_proj)):
+        getattr(lib, ring).restype = i32
+        getattr(lib, ring).argtypes = list(proj.argtypes)
+    lib.rwh_stitch_multiband_ring_workspace_bytes.restype = i64
+    lib.rwh_stitch_multiband_ring_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]   # rects n canvas_h canvas_w bands
     # the bundle rule: the edge blocks (device and host twin) and the damped step
     lib.rwh_bundle_blocks.restype = i32
     lib.rwh_bundle_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]     # pts_a pts_b offsets n_edges masks words T blocks count status stream

@@ -43,7 +43,7 @@ struct MbArgs {
 // P and the winner at canvas pixel (cx, cy): the covering image with the greatest feather weight g, the lowest index on equal
 // weights (candidates are visited in index order and only a greater g replaces the best; g >= 1 wherever an image covers).
 // rays: the ray tables of the projection rule, read with PROJ only.
-template <bool GAIN, bool PROJ = false>
+template <bool GAIN, bool PROJ = false, bool RING = false>
 __host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains,
                                                              SeqRays rays = SeqRays{nullptr, nullptr}) {
     const int fx = a.ox + cx, fy = a.oy + cy;
@@ -55,7 +55,7 @@ __host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, u
         const int i = __builtin_ctzll(m);
         double v[3], g = 0.0, gain = 1.0;
         if constexpr (GAIN) gain = gains[i];
-        if (!seq_sample<true, GAIN, PROJ>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray)) continue;
+        if (!seq_sample<true, GAIN, PROJ, RING>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray, a.fw)) continue;
         if (g > best) {
             best = g;
             out = (uint32_t)i << 24;
@@ -67,7 +67,7 @@ __host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, u
 }
 
 // (I_i, W_i) at plane pixel (x, y) of level 0: image i's bytes where it covers, P elsewhere; MB_ONE where i is the winner.
-template <bool GAIN, bool PROJ = false>
+template <bool GAIN, bool PROJ = false, bool RING = false>
 __host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i, uint32_t pwv, int x, int y, const double* gains,
                                                          SeqRays rays = SeqRays{nullptr, nullptr}) {
     MbPx o;
@@ -79,7 +79,7 @@ __host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i
         if constexpr (GAIN) gain = gains[i];
         SeqRay ray;
         if constexpr (PROJ) ray = seq_ray(rays, x, y);
-        if (seq_sample<false, GAIN, PROJ>(a.desc[i], i == a.anchor, a.ox + x, a.oy + y, v, g, gain, &ray)) {
+        if (seq_sample<false, GAIN, PROJ, RING>(a.desc[i], i == a.anchor, a.ox + x, a.oy + y, v, g, gain, &ray, a.fw)) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) o.c[k] = (int16_t)(unsigned char)(int)v[k];
         }
@@ -89,8 +89,18 @@ __host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i
 
 // A window's pixel at plane coordinates (x, y); 0 outside the window (beyond the plane's edge the rule reads 0, and inside the plane
 // the windows are made so that nothing outside them is ever needed: mb_plan).
-__host__ __device__ __forceinline__ MbPx mb_fetch(const MbPx* g, const MbWin& w, int x, int y) {
+// RING (the ring rule): the level's plane is periodic in x with `period` columns and the window is an interval of the unwrapped
+// axis, x0 possibly negative or x0 + w past the period; x may be any tap, left of 0 or past the period.  The one place where a ring
+// window is indexed: a non-negative modulo, then the same bounds test.
+__host__ __device__ __forceinline__ int mb_mod(int x, int period) {
+    if ((unsigned)x < (unsigned)period) return x;       // (most taps; a wave away from the seam never divides)
+    x %= period;
+    return x + (x < 0 ? period : 0);
+}
+template <bool RING = false>
+__host__ __device__ __forceinline__ MbPx mb_fetch(const MbPx* g, const MbWin& w, int x, int y, int period = 0) {
     x -= w.x0; y -= w.y0;
+    if constexpr (RING) x = mb_mod(x, period);
     if ((unsigned)x >= (unsigned)w.w || (unsigned)y >= (unsigned)w.h) return MbPx{{0, 0, 0, 0}};
     return g[w.off + (int64_t)y * w.w + x];
 }
@@ -151,20 +161,34 @@ struct MbPlaneAt {              // a whole R plane as mb_up's source, 0 beyond i
     }
 };
 
+template <bool RING> struct MbRingWinAt {     // MbWinAt with the accessor's form (RING: on a ring of `period` columns)
+    const MbPx* g; const MbWin& w; int period;
+    __host__ __device__ __forceinline__ MbPx operator()(int y, int x) const { return mb_fetch<RING>(g, w, x, y, period); }
+};
+struct MbRingPlaneAt {          // a whole R plane of the ring rule: periodic in x, 0 above and below
+    const MbPx* r; int w, h;
+    __host__ __device__ __forceinline__ MbPx operator()(int y, int x) const {
+        if ((unsigned)y >= (unsigned)h) return MbPx{{0, 0, 0, 0}};
+        return r[(int64_t)y * w + mb_mod(x, w)];
+    }
+};
+
 // R^l at plane pixel (x, y) of level l: bands, accumulate, normalise and one collapse step.  cand: the images whose level-l window
 // may hold the pixel.
+template <bool RING = false>
 __host__ __device__ __forceinline__ void mb_collapse_pixel(const MbArgs& m, int l, uint64_t cand, int x, int y, int R[3]) {
     int num[3] = {0, 0, 0}, den = 0;
     for (uint64_t c = cand; c; c &= c - 1) {
         const int i = __builtin_ctzll(c);
         const MbWin* w = m.win + (size_t)i * (m.K + 1) + l;
-        const MbPx gp = mb_fetch(m.g, w[0], x, y);
+        const MbPx gp = mb_fetch<RING>(m.g, w[0], x, y, m.PW >> l);
         const int wt = gp.c[3];
         if (wt <= 0) continue;
         int L[3] = {gp.c[0], gp.c[1], gp.c[2]};
         if (l < m.K) {
             int u[3];
-            mb_up(MbWinAt{m.g, w[1]}, x, y, u);
+            if constexpr (RING) mb_up(MbRingWinAt<true>{m.g, w[1], m.PW >> (l + 1)}, x, y, u);
+            else mb_up(MbWinAt{m.g, w[1]}, x, y, u);
 #pragma unroll
             for (int k = 0; k < 3; ++k) L[k] -= u[k];
         }
@@ -183,7 +207,8 @@ __host__ __device__ __forceinline__ void mb_collapse_pixel(const MbArgs& m, int 
     }
     if (l < m.K) {
         int u[3];
-        mb_up(MbPlaneAt{m.r[l + 1], m.PW >> (l + 1), m.PH >> (l + 1)}, x, y, u);
+        if constexpr (RING) mb_up(MbRingPlaneAt{m.r[l + 1], m.PW >> (l + 1), m.PH >> (l + 1)}, x, y, u);
+        else mb_up(MbPlaneAt{m.r[l + 1], m.PW >> (l + 1), m.PH >> (l + 1)}, x, y, u);
 #pragma unroll
         for (int k = 0; k < 3; ++k) R[k] += u[k];
     }
@@ -203,38 +228,47 @@ __host__ __device__ __forceinline__ void mb_store(const MbArgs& m, int l, int x,
 }
 
 // The images whose level-l window meets columns [x0, x1) and rows [y0, y1) of the level's plane.
+// RING: a window is an interval of the unwrapped axis that starts within one period of the plane (mb_plan), so it is also tested
+// shifted by the level's period either way.
+template <bool RING = false>
 __host__ __device__ __forceinline__ uint64_t mb_window_mask(const MbArgs& m, int l, int x0, int x1, int y0, int y1) {
     uint64_t c = 0;
     for (int i = 0; i < m.a.n; ++i) {
         const MbWin& w = m.win[(size_t)i * (m.K + 1) + l];
-        if ((w.x0 < x1) & (w.x0 + w.w > x0) & (w.y0 < y1) & (w.y0 + w.h > y0)) c |= 1ull << i;
+        bool cols = (w.x0 < x1) & (w.x0 + w.w > x0);
+        if constexpr (RING) {
+            const int period = m.PW >> l;
+            cols |= ((w.x0 + period < x1) & (w.x0 + period + w.w > x0)) | ((w.x0 - period < x1) & (w.x0 - period + w.w > x0));
+        }
+        if (cols & (w.y0 < y1) & (w.y0 + w.h > y0)) c |= 1ull << i;
     }
     return c;
 }
 
 // ---- the kernels ----
 // 256 lanes as 64 x 4, one pixel of the padded canvas each; the tile is tested once against the n rectangles (block-uniform).
-template <bool GAIN, bool PROJ = false>
+template <bool GAIN, bool PROJ = false, bool RING = false>
 __global__ __launch_bounds__(256) void mb_winner_kernel(const SeqWith<MbArgs, GAIN, PROJ> l) {
     const MbArgs& m = l.a;
     const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
-    const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
+    const uint64_t cand = seq_tile_mask<RING>(m.a, bx0, bx0 + 64, by0, by0 + 4);
     const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
     if (x >= m.PW || y >= m.PH) return;
     const bool on = x < m.a.fw && y < m.a.fh;
-    m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<GAIN, PROJ>(m.a, cand, x, y, seq_gains(l), seq_rays(l)) : MB_NONE << 24;
+    m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<GAIN, PROJ, RING>(m.a, cand, x, y, seq_gains(l), seq_rays(l)) : MB_NONE << 24;
 }
 
 // blockIdx.z is the image; a block takes 64 x 4 pixels of its level-0 window (blocks beyond the window leave at once).
-template <bool GAIN, bool PROJ = false>
+// RING: the window's columns are taken modulo the period (PW).
+template <bool GAIN, bool PROJ = false, bool RING = false>
 __global__ __launch_bounds__(256) void mb_level0_kernel(const SeqWith<MbArgs, GAIN, PROJ> l) {
     const MbArgs& m = l.a;
     const int i = blockIdx.z;
     const MbWin w = m.win[(size_t)i * (m.K + 1)];
     const int lx = blockIdx.x * 64 + (threadIdx.x & 63), ly = blockIdx.y * 4 + seq_wave_row<PROJ>(threadIdx.x >> 6);
     if (lx >= w.w || ly >= w.h) return;
-    const int x = w.x0 + lx, y = w.y0 + ly;
-    m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN, PROJ>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l), seq_rays(l));
+    const int x = RING ? mb_mod(w.x0 + lx, m.PW) : w.x0 + lx, y = w.y0 + ly;
+    m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN, PROJ, RING>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l), seq_rays(l));
 }
 
 // The reduce from level l to l + 1 of image blockIdx.z.  A block makes MB_TW x MB_TH outputs from a (2 MB_TW + 3) x (2 MB_TH + 3)
@@ -249,6 +283,7 @@ struct MbLdsAt {
         return (kx & 1) ? O[row][tx + ((kx + 1) >> 1)] : E[row][tx + ((kx + 2) >> 1)];
     }
 };
+template <bool RING = false>
 __global__ __launch_bounds__(256) void mb_down_kernel(const MbArgs m, int l) {
     __shared__ MbPx E[MB_SH][MB_EW], O[MB_SH][MB_EW];
     const int i = blockIdx.z;
@@ -258,7 +293,7 @@ __global__ __launch_bounds__(256) void mb_down_kernel(const MbArgs m, int l) {
     const int c0 = 2 * (dst.x0 + ox0) - 2, r0 = 2 * (dst.y0 + oy0) - 2;
     for (int t = threadIdx.x; t < MB_SH * MB_SW; t += 256) {
         const int row = t / MB_SW, j = t - row * MB_SW;
-        const MbPx v = mb_fetch(m.g, src, c0 + j, r0 + row);
+        const MbPx v = mb_fetch<RING>(m.g, src, c0 + j, r0 + row, m.PW >> l);
         if (j & 1) O[row][j >> 1] = v; else E[row][j >> 1] = v;
     }
     __syncthreads();
@@ -267,19 +302,21 @@ __global__ __launch_bounds__(256) void mb_down_kernel(const MbArgs m, int l) {
     m.g[dst.off + (int64_t)(oy0 + ty) * dst.w + ox0 + tx] = mb_down(MbLdsAt{E, O, tx, ty});
 }
 
-struct MbWinTap {               // the host twin's source of mb_down: the window itself
-    const MbPx* g; const MbWin& w; int x, y;
-    __host__ __device__ __forceinline__ MbPx operator()(int ky, int kx) const { return mb_fetch(g, w, 2 * x + kx, 2 * y + ky); }
+template <bool RING = false>
+struct MbWinTap {               // the host twin's source of mb_down: the window itself (RING: on a ring of `period` columns)
+    const MbPx* g; const MbWin& w; int x, y, period;
+    __host__ __device__ __forceinline__ MbPx operator()(int ky, int kx) const { return mb_fetch<RING>(g, w, 2 * x + kx, 2 * y + ky, period); }
 };
 
 // One pass over the plane of level l, 64 x 4 pixels per block; the tile is tested once against the n windows of the level.
+template <bool RING = false>
 __global__ __launch_bounds__(256) void mb_collapse_kernel(const MbArgs m, int l) {
     const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
-    const uint64_t cand = mb_window_mask(m, l, bx0, bx0 + 64, by0, by0 + 4);
+    const uint64_t cand = mb_window_mask<RING>(m, l, bx0, bx0 + 64, by0, by0 + 4);
     const int x = bx0 + (threadIdx.x & 63), y = by0 + (threadIdx.x >> 6);
     if (x >= (m.PW >> l) || y >= (m.PH >> l)) return;
     int R[3];
-    mb_collapse_pixel(m, l, cand, x, y, R);
+    mb_collapse_pixel<RING>(m, l, cand, x, y, R);
     mb_store(m, l, x, y, R);
 }
 
@@ -299,7 +336,9 @@ struct MbPlan {
 // Every set is an interval (hulls are taken), N_l holds all taps of N_{l+1}, and level 0 is exact everywhere, so every value stored
 // in a window is the rule's; what lies outside a window is never needed, or lies beyond the plane and is 0.  N_0 reaches less than
 // 6 * 2^K + 2 pixels beyond the rectangle.
-static void mb_axis(int a, int b, int P, int K, int* lo, int* hi) {
+// ring (the ring rule's x axis): no clip -- an interval shorter than the level's period P >> l stays as it is, on the unwrapped
+// axis, and one that would reach the period is the whole ring, [0, P >> l).
+static void mb_axis(int a, int b, int P, int K, int* lo, int* hi, bool ring = false) {
     int dl[MB_LEVELS], dh[MB_LEVELS];            // D_l, inclusive
     dl[0] = a; dh[0] = b - 1;
     for (int l = 0; l < K; ++l) { dl[l + 1] = (dl[l] - 1) >> 1; dh[l + 1] = (dh[l] + 2) >> 1; }
@@ -316,6 +355,10 @@ static void mb_axis(int a, int b, int P, int K, int* lo, int* hi) {
         lo[l] = nl; hi[l] = nh;
     }
     for (int l = 0; l <= K; ++l) {
+        if (ring) {
+            if (hi[l] - lo[l] + 1 >= (P >> l)) { lo[l] = 0; hi[l] = (P >> l) - 1; }
+            continue;
+        }
         if (lo[l] < 0) lo[l] = 0;
         if (hi[l] > (P >> l) - 1) hi[l] = (P >> l) - 1;
     }
@@ -324,9 +367,11 @@ static void mb_axis(int a, int b, int P, int K, int* lo, int* hi) {
 static int64_t mb_align(int64_t v) { return (v + 127) & ~(int64_t)127; }
 
 // What the size function and both entry points check of the geometry, and the plan.
-static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y, int bands, MbPlan& p) {
+// ring: the ring rule -- canvas_w is the period (PW = canvas_w), a rectangle may pass the canvas's edge.
+static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y, int bands, MbPlan& p,
+                   bool ring = false) {
     if (!rects || n < 1 || n > RWH_SEQ_MAX_IMAGES || bands < 1 || bands > RWH_SEQ_MAX_BANDS) return RWH_E_INVALID;
-    if (!seq_canvas_ok(canvas_h, canvas_w)) return RWH_E_INVALID;
+    if (!seq_canvas_ok(canvas_h, canvas_w) || (ring && !seq_period_ok(canvas_w))) return RWH_E_INVALID;
     const int K = bands, mask = (1 << K) - 1;
     p.K = K; p.PW = (canvas_w + mask) & ~mask; p.PH = (canvas_h + mask) & ~mask;
     for (int l = 0; l <= K; ++l) p.maxw[l] = p.maxh[l] = 0;
@@ -334,9 +379,10 @@ static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int 
     for (int i = 0; i < n; ++i) {
         const int wt = rects[4 * i + 2], ht = rects[4 * i + 3];
         const int64_t rx = (int64_t)rects[4 * i] - origin_x, ry = (int64_t)rects[4 * i + 1] - origin_y;
-        if (wt <= 0 || ht <= 0 || rx < 0 || ry < 0 || rx + wt > canvas_w || ry + ht > canvas_h) return RWH_E_INVALID;
+        if (wt <= 0 || ht <= 0 || rx < 0 || ry < 0 || ry + ht > canvas_h) return RWH_E_INVALID;
+        if (ring ? (rx >= canvas_w || wt > canvas_w) : (rx + wt > canvas_w)) return RWH_E_INVALID;
         int xl[MB_LEVELS], xh[MB_LEVELS], yl[MB_LEVELS], yh[MB_LEVELS];
-        mb_axis((int)rx, (int)rx + wt, p.PW, K, xl, xh);
+        mb_axis((int)rx, (int)rx + wt, p.PW, K, xl, xh, ring);
         mb_axis((int)ry, (int)ry + ht, p.PH, K, yl, yh);
         for (int l = 0; l <= K; ++l) {
             MbWin& w = p.win[i * (K + 1) + l];
@@ -361,11 +407,11 @@ static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int 
 // Everything both entry points check, the descriptors and the plan.
 static int mb_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor, int bands,
                       const double* gains, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, MbArgs& m,
-                      MbPlan& p, bool proj = false) {
-    int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m.a, proj);
+                      MbPlan& p, bool proj = false, bool ring = false) {
+    int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m.a, proj, ring);
     if (st != RWH_OK) return st;
     if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
-    st = mb_plan(rects, n, canvas_h, canvas_w, origin_x, origin_y, bands, p);
+    st = mb_plan(rects, n, canvas_h, canvas_w, origin_x, origin_y, bands, p, ring);
     if (st != RWH_OK) return st;
     m.K = p.K; m.PW = p.PW; m.PH = p.PH;
     return RWH_OK;
@@ -381,38 +427,40 @@ static void mb_bind(MbArgs& m, const MbPlan& p, char* base) {
     for (int l = 1; l < MB_LEVELS; ++l) m.r[l] = l <= p.K ? reinterpret_cast<MbPx*>(base + p.r_at[l]) : nullptr;
 }
 
-template <bool GAIN, bool PROJ>
+template <bool GAIN, bool PROJ, bool RING>
 static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays, hipStream_t s) {
     const SeqWith<MbArgs, GAIN, PROJ> l = seq_with<GAIN, PROJ>(m, gains, m.a.n, rays);
-    hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
-    hipLaunchKernelGGL((mb_level0_kernel<GAIN, PROJ>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
+    hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ, RING>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
+    hipLaunchKernelGGL((mb_level0_kernel<GAIN, PROJ, RING>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
 }
 
-template <bool GAIN, bool PROJ>
+template <bool GAIN, bool PROJ, bool RING>
 static void mb_host_run(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays) {
     const int n = m.a.n, K = p.K;
     const uint64_t all = seq_all(n);
     for (int y = 0; y < p.PH; ++y)
         for (int x = 0; x < p.PW; ++x)
-            m.pw[(int64_t)y * p.PW + x] = (x < m.a.fw && y < m.a.fh) ? mb_winner_pixel<GAIN, PROJ>(m.a, all, x, y, gains, rays) : MB_NONE << 24;
+            m.pw[(int64_t)y * p.PW + x] = (x < m.a.fw && y < m.a.fh) ? mb_winner_pixel<GAIN, PROJ, RING>(m.a, all, x, y, gains, rays) : MB_NONE << 24;
     for (int i = 0; i < n; ++i) {
         const MbWin& w = m.win[i * (K + 1)];
         for (int ly = 0; ly < w.h; ++ly)
-            for (int lx = 0; lx < w.w; ++lx)
-                m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN, PROJ>(m.a, i, m.pw[(int64_t)(w.y0 + ly) * p.PW + w.x0 + lx], w.x0 + lx, w.y0 + ly, gains, rays);
+            for (int lx = 0; lx < w.w; ++lx) {
+                const int x = RING ? mb_mod(w.x0 + lx, p.PW) : w.x0 + lx;
+                m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN, PROJ, RING>(m.a, i, m.pw[(int64_t)(w.y0 + ly) * p.PW + x], x, w.y0 + ly, gains, rays);
+            }
         for (int l = 0; l < K; ++l) {
             const MbWin& src = m.win[i * (K + 1) + l];
             const MbWin& dst = m.win[i * (K + 1) + l + 1];
             for (int ly = 0; ly < dst.h; ++ly)
                 for (int lx = 0; lx < dst.w; ++lx)
-                    m.g[dst.off + (int64_t)ly * dst.w + lx] = mb_down(MbWinTap{m.g, src, dst.x0 + lx, dst.y0 + ly});
+                    m.g[dst.off + (int64_t)ly * dst.w + lx] = mb_down(MbWinTap<RING>{m.g, src, dst.x0 + lx, dst.y0 + ly, p.PW >> l});
         }
     }
     for (int l = K; l >= 0; --l)
         for (int y = 0; y < (p.PH >> l); ++y)
             for (int x = 0; x < (p.PW >> l); ++x) {
                 int R[3];
-                mb_collapse_pixel(m, l, all, x, y, R);
+                mb_collapse_pixel<RING>(m, l, all, x, y, R);
                 mb_store(m, l, x, y, R);
             }
 }
@@ -428,7 +476,7 @@ extern "C" int64_t rwh_stitch_multiband_workspace_bytes(const int32_t* rects, in
 
 // The device call behind rwh_stitch_multiband (PROJ false: rays unused) and rwh_stitch_multiband_proj (PROJ true: mats holds the
 // M_i, no anchor, origin (0, 0)).  The reduce and collapse passes work on canvas planes and are the same for both.
-template <bool PROJ>
+template <bool PROJ, bool RING = false>
 static int mb_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
                      int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
                      int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays) {
@@ -436,7 +484,7 @@ static int mb_device(const void* const* d_images, const int32_t* hw, const doubl
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
     MbPlan p;
-    const int st = mb_prepare(d_images, hw, mats, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ);
+    const int st = mb_prepare(d_images, hw, mats, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ, RING);
     if (st != RWH_OK) return st;
     if (!d_workspace || workspace_bytes < p.bytes || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
     if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
@@ -445,11 +493,11 @@ static int mb_device(const void* const* d_images, const int32_t* hw, const doubl
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
     seq_put(p.win, (size_t)n * (p.K + 1) * (sizeof(MbWin) / 8), reinterpret_cast<uint64_t*>(base + p.win_at), s);
     mb_bind(m, p, base);
-    if (gains) mb_launch_head<true, PROJ>(m, p, gains, rays, s); else mb_launch_head<false, PROJ>(m, p, nullptr, rays, s);
+    if (gains) mb_launch_head<true, PROJ, RING>(m, p, gains, rays, s); else mb_launch_head<false, PROJ, RING>(m, p, nullptr, rays, s);
     for (int l = 0; l < p.K; ++l)
-        hipLaunchKernelGGL(mb_down_kernel, dim3((p.maxw[l + 1] + MB_TW - 1) / MB_TW, (p.maxh[l + 1] + MB_TH - 1) / MB_TH, n), dim3(256), 0, s, m, l);
+        hipLaunchKernelGGL(mb_down_kernel<RING>, dim3((p.maxw[l + 1] + MB_TW - 1) / MB_TW, (p.maxh[l + 1] + MB_TH - 1) / MB_TH, n), dim3(256), 0, s, m, l);
     for (int l = p.K; l >= 0; --l)
-        hipLaunchKernelGGL(mb_collapse_kernel, dim3(((p.PW >> l) + 63) / 64, ((p.PH >> l) + 3) / 4), dim3(256), 0, s, m, l);
+        hipLaunchKernelGGL(mb_collapse_kernel<RING>, dim3(((p.PW >> l) + 63) / 64, ((p.PH >> l) + 3) / 4), dim3(256), 0, s, m, l);
     return check_launch();
 }
 
@@ -467,7 +515,7 @@ extern "C" int rwh_stitch_multiband_proj(const void* const* d_images, const int3
                            d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
 }
 
-template <bool PROJ>
+template <bool PROJ, bool RING = false>
 static int mb_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
                    int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
                    int origin_x, int origin_y, rwh::SeqRays rays) {
@@ -475,7 +523,7 @@ static int mb_host(const void* const* images, const int32_t* hw, const double* m
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
     MbPlan p;
-    const int st = mb_prepare(images, hw, mats, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ);
+    const int st = mb_prepare(images, hw, mats, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ, RING);
     if (st != RWH_OK) return st;
     if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
     char* base = static_cast<char*>(malloc((size_t)p.bytes));
@@ -483,7 +531,7 @@ static int mb_host(const void* const* images, const int32_t* hw, const double* m
     memcpy(base + p.desc_at, descs, (size_t)n * sizeof(SeqDesc));
     memcpy(base + p.win_at, p.win, (size_t)n * (p.K + 1) * sizeof(MbWin));
     mb_bind(m, p, base);
-    if (gains) mb_host_run<true, PROJ>(m, p, gains, rays); else mb_host_run<false, PROJ>(m, p, nullptr, rays);
+    if (gains) mb_host_run<true, PROJ, RING>(m, p, gains, rays); else mb_host_run<false, PROJ, RING>(m, p, nullptr, rays);
     free(base);
     return RWH_OK;
 }
@@ -500,4 +548,24 @@ extern "C" int rwh_host_stitch_multiband_proj(const void* const* images, const i
                                               int canvas_h, int canvas_w) {
     return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
                          rwh::SeqRays{col, row});
+}
+
+extern "C" int64_t rwh_stitch_multiband_ring_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int bands) {
+    rwh::MbPlan p;
+    const int st = rwh::mb_plan(rects, n, canvas_h, canvas_w, 0, 0, bands, p, true);
+    return st == RWH_OK ? p.bytes : (int64_t)st;
+}
+
+extern "C" int rwh_stitch_multiband_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                         int bands, const double* gains, const double* d_col, const double* d_row, void* d_canvas,
+                                         int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    return mb_device<true, true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, d_canvas, canvas_h, canvas_w, 0, 0,
+                                 d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
+}
+
+extern "C" int rwh_host_stitch_multiband_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                              int bands, const double* gains, const double* col, const double* row, void* canvas,
+                                              int canvas_h, int canvas_w) {
+    return mb_host<true, true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
+                               rwh::SeqRays{col, row});
 }

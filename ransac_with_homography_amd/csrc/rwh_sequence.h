@@ -92,10 +92,15 @@ __host__ __device__ __forceinline__ double seq_min(double a, double b) { return 
 // min(v * gain, 255.0), the product rounded on its own; without GAIN `gain` is not read.
 // PROJ (the projection rule): (fx, fy) is the canvas pixel, `ray` its ray and d.ih the image's M; X, Y and W are M's rows on the
 // ray, a ray behind the camera (W <= 0) is not valid, and no image enters unwarped (is_anchor is not read).
-template <bool FEATHER, bool GAIN = false, bool PROJ = false>
+// RING (the ring rule, with PROJ): the canvas is periodic in x with `period` columns and the rectangle may pass its edge; the
+// containment is one conditional add, and nothing else of the recipe changes.
+template <bool FEATHER, bool GAIN = false, bool PROJ = false, bool RING = false>
 __host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_anchor, int fx, int fy, double v[3], double& g,
-                                                    double gain = 1.0, const SeqRay* ray = nullptr) {
-    const int tx = fx - d.mx, ty = fy - d.my;
+                                                    double gain = 1.0, const SeqRay* ray = nullptr, int period = 0) {
+    static_assert(PROJ || !RING, "the ring rule is stated on the projection rule");
+    int tx = fx - d.mx;
+    const int ty = fy - d.my;
+    if constexpr (RING) tx += tx < 0 ? period : 0;      // (0 <= fx, mx < period: tx lands in [0, period))
     if (!((tx >= 0) & (tx < d.wt) & (ty >= 0) & (ty < d.ht))) return false;
     const size_t bytes = (size_t)d.h * d.w * 3;
     double sx, sy;
@@ -146,7 +151,8 @@ __host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_an
 
 // One canvas pixel as 0x00BBGGRR.  cand: bit k set = image order[k] may cover the pixel (its rectangle meets the pixel's tile).
 // gains: the N gains of the gain rule, read with GAIN only.  rays: the ray tables, read with PROJ only (then ox = oy = 0).
-template <bool FEATHER, bool GAIN = false, bool PROJ = false>
+// RING: a.fw is the period.
+template <bool FEATHER, bool GAIN = false, bool PROJ = false, bool RING = false>
 __host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains = nullptr,
                                                        SeqRays rays = SeqRays{nullptr, nullptr}) {
     const int fx = a.ox + cx, fy = a.oy + cy;
@@ -159,7 +165,7 @@ __host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_
         double v[3], g = 0.0;
         double gain = 1.0;
         if constexpr (GAIN) gain = gains[i];
-        if (!seq_sample<FEATHER, GAIN, PROJ>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray)) continue;
+        if (!seq_sample<FEATHER, GAIN, PROJ, RING>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray, a.fw)) continue;
         if constexpr (!FEATHER) {       // paste: the first image in `order` that covers the pixel
             uint32_t out = 0u;
 #pragma unroll
@@ -181,12 +187,17 @@ __host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_
 }
 
 // The images whose rectangles meet canvas columns [x0, x1) and rows [y0, y1), as bits in `order`'s numbering.
+// RING: a rectangle that passes the canvas's edge comes back in at column 0, so the rectangle shifted by -period (a.fw) is tested
+// as well; it starts left of every tile, which leaves one compare of wave-uniform values.
+template <bool RING = false>
 __host__ __device__ __forceinline__ uint64_t seq_tile_mask(const SeqArgs& a, int x0, int x1, int y0, int y1) {
     uint64_t m = 0;
     for (int k = 0; k < a.n; ++k) {
         const SeqDesc& d = a.desc[a.order[k]];
         const int rx = d.mx - a.ox, ry = d.my - a.oy;
-        if ((rx < x1) & (rx + d.wt > x0) & (ry < y1) & (ry + d.ht > y0)) m |= 1ull << k;
+        bool cols = (rx < x1) & (rx + d.wt > x0);
+        if constexpr (RING) cols |= rx + d.wt - a.fw > x0;
+        if (cols & (ry < y1) & (ry + d.ht > y0)) m |= 1ull << k;
     }
     return m;
 }
@@ -196,6 +207,10 @@ static uint64_t seq_all(int n) { return n == 64 ? ~0ull : (1ull << n) - 1; }
 
 // The canvas every rule of the family takes: sides of 1 .. 65535, byte offsets within int32.
 static bool seq_canvas_ok(int h, int w) { return h >= 1 && w >= 1 && h <= 65535 && w <= 65535 && (int64_t)h * w * 3 <= INT32_MAX; }
+
+// The period of the ring rule: a whole number of the kernels' 256-column tiles (and so of 2^RWH_SEQ_MAX_BANDS).
+constexpr int SEQ_RING_TILE = 256;
+static bool seq_period_ok(int w) { return w >= SEQ_RING_TILE && w % SEQ_RING_TILE == 0; }
 
 // Lays `words` eight-byte words of a host table down at `dev` on the stream (rwh_sequence.hip).
 void seq_put(const void* host, size_t words, uint64_t* dev, hipStream_t s);
@@ -211,13 +226,15 @@ static bool seq_rays_ok(const double* col, const double* row, bool device) {
 
 // Everything both entry points check, and the descriptors / arguments they share.  descs: room for RWH_SEQ_MAX_IMAGES.
 // proj: a projected call -- inv_g holds the M_i, anchor is SEQ_NO_ANCHOR and the origin (0, 0).
+// ring: a call of the ring rule (with proj) -- canvas_w is the period, a multiple of SEQ_RING_TILE; a rectangle starts on the canvas,
+// is at most one period wide and may pass the canvas's edge.
 static int seq_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
                        const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                       int row_begin, int row_end, SeqDesc* descs, SeqArgs& a, bool proj = false) {
+                       int row_begin, int row_end, SeqDesc* descs, SeqArgs& a, bool proj = false, bool ring = false) {
     if (!images || !hw || !inv_g || !rects || !order || !canvas) return RWH_E_INVALID;
     if (proj ? (anchor != SEQ_NO_ANCHOR || origin_x || origin_y) : (anchor < 0 || anchor >= n)) return RWH_E_INVALID;
     if (n < 1 || n > RWH_SEQ_MAX_IMAGES || (blend != RWH_SEQ_PASTE && blend != RWH_SEQ_FEATHER)) return RWH_E_INVALID;
-    if (!seq_canvas_ok(canvas_h, canvas_w)) return RWH_E_INVALID;
+    if (!seq_canvas_ok(canvas_h, canvas_w) || (ring && !seq_period_ok(canvas_w))) return RWH_E_INVALID;
     if (row_begin < 0 || row_end > canvas_h || row_begin > row_end) return RWH_E_INVALID;
     uint64_t seen = 0;
     for (int k = 0; k < n; ++k) {
@@ -232,7 +249,8 @@ static int seq_prepare(const void* const* images, const int32_t* hw, const doubl
         if (!d.src || d.h < 2 || d.w < 2 || d.wt <= 0 || d.ht <= 0) return RWH_E_INVALID;
         // the rectangle lies on the canvas (so no frame coordinate leaves int32), the anchor's is its own image
         const int64_t rx = (int64_t)d.mx - origin_x, ry = (int64_t)d.my - origin_y;
-        if (rx < 0 || ry < 0 || rx + d.wt > canvas_w || ry + d.ht > canvas_h) return RWH_E_INVALID;
+        if (rx < 0 || ry < 0 || ry + d.ht > canvas_h) return RWH_E_INVALID;
+        if (ring ? (rx >= canvas_w || d.wt > canvas_w) : (rx + d.wt > canvas_w)) return RWH_E_INVALID;
         if (i == anchor && (d.mx != 0 || d.my != 0 || d.wt != d.w || d.ht != d.h)) return RWH_E_INVALID;
         for (int j = 0; j < 9; ++j) {
             d.ih[j] = inv_g[9 * i + j];
@@ -251,12 +269,12 @@ static int seq_prepare(const void* const* images, const int32_t* hw, const doubl
 // seq_prepare for the rules that take the images in index order over the whole canvas: the identity order, feather, all rows.
 static int seq_prepare_indexed(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
                                void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, SeqArgs& a,
-                               bool proj = false) {
+                               bool proj = false, bool ring = false) {
     if (n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;     // (before order[] is filled)
     int32_t order[RWH_SEQ_MAX_IMAGES];
     for (int k = 0; k < n; ++k) order[k] = k;
     return seq_prepare(images, hw, inv_g, rects, n, anchor, order, RWH_SEQ_FEATHER, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                       0, canvas_h, descs, a, proj);
+                       0, canvas_h, descs, a, proj, ring);
 }
 
 // f(feather, gain), the two flags as std::true_type / std::false_type: the four forms of the compositor, device and host.

@@ -12,20 +12,23 @@ namespace rwh {
 // test and the descriptor reads of the pixel loop stay on the scalar side.
 constexpr int SEQ_PX = 4;
 
-template <bool FEATHER, bool GAIN = false, bool PROJ = false>
+// RING: the canvas is a whole number of tiles wide (checked before the launch), so every lane has its four pixels and there is no
+// tail path.
+template <bool FEATHER, bool GAIN = false, bool PROJ = false, bool RING = false>
 __global__ __launch_bounds__(256) void seq_kernel(const SeqWith<SeqArgs, GAIN, PROJ> l) {
+    static_assert(SEQ_RING_TILE == 64 * SEQ_PX, "a ring canvas is made of whole tiles");
     const SeqArgs& a = l.a;
     const int bx0 = blockIdx.x * 64 * SEQ_PX, by0 = a.row_begin + blockIdx.y * 4;
-    const uint64_t cand = seq_tile_mask(a, bx0, bx0 + 64 * SEQ_PX, by0, by0 + 4);
+    const uint64_t cand = seq_tile_mask<RING>(a, bx0, bx0 + 64 * SEQ_PX, by0, by0 + 4);
     const int cx0 = bx0 + (threadIdx.x & 63) * SEQ_PX;
     const int cy = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
-    if (cx0 >= a.fw || cy >= a.row_end) return;
+    if ((!RING && cx0 >= a.fw) || cy >= a.row_end) return;
     unsigned char* out = a.dst + ((size_t)cy * a.fw + cx0) * 3;
     uint32_t px[SEQ_PX];
 #pragma unroll
     for (int j = 0; j < SEQ_PX; ++j)
-        px[j] = cx0 + j < a.fw ? seq_pixel<FEATHER, GAIN, PROJ>(a, cand, cx0 + j, cy, seq_gains(l), seq_rays(l)) : 0u;
-    if (cx0 + SEQ_PX <= a.fw) {
+        px[j] = (RING || cx0 + j < a.fw) ? seq_pixel<FEATHER, GAIN, PROJ, RING>(a, cand, cx0 + j, cy, seq_gains(l), seq_rays(l)) : 0u;
+    if (RING || cx0 + SEQ_PX <= a.fw) {
         pk3 w;
         w.a = px[0] | (px[1] << 24);
         w.b = (px[1] >> 8) | (px[2] << 16);
@@ -54,12 +57,12 @@ void seq_put(const void* host, size_t words, uint64_t* dev, hipStream_t s) {
     }
 }
 
-template <bool FEATHER, bool GAIN, bool PROJ = false>
+template <bool FEATHER, bool GAIN, bool PROJ = false, bool RING = false>
 static void seq_host_rows(const SeqArgs& a, const double* gains, SeqRays rays = SeqRays{nullptr, nullptr}) {
     const uint64_t all = seq_all(a.n);
     for (int cy = a.row_begin; cy < a.row_end; ++cy)
         for (int cx = 0; cx < a.fw; ++cx) {
-            const uint32_t p = seq_pixel<FEATHER, GAIN, PROJ>(a, all, cx, cy, gains, rays);
+            const uint32_t p = seq_pixel<FEATHER, GAIN, PROJ, RING>(a, all, cx, cy, gains, rays);
             unsigned char* out = a.dst + ((size_t)cy * a.fw + cx) * 3;
             out[0] = (unsigned char)p; out[1] = (unsigned char)(p >> 8); out[2] = (unsigned char)(p >> 16);
         }
@@ -68,7 +71,7 @@ static void seq_host_rows(const SeqArgs& a, const double* gains, SeqRays rays = 
 // ---- the gain rule's overlap statistics (include/rwh.h) ----
 // The images that cover canvas pixel (cx, cy), bit i = image i (cand: bits of image indices), by the sequence rule's Coverage:
 // seq_sample's own test, its taps unused.  rays: the ray tables, read with PROJ only.
-template <bool PROJ = false>
+template <bool PROJ = false, bool RING = false>
 __host__ __device__ __forceinline__ uint64_t seq_cover(const SeqArgs& a, uint64_t cand, int cx, int cy, SeqRays rays = SeqRays{nullptr, nullptr}) {
     const int fx = a.ox + cx, fy = a.oy + cy;
     SeqRay ray;
@@ -77,18 +80,18 @@ __host__ __device__ __forceinline__ uint64_t seq_cover(const SeqArgs& a, uint64_
     for (uint64_t m = cand; m; m &= m - 1) {
         const int i = __builtin_ctzll(m);
         double v[3], g = 0.0;
-        if (seq_sample<false, false, PROJ>(a.desc[i], i == a.anchor, fx, fy, v, g, 1.0, &ray)) cov |= 1ull << i;
+        if (seq_sample<false, false, PROJ, RING>(a.desc[i], i == a.anchor, fx, fy, v, g, 1.0, &ray, a.fw)) cov |= 1ull << i;
     }
     return cov;
 }
 
 // L_i of the gain rule: the sum of the three bytes paste would write for image i at a canvas pixel that it covers.
-template <bool PROJ = false>
+template <bool PROJ = false, bool RING = false>
 __host__ __device__ __forceinline__ uint32_t seq_byte_sum(const SeqArgs& a, int i, int cx, int cy, SeqRays rays = SeqRays{nullptr, nullptr}) {
     double v[3], g = 0.0;
     SeqRay ray;
     if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
-    if (!seq_sample<false, false, PROJ>(a.desc[i], i == a.anchor, a.ox + cx, a.oy + cy, v, g, 1.0, &ray)) return 0u;
+    if (!seq_sample<false, false, PROJ, RING>(a.desc[i], i == a.anchor, a.ox + cx, a.oy + cy, v, g, 1.0, &ray, a.fw)) return 0u;
     return (uint32_t)(unsigned char)(int)v[0] + (uint32_t)(unsigned char)(int)v[1] + (uint32_t)(unsigned char)(int)v[2];
 }
 
@@ -106,8 +109,9 @@ __host__ __device__ __forceinline__ int seq_slab_words(int n) { return (2 * n * 
 
 // The candidates of the samples [u0, u1) x [v0, v1): the images whose rectangles meet the canvas pixels between the first and the
 // last of them.
+template <bool RING = false>
 __host__ __device__ __forceinline__ uint64_t seq_stat_mask(const StatArgs& s, int u0, int u1, int v0, int v1) {
-    return seq_tile_mask(s.a, u0 * s.stride, (u1 - 1) * s.stride + 1, v0 * s.stride, (v1 - 1) * s.stride + 1);
+    return seq_tile_mask<RING>(s.a, u0 * s.stride, (u1 - 1) * s.stride + 1, v0 * s.stride, (v1 - 1) * s.stride + 1);
 }
 
 __device__ __forceinline__ uint32_t seq_wave_sum(uint32_t v) {
@@ -123,7 +127,7 @@ __device__ __forceinline__ uint32_t seq_wave_sum(uint32_t v) {
 // integer atomic add per non-zero count and sum per block, into the block's slab.  Integer adds commute: the tables do not depend
 // on the order.
 constexpr int STAT_W = 256, STAT_H = 4;
-template <bool PROJ = false>
+template <bool PROJ = false, bool RING = false>
 __global__ __launch_bounds__(256) void seq_stats_kernel(const SeqWith<StatArgs, false, PROJ> l) {
     const StatArgs& s = l.a;
     static_assert(STAT_W * STAT_H * 765 < (1 << 20) && STAT_W * STAT_H < (1 << 12), "count << 20 | sum in 32 bits");
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(256) void seq_stats_kernel(const SeqWith<StatArgs, 
     const SeqArgs& a = s.a;
     const int u0 = blockIdx.x * STAT_W, v0 = blockIdx.y * STAT_H;
     const int u1 = u0 + STAT_W < s.nsx ? u0 + STAT_W : s.nsx, v1 = v0 + STAT_H < s.nsy ? v0 + STAT_H : s.nsy;
-    const uint64_t cand = seq_stat_mask(s, u0, u1, v0, v1);
+    const uint64_t cand = seq_stat_mask<RING>(s, u0, u1, v0, v1);
     const int nc = __builtin_popcountll(cand);
     if (nc == 0) return;                                   // (block-uniform)
     for (int t = threadIdx.x; t < nc * nc; t += 256) acc[t] = 0u;
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(256) void seq_stats_kernel(const SeqWith<StatArgs, 
     const int cy = v * s.stride;
     uint64_t cov[SEQ_PX];
 #pragma unroll
-    for (int k = 0; k < SEQ_PX; ++k) cov[k] = (u + k < s.nsx && v < s.nsy) ? seq_cover<PROJ>(a, cand, (u + k) * s.stride, cy, seq_rays(l)) : 0ull;
+    for (int k = 0; k < SEQ_PX; ++k) cov[k] = (u + k < s.nsx && v < s.nsy) ? seq_cover<PROJ, RING>(a, cand, (u + k) * s.stride, cy, seq_rays(l)) : 0ull;
     int ri = 0;
     for (uint64_t mi = cand; mi; mi &= mi - 1, ++ri) {
         const int i = __builtin_ctzll(mi);
@@ -153,7 +157,7 @@ __global__ __launch_bounds__(256) void seq_stats_kernel(const SeqWith<StatArgs, 
 #pragma unroll
         for (int k = 0; k < SEQ_PX; ++k) {
             const bool c = cov[k] >> i & 1;
-            L[k] = c ? seq_byte_sum<PROJ>(a, i, (u + k) * s.stride, cy, seq_rays(l)) : 0u;
+            L[k] = c ? seq_byte_sum<PROJ, RING>(a, i, (u + k) * s.stride, cy, seq_rays(l)) : 0u;
             any |= c;
         }
         if (!__any(any)) continue;                         // (wave-uniform)
@@ -197,9 +201,9 @@ static int64_t seq_stat_table_bytes(int n) { return ((int64_t)n * (int64_t)sizeo
 // buffer and all rows) plus the stride range.
 static int seq_stat_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
                             int canvas_h, int canvas_w, int origin_x, int origin_y, int stride, uint64_t* count, uint64_t* sum,
-                            SeqDesc* descs, StatArgs& s, bool proj = false) {
+                            SeqDesc* descs, StatArgs& s, bool proj = false, bool ring = false) {
     if (!count || !sum || stride < 1 || stride > 255) return RWH_E_INVALID;
-    const int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, count, canvas_h, canvas_w, origin_x, origin_y, descs, s.a, proj);
+    const int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, count, canvas_h, canvas_w, origin_x, origin_y, descs, s.a, proj, ring);
     if (st != RWH_OK) return st;
     s.a.dst = nullptr;
     s.stride = stride;
@@ -218,8 +222,8 @@ extern "C" int64_t rwh_stitch_sequence_workspace_bytes(int n) {
 }
 
 // The device compositor behind rwh_stitch_sequence_ex (PROJ false: rays unused) and rwh_stitch_sequence_proj (PROJ true: mats holds
-// the M_i, no anchor, origin (0, 0)).
-template <bool PROJ>
+// the M_i, no anchor, origin (0, 0)) and rwh_stitch_sequence_ring (RING with PROJ: canvas_w is the period).
+template <bool PROJ, bool RING = false>
 static int seq_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
                       const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
                       int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes, void* stream, const double* gains,
@@ -228,7 +232,7 @@ static int seq_device(const void* const* d_images, const int32_t* hw, const doub
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SeqArgs a;
     const int st = seq_prepare(d_images, hw, mats, rects, n, anchor, order, blend, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                               row_begin, row_end, descs, a, PROJ);
+                               row_begin, row_end, descs, a, PROJ, RING);
     if (st != RWH_OK) return st;
     if (!d_workspace || workspace_bytes < rwh_stitch_sequence_workspace_bytes(n) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
     if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
@@ -240,13 +244,13 @@ static int seq_device(const void* const* d_images, const int32_t* hw, const doub
     a.desc = reinterpret_cast<const SeqDesc*>(table);
     const dim3 grid((canvas_w + 64 * SEQ_PX - 1) / (64 * SEQ_PX), (row_end - row_begin + 3) / 4);
     seq_dispatch(blend == RWH_SEQ_FEATHER, gains != nullptr, [&](auto feather, auto gain) {
-        hipLaunchKernelGGL((seq_kernel<decltype(feather)::value, decltype(gain)::value, PROJ>), grid, dim3(256), 0, s,
+        hipLaunchKernelGGL((seq_kernel<decltype(feather)::value, decltype(gain)::value, PROJ, RING>), grid, dim3(256), 0, s,
                            (seq_with<decltype(gain)::value, PROJ>(a, gains, n, rays)));
     });
     return check_launch();
 }
 
-template <bool PROJ>
+template <bool PROJ, bool RING = false>
 static int seq_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
                     const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
                     int row_begin, int row_end, const double* gains, rwh::SeqRays rays) {
@@ -254,12 +258,12 @@ static int seq_host(const void* const* images, const int32_t* hw, const double* 
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SeqArgs a;
     const int st = seq_prepare(images, hw, mats, rects, n, anchor, order, blend, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                               row_begin, row_end, descs, a, PROJ);
+                               row_begin, row_end, descs, a, PROJ, RING);
     if (st != RWH_OK) return st;
     if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
     if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
     seq_dispatch(blend == RWH_SEQ_FEATHER, gains != nullptr,
-                 [&](auto feather, auto gain) { seq_host_rows<decltype(feather)::value, decltype(gain)::value, PROJ>(a, gains, rays); });
+                 [&](auto feather, auto gain) { seq_host_rows<decltype(feather)::value, decltype(gain)::value, PROJ, RING>(a, gains, rays); });
     return RWH_OK;
 }
 
@@ -277,6 +281,14 @@ extern "C" int rwh_stitch_sequence_proj(const void* const* d_images, const int32
                                         void* stream, const double* gains) {
     return seq_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, d_canvas, canvas_h, canvas_w, 0, 0,
                             row_begin, row_end, d_workspace, workspace_bytes, stream, gains, rwh::SeqRays{d_col, d_row});
+}
+
+extern "C" int rwh_stitch_sequence_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                        const int32_t* order, int blend, const double* d_col, const double* d_row, void* d_canvas,
+                                        int canvas_h, int canvas_w, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                        void* stream, const double* gains) {
+    return seq_device<true, true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, d_canvas, canvas_h, canvas_w, 0, 0,
+                                  row_begin, row_end, d_workspace, workspace_bytes, stream, gains, rwh::SeqRays{d_col, d_row});
 }
 
 extern "C" int rwh_stitch_sequence(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
@@ -301,6 +313,13 @@ extern "C" int rwh_host_stitch_sequence_proj(const void* const* images, const in
                           row_begin, row_end, gains, rwh::SeqRays{col, row});
 }
 
+extern "C" int rwh_host_stitch_sequence_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                             const int32_t* order, int blend, const double* col, const double* row, void* canvas,
+                                             int canvas_h, int canvas_w, int row_begin, int row_end, const double* gains) {
+    return seq_host<true, true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, canvas, canvas_h, canvas_w, 0, 0,
+                                row_begin, row_end, gains, rwh::SeqRays{col, row});
+}
+
 extern "C" int rwh_host_stitch_sequence(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                         int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
                                         int origin_x, int origin_y, int row_begin, int row_end) {
@@ -314,7 +333,7 @@ extern "C" int64_t rwh_sequence_overlap_stats_workspace_bytes(int n, int canvas_
     return rwh::seq_stat_table_bytes(n) + (int64_t)rwh::STAT_SLABS * rwh::seq_slab_words(n) * (int64_t)sizeof(uint64_t);
 }
 
-template <bool PROJ>
+template <bool PROJ, bool RING = false>
 static int seq_stat_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
                            int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
                            uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays) {
@@ -322,7 +341,7 @@ static int seq_stat_device(const void* const* d_images, const int32_t* hw, const
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     StatArgs a;
     const int st = seq_stat_prepare(d_images, hw, mats, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, d_count, d_sum,
-                                    descs, a, PROJ);
+                                    descs, a, PROJ, RING);
     if (st != RWH_OK) return st;
     if (!d_workspace || workspace_bytes < rwh_sequence_overlap_stats_workspace_bytes(n, canvas_h, canvas_w, stride) ||
         ((uintptr_t)d_workspace & 7u) || ((uintptr_t)d_count & 7u) || ((uintptr_t)d_sum & 7u)) return RWH_E_INVALID;
@@ -334,7 +353,7 @@ static int seq_stat_device(const void* const* d_images, const int32_t* hw, const
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
     a.a.desc = reinterpret_cast<const SeqDesc*>(table);
     const dim3 grid((a.nsx + STAT_W - 1) / STAT_W, (a.nsy + STAT_H - 1) / STAT_H);
-    hipLaunchKernelGGL((seq_stats_kernel<PROJ>), grid, dim3(256), 0, s, (seq_with<false, PROJ>(a, nullptr, n, rays)));
+    hipLaunchKernelGGL((seq_stats_kernel<PROJ, RING>), grid, dim3(256), 0, s, (seq_with<false, PROJ>(a, nullptr, n, rays)));
     hipLaunchKernelGGL(seq_stats_sum_kernel, dim3((2 * n * n + 255) / 256), dim3(256), 0, s, a.slabs, a.slab_words, n * n,
                        reinterpret_cast<unsigned long long*>(d_count), reinterpret_cast<unsigned long long*>(d_sum));
     return check_launch();
@@ -354,14 +373,14 @@ extern "C" int rwh_sequence_overlap_stats_proj(const void* const* d_images, cons
                                  d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
 }
 
-template <bool PROJ>
+template <bool PROJ, bool RING = false>
 static int seq_stat_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
                          int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
                          uint64_t* count, uint64_t* sum, rwh::SeqRays rays) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     StatArgs a;
-    const int st = seq_stat_prepare(images, hw, mats, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, count, sum, descs, a, PROJ);
+    const int st = seq_stat_prepare(images, hw, mats, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, count, sum, descs, a, PROJ, RING);
     if (st != RWH_OK) return st;
     if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
     uint64_t* cnt = count;
@@ -372,10 +391,10 @@ static int seq_stat_host(const void* const* images, const int32_t* hw, const dou
     for (int v = 0; v < a.nsy; ++v)
         for (int u = 0; u < a.nsx; ++u) {
             const int cx = u * stride, cy = v * stride;
-            const uint64_t cov = seq_cover<PROJ>(a.a, all, cx, cy, rays);
+            const uint64_t cov = seq_cover<PROJ, RING>(a.a, all, cx, cy, rays);
             for (uint64_t mi = cov; mi; mi &= mi - 1) {
                 const int i = __builtin_ctzll(mi);
-                const uint64_t l = seq_byte_sum<PROJ>(a.a, i, cx, cy, rays);
+                const uint64_t l = seq_byte_sum<PROJ, RING>(a.a, i, cx, cy, rays);
                 for (uint64_t mj = cov; mj; mj &= mj - 1) {
                     const int j = __builtin_ctzll(mj);
                     cnt[(size_t)i * n + j] += 1;
@@ -384,6 +403,20 @@ static int seq_stat_host(const void* const* images, const int32_t* hw, const dou
             }
         }
     return RWH_OK;
+}
+
+extern "C" int rwh_sequence_overlap_stats_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                               const double* d_col, const double* d_row, int canvas_h, int canvas_w, int stride,
+                                               uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    return seq_stat_device<true, true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, stride, d_count, d_sum,
+                                       d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
+}
+
+extern "C" int rwh_host_sequence_overlap_stats_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                    const double* col, const double* row, int canvas_h, int canvas_w, int stride,
+                                                    uint64_t* count, uint64_t* sum) {
+    return seq_stat_host<true, true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, stride, count, sum,
+                                     rwh::SeqRays{col, row});
 }
 
 extern "C" int rwh_host_sequence_overlap_stats(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,

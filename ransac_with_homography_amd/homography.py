@@ -855,6 +855,74 @@ def _projected_canvas(shapes, Gs, anchor, projection, focal):
     return rects, (ox, oy), (fh, fw), order
 
 
+RING_TILE, RING_MAX_PERIOD = 256, 65280
+
+
+def sequence_period(focal):
+    """The default period of the ring rule (include/rwh.h) for a focal length in pixels: P = 256 * max(1, rint(2 pi f / 256)), the
+    multiple of 256 nearest the circumference of a cylinder of radius f.  ValueError: a focal that is not finite and > 0, a period
+    above 65280."""
+    _check_projection("sequence_period", PROJECTIONS[0], focal)
+    period = RING_TILE * max(1, int(np.rint(2.0 * np.pi * float(focal) / RING_TILE)))
+    if period > RING_MAX_PERIOD:
+        raise ValueError("sequence_period: focal=%r gives a period of %d columns; at most %d" % (focal, period, RING_MAX_PERIOD))
+    return period
+
+
+def _check_wrap(who, wrap, projection, focal):
+    """The period of a `wrap=` argument, None for wrap=False; ValueError for a wrap without a projection or one that is neither a bool
+    nor a positive multiple of 256 up to 65280.  (projection, focal) have passed `_check_projection`."""
+    if wrap is False:
+        return None
+    if wrap is not True and not (isinstance(wrap, (int, np.integer)) and not isinstance(wrap, (bool, np.bool_))
+                                 and 0 < wrap <= RING_MAX_PERIOD and wrap % RING_TILE == 0):
+        raise ValueError("%s: wrap=%r; False, True or a period in columns, a positive multiple of %d up to %d"
+                         % (who, wrap, RING_TILE, RING_MAX_PERIOD))
+    if projection is None:
+        raise ValueError("%s: wrap=%r without a projection" % (who, wrap))
+    return sequence_period(focal) if wrap is True else int(wrap)
+
+
+def _ring_canvas(shapes, Gs, anchor, projection, focal, period):
+    """Rectangles (in UNWRAPPED surface pixels: a rectangle may start left of -P / 2 or end right of P / 2), canvas and default order
+    of the ring rule (include/rwh.h) for oriented G_i and the period P: -> (rects, (-P / 2, oy), (fh, P), order), or the rule's
+    ValueError."""
+    n = len(shapes)
+    rho = period / (2.0 * np.pi)
+    kinv = np.linalg.inv(_camera(shapes[anchor], focal))
+    rects = []
+    for i, (shape, G) in enumerate(zip(shapes, Gs)):
+        h, w = int(shape[0]), int(shape[1])
+        if h < 2 or w < 2:
+            raise ValueError("sequence: image %d is %d x %d; sides of 2 at least" % (i, h, w))
+        with np.errstate(all="ignore"):
+            rays = kinv @ (G @ _perimeter(h, w))
+            theta = np.arctan2(rays[0], rays[2])
+            v = _surface(rays, projection, rho)[1]
+        if not (np.isfinite(theta).all() and np.isfinite(v).all() and np.abs(v).max() < 2.0 ** 30):
+            raise ValueError("sequence: image %d has a perimeter point on the %s surface that is not finite" % (i, projection))
+        step = np.diff(np.append(theta, theta[0]))
+        wrapped = (step + np.pi) % (2.0 * np.pi) - np.pi
+        if int(np.rint(wrapped.sum() / (2.0 * np.pi))) != 0:
+            raise ValueError("sequence: image %d contains a pole of the %s surface" % (i, projection))
+        u = rho * np.cumsum(np.append(theta[0], wrapped[:-1]))
+        lo, my = int(np.floor(u.min())) - 1, int(np.floor(v.min())) - 1
+        rects.append((lo, my, min(int(np.ceil(u.max())) + 1 - lo + 1, period), int(np.ceil(v.max())) + 1 - my + 1))
+    oy = min(r[1] for r in rects)
+    fh = max(r[1] + r[3] for r in rects) - oy
+    if fh > 65535 or period * fh * 3 > 2 ** 31 - 1:
+        raise ValueError("sequence: a %d x %d canvas; sides of at most 65535 and at most 2^31 - 1 bytes" % (fh, period))
+    order = sorted(range(n), key=lambda i: (abs(i - anchor), i))
+    return rects, (-(period // 2), oy), (fh, period), order
+
+
+def _curved_canvas(shapes, Gs, anchor, projection, focal, period):
+    """`_projected_canvas`, or with a period `_ring_canvas`."""
+    if period is None:
+        return _projected_canvas(shapes, Gs, anchor, projection, focal)
+    return _ring_canvas(shapes, Gs, anchor, projection, focal, period)
+
+
 def sequence_ray_tables(projection, focal, origin, size):
     """The two ray tables of the projection rule (include/rwh.h) for a canvas of size (fh, fw) whose pixel (0, 0) is surface point
     origin = (ox, oy): -> (col float64 [fw, 2], row float64 [fh, 2]); col[cx] = (sin(u / f), cos(u / f)) with u = ox + cx,
@@ -913,7 +981,7 @@ def sequence_focal(shapes, Hs, pairs=None):
     return float(np.median(found))
 
 
-def sequence_plan(shapes, Hs, anchor=0, projection=None, focal=None):
+def sequence_plan(shapes, Hs, anchor=0, projection=None, focal=None, wrap=False):
     """The geometry of a sequence panorama from its pairwise homographies; pure numpy, no GPU.
 
     shapes: N image shapes (h, w[, c]); Hs: N - 1 matrices, Hs[i] maps image i+1 into image i -- what
@@ -927,10 +995,17 @@ def sequence_plan(shapes, Hs, anchor=0, projection=None, focal=None):
     anchor's camera, with `focal` (pixels, finite and > 0) its radius (the projection rule of include/rwh.h).  The 5-tuple is the
     same, with Gs each multiplied by the sign of its determinant and rectangles and origin in SURFACE pixels.  ValueError in
     addition: an unknown projection, one without the other of projection and focal, a determinant that is zero or not finite, a
-    perimeter point that is not finite, an image that straddles the seam behind the anchor or contains a pole."""
+    perimeter point that is not finite, an image that straddles the seam behind the anchor or contains a pole.
+
+    wrap: False -- as above; True or a period P in columns (a positive multiple of 256 up to 65280; True is `sequence_period(focal)`)
+    -- the canvas closes the circle (the ring rule of include/rwh.h): the surface has the radius P / (2 pi) while the cameras keep
+    `focal`, the rectangles are in UNWRAPPED surface pixels (one may pass -P / 2 or P / 2; no image is refused for lying across the
+    seam), the origin is (-P / 2, oy) and the size (fh, P).  ValueError in addition: wrap without a projection, a wrap that is
+    neither a bool nor such a period."""
     n = len(shapes)
     _check_count(n, anchor)
     _check_projection("sequence_plan", projection, focal)
+    period = _check_wrap("sequence_plan", wrap, projection, focal)
     Hs = [np.asarray(H, dtype=np.float64) for H in Hs]
     if len(Hs) != n - 1 or any(H.shape != (3, 3) for H in Hs):
         raise ValueError("sequence: %d images take %d 3 x 3 homographies, got %d" % (n, n - 1, len(Hs)))
@@ -945,7 +1020,7 @@ def sequence_plan(shapes, Hs, anchor=0, projection=None, focal=None):
     Gs[anchor] = np.eye(3)
     if projection is not None:
         Gs = _oriented(Gs)
-        rects, origin, size, order = _projected_canvas(shapes, Gs, anchor, projection, focal)
+        rects, origin, size, order = _curved_canvas(shapes, Gs, anchor, projection, focal, period)
         return Gs, rects, origin, size, order
     rects, origin, size, order = _sequence_canvas(shapes, Gs, anchor)
     return Gs, rects, origin, size, order
@@ -1381,13 +1456,16 @@ def sequence_adjust_cameras(shapes, Rs, fs, pairs, matches, masks=None, anchor=0
     return Rs, fs
 
 
-def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None):
+def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None, wrap=False):
     """What stitchSequence and sequence_gains check of their images and geometry, before any GPU use: -> (rects, origin, size,
     default order, inv_g float64 [N, 3, 3], rays).  rays is None on the anchor's plane.  With a projection it is the two ray tables
-    (numpy), the rectangles are in canvas coordinates and the matrices are the M_i = inv(G_i) @ K of the projection rule."""
+    (numpy), the rectangles are in canvas coordinates and the matrices are the M_i = inv(G_i) @ K of the projection rule.  With
+    wrap (the ring rule) the canvas is (fh, P), a rectangle's mx is taken modulo P (0 for a rectangle P wide) and the tables are made
+    with the radius P / (2 pi)."""
     n = len(images)
     _check_count(n, anchor)
     _check_projection(who, projection, focal)
+    period = _check_wrap(who, wrap, projection, focal)
     if (Hs is None) == (Gs is None):
         raise ValueError("%s: exactly one of Hs and Gs" % who)
     for i, img in enumerate(images):
@@ -1395,14 +1473,14 @@ def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None):
             raise NotImplementedError("%s: image %d is %s %s; uint8 [h, w, 3] images are taken" % (who, i, img.dtype, tuple(img.shape)))
     shapes = [tuple(int(v) for v in img.shape) for img in images]
     if Hs is not None:
-        Gs, rects, origin, size, default = sequence_plan(shapes, Hs, anchor, projection, focal)
+        Gs, rects, origin, size, default = sequence_plan(shapes, Hs, anchor, projection, focal, wrap)
     else:
         Gs = np.array([np.asarray(G, dtype=np.float64) for G in Gs])
         if Gs.shape != (n, 3, 3) or not np.array_equal(Gs[anchor], np.eye(3)):
             raise ValueError("%s: Gs takes %d 3 x 3 matrices with the identity at the anchor" % (who, n))
         if projection is not None:
             Gs = _oriented(Gs)
-            rects, origin, size, default = _projected_canvas(shapes, Gs, anchor, projection, focal)
+            rects, origin, size, default = _curved_canvas(shapes, Gs, anchor, projection, focal, period)
         else:
             rects, origin, size, default = _sequence_canvas(shapes, Gs, anchor)
     if projection is not None:
@@ -1411,6 +1489,9 @@ def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None):
             m = np.stack([K if i == anchor else np.linalg.inv(Gs[i]) @ K for i in range(n)])
         if not np.isfinite(m).all():
             raise ValueError("%s: an inverse homography is not finite" % who)
+        if period is not None:
+            rects = [(0 if r[2] == period else (r[0] - origin[0]) % period, r[1] - origin[1], r[2], r[3]) for r in rects]
+            return rects, origin, size, default, m, sequence_ray_tables(projection, period / (2.0 * np.pi), origin, size)
         rects = [(r[0] - origin[0], r[1] - origin[1], r[2], r[3]) for r in rects]
         return rects, origin, size, default, m, sequence_ray_tables(projection, focal, origin, size)
     inv_g = np.stack([np.eye(3) if i == anchor else np.linalg.inv(Gs[i]) for i in range(n)])
@@ -1435,12 +1516,15 @@ def _rays_upload(rays, dev):
     return None if rays is None else tuple(_xfer.to_device(t, dev) for t in rays)
 
 
-def _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info, rays=None):
+def _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info, rays=None, ring=False):
     """One statistics launch, one download of the two n x n tables, one call of rwh_host_sequence_gains -> float64 [N].
-    rays: the device ray tables of a projected call (inv_g then holds the M_i and the rectangles are the canvas's)."""
+    rays: the device ray tables of a projected call (inv_g then holds the M_i and the rectangles are the canvas's); ring: that call
+    is one of the ring rule."""
     n = len(on_dev)
     if rays is None:
         tabs = kernels.sequence_overlap_tables(on_dev, inv_g, rects, anchor, origin, size, int(stride))
+    elif ring:
+        tabs = kernels.sequence_overlap_tables_ring(on_dev, inv_g, rects, rays[0], rays[1], size, int(stride))
     else:
         tabs = kernels.sequence_overlap_tables_proj(on_dev, inv_g, rects, rays[0], rays[1], size, int(stride))
     tabs = tabs.cpu().numpy().view(np.uint64)
@@ -1454,7 +1538,8 @@ def _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n
     return gains
 
 
-def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, sigma_g=0.1, info=None, projection=None, focal=None):
+def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, sigma_g=0.1, info=None, projection=None, focal=None,
+                   wrap=False):
     """One exposure gain per image of a sequence (the gain rule of include/rwh.h; Brown & Lowe 2007, section 6): the overlap
     statistics of the images, warped as `stitchSequence` warps them, are reduced on the GPU in one pass over every stride-th canvas
     pixel each way (`rwh_sequence_overlap_stats`), the two N x N integer tables come down in one copy, and the N x N system is
@@ -1463,12 +1548,15 @@ def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, s
     images, Hs, Gs, anchor: as `stitchSequence`'s, and refused as there.  sigma_n (10.0): the standard deviation of the intensity
     error, on the 0 .. 255 scale; sigma_g (0.1): that of the gain about 1.  stride=4 is a convention -- a sixteenth of the samples
     moves the gains of the test scenes in the third decimal -- not a measured optimum.  `info`: optional dict, receives "count" and
-    "sum" (uint64 [N, N]).  projection, focal: as `stitchSequence`'s -- the statistics are taken on that canvas.  ValueError: a
-    stride outside 1 .. 255, a sigma that is not finite and > 0, before the GPU is touched."""
-    rects, origin, size, _, inv_g, rays = _sequence_inputs("sequence_gains", images, Hs, Gs, anchor, projection, focal)
+    "sum" (uint64 [N, N]), and with wrap "period" and "radius".  projection, focal, wrap: as `stitchSequence`'s -- the statistics
+    are taken on that canvas.  ValueError: a stride outside 1 .. 255, a sigma that is not finite and > 0, before the GPU is touched."""
+    rects, origin, size, _, inv_g, rays = _sequence_inputs("sequence_gains", images, Hs, Gs, anchor, projection, focal, wrap)
     _check_gain_options("sequence_gains", stride, sigma_n, sigma_g)
+    ring = wrap is not False
+    if ring and info is not None:
+        info["period"], info["radius"] = int(size[1]), int(size[1]) / (2.0 * np.pi)
     on_dev = _sequence_upload(images)
-    return _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info, _rays_upload(rays, on_dev[0].device))
+    return _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info, _rays_upload(rays, on_dev[0].device), ring)
 
 
 def _check_bands(who, bands):
@@ -1476,7 +1564,7 @@ def _check_bands(who, bands):
 
 
 def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None, gains=None, info=None, projection=None, focal=None,
-                   bands=5):
+                   wrap=False, bands=5):
     """N images into one panorama in ONE pass over the canvas (`rwh_stitch_sequence`): every image is warped once into the
     anchor's frame and every canvas pixel written once.  The reference has no counterpart -- its stitchPanorama takes two images,
     and folding it over a list resamples the growing canvas once per image; this is held to the sequence rule stated in
@@ -1499,7 +1587,13 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     projection: None -- the canvas is the anchor's image plane, which suits a narrow sweep (at 100 degrees off the anchor the plane
     is behind the camera); "cylindrical" or "spherical" -- the canvas is that surface about the anchor's camera with radius `focal`
     (pixels; `sequence_focal` estimates one from Hs), held to the projection rule of include/rwh.h: every image is warped, the
-    anchor included, and all blends, gains and bands work on it as on the plane.  A sweep that closes the circle is refused.
+    anchor included, and all blends, gains and bands work on it as on the plane.  Without `wrap` an image that lies across the
+    seam behind the anchor is refused.
+    wrap: False; True or a period P in columns (a positive multiple of 256 up to 65280; True is `sequence_period(focal)`) -- a sweep
+    that closes the circle, on a canvas exactly P columns wide that wraps around at the seam behind the anchor (the ring rule of
+    include/rwh.h): the surface has the radius P / (2 pi), the cameras keep `focal`, an image may lie across the seam, and all
+    blends, gains and bands work across it.  It takes a projection.  `info` then also receives "period" and "radius".  `bands` stays
+    the last parameter: pass it, and `wrap`, by name.
     ValueError: what `sequence_plan` refuses, an `order` that is not a permutation, another `blending`, gains of another length,
     not finite or <= 0, or another string; NotImplementedError: images that are not uint8 [h, w, 3]."""
     n = len(images)
@@ -1509,7 +1603,8 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     if blending == "multiband":
         _check_bands("stitchSequence", bands)
     blend = _lib.RWH_SEQ_FEATHER if blending == "feather" else _lib.RWH_SEQ_PASTE
-    rects, origin, size, default, inv_g, rays = _sequence_inputs("stitchSequence", images, Hs, Gs, anchor, projection, focal)
+    rects, origin, size, default, inv_g, rays = _sequence_inputs("stitchSequence", images, Hs, Gs, anchor, projection, focal, wrap)
+    ring = wrap is not False
     order = default if order is None else [int(v) for v in order]
     if sorted(order) != list(range(n)):
         raise ValueError("stitchSequence: order %r is not a permutation of 0 .. %d" % (order, n - 1))
@@ -1522,10 +1617,17 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     on_dev = _sequence_upload(images)
     rays = _rays_upload(rays, on_dev[0].device)
     if isinstance(gains, str):
-        gains = _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, 4, 10.0, 0.1, None, rays)
+        gains = _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, 4, 10.0, 0.1, None, rays, ring)
     if info is not None:
         info["gains"] = gains
-    if rays is not None:
+        if ring:
+            info["period"], info["radius"] = int(size[1]), int(size[1]) / (2.0 * np.pi)
+    if ring:
+        if blending == "multiband":
+            out = kernels.stitch_sequence_multiband_ring(on_dev, inv_g, rects, rays[0], rays[1], size, int(bands), gains=gains)
+        else:
+            out = kernels.stitch_sequence_ring(on_dev, inv_g, rects, rays[0], rays[1], order, blend, size, gains=gains)
+    elif rays is not None:
         if blending == "multiband":
             out = kernels.stitch_sequence_multiband_proj(on_dev, inv_g, rects, rays[0], rays[1], size, int(bands), gains=gains)
         else:

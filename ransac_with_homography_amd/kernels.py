@@ -1068,6 +1068,73 @@ def stitch_sequence_multiband_proj(images, m, rects, col, row, canvas_hw, bands,
     return out
 
 
+_RING_REFUSED = ("%s: the library refused the arguments (include/rwh.h, the ring rule: %s, a period that is a multiple of 256, rectangles "
+                 "that start on the canvas and are at most one period wide, finite M, the tables)")
+
+
+def stitch_sequence_ring(images, m, rects, col, row, order, blend, canvas_hw, rows=None, out=None, gains=None):
+    """Launch the sequence compositor on a wrap-around canvas (rwh_stitch_sequence_ring; the ring rule of include/rwh.h): every
+    argument as `stitch_sequence_proj`'s, with canvas_hw = (fh, P), P the period, and rects (mx, my, wt, ht) in canvas coordinates
+    with 0 <= mx < P, wt <= P and mx + wt allowed past the edge -> canvas [fh, P, 3] uint8, on torch's current stream.  What the
+    library refuses (RWH_E_INVALID) raises ValueError."""
+    lib = _lib.load()
+    who = "stitch_sequence_ring"
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, mm, rc, od = _sequence_marshal(who, images, m, rects, canvas_hw, order)
+    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    out = _sequence_canvas(images, fh, fw, out)
+    r0, r1 = (0, fh) if rows is None else (int(rows[0]), int(rows[1]))
+    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
+    status = lib.rwh_stitch_sequence_ring(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, od.ctypes.data, int(blend),
+                                          pc, pr, _ptr(out), fh, fw, r0, r1, _ptr(ws), ws.numel() * 8, _lib.stream_ptr(),
+                                          None if gains is None else gains.ctypes.data)
+    _sequence_status(status, "rwh_stitch_sequence_ring", _RING_REFUSED % (who, "order, row range"))
+    return out
+
+
+def sequence_overlap_tables_ring(images, m, rects, col, row, canvas_hw, stride):
+    """The overlap statistics of the gain rule on a wrap-around canvas (rwh_sequence_overlap_stats_ring): images, m, rects, col, row,
+    canvas_hw as `stitch_sequence_ring`'s, stride as `sequence_overlap_stats`'s -> one int64 [2, n, n] GPU tensor (count, sum)."""
+    lib = _lib.load()
+    who = "sequence_overlap_tables_ring"
+
+    def own():
+        if not (isinstance(stride, (int, np.integer)) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
+            raise ValueError("%s: stride %r; 1 .. %d" % (who, stride, _lib.RWH_SEQ_MAX_STRIDE))
+    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=own)
+    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    dev = images[0].device
+    tabs = torch.empty((2, n, n), dtype=torch.int64, device=dev)
+    ws = torch.empty((int(lib.rwh_sequence_overlap_stats_workspace_bytes(n, fh, fw, int(stride))) // 8,), dtype=torch.int64, device=dev)
+    status = lib.rwh_sequence_overlap_stats_ring(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, pc, pr, fh, fw,
+                                                 int(stride), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
+    _sequence_status(status, "rwh_sequence_overlap_stats_ring", _RING_REFUSED % (who, "stride"))
+    return tabs
+
+
+def stitch_sequence_multiband_ring(images, m, rects, col, row, canvas_hw, bands, gains=None, out=None):
+    """Launch the multi-band compositor on a wrap-around canvas (rwh_stitch_multiband_ring): images, m, rects, col, row, canvas_hw
+    as `stitch_sequence_ring`'s; bands, gains, out as `stitch_sequence_multiband`'s -> canvas [fh, P, 3] uint8.  The workspace is
+    allocated here, of rwh_stitch_multiband_ring_workspace_bytes bytes."""
+    lib = _lib.load()
+    who = "stitch_sequence_multiband_ring"
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
+    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    out = _sequence_canvas(images, fh, fw, out)
+    need = int(lib.rwh_stitch_multiband_ring_workspace_bytes(rc.ctypes.data, n, fh, fw, int(bands)))
+    if need <= 0:
+        raise ValueError(_RING_REFUSED % (who, "bands"))
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
+    status = lib.rwh_stitch_multiband_ring(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, int(bands),
+                                           None if gains is None else gains.ctypes.data, pc, pr, _ptr(out), fh, fw,
+                                           _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
+    _sequence_status(status, "rwh_stitch_multiband_ring", _RING_REFUSED % (who, "bands"))
+    return out
+
+
 def decode_best(best_words, k_total):
     """Unpack the two argmax words (host ints) -> (winner_index, count, early_exit).
     Word 1 (first index reaching `need`) takes precedence, like the reference's

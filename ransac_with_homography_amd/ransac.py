@@ -53,10 +53,10 @@ from . import _lapack, _lib, kernels
 from .features import (DeviceProblems, _host_rows, default_pattern, detect_and_describe, extract_batch, match_batch,  # noqa: F401
                        match_descriptors, match_descriptors_ratio, match_graph, match_ratio, orb_bin_table, orb_layout,
                        orb_level_quotas, orb_scales, rotate_pattern)
-from .homography import (_check_bands, _check_focal, _check_pairs, _check_projection, _oriented, _pair_rows, _sequence_inputs,  # noqa: F401
-                         calcHomography, calcHomographyLinear, cylindericlMap, sequence_adjust, sequence_adjust_cameras,
-                         sequence_camera_maps, sequence_cameras, sequence_focal, sequence_gains, sequence_graph, sequence_plan,
-                         stitchPanorama, stitchSequence)
+from .homography import (_check_bands, _check_focal, _check_pairs, _check_projection, _check_wrap, _oriented, _pair_rows,  # noqa: F401
+                         _sequence_inputs, calcHomography, calcHomographyLinear, cylindericlMap, sequence_adjust,
+                         sequence_adjust_cameras, sequence_camera_maps, sequence_cameras, sequence_focal, sequence_gains,
+                         sequence_graph, sequence_period, sequence_plan, stitchPanorama, stitchSequence)
 
 # Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
 # in csrc/rwh_settle.h.  RESCORE_MARGIN caps the margin of the 'backward' / 'reproj' rule: an unflagged K1 count moves by <= 2
@@ -814,7 +814,34 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     `extract_batch`: the pairs -- adjacent or of the graph -- are then matched by `match_graph(feats, pairs, ratio)`, Lowe's ratio
     test with every image's descriptors held once, in place of `match_batch`'s cross-check.  With pairs="all" that is the matcher to
     use: cross-check's unsupported matches raise the bar of `sequence_graph`'s acceptance rule and can cost a true overlap.
-    Without the key every call and result is what it was.  ValueError, before any GPU work: a ratio `match_ratio` refuses."""
+    Without the key every call and result is what it was.  ValueError, before any GPU work: a ratio `match_ratio` refuses.
+
+    A full circle.  pairs="ring": the adjacent pairs plus (0, N - 1), the pair that closes the circle, for N >= 3; it goes down the
+    graph path.  Without `adjust` only the spanning tree places the images, so the drift of the chain shows at the closing overlap,
+    as a step where the last image meets the first; adjust="cameras" is the mode to use, since it spreads the closing error over all
+    rotations and fits the focal length that makes the circle close.  ValueError, before any GPU work: pairs="ring" with fewer than
+    3 images.  The canvas of this call does not wrap around, so a sweep that closes the circle still has an image across the seam
+    behind the anchor and is refused: `stitch_ring` is this call on a canvas that wraps (`wrap=`).  The parameter list of this
+    function is fixed."""
+    return _stitch_sequence(images, anchor, th, d, k, ransacMet, seed, blending, features, info, gains, projection, focal, pairs, adjust, bands, False)
+
+
+def stitch_ring(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, blending=False, features=None, info=None, gains=None,
+                projection="cylindrical", focal="auto", pairs="ring", adjust="cameras", bands=5, wrap=True):
+    """Pixels -> a FULL-CIRCLE panorama: `stitch_sequence` on a canvas that wraps around behind the anchor (the ring rule of
+    include/rwh.h).  Every parameter is `stitch_sequence`'s, with defaults that suit a sweep that closes the circle -- a cylinder,
+    focal="auto", pairs="ring" (the chain plus the pair that closes it) and adjust="cameras" (the mode that spreads the closing error
+    over all rotations and fits the focal length that makes the circle close; without `adjust` only the spanning tree places the
+    images and the drift of the chain shows where the last image meets the first) -- and one more: wrap, as `stitchSequence`'s:
+    True -- the period is `sequence_period` of the focal the canvas ends up with; a period in columns (a positive multiple of 256 up
+    to 65280); False -- `stitch_sequence` itself.  `info` also receives "period" and "radius".  With fewer than 3 images pass
+    pairs="adjacent".  ValueError, before any GPU work: what `stitch_sequence` refuses, wrap without a projection, a wrap that is
+    neither a bool nor such a period."""
+    return _stitch_sequence(images, anchor, th, d, k, ransacMet, seed, blending, features, info, gains, projection, focal, pairs, adjust, bands, wrap)
+
+
+def _stitch_sequence(images, anchor, th, d, k, ransacMet, seed, blending, features, info, gains, projection, focal, pairs, adjust, bands, wrap):
+    """`stitch_sequence` and `stitch_ring`: the checks that come before any GPU work, then the chain or the graph path."""
     n = len(images)
     ratio = None
     if isinstance(features, dict) and "ratio" in features:
@@ -826,8 +853,10 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     if not isinstance(adjust, (bool, np.bool_)) and not cameras:
         raise ValueError("stitch_sequence: adjust=%r; True or False, 'cameras' or 'cameras-per-image'" % (adjust,))
     if isinstance(pairs, str):
-        if pairs not in ("adjacent", "all"):
-            raise ValueError("stitch_sequence: pairs=%r; 'adjacent', 'all' or a list of (s, d)" % (pairs,))
+        if pairs not in ("adjacent", "all", "ring"):
+            raise ValueError("stitch_sequence: pairs=%r; 'adjacent', 'all', 'ring' or a list of (s, d)" % (pairs,))
+        if pairs == "ring" and n < 3:
+            raise ValueError("stitch_sequence: pairs='ring' takes 3 images at least, got %d" % n)
     else:
         pairs = _check_pairs("stitch_sequence", n, pairs)
         if len(set(pairs)) != len(pairs):
@@ -846,9 +875,10 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
             _check_focal("stitch_sequence", focal)
     else:
         _check_projection("stitch_sequence", projection, 1.0 if auto_focal else focal)
+    _check_wrap("stitch_sequence", wrap, projection, 1.0 if auto_focal else focal)
     if graph:
         return _stitch_sequence_graph(images, anchor, dict(th=th, d=d, n=4, k=k, method=ransacMet, seed=seed), blending, features, info, gains,
-                                      projection, focal, auto_focal, bands, pairs, adjust, ratio)
+                                      projection, focal, auto_focal, bands, pairs, adjust, ratio, wrap)
     Hs, sizes, inliers = np.zeros((0, 3, 3)), [], []
     if n > 1:
         feats = extract_batch(images, **(features or {}))
@@ -868,20 +898,22 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     shapes = [tuple(int(v) for v in img.shape) for img in images]
     if auto_focal:
         focal = sequence_focal(shapes, Hs)
-    Gs, _, origin, _, _ = sequence_plan(shapes, Hs, anchor, projection, focal)
+    Gs, _, origin, _, _ = sequence_plan(shapes, Hs, anchor, projection, focal, wrap)
     if info is not None:
         info["Hs"], info["Gs"], info["origin"], info["sizes"], info["inliers"] = Hs, Gs, origin, sizes, inliers
         info["focal"] = focal
     used = {}
     out = stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands, projection=projection,
-                         focal=focal)
+                         focal=focal, wrap=wrap)
     if info is not None:
         info["gains"] = used["gains"]
+        if wrap is not False:
+            info["period"], info["radius"] = used["period"], used["radius"]
     return out
 
 
 def _stitch_sequence_graph(images, anchor, search, blending, features, info, gains, projection, focal, auto_focal, bands, pairs, adjust,
-                           ratio=None):
+                           ratio=None, wrap=False):
     """`stitch_sequence` over a pair graph: one extract, one match (`match_batch`, or `match_graph` with a ratio) and one search over
     the listed pairs, `sequence_graph`, with adjust=True `sequence_adjust` on the device -- with adjust="cameras" or
     "cameras-per-image" `sequence_cameras`, `sequence_adjust_cameras` on the device and `sequence_camera_maps` --, then
@@ -889,7 +921,10 @@ def _stitch_sequence_graph(images, anchor, search, blending, features, info, gai
     n = len(images)
     adjacent = isinstance(pairs, str) and pairs == "adjacent"
     if isinstance(pairs, str):
-        pairs = [(i + 1, i) for i in range(n - 1)] if adjacent else [(s, d) for d in range(n) for s in range(d + 1, n)]
+        if pairs == "all":
+            pairs = [(s, d) for d in range(n) for s in range(d + 1, n)]
+        else:       # the chain, and with "ring" the pair that closes the circle
+            pairs = [(i + 1, i) for i in range(n - 1)] + ([] if adjacent else [(0, n - 1)])
     Hs, sizes, inliers, masks, problems = [], [], [], None, None
     if pairs:
         feats = extract_batch(images, **(features or {}))
@@ -942,7 +977,7 @@ def _stitch_sequence_graph(images, anchor, search, blending, features, info, gai
     if auto_focal and isinstance(focal, str):
         focal = estimate()
     if info is not None:
-        _, origin, _, _, _, _ = _sequence_inputs("stitch_sequence", images, None, Gs, anchor, projection, focal)
+        _, origin, _, _, _, _ = _sequence_inputs("stitch_sequence", images, None, Gs, anchor, projection, focal, wrap)
         info["Gs"], info["origin"] = (Gs if projection is None else _oriented(Gs)), origin
         info["sizes"], info["inliers"], info["focal"] = sizes, inliers, focal
         info["pairs"], info["accepted"], info["tree"], info["adjust"] = pairs, accepted, tree, adjusted
@@ -950,7 +985,9 @@ def _stitch_sequence_graph(images, anchor, search, blending, features, info, gai
             info["Hs"] = np.stack(Hs) if Hs else np.zeros((0, 3, 3))
     used = {}
     out = stitchSequence(images, Gs=Gs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands, projection=projection,
-                         focal=focal)
+                         focal=focal, wrap=wrap)
     if info is not None:
         info["gains"] = used["gains"]
+        if wrap is not False:
+            info["period"], info["radius"] = used["period"], used["radius"]
     return out
