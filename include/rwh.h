@@ -385,6 +385,8 @@ RWH_API int rwh_host_refit(const float* pts_a, const float* pts_b, int m, const 
 #define RWH_MATCH_TILE_TRAIN 256
 #define RWH_MATCH_CHUNK_QUERY 64
 #define RWH_MATCH_SEG_QUERY 256
+/* the most blocks the main kernel is launched with (256 CUs x 8 blocks of 4 waves); a longer block list is walked with that stride */
+#define RWH_MATCH_GRID_MAX 2048
 RWH_API int64_t rwh_match_workspace_bytes(int n_problems, int total_a, int total_b);
 RWH_API int rwh_match_hamming_batched(const uint8_t* d_desc_a, const uint8_t* d_desc_b, int nbytes, const int32_t* d_offsets_a,
                               const int32_t* d_offsets_b, int n_problems, int total_a, int total_b, int32_t* d_train_idx,
@@ -426,7 +428,9 @@ RWH_API int rwh_host_match_hamming(const uint8_t* desc_a, int na, const uint8_t*
  *   memory, 8-byte aligned, contents irrelevant before and after; max_train_rows = the largest nb.  The size is
  *   8 * (total_train + 4 (P + 1) + total_query * ceil(max(max_train_rows, 1) / RWH_MATCH2_SEG_TRAIN)).  The call itself cannot know
  *   max_train_rows without a download: it refuses a workspace below the size for max_train_rows = 1, and a pair whose partial
- *   results would not fit into the workspace given has no matches -- never a write outside it.
+ *   results would not fit into the workspace given has no matches -- never a write outside it.  The three bounds (total_query,
+ *   total_train, the workspace) are held against sums that run over the pairs in order, so behind the first pair that has no
+ *   matches for one of these reasons none has any either: its rows inside total_query hold -1 / -1 / -1.
  * Work is split into blocks of RWH_MATCH2_TILE_QUERY query rows x RWH_MATCH2_SEG_TRAIN train rows (train rows staged
  * RWH_MATCH2_CHUNK_TRAIN at a time); a block leaves its two nearest per query row, a second kernel merges them (the (distance, row)
  * keys of one query are distinct, so the merge is commutative and associative), applies rule 2 and claims the train row of rule 3
@@ -443,6 +447,8 @@ RWH_API int rwh_host_match_hamming(const uint8_t* desc_a, int na, const uint8_t*
 #define RWH_MATCH2_CHUNK_TRAIN 64   /* train rows staged in LDS at a time            */
 #define RWH_MATCH2_SEG_TRAIN  256   /* train rows per block                          */
 #define RWH_MATCH2_RATIO_MAX 1024   /* the largest denominator of the ratio          */
+/* the most blocks the main kernel is launched with (256 CUs x 8 blocks of 4 waves); a longer block list is walked with that stride */
+#define RWH_MATCH2_GRID_MAX 2048
 RWH_API int64_t rwh_match_ratio_workspace_bytes(int n_pairs, int total_query, int total_train, int max_train_rows);
 RWH_API int rwh_match_ratio_graph(const uint8_t* d_desc, int nbytes, const int32_t* d_image_offsets, int n_images, int total_rows,
                           const int32_t* d_pairs, int n_pairs, int total_query, int total_train, int ratio_num, int ratio_den,

@@ -29,6 +29,8 @@ RWH_MATCH_TILE_TRAIN, RWH_MATCH_CHUNK_QUERY, RWH_MATCH_SEG_QUERY = 256, 64, 256 
 # the ratio matcher over a pair graph (include/rwh.h, the ratio rule): query rows per block, train rows staged at a time, train rows
 # per block; the largest denominator of the ratio
 RWH_MATCH2_TILE_QUERY, RWH_MATCH2_CHUNK_TRAIN, RWH_MATCH2_SEG_TRAIN, RWH_MATCH2_RATIO_MAX = 256, 64, 256, 1024
+# the most blocks either matcher's main kernel is launched with; a longer block list is walked with that stride
+RWH_MATCH_GRID_MAX, RWH_MATCH2_GRID_MAX = 2048, 2048
 # the extractor (include/rwh.h): border of a keypoint's centre, orientation bins, radius of the moment patch and of the test points,
 # the detector's tile
 RWH_ORB_BORDER, RWH_ORB_BINS, RWH_ORB_PATCH_RADIUS, RWH_ORB_TEST_RADIUS, RWH_ORB_TILE_W, RWH_ORB_TILE_H = 16, 30, 15, 13, 64, 16

@@ -14,8 +14,6 @@
 // grid walks with a stride.
 #include "rwh_match.h"            // desc_dword, match_range, MATCH_NONE: shared with rwh_match_ratio.hip
 
-#define RWH_MATCH_GRID_MAX 2048     /* 256 CUs x 8 blocks of 4 waves */
-
 namespace rwh {
 
 static_assert(RWH_MATCH_SEG_QUERY % RWH_MATCH_CHUNK_QUERY == 0 && RWH_MATCH_SEG_QUERY <= 65536, "the row in its segment takes 16 bits");

@@ -18,8 +18,6 @@
 
 #include "rwh_match.h"
 
-#define RWH_MATCH2_GRID_MAX 2048    /* 256 CUs x 8 blocks of 4 waves */
-
 namespace rwh {
 
 static_assert(RWH_MATCH2_SEG_TRAIN % RWH_MATCH2_CHUNK_TRAIN == 0 && RWH_MATCH2_SEG_TRAIN <= 65536, "the row in its segment takes 16 bits");

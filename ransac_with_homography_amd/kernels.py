@@ -567,6 +567,7 @@ def host_camera_step(n, anchor, edges, blocks, lam, focals="shared"):
 # a time, query rows per block (include/rwh.h)
 MATCH_TILE_TRAIN, MATCH_CHUNK_QUERY, MATCH_SEG_QUERY = _lib.RWH_MATCH_TILE_TRAIN, _lib.RWH_MATCH_CHUNK_QUERY, _lib.RWH_MATCH_SEG_QUERY
 MATCH_MAX_BYTES = _lib.RWH_MATCH_MAX_BYTES
+MATCH_GRID_MAX = _lib.RWH_MATCH_GRID_MAX    # the most blocks of the main kernel; a longer block list is walked with that stride
 
 
 def match_hamming_batched(desc_a, desc_b, offsets_a, offsets_b):
@@ -607,6 +608,7 @@ def match_hamming_batched(desc_a, desc_b, offsets_a, offsets_b):
 # rows per block
 MATCH2_TILE_QUERY, MATCH2_CHUNK_TRAIN, MATCH2_SEG_TRAIN = _lib.RWH_MATCH2_TILE_QUERY, _lib.RWH_MATCH2_CHUNK_TRAIN, _lib.RWH_MATCH2_SEG_TRAIN
 MATCH2_RATIO_MAX = _lib.RWH_MATCH2_RATIO_MAX
+MATCH2_GRID_MAX = _lib.RWH_MATCH2_GRID_MAX  # the most blocks of the main kernel; a longer block list is walked with that stride
 
 
 def match_ratio_rows(image_offsets, pairs, total_rows):

@@ -121,10 +121,10 @@ def test_argument_validation(lib):
 def test_python_constants_match_the_header():
     from ransac_with_homography_amd import _lib, kernels
     hdr = open(os.path.join(ROOT, "include", "rwh.h")).read()
-    for name in ("RWH_MATCH_MAX_BYTES", "RWH_MATCH_TILE_TRAIN", "RWH_MATCH_CHUNK_QUERY", "RWH_MATCH_SEG_QUERY"):
+    for name in ("RWH_MATCH_MAX_BYTES", "RWH_MATCH_TILE_TRAIN", "RWH_MATCH_CHUNK_QUERY", "RWH_MATCH_SEG_QUERY", "RWH_MATCH_GRID_MAX"):
         assert int(re.search(r"#define %s (\d+)" % name, hdr).group(1)) == getattr(_lib, name)
-    assert (kernels.MATCH_TILE_TRAIN, kernels.MATCH_CHUNK_QUERY, kernels.MATCH_SEG_QUERY) == \
-        (_lib.RWH_MATCH_TILE_TRAIN, _lib.RWH_MATCH_CHUNK_QUERY, _lib.RWH_MATCH_SEG_QUERY)
+    assert (kernels.MATCH_TILE_TRAIN, kernels.MATCH_CHUNK_QUERY, kernels.MATCH_SEG_QUERY, kernels.MATCH_GRID_MAX) == \
+        (_lib.RWH_MATCH_TILE_TRAIN, _lib.RWH_MATCH_CHUNK_QUERY, _lib.RWH_MATCH_SEG_QUERY, _lib.RWH_MATCH_GRID_MAX)
     assert kernels.MATCH_SEG_QUERY % kernels.MATCH_CHUNK_QUERY == 0
 
 

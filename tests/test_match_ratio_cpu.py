@@ -163,10 +163,10 @@ def test_error_codes(lib):
 def test_python_constants_match_the_header(lib):
     from ransac_with_homography_amd import _lib, kernels
     hdr = open(os.path.join(ROOT, "include", "rwh.h")).read()
-    for name in ("RWH_MATCH2_TILE_QUERY", "RWH_MATCH2_CHUNK_TRAIN", "RWH_MATCH2_SEG_TRAIN", "RWH_MATCH2_RATIO_MAX"):
+    for name in ("RWH_MATCH2_TILE_QUERY", "RWH_MATCH2_CHUNK_TRAIN", "RWH_MATCH2_SEG_TRAIN", "RWH_MATCH2_RATIO_MAX", "RWH_MATCH2_GRID_MAX"):
         assert int(re.search(r"#define %s\s+(\d+)" % name, hdr).group(1)) == getattr(_lib, name)
-    assert (kernels.MATCH2_TILE_QUERY, kernels.MATCH2_CHUNK_TRAIN, kernels.MATCH2_SEG_TRAIN) == \
-        (_lib.RWH_MATCH2_TILE_QUERY, _lib.RWH_MATCH2_CHUNK_TRAIN, _lib.RWH_MATCH2_SEG_TRAIN)
+    assert (kernels.MATCH2_TILE_QUERY, kernels.MATCH2_CHUNK_TRAIN, kernels.MATCH2_SEG_TRAIN, kernels.MATCH2_GRID_MAX) == \
+        (_lib.RWH_MATCH2_TILE_QUERY, _lib.RWH_MATCH2_CHUNK_TRAIN, _lib.RWH_MATCH2_SEG_TRAIN, _lib.RWH_MATCH2_GRID_MAX)
     assert kernels.MATCH2_SEG_TRAIN % kernels.MATCH2_CHUNK_TRAIN == 0
     assert lib.rwh_abi_version() == 5
     na, nb = kernels.match_ratio_rows([0, 3, 3, 10, 99], [(0, 2), (2, 0), (1, 1), (4, 0), (0, -1), (3, 0)], 10)
