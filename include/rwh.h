@@ -1072,6 +1072,114 @@ RWH_API int rwh_host_stitch_multiband_ring(const void* const* images, const int3
                                            int canvas_h, int canvas_w);
 
 /*
+ * Seam finding for the sequence compositor: which image owns a canvas pixel, decided by what the images show instead of by geometry
+ * alone.  Paste takes the first image in `order` and multi-band the image with the greatest feather weight, so their seams lie
+ * where the rectangles put them, and an object that moved between two shots, or parallax on a near one, is cut along the overlap's
+ * midline.  Stitchers place a seam finder between exposure compensation and blending (OpenCV's pipeline does); the usual graph cut
+ * has no order-independent answer, so this is a geodesic, watershed-style seam (distance-transform watersheds, Meyer 1994; OpenCV's
+ * seam finders are the same idea with other costs), whose result is the unique fixed point of an integer shortest-path problem:
+ * any relaxation order on the device, Dijkstra in the host twin and Jacobi sweeps in a restatement give the same integers.  The
+ * reference has no counterpart; this is held to THE SEAM RULE below.  Everything not restated is the sequence rule's, and on a
+ * curved canvas the projection rule's: rectangles, canvas, Sample, Coverage, the feather weight g, gains.
+ *
+ * The seam rule.
+ *   Inputs.  Those of the sequence rule without `order` and the row range; optional gains; margin, float64, >= 0, may be +inf
+ *     (default 8.0); tau, an integer of 1 .. 766 (default 64).  Both defaults are conventions, not measured optima.
+ *   Bytes, C, feather winner.  As the multi-band rule defines them: C(p) is the set of images that cover canvas pixel p, b_i(p) the
+ *     bytes paste would write of image i there (with gains where given), w(p) the covering image of greatest g, the lowest index
+ *     on equal weights.
+ *   Disagreement and cost.  d(p) = sum over the three channels of (max_{i in C} b_i - min_{i in C} b_i), 0 .. 765, 0 where one
+ *     image covers.  c(p) = max(1, tau - d(p)): where the images disagree by tau or more a step costs 1, where they agree it costs tau.
+ *   Seeds.  p is a seed of w(p) when every other covering image j has g_j(p) <= margin, compared in float64; a pixel with a single
+ *     covering image is always a seed; no other image has a seed at p.  An image owns beyond dispute what lies within `margin` of
+ *     every other image's border (or outside them).
+ *   Distance.  For image i, dist_i(p) is defined on the pixels i covers.  It is 0 at i's seeds; elsewhere it is the minimum, over
+ *     all 4-connected paths from a seed of i to p that stay inside i's coverage, of the sum of c(q) over the pixels q of the path
+ *     that are not seeds of i (the start is one; p itself is not); unreached if there is no such path.  Distances are uint32: a call
+ *     is refused when wt_i * ht_i * tau > 2^32 - 3 for some i, so that no sum can wrap.
+ *   Label.  label(p) = the i in C(p) with the smallest (dist_i(p), i) among the reached; w(p) if p is covered and no covering image
+ *     reaches it; 0xff where nothing covers.  Labels are a uint8 plane of fh x fw.
+ *   Consequences.  margin = +inf gives label = w everywhere.  tau = 1 gives every c = 1: the label is the nearest seed by city-block
+ *     path length inside coverage.  With N = 1 every covered pixel has label 0.  An image without seeds labels nothing.  label(p)
+ *     always covers p.
+ *   Termination.  A relaxation stores only lengths of real paths -- upper bounds that only decrease, on integers -- so "repeat
+ *     until nothing changes" ends, and its fixed point is the definition above whatever the order and whatever races occur between
+ *     monotone 32-bit stores.
+ *   Using labels.  Winner of the multi-band rule becomes: label(p), if label(p) < N and that image covers p; otherwise the
+ *     multi-band rule's own Winner.  A caller's plane therefore cannot index out of range, and an all-0xff plane gives the canvas
+ *     without labels byte for byte.  Label paste: the canvas is the Winner's bytes under that same definition (the P plane of the
+ *     multi-band rule), 0 where nothing covers.  Feather has no single owner and takes no labels.
+ *   Out.  The wrap-around canvas (no ring form), 8-connected paths, gradient terms in the cost, graph cuts, seams on a downscaled
+ *     canvas, images that are not uint8.
+ *
+ * rwh_sequence_seams_workspace_bytes: the bytes rwh_sequence_seams needs for these rectangles and canvas (the two tables, a
+ * coverage set and a survey dword per canvas pixel, a uint32 distance per pixel of every rectangle, two dirty bytes per tile); <= 0
+ * for arguments the main call would refuse.
+ * rwh_sequence_seams: images, hw, inv_g, rects, n, anchor, canvas size and origin as rwh_stitch_sequence's; gains: a HOST array of
+ * N, or NULL; d_labels: device, canvas_h x canvas_w uint8, written whole; d_workspace: that many bytes on the device, 8-byte
+ * aligned -- the call writes everything it reads there.  passes: NULL, or receives the number of relaxation passes that changed a
+ * distance.  Launches: the survey pass over the canvas (cost, feather winner, seed flag and coverage set, every candidate sampled
+ * once), the first distances of all images (one launch), relaxation passes over all images' RWH_SEAM_TILE_W x RWH_SEAM_TILE_H
+ * tiles (a block relaxes its tile in LDS and stores what changed; a tile that did not change and whose four neighbours did not
+ * either leaves at once), the label pass.  The host launches passes until one changes nothing and reads a 4-byte flag every fourth
+ * pass to learn it: UNLIKE THE OTHER ENTRY POINTS THIS CALL SYNCHRONISES ITS STREAM, and it cannot be captured into a hipGraph.
+ * There is no pass limit other than termination itself.
+ * RWH_E_INVALID, before anything is launched: everything rwh_stitch_multiband refuses (no bands here), a margin that is NaN or
+ * negative, tau outside 1 .. 766, a rectangle with wt * ht * tau > 2^32 - 3, a NULL label plane, a workspace too small or misaligned.
+ * rwh_host_sequence_seams: the same rule on host memory by Dijkstra with a binary heap -- on purpose another algorithm than the
+ * device's --, no workspace, no GPU involved.
+ * rwh_stitch_multiband_labels / rwh_host_stitch_multiband_labels: rwh_stitch_multiband / rwh_host_stitch_multiband with the label
+ * plane (d_labels: device, canvas_h x canvas_w uint8; NULL is refused) as the Winner; workspace of rwh_stitch_multiband_workspace_bytes.
+ * rwh_stitch_sequence_labels / rwh_host_stitch_sequence_labels: label paste; workspace of rwh_stitch_sequence_workspace_bytes(n).
+ * The _proj forms take m, d_col and d_row as the projection rule's calls do, rectangles in canvas coordinates, no anchor, no origin.
+ */
+#define RWH_SEAM_TILE_W 64
+#define RWH_SEAM_TILE_H 16
+RWH_API int64_t rwh_sequence_seams_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y);
+RWH_API int rwh_sequence_seams(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                               int anchor, const double* gains, double margin, int tau, unsigned char* d_labels, int canvas_h,
+                               int canvas_w, int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream,
+                               int32_t* passes);
+RWH_API int rwh_sequence_seams_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                    const double* gains, double margin, int tau, const double* d_col, const double* d_row,
+                                    unsigned char* d_labels, int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes,
+                                    void* stream, int32_t* passes);
+RWH_API int rwh_host_sequence_seams(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                    int anchor, const double* gains, double margin, int tau, unsigned char* labels, int canvas_h,
+                                    int canvas_w, int origin_x, int origin_y);
+RWH_API int rwh_host_sequence_seams_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                         const double* gains, double margin, int tau, const double* col, const double* row,
+                                         unsigned char* labels, int canvas_h, int canvas_w);
+RWH_API int rwh_stitch_multiband_labels(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                        int anchor, int bands, const double* gains, const unsigned char* d_labels, void* d_canvas,
+                                        int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
+                                        int64_t workspace_bytes, void* stream);
+RWH_API int rwh_stitch_multiband_labels_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                             int bands, const double* gains, const unsigned char* d_labels, const double* d_col,
+                                             const double* d_row, void* d_canvas, int canvas_h, int canvas_w, void* d_workspace,
+                                             int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_stitch_multiband_labels(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                             int anchor, int bands, const double* gains, const unsigned char* labels, void* canvas,
+                                             int canvas_h, int canvas_w, int origin_x, int origin_y);
+RWH_API int rwh_host_stitch_multiband_labels_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                  int bands, const double* gains, const unsigned char* labels, const double* col,
+                                                  const double* row, void* canvas, int canvas_h, int canvas_w);
+RWH_API int rwh_stitch_sequence_labels(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                       int anchor, const double* gains, const unsigned char* d_labels, void* d_canvas, int canvas_h,
+                                       int canvas_w, int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes,
+                                       void* stream);
+RWH_API int rwh_stitch_sequence_labels_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                            const double* gains, const unsigned char* d_labels, const double* d_col,
+                                            const double* d_row, void* d_canvas, int canvas_h, int canvas_w, void* d_workspace,
+                                            int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_stitch_sequence_labels(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects,
+                                            int n, int anchor, const double* gains, const unsigned char* labels, void* canvas,
+                                            int canvas_h, int canvas_w, int origin_x, int origin_y);
+RWH_API int rwh_host_stitch_sequence_labels_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects,
+                                                 int n, const double* gains, const unsigned char* labels, const double* col,
+                                                 const double* row, void* canvas, int canvas_h, int canvas_w);
+
+/*
  * Registration of a sequence over a pair graph: the maps G_i of the sequence rule refined jointly over the inliers of every verified
  * pair (bundle adjustment, Brown & Lowe 2007, section 4; Triggs et al. 1999), instead of chained from N - 1 adjacent pairs.  The
  * reference has no counterpart; this is held to THE BUNDLE RULE below.  The per-edge normal-equation blocks are summed on the

@@ -40,6 +40,7 @@ RWH_ORB_SCALE_ONE, RWH_ORB_SCALE_MAX, RWH_ORB_LEVELS_MAX, RWH_ORB_PYR_TILE_W, RW
 RWH_SEQ_MAX_IMAGES, RWH_SEQ_PASTE, RWH_SEQ_FEATHER = 64, 0, 1
 RWH_SEQ_MAX_STRIDE = 255
 RWH_SEQ_MAX_BANDS = 8         # the multi-band rule: most bands
+RWH_SEAM_TILE_W, RWH_SEAM_TILE_H = 64, 16      # the seam rule: the relaxation kernel's tile
 # the bundle rule: float64 values per edge block, most edges (64 * 63 / 2), the statuses of an edge and of a step
 RWH_BUNDLE_BLOCK, RWH_BUNDLE_MAX_EDGES = 153, 2016
 RWH_BUNDLE_OK, RWH_BUNDLE_BEHIND, RWH_BUNDLE_SINGULAR = 0, 1, 2
@@ -66,6 +67,10 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_stitch_sequence_ring", "rwh_host_stitch_sequence_ring", "rwh_sequence_overlap_stats_ring",
            "rwh_host_sequence_overlap_stats_ring", "rwh_stitch_multiband_ring_workspace_bytes", "rwh_stitch_multiband_ring",
            "rwh_host_stitch_multiband_ring",
+           "rwh_sequence_seams_workspace_bytes", "rwh_sequence_seams", "rwh_sequence_seams_proj", "rwh_host_sequence_seams",
+           "rwh_host_sequence_seams_proj", "rwh_stitch_multiband_labels", "rwh_stitch_multiband_labels_proj",
+           "rwh_host_stitch_multiband_labels", "rwh_host_stitch_multiband_labels_proj", "rwh_stitch_sequence_labels",
+           "rwh_stitch_sequence_labels_proj", "rwh_host_stitch_sequence_labels", "rwh_host_stitch_sequence_labels_proj",
            "rwh_bundle_blocks", "rwh_host_bundle_blocks", "rwh_host_bundle_step",
            "rwh_camera_blocks", "rwh_host_camera_blocks", "rwh_host_camera_step")
 
@@ -239,6 +244,39 @@ def _bind(lib):
         getattr(lib, ring).argtypes = list(proj.argtypes)
     lib.rwh_stitch_multiband_ring_workspace_bytes.restype = i64
     lib.rwh_stitch_multiband_ring_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]   # rects n canvas_h canvas_w bands
+    # the seam rule: labels, and the two compositors that take them
+    lib.rwh_sequence_seams_workspace_bytes.restype = i64
+    lib.rwh_sequence_seams_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32]           # rects n canvas h w origin_x origin_y
+    lib.rwh_sequence_seams.restype = i32
+    lib.rwh_sequence_seams.argtypes = [vp, vp, vp, vp, i32, i32, vp, f64, i32,                # images hw inv_g rects n anchor gains margin tau
+                                       vp, i32, i32, i32, i32, vp, i64, vp, vp]               # labels h w origin_x origin_y workspace bytes stream passes
+    lib.rwh_sequence_seams_proj.restype = i32
+    lib.rwh_sequence_seams_proj.argtypes = [vp, vp, vp, vp, i32, vp, f64, i32, vp, vp,        # images hw m rects n gains margin tau col row
+                                            vp, i32, i32, vp, i64, vp, vp]                    # labels h w workspace bytes stream passes
+    lib.rwh_host_sequence_seams.restype = i32
+    lib.rwh_host_sequence_seams.argtypes = [vp, vp, vp, vp, i32, i32, vp, f64, i32, vp, i32, i32, i32, i32]
+    lib.rwh_host_sequence_seams_proj.restype = i32
+    lib.rwh_host_sequence_seams_proj.argtypes = [vp, vp, vp, vp, i32, vp, f64, i32, vp, vp, vp, i32, i32]
+    lib.rwh_stitch_multiband_labels.restype = i32
+    lib.rwh_stitch_multiband_labels.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp,        # images hw inv_g rects n anchor bands gains labels
+                                                vp, i32, i32, i32, i32, vp, i64, vp]          # canvas h w origin_x origin_y workspace bytes stream
+    lib.rwh_stitch_multiband_labels_proj.restype = i32
+    lib.rwh_stitch_multiband_labels_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp,   # images hw m rects n bands gains labels col row
+                                                     vp, i32, i32, vp, i64, vp]                  # canvas h w workspace bytes stream
+    lib.rwh_host_stitch_multiband_labels.restype = i32
+    lib.rwh_host_stitch_multiband_labels.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32]
+    lib.rwh_host_stitch_multiband_labels_proj.restype = i32
+    lib.rwh_host_stitch_multiband_labels_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32]
+    lib.rwh_stitch_sequence_labels.restype = i32
+    lib.rwh_stitch_sequence_labels.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp,              # images hw inv_g rects n anchor gains labels
+                                               vp, i32, i32, i32, i32, vp, i64, vp]           # canvas h w origin_x origin_y workspace bytes stream
+    lib.rwh_stitch_sequence_labels_proj.restype = i32
+    lib.rwh_stitch_sequence_labels_proj.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp,      # images hw m rects n gains labels col row
+                                                    vp, i32, i32, vp, i64, vp]                # canvas h w workspace bytes stream
+    lib.rwh_host_stitch_sequence_labels.restype = i32
+    lib.rwh_host_stitch_sequence_labels.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32]
+    lib.rwh_host_stitch_sequence_labels_proj.restype = i32
+    lib.rwh_host_stitch_sequence_labels_proj.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32]
     # the bundle rule: the edge blocks (device and host twin) and the damped step
     lib.rwh_bundle_blocks.restype = i32
     lib.rwh_bundle_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]     # pts_a pts_b offsets n_edges masks words T blocks count status stream

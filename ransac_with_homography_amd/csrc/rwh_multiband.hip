@@ -38,6 +38,8 @@ struct MbArgs {
     MbPx* r[MB_LEVELS];         // R^l, the whole (PH >> l) x (PW >> l) plane, l = 1 .. K (r[0] unused: R^0 is the canvas)
     int K, PW, PH;
 };
+// The labelled winner pass's arguments: MbArgs stays the record the other kernels take.
+struct MbLabelArgs { MbArgs m; const unsigned char* labels; };   // labels: fh x fw, the label plane of the seam rule
 
 // ---- the per-pixel functions ----
 // P and the winner at canvas pixel (cx, cy): the covering image with the greatest feather weight g, the lowest index on equal
@@ -258,6 +260,20 @@ __global__ __launch_bounds__(256) void mb_winner_kernel(const SeqWith<MbArgs, GA
     m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<GAIN, PROJ, RING>(m.a, cand, x, y, seq_gains(l), seq_rays(l)) : MB_NONE << 24;
 }
 
+// mb_winner_kernel under a label plane (the seam rule, "Using labels"): the pixel's label names the winner where that image covers
+// the pixel, the multi-band rule's own Winner stands everywhere else.  A kernel of its own: the unlabelled pass stays the code it was.
+template <bool GAIN, bool PROJ = false>
+__global__ __launch_bounds__(256) void mb_label_winner_kernel(const SeqWith<MbLabelArgs, GAIN, PROJ> l) {
+    const MbArgs& m = l.a.m;
+    const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
+    const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
+    const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
+    if (x >= m.PW || y >= m.PH) return;
+    uint32_t out = MB_NONE << 24;
+    if (x < m.a.fw && y < m.a.fh) out = seq_label_winner_pixel<GAIN, PROJ>(m.a, cand, x, y, l.a.labels[(int64_t)y * m.a.fw + x], seq_gains(l), seq_rays(l));
+    m.pw[(int64_t)y * m.PW + x] = out;
+}
+
 // blockIdx.z is the image; a block takes 64 x 4 pixels of its level-0 window (blocks beyond the window leave at once).
 // RING: the window's columns are taken modulo the period (PW).
 template <bool GAIN, bool PROJ = false, bool RING = false>
@@ -428,19 +444,35 @@ static void mb_bind(MbArgs& m, const MbPlan& p, char* base) {
 }
 
 template <bool GAIN, bool PROJ, bool RING>
-static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays, hipStream_t s) {
+static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays, hipStream_t s, const unsigned char* labels) {
     const SeqWith<MbArgs, GAIN, PROJ> l = seq_with<GAIN, PROJ>(m, gains, m.a.n, rays);
-    hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ, RING>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
+    if constexpr (!RING) {
+        if (labels) hipLaunchKernelGGL((mb_label_winner_kernel<GAIN, PROJ>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s,
+                                       seq_with<GAIN, PROJ>(MbLabelArgs{m, labels}, gains, m.a.n, rays));
+        else hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ, RING>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
+    } else {
+        hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ, RING>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
+    }
     hipLaunchKernelGGL((mb_level0_kernel<GAIN, PROJ, RING>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
 }
 
 template <bool GAIN, bool PROJ, bool RING>
-static void mb_host_run(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays) {
+static void mb_host_run(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays, const unsigned char* labels) {
     const int n = m.a.n, K = p.K;
     const uint64_t all = seq_all(n);
     for (int y = 0; y < p.PH; ++y)
-        for (int x = 0; x < p.PW; ++x)
-            m.pw[(int64_t)y * p.PW + x] = (x < m.a.fw && y < m.a.fh) ? mb_winner_pixel<GAIN, PROJ, RING>(m.a, all, x, y, gains, rays) : MB_NONE << 24;
+        for (int x = 0; x < p.PW; ++x) {
+            uint32_t out = MB_NONE << 24;
+            if (x < m.a.fw && y < m.a.fh) {
+                if constexpr (!RING) {
+                    if (labels) out = seq_label_winner_pixel<GAIN, PROJ>(m.a, all, x, y, labels[(int64_t)y * m.a.fw + x], gains, rays);
+                    else out = mb_winner_pixel<GAIN, PROJ, RING>(m.a, all, x, y, gains, rays);
+                } else {
+                    out = mb_winner_pixel<GAIN, PROJ, RING>(m.a, all, x, y, gains, rays);
+                }
+            }
+            m.pw[(int64_t)y * p.PW + x] = out;
+        }
     for (int i = 0; i < n; ++i) {
         const MbWin& w = m.win[i * (K + 1)];
         for (int ly = 0; ly < w.h; ++ly)
@@ -479,11 +511,13 @@ extern "C" int64_t rwh_stitch_multiband_workspace_bytes(const int32_t* rects, in
 template <bool PROJ, bool RING = false>
 static int mb_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
                      int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
-                     int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays) {
+                     int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays,
+                     const unsigned char* d_labels = nullptr, bool labelled = false) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
     MbPlan p;
+    if (labelled && !d_labels) return RWH_E_INVALID;
     const int st = mb_prepare(d_images, hw, mats, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ, RING);
     if (st != RWH_OK) return st;
     if (!d_workspace || workspace_bytes < p.bytes || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
@@ -493,7 +527,7 @@ static int mb_device(const void* const* d_images, const int32_t* hw, const doubl
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
     seq_put(p.win, (size_t)n * (p.K + 1) * (sizeof(MbWin) / 8), reinterpret_cast<uint64_t*>(base + p.win_at), s);
     mb_bind(m, p, base);
-    if (gains) mb_launch_head<true, PROJ, RING>(m, p, gains, rays, s); else mb_launch_head<false, PROJ, RING>(m, p, nullptr, rays, s);
+    if (gains) mb_launch_head<true, PROJ, RING>(m, p, gains, rays, s, d_labels); else mb_launch_head<false, PROJ, RING>(m, p, nullptr, rays, s, d_labels);
     for (int l = 0; l < p.K; ++l)
         hipLaunchKernelGGL(mb_down_kernel<RING>, dim3((p.maxw[l + 1] + MB_TW - 1) / MB_TW, (p.maxh[l + 1] + MB_TH - 1) / MB_TH, n), dim3(256), 0, s, m, l);
     for (int l = p.K; l >= 0; --l)
@@ -518,11 +552,12 @@ extern "C" int rwh_stitch_multiband_proj(const void* const* d_images, const int3
 template <bool PROJ, bool RING = false>
 static int mb_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
                    int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
-                   int origin_x, int origin_y, rwh::SeqRays rays) {
+                   int origin_x, int origin_y, rwh::SeqRays rays, const unsigned char* labels = nullptr, bool labelled = false) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
     MbPlan p;
+    if (labelled && !labels) return RWH_E_INVALID;
     const int st = mb_prepare(images, hw, mats, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ, RING);
     if (st != RWH_OK) return st;
     if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
@@ -531,7 +566,7 @@ static int mb_host(const void* const* images, const int32_t* hw, const double* m
     memcpy(base + p.desc_at, descs, (size_t)n * sizeof(SeqDesc));
     memcpy(base + p.win_at, p.win, (size_t)n * (p.K + 1) * sizeof(MbWin));
     mb_bind(m, p, base);
-    if (gains) mb_host_run<true, PROJ, RING>(m, p, gains, rays); else mb_host_run<false, PROJ, RING>(m, p, nullptr, rays);
+    if (gains) mb_host_run<true, PROJ, RING>(m, p, gains, rays, labels); else mb_host_run<false, PROJ, RING>(m, p, nullptr, rays, labels);
     free(base);
     return RWH_OK;
 }
@@ -548,6 +583,37 @@ extern "C" int rwh_host_stitch_multiband_proj(const void* const* images, const i
                                               int canvas_h, int canvas_w) {
     return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
                          rwh::SeqRays{col, row});
+}
+
+// The multi-band rule with the seam rule's Winner (include/rwh.h, "Using labels"): the calls above with a label plane.
+extern "C" int rwh_stitch_multiband_labels(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                           int anchor, int bands, const double* gains, const unsigned char* d_labels, void* d_canvas,
+                                           int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
+                                           int64_t workspace_bytes, void* stream) {
+    return mb_device<false>(d_images, hw, inv_g, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
+                            d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr}, d_labels, true);
+}
+
+extern "C" int rwh_stitch_multiband_labels_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                int bands, const double* gains, const unsigned char* d_labels, const double* d_col,
+                                                const double* d_row, void* d_canvas, int canvas_h, int canvas_w, void* d_workspace,
+                                                int64_t workspace_bytes, void* stream) {
+    return mb_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, d_canvas, canvas_h, canvas_w, 0, 0,
+                           d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row}, d_labels, true);
+}
+
+extern "C" int rwh_host_stitch_multiband_labels(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                                int anchor, int bands, const double* gains, const unsigned char* labels, void* canvas,
+                                                int canvas_h, int canvas_w, int origin_x, int origin_y) {
+    return mb_host<false>(images, hw, inv_g, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y,
+                          rwh::SeqRays{nullptr, nullptr}, labels, true);
+}
+
+extern "C" int rwh_host_stitch_multiband_labels_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                     int bands, const double* gains, const unsigned char* labels, const double* col,
+                                                     const double* row, void* canvas, int canvas_h, int canvas_w) {
+    return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
+                         rwh::SeqRays{col, row}, labels, true);
 }
 
 extern "C" int64_t rwh_stitch_multiband_ring_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int bands) {

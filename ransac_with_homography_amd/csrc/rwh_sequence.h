@@ -186,6 +186,36 @@ __host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_
     return out;
 }
 
+// The Winner of the multi-band rule under a label plane (include/rwh.h, the seam rule, "Using labels"): image `label` where it is
+// one of the candidates and covers the pixel, otherwise the covering image with the greatest feather weight g, the lowest index on
+// equal weights.  -> the winner's bytes as 0x00BBGGRR with its index in the top byte, SEQ_LABEL_NONE there where nobody covers.
+// cand: candidate bits are image indices (order is 0 .. n-1), so a label of n or more meets no candidate and indexes nothing.
+constexpr uint32_t SEQ_LABEL_NONE = 0xffu;
+template <bool GAIN, bool PROJ = false>
+__host__ __device__ __forceinline__ uint32_t seq_label_winner_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, uint32_t label,
+                                                                    const double* gains, SeqRays rays = SeqRays{nullptr, nullptr}) {
+    const int fx = a.ox + cx, fy = a.oy + cy;
+    SeqRay ray;
+    if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
+    double best = 0.0;
+    uint32_t out = SEQ_LABEL_NONE << 24;
+    for (uint64_t m = cand; m; m &= m - 1) {
+        const int i = __builtin_ctzll(m);
+        double v[3], g = 0.0, gain = 1.0;
+        if constexpr (GAIN) gain = gains[i];
+        if (!seq_sample<true, GAIN, PROJ>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray, a.fw)) continue;
+        const bool named = (uint32_t)i == label;
+        if (named || g > best) {
+            best = g;
+            out = (uint32_t)i << 24;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) out |= (uint32_t)(unsigned char)(int)v[k] << (8 * k);
+            if (named) break;
+        }
+    }
+    return out;
+}
+
 // The images whose rectangles meet canvas columns [x0, x1) and rows [y0, y1), as bits in `order`'s numbering.
 // RING: a rectangle that passes the canvas's edge comes back in at column 0, so the rectangle shifted by -period (a.fw) is tested
 // as well; it starts left of every tile, which leaves one compare of wave-uniform values.

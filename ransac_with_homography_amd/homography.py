@@ -54,7 +54,7 @@ __all__ = [
     "calc_corresp", "calc_correspLinear", "calc_correspCollective", "calc_correspLinearCollective",
     "calcHomography", "calcHomographyLinear", "calcH", "nearestNeighbor", "bilinear", "convertfunc",
     "wrapPerspective", "wrapPerspectiveScan", "perspectiveTransform", "transformImage", "transformImageH",
-    "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence", "sequence_gains",
+    "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence", "sequence_gains", "sequence_seams",
     "sequence_ray_tables", "sequence_focal", "sequence_graph", "sequence_adjust",
     "sequence_cameras", "sequence_camera_maps", "sequence_adjust_cameras",
 ]
@@ -1563,8 +1563,63 @@ def _check_bands(who, bands):
     kernels.sequence_bands_check(who, bands)
 
 
+def _seams_on_device(on_dev, inv_g, rects, anchor, origin, size, gains, margin, tau, info, rays=None):
+    """One call of the seam finder on uploaded images -> labels, a uint8 [fh, fw] device tensor.  rays: the device ray tables of a
+    projected call (inv_g then holds the M_i and the rectangles are the canvas's)."""
+    if rays is None:
+        return kernels.sequence_seams(on_dev, inv_g, rects, anchor, origin, size, gains=gains, margin=margin, tau=tau, info=info)
+    return kernels.sequence_seams_proj(on_dev, inv_g, rects, rays[0], rays[1], size, gains=gains, margin=margin, tau=tau, info=info)
+
+
+def sequence_seams(images, Hs=None, Gs=None, anchor=0, gains=None, margin=8.0, tau=64, info=None, projection=None, focal=None):
+    """Which image owns each canvas pixel of a sequence, decided by what the images show (the seam rule of include/rwh.h; a
+    geodesic, watershed-style seam): every image grows outward from the pixels it owns beyond dispute -- those where every other
+    covering image is within `margin` of its own border -- slowly (`tau` per pixel) where the covering images agree and fast where
+    they disagree, and a pixel goes to the image that reaches it first.  An object that only one image shows is swept whole by one
+    front instead of being cut along the overlap's midline.  -> labels, uint8 [fh, fw] on `stitchSequence`'s canvas: the owner's
+    index, 255 where nothing covers; numpy arrays in -> a numpy plane, any tensor in -> a device tensor.
+    `stitchSequence(..., seams=labels)` composites with them.
+
+    images, Hs, Gs, anchor, projection, focal: as `stitchSequence`'s, and refused as there.  gains: None or N exposure gains (the
+    disagreement is taken on the compensated bytes).  margin=8.0 and tau=64 (an integer of 1 .. 766) are conventions, not measured
+    optima; margin=inf gives the feather winner of multi-band blending.  `info`: optional dict, receives "passes", the number of
+    relaxation passes that changed a distance.  The relaxation runs until nothing changes and the host reads a flag between
+    passes: the call synchronises torch's current stream.  The wrap-around canvas is not taken.
+    ValueError: a margin that is negative or not a number, another tau, before the GPU is touched."""
+    n = len(images)
+    rects, origin, size, _, inv_g, rays = _sequence_inputs("sequence_seams", images, Hs, Gs, anchor, projection, focal, False)
+    kernels.sequence_seam_options("sequence_seams", margin, tau)
+    if gains is not None:
+        gains = kernels.sequence_gains_array(gains, n, "sequence_seams")
+    tens = any(_is_tensor(img) for img in images)
+    on_dev = _sequence_upload(images)
+    labels = _seams_on_device(on_dev, inv_g, rects, anchor, origin, size, gains, margin, int(tau), info, _rays_upload(rays, on_dev[0].device))
+    return labels if tens else _xfer.to_host(labels)
+
+
+def _check_seams(who, seams, blending, wrap):
+    """`seams` of stitchSequence, before the GPU is touched -> None (no seams), ("find", margin, tau) or ("plane", labels)."""
+    if seams is None or seams is False:
+        return None
+    if blending == "feather":
+        raise ValueError("%s: seams with blending='feather': a feathered pixel has no single owner; blending=False or 'multiband'" % who)
+    if wrap is not False:
+        raise NotImplementedError("%s: seams on a wrap-around canvas are not provided (the seam rule has no ring form)" % who)
+    if seams is True:
+        return ("find", 8.0, 64)
+    if isinstance(seams, dict):
+        if set(seams) - {"margin", "tau"}:
+            raise ValueError("%s: seams=%r; the keys are 'margin' and 'tau'" % (who, seams))
+        margin, tau = seams.get("margin", 8.0), seams.get("tau", 64)
+        kernels.sequence_seam_options(who, margin, tau)
+        return ("find", margin, int(tau))
+    if len(getattr(seams, "shape", ())) != 2 or str(seams.dtype).replace("torch.", "") != "uint8":
+        raise ValueError("%s: seams=%r; None, True, a dict of 'margin' and 'tau', or a uint8 [fh, fw] label plane" % (who, type(seams)))
+    return ("plane", seams)
+
+
 def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=None, gains=None, info=None, projection=None, focal=None,
-                   wrap=False, bands=5):
+                   wrap=False, seams=None, bands=5):
     """N images into one panorama in ONE pass over the canvas (`rwh_stitch_sequence`): every image is warped once into the
     anchor's frame and every canvas pixel written once.  The reference has no counterpart -- its stitchPanorama takes two images,
     and folding it over a list resamples the growing canvas once per image; this is held to the sequence rule stated in
@@ -1594,6 +1649,14 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     include/rwh.h): the surface has the radius P / (2 pi), the cameras keep `focal`, an image may lie across the seam, and all
     blends, gains and bands work across it.  It takes a projection.  `info` then also receives "period" and "radius".  `bands` stays
     the last parameter: pass it, and `wrap`, by name.
+    seams: None -- the owner of a pixel is decided by geometry alone, as above; True -- `sequence_seams` with its defaults (margin
+    8.0, tau 64: conventions, not measured optima) on the same upload and with the gains in use; a dict with "margin" and / or
+    "tau" -- the same with those; a uint8 [fh, fw] label plane (numpy or tensor) -- used as given, a label that names no covering
+    image leaves the pixel to the geometric rule.  With blending=False the canvas is label paste (every pixel the bytes of its
+    owner; `order` is validated and otherwise ignored), with "multiband" the labels replace the winner of the multi-band rule (the
+    seam rule of include/rwh.h, "Using labels").  When seams are found `info` receives "passes" and "labels" (the plane used), and
+    the call synchronises the stream.  ValueError: seams with "feather"; NotImplementedError, before the GPU is touched: seams
+    with `wrap`.
     ValueError: what `sequence_plan` refuses, an `order` that is not a permutation, another `blending`, gains of another length,
     not finite or <= 0, or another string; NotImplementedError: images that are not uint8 [h, w, 3]."""
     n = len(images)
@@ -1602,8 +1665,11 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
         raise ValueError("stitchSequence: blending=%r; False, 'feather' or 'multiband'" % (blending,))
     if blending == "multiband":
         _check_bands("stitchSequence", bands)
+    seam = _check_seams("stitchSequence", seams, blending, wrap)
     blend = _lib.RWH_SEQ_FEATHER if blending == "feather" else _lib.RWH_SEQ_PASTE
     rects, origin, size, default, inv_g, rays = _sequence_inputs("stitchSequence", images, Hs, Gs, anchor, projection, focal, wrap)
+    if seam is not None and seam[0] == "plane" and tuple(int(v) for v in seam[1].shape) != tuple(int(v) for v in size):
+        raise ValueError("stitchSequence: seams is a %s plane, the canvas is %s" % (tuple(seam[1].shape), tuple(size)))
     ring = wrap is not False
     order = default if order is None else [int(v) for v in order]
     if sorted(order) != list(range(n)):
@@ -1622,7 +1688,24 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
         info["gains"] = gains
         if ring:
             info["period"], info["radius"] = int(size[1]), int(size[1]) / (2.0 * np.pi)
-    if ring:
+    if seam is not None:
+        if seam[0] == "find":
+            found = {}
+            labels = _seams_on_device(on_dev, inv_g, rects, anchor, origin, size, gains, seam[1], seam[2], found, rays)
+            if info is not None:
+                info["passes"], info["labels"] = found["passes"], labels if tens else _xfer.to_host(labels)
+        else:
+            labels = seam[1]
+        if rays is not None:
+            if blending == "multiband":
+                out = kernels.stitch_sequence_multiband_labels_proj(on_dev, inv_g, rects, rays[0], rays[1], size, int(bands), labels, gains=gains)
+            else:
+                out = kernels.stitch_sequence_labels_proj(on_dev, inv_g, rects, rays[0], rays[1], size, labels, gains=gains)
+        elif blending == "multiband":
+            out = kernels.stitch_sequence_multiband_labels(on_dev, inv_g, rects, anchor, origin, size, int(bands), labels, gains=gains)
+        else:
+            out = kernels.stitch_sequence_labels(on_dev, inv_g, rects, anchor, origin, size, labels, gains=gains)
+    elif ring:
         if blending == "multiband":
             out = kernels.stitch_sequence_multiband_ring(on_dev, inv_g, rects, rays[0], rays[1], size, int(bands), gains=gains)
         else:

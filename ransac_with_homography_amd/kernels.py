@@ -1070,6 +1070,164 @@ def stitch_sequence_multiband_proj(images, m, rects, col, row, canvas_hw, bands,
     return out
 
 
+SEAM_TILE = (_lib.RWH_SEAM_TILE_W, _lib.RWH_SEAM_TILE_H)
+_SEAM_REFUSED = ("%s: the library refused the arguments (include/rwh.h, the seam rule: anchor, rectangles on the canvas, finite matrices, "
+                 "margin >= 0, tau of 1 .. 766, wt * ht * tau <= 2^32 - 3, the label plane)")
+
+
+def sequence_seam_options(who, margin, tau):
+    """ValueError unless `margin` of the seam rule is a number >= 0 (inf included) and `tau` an integer of 1 .. 766."""
+    if not (isinstance(margin, (int, float, np.integer, np.floating)) and not isinstance(margin, bool) and margin >= 0):
+        raise ValueError("%s: margin %r; a number >= 0 (inf included)" % (who, margin))
+    if not (isinstance(tau, (int, np.integer)) and not isinstance(tau, bool) and 1 <= tau <= 766):
+        raise ValueError("%s: tau %r; an integer of 1 .. 766" % (who, tau))
+
+
+def _sequence_labels(who, labels, fh, fw, dev):
+    """A label plane as the library takes it: a contiguous uint8 [fh, fw] GPU tensor (a numpy plane is uploaded)."""
+    if not isinstance(labels, torch.Tensor):
+        labels = torch.from_numpy(np.ascontiguousarray(labels))
+    if labels.dtype != torch.uint8 or tuple(labels.shape) != (fh, fw):
+        raise ValueError("%s: labels are %s %s; a uint8 [%d, %d] plane" % (who, labels.dtype, tuple(labels.shape), fh, fw))
+    return labels.to(dev).contiguous()
+
+
+def _sequence_label_plane(images, fh, fw, out):
+    if out is None:
+        return torch.empty((fh, fw), dtype=torch.uint8, device=images[0].device)
+    _dev_check(out)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (fh, fw) and out.is_contiguous()
+    return out
+
+
+def sequence_seams(images, inv_g, rects, anchor, origin, canvas_hw, gains=None, margin=8.0, tau=64, out=None, info=None):
+    """Launch the seam finder (rwh_sequence_seams; the seam rule of include/rwh.h): images, inv_g, rects, anchor, origin, canvas_hw
+    as `stitch_sequence`'s; gains: None, or n gains of the gain rule; margin (8.0) and tau (64): the rule's two conventions ->
+    labels [fh, fw] uint8 (`out` when given), on torch's current stream, which the call SYNCHRONISES between its relaxation passes.
+    `info`: optional dict, receives "passes".  The workspace is allocated here.  What the library refuses raises ValueError."""
+    import ctypes
+    lib = _lib.load()
+    who = "sequence_seams"
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal(who, images, inv_g, rects, canvas_hw, own=lambda: sequence_seam_options(who, margin, tau))
+    out = _sequence_label_plane(images, fh, fw, out)
+    need = int(lib.rwh_sequence_seams_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1])))
+    if need <= 0:
+        raise ValueError(_SEAM_REFUSED % who)
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
+    passes = ctypes.c_int32(0)
+    status = lib.rwh_sequence_seams(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor),
+                                    None if gains is None else gains.ctypes.data, float(margin), int(tau), _ptr(out), fh, fw,
+                                    int(origin[0]), int(origin[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr(), ctypes.addressof(passes))
+    _sequence_status(status, "rwh_sequence_seams", _SEAM_REFUSED % who)
+    if info is not None:
+        info["passes"] = int(passes.value)
+    return out
+
+
+def sequence_seams_proj(images, m, rects, col, row, canvas_hw, gains=None, margin=8.0, tau=64, out=None, info=None):
+    """`sequence_seams` on a curved canvas (rwh_sequence_seams_proj): images, m, rects, col, row as `stitch_sequence_proj`'s."""
+    import ctypes
+    lib = _lib.load()
+    who = "sequence_seams_proj"
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=lambda: sequence_seam_options(who, margin, tau))
+    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    out = _sequence_label_plane(images, fh, fw, out)
+    need = int(lib.rwh_sequence_seams_workspace_bytes(rc.ctypes.data, n, fh, fw, 0, 0))
+    if need <= 0:
+        raise ValueError(_SEAM_REFUSED % who)
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
+    passes = ctypes.c_int32(0)
+    status = lib.rwh_sequence_seams_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n,
+                                         None if gains is None else gains.ctypes.data, float(margin), int(tau), pc, pr, _ptr(out), fh, fw,
+                                         _ptr(ws), ws.numel() * 8, _lib.stream_ptr(), ctypes.addressof(passes))
+    _sequence_status(status, "rwh_sequence_seams_proj", _SEAM_REFUSED % who)
+    if info is not None:
+        info["passes"] = int(passes.value)
+    return out
+
+
+def stitch_sequence_multiband_labels(images, inv_g, rects, anchor, origin, canvas_hw, bands, labels, gains=None, out=None):
+    """`stitch_sequence_multiband` with a label plane as the Winner (rwh_stitch_multiband_labels; the seam rule, "Using labels"):
+    labels: uint8 [fh, fw], a GPU tensor or a numpy plane; a label that names no covering image leaves the multi-band rule's Winner."""
+    lib = _lib.load()
+    who = "stitch_sequence_multiband_labels"
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal(who, images, inv_g, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
+    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
+    out = _sequence_canvas(images, fh, fw, out)
+    need = int(lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1]), int(bands)))
+    if need <= 0:
+        raise ValueError(_SEAM_REFUSED % who)
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
+    status = lib.rwh_stitch_multiband_labels(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), int(bands),
+                                             None if gains is None else gains.ctypes.data, _ptr(labels), _ptr(out), fh, fw,
+                                             int(origin[0]), int(origin[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
+    _sequence_status(status, "rwh_stitch_multiband_labels", _SEAM_REFUSED % who)
+    return out
+
+
+def stitch_sequence_multiband_labels_proj(images, m, rects, col, row, canvas_hw, bands, labels, gains=None, out=None):
+    """`stitch_sequence_multiband_proj` with a label plane as the Winner (rwh_stitch_multiband_labels_proj)."""
+    lib = _lib.load()
+    who = "stitch_sequence_multiband_labels_proj"
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
+    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
+    out = _sequence_canvas(images, fh, fw, out)
+    need = int(lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, 0, 0, int(bands)))
+    if need <= 0:
+        raise ValueError(_SEAM_REFUSED % who)
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
+    status = lib.rwh_stitch_multiband_labels_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, int(bands),
+                                                  None if gains is None else gains.ctypes.data, _ptr(labels), pc, pr, _ptr(out), fh, fw,
+                                                  _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
+    _sequence_status(status, "rwh_stitch_multiband_labels_proj", _SEAM_REFUSED % who)
+    return out
+
+
+def stitch_sequence_labels(images, inv_g, rects, anchor, origin, canvas_hw, labels, gains=None, out=None):
+    """Label paste (rwh_stitch_sequence_labels; the seam rule, "Using labels"): every canvas pixel takes the bytes of the image its
+    label names where that image covers it, of the covering image with the greatest feather weight elsewhere."""
+    lib = _lib.load()
+    who = "stitch_sequence_labels"
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal(who, images, inv_g, rects, canvas_hw)
+    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
+    out = _sequence_canvas(images, fh, fw, out)
+    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
+    status = lib.rwh_stitch_sequence_labels(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor),
+                                            None if gains is None else gains.ctypes.data, _ptr(labels), _ptr(out), fh, fw,
+                                            int(origin[0]), int(origin[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
+    _sequence_status(status, "rwh_stitch_sequence_labels", _SEAM_REFUSED % who)
+    return out
+
+
+def stitch_sequence_labels_proj(images, m, rects, col, row, canvas_hw, labels, gains=None, out=None):
+    """Label paste on a curved canvas (rwh_stitch_sequence_labels_proj)."""
+    lib = _lib.load()
+    who = "stitch_sequence_labels_proj"
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw)
+    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
+    out = _sequence_canvas(images, fh, fw, out)
+    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
+    status = lib.rwh_stitch_sequence_labels_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n,
+                                                 None if gains is None else gains.ctypes.data, _ptr(labels), pc, pr, _ptr(out), fh, fw,
+                                                 _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
+    _sequence_status(status, "rwh_stitch_sequence_labels_proj", _SEAM_REFUSED % who)
+    return out
+
+
 _RING_REFUSED = ("%s: the library refused the arguments (include/rwh.h, the ring rule: %s, a period that is a multiple of 256, rectangles "
                  "that start on the canvas and are at most one period wide, finite M, the tables)")
 

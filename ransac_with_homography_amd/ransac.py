@@ -56,7 +56,7 @@ from .features import (DeviceProblems, _host_rows, default_pattern, detect_and_d
 from .homography import (_check_bands, _check_focal, _check_pairs, _check_projection, _check_wrap, _oriented, _pair_rows,  # noqa: F401
                          _sequence_inputs, calcHomography, calcHomographyLinear, cylindericlMap, sequence_adjust,
                          sequence_adjust_cameras, sequence_camera_maps, sequence_cameras, sequence_focal, sequence_gains,
-                         sequence_graph, sequence_period, sequence_plan, stitchPanorama, stitchSequence)
+                         sequence_graph, sequence_period, sequence_plan, sequence_seams, stitchPanorama, stitchSequence)
 
 # Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
 # in csrc/rwh_settle.h.  RESCORE_MARGIN caps the margin of the 'backward' / 'reproj' rule: an unflagged K1 count moves by <= 2
@@ -782,7 +782,9 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
 
     th, d, k, ransacMet, seed: as `run_batch`'s (device sampling, the float64 device refit: a NON-PARITY mode);
     features: a dict of `extract_batch`'s keyword arguments; anchor, blending, bands, gains: as `stitchSequence`'s
-    (blending="multiband": multi-band blending with `bands` pyramid levels, checked before any GPU work; gains="auto": exposure
+    (blending="multiband": multi-band blending with `bands` pyramid levels, checked before any GPU work; blending="seams" and
+    "multiband+seams": `stitchSequence(blending=False | "multiband", seams=True)`, seam finding by the seam rule of include/rwh.h
+    with its defaults, then label paste or labelled multi-band -- not on a canvas that wraps; gains="auto": exposure
     gains from the overlaps, `sequence_gains` with its defaults).  numpy arrays in -> a numpy canvas, tensors in -> a device
     tensor.  `info`: optional dict, receives "Hs" (float64 [N - 1, 3, 3], Hs[i] maps image i+1 into image i), "Gs", "origin"
     ((ox, oy) of the canvas in the anchor's frame), "sizes" (matches per pair), "inliers" (per pair) and "gains" (the gains used,
@@ -843,6 +845,11 @@ def stitch_ring(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=0, b
 def _stitch_sequence(images, anchor, th, d, k, ransacMet, seed, blending, features, info, gains, projection, focal, pairs, adjust, bands, wrap):
     """`stitch_sequence` and `stitch_ring`: the checks that come before any GPU work, then the chain or the graph path."""
     n = len(images)
+    seams = None
+    if isinstance(blending, str) and blending in ("seams", "multiband+seams"):      # (the parameter lists are fixed: seams ride on `blending`)
+        blending, seams = (False if blending == "seams" else "multiband"), True
+        if wrap is not False:
+            raise NotImplementedError("stitch_sequence: seams on a wrap-around canvas are not provided (the seam rule has no ring form)")
     ratio = None
     if isinstance(features, dict) and "ratio" in features:
         features = dict(features)
@@ -878,7 +885,7 @@ def _stitch_sequence(images, anchor, th, d, k, ransacMet, seed, blending, featur
     _check_wrap("stitch_sequence", wrap, projection, 1.0 if auto_focal else focal)
     if graph:
         return _stitch_sequence_graph(images, anchor, dict(th=th, d=d, n=4, k=k, method=ransacMet, seed=seed), blending, features, info, gains,
-                                      projection, focal, auto_focal, bands, pairs, adjust, ratio, wrap)
+                                      projection, focal, auto_focal, bands, pairs, adjust, ratio, wrap, seams)
     Hs, sizes, inliers = np.zeros((0, 3, 3)), [], []
     if n > 1:
         feats = extract_batch(images, **(features or {}))
@@ -904,16 +911,18 @@ def _stitch_sequence(images, anchor, th, d, k, ransacMet, seed, blending, featur
         info["focal"] = focal
     used = {}
     out = stitchSequence(images, Hs=Hs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands, projection=projection,
-                         focal=focal, wrap=wrap)
+                         focal=focal, wrap=wrap, seams=seams)
     if info is not None:
         info["gains"] = used["gains"]
+        if "passes" in used:
+            info["passes"], info["labels"] = used["passes"], used["labels"]
         if wrap is not False:
             info["period"], info["radius"] = used["period"], used["radius"]
     return out
 
 
 def _stitch_sequence_graph(images, anchor, search, blending, features, info, gains, projection, focal, auto_focal, bands, pairs, adjust,
-                           ratio=None, wrap=False):
+                           ratio=None, wrap=False, seams=None):
     """`stitch_sequence` over a pair graph: one extract, one match (`match_batch`, or `match_graph` with a ratio) and one search over
     the listed pairs, `sequence_graph`, with adjust=True `sequence_adjust` on the device -- with adjust="cameras" or
     "cameras-per-image" `sequence_cameras`, `sequence_adjust_cameras` on the device and `sequence_camera_maps` --, then
@@ -985,9 +994,11 @@ def _stitch_sequence_graph(images, anchor, search, blending, features, info, gai
             info["Hs"] = np.stack(Hs) if Hs else np.zeros((0, 3, 3))
     used = {}
     out = stitchSequence(images, Gs=Gs, anchor=anchor, blending=blending, gains=gains, info=used, bands=bands, projection=projection,
-                         focal=focal, wrap=wrap)
+                         focal=focal, wrap=wrap, seams=seams)
     if info is not None:
         info["gains"] = used["gains"]
+        if "passes" in used:
+            info["passes"], info["labels"] = used["passes"], used["labels"]
         if wrap is not False:
             info["period"], info["radius"] = used["period"], used["radius"]
     return out
