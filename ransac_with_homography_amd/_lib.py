@@ -186,97 +186,62 @@ def _bind(lib):
     lib.rwh_host_orb_pyramid.argtypes = [vp, i32, i32, i32, vp, i32, vp, i64]
     lib.rwh_host_orb_extract_pyramid.restype = i32
     lib.rwh_host_orb_extract_pyramid.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.rwh_stitch_sequence_workspace_bytes.restype = i64
-    lib.rwh_stitch_sequence_workspace_bytes.argtypes = [i32]
-    lib.rwh_stitch_sequence.restype = i32
-    lib.rwh_stitch_sequence.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32,        # images hw inv_g rects n anchor order blend
-                                        vp, i32, i32, i32, i32, i32, i32,         # canvas h w origin_x origin_y row_begin row_end
-                                        vp, i64, vp]                              # workspace bytes stream
-    lib.rwh_host_stitch_sequence.restype = i32
-    lib.rwh_host_stitch_sequence.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32]
-    # the gain rule: overlap statistics, the gains, the compositor with gains (the plain calls' arguments, then gains)
-    lib.rwh_sequence_overlap_stats_workspace_bytes.restype = i64
-    lib.rwh_sequence_overlap_stats_workspace_bytes.argtypes = [i32, i32, i32, i32]
-    lib.rwh_sequence_overlap_stats.restype = i32
-    lib.rwh_sequence_overlap_stats.argtypes = [vp, vp, vp, vp, i32, i32,                  # images hw inv_g rects n anchor
-                                               i32, i32, i32, i32, i32,                  # canvas h w origin_x origin_y stride
-                                               vp, vp, vp, i64, vp]                      # count sum workspace bytes stream
-    lib.rwh_host_sequence_overlap_stats.restype = i32
-    lib.rwh_host_sequence_overlap_stats.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+    # the sequence family (include/rwh.h: the sequence, gain, multi-band, projection, ring and seam rules).  Every entry point takes
+    #     images hw mats rects n [anchor] | the operation's own | [col row] | [out] h w | [origin_x origin_y] | the operation's tail
+    # with anchor and origin on the anchor's plane only (form ""), the ray tables on a curved ("_proj") or wrap-around ("_ring")
+    # canvas only, and `workspace bytes stream` inside the tail; a host twin is the same list without those three.
+    # kernels.SeqGeometry.layout lays the calls out in the same order.
+    def front(form, own, canvas, tail):
+        """An entry point's list up to `workspace bytes stream`."""
+        if form == "":
+            return [vp, vp, vp, vp, i32, i32] + own + canvas + [i32, i32] + tail
+        return [vp, vp, vp, vp, i32] + own + [vp, vp] + canvas + tail
+
+    def bind(name, types):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = i32, types
+
+    ws, out, forms = [vp, i64, vp], [vp, i32, i32], ("", "_proj", "_ring")
+    # the compositor: order blend | canvas h w | row_begin row_end, workspace bytes stream, gains.  On the plane the call with
+    # gains is `_ex`, and the plain call is that list without gains
+    for form in forms:
+        f = front(form, [vp, i32], out, [i32, i32])
+        bind("rwh_stitch_sequence" + (form or "_ex"), f + ws + [vp])
+        bind("rwh_host_stitch_sequence" + (form or "_ex"), f + [vp])
+    bind("rwh_stitch_sequence", lib.rwh_stitch_sequence_ex.argtypes[:-1])
+    bind("rwh_host_stitch_sequence", lib.rwh_host_stitch_sequence_ex.argtypes[:-1])
+    # the overlap statistics: nothing of their own | h w, no out | stride count sum, workspace bytes stream
+    for form in forms:
+        f = front(form, [], [i32, i32], [i32, vp, vp])
+        bind("rwh_sequence_overlap_stats" + form, f + ws)
+        bind("rwh_host_sequence_overlap_stats" + form, f)
+    # multi-band: bands gains | canvas h w | workspace bytes stream
+    for form in forms:
+        f = front(form, [i32, vp], out, [])
+        bind("rwh_stitch_multiband" + form, f + ws)
+        bind("rwh_host_stitch_multiband" + form, f)
+    for form in ("", "_proj"):                     # the seam rule has no ring form
+        # multi-band with labels: bands gains labels | canvas h w | workspace bytes stream
+        f = front(form, [i32, vp, vp], out, [])
+        bind("rwh_stitch_multiband_labels" + form, f + ws)
+        bind("rwh_host_stitch_multiband_labels" + form, f)
+        # label paste: gains labels | canvas h w | workspace bytes stream
+        f = front(form, [vp, vp], out, [])
+        bind("rwh_stitch_sequence_labels" + form, f + ws)
+        bind("rwh_host_stitch_sequence_labels" + form, f)
+        # the seam finder: gains margin tau | labels h w | workspace bytes stream passes; the host twin has no passes
+        f = front(form, [vp, f64, i32], out, [])
+        bind("rwh_sequence_seams" + form, f + ws + [vp])
+        bind("rwh_host_sequence_seams" + form, f)
+    # their workspace sizes, and the gain rule's host solve
+    for fn, types in ((lib.rwh_stitch_sequence_workspace_bytes, [i32]),                                       # n
+                      (lib.rwh_sequence_overlap_stats_workspace_bytes, [i32, i32, i32, i32]),                 # n canvas h w stride
+                      (lib.rwh_stitch_multiband_workspace_bytes, [vp, i32, i32, i32, i32, i32, i32]),         # rects n canvas h w origin_x origin_y bands
+                      (lib.rwh_stitch_multiband_ring_workspace_bytes, [vp, i32, i32, i32, i32]),              # rects n canvas_h canvas_w bands
+                      (lib.rwh_sequence_seams_workspace_bytes, [vp, i32, i32, i32, i32, i32])):               # rects n canvas h w origin_x origin_y
+        fn.restype, fn.argtypes = i64, types
     lib.rwh_host_sequence_gains.restype = i32
-    lib.rwh_host_sequence_gains.argtypes = [vp, vp, i32, f64, f64, vp]
-    lib.rwh_stitch_sequence_ex.restype = i32
-    lib.rwh_stitch_sequence_ex.argtypes = lib.rwh_stitch_sequence.argtypes + [vp]
-    lib.rwh_host_stitch_sequence_ex.restype = i32
-    lib.rwh_host_stitch_sequence_ex.argtypes = lib.rwh_host_stitch_sequence.argtypes + [vp]
-    # the multi-band rule
-    lib.rwh_stitch_multiband_workspace_bytes.restype = i64
-    lib.rwh_stitch_multiband_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32, i32]       # rects n canvas h w origin_x origin_y bands
-    lib.rwh_stitch_multiband.restype = i32
-    lib.rwh_stitch_multiband.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp,                      # images hw inv_g rects n anchor bands gains
-                                         vp, i32, i32, i32, i32, vp, i64, vp]                    # canvas h w origin_x origin_y workspace bytes stream
-    lib.rwh_host_stitch_multiband.restype = i32
-    lib.rwh_host_stitch_multiband.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32]
-    # the projection rule: m in place of inv_g, the two ray tables, rectangles on the canvas, no anchor and no origin
-    lib.rwh_stitch_sequence_proj.restype = i32
-    lib.rwh_stitch_sequence_proj.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp,      # images hw m rects n order blend col row
-                                             vp, i32, i32, i32, i32,                    # canvas h w row_begin row_end
-                                             vp, i64, vp, vp]                           # workspace bytes stream gains
-    lib.rwh_host_stitch_sequence_proj.restype = i32
-    lib.rwh_host_stitch_sequence_proj.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp]
-    lib.rwh_sequence_overlap_stats_proj.restype = i32
-    lib.rwh_sequence_overlap_stats_proj.argtypes = [vp, vp, vp, vp, i32, vp, vp,        # images hw m rects n col row
-                                                    i32, i32, i32,                      # canvas h w stride
-                                                    vp, vp, vp, i64, vp]                # count sum workspace bytes stream
-    lib.rwh_host_sequence_overlap_stats_proj.restype = i32
-    lib.rwh_host_sequence_overlap_stats_proj.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp]
-    lib.rwh_stitch_multiband_proj.restype = i32
-    lib.rwh_stitch_multiband_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp,     # images hw m rects n bands gains col row
-                                              vp, i32, i32, vp, i64, vp]                # canvas h w workspace bytes stream
-    lib.rwh_host_stitch_multiband_proj.restype = i32
-    lib.rwh_host_stitch_multiband_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32]
-    # the ring rule: the projected calls' arguments, canvas_w the period; the multi-band workspace has its own size function
-    for ring, proj in (("rwh_stitch_sequence_ring", lib.rwh_stitch_sequence_proj), ("rwh_host_stitch_sequence_ring", lib.rwh_host_stitch_sequence_proj),
-                       ("rwh_sequence_overlap_stats_ring", lib.rwh_sequence_overlap_stats_proj),
-                       ("rwh_host_sequence_overlap_stats_ring", lib.rwh_host_sequence_overlap_stats_proj),
-                       ("rwh_stitch_multiband_ring", lib.rwh_stitch_multiband_proj), ("rwh_host_stitch_multiband_ring", lib.rwh_host_stitch_multiband_proj)):
-        getattr(lib, ring).restype = i32
-        getattr(lib, ring).argtypes = list(proj.argtypes)
-    lib.rwh_stitch_multiband_ring_workspace_bytes.restype = i64
-    lib.rwh_stitch_multiband_ring_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]   # rects n canvas_h canvas_w bands
-    # the seam rule: labels, and the two compositors that take them
-    lib.rwh_sequence_seams_workspace_bytes.restype = i64
-    lib.rwh_sequence_seams_workspace_bytes.argtypes = [vp, i32, i32, i32, i32, i32]           # rects n canvas h w origin_x origin_y
-    lib.rwh_sequence_seams.restype = i32
-    lib.rwh_sequence_seams.argtypes = [vp, vp, vp, vp, i32, i32, vp, f64, i32,                # images hw inv_g rects n anchor gains margin tau
-                                       vp, i32, i32, i32, i32, vp, i64, vp, vp]               # labels h w origin_x origin_y workspace bytes stream passes
-    lib.rwh_sequence_seams_proj.restype = i32
-    lib.rwh_sequence_seams_proj.argtypes = [vp, vp, vp, vp, i32, vp, f64, i32, vp, vp,        # images hw m rects n gains margin tau col row
-                                            vp, i32, i32, vp, i64, vp, vp]                    # labels h w workspace bytes stream passes
-    lib.rwh_host_sequence_seams.restype = i32
-    lib.rwh_host_sequence_seams.argtypes = [vp, vp, vp, vp, i32, i32, vp, f64, i32, vp, i32, i32, i32, i32]
-    lib.rwh_host_sequence_seams_proj.restype = i32
-    lib.rwh_host_sequence_seams_proj.argtypes = [vp, vp, vp, vp, i32, vp, f64, i32, vp, vp, vp, i32, i32]
-    lib.rwh_stitch_multiband_labels.restype = i32
-    lib.rwh_stitch_multiband_labels.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp,        # images hw inv_g rects n anchor bands gains labels
-                                                vp, i32, i32, i32, i32, vp, i64, vp]          # canvas h w origin_x origin_y workspace bytes stream
-    lib.rwh_stitch_multiband_labels_proj.restype = i32
-    lib.rwh_stitch_multiband_labels_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp,   # images hw m rects n bands gains labels col row
-                                                     vp, i32, i32, vp, i64, vp]                  # canvas h w workspace bytes stream
-    lib.rwh_host_stitch_multiband_labels.restype = i32
-    lib.rwh_host_stitch_multiband_labels.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32]
-    lib.rwh_host_stitch_multiband_labels_proj.restype = i32
-    lib.rwh_host_stitch_multiband_labels_proj.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32]
-    lib.rwh_stitch_sequence_labels.restype = i32
-    lib.rwh_stitch_sequence_labels.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp,              # images hw inv_g rects n anchor gains labels
-                                               vp, i32, i32, i32, i32, vp, i64, vp]           # canvas h w origin_x origin_y workspace bytes stream
-    lib.rwh_stitch_sequence_labels_proj.restype = i32
-    lib.rwh_stitch_sequence_labels_proj.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp,      # images hw m rects n gains labels col row
-                                                    vp, i32, i32, vp, i64, vp]                # canvas h w workspace bytes stream
-    lib.rwh_host_stitch_sequence_labels.restype = i32
-    lib.rwh_host_stitch_sequence_labels.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32]
-    lib.rwh_host_stitch_sequence_labels_proj.restype = i32
-    lib.rwh_host_stitch_sequence_labels_proj.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32]
+    lib.rwh_host_sequence_gains.argtypes = [vp, vp, i32, f64, f64, vp]                   # count sum n sigma_n sigma_g gains
     # the bundle rule: the edge blocks (device and host twin) and the damped step
     lib.rwh_bundle_blocks.restype = i32
     lib.rwh_bundle_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]     # pts_a pts_b offsets n_edges masks words T blocks count status stream

@@ -1461,7 +1461,7 @@ def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None, w
     default order, inv_g float64 [N, 3, 3], rays).  rays is None on the anchor's plane.  With a projection it is the two ray tables
     (numpy), the rectangles are in canvas coordinates and the matrices are the M_i = inv(G_i) @ K of the projection rule.  With
     wrap (the ring rule) the canvas is (fh, P), a rectangle's mx is taken modulo P (0 for a rectangle P wide) and the tables are made
-    with the radius P / (2 pi)."""
+    with the radius P / (2 pi).  The six-tuple is pinned: tests, probes and the registration driver unpack it."""
     n = len(images)
     _check_count(n, anchor)
     _check_projection(who, projection, focal)
@@ -1498,6 +1498,14 @@ def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None, w
     return rects, origin, size, default, inv_g, None
 
 
+def _sequence_geometry(who, images, Hs, Gs, anchor, projection=None, focal=None, wrap=False):
+    """`_sequence_inputs` as the launchers take it -> (default order, kernels.SeqGeometry); the ray tables are still on the host."""
+    rects, origin, size, default, mats, rays = _sequence_inputs(who, images, Hs, Gs, anchor, projection, focal, wrap)
+    if rays is None:
+        return default, kernels.SeqGeometry(mats, rects, size, anchor, origin)
+    return default, kernels.SeqGeometry(mats, rects, size, rays=rays, ring=wrap is not False)
+
+
 def _sequence_upload(images):
     dev = _lib.require_gpu()
     return [img.to(dev).contiguous() if _is_tensor(img) else _xfer.to_device(img, dev) for img in images]
@@ -1511,23 +1519,11 @@ def _check_gain_options(who, stride, sigma_n, sigma_g):
             raise ValueError("%s: %s = %r; finite and > 0" % (who, name, v))
 
 
-def _rays_upload(rays, dev):
-    """The ray tables of a projected call on the device (None stays None)."""
-    return None if rays is None else tuple(_xfer.to_device(t, dev) for t in rays)
-
-
-def _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info, rays=None, ring=False):
+def _gains_on_device(on_dev, geom, stride, sigma_n, sigma_g, info):
     """One statistics launch, one download of the two n x n tables, one call of rwh_host_sequence_gains -> float64 [N].
-    rays: the device ray tables of a projected call (inv_g then holds the M_i and the rectangles are the canvas's); ring: that call
-    is one of the ring rule."""
+    geom: the call's kernels.SeqGeometry, its ray tables on the device."""
     n = len(on_dev)
-    if rays is None:
-        tabs = kernels.sequence_overlap_tables(on_dev, inv_g, rects, anchor, origin, size, int(stride))
-    elif ring:
-        tabs = kernels.sequence_overlap_tables_ring(on_dev, inv_g, rects, rays[0], rays[1], size, int(stride))
-    else:
-        tabs = kernels.sequence_overlap_tables_proj(on_dev, inv_g, rects, rays[0], rays[1], size, int(stride))
-    tabs = tabs.cpu().numpy().view(np.uint64)
+    tabs = kernels.sequence_overlap_tables_on(on_dev, geom, int(stride)).cpu().numpy().view(np.uint64)
     gains = np.empty(n, dtype=np.float64)
     status = _lib.load().rwh_host_sequence_gains(tabs[0].ctypes.data, tabs[1].ctypes.data, n, float(sigma_n), float(sigma_g), gains.ctypes.data)
     if status == _lib.RWH_E_INVALID:
@@ -1550,25 +1546,16 @@ def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, s
     moves the gains of the test scenes in the third decimal -- not a measured optimum.  `info`: optional dict, receives "count" and
     "sum" (uint64 [N, N]), and with wrap "period" and "radius".  projection, focal, wrap: as `stitchSequence`'s -- the statistics
     are taken on that canvas.  ValueError: a stride outside 1 .. 255, a sigma that is not finite and > 0, before the GPU is touched."""
-    rects, origin, size, _, inv_g, rays = _sequence_inputs("sequence_gains", images, Hs, Gs, anchor, projection, focal, wrap)
+    _, geom = _sequence_geometry("sequence_gains", images, Hs, Gs, anchor, projection, focal, wrap)
     _check_gain_options("sequence_gains", stride, sigma_n, sigma_g)
-    ring = wrap is not False
-    if ring and info is not None:
-        info["period"], info["radius"] = int(size[1]), int(size[1]) / (2.0 * np.pi)
+    if geom.ring and info is not None:
+        info["period"], info["radius"] = int(geom.size[1]), int(geom.size[1]) / (2.0 * np.pi)
     on_dev = _sequence_upload(images)
-    return _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, stride, sigma_n, sigma_g, info, _rays_upload(rays, on_dev[0].device), ring)
+    return _gains_on_device(on_dev, geom.on_device(on_dev[0].device), stride, sigma_n, sigma_g, info)
 
 
 def _check_bands(who, bands):
     kernels.sequence_bands_check(who, bands)
-
-
-def _seams_on_device(on_dev, inv_g, rects, anchor, origin, size, gains, margin, tau, info, rays=None):
-    """One call of the seam finder on uploaded images -> labels, a uint8 [fh, fw] device tensor.  rays: the device ray tables of a
-    projected call (inv_g then holds the M_i and the rectangles are the canvas's)."""
-    if rays is None:
-        return kernels.sequence_seams(on_dev, inv_g, rects, anchor, origin, size, gains=gains, margin=margin, tau=tau, info=info)
-    return kernels.sequence_seams_proj(on_dev, inv_g, rects, rays[0], rays[1], size, gains=gains, margin=margin, tau=tau, info=info)
 
 
 def sequence_seams(images, Hs=None, Gs=None, anchor=0, gains=None, margin=8.0, tau=64, info=None, projection=None, focal=None):
@@ -1587,13 +1574,13 @@ def sequence_seams(images, Hs=None, Gs=None, anchor=0, gains=None, margin=8.0, t
     passes: the call synchronises torch's current stream.  The wrap-around canvas is not taken.
     ValueError: a margin that is negative or not a number, another tau, before the GPU is touched."""
     n = len(images)
-    rects, origin, size, _, inv_g, rays = _sequence_inputs("sequence_seams", images, Hs, Gs, anchor, projection, focal, False)
+    _, geom = _sequence_geometry("sequence_seams", images, Hs, Gs, anchor, projection, focal, False)
     kernels.sequence_seam_options("sequence_seams", margin, tau)
     if gains is not None:
         gains = kernels.sequence_gains_array(gains, n, "sequence_seams")
     tens = any(_is_tensor(img) for img in images)
     on_dev = _sequence_upload(images)
-    labels = _seams_on_device(on_dev, inv_g, rects, anchor, origin, size, gains, margin, int(tau), info, _rays_upload(rays, on_dev[0].device))
+    labels = kernels.sequence_seams_on(on_dev, geom.on_device(on_dev[0].device), gains=gains, margin=margin, tau=int(tau), info=info)
     return labels if tens else _xfer.to_host(labels)
 
 
@@ -1667,10 +1654,9 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
         _check_bands("stitchSequence", bands)
     seam = _check_seams("stitchSequence", seams, blending, wrap)
     blend = _lib.RWH_SEQ_FEATHER if blending == "feather" else _lib.RWH_SEQ_PASTE
-    rects, origin, size, default, inv_g, rays = _sequence_inputs("stitchSequence", images, Hs, Gs, anchor, projection, focal, wrap)
-    if seam is not None and seam[0] == "plane" and tuple(int(v) for v in seam[1].shape) != tuple(int(v) for v in size):
-        raise ValueError("stitchSequence: seams is a %s plane, the canvas is %s" % (tuple(seam[1].shape), tuple(size)))
-    ring = wrap is not False
+    default, geom = _sequence_geometry("stitchSequence", images, Hs, Gs, anchor, projection, focal, wrap)
+    if seam is not None and seam[0] == "plane" and tuple(int(v) for v in seam[1].shape) != tuple(int(v) for v in geom.size):
+        raise ValueError("stitchSequence: seams is a %s plane, the canvas is %s" % (tuple(seam[1].shape), tuple(geom.size)))
     order = default if order is None else [int(v) for v in order]
     if sorted(order) != list(range(n)):
         raise ValueError("stitchSequence: order %r is not a permutation of 0 .. %d" % (order, n - 1))
@@ -1681,44 +1667,27 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
         gains = kernels.sequence_gains_array(gains, n, "stitchSequence")
     tens = any(_is_tensor(img) for img in images)
     on_dev = _sequence_upload(images)
-    rays = _rays_upload(rays, on_dev[0].device)
+    geom = geom.on_device(on_dev[0].device)
     if isinstance(gains, str):
-        gains = _gains_on_device(on_dev, inv_g, rects, anchor, origin, size, 4, 10.0, 0.1, None, rays, ring)
+        gains = _gains_on_device(on_dev, geom, 4, 10.0, 0.1, None)
     if info is not None:
         info["gains"] = gains
-        if ring:
-            info["period"], info["radius"] = int(size[1]), int(size[1]) / (2.0 * np.pi)
-    if seam is not None:
-        if seam[0] == "find":
-            found = {}
-            labels = _seams_on_device(on_dev, inv_g, rects, anchor, origin, size, gains, seam[1], seam[2], found, rays)
-            if info is not None:
-                info["passes"], info["labels"] = found["passes"], labels if tens else _xfer.to_host(labels)
-        else:
-            labels = seam[1]
-        if rays is not None:
-            if blending == "multiband":
-                out = kernels.stitch_sequence_multiband_labels_proj(on_dev, inv_g, rects, rays[0], rays[1], size, int(bands), labels, gains=gains)
-            else:
-                out = kernels.stitch_sequence_labels_proj(on_dev, inv_g, rects, rays[0], rays[1], size, labels, gains=gains)
-        elif blending == "multiband":
-            out = kernels.stitch_sequence_multiband_labels(on_dev, inv_g, rects, anchor, origin, size, int(bands), labels, gains=gains)
-        else:
-            out = kernels.stitch_sequence_labels(on_dev, inv_g, rects, anchor, origin, size, labels, gains=gains)
-    elif ring:
-        if blending == "multiband":
-            out = kernels.stitch_sequence_multiband_ring(on_dev, inv_g, rects, rays[0], rays[1], size, int(bands), gains=gains)
-        else:
-            out = kernels.stitch_sequence_ring(on_dev, inv_g, rects, rays[0], rays[1], order, blend, size, gains=gains)
-    elif rays is not None:
-        if blending == "multiband":
-            out = kernels.stitch_sequence_multiband_proj(on_dev, inv_g, rects, rays[0], rays[1], size, int(bands), gains=gains)
-        else:
-            out = kernels.stitch_sequence_proj(on_dev, inv_g, rects, rays[0], rays[1], order, blend, size, gains=gains)
-    elif blending == "multiband":
-        out = kernels.stitch_sequence_multiband(on_dev, inv_g, rects, anchor, origin, size, int(bands), gains=gains)
+        if geom.ring:
+            info["period"], info["radius"] = int(geom.size[1]), int(geom.size[1]) / (2.0 * np.pi)
+    labels = None
+    if seam is not None and seam[0] == "find":
+        found = {}
+        labels = kernels.sequence_seams_on(on_dev, geom, gains=gains, margin=seam[1], tau=seam[2], info=found)
+        if info is not None:
+            info["passes"], info["labels"] = found["passes"], labels if tens else _xfer.to_host(labels)
+    elif seam is not None:
+        labels = seam[1]
+    if blending == "multiband":
+        out = kernels.stitch_sequence_multiband_on(on_dev, geom, int(bands), gains=gains, labels=labels)
+    elif labels is not None:
+        out = kernels.stitch_sequence_labels_on(on_dev, geom, labels, gains=gains)
     else:
-        out = kernels.stitch_sequence(on_dev, inv_g, rects, anchor, order, blend, origin, size, gains=gains)
+        out = kernels.stitch_sequence_on(on_dev, geom, order, blend, gains=gains)
     return out if tens else _xfer.to_host(out)
 
 

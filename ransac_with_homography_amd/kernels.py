@@ -7,11 +7,12 @@ inside librwh_hip.so.
 import ctypes
 import threading
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _xfer
 from ._lib import (RWH_BILINEAR, RWH_F32, RWH_F64, RWH_LOSS, RWH_NEAREST, RWH_U8, RWH_WARP_EXACT, RWH_WARP_ZERO_ORIGIN, check)
 
 _DTYPE = {torch.uint8: RWH_U8, torch.float32: RWH_F32, torch.float64: RWH_F64}
@@ -865,6 +866,42 @@ SEQ_MAX_IMAGES = _lib.RWH_SEQ_MAX_IMAGES
 SEQ_BLEND = {False: _lib.RWH_SEQ_PASTE, "feather": _lib.RWH_SEQ_FEATHER}
 
 
+class SeqGeometry(NamedTuple):
+    """Where a sequence call composites: what every launcher of the family takes beside the images, in one of three forms -- the
+    anchor's plane (the sequence rule of include/rwh.h), a curved canvas (the projection rule) or a wrap-around one (the ring rule).
+    mats: n matrices, inv(G_i) on the plane and M_i = inv(G_i) @ K on a curved canvas; rects: n (mx, my, wt, ht), off the plane in
+    CANVAS coordinates (on the ring 0 <= mx < P, wt <= P and mx + wt allowed past the edge); size: (fh, fw), on the ring (fh, P);
+    anchor and origin (ox, oy): of the plane, where alone the library takes them; rays: None on the plane, else the two ray tables
+    (homography.sequence_ray_tables), which a launcher takes as float64 GPU tensors [fw, 2] and [fh, 2]; ring: the canvas wraps."""
+    mats: object
+    rects: object
+    size: tuple
+    anchor: int = 0
+    origin: tuple = (0, 0)
+    rays: object = None
+    ring: bool = False
+
+    @property
+    def form(self):
+        """What the names of this form's entry points end in."""
+        return "" if self.rays is None else "_ring" if self.ring else "_proj"
+
+    def on_device(self, dev):
+        """A copy with the ray tables (numpy arrays or tensors) on `dev`; the plane has none and is returned as it is."""
+        if self.rays is None:
+            return self
+        return self._replace(rays=tuple(t.to(dev) if isinstance(t, torch.Tensor) else _xfer.to_device(t, dev) for t in self.rays))
+
+    def layout(self, tables, n, own, rays, canvas, tail):
+        """The argument list of an entry point of this form -- the one place that knows where anchor, ray tables and origin go:
+            images hw mats rects n [anchor] | own | [col row] | canvas = [out] h w | [origin_x origin_y] | tail
+        tables: the four arrays of `_sequence_marshal`; own: the operation's own arguments; rays: `_sequence_rays`'s addresses."""
+        head = (tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data, tables[3].ctypes.data, n)
+        if self.rays is None:
+            return head + (int(self.anchor),) + own + canvas + (int(self.origin[0]), int(self.origin[1])) + tail
+        return head + own + rays + canvas + tail
+
+
 def sequence_tables(shapes, inv_g, rects, order):
     """The host tables of rwh_stitch_sequence / rwh_host_stitch_sequence as contiguous arrays: (hw int32 [n, 2], inv_g float64
     [n, 9], rects int32 [n, 4], order int32 [n])."""
@@ -888,24 +925,24 @@ def sequence_bands_check(who, bands):
         raise ValueError("%s: bands %r; an integer of 1 .. %d" % (who, bands, _lib.RWH_SEQ_MAX_BANDS))
 
 
-def _sequence_marshal(who, images, inv_g, rects, canvas_hw, order=None, own=None):
-    """What every launcher of the sequence family checks and lays out -> (n, fh, fw, ptrs, hw, inv_g, rects, order), `order` the
-    index order when none is given.  own(): the launcher's own refusals, which come before the canvas's.  The library gets raw
-    addresses: the caller holds the arrays until its call has returned."""
+def _sequence_marshal(who, images, geom, order=None, own=None):
+    """What every launcher of the sequence family checks and lays out -> (n, fh, fw, tables, order): tables the four arrays
+    (image addresses, hw, mats, rects), `order` the index order when none is given.  own(): the launcher's own refusals, which come
+    before the canvas's.  The library gets raw addresses: the caller holds the arrays until its call has returned."""
     _dev_check(*images)
     n = len(images)
     for t in images:
         assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] == 3
-    fh, fw = (int(v) for v in canvas_hw)
-    if not (1 <= n <= SEQ_MAX_IMAGES) or (order is not None and len(order) != n) or len(rects) != n or len(inv_g) != n:
+    fh, fw = (int(v) for v in geom.size)
+    if not (1 <= n <= SEQ_MAX_IMAGES) or (order is not None and len(order) != n) or len(geom.rects) != n or len(geom.mats) != n:
         raise ValueError("%s: %d images (1 .. %d), %d rectangles, %d matrices%s"
-                         % (who, n, SEQ_MAX_IMAGES, len(rects), len(inv_g), "" if order is None else ", order of %d" % len(order)))
+                         % (who, n, SEQ_MAX_IMAGES, len(geom.rects), len(geom.mats), "" if order is None else ", order of %d" % len(order)))
     if own is not None:
         own()
     if not (1 <= fh <= 65535 and 1 <= fw <= 65535 and fh * fw * 3 <= 2 ** 31 - 1):
         raise ValueError("%s: a %d x %d canvas; sides of 1 .. 65535 and at most 2^31 - 1 bytes" % (who, fh, fw))
-    hw, ig, rc, od = sequence_tables([t.shape for t in images], inv_g, rects, list(range(n)) if order is None else order)
-    return n, fh, fw, np.array([t.data_ptr() for t in images], dtype=np.uint64), hw, ig, rc, od
+    hw, mats, rc, od = sequence_tables([t.shape for t in images], geom.mats, geom.rects, list(range(n)) if order is None else order)
+    return n, fh, fw, (np.array([t.data_ptr() for t in images], dtype=np.uint64), hw, mats, rc), od
 
 
 def _sequence_canvas(images, fh, fw, out):
@@ -918,169 +955,23 @@ def _sequence_canvas(images, fh, fw, out):
 
 
 def _sequence_status(status, what, refused):
-    """RWH_E_INVALID -> ValueError(refused); any other status through `check`."""
+    """RWH_E_INVALID -> ValueError(refused()), the text made only when it is needed; any other status through `check`."""
     if status == _lib.RWH_E_INVALID:
-        raise ValueError(refused)
+        raise ValueError(refused())
     check(status, what)
 
 
-def sequence_overlap_tables(images, inv_g, rects, anchor, origin, canvas_hw, stride):
-    """`sequence_overlap_stats` with both tables in ONE int64 [2, n, n] tensor (count, sum): one copy brings them down."""
-    lib = _lib.load()
-
-    def own():
-        if not (isinstance(stride, (int, np.integer)) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
-            raise ValueError("sequence_overlap_stats: stride %r; 1 .. %d" % (stride, _lib.RWH_SEQ_MAX_STRIDE))
-    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal("sequence_overlap_stats", images, inv_g, rects, canvas_hw, own=own)
-    dev = images[0].device
-    tabs = torch.empty((2, n, n), dtype=torch.int64, device=dev)
-    ws = torch.empty((int(lib.rwh_sequence_overlap_stats_workspace_bytes(n, fh, fw, int(stride))) // 8,), dtype=torch.int64, device=dev)
-    status = lib.rwh_sequence_overlap_stats(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), fh, fw,
-                                            int(origin[0]), int(origin[1]), int(stride), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(ws),
-                                            ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_sequence_overlap_stats", "sequence_overlap_stats: the library refused the arguments (include/rwh.h, "
-                     "rwh_sequence_overlap_stats: anchor, rectangles on the canvas, finite inv(G), stride)")
-    return tabs
-
-
-def sequence_overlap_stats(images, inv_g, rects, anchor, origin, canvas_hw, stride):
-    """Launch the overlap statistics of the gain rule (rwh_sequence_overlap_stats; include/rwh.h): images, inv_g, rects, anchor,
-    origin, canvas_hw as `stitch_sequence`'s; stride: 1 .. 255, every stride-th canvas pixel each way is a sample ->
-    (count, sum), int64 [n, n] GPU tensors (the library's uint64 tables: count[i][j] samples where i and j both cover, sum[i][j]
-    the byte sums of i there), on torch's current stream.  What the library refuses (RWH_E_INVALID) raises ValueError."""
-    tabs = sequence_overlap_tables(images, inv_g, rects, anchor, origin, canvas_hw, stride)
-    return tabs[0], tabs[1]
-
-
-def stitch_sequence(images, inv_g, rects, anchor, order, blend, origin, canvas_hw, rows=None, out=None, gains=None):
-    """Launch the sequence compositor (rwh_stitch_sequence; the sequence rule of include/rwh.h): images: n [h, w, 3] uint8 GPU
-    tensors; inv_g: n inv(G_i); rects: n (mx, my, wt, ht); order: a permutation of 0 .. n-1; blend: RWH_SEQ_PASTE / RWH_SEQ_FEATHER;
-    origin: (ox, oy) -> canvas [fh, fw, 3] uint8, on torch's current stream.  rows=(r0, r1): only those canvas rows, into `out`
-    (the whole canvas tensor) when given.  gains: None, or n gains of the gain rule (rwh_stitch_sequence_ex: every sample value v of
-    image i enters as min(v * gains[i], 255.0)).  What the library refuses (RWH_E_INVALID) raises ValueError."""
-    lib = _lib.load()
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images))
-    n, fh, fw, ptrs, hw, ig, rc, od = _sequence_marshal("stitch_sequence", images, inv_g, rects, canvas_hw, order)
-    out = _sequence_canvas(images, fh, fw, out)
-    r0, r1 = (0, fh) if rows is None else (int(rows[0]), int(rows[1]))
-    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
-    args = (ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), od.ctypes.data, int(blend), _ptr(out), fh, fw,
-            int(origin[0]), int(origin[1]), r0, r1, _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    status = lib.rwh_stitch_sequence(*args) if gains is None else lib.rwh_stitch_sequence_ex(*args, gains.ctypes.data)
-    _sequence_status(status, "rwh_stitch_sequence", "stitch_sequence: the library refused the arguments (include/rwh.h, "
-                     "rwh_stitch_sequence: order, anchor, rectangles on the canvas, finite inv(G), row range)")
-    return out
-
-
-def stitch_sequence_multiband(images, inv_g, rects, anchor, origin, canvas_hw, bands, gains=None, out=None):
-    """Launch the multi-band compositor (rwh_stitch_multiband; the multi-band rule of include/rwh.h): images, inv_g, rects, anchor,
-    origin, canvas_hw as `stitch_sequence`'s; bands: 1 .. 8 pyramid levels below the top; gains: None, or n gains of the gain rule
-    -> canvas [fh, fw, 3] uint8 (`out` when given), on torch's current stream.  The workspace is allocated here, of
-    rwh_stitch_multiband_workspace_bytes bytes.  What the library refuses (RWH_E_INVALID) raises ValueError."""
-    lib = _lib.load()
-    who = "stitch_sequence_multiband"
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal(who, images, inv_g, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
-    out = _sequence_canvas(images, fh, fw, out)
-    refused = ("stitch_sequence_multiband: the library refused the arguments (include/rwh.h, rwh_stitch_multiband: anchor, "
-               "rectangles on the canvas, finite inv(G), bands)")
-    need = int(lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1]), int(bands)))
-    if need <= 0:
-        raise ValueError(refused)
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_multiband(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), int(bands),
-                                      None if gains is None else gains.ctypes.data, _ptr(out), fh, fw, int(origin[0]), int(origin[1]),
-                                      _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_stitch_multiband", refused)
-    return out
-
-
-def _sequence_rays(who, col, row, fh, fw):
-    """The ray tables of the projection rule as the library takes them: float64 GPU tensors of exactly [fw, 2] and [fh, 2]."""
+def _sequence_rays(who, geom, fh, fw):
+    """The addresses of a curved canvas's ray tables as the library takes them, float64 GPU tensors of exactly [fw, 2] and [fh, 2];
+    () on the plane."""
+    if geom.rays is None:
+        return ()
+    col, row = geom.rays
     _dev_check(col, row)
     for name, t, side in (("col", col, fw), ("row", row, fh)):
         if t.dtype != torch.float64 or tuple(t.shape) != (side, 2) or not t.is_contiguous():
             raise ValueError("%s: %s is %s %s; a contiguous float64 [%d, 2] table" % (who, name, t.dtype, tuple(t.shape), side))
     return _ptr(col), _ptr(row)
-
-
-_PROJ_REFUSED = "%s: the library refused the arguments (include/rwh.h, the projection rule: %s, rectangles on the canvas, finite M, the tables)"
-
-
-def stitch_sequence_proj(images, m, rects, col, row, order, blend, canvas_hw, rows=None, out=None, gains=None):
-    """Launch the sequence compositor on a curved canvas (rwh_stitch_sequence_proj; the projection rule of include/rwh.h): images,
-    order, blend, rows, out, gains as `stitch_sequence`'s; m: n matrices M_i = inv(G_i) @ K; rects: n (mx, my, wt, ht) in CANVAS
-    coordinates; col, row: the ray tables, float64 GPU tensors [fw, 2] and [fh, 2] (homography.sequence_ray_tables) -> canvas
-    [fh, fw, 3] uint8, on torch's current stream.  What the library refuses (RWH_E_INVALID) raises ValueError."""
-    lib = _lib.load()
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), "stitch_sequence_proj")
-    n, fh, fw, ptrs, hw, mm, rc, od = _sequence_marshal("stitch_sequence_proj", images, m, rects, canvas_hw, order)
-    pc, pr = _sequence_rays("stitch_sequence_proj", col, row, fh, fw)
-    out = _sequence_canvas(images, fh, fw, out)
-    r0, r1 = (0, fh) if rows is None else (int(rows[0]), int(rows[1]))
-    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_sequence_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, od.ctypes.data, int(blend),
-                                          pc, pr, _ptr(out), fh, fw, r0, r1, _ptr(ws), ws.numel() * 8, _lib.stream_ptr(),
-                                          None if gains is None else gains.ctypes.data)
-    _sequence_status(status, "rwh_stitch_sequence_proj", _PROJ_REFUSED % ("stitch_sequence_proj", "order, row range"))
-    return out
-
-
-def sequence_overlap_tables_proj(images, m, rects, col, row, canvas_hw, stride):
-    """The overlap statistics of the gain rule on a curved canvas (rwh_sequence_overlap_stats_proj): images, m, rects, col, row as
-    `stitch_sequence_proj`'s, stride as `sequence_overlap_stats`'s -> one int64 [2, n, n] GPU tensor (count, sum)."""
-    lib = _lib.load()
-    who = "sequence_overlap_tables_proj"
-
-    def own():
-        if not (isinstance(stride, (int, np.integer)) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
-            raise ValueError("%s: stride %r; 1 .. %d" % (who, stride, _lib.RWH_SEQ_MAX_STRIDE))
-    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=own)
-    pc, pr = _sequence_rays(who, col, row, fh, fw)
-    dev = images[0].device
-    tabs = torch.empty((2, n, n), dtype=torch.int64, device=dev)
-    ws = torch.empty((int(lib.rwh_sequence_overlap_stats_workspace_bytes(n, fh, fw, int(stride))) // 8,), dtype=torch.int64, device=dev)
-    status = lib.rwh_sequence_overlap_stats_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, pc, pr, fh, fw,
-                                                 int(stride), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_sequence_overlap_stats_proj", _PROJ_REFUSED % (who, "stride"))
-    return tabs
-
-
-def stitch_sequence_multiband_proj(images, m, rects, col, row, canvas_hw, bands, gains=None, out=None):
-    """Launch the multi-band compositor on a curved canvas (rwh_stitch_multiband_proj): images, m, rects, col, row as
-    `stitch_sequence_proj`'s; bands, gains, out as `stitch_sequence_multiband`'s -> canvas [fh, fw, 3] uint8."""
-    lib = _lib.load()
-    who = "stitch_sequence_multiband_proj"
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
-    pc, pr = _sequence_rays(who, col, row, fh, fw)
-    out = _sequence_canvas(images, fh, fw, out)
-    need = int(lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, 0, 0, int(bands)))
-    if need <= 0:
-        raise ValueError(_PROJ_REFUSED % (who, "bands"))
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_multiband_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, int(bands),
-                                           None if gains is None else gains.ctypes.data, pc, pr, _ptr(out), fh, fw,
-                                           _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_stitch_multiband_proj", _PROJ_REFUSED % (who, "bands"))
-    return out
-
-
-SEAM_TILE = (_lib.RWH_SEAM_TILE_W, _lib.RWH_SEAM_TILE_H)
-_SEAM_REFUSED = ("%s: the library refused the arguments (include/rwh.h, the seam rule: anchor, rectangles on the canvas, finite matrices, "
-                 "margin >= 0, tau of 1 .. 766, wt * ht * tau <= 2^32 - 3, the label plane)")
-
-
-def sequence_seam_options(who, margin, tau):
-    """ValueError unless `margin` of the seam rule is a number >= 0 (inf included) and `tau` an integer of 1 .. 766."""
-    if not (isinstance(margin, (int, float, np.integer, np.floating)) and not isinstance(margin, bool) and margin >= 0):
-        raise ValueError("%s: margin %r; a number >= 0 (inf included)" % (who, margin))
-    if not (isinstance(tau, (int, np.integer)) and not isinstance(tau, bool) and 1 <= tau <= 766):
-        raise ValueError("%s: tau %r; an integer of 1 .. 766" % (who, tau))
 
 
 def _sequence_labels(who, labels, fh, fw, dev):
@@ -1100,199 +991,249 @@ def _sequence_label_plane(images, fh, fw, out):
     return out
 
 
-def sequence_seams(images, inv_g, rects, anchor, origin, canvas_hw, gains=None, margin=8.0, tau=64, out=None, info=None):
-    """Launch the seam finder (rwh_sequence_seams; the seam rule of include/rwh.h): images, inv_g, rects, anchor, origin, canvas_hw
-    as `stitch_sequence`'s; gains: None, or n gains of the gain rule; margin (8.0) and tau (64): the rule's two conventions ->
-    labels [fh, fw] uint8 (`out` when given), on torch's current stream, which the call SYNCHRONISES between its relaxation passes.
-    `info`: optional dict, receives "passes".  The workspace is allocated here.  What the library refuses raises ValueError."""
-    import ctypes
-    lib = _lib.load()
-    who = "sequence_seams"
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal(who, images, inv_g, rects, canvas_hw, own=lambda: sequence_seam_options(who, margin, tau))
-    out = _sequence_label_plane(images, fh, fw, out)
-    need = int(lib.rwh_sequence_seams_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1])))
+def _sequence_workspace(need, dev, refused):
+    """A workspace of `need` bytes, allocated per call -> (the tensor, its three arguments: workspace bytes stream).  A size <= 0
+    is the size function's refusal: ValueError(refused())."""
     if need <= 0:
-        raise ValueError(_SEAM_REFUSED % who)
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
-    passes = ctypes.c_int32(0)
-    status = lib.rwh_sequence_seams(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor),
-                                    None if gains is None else gains.ctypes.data, float(margin), int(tau), _ptr(out), fh, fw,
-                                    int(origin[0]), int(origin[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr(), ctypes.addressof(passes))
-    _sequence_status(status, "rwh_sequence_seams", _SEAM_REFUSED % who)
-    if info is not None:
-        info["passes"] = int(passes.value)
-    return out
+        raise ValueError(refused())
+    ws = torch.empty(((int(need) + 7) // 8,), dtype=torch.int64, device=dev)
+    return ws, (_ptr(ws), ws.numel() * 8, _lib.stream_ptr())
 
 
-def sequence_seams_proj(images, m, rects, col, row, canvas_hw, gains=None, margin=8.0, tau=64, out=None, info=None):
-    """`sequence_seams` on a curved canvas (rwh_sequence_seams_proj): images, m, rects, col, row as `stitch_sequence_proj`'s."""
-    import ctypes
+def _addr(array):
+    return None if array is None else array.ctypes.data
+
+
+_REFUSED = {"": "anchor, rectangles on the canvas, finite inv(G)",
+            "_proj": "rectangles on the canvas, finite M, the tables",
+            "_ring": "a period that is a multiple of 256, rectangles that start on the canvas and are at most one period wide, finite M, the tables"}
+_SEAM_REFUSED = ("%s: the library refused the arguments (include/rwh.h, the seam rule: anchor, rectangles on the canvas, finite matrices, "
+                 "margin >= 0, tau of 1 .. 766, wt * ht * tau <= 2^32 - 3, the label plane)")
+
+
+def _sequence_refused(who, geom, entry, what):
+    """What a launcher says when the library refuses its arguments: the rule of the form (on the plane the entry point's), and
+    what it refuses -- `what` the operation adds; on the plane its last item closes the list, as the texts always had it."""
+    if geom.form == "":
+        *first, last = what.split(", ")
+        return "%s: the library refused the arguments (include/rwh.h, %s: %s)" % (who, entry, ", ".join(first + [_REFUSED[""], last]))
+    rule = {"_proj": "the projection rule", "_ring": "the ring rule"}[geom.form]
+    return "%s: the library refused the arguments (include/rwh.h, %s: %s, %s)" % (who, rule, what, _REFUSED[geom.form])
+
+
+def _sequence_no_ring(who, geom):
+    if geom.ring:
+        raise NotImplementedError("%s: a wrap-around canvas; the seam rule (include/rwh.h) has no ring form" % who)
+
+
+SEAM_TILE = (_lib.RWH_SEAM_TILE_W, _lib.RWH_SEAM_TILE_H)
+
+
+def sequence_seam_options(who, margin, tau):
+    """ValueError unless `margin` of the seam rule is a number >= 0 (inf included) and `tau` an integer of 1 .. 766."""
+    if not (isinstance(margin, (int, float, np.integer, np.floating)) and not isinstance(margin, bool) and margin >= 0):
+        raise ValueError("%s: margin %r; a number >= 0 (inf included)" % (who, margin))
+    if not (isinstance(tau, (int, np.integer)) and not isinstance(tau, bool) and 1 <= tau <= 766):
+        raise ValueError("%s: tau %r; an integer of 1 .. 766" % (who, tau))
+
+
+# The five launchers, named for their operation with `_on` (a geometry).  Each takes the images (n [h, w, 3] uint8 GPU tensors)
+# and a SeqGeometry, finds its entry point by name -- operation plus the geometry's form -- and runs on torch's current stream.
+# They refuse in one order: the device check and the image asserts, the counts, the launcher's own option, the canvas bound, the
+# ray tables, the label plane, the output tensor, a workspace size <= 0, the library's status (RWH_E_INVALID raises ValueError).
+def stitch_sequence_on(images, geom, order, blend, rows=None, out=None, gains=None):
+    """The sequence compositor (rwh_stitch_sequence_ex / _proj / _ring): order: a permutation of 0 .. n-1; blend: RWH_SEQ_PASTE /
+    RWH_SEQ_FEATHER -> canvas [fh, fw, 3] uint8.  rows=(r0, r1): only those canvas rows, into `out` (the whole canvas tensor) when
+    given.  gains: None, or n gains of the gain rule (every sample value v of image i enters as min(v * gains[i], 255.0))."""
     lib = _lib.load()
-    who = "sequence_seams_proj"
+    who = "stitch_sequence"
     if gains is not None:
         gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=lambda: sequence_seam_options(who, margin, tau))
-    pc, pr = _sequence_rays(who, col, row, fh, fw)
-    out = _sequence_label_plane(images, fh, fw, out)
-    need = int(lib.rwh_sequence_seams_workspace_bytes(rc.ctypes.data, n, fh, fw, 0, 0))
-    if need <= 0:
-        raise ValueError(_SEAM_REFUSED % who)
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
-    passes = ctypes.c_int32(0)
-    status = lib.rwh_sequence_seams_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n,
-                                         None if gains is None else gains.ctypes.data, float(margin), int(tau), pc, pr, _ptr(out), fh, fw,
-                                         _ptr(ws), ws.numel() * 8, _lib.stream_ptr(), ctypes.addressof(passes))
-    _sequence_status(status, "rwh_sequence_seams_proj", _SEAM_REFUSED % who)
-    if info is not None:
-        info["passes"] = int(passes.value)
-    return out
-
-
-def stitch_sequence_multiband_labels(images, inv_g, rects, anchor, origin, canvas_hw, bands, labels, gains=None, out=None):
-    """`stitch_sequence_multiband` with a label plane as the Winner (rwh_stitch_multiband_labels; the seam rule, "Using labels"):
-    labels: uint8 [fh, fw], a GPU tensor or a numpy plane; a label that names no covering image leaves the multi-band rule's Winner."""
-    lib = _lib.load()
-    who = "stitch_sequence_multiband_labels"
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal(who, images, inv_g, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
-    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
-    out = _sequence_canvas(images, fh, fw, out)
-    need = int(lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1]), int(bands)))
-    if need <= 0:
-        raise ValueError(_SEAM_REFUSED % who)
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_multiband_labels(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor), int(bands),
-                                             None if gains is None else gains.ctypes.data, _ptr(labels), _ptr(out), fh, fw,
-                                             int(origin[0]), int(origin[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_stitch_multiband_labels", _SEAM_REFUSED % who)
-    return out
-
-
-def stitch_sequence_multiband_labels_proj(images, m, rects, col, row, canvas_hw, bands, labels, gains=None, out=None):
-    """`stitch_sequence_multiband_proj` with a label plane as the Winner (rwh_stitch_multiband_labels_proj)."""
-    lib = _lib.load()
-    who = "stitch_sequence_multiband_labels_proj"
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
-    pc, pr = _sequence_rays(who, col, row, fh, fw)
-    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
-    out = _sequence_canvas(images, fh, fw, out)
-    need = int(lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, 0, 0, int(bands)))
-    if need <= 0:
-        raise ValueError(_SEAM_REFUSED % who)
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_multiband_labels_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, int(bands),
-                                                  None if gains is None else gains.ctypes.data, _ptr(labels), pc, pr, _ptr(out), fh, fw,
-                                                  _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_stitch_multiband_labels_proj", _SEAM_REFUSED % who)
-    return out
-
-
-def stitch_sequence_labels(images, inv_g, rects, anchor, origin, canvas_hw, labels, gains=None, out=None):
-    """Label paste (rwh_stitch_sequence_labels; the seam rule, "Using labels"): every canvas pixel takes the bytes of the image its
-    label names where that image covers it, of the covering image with the greatest feather weight elsewhere."""
-    lib = _lib.load()
-    who = "stitch_sequence_labels"
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, ig, rc, _ = _sequence_marshal(who, images, inv_g, rects, canvas_hw)
-    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
-    out = _sequence_canvas(images, fh, fw, out)
-    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_sequence_labels(ptrs.ctypes.data, hw.ctypes.data, ig.ctypes.data, rc.ctypes.data, n, int(anchor),
-                                            None if gains is None else gains.ctypes.data, _ptr(labels), _ptr(out), fh, fw,
-                                            int(origin[0]), int(origin[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_stitch_sequence_labels", _SEAM_REFUSED % who)
-    return out
-
-
-def stitch_sequence_labels_proj(images, m, rects, col, row, canvas_hw, labels, gains=None, out=None):
-    """Label paste on a curved canvas (rwh_stitch_sequence_labels_proj)."""
-    lib = _lib.load()
-    who = "stitch_sequence_labels_proj"
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw)
-    pc, pr = _sequence_rays(who, col, row, fh, fw)
-    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
-    out = _sequence_canvas(images, fh, fw, out)
-    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_sequence_labels_proj(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n,
-                                                 None if gains is None else gains.ctypes.data, _ptr(labels), pc, pr, _ptr(out), fh, fw,
-                                                 _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_stitch_sequence_labels_proj", _SEAM_REFUSED % who)
-    return out
-
-
-_RING_REFUSED = ("%s: the library refused the arguments (include/rwh.h, the ring rule: %s, a period that is a multiple of 256, rectangles "
-                 "that start on the canvas and are at most one period wide, finite M, the tables)")
-
-
-def stitch_sequence_ring(images, m, rects, col, row, order, blend, canvas_hw, rows=None, out=None, gains=None):
-    """Launch the sequence compositor on a wrap-around canvas (rwh_stitch_sequence_ring; the ring rule of include/rwh.h): every
-    argument as `stitch_sequence_proj`'s, with canvas_hw = (fh, P), P the period, and rects (mx, my, wt, ht) in canvas coordinates
-    with 0 <= mx < P, wt <= P and mx + wt allowed past the edge -> canvas [fh, P, 3] uint8, on torch's current stream.  What the
-    library refuses (RWH_E_INVALID) raises ValueError."""
-    lib = _lib.load()
-    who = "stitch_sequence_ring"
-    if gains is not None:
-        gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, mm, rc, od = _sequence_marshal(who, images, m, rects, canvas_hw, order)
-    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    n, fh, fw, tables, od = _sequence_marshal(who, images, geom, order)
+    rays = _sequence_rays(who, geom, fh, fw)
     out = _sequence_canvas(images, fh, fw, out)
     r0, r1 = (0, fh) if rows is None else (int(rows[0]), int(rows[1]))
-    ws = torch.empty((int(lib.rwh_stitch_sequence_workspace_bytes(n)) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_sequence_ring(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, od.ctypes.data, int(blend),
-                                          pc, pr, _ptr(out), fh, fw, r0, r1, _ptr(ws), ws.numel() * 8, _lib.stream_ptr(),
-                                          None if gains is None else gains.ctypes.data)
-    _sequence_status(status, "rwh_stitch_sequence_ring", _RING_REFUSED % (who, "order, row range"))
+    refused = lambda: _sequence_refused(who, geom, "rwh_stitch_sequence", "order, row range")
+    ws, ws_args = _sequence_workspace(lib.rwh_stitch_sequence_workspace_bytes(n), out.device, refused)
+    entry = "rwh_stitch_sequence" + (geom.form or "_ex")
+    status = getattr(lib, entry)(*geom.layout(tables, n, (od.ctypes.data, int(blend)), rays, (_ptr(out), fh, fw),
+                                              (r0, r1) + ws_args + (_addr(gains),)))
+    _sequence_status(status, entry, refused)
     return out
 
 
-def sequence_overlap_tables_ring(images, m, rects, col, row, canvas_hw, stride):
-    """The overlap statistics of the gain rule on a wrap-around canvas (rwh_sequence_overlap_stats_ring): images, m, rects, col, row,
-    canvas_hw as `stitch_sequence_ring`'s, stride as `sequence_overlap_stats`'s -> one int64 [2, n, n] GPU tensor (count, sum)."""
+def sequence_overlap_tables_on(images, geom, stride):
+    """The overlap statistics of the gain rule (rwh_sequence_overlap_stats / _proj / _ring): stride: 1 .. 255, every stride-th canvas
+    pixel each way is a sample -> ONE int64 [2, n, n] GPU tensor (count, sum), so that one copy brings both down (the library's
+    uint64 tables: count[i][j] samples where i and j both cover, sum[i][j] the byte sums of i there)."""
     lib = _lib.load()
-    who = "sequence_overlap_tables_ring"
+    who = "sequence_overlap_tables"
 
     def own():
         if not (isinstance(stride, (int, np.integer)) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
             raise ValueError("%s: stride %r; 1 .. %d" % (who, stride, _lib.RWH_SEQ_MAX_STRIDE))
-    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=own)
-    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    n, fh, fw, tables, _ = _sequence_marshal(who, images, geom, own=own)
+    rays = _sequence_rays(who, geom, fh, fw)
     dev = images[0].device
     tabs = torch.empty((2, n, n), dtype=torch.int64, device=dev)
-    ws = torch.empty((int(lib.rwh_sequence_overlap_stats_workspace_bytes(n, fh, fw, int(stride))) // 8,), dtype=torch.int64, device=dev)
-    status = lib.rwh_sequence_overlap_stats_ring(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, pc, pr, fh, fw,
-                                                 int(stride), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_sequence_overlap_stats_ring", _RING_REFUSED % (who, "stride"))
+    refused = lambda: _sequence_refused(who, geom, "rwh_sequence_overlap_stats", "stride")
+    ws, ws_args = _sequence_workspace(lib.rwh_sequence_overlap_stats_workspace_bytes(n, fh, fw, int(stride)), dev, refused)
+    entry = "rwh_sequence_overlap_stats" + geom.form
+    status = getattr(lib, entry)(*geom.layout(tables, n, (), rays, (fh, fw), (int(stride), _ptr(tabs[0]), _ptr(tabs[1])) + ws_args))
+    _sequence_status(status, entry, refused)
     return tabs
 
 
-def stitch_sequence_multiband_ring(images, m, rects, col, row, canvas_hw, bands, gains=None, out=None):
-    """Launch the multi-band compositor on a wrap-around canvas (rwh_stitch_multiband_ring): images, m, rects, col, row, canvas_hw
-    as `stitch_sequence_ring`'s; bands, gains, out as `stitch_sequence_multiband`'s -> canvas [fh, P, 3] uint8.  The workspace is
-    allocated here, of rwh_stitch_multiband_ring_workspace_bytes bytes."""
+def stitch_sequence_multiband_on(images, geom, bands, gains=None, out=None, labels=None):
+    """The multi-band compositor (rwh_stitch_multiband / _proj / _ring; the multi-band rule of include/rwh.h): bands: 1 .. 8 pyramid
+    levels below the top; gains: as `stitch_sequence_on`'s -> canvas [fh, fw, 3] uint8 (`out` when given).  labels: None, or a uint8
+    [fh, fw] plane (a GPU tensor or numpy) that takes the Winner's place (rwh_stitch_multiband_labels / _labels_proj; the seam rule,
+    "Using labels"): a label that names no covering image leaves the multi-band rule's Winner; not on the ring."""
+    who = "stitch_sequence_multiband"
+    if labels is not None:
+        _sequence_no_ring(who, geom)
     lib = _lib.load()
-    who = "stitch_sequence_multiband_ring"
     if gains is not None:
         gains = sequence_gains_array(gains, len(images), who)
-    n, fh, fw, ptrs, hw, mm, rc, _ = _sequence_marshal(who, images, m, rects, canvas_hw, own=lambda: sequence_bands_check(who, bands))
-    pc, pr = _sequence_rays(who, col, row, fh, fw)
+    n, fh, fw, tables, _ = _sequence_marshal(who, images, geom, own=lambda: sequence_bands_check(who, bands))
+    rays = _sequence_rays(who, geom, fh, fw)
+    if labels is not None:
+        labels = _sequence_labels(who, labels, fh, fw, images[0].device)
     out = _sequence_canvas(images, fh, fw, out)
-    need = int(lib.rwh_stitch_multiband_ring_workspace_bytes(rc.ctypes.data, n, fh, fw, int(bands)))
-    if need <= 0:
-        raise ValueError(_RING_REFUSED % (who, "bands"))
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=out.device)
-    status = lib.rwh_stitch_multiband_ring(ptrs.ctypes.data, hw.ctypes.data, mm.ctypes.data, rc.ctypes.data, n, int(bands),
-                                           None if gains is None else gains.ctypes.data, pc, pr, _ptr(out), fh, fw,
-                                           _ptr(ws), ws.numel() * 8, _lib.stream_ptr())
-    _sequence_status(status, "rwh_stitch_multiband_ring", _RING_REFUSED % (who, "bands"))
+    refused = lambda: _sequence_refused(who, geom, "rwh_stitch_multiband", "bands") if labels is None else _SEAM_REFUSED % who
+    if geom.ring:
+        need = lib.rwh_stitch_multiband_ring_workspace_bytes(tables[3].ctypes.data, n, fh, fw, int(bands))
+    else:
+        need = lib.rwh_stitch_multiband_workspace_bytes(tables[3].ctypes.data, n, fh, fw, int(geom.origin[0]), int(geom.origin[1]), int(bands))
+    ws, ws_args = _sequence_workspace(need, out.device, refused)
+    entry = "rwh_stitch_multiband" + ("" if labels is None else "_labels") + geom.form
+    own = (int(bands), _addr(gains)) + (() if labels is None else (_ptr(labels),))
+    status = getattr(lib, entry)(*geom.layout(tables, n, own, rays, (_ptr(out), fh, fw), ws_args))
+    _sequence_status(status, entry, refused)
     return out
+
+
+def stitch_sequence_labels_on(images, geom, labels, gains=None, out=None):
+    """Label paste (rwh_stitch_sequence_labels / _proj; the seam rule, "Using labels"): every canvas pixel takes the bytes of the image
+    its label names where that image covers it, of the covering image with the greatest feather weight elsewhere.  labels: as
+    `stitch_sequence_multiband_on`'s.  Not on the ring."""
+    who = "stitch_sequence_labels"
+    _sequence_no_ring(who, geom)
+    lib = _lib.load()
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, tables, _ = _sequence_marshal(who, images, geom)
+    rays = _sequence_rays(who, geom, fh, fw)
+    labels = _sequence_labels(who, labels, fh, fw, images[0].device)
+    out = _sequence_canvas(images, fh, fw, out)
+    refused = lambda: _SEAM_REFUSED % who
+    ws, ws_args = _sequence_workspace(lib.rwh_stitch_sequence_workspace_bytes(n), out.device, refused)
+    entry = "rwh_stitch_sequence_labels" + geom.form
+    status = getattr(lib, entry)(*geom.layout(tables, n, (_addr(gains), _ptr(labels)), rays, (_ptr(out), fh, fw), ws_args))
+    _sequence_status(status, entry, refused)
+    return out
+
+
+def sequence_seams_on(images, geom, gains=None, margin=8.0, tau=64, out=None, info=None):
+    """The seam finder (rwh_sequence_seams / _proj; the seam rule of include/rwh.h): gains: as `stitch_sequence_on`'s; margin (8.0) and
+    tau (64): the rule's two conventions -> labels [fh, fw] uint8 (`out` when given).  The call SYNCHRONISES the stream between its
+    relaxation passes.  `info`: optional dict, receives "passes".  Not on the ring."""
+    who = "sequence_seams"
+    _sequence_no_ring(who, geom)
+    lib = _lib.load()
+    if gains is not None:
+        gains = sequence_gains_array(gains, len(images), who)
+    n, fh, fw, tables, _ = _sequence_marshal(who, images, geom, own=lambda: sequence_seam_options(who, margin, tau))
+    rays = _sequence_rays(who, geom, fh, fw)
+    out = _sequence_label_plane(images, fh, fw, out)
+    need = lib.rwh_sequence_seams_workspace_bytes(tables[3].ctypes.data, n, fh, fw, int(geom.origin[0]), int(geom.origin[1]))
+    refused = lambda: _SEAM_REFUSED % who
+    ws, ws_args = _sequence_workspace(need, out.device, refused)
+    passes = ctypes.c_int32(0)
+    entry = "rwh_sequence_seams" + geom.form
+    status = getattr(lib, entry)(*geom.layout(tables, n, (_addr(gains), float(margin), int(tau)), rays, (_ptr(out), fh, fw),
+                                              ws_args + (ctypes.addressof(passes),)))
+    _sequence_status(status, entry, refused)
+    if info is not None:
+        info["passes"] = int(passes.value)
+    return out
+
+
+# The launchers under their earlier names, one per canvas form, with the argument lists that callers of this module know (the
+# planar five are named in README.md and INTEGRATION.md as the family's Python surface).  Each makes the geometry from its loose
+# arguments and calls the `_on` launcher of its operation; nothing else happens here.
+def _plane(inv_g, rects, anchor, origin, canvas_hw):
+    return SeqGeometry(inv_g, rects, canvas_hw, anchor, origin)
+
+
+def _curved(m, rects, col, row, canvas_hw, ring=False):
+    return SeqGeometry(m, rects, canvas_hw, rays=(col, row), ring=ring)
+
+
+def stitch_sequence(images, inv_g, rects, anchor, order, blend, origin, canvas_hw, rows=None, out=None, gains=None):
+    return stitch_sequence_on(images, _plane(inv_g, rects, anchor, origin, canvas_hw), order, blend, rows, out, gains)
+
+
+def stitch_sequence_proj(images, m, rects, col, row, order, blend, canvas_hw, rows=None, out=None, gains=None):
+    return stitch_sequence_on(images, _curved(m, rects, col, row, canvas_hw), order, blend, rows, out, gains)
+
+
+def stitch_sequence_ring(images, m, rects, col, row, order, blend, canvas_hw, rows=None, out=None, gains=None):
+    return stitch_sequence_on(images, _curved(m, rects, col, row, canvas_hw, True), order, blend, rows, out, gains)
+
+
+def sequence_overlap_tables(images, inv_g, rects, anchor, origin, canvas_hw, stride):
+    return sequence_overlap_tables_on(images, _plane(inv_g, rects, anchor, origin, canvas_hw), stride)
+
+
+def sequence_overlap_tables_proj(images, m, rects, col, row, canvas_hw, stride):
+    return sequence_overlap_tables_on(images, _curved(m, rects, col, row, canvas_hw), stride)
+
+
+def sequence_overlap_tables_ring(images, m, rects, col, row, canvas_hw, stride):
+    return sequence_overlap_tables_on(images, _curved(m, rects, col, row, canvas_hw, True), stride)
+
+
+def sequence_overlap_stats(images, inv_g, rects, anchor, origin, canvas_hw, stride):
+    """`sequence_overlap_tables` as (count, sum), two int64 [n, n] GPU tensors."""
+    tabs = sequence_overlap_tables(images, inv_g, rects, anchor, origin, canvas_hw, stride)
+    return tabs[0], tabs[1]
+
+
+def stitch_sequence_multiband(images, inv_g, rects, anchor, origin, canvas_hw, bands, gains=None, out=None):
+    return stitch_sequence_multiband_on(images, _plane(inv_g, rects, anchor, origin, canvas_hw), bands, gains, out)
+
+
+def stitch_sequence_multiband_proj(images, m, rects, col, row, canvas_hw, bands, gains=None, out=None):
+    return stitch_sequence_multiband_on(images, _curved(m, rects, col, row, canvas_hw), bands, gains, out)
+
+
+def stitch_sequence_multiband_ring(images, m, rects, col, row, canvas_hw, bands, gains=None, out=None):
+    return stitch_sequence_multiband_on(images, _curved(m, rects, col, row, canvas_hw, True), bands, gains, out)
+
+
+def stitch_sequence_multiband_labels(images, inv_g, rects, anchor, origin, canvas_hw, bands, labels, gains=None, out=None):
+    return stitch_sequence_multiband_on(images, _plane(inv_g, rects, anchor, origin, canvas_hw), bands, gains, out, labels)
+
+
+def stitch_sequence_multiband_labels_proj(images, m, rects, col, row, canvas_hw, bands, labels, gains=None, out=None):
+    return stitch_sequence_multiband_on(images, _curved(m, rects, col, row, canvas_hw), bands, gains, out, labels)
+
+
+def stitch_sequence_labels(images, inv_g, rects, anchor, origin, canvas_hw, labels, gains=None, out=None):
+    return stitch_sequence_labels_on(images, _plane(inv_g, rects, anchor, origin, canvas_hw), labels, gains, out)
+
+
+def stitch_sequence_labels_proj(images, m, rects, col, row, canvas_hw, labels, gains=None, out=None):
+    return stitch_sequence_labels_on(images, _curved(m, rects, col, row, canvas_hw), labels, gains, out)
+
+
+def sequence_seams(images, inv_g, rects, anchor, origin, canvas_hw, gains=None, margin=8.0, tau=64, out=None, info=None):
+    return sequence_seams_on(images, _plane(inv_g, rects, anchor, origin, canvas_hw), gains, margin, tau, out, info)
+
+
+def sequence_seams_proj(images, m, rects, col, row, canvas_hw, gains=None, margin=8.0, tau=64, out=None, info=None):
+    return sequence_seams_on(images, _curved(m, rects, col, row, canvas_hw), gains, margin, tau, out, info)
 
 
 def decode_best(best_words, k_total):

@@ -263,30 +263,27 @@ def device_tables(t):
 
 
 def device(images, Gs, anchor=0, kind="cylindrical", f=40.0, blend=PASTE, order=None, rows=None, gains=None, on=None, t=None):
-    """kernels.stitch_sequence_proj into a guarded device canvas -> the canvas in numpy.  t: as host_twin's."""
+    """kernels.stitch_sequence on a curved canvas, into a guarded device canvas -> the canvas in numpy.  t: as host_twin's."""
     from ransac_with_homography_amd import kernels
     t = tables(images, Gs, anchor, kind, f, order) if t is None else t
-    col, row = device_tables(t)
     can, fetch = sc.guarded_device_canvas(*t["size"])
-    kernels.stitch_sequence_proj(sc.upload(images) if on is None else on, t["m"], t["rects"], col, row, t["order"], blend, t["size"],
-                                 rows=rows, out=can, gains=gains)
+    kernels.stitch_sequence_on(sc.upload(images) if on is None else on, sc.geometry(t, device_tables(t)), t["order"], blend,
+                            rows=rows, out=can, gains=gains)
     return fetch()
 
 
 def device_stats(images, Gs, anchor=0, kind="cylindrical", f=40.0, stride=1):
     from ransac_with_homography_amd import kernels
     t = tables(images, Gs, anchor, kind, f)
-    col, row = device_tables(t)
-    tabs = kernels.sequence_overlap_tables_proj(sc.upload(images), t["m"], t["rects"], col, row, t["size"], stride).cpu().numpy().view(np.uint64)
+    tabs = kernels.sequence_overlap_tables_on(sc.upload(images), sc.geometry(t, device_tables(t)), stride).cpu().numpy().view(np.uint64)
     return tabs[0], tabs[1]
 
 
 def device_multiband(images, Gs, anchor=0, kind="cylindrical", f=40.0, bands=2, gains=None):
     from ransac_with_homography_amd import kernels
     t = tables(images, Gs, anchor, kind, f)
-    col, row = device_tables(t)
     can, fetch = sc.guarded_device_canvas(*t["size"])
-    kernels.stitch_sequence_multiband_proj(sc.upload(images), t["m"], t["rects"], col, row, t["size"], bands, gains=gains, out=can)
+    kernels.stitch_sequence_multiband_on(sc.upload(images), sc.geometry(t, device_tables(t)), bands, gains=gains, out=can)
     return fetch()
 
 

@@ -284,19 +284,17 @@ def workspace_bytes(lib, t, bands, size=None):
 
 
 def device(images, t, blend=PASTE, rows=None, gains=None, on=None):
-    """kernels.stitch_sequence_ring into a guarded device canvas -> the canvas in numpy."""
+    """kernels.stitch_sequence on the ring, into a guarded device canvas -> the canvas in numpy."""
     from ransac_with_homography_amd import kernels
-    col, row = pc.device_tables(t)
     can, fetch = sc.guarded_device_canvas(*t["size"])
-    kernels.stitch_sequence_ring(sc.upload(images) if on is None else on, t["m"], t["rects"], col, row, t["order"], blend, t["size"],
-                                 rows=rows, out=can, gains=gains)
+    kernels.stitch_sequence_on(sc.upload(images) if on is None else on, sc.geometry(t, pc.device_tables(t), ring=True), t["order"], blend,
+                            rows=rows, out=can, gains=gains)
     return fetch()
 
 
 def device_stats(images, t, stride=1):
     from ransac_with_homography_amd import kernels
-    col, row = pc.device_tables(t)
-    tabs = kernels.sequence_overlap_tables_ring(sc.upload(images), t["m"], t["rects"], col, row, t["size"], stride).cpu().numpy().view(np.uint64)
+    tabs = kernels.sequence_overlap_tables_on(sc.upload(images), sc.geometry(t, pc.device_tables(t), ring=True), stride).cpu().numpy().view(np.uint64)
     return tabs[0], tabs[1]
 
 

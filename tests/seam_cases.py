@@ -266,12 +266,11 @@ def device(lib, images, Gs, anchor=0, gains=None, margin=MARGIN, tau=TAU, on=Non
 
 
 def device_proj(images, Gs, anchor=0, kind="cylindrical", f=40.0, gains=None, margin=MARGIN, tau=TAU):
-    """kernels.sequence_seams_proj into a guarded plane -> numpy."""
+    """kernels.sequence_seams on a curved canvas, into a guarded plane -> numpy."""
     from ransac_with_homography_amd import kernels
     t = pc.tables(images, Gs, anchor, kind, f)
-    col, row = pc.device_tables(t)
     lab, fetch = guarded_device_plane(*t["size"])
-    kernels.sequence_seams_proj(sc.upload(images), t["m"], t["rects"], col, row, t["size"], gains=gains, margin=margin, tau=tau, out=lab)
+    kernels.sequence_seams_on(sc.upload(images), sc.geometry(t, pc.device_tables(t)), gains=gains, margin=margin, tau=tau, out=lab)
     return fetch()
 
 

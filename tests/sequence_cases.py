@@ -152,13 +152,21 @@ def host_ex(lib, *a, **k):
     return host(lib, *a, ex=True, **k)
 
 
+def geometry(t, rays=None, ring=False):
+    """kernels.SeqGeometry of a case's tables: the anchor's plane of `tables` here, or with rays = (col, row), device tensors, the
+    curved canvas of projection_cases.tables and, with ring, the wrap-around one of ring_cases'."""
+    from ransac_with_homography_amd import kernels
+    if rays is None:
+        return kernels.SeqGeometry(t["inv"], t["rects"], t["size"], t["anchor"], t["origin"])
+    return kernels.SeqGeometry(t["m"], t["rects"], t["size"], rays=tuple(rays), ring=ring)
+
+
 def device(images, Gs, anchor=0, blend=PASTE, order=None, rows=None, on=None, gains=None):
     """kernels.stitch_sequence (gains=...) into a guarded device canvas -> the canvas in numpy."""
     from ransac_with_homography_amd import kernels
     t = tables(images, Gs, anchor, order)
     can, fetch = guarded_device_canvas(*t["size"])
-    kernels.stitch_sequence(upload(images) if on is None else on, t["inv"], t["rects"], anchor, t["order"], blend, t["origin"], t["size"],
-                            rows=rows, out=can, gains=gains)
+    kernels.stitch_sequence_on(upload(images) if on is None else on, geometry(t), t["order"], blend, rows=rows, out=can, gains=gains)
     return fetch()
 
 

@@ -266,6 +266,19 @@ def test_the_python_layer_refuses_before_the_gpu():
             hg.sequence_seams(images, Hs=Hs, **kw)
 
 
+def test_the_launchers_refuse_a_ring_geometry_before_the_gpu():
+    from ransac_with_homography_amd import kernels
+    images = [sc.random_image(20, 30, 1), sc.random_image(20, 30, 2)]          # numpy: a launcher that looked at them would not get past them
+    m, rects = np.stack([np.eye(3)] * 2), [(0, 0, 30, 20), (12, 3, 30, 20)]
+    ring = kernels.SeqGeometry(m, rects, (24, 256), rays=(np.zeros((256, 2)), np.zeros((24, 2))), ring=True)
+    assert ring.form == "_ring" and ring._replace(ring=False).form == "_proj" and kernels.SeqGeometry(m, rects, (24, 256)).form == ""
+    lab = np.zeros((24, 256), np.uint8)
+    for call in (lambda: kernels.sequence_seams_on(images, ring), lambda: kernels.stitch_sequence_labels_on(images, ring, lab),
+                 lambda: kernels.stitch_sequence_multiband_on(images, ring, 2, labels=lab)):
+        with pytest.raises(NotImplementedError, match="seam rule"):
+            call()
+
+
 def test_the_signatures_are_pinned():
     import homography as hg
     import ransac as rs

@@ -48,20 +48,21 @@ for name, (h, w) in (("1080p", (1080, 1920)), ("4K", (2160, 3840))):
         Hs = [pair_h(w)] * (n - 1)
         Gs, rects, origin, (fh, fw), order = hg.sequence_plan([(h, w, 3)] * n, Hs)
         inv = np.stack([np.eye(3) if i == 0 else np.linalg.inv(Gs[i]) for i in range(n)])
+        geom = kernels.SeqGeometry(inv, rects, (fh, fw), 0, origin)
         out = torch.empty((fh, fw, 3), dtype=torch.uint8, device="cuda")
-        one = kernels.sequence_overlap_tables(imgs, inv, rects, 0, origin, (fh, fw), 1)
-        two = kernels.sequence_overlap_tables(imgs, inv, rects, 0, origin, (fh, fw), 1)
+        one = kernels.sequence_overlap_tables_on(imgs, geom, 1)
+        two = kernels.sequence_overlap_tables_on(imgs, geom, 1)
         assert bool((one == two).all()) and int(one[0, 0, 0]) == h * w, "the statistics are not reproducible"
         gains = hg.sequence_gains(imgs, Hs=Hs)
 
         def line(what, med, mn, samples):
             print("%-6s %2d %-16s %6d x %-5d %9.3f %9.3f %12.0f" % (name, n, what, fw, fh, med, mn, samples / med / 1e3))
         for stride in (1, 4):
-            med, mn = timed(lambda: kernels.sequence_overlap_tables(imgs, inv, rects, 0, origin, (fh, fw), stride))
+            med, mn = timed(lambda: kernels.sequence_overlap_tables_on(imgs, geom, stride))
             line("stats stride %d" % stride, med, mn, -(-fw // stride) * -(-fh // stride))
         for mode, blend in (("paste", _lib.RWH_SEQ_PASTE), ("feather", _lib.RWH_SEQ_FEATHER)):
             for g in (None, gains):
-                med, mn = timed(lambda: kernels.stitch_sequence(imgs, inv, rects, 0, order, blend, origin, (fh, fw), out=out, gains=g))
+                med, mn = timed(lambda: kernels.stitch_sequence_on(imgs, geom, order, blend, out=out, gains=g))
                 line(mode + (" + gains" if g is not None else ""), med, mn, fw * fh)
         t0 = time.perf_counter()
         for _ in range(REPS):

@@ -48,6 +48,7 @@ for name, (h, w) in (("1080p", (1080, 1920)), ("4K", (2160, 3840))):
         Hs = [pair_h(w)] * (n - 1)
         Gs, rects, origin, (fh, fw), order = hg.sequence_plan([(h, w, 3)] * n, Hs)
         inv = np.stack([np.eye(3) if i == 0 else np.linalg.inv(Gs[i]) for i in range(n)])
+        geom = kernels.SeqGeometry(inv, rects, (fh, fw), 0, origin)
         rc = np.ascontiguousarray(rects, dtype=np.int32)
         out = torch.empty((fh, fw, 3), dtype=torch.uint8, device="cuda")
         gains = hg.sequence_gains(imgs, Hs=Hs)
@@ -55,15 +56,15 @@ for name, (h, w) in (("1080p", (1080, 1920)), ("4K", (2160, 3840))):
         def line(what, med, mn, ws=""):
             print("%-6s %2d %-20s %6d x %-5d %9.3f %9.3f %10.0f %10s" % (name, n, what, fw, fh, med, mn, fw * fh / med / 1e3, ws))
         for g in (None, gains):
-            med, mn = timed(lambda: kernels.stitch_sequence(imgs, inv, rects, 0, order, _lib.RWH_SEQ_FEATHER, origin, (fh, fw), out=out, gains=g))
+            med, mn = timed(lambda: kernels.stitch_sequence_on(imgs, geom, order, _lib.RWH_SEQ_FEATHER, out=out, gains=g))
             line("feather" + (" + gains" if g is not None else ""), med, mn)
         for bands in (1, 3, 5):
-            one = kernels.stitch_sequence_multiband(imgs, inv, rects, 0, origin, (fh, fw), bands).clone()
-            two = kernels.stitch_sequence_multiband(imgs, inv, rects, 0, origin, (fh, fw), bands)
+            one = kernels.stitch_sequence_multiband_on(imgs, geom, bands).clone()
+            two = kernels.stitch_sequence_multiband_on(imgs, geom, bands)
             assert bool((one == two).all()), "the canvas is not reproducible"
             need = lib.rwh_stitch_multiband_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1]), bands)
             for g in (None, gains):
-                med, mn = timed(lambda: kernels.stitch_sequence_multiband(imgs, inv, rects, 0, origin, (fh, fw), bands, gains=g, out=out))
+                med, mn = timed(lambda: kernels.stitch_sequence_multiband_on(imgs, geom, bands, gains=g, out=out))
                 line("multiband %d" % bands + (" + gains" if g is not None else ""), med, mn, "%d MiB" % (need >> 20))
     del frames
     torch.cuda.empty_cache()

@@ -58,20 +58,14 @@ for n in (4, 8):
             print("%-6s %2d %-12s refused: %s" % ("1080p", n, projection or "planar", e))
             continue
         out = torch.empty((fh, fw, 3), dtype=torch.uint8, device="cuda")
-        if rays is not None:
-            col, row = (torch.from_numpy(t).cuda() for t in rays)
-        passes = []
-        for mode, blend in (("paste", _lib.RWH_SEQ_PASTE), ("feather", _lib.RWH_SEQ_FEATHER)):
-            if rays is None:
-                passes.append((mode, lambda blend=blend: kernels.stitch_sequence(imgs, mats, rects, anchor, order, blend, origin, (fh, fw), out=out)))
-            else:
-                passes.append((mode, lambda blend=blend: kernels.stitch_sequence_proj(imgs, mats, rects, col, row, order, blend, (fh, fw), out=out)))
         if rays is None:
-            passes.append(("stats 4", lambda: kernels.sequence_overlap_tables(imgs, mats, rects, anchor, origin, (fh, fw), 4)))
-            passes.append(("multiband 5", lambda: kernels.stitch_sequence_multiband(imgs, mats, rects, anchor, origin, (fh, fw), 5, out=out)))
+            geom = kernels.SeqGeometry(mats, rects, (fh, fw), anchor, origin)
         else:
-            passes.append(("stats 4", lambda: kernels.sequence_overlap_tables_proj(imgs, mats, rects, col, row, (fh, fw), 4)))
-            passes.append(("multiband 5", lambda: kernels.stitch_sequence_multiband_proj(imgs, mats, rects, col, row, (fh, fw), 5, out=out)))
+            geom = kernels.SeqGeometry(mats, rects, (fh, fw), rays=rays).on_device(imgs[0].device)
+        passes = [(mode, lambda blend=blend: kernels.stitch_sequence_on(imgs, geom, order, blend, out=out))
+                  for mode, blend in (("paste", _lib.RWH_SEQ_PASTE), ("feather", _lib.RWH_SEQ_FEATHER))]
+        passes.append(("stats 4", lambda: kernels.sequence_overlap_tables_on(imgs, geom, 4)))
+        passes.append(("multiband 5", lambda: kernels.stitch_sequence_multiband_on(imgs, geom, 5, out=out)))
         mpix = fh * fw / 1e6
         for mode, fn in passes:
             med, mn = timed(fn)

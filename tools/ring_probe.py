@@ -47,14 +47,11 @@ def pair_h():
     return K @ R @ np.linalg.inv(K)
 
 
-def passes(form, imgs, mats, rects, col, row, order, size, out):
-    seq = kernels.stitch_sequence_ring if form == "ring" else kernels.stitch_sequence_proj
-    tabs = kernels.sequence_overlap_tables_ring if form == "ring" else kernels.sequence_overlap_tables_proj
-    band = kernels.stitch_sequence_multiband_ring if form == "ring" else kernels.stitch_sequence_multiband_proj
-    return [("paste", lambda: seq(imgs, mats, rects, col, row, order, _lib.RWH_SEQ_PASTE, size, out=out)),
-            ("feather", lambda: seq(imgs, mats, rects, col, row, order, _lib.RWH_SEQ_FEATHER, size, out=out)),
-            ("stats 4", lambda: tabs(imgs, mats, rects, col, row, size, 4)),
-            ("multiband 5", lambda: band(imgs, mats, rects, col, row, size, 5, out=out))]
+def passes(imgs, geom, order, out):
+    return [("paste", lambda: kernels.stitch_sequence_on(imgs, geom, order, _lib.RWH_SEQ_PASTE, out=out)),
+            ("feather", lambda: kernels.stitch_sequence_on(imgs, geom, order, _lib.RWH_SEQ_FEATHER, out=out)),
+            ("stats 4", lambda: kernels.sequence_overlap_tables_on(imgs, geom, 4)),
+            ("multiband 5", lambda: kernels.stitch_sequence_multiband_on(imgs, geom, 5, out=out))]
 
 
 rng = np.random.default_rng(0)
@@ -63,10 +60,11 @@ print("%-2s %-12s %13s %7s | %9s %9s | %9s %9s | %s" % ("N", "pass", "canvas", "
 for n in (8, 24):
     imgs, anchor = frames[:n], 0 if n == 24 else n // 2
     rects, origin, (fh, fw), order, mats, rays = hg._sequence_inputs("ring_probe", imgs, [pair_h()] * (n - 1), None, anchor, "cylindrical", F, True)
-    col, row = (torch.from_numpy(t).cuda() for t in rays)
+    ring = kernels.SeqGeometry(mats, rects, (fh, fw), rays=rays, ring=True).on_device(imgs[0].device)
+    geoms = {"ring": ring, "proj": ring._replace(ring=False)}
     both = not any(r[0] + r[2] > fw for r in rects)        # no rectangle passes the edge: the projected forms take these tables too
     outs = {form: torch.zeros((fh, fw, 3), dtype=torch.uint8, device="cuda") for form in ("proj", "ring")}
-    forms = {form: passes(form, imgs, mats, rects, col, row, order, (fh, fw), outs[form]) for form in (("proj", "ring") if both else ("ring",))}
+    forms = {form: passes(imgs, geoms[form], order, outs[form]) for form in (("proj", "ring") if both else ("ring",))}
     for k, (mode, ring_fn) in enumerate(forms["ring"]):
         if both:
             proj_fn = forms["proj"][k][1]

@@ -63,19 +63,20 @@ def run(name, frames, Hs, h, w):
     out = torch.empty((fh, fw, 3), dtype=torch.uint8, device="cuda")
     lab = torch.empty((fh, fw), dtype=torch.uint8, device="cuda")
     info = {}
-    one = kernels.sequence_seams(frames, inv, rects, 0, origin, (fh, fw), info=info).clone()
-    two = kernels.sequence_seams(frames, inv, rects, 0, origin, (fh, fw))
+    geom = kernels.SeqGeometry(inv, rects, (fh, fw), 0, origin)
+    one = kernels.sequence_seams_on(frames, geom, info=info).clone()
+    two = kernels.sequence_seams_on(frames, geom)
     assert bool((one == two).all()), "the labels are not reproducible"
     need = _lib.load().rwh_sequence_seams_workspace_bytes(rc.ctypes.data, n, fh, fw, int(origin[0]), int(origin[1]))
 
     def line(what, t, extra=""):
         print("%-7s %2d %-26s %6d x %-5d %9.3f %9.3f %8.0f %10.0f  %s" % (name, n, what, fw, fh, t[0], t[1], t[2], fw * fh / t[0] / 1e3, extra))
-    line("sequence_seams", timed(lambda: kernels.sequence_seams(frames, inv, rects, 0, origin, (fh, fw), out=lab)),
+    line("sequence_seams", timed(lambda: kernels.sequence_seams_on(frames, geom, out=lab)),
          "%d passes, workspace %d MiB" % (info["passes"], need >> 20))
-    line("paste", timed(lambda: kernels.stitch_sequence(frames, inv, rects, 0, order, _lib.RWH_SEQ_PASTE, origin, (fh, fw), out=out)))
-    line("label paste (plane given)", timed(lambda: kernels.stitch_sequence_labels(frames, inv, rects, 0, origin, (fh, fw), lab, out=out)))
-    line("multiband 5", timed(lambda: kernels.stitch_sequence_multiband(frames, inv, rects, 0, origin, (fh, fw), 5, out=out)))
-    line("multiband 5 (plane given)", timed(lambda: kernels.stitch_sequence_multiband_labels(frames, inv, rects, 0, origin, (fh, fw), 5, lab, out=out)))
+    line("paste", timed(lambda: kernels.stitch_sequence_on(frames, geom, order, _lib.RWH_SEQ_PASTE, out=out)))
+    line("label paste (plane given)", timed(lambda: kernels.stitch_sequence_labels_on(frames, geom, lab, out=out)))
+    line("multiband 5", timed(lambda: kernels.stitch_sequence_multiband_on(frames, geom, 5, out=out)))
+    line("multiband 5 (plane given)", timed(lambda: kernels.stitch_sequence_multiband_on(frames, geom, 5, out=out, labels=lab)))
     line("stitchSequence multiband", timed(lambda: hg.stitchSequence(frames, Hs=Hs, blending="multiband")))
     line("stitchSequence mb + seams", timed(lambda: hg.stitchSequence(frames, Hs=Hs, blending="multiband", seams=True)))
 

@@ -46,11 +46,12 @@ for name, (h, w) in (("1080p", (1080, 1920)), ("4K", (2160, 3840))):
         imgs = frames[:n]
         Gs, rects, origin, (fh, fw), order = hg.sequence_plan([(h, w, 3)] * n, [pair_h(w)] * (n - 1))
         inv = np.stack([np.eye(3) if i == 0 else np.linalg.inv(Gs[i]) for i in range(n)])
+        geom = kernels.SeqGeometry(inv, rects, (fh, fw), 0, origin)
         out = torch.empty((fh, fw, 3), dtype=torch.uint8, device="cuda")
         src = torch.empty_like(out)
         mb = fh * fw * 3 / 1e6
         for mode, blend in (("paste", _lib.RWH_SEQ_PASTE), ("feather", _lib.RWH_SEQ_FEATHER)):
-            med, mn = timed(lambda: kernels.stitch_sequence(imgs, inv, rects, 0, order, blend, origin, (fh, fw), out=out))
+            med, mn = timed(lambda: kernels.stitch_sequence_on(imgs, geom, order, blend, out=out))
             print("%-6s %2d %-8s %6d x %-5d %9.3f %9.3f %9.1f %9.0f" % (name, n, mode, fw, fh, med, mn, mb, mb / med))
         med, mn = timed(lambda: out.copy_(src))
         print("%-6s %2d %-8s %6d x %-5d %9.3f %9.3f %9.1f %9.0f" % (name, n, "copy", fw, fh, med, mn, mb, mb / med))
@@ -64,7 +65,7 @@ for name, (h, w) in (("1080p", (1080, 1920)), ("4K", (2160, 3840))):
             def two():
                 return kernels.stitch_panorama(T, imgs[0], np.linalg.inv(H), (mx, my), (wt, ht), (tsx, tsy), (qsx, qsy), (ph, pw), 0, 0.2,
                                                zero_origin=False, fast=False)
-            same = (ph, pw) == (fh, fw) and bool((two() == kernels.stitch_sequence(imgs, inv, rects, 0, order, 0, origin, (fh, fw))).all())
+            same = (ph, pw) == (fh, fw) and bool((two() == kernels.stitch_sequence_on(imgs, geom, order, 0)).all())
             med, mn = timed(two)
             print("%-6s %2d %-8s %6d x %-5d %9.3f %9.3f %9.1f %9.0f   (stitch_panorama exact; same bytes as the sequence paste: %s)"
                   % (name, n, "pair", pw, ph, med, mn, mb, mb / med, same))
