@@ -1119,6 +1119,108 @@ def _delta_matrix(delta):
     return np.eye(3) + np.append(delta, 0.0).reshape(3, 3)
 
 
+def _adjust_problem(who, rule, pairs, matches, masks, on):
+    """What `sequence_adjust` and `sequence_adjust_cameras` make of their matches and masks, once: sizes, offsets and mask words
+    checked, and everything put where `on` says -> blocks(records): the (blocks, count, status) of every edge for the rule's
+    per-edge records, from `kernels.<rule>_blocks` on the device or `kernels.host_<rule>_blocks` on the host.  rule: "bundle" or
+    "camera"; the entry points are looked up in `kernels` at every call."""
+    from .features import DeviceProblems
+    E = len(pairs)
+    on_dev = isinstance(matches, DeviceProblems)
+    sizes = list(matches.sizes) if on_dev else [int(np.asarray(a).reshape(-1, 2).shape[0]) for a, _ in matches]
+    if len(sizes) != E:
+        raise ValueError("%s: %d pairs take %d sets of matches, got %d" % (who, E, E, len(sizes)))
+    offsets = np.zeros(E + 1, dtype=np.int32)
+    offsets[1:] = np.cumsum(sizes)
+    words = max((max(sizes) + 63) // 64, 1)
+    tensor_masks = masks is not None and _is_tensor(masks)
+    if masks is None:
+        masks = np.full((E, words), -1, dtype=np.int64)
+    elif not tensor_masks:
+        masks = np.ascontiguousarray(masks)
+        if masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)) or masks.ndim != 2:
+            raise ValueError("%s: masks takes [E, words] uint64 or int64 words" % who)
+        masks = masks.view(np.int64)
+    if tuple(masks.shape)[0] != E or len(masks.shape) != 2 or masks.shape[1] < 1:
+        raise ValueError("%s: masks of shape %s for %d pairs" % (who, tuple(masks.shape), E))
+    if on == "device":
+        import torch
+        dev = _lib.require_gpu()
+        if on_dev:
+            pa, pb = matches.pts_a, matches.pts_b
+        else:
+            pa = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])).to(dev)
+            pb = torch.from_numpy(np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])).to(dev)
+        off_dev = torch.from_numpy(offsets).to(dev)
+        m_dev = (masks if tensor_masks else torch.from_numpy(masks)).to(dev).to(torch.int64).contiguous()
+
+        def blocks(records):
+            packed = getattr(kernels, rule + "_blocks")(pa, pb, off_dev, m_dev, records)
+            return getattr(kernels, rule + "_split")(packed.cpu().numpy())
+    else:
+        if on_dev:
+            pa, pb = matches.pts_a.cpu().numpy(), matches.pts_b.cpu().numpy()
+        else:
+            pa = np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])
+            pb = np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])
+        m_host = masks.cpu().numpy() if tensor_masks else masks
+
+        def blocks(records):
+            return getattr(kernels, "host_%s_blocks" % rule)(pa, pb, offsets, m_host, records)
+    return blocks
+
+
+def _levenberg(who, pairs, state, max_iters, info, evaluate, step, candidate, singular):
+    """The Levenberg-Marquardt loop of both registration rules -> the state of the last accepted step (`state` itself if none).
+
+    A rule supplies evaluate(state) -> (blocks, count, status) of every edge at a state, and the three things in which the loops
+    differ:
+      candidate(state, delta) -> the state the step leads to, or None for one that is refused without an evaluation;
+      singular: what a step whose system is singular means after the first step tried (on the first it raises) -- "raise", or
+        "reject" (a rejected step, lambda goes up);
+      step(blocks, lam) -> (delta, status): its `kernels.host_<rule>_step` call.
+    The rest is written once: the start's two refusals, lambda from ADJUST_LAMBDA0 by ADJUST_LAMBDA_FACTOR up to ADJUST_LAMBDA_MAX,
+    a step accepted iff its candidate's cost is strictly lower and no edge reports RWH_BUNDLE_BEHIND, the end after `max_iters`
+    accepted steps or on one that lowers the cost by less than ADJUST_REL_STOP of it, and `info`."""
+    blocks, _, status = evaluate(state)
+    if (status != _lib.RWH_BUNDLE_OK).any():
+        e = int(np.nonzero(status != _lib.RWH_BUNDLE_OK)[0][0])
+        raise ValueError("%s: pair %d (images %d and %d) has an inlier behind the camera at the start" % ((who, e) + pairs[e]))
+    if not np.isfinite(blocks[:, -1]).all():
+        e = int(np.nonzero(~np.isfinite(blocks[:, -1]))[0][0])
+        raise ValueError("%s: pair %d (images %d and %d) has a cost that is not finite at the start (a correspondence that is not "
+                         "finite?)" % ((who, e) + pairs[e]))
+    cost = float(blocks[:, -1].sum())
+    history, lam, iters, tried = [cost], ADJUST_LAMBDA0, 0, 0
+    while iters < max_iters and lam <= ADJUST_LAMBDA_MAX:
+        delta, st = step(blocks, lam)
+        tried += 1
+        if st != _lib.RWH_BUNDLE_OK:
+            if tried == 1 or singular == "raise":
+                raise ValueError("%s: the step's system is singular (an image that no edge with inliers touches?)" % who)
+            lam *= ADJUST_LAMBDA_FACTOR
+            continue
+        cand = candidate(state, delta)
+        accept = cand is not None
+        if accept:
+            cblocks, _, cstatus = evaluate(cand)
+            ccost = float(cblocks[:, -1].sum())
+            accept = bool((cstatus == _lib.RWH_BUNDLE_OK).all()) and ccost < cost
+        if not accept:
+            lam *= ADJUST_LAMBDA_FACTOR
+            continue
+        small = cost - ccost < ADJUST_REL_STOP * cost
+        state, blocks, cost = cand, cblocks, ccost
+        history.append(cost)
+        iters += 1
+        lam /= ADJUST_LAMBDA_FACTOR
+        if small:
+            break
+    if info is not None:
+        info["cost"], info["iters"], info["lambda"] = history, iters, lam
+    return state
+
+
 def sequence_adjust(Gs, pairs, matches, masks=None, anchor=0, max_iters=20, on="device", info=None):
     """Bundle adjustment of a sequence over its pair graph (the bundle rule of include/rwh.h): all G_i refined jointly, by
     Levenberg-Marquardt, over the inlier correspondences of every edge, so that the error of a chain no longer accumulates.
@@ -1158,87 +1260,22 @@ def sequence_adjust(Gs, pairs, matches, masks=None, anchor=0, max_iters=20, on="
         raise ValueError("sequence_adjust: a map that is not finite or not invertible")
     if E < 1:
         raise ValueError("sequence_adjust: no pairs")
-    from .features import DeviceProblems
-    on_dev = isinstance(matches, DeviceProblems)
-    sizes = list(matches.sizes) if on_dev else [int(np.asarray(a).reshape(-1, 2).shape[0]) for a, _ in matches]
-    if len(sizes) != E:
-        raise ValueError("sequence_adjust: %d pairs take %d sets of matches, got %d" % (E, E, len(sizes)))
-    offsets = np.zeros(E + 1, dtype=np.int32)
-    offsets[1:] = np.cumsum(sizes)
-    words = max((max(sizes) + 63) // 64, 1)
-    tensor_masks = masks is not None and _is_tensor(masks)
-    if masks is None:
-        masks = np.full((E, words), -1, dtype=np.int64)
-    elif not tensor_masks:
-        masks = np.ascontiguousarray(masks)
-        if masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)) or masks.ndim != 2:
-            raise ValueError("sequence_adjust: masks takes [E, words] uint64 or int64 words")
-        masks = masks.view(np.int64)
-    if tuple(masks.shape)[0] != E or len(masks.shape) != 2 or masks.shape[1] < 1:
-        raise ValueError("sequence_adjust: masks of shape %s for %d pairs" % (tuple(masks.shape), E))
-    if on == "device":
-        import torch
-        dev = _lib.require_gpu()
-        if on_dev:
-            pa, pb = matches.pts_a, matches.pts_b
-        else:
-            pa = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])).to(dev)
-            pb = torch.from_numpy(np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])).to(dev)
-        off_dev = torch.from_numpy(offsets).to(dev)
-        m_dev = (masks if tensor_masks else torch.from_numpy(masks)).to(dev).to(torch.int64).contiguous()
-
-        def evaluate(G):
-            return kernels.bundle_split(kernels.bundle_blocks(pa, pb, off_dev, m_dev, _bundle_transfers(G, pairs)).cpu().numpy())
-    else:
-        if on_dev:
-            pa, pb = matches.pts_a.cpu().numpy(), matches.pts_b.cpu().numpy()
-        else:
-            pa = np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])
-            pb = np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])
-        m_host = masks.cpu().numpy() if tensor_masks else masks
-
-        def evaluate(G):
-            return kernels.host_bundle_blocks(pa, pb, offsets, m_host, _bundle_transfers(G, pairs))
-
-    blocks, _, status = evaluate(Gs)
-    if (status != _lib.RWH_BUNDLE_OK).any():
-        e = int(np.nonzero(status != _lib.RWH_BUNDLE_OK)[0][0])
-        raise ValueError("sequence_adjust: pair %d (images %d and %d) has an inlier behind the camera at the start" % ((e,) + pairs[e]))
-    if not np.isfinite(blocks[:, -1]).all():
-        e = int(np.nonzero(~np.isfinite(blocks[:, -1]))[0][0])
-        raise ValueError("sequence_adjust: pair %d (images %d and %d) has a cost that is not finite at the start (a correspondence "
-                         "that is not finite?)" % ((e,) + pairs[e]))
-    cost = float(blocks[:, -1].sum())
-    history, lam, iters = [cost], ADJUST_LAMBDA0, 0
+    blocks = _adjust_problem("sequence_adjust", "bundle", pairs, matches, masks, on)
     signs = np.sign(dets)
-    while iters < max_iters and lam <= ADJUST_LAMBDA_MAX:
-        delta, st = kernels.host_bundle_step(n, anchor, pairs, blocks, lam)
-        if st != _lib.RWH_BUNDLE_OK:
-            raise ValueError("sequence_adjust: the step's system is singular (an image that no edge with inliers touches?)")
+
+    def candidate(G, delta):
+        # G_i (I + D(delta_i)), each over its largest |entry|; refused unless every determinant is finite with its starting sign
         with np.errstate(all="ignore"):
-            cand = np.stack([Gs[i] if i == anchor else Gs[i] @ _delta_matrix(delta[i]) for i in range(n)])
+            cand = np.stack([G[i] if i == anchor else G[i] @ _delta_matrix(delta[i]) for i in range(n)])
             scale = np.abs(cand).reshape(n, 9).max(axis=1)
             scale[anchor] = 1.0
             cand = cand / scale[:, None, None]
             cdet = np.linalg.det(cand) if np.isfinite(cand).all() else np.full(n, np.nan)
-        accept = bool((np.isfinite(cdet) & (np.sign(cdet) == signs)).all())
-        if accept:
-            cblocks, _, cstatus = evaluate(cand)
-            ccost = float(cblocks[:, -1].sum())
-            accept = bool((cstatus == _lib.RWH_BUNDLE_OK).all()) and ccost < cost
-        if not accept:
-            lam *= ADJUST_LAMBDA_FACTOR
-            continue
-        small = cost - ccost < ADJUST_REL_STOP * cost
-        Gs, blocks, cost = cand, cblocks, ccost
-        history.append(cost)
-        iters += 1
-        lam /= ADJUST_LAMBDA_FACTOR
-        if small:
-            break
-    if info is not None:
-        info["cost"], info["iters"], info["lambda"] = history, iters, lam
-    return Gs
+        return cand if bool((np.isfinite(cdet) & (np.sign(cdet) == signs)).all()) else None
+
+    return _levenberg("sequence_adjust", pairs, Gs, max_iters, info, evaluate=lambda G: blocks(_bundle_transfers(G, pairs)),
+                      candidate=candidate, singular="raise",        # at every step
+                      step=lambda blk, lam: kernels.host_bundle_step(n, anchor, pairs, blk, lam))
 
 
 # ------------------------------------------- registration over rotations and focal lengths (the camera rule) ----
@@ -1370,90 +1407,24 @@ def sequence_adjust_cameras(shapes, Rs, fs, pairs, matches, masks=None, anchor=0
             raise ValueError("%s: shape %r of image %d; (h, w[, c])" % (who, shape, i))
     if E < 1:
         raise ValueError("%s: no pairs" % who)
-    from .features import DeviceProblems
-    on_dev = isinstance(matches, DeviceProblems)
-    sizes = list(matches.sizes) if on_dev else [int(np.asarray(a).reshape(-1, 2).shape[0]) for a, _ in matches]
-    if len(sizes) != E:
-        raise ValueError("%s: %d pairs take %d sets of matches, got %d" % (who, E, E, len(sizes)))
-    offsets = np.zeros(E + 1, dtype=np.int32)
-    offsets[1:] = np.cumsum(sizes)
-    words = max((max(sizes) + 63) // 64, 1)
-    tensor_masks = masks is not None and _is_tensor(masks)
-    if masks is None:
-        masks = np.full((E, words), -1, dtype=np.int64)
-    elif not tensor_masks:
-        masks = np.ascontiguousarray(masks)
-        if masks.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)) or masks.ndim != 2:
-            raise ValueError("%s: masks takes [E, words] uint64 or int64 words" % who)
-        masks = masks.view(np.int64)
-    if tuple(masks.shape)[0] != E or len(masks.shape) != 2 or masks.shape[1] < 1:
-        raise ValueError("%s: masks of shape %s for %d pairs" % (who, tuple(masks.shape), E))
-    if on == "device":
-        import torch
-        dev = _lib.require_gpu()
-        if on_dev:
-            pa, pb = matches.pts_a, matches.pts_b
-        else:
-            pa = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])).to(dev)
-            pb = torch.from_numpy(np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])).to(dev)
-        off_dev = torch.from_numpy(offsets).to(dev)
-        m_dev = (masks if tensor_masks else torch.from_numpy(masks)).to(dev).to(torch.int64).contiguous()
+    blocks = _adjust_problem(who, "camera", pairs, matches, masks, on)
 
-        def evaluate(R, f):
-            return kernels.camera_split(kernels.camera_blocks(pa, pb, off_dev, m_dev, _camera_records(shapes, R, f, pairs)).cpu().numpy())
-    else:
-        if on_dev:
-            pa, pb = matches.pts_a.cpu().numpy(), matches.pts_b.cpu().numpy()
-        else:
-            pa = np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1, 2) for a, _ in matches])
-            pb = np.concatenate([np.asarray(b, dtype=np.float32).reshape(-1, 2) for _, b in matches])
-        m_host = masks.cpu().numpy() if tensor_masks else masks
-
-        def evaluate(R, f):
-            return kernels.host_camera_blocks(pa, pb, offsets, m_host, _camera_records(shapes, R, f, pairs))
-
-    blocks, _, status = evaluate(Rs, fs)
-    if (status != _lib.RWH_BUNDLE_OK).any():
-        e = int(np.nonzero(status != _lib.RWH_BUNDLE_OK)[0][0])
-        raise ValueError("%s: pair %d (images %d and %d) has an inlier behind the camera at the start" % ((who, e) + pairs[e]))
-    if not np.isfinite(blocks[:, -1]).all():
-        e = int(np.nonzero(~np.isfinite(blocks[:, -1]))[0][0])
-        raise ValueError("%s: pair %d (images %d and %d) has a cost that is not finite at the start (a correspondence that is not "
-                         "finite?)" % ((who, e) + pairs[e]))
-    cost = float(blocks[:, -1].sum())
-    history, lam, iters, tried = [cost], ADJUST_LAMBDA0, 0, 0
-    while iters < max_iters and lam <= ADJUST_LAMBDA_MAX:
-        delta, st = kernels.host_camera_step(n, anchor, pairs, blocks, lam, focals)
-        tried += 1
-        if st != _lib.RWH_BUNDLE_OK:
-            if tried == 1:
-                raise ValueError("%s: the step's system is singular (an image that no edge with inliers touches?)" % who)
-            # Later on it is the damping that has become too small for a direction the data do not determine (the focal length of
-            # images that are translations of each other): a rejected step, lambda goes up again.
-            lam *= ADJUST_LAMBDA_FACTOR
-            continue
+    def candidate(cameras, delta):
+        # f_i (1 + phi_i), refused unless every one is finite and > 0 (and delta finite); then the rotations nearest to
+        # R_i exp([omega_i]x), which are not computed for a refused candidate
+        R, f = cameras
         with np.errstate(all="ignore"):
-            cf = fs * (1.0 + delta[:, 3])
-            accept = bool((np.isfinite(cf) & (cf > 0)).all()) and bool(np.isfinite(delta).all())
-            if accept:
-                cR = np.stack([Rs[i] if i == anchor else _nearest_rotation(Rs[i] @ _rodrigues(delta[i, :3])) for i in range(n)])
-        if accept:
-            cblocks, _, cstatus = evaluate(cR, cf)
-            ccost = float(cblocks[:, -1].sum())
-            accept = bool((cstatus == _lib.RWH_BUNDLE_OK).all()) and ccost < cost
-        if not accept:
-            lam *= ADJUST_LAMBDA_FACTOR
-            continue
-        small = cost - ccost < ADJUST_REL_STOP * cost
-        Rs, fs, blocks, cost = cR, cf, cblocks, ccost
-        history.append(cost)
-        iters += 1
-        lam /= ADJUST_LAMBDA_FACTOR
-        if small:
-            break
-    if info is not None:
-        info["cost"], info["iters"], info["lambda"] = history, iters, lam
-    return Rs, fs
+            cf = f * (1.0 + delta[:, 3])
+            if not (bool((np.isfinite(cf) & (cf > 0)).all()) and bool(np.isfinite(delta).all())):
+                return None
+            return np.stack([R[i] if i == anchor else _nearest_rotation(R[i] @ _rodrigues(delta[i, :3])) for i in range(n)]), cf
+
+    # A singular step raises on the first step tried only.  Later on it is the damping that has become too small for a direction the
+    # data do not determine (the focal length of images that are translations of each other): a rejected step, lambda goes up again.
+    return _levenberg(who, pairs, (Rs, fs), max_iters, info,
+                      evaluate=lambda cameras: blocks(_camera_records(shapes, cameras[0], cameras[1], pairs)),
+                      candidate=candidate, singular="reject",
+                      step=lambda blk, lam: kernels.host_camera_step(n, anchor, pairs, blk, lam, focals))
 
 
 def _sequence_inputs(who, images, Hs, Gs, anchor, projection=None, focal=None, wrap=False):

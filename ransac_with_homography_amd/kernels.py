@@ -405,13 +405,73 @@ def refit_batched(pts_a, pts_b, offsets, masks):
 
 
 BUNDLE_BLOCK, BUNDLE_MAX_EDGES = _lib.RWH_BUNDLE_BLOCK, _lib.RWH_BUNDLE_MAX_EDGES
+CAMERA_BLOCK, CAMERA_RECORD = _lib.RWH_CAMERA_BLOCK, _lib.RWH_CAMERA_RECORD
+CAMERA_FOCALS = {"shared": _lib.RWH_CAMERA_FOCAL_SHARED, "per-image": _lib.RWH_CAMERA_FOCAL_PER_IMAGE}
 
 
+# ---- the registration rules (include/rwh.h): one marshalling per call shape, a rule gives its entry point, block width and records ----
 def _bundle_transfers(transfers, n_edges):
     t = np.ascontiguousarray(transfers, dtype=np.float64).reshape(-1, 9)
     if t.shape[0] != n_edges or not 1 <= n_edges <= BUNDLE_MAX_EDGES:
         raise ValueError("bundle_blocks: %d transfers for %d edges; 1 .. %d edges, a 3 x 3 transfer each" % (t.shape[0], n_edges, BUNDLE_MAX_EDGES))
     return t
+
+
+def _camera_records(records, n_edges):
+    r = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, CAMERA_RECORD)
+    if r.shape[0] != n_edges or not 1 <= n_edges <= BUNDLE_MAX_EDGES:
+        raise ValueError("camera_blocks: %d records for %d edges; 1 .. %d edges, a record of %d doubles each"
+                         % (r.shape[0], n_edges, BUNDLE_MAX_EDGES, CAMERA_RECORD))
+    return r
+
+
+def _edge_blocks(entry, width, checked, pts_a, pts_b, offsets, masks, records, out):
+    """The blocks of every edge on the device: library entry point `entry`, blocks of `width` values, `checked(records, E)` the
+    rule's per-edge records as a float64 [E, record] host array -> the packed [E, width + 2] tensor."""
+    lib = _lib.load()
+    _dev_check(pts_a, pts_b, offsets, masks)
+    E = offsets.shape[0] - 1
+    assert pts_a.dtype == torch.float32 and pts_b.dtype == torch.float32 and offsets.dtype == torch.int32
+    assert masks.dtype == torch.int64 and masks.dim() == 2 and masks.shape[0] == E and tuple(pts_a.shape) == tuple(pts_b.shape)
+    r_dev = torch.from_numpy(checked(records, E)).to(pts_a.device)
+    if pts_a.shape[0] == 0:
+        # edges without a single correspondence: an empty tensor has no address and the library refuses a null pointer, where the
+        # host twin gives zero blocks.  One row that no edge's offsets reach stands in; nothing of it is read.
+        pts_a = pts_b = torch.zeros((1, 2), dtype=torch.float32, device=pts_a.device)
+    if out is None:
+        blocks = torch.empty((E, width), dtype=torch.float64, device=pts_a.device)
+        count, status = torch.empty((2, E), dtype=torch.int32, device=pts_a.device)
+    else:
+        blocks, count, status = out
+        _dev_check(blocks, count, status)
+        assert blocks.dtype == torch.float64 and tuple(blocks.shape) == (E, width)
+        assert count.dtype == torch.int32 and status.dtype == torch.int32 and tuple(count.shape) == (E,) and tuple(status.shape) == (E,)
+    check(getattr(lib, entry)(_ptr(pts_a), _ptr(pts_b), _ptr(offsets), E, _ptr(masks), masks.shape[1], _ptr(r_dev), _ptr(blocks),
+                              _ptr(count), _ptr(status), _lib.stream_ptr()), entry)
+    return torch.cat([blocks, count.to(torch.float64)[:, None], status.to(torch.float64)[:, None]], dim=1)
+
+
+def _split(packed, width):
+    """(blocks float64 [E, width], count int32 [E], status int32 [E]) of a downloaded packed result (numpy)."""
+    packed = np.asarray(packed)
+    return np.ascontiguousarray(packed[:, :width]), packed[:, width].astype(np.int32), packed[:, width + 1].astype(np.int32)
+
+
+def _host_edge_blocks(entry, width, checked, pts_a, pts_b, offsets, masks, records):
+    """The host twin `entry` ("rwh_host_<rule>_blocks") of `_edge_blocks`: numpy in, (blocks, count, status) numpy out."""
+    lib = _lib.load()
+    pts_a, pts_b = np.ascontiguousarray(pts_a, dtype=np.float32).reshape(-1, 2), np.ascontiguousarray(pts_b, dtype=np.float32).reshape(-1, 2)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+    E = offsets.shape[0] - 1
+    masks = np.ascontiguousarray(masks).view(np.uint64).reshape(E, -1)
+    r = checked(records, E)
+    if pts_a.shape != pts_b.shape or E < 1 or int(offsets[0]) != 0 or int(offsets[-1]) != pts_a.shape[0] or (np.diff(offsets) < 0).any():
+        raise ValueError("%s: offsets must run from 0 to the %d correspondences without decreasing" % (entry[len("rwh_"):], pts_a.shape[0]))
+    blocks = np.empty((E, width), dtype=np.float64)
+    count, status = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
+    check(getattr(lib, entry)(pts_a.ctypes.data, pts_b.ctypes.data, offsets.ctypes.data, E, masks.ctypes.data, masks.shape[1],
+                              r.ctypes.data, blocks.ctypes.data, count.ctypes.data, status.ctypes.data), entry)
+    return blocks, count, status
 
 
 def bundle_blocks(pts_a, pts_b, offsets, masks, transfers, out=None):
@@ -423,52 +483,18 @@ def bundle_blocks(pts_a, pts_b, offsets, masks, transfers, out=None):
     (`bundle_split` takes it apart).  out: optionally the three tensors the library writes -- blocks [E, 153] float64, count [E]
     and status [E] int32, contiguous, on the GPU -- instead of fresh ones.  Edges without any correspondence ([0, 2] points) give
     zero blocks, as the host twin's.  Enqueued on torch's current stream."""
-    lib = _lib.load()
-    _dev_check(pts_a, pts_b, offsets, masks)
-    E = offsets.shape[0] - 1
-    assert pts_a.dtype == torch.float32 and pts_b.dtype == torch.float32 and offsets.dtype == torch.int32
-    assert masks.dtype == torch.int64 and masks.dim() == 2 and masks.shape[0] == E and tuple(pts_a.shape) == tuple(pts_b.shape)
-    t_dev = torch.from_numpy(_bundle_transfers(transfers, E)).to(pts_a.device)
-    if pts_a.shape[0] == 0:
-        # edges without a single correspondence: an empty tensor has no address and the library refuses a null pointer, where the
-        # host twin gives zero blocks.  One row that no edge's offsets reach stands in; nothing of it is read.
-        pts_a = pts_b = torch.zeros((1, 2), dtype=torch.float32, device=pts_a.device)
-    if out is None:
-        blocks = torch.empty((E, BUNDLE_BLOCK), dtype=torch.float64, device=pts_a.device)
-        count, status = torch.empty((2, E), dtype=torch.int32, device=pts_a.device)
-    else:
-        blocks, count, status = out
-        _dev_check(blocks, count, status)
-        assert blocks.dtype == torch.float64 and tuple(blocks.shape) == (E, BUNDLE_BLOCK)
-        assert count.dtype == torch.int32 and status.dtype == torch.int32 and tuple(count.shape) == (E,) and tuple(status.shape) == (E,)
-    check(lib.rwh_bundle_blocks(_ptr(pts_a), _ptr(pts_b), _ptr(offsets), E, _ptr(masks), masks.shape[1], _ptr(t_dev), _ptr(blocks),
-                                _ptr(count), _ptr(status), _lib.stream_ptr()), "rwh_bundle_blocks")
-    return torch.cat([blocks, count.to(torch.float64)[:, None], status.to(torch.float64)[:, None]], dim=1)
+    return _edge_blocks("rwh_bundle_blocks", BUNDLE_BLOCK, _bundle_transfers, pts_a, pts_b, offsets, masks, transfers, out)
 
 
 def bundle_split(packed):
     """(blocks float64 [E, 153], count int32 [E], status int32 [E]) of a downloaded `bundle_blocks` result (numpy)."""
-    packed = np.asarray(packed)
-    return (np.ascontiguousarray(packed[:, :BUNDLE_BLOCK]), packed[:, BUNDLE_BLOCK].astype(np.int32),
-            packed[:, BUNDLE_BLOCK + 1].astype(np.int32))
+    return _split(packed, BUNDLE_BLOCK)
 
 
 def host_bundle_blocks(pts_a, pts_b, offsets, masks, transfers):
     """The host twin of `bundle_blocks` (rwh_host_bundle_blocks): numpy arrays in, (blocks, count, status) numpy out, the same
     operations in the same order.  Uses no device and works without a GPU."""
-    lib = _lib.load()
-    pts_a, pts_b = np.ascontiguousarray(pts_a, dtype=np.float32).reshape(-1, 2), np.ascontiguousarray(pts_b, dtype=np.float32).reshape(-1, 2)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-    E = offsets.shape[0] - 1
-    masks = np.ascontiguousarray(masks).view(np.uint64).reshape(E, -1)
-    t = _bundle_transfers(transfers, E)
-    if pts_a.shape != pts_b.shape or E < 1 or int(offsets[0]) != 0 or int(offsets[-1]) != pts_a.shape[0] or (np.diff(offsets) < 0).any():
-        raise ValueError("host_bundle_blocks: offsets must run from 0 to the %d correspondences without decreasing" % pts_a.shape[0])
-    blocks = np.empty((E, BUNDLE_BLOCK), dtype=np.float64)
-    count, status = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
-    check(lib.rwh_host_bundle_blocks(pts_a.ctypes.data, pts_b.ctypes.data, offsets.ctypes.data, E, masks.ctypes.data, masks.shape[1],
-                                     t.ctypes.data, blocks.ctypes.data, count.ctypes.data, status.ctypes.data), "rwh_host_bundle_blocks")
-    return blocks, count, status
+    return _host_edge_blocks("rwh_host_bundle_blocks", BUNDLE_BLOCK, _bundle_transfers, pts_a, pts_b, offsets, masks, transfers)
 
 
 def host_bundle_step(n, anchor, edges, blocks, lam):
@@ -482,18 +508,6 @@ def host_bundle_step(n, anchor, edges, blocks, lam):
     return delta, int(status[0])
 
 
-CAMERA_BLOCK, CAMERA_RECORD = _lib.RWH_CAMERA_BLOCK, _lib.RWH_CAMERA_RECORD
-CAMERA_FOCALS = {"shared": _lib.RWH_CAMERA_FOCAL_SHARED, "per-image": _lib.RWH_CAMERA_FOCAL_PER_IMAGE}
-
-
-def _camera_records(records, n_edges):
-    r = np.ascontiguousarray(records, dtype=np.float64).reshape(-1, CAMERA_RECORD)
-    if r.shape[0] != n_edges or not 1 <= n_edges <= BUNDLE_MAX_EDGES:
-        raise ValueError("camera_blocks: %d records for %d edges; 1 .. %d edges, a record of %d doubles each"
-                         % (r.shape[0], n_edges, BUNDLE_MAX_EDGES, CAMERA_RECORD))
-    return r
-
-
 def camera_blocks(pts_a, pts_b, offsets, masks, records, out=None):
     """The normal-equation blocks of every edge over rotations and focal lengths in one launch (rwh_camera_blocks; the camera rule of
     include/rwh.h).
@@ -503,51 +517,18 @@ def camera_blocks(pts_a, pts_b, offsets, masks, records, out=None):
     each block, then the edge's count and status as float64, for ONE download (`camera_split` takes it apart).  out: optionally the
     three tensors the library writes -- blocks [E, 45] float64, count [E] and status [E] int32, contiguous, on the GPU.  Edges
     without any correspondence give zero blocks, as the host twin's.  Enqueued on torch's current stream."""
-    lib = _lib.load()
-    _dev_check(pts_a, pts_b, offsets, masks)
-    E = offsets.shape[0] - 1
-    assert pts_a.dtype == torch.float32 and pts_b.dtype == torch.float32 and offsets.dtype == torch.int32
-    assert masks.dtype == torch.int64 and masks.dim() == 2 and masks.shape[0] == E and tuple(pts_a.shape) == tuple(pts_b.shape)
-    r_dev = torch.from_numpy(_camera_records(records, E)).to(pts_a.device)
-    if pts_a.shape[0] == 0:
-        # as in bundle_blocks: one row that no edge's offsets reach stands in for tensors without an address
-        pts_a = pts_b = torch.zeros((1, 2), dtype=torch.float32, device=pts_a.device)
-    if out is None:
-        blocks = torch.empty((E, CAMERA_BLOCK), dtype=torch.float64, device=pts_a.device)
-        count, status = torch.empty((2, E), dtype=torch.int32, device=pts_a.device)
-    else:
-        blocks, count, status = out
-        _dev_check(blocks, count, status)
-        assert blocks.dtype == torch.float64 and tuple(blocks.shape) == (E, CAMERA_BLOCK)
-        assert count.dtype == torch.int32 and status.dtype == torch.int32 and tuple(count.shape) == (E,) and tuple(status.shape) == (E,)
-    check(lib.rwh_camera_blocks(_ptr(pts_a), _ptr(pts_b), _ptr(offsets), E, _ptr(masks), masks.shape[1], _ptr(r_dev), _ptr(blocks),
-                                _ptr(count), _ptr(status), _lib.stream_ptr()), "rwh_camera_blocks")
-    return torch.cat([blocks, count.to(torch.float64)[:, None], status.to(torch.float64)[:, None]], dim=1)
+    return _edge_blocks("rwh_camera_blocks", CAMERA_BLOCK, _camera_records, pts_a, pts_b, offsets, masks, records, out)
 
 
 def camera_split(packed):
     """(blocks float64 [E, 45], count int32 [E], status int32 [E]) of a downloaded `camera_blocks` result (numpy)."""
-    packed = np.asarray(packed)
-    return (np.ascontiguousarray(packed[:, :CAMERA_BLOCK]), packed[:, CAMERA_BLOCK].astype(np.int32),
-            packed[:, CAMERA_BLOCK + 1].astype(np.int32))
+    return _split(packed, CAMERA_BLOCK)
 
 
 def host_camera_blocks(pts_a, pts_b, offsets, masks, records):
     """The host twin of `camera_blocks` (rwh_host_camera_blocks): numpy arrays in, (blocks, count, status) numpy out, the same
     operations in the same order.  Uses no device and works without a GPU."""
-    lib = _lib.load()
-    pts_a, pts_b = np.ascontiguousarray(pts_a, dtype=np.float32).reshape(-1, 2), np.ascontiguousarray(pts_b, dtype=np.float32).reshape(-1, 2)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int32)
-    E = offsets.shape[0] - 1
-    masks = np.ascontiguousarray(masks).view(np.uint64).reshape(E, -1)
-    r = _camera_records(records, E)
-    if pts_a.shape != pts_b.shape or E < 1 or int(offsets[0]) != 0 or int(offsets[-1]) != pts_a.shape[0] or (np.diff(offsets) < 0).any():
-        raise ValueError("host_camera_blocks: offsets must run from 0 to the %d correspondences without decreasing" % pts_a.shape[0])
-    blocks = np.empty((E, CAMERA_BLOCK), dtype=np.float64)
-    count, status = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
-    check(lib.rwh_host_camera_blocks(pts_a.ctypes.data, pts_b.ctypes.data, offsets.ctypes.data, E, masks.ctypes.data, masks.shape[1],
-                                     r.ctypes.data, blocks.ctypes.data, count.ctypes.data, status.ctypes.data), "rwh_host_camera_blocks")
-    return blocks, count, status
+    return _host_edge_blocks("rwh_host_camera_blocks", CAMERA_BLOCK, _camera_records, pts_a, pts_b, offsets, masks, records)
 
 
 def host_camera_step(n, anchor, edges, blocks, lam, focals="shared"):

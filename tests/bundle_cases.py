@@ -333,44 +333,54 @@ def concatenated(matches):
 
 
 # ---- the host twins ----
-def host_blocks(lib, pa, pb, offsets, masks, T):
-    """rwh_host_bundle_blocks -> (status of the call, blocks, count, status); the three outputs sit between 64-byte canaries that
-    are checked here."""
+def rule_host_blocks(lib, entry, block, record, pa, pb, offsets, masks, rec):
+    """The host twin `entry` of a rule with blocks of `block` values and records of `record` -> (status of the call, blocks, count,
+    status); the three outputs sit between 64-byte canaries that are checked here."""
     E = len(offsets) - 1
     pa, pb = np.ascontiguousarray(pa, dtype=np.float32), np.ascontiguousarray(pb, dtype=np.float32)
     offsets, masks = np.ascontiguousarray(offsets, dtype=np.int32), np.ascontiguousarray(masks).view(np.uint64)
-    T = np.ascontiguousarray(T, dtype=np.float64).reshape(E, 9)
-    sizes = [E * BLOCK * 8, E * 4, E * 4]
+    rec = np.ascontiguousarray(rec, dtype=np.float64).reshape(E, record)
+    sizes = [E * block * 8, E * 4, E * 4]
     bufs = [np.full(sz + 128, 0xA5, dtype=np.uint8) for sz in sizes]
-    st = lib.rwh_host_bundle_blocks(pa.ctypes.data, pb.ctypes.data, offsets.ctypes.data, E, masks.ctypes.data, masks.shape[1], T.ctypes.data,
-                                    bufs[0][64:].ctypes.data, bufs[1][64:].ctypes.data, bufs[2][64:].ctypes.data)
+    st = getattr(lib, entry)(pa.ctypes.data, pb.ctypes.data, offsets.ctypes.data, E, masks.ctypes.data, masks.shape[1], rec.ctypes.data,
+                             bufs[0][64:].ctypes.data, bufs[1][64:].ctypes.data, bufs[2][64:].ctypes.data)
     for buf in bufs:
         assert (buf[:64] == 0xA5).all() and (buf[-64:] == 0xA5).all(), "a byte outside an output was written"
-    return (st, bufs[0][64:-64].view(np.float64).reshape(E, BLOCK).copy(), bufs[1][64:-64].view(np.int32).copy(),
+    return (st, bufs[0][64:-64].view(np.float64).reshape(E, block).copy(), bufs[1][64:-64].view(np.int32).copy(),
             bufs[2][64:-64].view(np.int32).copy())
+
+
+def host_blocks(lib, pa, pb, offsets, masks, T):
+    """rwh_host_bundle_blocks through `rule_host_blocks`."""
+    return rule_host_blocks(lib, "rwh_host_bundle_blocks", BLOCK, 9, pa, pb, offsets, masks, T)
 
 
 def _same_bits(a, b):
     return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
 
 
-def device_blocks(pa, pb, offsets, masks, T):
-    """kernels.bundle_blocks into outputs that sit between guard words -> (blocks, count, status) in numpy; the guards are checked
-    and the packed result is checked against the three outputs."""
+def rule_device_blocks(rule, block, pa, pb, offsets, masks, rec):
+    """kernels.<rule>_blocks into outputs that sit between guard words -> (blocks, count, status) in numpy; the guards are checked
+    and the packed result, taken apart by kernels.<rule>_split, is checked against the three outputs."""
     import torch
     from ransac_with_homography_amd import kernels
     E = len(offsets) - 1
-    blocks_buf = torch.full((E * BLOCK + 16,), -7.0, dtype=torch.float64, device="cuda")
+    blocks_buf = torch.full((E * block + 16,), -7.0, dtype=torch.float64, device="cuda")
     tail_buf = torch.full((2, E + 32), -7, dtype=torch.int32, device="cuda")
-    out = (blocks_buf[8:-8].view(E, BLOCK), tail_buf[0, 16:-16], tail_buf[1, 16:-16])
-    packed = kernels.bundle_blocks(torch.from_numpy(pa).cuda(), torch.from_numpy(pb).cuda(), torch.from_numpy(offsets).cuda(),
-                                   torch.from_numpy(np.ascontiguousarray(masks).view(np.int64)).cuda(), T, out=out)
+    out = (blocks_buf[8:-8].view(E, block), tail_buf[0, 16:-16], tail_buf[1, 16:-16])
+    packed = getattr(kernels, rule + "_blocks")(torch.from_numpy(pa).cuda(), torch.from_numpy(pb).cuda(), torch.from_numpy(offsets).cuda(),
+                                                torch.from_numpy(np.ascontiguousarray(masks).view(np.int64)).cuda(), rec, out=out)
     flat, tail = blocks_buf.cpu().numpy(), tail_buf.cpu().numpy()
     assert (flat[:8] == -7.0).all() and (flat[-8:] == -7.0).all(), "a value outside the blocks was written"
     assert (tail[:, :16] == -7).all() and (tail[:, -16:] == -7).all(), "a word outside count or status was written"
-    blocks, count, status = kernels.bundle_split(packed.cpu().numpy())
-    assert _same_bits(blocks, flat[8:-8].reshape(E, BLOCK)) and np.array_equal(count, tail[0, 16:-16]) and np.array_equal(status, tail[1, 16:-16])
+    blocks, count, status = getattr(kernels, rule + "_split")(packed.cpu().numpy())
+    assert _same_bits(blocks, flat[8:-8].reshape(E, block)) and np.array_equal(count, tail[0, 16:-16]) and np.array_equal(status, tail[1, 16:-16])
     return blocks, count, status
+
+
+def device_blocks(pa, pb, offsets, masks, T):
+    """kernels.bundle_blocks through `rule_device_blocks`."""
+    return rule_device_blocks("bundle", BLOCK, pa, pb, offsets, masks, T)
 
 
 def host_step(lib, n, anchor, pairs, blocks, lam):

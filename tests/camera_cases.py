@@ -253,39 +253,13 @@ def grid_cameras():
 
 # ---- the host twins ----
 def host_blocks(lib, pa, pb, offsets, masks, rec):
-    """rwh_host_camera_blocks -> (status of the call, blocks, count, status); the three outputs sit between 64-byte canaries that
-    are checked here."""
-    E = len(offsets) - 1
-    pa, pb = np.ascontiguousarray(pa, dtype=np.float32), np.ascontiguousarray(pb, dtype=np.float32)
-    offsets, masks = np.ascontiguousarray(offsets, dtype=np.int32), np.ascontiguousarray(masks).view(np.uint64)
-    rec = np.ascontiguousarray(rec, dtype=np.float64).reshape(E, RECORD)
-    sizes = [E * BLOCK * 8, E * 4, E * 4]
-    bufs = [np.full(sz + 128, 0xA5, dtype=np.uint8) for sz in sizes]
-    st = lib.rwh_host_camera_blocks(pa.ctypes.data, pb.ctypes.data, offsets.ctypes.data, E, masks.ctypes.data, masks.shape[1], rec.ctypes.data,
-                                    bufs[0][64:].ctypes.data, bufs[1][64:].ctypes.data, bufs[2][64:].ctypes.data)
-    for buf in bufs:
-        assert (buf[:64] == 0xA5).all() and (buf[-64:] == 0xA5).all(), "a byte outside an output was written"
-    return (st, bufs[0][64:-64].view(np.float64).reshape(E, BLOCK).copy(), bufs[1][64:-64].view(np.int32).copy(),
-            bufs[2][64:-64].view(np.int32).copy())
+    """rwh_host_camera_blocks through bundle_cases.rule_host_blocks: the outputs between canaries."""
+    return bc.rule_host_blocks(lib, "rwh_host_camera_blocks", BLOCK, RECORD, pa, pb, offsets, masks, rec)
 
 
 def device_blocks(pa, pb, offsets, masks, rec):
-    """kernels.camera_blocks into outputs that sit between guard words -> (blocks, count, status) in numpy; the guards are checked
-    and the packed result is checked against the three outputs."""
-    import torch
-    from ransac_with_homography_amd import kernels
-    E = len(offsets) - 1
-    blocks_buf = torch.full((E * BLOCK + 16,), -7.0, dtype=torch.float64, device="cuda")
-    tail_buf = torch.full((2, E + 32), -7, dtype=torch.int32, device="cuda")
-    out = (blocks_buf[8:-8].view(E, BLOCK), tail_buf[0, 16:-16], tail_buf[1, 16:-16])
-    packed = kernels.camera_blocks(torch.from_numpy(pa).cuda(), torch.from_numpy(pb).cuda(), torch.from_numpy(offsets).cuda(),
-                                   torch.from_numpy(np.ascontiguousarray(masks).view(np.int64)).cuda(), rec, out=out)
-    flat, tail = blocks_buf.cpu().numpy(), tail_buf.cpu().numpy()
-    assert (flat[:8] == -7.0).all() and (flat[-8:] == -7.0).all(), "a value outside the blocks was written"
-    assert (tail[:, :16] == -7).all() and (tail[:, -16:] == -7).all(), "a word outside count or status was written"
-    blocks, count, status = kernels.camera_split(packed.cpu().numpy())
-    assert bc._same_bits(blocks, flat[8:-8].reshape(E, BLOCK)) and np.array_equal(count, tail[0, 16:-16]) and np.array_equal(status, tail[1, 16:-16])
-    return blocks, count, status
+    """kernels.camera_blocks through bundle_cases.rule_device_blocks: the outputs between guard words."""
+    return bc.rule_device_blocks("camera", BLOCK, pa, pb, offsets, masks, rec)
 
 
 def host_step(lib, n, anchor, focals, pairs, blocks, lam):

@@ -1,6 +1,6 @@
 """What sits around the bundle rule's arithmetic, without a GPU: the Levenberg-Marquardt loop of `sequence_adjust(on="host")` --
 its minimum against an independent optimiser (bundle_cases.reference_optimum), its reject branch, its lambda ceiling, its prefix,
-a BEHIND candidate, a determinant flip, wide mask rows, a non-finite b --, every side of the validity test and the two ends of a
+a BEHIND candidate, a determinant flip, a singular step, wide mask rows, a non-finite b --, every side of the validity test and the two ends of a
 launch on the host twin against the numpy restatement.  The steps tried are counted by wrapping kernels.host_bundle_step and
 kernels.host_bundle_blocks; the library is not changed for it."""
 import math
@@ -37,13 +37,14 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
 
 
-def traced_adjust(Gs, grid, on_step=None, on_blocks=None, **kw):
+def traced_adjust(Gs, grid, on_step=None, on_blocks=None, singular_at=None, events=None, **kw):
     """sequence_adjust(on="host") with both kernels entries wrapped -> (Gs, info, events).  events: ("blocks", blocks, status) for
-    every evaluation, ("step", lambda, the blocks it was given, delta) for every step tried.  on_step(k, delta) / on_blocks(k,
-    status) may replace what call k (from 0) returns."""
+    every evaluation, ("step", lambda, the blocks it was given, delta) for every step tried (a list given as `events` receives them,
+    for a run that raises).  on_step(k, delta) / on_blocks(k, status) may replace what call k (from 0) returns; singular_at makes
+    step k report RWH_BUNDLE_SINGULAR."""
     import homography as hg
     from ransac_with_homography_amd import kernels
-    events, info = [], {}
+    events, info = [] if events is None else events, {}
     real_step, real_blocks = kernels.host_bundle_step, kernels.host_bundle_blocks
 
     def step(n, anchor, edges, blocks, lam):
@@ -52,6 +53,8 @@ def traced_adjust(Gs, grid, on_step=None, on_blocks=None, **kw):
         delta, st = real_step(n, anchor, edges, blocks, lam)
         if on_step is not None:
             delta = on_step(k, delta)
+        if singular_at == k:
+            delta, st = np.zeros_like(delta), bc.SINGULAR
         events.append(("step", float(lam), np.array(blocks, dtype=np.float64, copy=True), delta.copy()))
         return delta, st
 
@@ -257,6 +260,21 @@ def test_a_determinant_flip_is_rejected_without_an_evaluation(grid, start, runs)
     assert rejects >= 1
     assert all(np.sign(np.linalg.det(G)) == np.sign(np.linalg.det(G0)) for G, G0 in zip(Gs, start))
     assert relative(bc.reference_cost(Gs, grid["pairs"], grid["matches"]), runs("chain")["cost"]) <= REL
+
+
+@pytest.mark.parametrize("at", [0, 1])
+def test_a_singular_step_raises_at_any_step(grid, start, at):
+    """A stand-in: step `at` reports RWH_BUNDLE_SINGULAR -- the first step tried, and the first one after an accepted step (from
+    the chain's start step 0 is accepted: its candidate's cost is lower and no edge is BEHIND, asserted).  ValueError both times,
+    where the camera rule counts the later one as a rejected step; no further step is tried and nothing more is evaluated."""
+    events = []
+    with pytest.raises(ValueError, match="sequence_adjust: the step's system is singular"):
+        traced_adjust(start, grid, singular_at=at, events=events)
+    assert [ev[0] for ev in events] == ["blocks", "step"] * (at + 1)
+    assert not events[-1][3].any()
+    if at == 1:
+        assert not events[2][2].any() and events[2][1][:, -1].sum() < events[0][1][:, -1].sum()
+        assert events[3][1] == 1e-3 / 10.0 and same_bits(events[3][2], events[2][1])
 
 
 # ---- 4. masks ----
