@@ -880,6 +880,125 @@ RWH_API int rwh_host_stitch_sequence_ex(const void* const* images, const int32_t
                                         int origin_x, int origin_y, int row_begin, int row_end, const double* gains);
 
 /*
+ * Block exposure gains for the sequence compositor (what OpenCV's BlocksGainCompensator does, and its stitcher's default): one gain
+ * MAP per image instead of one gain, so that what varies inside an image -- vignetting, a sky brighter on one side -- is
+ * compensated too.  The reference has no counterpart; this is held to THE BLOCK GAIN RULE below.  Everything not restated is the
+ * sequence, gain and projection rule's.  There is no ring form.
+ *
+ * The block gain rule.
+ *   Cells.  `block` is B = 2^s, one of 16, 32, 64, 128 (s = `shift`, 4 .. 7); 32 is OpenCV's block size, a convention and not a
+ *     measured optimum.  The canvas is cut into gh x gw cells of B x B pixels, gw = ceil(fw / B), gh = ceil(fh / B); cell (gx, gy)
+ *     holds the canvas pixels [gx B, min(gx B + B, fw)) x [gy B, min(gy B + B, fh)): edge cells are partial.  The candidates of a cell
+ *     are the images whose rectangles meet those pixels, in index order; the rank of a candidate is its place among them.  K
+ *     (`slots`) is the largest candidate count over all cells; the host computes it from the rectangles (rwh_sequence_cell_slots).
+ *   Cell statistics.  The sample set is the gain rule's (cx % stride == 0 and cy % stride == 0, 1 <= stride <= 255; the Python
+ *     default 1 is a convention).  For every cell, count and sum of the gain rule over the samples that lie in the cell, indexed by
+ *     candidate rank: tables is uint32 [gh][gw][2][K][K], count then sum (a 128 x 128 cell gives at most 16384 * 765 < 2^32).  A call
+ *     writes the table whole; ranks at or above the cell's candidate count are 0, as are pairs that never meet.  The values are
+ *     integers: they do not depend on the order of the adds.  Consequence: scattered back to image indices and summed over the
+ *     cells, the tables are the gain rule's count and sum at the same stride, exactly.
+ *   Cell gains.  Inputs: tables, `base` (N gains, each finite and > 0; NULL: all 1.0), sigma_n and sigma_g as the gain rule's.  Per
+ *     cell, the gain rule's Gains step on the candidates' K' x K' sub-tables with one change: I_ij = (double)sum / (3.0 * N_ij) *
+ *     base_i, the product rounded on its own.  The solution is r_{i,c}, the correction of image i in cell c on top of its base
+ *     gain.  r = 1.0 exactly for an image that is no candidate of the cell or that meets nobody in it.  A non-positive pivot or a
+ *     non-finite value anywhere refuses the call.
+ *   Smoothing.  `smooth` iterations, an integer of 0 .. 8 (the Python default 2 is OpenCV's convention).  Each applies
+ *     out = ((a + 2.0 * b) + c) * 0.25 to every plane r_i (float64 [gh][gw]), first along x (a, b, c = the left neighbour, the cell, the
+ *     right neighbour), then along y on the result, with edge replication, in that order of operations.
+ *   Maps.  M_i[c] = base_i * r_i[c]: float64 [N][gh][gw].  An entry that is not finite and > 0 refuses the call.
+ *   Applying maps.  At canvas pixel (cx, cy): u = ((double)cx + 0.5) / B - 0.5 (exact).  If u <= 0: x0 = x1 = 0 and t = 0; if
+ *     u >= gw - 1: x0 = x1 = gw - 1 and t = 0; otherwise x0 = floor(u), x1 = x0 + 1, t = u - x0.  The same for y with fraction q.
+ *     top = M[y0][x0] * (1 - t) + M[y0][x1] * t, bot likewise on row y1, g = top * (1 - q) + bot * q; nothing is contracted.
+ *     Wherever the gain rule uses g_i this uses g: the sample value is min(v_k * g, 255.0).  With every entry 1.0 the canvas is the
+ *     canvas without gains.  With every entry of M_i equal to g_i the canvas is the gain rule's for those g_i, byte for byte,
+ *     WHENEVER g_i has at most 53 - (s + 1) significant bits (any float32 value has): t and q are multiples of 2^-(s+1), so the two
+ *     products are then exact and their sum is g_i.  For another g_i the lerp of a constant may round to a neighbour of g_i (1.3 does,
+ *     at t = 3/16), and a byte whose product lies on an integer may then differ by one.
+ *   The seam finder's survey (the seam rule) keeps scalar gains: with maps in use it is given `base`.
+ *
+ * rwh_sequence_cell_slots: K from the rectangles (rects, origin and canvas as rwh_stitch_sequence's; (0, 0) on a projected canvas).
+ * RWH_E_INVALID (negative): a shift outside 4 .. 7, n outside 1 .. RWH_SEQ_MAX_IMAGES, a rectangle off the canvas.
+ * rwh_sequence_cell_stats / _proj: images .. origin (or ray tables) as rwh_sequence_overlap_stats / _proj; slots must be
+ * rwh_sequence_cell_slots's value; d_tables: device, uint32, rwh_sequence_cell_stats_table_bytes(canvas_h, canvas_w, shift, slots)
+ * bytes, 4-byte aligned, written whole by every call; d_workspace: rwh_sequence_cell_stats_workspace_bytes(n) bytes, 8-byte aligned
+ * (the descriptor table).  One workgroup owns one cell: it tests the clipped cell once against the N rectangles, walks the cell's
+ * samples, reduces per-pair wave sums into 2 x K x K uint32 accumulators in LDS and stores its slot -- no global atomics, no second
+ * kernel.  RWH_E_INVALID, before anything is launched: what rwh_sequence_overlap_stats refuses, a shift outside 4 .. 7, another
+ * `slots`, a NULL or misaligned table.  rwh_host_sequence_cell_stats / _proj: the same per-sample arithmetic on host memory.
+ * rwh_host_sequence_block_gains: Cell gains, Smoothing and Maps (host only, plain C++; the cell solves are the gain rule's solver).
+ * maps: float64 [n][gh][gw], written whole.  RWH_E_INVALID: a NULL pointer, what rwh_sequence_cell_slots refuses, another `slots`, a
+ * sigma or base gain that is not finite and > 0, smooth outside 0 .. 8, a non-positive pivot, a map entry not finite and > 0.
+ * rwh_stitch_sequence_maps / _proj: rwh_stitch_sequence_ex / _proj with the gains read from maps: d_maps, device, float64
+ * [n][gh][gw] for `shift`, 8-byte aligned (a pointer and the block travel in the kernel arguments where the N gains travel).  The
+ * kernels of the calls without maps are the code they were.  RWH_E_INVALID: what rwh_stitch_sequence refuses, NULL or misaligned
+ * maps, a shift outside 4 .. 7.  The device entries cannot read the maps' values; rwh_host_stitch_sequence_maps / _proj (the host
+ * twins, maps in host memory) refuse an entry that is not finite and > 0.
+ * rwh_stitch_multiband_maps / _proj and rwh_stitch_sequence_labels_maps / _proj, with their host twins: rwh_stitch_multiband(_labels)
+ * and rwh_stitch_sequence_labels with `d_maps, shift` where those take `gains`.  The multi-band calls take a label plane that may be
+ * NULL: NULL is the multi-band rule's Winner, a plane the seam rule's.  Refusals as the calls they extend, plus the maps' and shift's.
+ */
+RWH_API int rwh_sequence_cell_slots(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y, int shift);
+RWH_API int64_t rwh_sequence_cell_stats_workspace_bytes(int n);
+RWH_API int64_t rwh_sequence_cell_stats_table_bytes(int canvas_h, int canvas_w, int shift, int slots);
+RWH_API int rwh_sequence_cell_stats(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                    int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int shift, int stride, int slots,
+                                    uint32_t* d_tables, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_sequence_cell_stats_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                         const double* d_col, const double* d_row, int canvas_h, int canvas_w, int shift, int stride,
+                                         int slots, uint32_t* d_tables, void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_sequence_cell_stats(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                         int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int shift, int stride,
+                                         int slots, uint32_t* tables);
+RWH_API int rwh_host_sequence_cell_stats_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                              const double* col, const double* row, int canvas_h, int canvas_w, int shift, int stride,
+                                              int slots, uint32_t* tables);
+RWH_API int rwh_host_sequence_block_gains(const uint32_t* tables, const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x,
+                                          int origin_y, int shift, int slots, const double* base, double sigma_n, double sigma_g,
+                                          int smooth, double* maps);
+RWH_API int rwh_stitch_sequence_maps(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                     int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
+                                     int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                     void* stream, const double* d_maps, int shift);
+RWH_API int rwh_stitch_sequence_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                          const int32_t* order, int blend, const double* d_col, const double* d_row, void* d_canvas,
+                                          int canvas_h, int canvas_w, int row_begin, int row_end, void* d_workspace,
+                                          int64_t workspace_bytes, void* stream, const double* d_maps, int shift);
+RWH_API int rwh_host_stitch_sequence_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                          int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
+                                          int origin_x, int origin_y, int row_begin, int row_end, const double* maps, int shift);
+RWH_API int rwh_host_stitch_sequence_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                               const int32_t* order, int blend, const double* col, const double* row, void* canvas,
+                                               int canvas_h, int canvas_w, int row_begin, int row_end, const double* maps, int shift);
+RWH_API int rwh_stitch_multiband_maps(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                      int anchor, int bands, const double* d_maps, int shift, const unsigned char* d_labels,
+                                      void* d_canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
+                                      int64_t workspace_bytes, void* stream);
+RWH_API int rwh_stitch_multiband_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                           int bands, const double* d_maps, int shift, const unsigned char* d_labels,
+                                           const double* d_col, const double* d_row, void* d_canvas, int canvas_h, int canvas_w,
+                                           void* d_workspace, int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_stitch_multiband_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                           int anchor, int bands, const double* maps, int shift, const unsigned char* labels,
+                                           void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y);
+RWH_API int rwh_host_stitch_multiband_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                int bands, const double* maps, int shift, const unsigned char* labels,
+                                                const double* col, const double* row, void* canvas, int canvas_h, int canvas_w);
+RWH_API int rwh_stitch_sequence_labels_maps(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                            int anchor, const double* d_maps, int shift, const unsigned char* d_labels, void* d_canvas,
+                                            int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
+                                            int64_t workspace_bytes, void* stream);
+RWH_API int rwh_stitch_sequence_labels_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                 const double* d_maps, int shift, const unsigned char* d_labels, const double* d_col,
+                                                 const double* d_row, void* d_canvas, int canvas_h, int canvas_w, void* d_workspace,
+                                                 int64_t workspace_bytes, void* stream);
+RWH_API int rwh_host_stitch_sequence_labels_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects,
+                                                 int n, int anchor, const double* maps, int shift, const unsigned char* labels,
+                                                 void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y);
+RWH_API int rwh_host_stitch_sequence_labels_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects,
+                                                      int n, const double* maps, int shift, const unsigned char* labels,
+                                                      const double* col, const double* row, void* canvas, int canvas_h, int canvas_w);
+
+/*
  * Multi-band blending for the sequence compositor (Burt & Adelson 1983, as Brown & Lowe 2007, section 7, and OpenCV's stitcher use
  * it): low frequencies are blended over a wide region, so no exposure step remains, and high frequencies come from one image, so
  * a misregistration of a pixel or two does not ghost.  The reference has no counterpart; this is held to THE MULTI-BAND RULE below.

@@ -39,6 +39,8 @@ RWH_ORB_SCALE_ONE, RWH_ORB_SCALE_MAX, RWH_ORB_LEVELS_MAX, RWH_ORB_PYR_TILE_W, RW
 # the sequence compositor (include/rwh.h, the sequence rule): most images per call, its blend modes; the gain rule's largest stride
 RWH_SEQ_MAX_IMAGES, RWH_SEQ_PASTE, RWH_SEQ_FEATHER = 64, 0, 1
 RWH_SEQ_MAX_STRIDE = 255
+RWH_SEQ_BLOCKS = (16, 32, 64, 128)     # the block gain rule: the cell sizes; most smoothing iterations
+RWH_SEQ_MAX_SMOOTH = 8
 RWH_SEQ_MAX_BANDS = 8         # the multi-band rule: most bands
 RWH_SEAM_TILE_W, RWH_SEAM_TILE_H = 64, 16      # the seam rule: the relaxation kernel's tile
 # the bundle rule: float64 values per edge block, most edges (64 * 63 / 2), the statuses of an edge and of a step
@@ -71,6 +73,13 @@ EXPORTS = ("rwh_abi_version", "rwh_strerror", "rwh_lab_tune", "rwh_lab_clock_pro
            "rwh_host_sequence_seams_proj", "rwh_stitch_multiband_labels", "rwh_stitch_multiband_labels_proj",
            "rwh_host_stitch_multiband_labels", "rwh_host_stitch_multiband_labels_proj", "rwh_stitch_sequence_labels",
            "rwh_stitch_sequence_labels_proj", "rwh_host_stitch_sequence_labels", "rwh_host_stitch_sequence_labels_proj",
+           "rwh_sequence_cell_slots", "rwh_sequence_cell_stats_workspace_bytes", "rwh_sequence_cell_stats_table_bytes",
+           "rwh_sequence_cell_stats", "rwh_sequence_cell_stats_proj", "rwh_host_sequence_cell_stats", "rwh_host_sequence_cell_stats_proj",
+           "rwh_host_sequence_block_gains", "rwh_stitch_sequence_maps", "rwh_stitch_sequence_maps_proj",
+           "rwh_host_stitch_sequence_maps", "rwh_host_stitch_sequence_maps_proj",
+           "rwh_stitch_multiband_maps", "rwh_stitch_multiband_maps_proj", "rwh_host_stitch_multiband_maps",
+           "rwh_host_stitch_multiband_maps_proj", "rwh_stitch_sequence_labels_maps", "rwh_stitch_sequence_labels_maps_proj",
+           "rwh_host_stitch_sequence_labels_maps", "rwh_host_stitch_sequence_labels_maps_proj",
            "rwh_bundle_blocks", "rwh_host_bundle_blocks", "rwh_host_bundle_step",
            "rwh_camera_blocks", "rwh_host_camera_blocks", "rwh_host_camera_step")
 
@@ -242,6 +251,26 @@ def _bind(lib):
         fn.restype, fn.argtypes = i64, types
     lib.rwh_host_sequence_gains.restype = i32
     lib.rwh_host_sequence_gains.argtypes = [vp, vp, i32, f64, f64, vp]                   # count sum n sigma_n sigma_g gains
+    # the block gain rule (no ring form): the cell statistics -- nothing of their own | h w, no out | shift stride slots tables,
+    # workspace bytes stream -- and the compositor on gain maps: the compositor's list with `maps shift` where it has `gains`
+    for form in forms[:2]:
+        f = front(form, [], [i32, i32], [i32, i32, i32, vp])
+        bind("rwh_sequence_cell_stats" + form, f + ws)
+        bind("rwh_host_sequence_cell_stats" + form, f)
+        f = front(form, [vp, i32], out, [i32, i32])
+        bind("rwh_stitch_sequence_maps" + form, f + ws + [vp, i32])
+        bind("rwh_host_stitch_sequence_maps" + form, f + [vp, i32])
+        f = front(form, [i32, vp, i32, vp], out, [])                                     # multi-band: bands maps shift labels (or NULL)
+        bind("rwh_stitch_multiband_maps" + form, f + ws)
+        bind("rwh_host_stitch_multiband_maps" + form, f)
+        f = front(form, [vp, i32, vp], out, [])                                          # label paste: maps shift labels
+        bind("rwh_stitch_sequence_labels_maps" + form, f + ws)
+        bind("rwh_host_stitch_sequence_labels_maps" + form, f)
+    bind("rwh_sequence_cell_slots", [vp, i32, i32, i32, i32, i32, i32])                  # rects n canvas h w origin_x origin_y shift
+    lib.rwh_sequence_cell_stats_workspace_bytes.restype, lib.rwh_sequence_cell_stats_workspace_bytes.argtypes = i64, [i32]
+    lib.rwh_sequence_cell_stats_table_bytes.restype, lib.rwh_sequence_cell_stats_table_bytes.argtypes = i64, [i32, i32, i32, i32]
+    # tables rects n canvas h w origin_x origin_y shift slots base sigma_n sigma_g smooth maps
+    bind("rwh_host_sequence_block_gains", [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, f64, f64, i32, vp])
     # the bundle rule: the edge blocks (device and host twin) and the damped step
     lib.rwh_bundle_blocks.restype = i32
     lib.rwh_bundle_blocks.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]     # pts_a pts_b offsets n_edges masks words T blocks count status stream

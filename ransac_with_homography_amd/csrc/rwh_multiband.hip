@@ -45,18 +45,19 @@ struct MbLabelArgs { MbArgs m; const unsigned char* labels; };   // labels: fh x
 // P and the winner at canvas pixel (cx, cy): the covering image with the greatest feather weight g, the lowest index on equal
 // weights (candidates are visited in index order and only a greater g replaces the best; g >= 1 wherever an image covers).
 // rays: the ray tables of the projection rule, read with PROJ only.
-template <bool GAIN, bool PROJ = false, bool RING = false>
-__host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains,
+template <bool GAIN, bool PROJ = false, bool RING = false, class G = const double*>
+__host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, G gains,
                                                              SeqRays rays = SeqRays{nullptr, nullptr}) {
     const int fx = a.ox + cx, fy = a.oy + cy;
     SeqRay ray;
     if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
+    [[maybe_unused]] const auto site = seq_gain_site(gains, cx, cy);
     double best = 0.0;
     uint32_t out = MB_NONE << 24;
     for (uint64_t m = cand; m; m &= m - 1) {
         const int i = __builtin_ctzll(m);
         double v[3], g = 0.0, gain = 1.0;
-        if constexpr (GAIN) gain = gains[i];
+        if constexpr (GAIN) gain = seq_gain_of(site, i);
         if (!seq_sample<true, GAIN, PROJ, RING>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray, a.fw)) continue;
         if (g > best) {
             best = g;
@@ -69,8 +70,8 @@ __host__ __device__ __forceinline__ uint32_t mb_winner_pixel(const SeqArgs& a, u
 }
 
 // (I_i, W_i) at plane pixel (x, y) of level 0: image i's bytes where it covers, P elsewhere; MB_ONE where i is the winner.
-template <bool GAIN, bool PROJ = false, bool RING = false>
-__host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i, uint32_t pwv, int x, int y, const double* gains,
+template <bool GAIN, bool PROJ = false, bool RING = false, class G = const double*>
+__host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i, uint32_t pwv, int x, int y, G gains,
                                                          SeqRays rays = SeqRays{nullptr, nullptr}) {
     MbPx o;
 #pragma unroll
@@ -78,7 +79,7 @@ __host__ __device__ __forceinline__ MbPx mb_level0_pixel(const SeqArgs& a, int i
     o.c[3] = (int16_t)((pwv >> 24) == (uint32_t)i ? MB_ONE : 0);
     if (x < a.fw && y < a.fh) {
         double v[3], g = 0.0, gain = 1.0;
-        if constexpr (GAIN) gain = gains[i];
+        if constexpr (GAIN) gain = seq_gain_of(seq_gain_site(gains, x, y), i);
         SeqRay ray;
         if constexpr (PROJ) ray = seq_ray(rays, x, y);
         if (seq_sample<false, GAIN, PROJ, RING>(a.desc[i], i == a.anchor, a.ox + x, a.oy + y, v, g, gain, &ray, a.fw)) {
@@ -287,6 +288,42 @@ __global__ __launch_bounds__(256) void mb_level0_kernel(const SeqWith<MbArgs, GA
     m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN, PROJ, RING>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l), seq_rays(l));
 }
 
+// The three head kernels on the gain maps of the block gain rule (include/rwh.h): the bodies above with the gain read from the
+// maps.  Kernels of their own: the forms above keep their argument types, their names and their code.  No ring form.
+template <bool PROJ>
+__global__ __launch_bounds__(256) void mb_maps_winner_kernel(const SeqWithMaps<MbArgs, PROJ> l) {
+    const MbArgs& m = l.a;
+    const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
+    const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
+    const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
+    if (x >= m.PW || y >= m.PH) return;
+    const bool on = x < m.a.fw && y < m.a.fh;
+    m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<true, PROJ, false>(m.a, cand, x, y, seq_gains(l), seq_rays(l)) : MB_NONE << 24;
+}
+
+template <bool PROJ>
+__global__ __launch_bounds__(256) void mb_maps_label_winner_kernel(const SeqWithMaps<MbLabelArgs, PROJ> l) {
+    const MbArgs& m = l.a.m;
+    const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
+    const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
+    const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
+    if (x >= m.PW || y >= m.PH) return;
+    uint32_t out = MB_NONE << 24;
+    if (x < m.a.fw && y < m.a.fh) out = seq_label_winner_pixel<true, PROJ>(m.a, cand, x, y, l.a.labels[(int64_t)y * m.a.fw + x], seq_gains(l), seq_rays(l));
+    m.pw[(int64_t)y * m.PW + x] = out;
+}
+
+template <bool PROJ>
+__global__ __launch_bounds__(256) void mb_maps_level0_kernel(const SeqWithMaps<MbArgs, PROJ> l) {
+    const MbArgs& m = l.a;
+    const int i = blockIdx.z;
+    const MbWin w = m.win[(size_t)i * (m.K + 1)];
+    const int lx = blockIdx.x * 64 + (threadIdx.x & 63), ly = blockIdx.y * 4 + seq_wave_row<PROJ>(threadIdx.x >> 6);
+    if (lx >= w.w || ly >= w.h) return;
+    const int x = w.x0 + lx, y = w.y0 + ly;
+    m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<true, PROJ, false>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l), seq_rays(l));
+}
+
 // The reduce from level l to l + 1 of image blockIdx.z.  A block makes MB_TW x MB_TH outputs from a (2 MB_TW + 3) x (2 MB_TH + 3)
 // source tile staged in LDS with whole-pixel (8-byte) loads, coalesced along the row.  Source column 2 X0 - 2 + j goes to E[j / 2]
 // (j even) or O[j / 2] (j odd): output tx then reads E[tx], O[tx], E[tx + 1], O[tx + 1], E[tx + 2], and the 32 lanes of a tile
@@ -456,8 +493,17 @@ static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains
     hipLaunchKernelGGL((mb_level0_kernel<GAIN, PROJ, RING>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
 }
 
-template <bool GAIN, bool PROJ, bool RING>
-static void mb_host_run(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays, const unsigned char* labels) {
+template <bool PROJ>
+static void mb_launch_head_maps(const MbArgs& m, const MbPlan& p, const SeqMaps& maps, SeqRays rays, hipStream_t s, const unsigned char* labels) {
+    const dim3 grid((p.PW + 63) / 64, (p.PH + 3) / 4);
+    if (labels) hipLaunchKernelGGL((mb_maps_label_winner_kernel<PROJ>), grid, dim3(256), 0, s, seq_with_maps<PROJ>(MbLabelArgs{m, labels}, maps, rays));
+    else hipLaunchKernelGGL((mb_maps_winner_kernel<PROJ>), grid, dim3(256), 0, s, seq_with_maps<PROJ>(m, maps, rays));
+    hipLaunchKernelGGL((mb_maps_level0_kernel<PROJ>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s,
+                       seq_with_maps<PROJ>(m, maps, rays));
+}
+
+template <bool GAIN, bool PROJ, bool RING, class G = const double*>
+static void mb_host_run(const MbArgs& m, const MbPlan& p, G gains, SeqRays rays, const unsigned char* labels) {
     const int n = m.a.n, K = p.K;
     const uint64_t all = seq_all(n);
     for (int y = 0; y < p.PH; ++y)
@@ -512,7 +558,7 @@ template <bool PROJ, bool RING = false>
 static int mb_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
                      int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
                      int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays,
-                     const unsigned char* d_labels = nullptr, bool labelled = false) {
+                     const unsigned char* d_labels = nullptr, bool labelled = false, const rwh::SeqMaps* maps = nullptr) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
@@ -527,7 +573,8 @@ static int mb_device(const void* const* d_images, const int32_t* hw, const doubl
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
     seq_put(p.win, (size_t)n * (p.K + 1) * (sizeof(MbWin) / 8), reinterpret_cast<uint64_t*>(base + p.win_at), s);
     mb_bind(m, p, base);
-    if (gains) mb_launch_head<true, PROJ, RING>(m, p, gains, rays, s, d_labels); else mb_launch_head<false, PROJ, RING>(m, p, nullptr, rays, s, d_labels);
+    if (maps) { if constexpr (!RING) mb_launch_head_maps<PROJ>(m, p, *maps, rays, s, d_labels); }
+    else if (gains) mb_launch_head<true, PROJ, RING>(m, p, gains, rays, s, d_labels); else mb_launch_head<false, PROJ, RING>(m, p, nullptr, rays, s, d_labels);
     for (int l = 0; l < p.K; ++l)
         hipLaunchKernelGGL(mb_down_kernel<RING>, dim3((p.maxw[l + 1] + MB_TW - 1) / MB_TW, (p.maxh[l + 1] + MB_TH - 1) / MB_TH, n), dim3(256), 0, s, m, l);
     for (int l = p.K; l >= 0; --l)
@@ -552,7 +599,8 @@ extern "C" int rwh_stitch_multiband_proj(const void* const* d_images, const int3
 template <bool PROJ, bool RING = false>
 static int mb_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
                    int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
-                   int origin_x, int origin_y, rwh::SeqRays rays, const unsigned char* labels = nullptr, bool labelled = false) {
+                   int origin_x, int origin_y, rwh::SeqRays rays, const unsigned char* labels = nullptr, bool labelled = false,
+                   const rwh::SeqMaps* maps = nullptr) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
@@ -566,7 +614,8 @@ static int mb_host(const void* const* images, const int32_t* hw, const double* m
     memcpy(base + p.desc_at, descs, (size_t)n * sizeof(SeqDesc));
     memcpy(base + p.win_at, p.win, (size_t)n * (p.K + 1) * sizeof(MbWin));
     mb_bind(m, p, base);
-    if (gains) mb_host_run<true, PROJ, RING>(m, p, gains, rays, labels); else mb_host_run<false, PROJ, RING>(m, p, nullptr, rays, labels);
+    if (maps) { if constexpr (!RING) mb_host_run<true, PROJ, false>(m, p, *maps, rays, labels); }
+    else if (gains) mb_host_run<true, PROJ, RING>(m, p, gains, rays, labels); else mb_host_run<false, PROJ, RING>(m, p, nullptr, rays, labels);
     free(base);
     return RWH_OK;
 }
@@ -614,6 +663,46 @@ extern "C" int rwh_host_stitch_multiband_labels_proj(const void* const* images, 
                                                      const double* row, void* canvas, int canvas_h, int canvas_w) {
     return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
                          rwh::SeqRays{col, row}, labels, true);
+}
+
+// The multi-band rule on the gain maps of the block gain rule: d_maps / maps and shift where the calls above take gains; labels may
+// be NULL (the multi-band rule's Winner) or a label plane (the seam rule's).  The host twins read the maps: every entry finite and > 0.
+extern "C" int rwh_stitch_multiband_maps(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                         int anchor, int bands, const double* d_maps, int shift, const unsigned char* d_labels,
+                                         void* d_canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
+                                         int64_t workspace_bytes, void* stream) {
+    rwh::SeqMaps maps;
+    if (!rwh::seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
+    return mb_device<false>(d_images, hw, inv_g, rects, n, anchor, bands, nullptr, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
+                            d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr}, d_labels, false, &maps);
+}
+
+extern "C" int rwh_stitch_multiband_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                              int bands, const double* d_maps, int shift, const unsigned char* d_labels,
+                                              const double* d_col, const double* d_row, void* d_canvas, int canvas_h, int canvas_w,
+                                              void* d_workspace, int64_t workspace_bytes, void* stream) {
+    rwh::SeqMaps maps;
+    if (!rwh::seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
+    return mb_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, nullptr, d_canvas, canvas_h, canvas_w, 0, 0,
+                           d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row}, d_labels, false, &maps);
+}
+
+extern "C" int rwh_host_stitch_multiband_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                              int anchor, int bands, const double* maps_in, int shift, const unsigned char* labels,
+                                              void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y) {
+    rwh::SeqMaps maps;
+    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || !rwh::seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !rwh::seq_maps_ok(maps, n)) return RWH_E_INVALID;
+    return mb_host<false>(images, hw, inv_g, rects, n, anchor, bands, nullptr, canvas, canvas_h, canvas_w, origin_x, origin_y,
+                          rwh::SeqRays{nullptr, nullptr}, labels, false, &maps);
+}
+
+extern "C" int rwh_host_stitch_multiband_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                   int bands, const double* maps_in, int shift, const unsigned char* labels,
+                                                   const double* col, const double* row, void* canvas, int canvas_h, int canvas_w) {
+    rwh::SeqMaps maps;
+    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || !rwh::seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !rwh::seq_maps_ok(maps, n)) return RWH_E_INVALID;
+    return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, nullptr, canvas, canvas_h, canvas_w, 0, 0,
+                         rwh::SeqRays{col, row}, labels, false, &maps);
 }
 
 extern "C" int64_t rwh_stitch_multiband_ring_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int bands) {

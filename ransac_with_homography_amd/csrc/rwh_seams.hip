@@ -236,6 +236,18 @@ __global__ __launch_bounds__(256) void sm_paste_kernel(const SeqWith<SmPasteArgs
     sm_paste_store(a, x, y, px & 0xffffffu);
 }
 
+// sm_paste_kernel on the gain maps of the block gain rule (include/rwh.h): a kernel of its own, the forms above stay the code they were.
+template <bool PROJ>
+__global__ __launch_bounds__(256) void sm_maps_paste_kernel(const SeqWithMaps<SmPasteArgs, PROJ> l) {
+    const SeqArgs& a = l.a.a;
+    const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
+    const uint64_t cand = seq_tile_mask(a, bx0, bx0 + 64, by0, by0 + 4);
+    const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
+    if (x >= a.fw || y >= a.fh) return;
+    const uint32_t px = seq_label_winner_pixel<true, PROJ>(a, cand, x, y, l.a.labels[(int64_t)y * a.fw + x], seq_gains(l), seq_rays(l));
+    sm_paste_store(a, x, y, px & 0xffffffu);
+}
+
 // ---- the plan: windows and workspace layout ----
 struct SmPlan {
     SmWin win[RWH_SEQ_MAX_IMAGES];
@@ -461,7 +473,8 @@ extern "C" int rwh_host_sequence_seams_proj(const void* const* images, const int
 template <bool PROJ>
 static int sm_paste_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
                            const double* gains, const unsigned char* d_labels, void* d_canvas, int canvas_h, int canvas_w,
-                           int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays) {
+                           int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays,
+                           const rwh::SeqMaps* maps = nullptr) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SmPasteArgs m;
@@ -476,7 +489,8 @@ static int sm_paste_device(const void* const* d_images, const int32_t* hw, const
     m.a.desc = static_cast<const SeqDesc*>(d_workspace);
     m.labels = d_labels;
     const dim3 grid((canvas_w + 63) / 64, (canvas_h + 3) / 4);
-    if (gains) hipLaunchKernelGGL((sm_paste_kernel<true, PROJ>), grid, dim3(256), 0, s, seq_with<true, PROJ>(m, gains, n, rays));
+    if (maps) hipLaunchKernelGGL((sm_maps_paste_kernel<PROJ>), grid, dim3(256), 0, s, seq_with_maps<PROJ>(m, *maps, rays));
+    else if (gains) hipLaunchKernelGGL((sm_paste_kernel<true, PROJ>), grid, dim3(256), 0, s, seq_with<true, PROJ>(m, gains, n, rays));
     else hipLaunchKernelGGL((sm_paste_kernel<false, PROJ>), grid, dim3(256), 0, s, seq_with<false, PROJ>(m, nullptr, n, rays));
     return check_launch();
 }
@@ -484,7 +498,7 @@ static int sm_paste_device(const void* const* d_images, const int32_t* hw, const
 template <bool PROJ>
 static int sm_paste_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
                          const double* gains, const unsigned char* labels, void* canvas, int canvas_h, int canvas_w, int origin_x,
-                         int origin_y, rwh::SeqRays rays) {
+                         int origin_y, rwh::SeqRays rays, const rwh::SeqMaps* maps = nullptr) {
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SeqArgs a;
@@ -497,7 +511,8 @@ static int sm_paste_host(const void* const* images, const int32_t* hw, const dou
     for (int y = 0; y < canvas_h; ++y)
         for (int x = 0; x < canvas_w; ++x) {
             const uint32_t lab = labels[(int64_t)y * canvas_w + x];
-            const uint32_t px = gains ? seq_label_winner_pixel<true, PROJ>(a, all, x, y, lab, gains, rays)
+            const uint32_t px = maps ? seq_label_winner_pixel<true, PROJ>(a, all, x, y, lab, *maps, rays)
+                                : gains ? seq_label_winner_pixel<true, PROJ>(a, all, x, y, lab, gains, rays)
                                       : seq_label_winner_pixel<false, PROJ>(a, all, x, y, lab, nullptr, rays);
             sm_paste_store(a, x, y, px & 0xffffffu);
         }
@@ -532,4 +547,44 @@ extern "C" int rwh_host_stitch_sequence_labels_proj(const void* const* images, c
                                                     const double* row, void* canvas, int canvas_h, int canvas_w) {
     return sm_paste_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, gains, labels, canvas, canvas_h, canvas_w, 0, 0,
                                rwh::SeqRays{col, row});
+}
+
+// Label paste on the gain maps of the block gain rule: d_maps / maps and shift where the calls above take gains.  The host twins
+// read the maps: every entry finite and > 0.
+extern "C" int rwh_stitch_sequence_labels_maps(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                               int anchor, const double* d_maps, int shift, const unsigned char* d_labels, void* d_canvas,
+                                               int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
+                                               int64_t workspace_bytes, void* stream) {
+    rwh::SeqMaps maps;
+    if (!rwh::seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
+    return sm_paste_device<false>(d_images, hw, inv_g, rects, n, anchor, nullptr, d_labels, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
+                                  d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr}, &maps);
+}
+
+extern "C" int rwh_stitch_sequence_labels_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                    const double* d_maps, int shift, const unsigned char* d_labels, const double* d_col,
+                                                    const double* d_row, void* d_canvas, int canvas_h, int canvas_w, void* d_workspace,
+                                                    int64_t workspace_bytes, void* stream) {
+    rwh::SeqMaps maps;
+    if (!rwh::seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
+    return sm_paste_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, nullptr, d_labels, d_canvas, canvas_h, canvas_w, 0, 0,
+                                 d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row}, &maps);
+}
+
+extern "C" int rwh_host_stitch_sequence_labels_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects,
+                                                    int n, int anchor, const double* maps_in, int shift, const unsigned char* labels,
+                                                    void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y) {
+    rwh::SeqMaps maps;
+    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || !rwh::seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !rwh::seq_maps_ok(maps, n)) return RWH_E_INVALID;
+    return sm_paste_host<false>(images, hw, inv_g, rects, n, anchor, nullptr, labels, canvas, canvas_h, canvas_w, origin_x, origin_y,
+                                rwh::SeqRays{nullptr, nullptr}, &maps);
+}
+
+extern "C" int rwh_host_stitch_sequence_labels_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects,
+                                                         int n, const double* maps_in, int shift, const unsigned char* labels,
+                                                         const double* col, const double* row, void* canvas, int canvas_h, int canvas_w) {
+    rwh::SeqMaps maps;
+    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || !rwh::seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !rwh::seq_maps_ok(maps, n)) return RWH_E_INVALID;
+    return sm_paste_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, nullptr, labels, canvas, canvas_h, canvas_w, 0, 0,
+                               rwh::SeqRays{col, row}, &maps);
 }

@@ -58,6 +58,71 @@ template <bool GAIN, bool PROJ = false, class A> static SeqWith<A, GAIN, PROJ> s
     return l;
 }
 
+// The third state of the gain switch (include/rwh.h, the block gain rule): gain MAPS instead of N gains.  m: float64 [n][gh][gw] (a
+// device pointer in a launch, host memory in the host twins), cells of 2^shift canvas pixels.  The pointer and three ints travel
+// where gains[64] travels; the forms above keep their types, so their kernels keep their names and their code.
+struct SeqMaps { const double* m; int gw, gh, shift; };
+template <class A, bool PROJ = false> struct SeqWithMaps { A a; SeqMaps maps; };
+template <class A> struct SeqWithMaps<A, true> { A a; SeqMaps maps; SeqRays rays; };
+template <class A, bool PROJ> __host__ __device__ __forceinline__ SeqMaps seq_gains(const SeqWithMaps<A, PROJ>& l) { return l.maps; }
+template <class A, bool PROJ> __host__ __device__ __forceinline__ SeqRays seq_rays(const SeqWithMaps<A, PROJ>& l) {
+    if constexpr (PROJ) return l.rays; else return SeqRays{nullptr, nullptr};
+}
+template <bool PROJ, class A> static SeqWithMaps<A, PROJ> seq_with_maps(const A& a, const SeqMaps& maps, SeqRays rays = SeqRays{nullptr, nullptr}) {
+    SeqWithMaps<A, PROJ> l;
+    l.a = a;
+    l.maps = maps;
+    if constexpr (PROJ) l.rays = rays;
+    return l;
+}
+
+// The cells of the block gain rule: B = 2^shift of 16 .. 128, ceil(side / B) cells along a side.
+constexpr int SEQ_SHIFT_MIN = 4, SEQ_SHIFT_MAX = 7;
+static int seq_cell_count(int side, int shift) { return (side + (1 << shift) - 1) >> shift; }
+// The maps of a call as the pixel functions take them; false: no maps, a misaligned pointer or another block.
+static bool seq_maps_of(const double* maps, int shift, int canvas_h, int canvas_w, SeqMaps& m) {
+    if (!maps || ((uintptr_t)maps & 7u) || shift < SEQ_SHIFT_MIN || shift > SEQ_SHIFT_MAX) return false;
+    m.m = maps; m.shift = shift;
+    m.gw = seq_cell_count(canvas_w, shift); m.gh = seq_cell_count(canvas_h, shift);
+    return true;
+}
+// Host maps are read before they are used (the host twins): every entry finite and > 0, as the gain rule asks of a gain.
+static bool seq_maps_ok(const SeqMaps& m, int n) {
+    for (size_t t = 0, end = (size_t)n * m.gw * m.gh; t < end; ++t)
+        if (!(isfinite(m.m[t]) && m.m[t] > 0.0)) return false;
+    return true;
+}
+
+// Where a pixel function gets the gain of image i at canvas pixel (cx, cy): seq_gain_site(gains, cx, cy) once per pixel, then
+// seq_gain_of(site, i) per image.  N gains: the site is the array and the gain gains[i].  Maps ("Applying maps" of the block gain
+// rule): the site is the pixel's four cells and two fractions -- u = ((double)cx + 0.5) / B - 0.5 is exact, B a power of two -- and
+// the gain the two-step lerp of image i's plane, every product and sum rounded on its own.
+struct SeqMapSite { const double* m; size_t plane; int o00, o01, o10, o11; double t, q; };
+__host__ __device__ __forceinline__ void seq_map_axis(int c, int cells, double inv_b, int& c0, int& c1, double& t) {
+    const double u = ((double)c + 0.5) * inv_b - 0.5;
+    if (u <= 0.0) { c0 = c1 = 0; t = 0.0; }
+    else if (u >= (double)(cells - 1)) { c0 = c1 = cells - 1; t = 0.0; }
+    else { c0 = (int)u; c1 = c0 + 1; t = u - (double)c0; }
+}
+__host__ __device__ __forceinline__ const double* seq_gain_site(const double* gains, int, int) { return gains; }
+__host__ __device__ __forceinline__ double seq_gain_of(const double* gains, int i) { return gains[i]; }
+__host__ __device__ __forceinline__ SeqMapSite seq_gain_site(const SeqMaps& g, int cx, int cy) {
+    const double inv_b = 1.0 / (double)(1 << g.shift);
+    int x0, x1, y0, y1;
+    SeqMapSite s;
+    seq_map_axis(cx, g.gw, inv_b, x0, x1, s.t);
+    seq_map_axis(cy, g.gh, inv_b, y0, y1, s.q);
+    s.m = g.m; s.plane = (size_t)g.gw * g.gh;
+    s.o00 = y0 * g.gw + x0; s.o01 = y0 * g.gw + x1; s.o10 = y1 * g.gw + x0; s.o11 = y1 * g.gw + x1;
+    return s;
+}
+__host__ __device__ __forceinline__ double seq_gain_of(const SeqMapSite& s, int i) {
+    const double* p = s.m + (size_t)i * s.plane;
+    const double top = p[s.o00] * (1.0 - s.t) + p[s.o01] * s.t;
+    const double bot = p[s.o10] * (1.0 - s.t) + p[s.o11] * s.t;
+    return top * (1.0 - s.q) + bot * s.q;
+}
+
 // The ray of canvas pixel (cx, cy) on the curved canvas: three products of table entries, no transcendental function.  Both
 // indices lie inside the canvas (the callers' bounds tests come first).  The column pair is one 16-byte load per lane; cy is
 // wave-uniform in every kernel, so the row pair is a scalar load.
@@ -150,21 +215,22 @@ __host__ __device__ __forceinline__ bool seq_sample(const SeqDesc& d, bool is_an
 }
 
 // One canvas pixel as 0x00BBGGRR.  cand: bit k set = image order[k] may cover the pixel (its rectangle meets the pixel's tile).
-// gains: the N gains of the gain rule, read with GAIN only.  rays: the ray tables, read with PROJ only (then ox = oy = 0).
+// gains: the N gains of the gain rule or the maps of the block gain rule (SeqMaps), read with GAIN only.  rays: the ray tables, read with PROJ only (then ox = oy = 0).
 // RING: a.fw is the period.
-template <bool FEATHER, bool GAIN = false, bool PROJ = false, bool RING = false>
-__host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, const double* gains = nullptr,
+template <bool FEATHER, bool GAIN = false, bool PROJ = false, bool RING = false, class G = const double*>
+__host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, G gains = nullptr,
                                                        SeqRays rays = SeqRays{nullptr, nullptr}) {
     const int fx = a.ox + cx, fy = a.oy + cy;
     SeqRay ray;
     if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
+    [[maybe_unused]] const auto site = seq_gain_site(gains, cx, cy);
     double num[3] = {0.0, 0.0, 0.0}, den = 0.0;
     bool covered = false;
     for (uint64_t m = cand; m; m &= m - 1) {
         const int i = a.order[__builtin_ctzll(m)];
         double v[3], g = 0.0;
         double gain = 1.0;
-        if constexpr (GAIN) gain = gains[i];
+        if constexpr (GAIN) gain = seq_gain_of(site, i);
         if (!seq_sample<FEATHER, GAIN, PROJ, RING>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray, a.fw)) continue;
         if constexpr (!FEATHER) {       // paste: the first image in `order` that covers the pixel
             uint32_t out = 0u;
@@ -191,18 +257,19 @@ __host__ __device__ __forceinline__ uint32_t seq_pixel(const SeqArgs& a, uint64_
 // equal weights.  -> the winner's bytes as 0x00BBGGRR with its index in the top byte, SEQ_LABEL_NONE there where nobody covers.
 // cand: candidate bits are image indices (order is 0 .. n-1), so a label of n or more meets no candidate and indexes nothing.
 constexpr uint32_t SEQ_LABEL_NONE = 0xffu;
-template <bool GAIN, bool PROJ = false>
+template <bool GAIN, bool PROJ = false, class G = const double*>
 __host__ __device__ __forceinline__ uint32_t seq_label_winner_pixel(const SeqArgs& a, uint64_t cand, int cx, int cy, uint32_t label,
-                                                                    const double* gains, SeqRays rays = SeqRays{nullptr, nullptr}) {
+                                                                    G gains, SeqRays rays = SeqRays{nullptr, nullptr}) {
     const int fx = a.ox + cx, fy = a.oy + cy;
     SeqRay ray;
     if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
+    [[maybe_unused]] const auto site = seq_gain_site(gains, cx, cy);
     double best = 0.0;
     uint32_t out = SEQ_LABEL_NONE << 24;
     for (uint64_t m = cand; m; m &= m - 1) {
         const int i = __builtin_ctzll(m);
         double v[3], g = 0.0, gain = 1.0;
-        if constexpr (GAIN) gain = gains[i];
+        if constexpr (GAIN) gain = seq_gain_of(site, i);
         if (!seq_sample<true, GAIN, PROJ>(a.desc[i], i == a.anchor, fx, fy, v, g, gain, &ray, a.fw)) continue;
         const bool named = (uint32_t)i == label;
         if (named || g > best) {
@@ -317,6 +384,106 @@ template <class F> static void seq_dispatch(bool feather, bool gain, const F& f)
 static bool seq_gains_ok(const double* gains, int n) {
     for (int i = 0; i < n; ++i)
         if (!(isfinite(gains[i]) && gains[i] > 0.0)) return false;
+    return true;
+}
+
+// The compositor's shape -- stitch_kernel's (rwh_stitch.hip): 256 lanes as 64 x 4, four consecutive pixels per lane, the 12 output
+// bytes in one store.
+constexpr int SEQ_PX = 4;
+
+__device__ __forceinline__ uint32_t seq_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = RWH_WAVE / 2; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+template <bool FEATHER, bool GAIN, bool PROJ = false, bool RING = false, class G = const double*>
+static void seq_host_rows(const SeqArgs& a, G gains, SeqRays rays = SeqRays{nullptr, nullptr}) {
+    const uint64_t all = seq_all(a.n);
+    for (int cy = a.row_begin; cy < a.row_end; ++cy)
+        for (int cx = 0; cx < a.fw; ++cx) {
+            const uint32_t p = seq_pixel<FEATHER, GAIN, PROJ, RING>(a, all, cx, cy, gains, rays);
+            unsigned char* out = a.dst + ((size_t)cy * a.fw + cx) * 3;
+            out[0] = (unsigned char)p; out[1] = (unsigned char)(p >> 8); out[2] = (unsigned char)(p >> 16);
+        }
+}
+
+// ---- the per-sample functions of the gain rule's statistics (include/rwh.h), which the block gain rule's cells share ----
+// The images that cover canvas pixel (cx, cy), bit i = image i (cand: bits of image indices), by the sequence rule's Coverage:
+// seq_sample's own test, its taps unused.  rays: the ray tables, read with PROJ only.
+template <bool PROJ = false, bool RING = false>
+__host__ __device__ __forceinline__ uint64_t seq_cover(const SeqArgs& a, uint64_t cand, int cx, int cy, SeqRays rays = SeqRays{nullptr, nullptr}) {
+    const int fx = a.ox + cx, fy = a.oy + cy;
+    SeqRay ray;
+    if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
+    uint64_t cov = 0;
+    for (uint64_t m = cand; m; m &= m - 1) {
+        const int i = __builtin_ctzll(m);
+        double v[3], g = 0.0;
+        if (seq_sample<false, false, PROJ, RING>(a.desc[i], i == a.anchor, fx, fy, v, g, 1.0, &ray, a.fw)) cov |= 1ull << i;
+    }
+    return cov;
+}
+
+// L_i of the gain rule: the sum of the three bytes paste would write for image i at a canvas pixel that it covers.
+template <bool PROJ = false, bool RING = false>
+__host__ __device__ __forceinline__ uint32_t seq_byte_sum(const SeqArgs& a, int i, int cx, int cy, SeqRays rays = SeqRays{nullptr, nullptr}) {
+    double v[3], g = 0.0;
+    SeqRay ray;
+    if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
+    if (!seq_sample<false, false, PROJ, RING>(a.desc[i], i == a.anchor, a.ox + cx, a.oy + cy, v, g, 1.0, &ray, a.fw)) return 0u;
+    return (uint32_t)(unsigned char)(int)v[0] + (uint32_t)(unsigned char)(int)v[1] + (uint32_t)(unsigned char)(int)v[2];
+}
+
+// the descriptor table at the head of a statistics workspace, a whole number of 128-byte lines
+static int64_t seq_stat_table_bytes(int n) { return ((int64_t)n * (int64_t)sizeof(SeqDesc) + 127) & ~(int64_t)127; }
+
+// The Gains step of the gain rule (include/rwh.h) on n images: A and b built in the rule's order from N(i, j) and I(i, j), the
+// square-root-free Cholesky A = L D L^T on the lower triangle, forward and back substitution.  Host only, float64, no LAPACK.
+// meets(i): count[i][i] > 0.  false: a non-positive pivot or a non-finite solution.  The gain rule calls it on its two tables, the
+// block gain rule on every cell's.
+template <class FM, class FN, class FI>
+static bool seq_solve_gains(int n, double alpha, double beta, const FM& meets, const FN& N, const FI& I, double* gains) {
+    static_assert(RWH_SEQ_MAX_IMAGES == 64, "A, b and y live on the stack");
+    double A[64 * 64], b[64], y[64];
+    memset(A, 0, sizeof(double) * (size_t)n * n);
+    memset(b, 0, sizeof(double) * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!meets(i)) { A[i * n + i] = 1.0; b[i] = 1.0; continue; }
+        for (int j = 0; j < n; ++j) {
+            A[i * n + i] += beta * N(i, j);
+            b[i] += beta * N(i, j);
+            if (j != i) {
+                A[i * n + i] += 2.0 * alpha * I(i, j) * I(i, j) * N(i, j);
+                A[i * n + j] -= 2.0 * alpha * I(i, j) * I(j, i) * N(i, j);
+            }
+        }
+    }
+    // A = L D L^T, L unit lower (kept below A's diagonal), D on the diagonal: a row that meets nobody (zeros off its diagonal,
+    // b_i == A_ii) comes out as b_i / A_ii = 1.0 exactly.
+    for (int j = 0; j < n; ++j) {
+        double d = A[j * n + j];
+        for (int k = 0; k < j; ++k) d -= A[j * n + k] * A[j * n + k] * A[k * n + k];
+        if (!(d > 0.0) || !isfinite(d)) return false;
+        A[j * n + j] = d;
+        for (int i = j + 1; i < n; ++i) {
+            double t = A[i * n + j];
+            for (int k = 0; k < j; ++k) t -= A[i * n + k] * A[j * n + k] * A[k * n + k];
+            A[i * n + j] = t / d;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        double t = b[i];
+        for (int k = 0; k < i; ++k) t -= A[i * n + k] * y[k];
+        y[i] = t;
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double t = y[i] / A[i * n + i];
+        for (int k = i + 1; k < n; ++k) t -= A[k * n + i] * gains[k];
+        gains[i] = t;
+    }
+    for (int i = 0; i < n; ++i)
+        if (!isfinite(gains[i])) return false;
     return true;
 }
 

@@ -7,11 +7,9 @@
 
 namespace rwh {
 
-// stitch_kernel's shape (rwh_stitch.hip): 256 lanes as 64 x 4, four consecutive pixels per lane, the 12 output bytes in one store.
-// A block's 256 x 4 tile is tested once against the n rectangles; blockIdx and the descriptor indices are wave-uniform, so the
-// test and the descriptor reads of the pixel loop stay on the scalar side.
-constexpr int SEQ_PX = 4;
-
+// stitch_kernel's shape (rwh_stitch.hip): 256 lanes as 64 x 4, four consecutive pixels per lane (SEQ_PX), the 12 output bytes in
+// one store.  A block's 256 x 4 tile is tested once against the n rectangles; blockIdx and the descriptor indices are wave-uniform,
+// so the test and the descriptor reads of the pixel loop stay on the scalar side.
 // RING: the canvas is a whole number of tiles wide (checked before the launch), so every lane has its four pixels and there is no
 // tail path.
 template <bool FEATHER, bool GAIN = false, bool PROJ = false, bool RING = false>
@@ -57,44 +55,7 @@ void seq_put(const void* host, size_t words, uint64_t* dev, hipStream_t s) {
     }
 }
 
-template <bool FEATHER, bool GAIN, bool PROJ = false, bool RING = false>
-static void seq_host_rows(const SeqArgs& a, const double* gains, SeqRays rays = SeqRays{nullptr, nullptr}) {
-    const uint64_t all = seq_all(a.n);
-    for (int cy = a.row_begin; cy < a.row_end; ++cy)
-        for (int cx = 0; cx < a.fw; ++cx) {
-            const uint32_t p = seq_pixel<FEATHER, GAIN, PROJ, RING>(a, all, cx, cy, gains, rays);
-            unsigned char* out = a.dst + ((size_t)cy * a.fw + cx) * 3;
-            out[0] = (unsigned char)p; out[1] = (unsigned char)(p >> 8); out[2] = (unsigned char)(p >> 16);
-        }
-}
-
-// ---- the gain rule's overlap statistics (include/rwh.h) ----
-// The images that cover canvas pixel (cx, cy), bit i = image i (cand: bits of image indices), by the sequence rule's Coverage:
-// seq_sample's own test, its taps unused.  rays: the ray tables, read with PROJ only.
-template <bool PROJ = false, bool RING = false>
-__host__ __device__ __forceinline__ uint64_t seq_cover(const SeqArgs& a, uint64_t cand, int cx, int cy, SeqRays rays = SeqRays{nullptr, nullptr}) {
-    const int fx = a.ox + cx, fy = a.oy + cy;
-    SeqRay ray;
-    if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
-    uint64_t cov = 0;
-    for (uint64_t m = cand; m; m &= m - 1) {
-        const int i = __builtin_ctzll(m);
-        double v[3], g = 0.0;
-        if (seq_sample<false, false, PROJ, RING>(a.desc[i], i == a.anchor, fx, fy, v, g, 1.0, &ray, a.fw)) cov |= 1ull << i;
-    }
-    return cov;
-}
-
-// L_i of the gain rule: the sum of the three bytes paste would write for image i at a canvas pixel that it covers.
-template <bool PROJ = false, bool RING = false>
-__host__ __device__ __forceinline__ uint32_t seq_byte_sum(const SeqArgs& a, int i, int cx, int cy, SeqRays rays = SeqRays{nullptr, nullptr}) {
-    double v[3], g = 0.0;
-    SeqRay ray;
-    if constexpr (PROJ) ray = seq_ray(rays, cx, cy);
-    if (!seq_sample<false, false, PROJ, RING>(a.desc[i], i == a.anchor, a.ox + cx, a.oy + cy, v, g, 1.0, &ray, a.fw)) return 0u;
-    return (uint32_t)(unsigned char)(int)v[0] + (uint32_t)(unsigned char)(int)v[1] + (uint32_t)(unsigned char)(int)v[2];
-}
-
+// ---- the gain rule's overlap statistics (include/rwh.h); the per-sample functions are rwh_sequence.h's ----
 struct StatArgs {
     SeqArgs a;                  // order: 0 .. n-1 (candidate bits are image indices); dst, row_begin, row_end unused
     int stride, nsx, nsy;       // the sample grid: nsx x nsy samples, sample (u, v) is canvas pixel (u * stride, v * stride)
@@ -112,12 +73,6 @@ __host__ __device__ __forceinline__ int seq_slab_words(int n) { return (2 * n * 
 template <bool RING = false>
 __host__ __device__ __forceinline__ uint64_t seq_stat_mask(const StatArgs& s, int u0, int u1, int v0, int v1) {
     return seq_tile_mask<RING>(s.a, u0 * s.stride, (u1 - 1) * s.stride + 1, v0 * s.stride, (v1 - 1) * s.stride + 1);
-}
-
-__device__ __forceinline__ uint32_t seq_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = RWH_WAVE / 2; o; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
 }
 
 // A block takes 256 x 4 samples (64 lanes x 4 consecutive samples, one wave per sample row) and tests their footprint once against
@@ -193,9 +148,6 @@ __global__ __launch_bounds__(256) void seq_stats_sum_kernel(const unsigned long 
     for (int r = 0; r < STAT_SLABS; ++r) total += slabs[(size_t)r * slab_words + t];
     if (t < nn) count[t] = total; else sum[t - nn] = total;
 }
-
-// the descriptor table at the head of the statistics workspace, a whole number of 128-byte lines
-static int64_t seq_stat_table_bytes(int n) { return ((int64_t)n * (int64_t)sizeof(SeqDesc) + 127) & ~(int64_t)127; }
 
 // What both statistics entry points check, and their arguments: rwh_stitch_sequence's checks (with the index order, no canvas
 // buffer and all rows) plus the stride range.
@@ -433,55 +385,15 @@ extern "C" int rwh_host_sequence_overlap_stats_proj(const void* const* images, c
                                rwh::SeqRays{col, row});
 }
 
-// The gains of the gain rule from the two tables: A and b built in the rule's order, the square-root-free Cholesky
-// A = L D L^T on the lower triangle, forward and back substitution.  Host only, float64, no LAPACK.
+// The gains of the gain rule from the two tables: seq_solve_gains (rwh_sequence.h) on them.
 extern "C" int rwh_host_sequence_gains(const uint64_t* count, const uint64_t* sum, int n, double sigma_n, double sigma_g, double* gains) {
     if (!count || !sum || !gains || n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;
     if (!(isfinite(sigma_n) && sigma_n > 0.0 && isfinite(sigma_g) && sigma_g > 0.0)) return RWH_E_INVALID;
     const uint64_t* cnt = count;
     const uint64_t* sm = sum;
     const double alpha = 1.0 / (sigma_n * sigma_n), beta = 1.0 / (sigma_g * sigma_g);
-    static_assert(RWH_SEQ_MAX_IMAGES == 64, "A, b and y live on the stack");
-    double A[64 * 64], b[64], y[64];
-    memset(A, 0, sizeof(A));
-    memset(b, 0, sizeof(b));
     auto N = [&](int i, int j) { return (double)cnt[(size_t)i * n + j]; };
     auto I = [&](int i, int j) { return cnt[(size_t)i * n + j] ? (double)sm[(size_t)i * n + j] / (3.0 * N(i, j)) : 0.0; };
-    for (int i = 0; i < n; ++i) {
-        if (cnt[(size_t)i * n + i] == 0) { A[i * n + i] = 1.0; b[i] = 1.0; continue; }
-        for (int j = 0; j < n; ++j) {
-            A[i * n + i] += beta * N(i, j);
-            b[i] += beta * N(i, j);
-            if (j != i) {
-                A[i * n + i] += 2.0 * alpha * I(i, j) * I(i, j) * N(i, j);
-                A[i * n + j] -= 2.0 * alpha * I(i, j) * I(j, i) * N(i, j);
-            }
-        }
-    }
-    // A = L D L^T, L unit lower (kept below A's diagonal), D on the diagonal: a row that meets nobody (zeros off its diagonal,
-    // b_i == A_ii) comes out as b_i / A_ii = 1.0 exactly.
-    for (int j = 0; j < n; ++j) {
-        double d = A[j * n + j];
-        for (int k = 0; k < j; ++k) d -= A[j * n + k] * A[j * n + k] * A[k * n + k];
-        if (!(d > 0.0) || !isfinite(d)) return RWH_E_INVALID;
-        A[j * n + j] = d;
-        for (int i = j + 1; i < n; ++i) {
-            double t = A[i * n + j];
-            for (int k = 0; k < j; ++k) t -= A[i * n + k] * A[j * n + k] * A[k * n + k];
-            A[i * n + j] = t / d;
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        double t = b[i];
-        for (int k = 0; k < i; ++k) t -= A[i * n + k] * y[k];
-        y[i] = t;
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        double t = y[i] / A[i * n + i];
-        for (int k = i + 1; k < n; ++k) t -= A[k * n + i] * gains[k];
-        gains[i] = t;
-    }
-    for (int i = 0; i < n; ++i)
-        if (!isfinite(gains[i])) return RWH_E_INVALID;
+    if (!rwh::seq_solve_gains(n, alpha, beta, [&](int i) { return cnt[(size_t)i * n + i] != 0; }, N, I, gains)) return RWH_E_INVALID;
     return RWH_OK;
 }

@@ -37,6 +37,7 @@ Documented divergences from the reference:
     the reference, needs OpenCV) are not provided beyond an import-compatible stub.
 """
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -55,6 +56,7 @@ __all__ = [
     "calcHomography", "calcHomographyLinear", "calcH", "nearestNeighbor", "bilinear", "convertfunc",
     "wrapPerspective", "wrapPerspectiveScan", "perspectiveTransform", "transformImage", "transformImageH",
     "BLENDDIR", "addAlpha", "stitchPanorama", "cylindericlMap", "sequence_plan", "stitchSequence", "sequence_gains", "sequence_seams",
+    "sequence_block_gains", "BlockGains",
     "sequence_ray_tables", "sequence_focal", "sequence_graph", "sequence_adjust",
     "sequence_cameras", "sequence_camera_maps", "sequence_adjust_cameras",
 ]
@@ -1525,6 +1527,87 @@ def sequence_gains(images, Hs=None, Gs=None, anchor=0, stride=4, sigma_n=10.0, s
     return _gains_on_device(on_dev, geom.on_device(on_dev[0].device), stride, sigma_n, sigma_g, info)
 
 
+class BlockGains(NamedTuple):
+    """What `sequence_block_gains` returns and `stitchSequence(gains=...)` takes: maps, float64 numpy [N, gh, gw], the gain of each
+    image in each `block` x `block` cell of the canvas; base, float64 [N], the one-gain-per-image part they were solved on top of
+    (what the seam finder's survey is given)."""
+    maps: object
+    block: int
+    base: object
+
+
+def _check_block_options(who, block, stride, sigma_n, sigma_g, smooth):
+    kernels.sequence_block_shift(who, block)
+    _check_gain_options(who, stride, sigma_n, sigma_g)
+    if not (isinstance(smooth, (int, np.integer)) and not isinstance(smooth, bool) and 0 <= smooth <= _lib.RWH_SEQ_MAX_SMOOTH):
+        raise ValueError("%s: smooth %r; an integer of 0 .. %d" % (who, smooth, _lib.RWH_SEQ_MAX_SMOOTH))
+
+
+def _no_wrap_blocks(who, wrap):
+    if wrap is not False:
+        raise NotImplementedError("%s: block gains on a wrap-around canvas are not provided (the block gain rule has no ring form)" % who)
+
+
+def _block_gains_on_device(on_dev, geom, block, stride, sigma_n, sigma_g, smooth, base, info):
+    """One cell-statistics launch, one download of the table, one call of rwh_host_sequence_block_gains -> BlockGains.
+    base: "auto" (`sequence_gains`' defaults on the same upload), None (all ones) or N checked gains."""
+    n = len(on_dev)
+    if isinstance(base, str):
+        base = _gains_on_device(on_dev, geom, 4, 10.0, 0.1, None)
+    elif base is None:
+        base = np.ones(n, dtype=np.float64)
+    tabs = kernels.sequence_cell_tables_on(on_dev, geom, int(block), int(stride)).cpu().numpy().view(np.uint32)
+    status, maps = kernels.host_sequence_block_gains(tabs, geom, n, int(block), base, sigma_n, sigma_g, int(smooth))
+    if status == _lib.RWH_E_INVALID:
+        raise ValueError("sequence_block_gains: a cell's gain system has a non-positive pivot, or a map entry is not finite and > 0")
+    _lib.check(status, "rwh_host_sequence_block_gains")
+    if info is not None:
+        info["tables"], info["slots"] = tabs, int(tabs.shape[-1])
+    return BlockGains(maps, int(block), base)
+
+
+def sequence_block_gains(images, Hs=None, Gs=None, anchor=0, block=32, stride=1, sigma_n=10.0, sigma_g=0.1, smooth=2, base="auto", info=None,
+                         projection=None, focal=None):
+    """One exposure gain MAP per image of a sequence (the block gain rule of include/rwh.h; what OpenCV's stitcher does by default):
+    the canvas is cut into `block` x `block` cells, the gain rule's overlap statistics are reduced per cell on the GPU in one launch
+    (`rwh_sequence_cell_stats`, one workgroup per cell), the table comes down in one copy, and on the host every cell's small gain
+    system is solved on top of `base`, the solutions are smoothed and become the maps (`rwh_host_sequence_block_gains`).  What
+    varies inside an image -- vignetting, a sky brighter on one side -- is compensated, which one gain per image cannot do.
+    -> BlockGains(maps float64 [N, gh, gw], block, base float64 [N]); `stitchSequence(..., gains=...)` applies it, interpolating
+    the maps bilinearly between cell centres.
+
+    images, Hs, Gs, anchor, projection, focal: as `stitchSequence`'s, and refused as there; the wrap-around canvas is not taken.
+    block (32): 16, 32, 64 or 128 -- OpenCV's block size, a convention and not a measured optimum.  stride (1): every stride-th
+    canvas pixel each way is a sample, 1 .. 255; 1 is a convention too (a cell of 32 x 32 has few samples to spare).  sigma_n, sigma_g:
+    as `sequence_gains`'s.  smooth (2): iterations of the 1-2-1 filter over the cells, 0 .. 8; OpenCV's convention.
+    base: "auto" -- `sequence_gains` with its defaults on the same upload; None -- all ones; or N gains, finite and > 0.
+    `info`: optional dict, receives "tables" (uint32 [gh, gw, 2, K, K]) and "slots" (K, the most images that meet one cell).
+    ValueError: another block, stride, sigma or smooth, a base of another length or string, before the GPU is touched."""
+    who = "sequence_block_gains"
+    _, geom = _sequence_geometry(who, images, Hs, Gs, anchor, projection, focal, False)
+    _check_block_options(who, block, stride, sigma_n, sigma_g, smooth)
+    if isinstance(base, str):
+        if base != "auto":
+            raise ValueError("%s: base=%r; 'auto', None or N gains" % (who, base))
+    elif base is not None:
+        base = kernels.sequence_gains_array(base, len(images), who)
+    on_dev = _sequence_upload(images)
+    return _block_gains_on_device(on_dev, geom.on_device(on_dev[0].device), block, stride, sigma_n, sigma_g, smooth, base, info)
+
+
+def _check_block_gains(who, gains, n, size):
+    """A BlockGains given to stitchSequence or sequence_seams, before the GPU is touched: ValueError for another block, maps that do
+    not fit the canvas and block, an entry or a base gain that is not finite and > 0."""
+    kernels.sequence_block_shift(who, gains.block)
+    maps = np.ascontiguousarray(gains.maps, dtype=np.float64)
+    want = (n,) + kernels.sequence_cell_grid(size, gains.block)
+    if maps.shape != want:
+        raise ValueError("%s: gain maps of shape %s; %s for a %d x %d canvas and block %d" % (who, maps.shape, want, size[0], size[1], gains.block))
+    if not (np.isfinite(maps).all() and (maps > 0).all()):
+        raise ValueError("%s: a gain map entry is not finite and > 0" % who)
+    return BlockGains(maps, int(gains.block), kernels.sequence_gains_array(gains.base, n, who))
+
+
 def _check_bands(who, bands):
     kernels.sequence_bands_check(who, bands)
 
@@ -1539,7 +1622,7 @@ def sequence_seams(images, Hs=None, Gs=None, anchor=0, gains=None, margin=8.0, t
     `stitchSequence(..., seams=labels)` composites with them.
 
     images, Hs, Gs, anchor, projection, focal: as `stitchSequence`'s, and refused as there.  gains: None or N exposure gains (the
-    disagreement is taken on the compensated bytes).  margin=8.0 and tau=64 (an integer of 1 .. 766) are conventions, not measured
+    disagreement is taken on the compensated bytes); a BlockGains gives its `base` -- the survey keeps one gain per image.  margin=8.0 and tau=64 (an integer of 1 .. 766) are conventions, not measured
     optima; margin=inf gives the feather winner of multi-band blending.  `info`: optional dict, receives "passes", the number of
     relaxation passes that changed a distance.  The relaxation runs until nothing changes and the host reads a flag between
     passes: the call synchronises torch's current stream.  The wrap-around canvas is not taken.
@@ -1547,7 +1630,9 @@ def sequence_seams(images, Hs=None, Gs=None, anchor=0, gains=None, margin=8.0, t
     n = len(images)
     _, geom = _sequence_geometry("sequence_seams", images, Hs, Gs, anchor, projection, focal, False)
     kernels.sequence_seam_options("sequence_seams", margin, tau)
-    if gains is not None:
+    if isinstance(gains, BlockGains):
+        gains = _check_block_gains("sequence_seams", gains, n, geom.size).base
+    elif gains is not None:
         gains = kernels.sequence_gains_array(gains, n, "sequence_seams")
     tens = any(_is_tensor(img) for img in images)
     on_dev = _sequence_upload(images)
@@ -1594,8 +1679,12 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     an integer of 1 .. 8, ignored by the other blends; 5 is OpenCV's convention, not a measured optimum, and it wants overlaps several
     times 2^(bands+2) pixels wide -- 170-pixel overlaps were visibly too narrow for 5.  gains: None -- the images
     as they are; N exposure gains (the gain rule of include/rwh.h: every sample value v of image i enters as min(v * g_i, 255.0));
-    "auto" -- `sequence_gains` with its defaults on the same images and geometry, the images uploaded once.  `info`: optional dict,
-    receives "gains" (the gains used, float64 [N], or None).  numpy arrays in -> a
+    "auto" -- `sequence_gains` with its defaults on the same images and geometry, the images uploaded once; a BlockGains (the
+    block gain rule: one gain MAP per image, `sequence_block_gains`) -- every sample value enters as min(v * g, 255.0) with g read
+    from image i's map at the pixel, under every blend; "blocks" -- `sequence_block_gains` with its defaults on the same upload.
+    Found seams survey the images with one gain each, the BlockGains' `base`.  Block gains are not provided with `wrap`
+    (NotImplementedError, before the GPU is touched).  `info`: optional dict,
+    receives "gains" (the gains used: float64 [N], the BlockGains, or None).  numpy arrays in -> a
     numpy canvas; any tensor in -> a device tensor and no host copy of pixels.  The caller's images are never written.
     projection: None -- the canvas is the anchor's image plane, which suits a narrow sweep (at 100 degrees off the anchor the plane
     is behind the camera); "cylindrical" or "spherical" -- the canvas is that surface about the anchor's camera with radius `focal`
@@ -1624,6 +1713,8 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     if blending == "multiband":
         _check_bands("stitchSequence", bands)
     seam = _check_seams("stitchSequence", seams, blending, wrap)
+    if isinstance(gains, BlockGains) or (isinstance(gains, str) and gains == "blocks"):
+        _no_wrap_blocks("stitchSequence", wrap)
     blend = _lib.RWH_SEQ_FEATHER if blending == "feather" else _lib.RWH_SEQ_PASTE
     default, geom = _sequence_geometry("stitchSequence", images, Hs, Gs, anchor, projection, focal, wrap)
     if seam is not None and seam[0] == "plane" and tuple(int(v) for v in seam[1].shape) != tuple(int(v) for v in geom.size):
@@ -1632,23 +1723,29 @@ def stitchSequence(images, Hs=None, Gs=None, anchor=0, blending=False, order=Non
     if sorted(order) != list(range(n)):
         raise ValueError("stitchSequence: order %r is not a permutation of 0 .. %d" % (order, n - 1))
     if isinstance(gains, str):
-        if gains != "auto":
-            raise ValueError("stitchSequence: gains=%r; None, N gains or 'auto'" % (gains,))
+        if gains not in ("auto", "blocks"):
+            raise ValueError("stitchSequence: gains=%r; None, N gains, a BlockGains, 'auto' or 'blocks'" % (gains,))
+    elif isinstance(gains, BlockGains):
+        gains = _check_block_gains("stitchSequence", gains, n, geom.size)
     elif gains is not None:
         gains = kernels.sequence_gains_array(gains, n, "stitchSequence")
     tens = any(_is_tensor(img) for img in images)
     on_dev = _sequence_upload(images)
     geom = geom.on_device(on_dev[0].device)
     if isinstance(gains, str):
-        gains = _gains_on_device(on_dev, geom, 4, 10.0, 0.1, None)
+        gains = (_gains_on_device(on_dev, geom, 4, 10.0, 0.1, None) if gains == "auto" else
+                 _block_gains_on_device(on_dev, geom, 32, 1, 10.0, 0.1, 2, "auto", None))
     if info is not None:
         info["gains"] = gains
         if geom.ring:
             info["period"], info["radius"] = int(geom.size[1]), int(geom.size[1]) / (2.0 * np.pi)
+    survey = gains
+    if isinstance(gains, BlockGains):                      # the compositors read the maps, the seam survey keeps one gain per image
+        survey, gains = gains.base, kernels.SeqGainMaps(_xfer.to_device(gains.maps, on_dev[0].device), gains.block)
     labels = None
     if seam is not None and seam[0] == "find":
         found = {}
-        labels = kernels.sequence_seams_on(on_dev, geom, gains=gains, margin=seam[1], tau=seam[2], info=found)
+        labels = kernels.sequence_seams_on(on_dev, geom, gains=survey, margin=seam[1], tau=seam[2], info=found)
         if info is not None:
             info["passes"], info["labels"] = found["passes"], labels if tens else _xfer.to_host(labels)
     elif seam is not None:

@@ -900,6 +900,48 @@ def sequence_gains_array(gains, n, who="stitch_sequence"):
     return g
 
 
+class SeqGainMaps(NamedTuple):
+    """Gain maps as a launcher takes them in place of N gains (the block gain rule of include/rwh.h, "Applying maps"): maps, float64
+    [n, gh, gw] (a GPU tensor, or numpy, which is uploaded) for cells of `block` x `block` canvas pixels."""
+    maps: object
+    block: int
+
+
+def sequence_block_shift(who, block):
+    """s of the block gain rule for `block` = 2^s; ValueError unless block is 16, 32, 64 or 128."""
+    if not (isinstance(block, (int, np.integer)) and not isinstance(block, bool) and block in _lib.RWH_SEQ_BLOCKS):
+        raise ValueError("%s: block %r; one of %s" % (who, block, ", ".join(str(b) for b in _lib.RWH_SEQ_BLOCKS)))
+    return int(block).bit_length() - 1
+
+
+def sequence_cell_grid(size, block):
+    """(gh, gw): the cells of a canvas of `size` = (fh, fw)."""
+    return -(-int(size[0]) // int(block)), -(-int(size[1]) // int(block))
+
+
+def _sequence_no_ring_maps(who, geom):
+    if geom.ring:
+        raise NotImplementedError("%s: a wrap-around canvas; the block gain rule (include/rwh.h) has no ring form" % who)
+
+
+def _sequence_gain_maps(who, gains, n, fh, fw, dev):
+    """A SeqGainMaps as the library takes it -> (the maps on `dev`, held by the caller until its call has returned; shift).
+    ValueError: another block, maps that are not float64 [n, gh, gw] for this canvas; a numpy array is also read: every entry
+    finite and > 0."""
+    shift = sequence_block_shift(who, gains.block)
+    maps = gains.maps
+    want = (n,) + sequence_cell_grid((fh, fw), gains.block)
+    if not isinstance(maps, torch.Tensor):
+        maps = np.ascontiguousarray(maps, dtype=np.float64)
+        if maps.shape == want and not (np.isfinite(maps).all() and (maps > 0).all()):
+            raise ValueError("%s: a gain map entry is not finite and > 0" % who)
+        maps = torch.from_numpy(maps)
+    if maps.dtype != torch.float64 or tuple(maps.shape) != want:
+        raise ValueError("%s: gain maps are %s %s; float64 %s for a %d x %d canvas and block %d"
+                         % (who, maps.dtype, tuple(maps.shape), want, fh, fw, gains.block))
+    return maps.to(dev).contiguous(), shift
+
+
 def sequence_bands_check(who, bands):
     """ValueError unless `bands` of the multi-band rule is an integer of 1 .. 8."""
     if not (isinstance(bands, (int, np.integer)) and not isinstance(bands, bool) and 1 <= bands <= _lib.RWH_SEQ_MAX_BANDS):
@@ -1018,27 +1060,34 @@ def sequence_seam_options(who, margin, tau):
         raise ValueError("%s: tau %r; an integer of 1 .. 766" % (who, tau))
 
 
-# The five launchers, named for their operation with `_on` (a geometry).  Each takes the images (n [h, w, 3] uint8 GPU tensors)
+# The six launchers, named for their operation with `_on` (a geometry).  Each takes the images (n [h, w, 3] uint8 GPU tensors)
 # and a SeqGeometry, finds its entry point by name -- operation plus the geometry's form -- and runs on torch's current stream.
 # They refuse in one order: the device check and the image asserts, the counts, the launcher's own option, the canvas bound, the
 # ray tables, the label plane, the output tensor, a workspace size <= 0, the library's status (RWH_E_INVALID raises ValueError).
 def stitch_sequence_on(images, geom, order, blend, rows=None, out=None, gains=None):
     """The sequence compositor (rwh_stitch_sequence_ex / _proj / _ring): order: a permutation of 0 .. n-1; blend: RWH_SEQ_PASTE /
     RWH_SEQ_FEATHER -> canvas [fh, fw, 3] uint8.  rows=(r0, r1): only those canvas rows, into `out` (the whole canvas tensor) when
-    given.  gains: None, or n gains of the gain rule (every sample value v of image i enters as min(v * gains[i], 255.0))."""
+    given.  gains: None, or n gains of the gain rule (every sample value v of image i enters as min(v * gains[i], 255.0)), or a
+    SeqGainMaps (the block gain rule: the gain is read from image i's map at the pixel; rwh_stitch_sequence_maps / _proj, not on
+    the ring)."""
     lib = _lib.load()
     who = "stitch_sequence"
-    if gains is not None:
+    by_maps = isinstance(gains, SeqGainMaps)
+    if by_maps:
+        _sequence_no_ring_maps(who, geom)
+    elif gains is not None:
         gains = sequence_gains_array(gains, len(images), who)
     n, fh, fw, tables, od = _sequence_marshal(who, images, geom, order)
     rays = _sequence_rays(who, geom, fh, fw)
+    if by_maps:
+        maps, shift = _sequence_gain_maps(who, gains, n, fh, fw, images[0].device)
     out = _sequence_canvas(images, fh, fw, out)
     r0, r1 = (0, fh) if rows is None else (int(rows[0]), int(rows[1]))
     refused = lambda: _sequence_refused(who, geom, "rwh_stitch_sequence", "order, row range")
     ws, ws_args = _sequence_workspace(lib.rwh_stitch_sequence_workspace_bytes(n), out.device, refused)
-    entry = "rwh_stitch_sequence" + (geom.form or "_ex")
+    entry = "rwh_stitch_sequence" + ("_maps" + geom.form if by_maps else geom.form or "_ex")
     status = getattr(lib, entry)(*geom.layout(tables, n, (od.ctypes.data, int(blend)), rays, (_ptr(out), fh, fw),
-                                              (r0, r1) + ws_args + (_addr(gains),)))
+                                              (r0, r1) + ws_args + ((_ptr(maps), shift) if by_maps else (_addr(gains),))))
     _sequence_status(status, entry, refused)
     return out
 
@@ -1065,19 +1114,97 @@ def sequence_overlap_tables_on(images, geom, stride):
     return tabs
 
 
+def sequence_cell_slots(geom, n, block):
+    """K of the block gain rule (rwh_sequence_cell_slots): the most candidates of any cell, from the rectangles alone."""
+    who = "sequence_cell_slots"
+    shift = sequence_block_shift(who, block)
+    rects = np.ascontiguousarray(geom.rects, dtype=np.int32).reshape(-1, 4)
+    k = _lib.load().rwh_sequence_cell_slots(rects.ctypes.data, int(n), int(geom.size[0]), int(geom.size[1]), int(geom.origin[0]),
+                                            int(geom.origin[1]), shift)
+    if k < 1:
+        raise ValueError("%s: the library refused the arguments (include/rwh.h, the block gain rule: 1 .. %d rectangles on the canvas)"
+                         % (who, SEQ_MAX_IMAGES))
+    return int(k)
+
+
+def sequence_cell_candidates(geom, n, block):
+    """The candidates of every cell of the block gain rule, in index order: bool [gh, gw, n] (the images whose rectangles meet the
+    clipped cell)."""
+    gh, gw = sequence_cell_grid(geom.size, block)
+    fh, fw = int(geom.size[0]), int(geom.size[1])
+    r = np.asarray(geom.rects, dtype=np.int64).reshape(n, 4)
+    rx, ry = r[:, 0] - int(geom.origin[0]), r[:, 1] - int(geom.origin[1])
+    x0, y0 = np.arange(gw) * block, np.arange(gh) * block
+    x1, y1 = np.minimum(x0 + block, fw), np.minimum(y0 + block, fh)
+    cols = (rx[None, :] < x1[:, None]) & (rx[None, :] + r[None, :, 2] > x0[:, None])
+    rows = (ry[None, :] < y1[:, None]) & (ry[None, :] + r[None, :, 3] > y0[:, None])
+    return rows[:, None, :] & cols[None, :, :]
+
+
+def sequence_cell_tables_on(images, geom, block, stride):
+    """The cell statistics of the block gain rule (rwh_sequence_cell_stats / _proj): block: 16, 32, 64 or 128; stride: as
+    `sequence_overlap_tables_on`'s -> ONE int32 [gh, gw, 2, K, K] GPU tensor holding the library's uint32 table (count, sum per
+    cell, by candidate rank; K = `sequence_cell_slots`), so that one copy brings it down.  Not on the ring."""
+    lib = _lib.load()
+    who = "sequence_cell_tables"
+    _sequence_no_ring_maps(who, geom)
+
+    def own():
+        sequence_block_shift(who, block)
+        if not (isinstance(stride, (int, np.integer)) and 1 <= stride <= _lib.RWH_SEQ_MAX_STRIDE):
+            raise ValueError("%s: stride %r; 1 .. %d" % (who, stride, _lib.RWH_SEQ_MAX_STRIDE))
+    n, fh, fw, tables, _ = _sequence_marshal(who, images, geom, own=own)
+    shift = sequence_block_shift(who, block)
+    rays = _sequence_rays(who, geom, fh, fw)
+    slots = sequence_cell_slots(geom, n, block)
+    gh, gw = sequence_cell_grid((fh, fw), block)
+    dev = images[0].device
+    assert lib.rwh_sequence_cell_stats_table_bytes(fh, fw, shift, slots) == gh * gw * 2 * slots * slots * 4
+    tabs = torch.empty((gh, gw, 2, slots, slots), dtype=torch.int32, device=dev)
+    refused = lambda: _sequence_refused(who, geom, "rwh_sequence_cell_stats", "block, stride, slots")
+    ws, ws_args = _sequence_workspace(lib.rwh_sequence_cell_stats_workspace_bytes(n), dev, refused)
+    entry = "rwh_sequence_cell_stats" + geom.form
+    status = getattr(lib, entry)(*geom.layout(tables, n, (), rays, (fh, fw), (shift, int(stride), slots, _ptr(tabs)) + ws_args))
+    _sequence_status(status, entry, refused)
+    return tabs
+
+
+def host_sequence_block_gains(tables, geom, n, block, base=None, sigma_n=10.0, sigma_g=0.1, smooth=2):
+    """Cell gains, smoothing and maps of the block gain rule (rwh_host_sequence_block_gains; host only): tables: the uint32
+    [gh, gw, 2, K, K] table of `sequence_cell_tables_on`, brought down; base: None or n gains -> (status, maps float64 [n, gh, gw])."""
+    shift = sequence_block_shift("sequence_block_gains", block)
+    gh, gw = sequence_cell_grid(geom.size, block)
+    tables = np.ascontiguousarray(tables).view(np.uint32)
+    slots = int(tables.shape[-1])
+    assert tables.shape == (gh, gw, 2, slots, slots)
+    rects = np.ascontiguousarray(geom.rects, dtype=np.int32).reshape(-1, 4)
+    base = None if base is None else np.ascontiguousarray(base, dtype=np.float64)
+    assert base is None or base.shape == (n,)
+    maps = np.empty((n, gh, gw), dtype=np.float64)
+    status = _lib.load().rwh_host_sequence_block_gains(tables.ctypes.data, rects.ctypes.data, int(n), int(geom.size[0]), int(geom.size[1]),
+                                                       int(geom.origin[0]), int(geom.origin[1]), shift, slots, _addr(base), float(sigma_n),
+                                                       float(sigma_g), int(smooth), maps.ctypes.data)
+    return status, maps
+
+
 def stitch_sequence_multiband_on(images, geom, bands, gains=None, out=None, labels=None):
     """The multi-band compositor (rwh_stitch_multiband / _proj / _ring; the multi-band rule of include/rwh.h): bands: 1 .. 8 pyramid
-    levels below the top; gains: as `stitch_sequence_on`'s -> canvas [fh, fw, 3] uint8 (`out` when given).  labels: None, or a uint8
+    levels below the top; gains: as `stitch_sequence_on`'s (a SeqGainMaps: rwh_stitch_multiband_maps / _proj) -> canvas [fh, fw, 3] uint8 (`out` when given).  labels: None, or a uint8
     [fh, fw] plane (a GPU tensor or numpy) that takes the Winner's place (rwh_stitch_multiband_labels / _labels_proj; the seam rule,
     "Using labels"): a label that names no covering image leaves the multi-band rule's Winner; not on the ring."""
     who = "stitch_sequence_multiband"
     if labels is not None:
         _sequence_no_ring(who, geom)
     lib = _lib.load()
-    if gains is not None:
+    by_maps = isinstance(gains, SeqGainMaps)
+    if by_maps:
+        _sequence_no_ring_maps(who, geom)
+    elif gains is not None:
         gains = sequence_gains_array(gains, len(images), who)
     n, fh, fw, tables, _ = _sequence_marshal(who, images, geom, own=lambda: sequence_bands_check(who, bands))
     rays = _sequence_rays(who, geom, fh, fw)
+    if by_maps:
+        maps, shift = _sequence_gain_maps(who, gains, n, fh, fw, images[0].device)
     if labels is not None:
         labels = _sequence_labels(who, labels, fh, fw, images[0].device)
     out = _sequence_canvas(images, fh, fw, out)
@@ -1087,8 +1214,12 @@ def stitch_sequence_multiband_on(images, geom, bands, gains=None, out=None, labe
     else:
         need = lib.rwh_stitch_multiband_workspace_bytes(tables[3].ctypes.data, n, fh, fw, int(geom.origin[0]), int(geom.origin[1]), int(bands))
     ws, ws_args = _sequence_workspace(need, out.device, refused)
-    entry = "rwh_stitch_multiband" + ("" if labels is None else "_labels") + geom.form
-    own = (int(bands), _addr(gains)) + (() if labels is None else (_ptr(labels),))
+    if by_maps:
+        entry = "rwh_stitch_multiband_maps" + geom.form
+        own = (int(bands), _ptr(maps), shift, None if labels is None else _ptr(labels))
+    else:
+        entry = "rwh_stitch_multiband" + ("" if labels is None else "_labels") + geom.form
+        own = (int(bands), _addr(gains)) + (() if labels is None else (_ptr(labels),))
     status = getattr(lib, entry)(*geom.layout(tables, n, own, rays, (_ptr(out), fh, fw), ws_args))
     _sequence_status(status, entry, refused)
     return out
@@ -1101,16 +1232,20 @@ def stitch_sequence_labels_on(images, geom, labels, gains=None, out=None):
     who = "stitch_sequence_labels"
     _sequence_no_ring(who, geom)
     lib = _lib.load()
-    if gains is not None:
+    by_maps = isinstance(gains, SeqGainMaps)
+    if gains is not None and not by_maps:
         gains = sequence_gains_array(gains, len(images), who)
     n, fh, fw, tables, _ = _sequence_marshal(who, images, geom)
     rays = _sequence_rays(who, geom, fh, fw)
+    if by_maps:
+        maps, shift = _sequence_gain_maps(who, gains, n, fh, fw, images[0].device)
     labels = _sequence_labels(who, labels, fh, fw, images[0].device)
     out = _sequence_canvas(images, fh, fw, out)
     refused = lambda: _SEAM_REFUSED % who
     ws, ws_args = _sequence_workspace(lib.rwh_stitch_sequence_workspace_bytes(n), out.device, refused)
-    entry = "rwh_stitch_sequence_labels" + geom.form
-    status = getattr(lib, entry)(*geom.layout(tables, n, (_addr(gains), _ptr(labels)), rays, (_ptr(out), fh, fw), ws_args))
+    entry = "rwh_stitch_sequence_labels" + ("_maps" if by_maps else "") + geom.form
+    own = (_ptr(maps), shift, _ptr(labels)) if by_maps else (_addr(gains), _ptr(labels))
+    status = getattr(lib, entry)(*geom.layout(tables, n, own, rays, (_ptr(out), fh, fw), ws_args))
     _sequence_status(status, entry, refused)
     return out
 

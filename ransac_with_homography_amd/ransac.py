@@ -56,7 +56,8 @@ from .features import (DeviceProblems, _host_rows, default_pattern, detect_and_d
 from .homography import (_check_bands, _check_focal, _check_pairs, _check_projection, _check_wrap, _oriented, _pair_rows,  # noqa: F401
                          _sequence_inputs, calcHomography, calcHomographyLinear, cylindericlMap, sequence_adjust,
                          sequence_adjust_cameras, sequence_camera_maps, sequence_cameras, sequence_focal, sequence_gains,
-                         sequence_graph, sequence_period, sequence_plan, sequence_seams, stitchPanorama, stitchSequence)
+                         sequence_block_gains, BlockGains, sequence_graph, sequence_period, sequence_plan, sequence_seams,
+                         stitchPanorama, stitchSequence)
 
 # Which hypotheses need the reference's own solver (`_settle_on_host`, natively `rwh_ransac_run`): the rule and its reasons are
 # in csrc/rwh_settle.h.  RESCORE_MARGIN caps the margin of the 'backward' / 'reproj' rule: an unflagged K1 count moves by <= 2
@@ -785,7 +786,8 @@ def stitch_sequence(images, anchor=0, th=5, d=70, k=1000, ransacMet="fwd", seed=
     (blending="multiband": multi-band blending with `bands` pyramid levels, checked before any GPU work; blending="seams" and
     "multiband+seams": `stitchSequence(blending=False | "multiband", seams=True)`, seam finding by the seam rule of include/rwh.h
     with its defaults, then label paste or labelled multi-band -- not on a canvas that wraps; gains="auto": exposure
-    gains from the overlaps, `sequence_gains` with its defaults).  numpy arrays in -> a numpy canvas, tensors in -> a device
+    gains from the overlaps, `sequence_gains` with its defaults; gains="blocks": one gain map per image, `sequence_block_gains`
+    with its defaults, which `stitch_ring` refuses).  numpy arrays in -> a numpy canvas, tensors in -> a device
     tensor.  `info`: optional dict, receives "Hs" (float64 [N - 1, 3, 3], Hs[i] maps image i+1 into image i), "Gs", "origin"
     ((ox, oy) of the canvas in the anchor's frame), "sizes" (matches per pair), "inliers" (per pair) and "gains" (the gains used,
     float64 [N], or None).  projection, focal: as `stitchSequence`'s (a cylindrical or spherical canvas, for sweeps too wide for the
@@ -870,9 +872,11 @@ def _stitch_sequence(images, anchor, th, d, k, ransacMet, seed, blending, featur
             raise ValueError("stitch_sequence: pairs=%r names a pair twice" % (pairs,))
     graph = adjust or pairs != "adjacent"
     if isinstance(gains, str):
-        if gains != "auto":
-            raise ValueError("stitch_sequence: gains=%r; None, N gains or 'auto'" % (gains,))
-    elif gains is not None:
+        if gains not in ("auto", "blocks"):
+            raise ValueError("stitch_sequence: gains=%r; None, N gains, 'auto' or 'blocks'" % (gains,))
+        if gains == "blocks" and wrap is not False:
+            raise NotImplementedError("stitch_ring: gains='blocks'; the block gain rule (include/rwh.h) has no ring form")
+    elif gains is not None and not isinstance(gains, BlockGains):          # (a BlockGains is checked against the canvas by stitchSequence)
         gains = kernels.sequence_gains_array(gains, n, "stitch_sequence")
     if blending == "multiband":
         _check_bands("stitch_sequence", bands)
