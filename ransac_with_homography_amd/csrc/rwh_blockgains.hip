@@ -1,7 +1,8 @@
 // Block exposure gains for the sequence compositor (include/rwh.h, "The block gain rule"): the gain rule's overlap statistics taken
-// per B x B cell of the canvas, a gain system solved per cell on the host, the solutions smoothed into one gain MAP per image, and
-// the paste / feather compositor reading its gains from those maps.  The per-sample functions, the solver and the pixel function
-// are rwh_sequence.h's: the cells sample an image, and a map-taking compositor composites it, with the one arithmetic of the family.
+// per B x B cell of the canvas, a gain system solved per cell on the host, and the solutions smoothed into one gain MAP per image.
+// The per-sample functions and the solver are rwh_sequence.h's: the cells sample an image with the one arithmetic of the family.
+// The compositors that read the maps are the family's own (rwh_sequence.hip, rwh_multiband.hip, rwh_seams.hip), instantiated on the
+// third state of the gain switch.
 #include <vector>
 #include "rwh_sequence.h"
 
@@ -87,8 +88,10 @@ __global__ __launch_bounds__(256) void seq_cell_stats_kernel(const SeqWith<CellA
     for (int t = threadIdx.x; t < 2 * KK; t += 256) out[t] = acc[t];
 }
 
-// The frame of a set of rectangles alone -- what seq_tile_mask reads -- for the functions that are given no images.
-static bool cell_frame(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, SeqArgs& a) {
+// The frame of a set of rectangles alone (seq_frame) -- what seq_tile_mask reads -- for the functions that are given no images.
+static bool cell_frame(const SeqCall& c, SeqDesc* descs, SeqArgs& a) {
+    const int32_t* rects = c.rects;
+    const int n = c.n, canvas_h = c.canvas_h, canvas_w = c.canvas_w, origin_x = c.origin_x, origin_y = c.origin_y;
     if (!rects || n < 1 || n > RWH_SEQ_MAX_IMAGES || !seq_canvas_ok(canvas_h, canvas_w)) return false;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < n; ++i) {
@@ -121,142 +124,70 @@ static int cell_slots(const SeqArgs& a, int shift) {
 }
 
 // What both statistics entry points check, and their arguments: the overlap statistics' checks plus the block, and K as the
-// rectangles give it.
-static int cell_prepare(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                        int canvas_h, int canvas_w, int origin_x, int origin_y, int shift, int stride, int slots, uint32_t* tables,
-                        SeqDesc* descs, CellArgs& c, bool proj) {
+// rectangles give it.  The cells have no ring form.
+static int cell_prepare(const SeqCall& c, int shift, int stride, int slots, uint32_t* tables, SeqDesc* descs, CellArgs& cell, bool device) {
     if (!tables || ((uintptr_t)tables & 3u) || stride < 1 || stride > 255 || shift < SEQ_SHIFT_MIN || shift > SEQ_SHIFT_MAX) return RWH_E_INVALID;
-    const int st = seq_prepare_indexed(images, hw, mats, rects, n, anchor, tables, canvas_h, canvas_w, origin_x, origin_y, descs, c.a, proj);
+    if (c.form == SEQ_RING) return RWH_E_INVALID;
+    const int st = seq_prepare_indexed(c, tables, descs, cell.a, device);
     if (st != RWH_OK) return st;
-    c.a.dst = nullptr;
-    if (slots != cell_slots(c.a, shift)) return RWH_E_INVALID;
-    c.shift = shift; c.stride = stride; c.slots = slots;
-    c.gw = seq_cell_count(canvas_w, shift); c.gh = seq_cell_count(canvas_h, shift);
-    c.tables = tables;
+    cell.a.dst = nullptr;
+    if (slots != cell_slots(cell.a, shift)) return RWH_E_INVALID;
+    cell.shift = shift; cell.stride = stride; cell.slots = slots;
+    cell.gw = seq_cell_count(c.canvas_w, shift); cell.gh = seq_cell_count(c.canvas_h, shift);
+    cell.tables = tables;
     return RWH_OK;
 }
 
-template <bool PROJ>
-static int cell_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                       int canvas_h, int canvas_w, int origin_x, int origin_y, int shift, int stride, int slots, uint32_t* d_tables,
-                       void* d_workspace, int64_t workspace_bytes, void* stream, SeqRays rays) {
+static int cell_device(const SeqCall& c, int shift, int stride, int slots, uint32_t* d_tables, void* d_workspace, int64_t workspace_bytes,
+                       void* stream) {
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    CellArgs c;
-    const int st = cell_prepare(d_images, hw, mats, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, shift, stride, slots, d_tables, descs, c, PROJ);
+    CellArgs cell;
+    const int st = cell_prepare(c, shift, stride, slots, d_tables, descs, cell, true);
     if (st != RWH_OK) return st;
-    if (!d_workspace || workspace_bytes < seq_stat_table_bytes(n) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
+    if (!d_workspace || workspace_bytes < seq_stat_table_bytes(c.n) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint64_t* table = static_cast<uint64_t*>(d_workspace);
-    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
-    c.a.desc = reinterpret_cast<const SeqDesc*>(table);
-    hipLaunchKernelGGL((seq_cell_stats_kernel<PROJ>), dim3(c.gw, c.gh), dim3(256), (size_t)2 * slots * slots * sizeof(uint32_t), s,
-                       (seq_with<false, PROJ>(c, nullptr, n, rays)));
+    seq_put(descs, (size_t)c.n * SEQ_DESC_WORDS, table, s);
+    cell.a.desc = reinterpret_cast<const SeqDesc*>(table);
+    seq_form_dispatch<false>(c.form, [&](auto form) {
+        constexpr bool PROJ = decltype(form)::proj;
+        hipLaunchKernelGGL((seq_cell_stats_kernel<PROJ>), dim3(cell.gw, cell.gh), dim3(256), (size_t)2 * slots * slots * sizeof(uint32_t), s,
+                           (seq_with<false, PROJ>(cell, nullptr, c.n, c.rays)));
+    });
     return check_launch();
 }
 
-template <bool PROJ>
-static int cell_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                     int canvas_h, int canvas_w, int origin_x, int origin_y, int shift, int stride, int slots, uint32_t* tables,
-                     SeqRays rays) {
+static int cell_host(const SeqCall& c, int shift, int stride, int slots, uint32_t* tables) {
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    CellArgs c;
-    const int st = cell_prepare(images, hw, mats, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, shift, stride, slots, tables, descs, c, PROJ);
+    CellArgs cell;
+    const int st = cell_prepare(c, shift, stride, slots, tables, descs, cell, false);
     if (st != RWH_OK) return st;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
-    const SeqArgs& a = c.a;
+    const SeqArgs& a = cell.a;
     const int K = slots, KK = K * K, B = 1 << shift;
-    memset(tables, 0, (size_t)c.gh * c.gw * 2 * KK * sizeof(uint32_t));
-    for (int gy = 0; gy < c.gh; ++gy)
-        for (int gx = 0; gx < c.gw; ++gx) {
-            const uint64_t cand = cell_mask(a, gx, gy, shift);
-            uint32_t* cnt = tables + ((size_t)gy * c.gw + gx) * (size_t)(2 * KK);
-            uint32_t* sm = cnt + KK;
-            const int x1 = (gx << shift) + B < a.fw ? (gx << shift) + B : a.fw, y1 = (gy << shift) + B < a.fh ? (gy << shift) + B : a.fh;
-            for (int cy = cell_first_sample(gy << shift, stride) * stride; cy < y1; cy += stride)
-                for (int cx = cell_first_sample(gx << shift, stride) * stride; cx < x1; cx += stride) {
-                    const uint64_t cov = seq_cover<PROJ>(a, cand, cx, cy, rays);
-                    for (uint64_t mi = cov; mi; mi &= mi - 1) {
-                        const int i = __builtin_ctzll(mi), ri = __builtin_popcountll(cand & ((1ull << i) - 1));
-                        const uint32_t lsum = seq_byte_sum<PROJ>(a, i, cx, cy, rays);
-                        for (uint64_t mj = cov; mj; mj &= mj - 1) {
-                            const int rj = __builtin_popcountll(cand & ((1ull << __builtin_ctzll(mj)) - 1));
-                            cnt[ri * K + rj] += 1u;
-                            sm[ri * K + rj] += lsum;
+    memset(tables, 0, (size_t)cell.gh * cell.gw * 2 * KK * sizeof(uint32_t));
+    seq_form_dispatch<false>(c.form, [&](auto form) {
+        constexpr bool PROJ = decltype(form)::proj;
+        for (int gy = 0; gy < cell.gh; ++gy)
+            for (int gx = 0; gx < cell.gw; ++gx) {
+                const uint64_t cand = cell_mask(a, gx, gy, shift);
+                uint32_t* cnt = tables + ((size_t)gy * cell.gw + gx) * (size_t)(2 * KK);
+                uint32_t* sm = cnt + KK;
+                const int x1 = (gx << shift) + B < a.fw ? (gx << shift) + B : a.fw, y1 = (gy << shift) + B < a.fh ? (gy << shift) + B : a.fh;
+                for (int cy = cell_first_sample(gy << shift, stride) * stride; cy < y1; cy += stride)
+                    for (int cx = cell_first_sample(gx << shift, stride) * stride; cx < x1; cx += stride) {
+                        const uint64_t cov = seq_cover<PROJ>(a, cand, cx, cy, c.rays);
+                        for (uint64_t mi = cov; mi; mi &= mi - 1) {
+                            const int i = __builtin_ctzll(mi), ri = __builtin_popcountll(cand & ((1ull << i) - 1));
+                            const uint32_t lsum = seq_byte_sum<PROJ>(a, i, cx, cy, c.rays);
+                            for (uint64_t mj = cov; mj; mj &= mj - 1) {
+                                const int rj = __builtin_popcountll(cand & ((1ull << __builtin_ctzll(mj)) - 1));
+                                cnt[ri * K + rj] += 1u;
+                                sm[ri * K + rj] += lsum;
+                            }
                         }
                     }
-                }
-        }
-    return RWH_OK;
-}
-
-// ---- the compositor on gain maps ----
-// seq_kernel (rwh_sequence.hip) with the gain read from the maps.  Its body is restated here rather than shared: called through a
-// common body function, one of seq_kernel's forms came out with another register allocation, and those kernels stay the code they
-// were.  No ring form.
-template <bool FEATHER, bool PROJ>
-__global__ __launch_bounds__(256) void seq_maps_kernel(const SeqWithMaps<SeqArgs, PROJ> l) {
-    const SeqArgs& a = l.a;
-    const int bx0 = blockIdx.x * 64 * SEQ_PX, by0 = a.row_begin + blockIdx.y * 4;
-    const uint64_t cand = seq_tile_mask(a, bx0, bx0 + 64 * SEQ_PX, by0, by0 + 4);
-    const int cx0 = bx0 + (threadIdx.x & 63) * SEQ_PX;
-    const int cy = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
-    if (cx0 >= a.fw || cy >= a.row_end) return;
-    unsigned char* out = a.dst + ((size_t)cy * a.fw + cx0) * 3;
-    uint32_t px[SEQ_PX];
-#pragma unroll
-    for (int j = 0; j < SEQ_PX; ++j)
-        px[j] = cx0 + j < a.fw ? seq_pixel<FEATHER, true, PROJ, false>(a, cand, cx0 + j, cy, seq_gains(l), seq_rays(l)) : 0u;
-    if (cx0 + SEQ_PX <= a.fw) {
-        pk3 w;
-        w.a = px[0] | (px[1] << 24);
-        w.b = (px[1] >> 8) | (px[2] << 16);
-        w.c = (px[2] >> 16) | (px[3] << 8);
-        __builtin_memcpy(out, &w, 12);
-    } else {
-        for (int j = 0; cx0 + j < a.fw; ++j) { out[3 * j] = (unsigned char)px[j]; out[3 * j + 1] = (unsigned char)(px[j] >> 8); out[3 * j + 2] = (unsigned char)(px[j] >> 16); }
-    }
-}
-
-template <bool PROJ>
-static int maps_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                       const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                       int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes, void* stream, const double* d_maps,
-                       int shift, SeqRays rays) {
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    SeqArgs a;
-    const int st = seq_prepare(d_images, hw, mats, rects, n, anchor, order, blend, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                               row_begin, row_end, descs, a, PROJ);
-    if (st != RWH_OK) return st;
-    SeqMaps maps;
-    if (!seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
-    if (!d_workspace || workspace_bytes < rwh_stitch_sequence_workspace_bytes(n) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
-    if (row_begin == row_end) return RWH_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint64_t* table = static_cast<uint64_t*>(d_workspace);
-    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
-    a.desc = reinterpret_cast<const SeqDesc*>(table);
-    const dim3 grid((canvas_w + 64 * SEQ_PX - 1) / (64 * SEQ_PX), (row_end - row_begin + 3) / 4);
-    if (blend == RWH_SEQ_FEATHER) hipLaunchKernelGGL((seq_maps_kernel<true, PROJ>), grid, dim3(256), 0, s, (seq_with_maps<PROJ>(a, maps, rays)));
-    else hipLaunchKernelGGL((seq_maps_kernel<false, PROJ>), grid, dim3(256), 0, s, (seq_with_maps<PROJ>(a, maps, rays)));
-    return check_launch();
-}
-
-template <bool PROJ>
-static int maps_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                     const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                     int row_begin, int row_end, const double* maps_in, int shift, SeqRays rays) {
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    SeqArgs a;
-    const int st = seq_prepare(images, hw, mats, rects, n, anchor, order, blend, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                               row_begin, row_end, descs, a, PROJ);
-    if (st != RWH_OK) return st;
-    SeqMaps maps;
-    if (!seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !seq_maps_ok(maps, n)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
-    if (blend == RWH_SEQ_FEATHER) seq_host_rows<true, true, PROJ, false>(a, maps, rays);
-    else seq_host_rows<false, true, PROJ, false>(a, maps, rays);
+            }
+    });
     return RWH_OK;
 }
 
@@ -266,7 +197,7 @@ extern "C" int rwh_sequence_cell_slots(const int32_t* rects, int n, int canvas_h
     using namespace rwh;
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SeqArgs a;
-    if (shift < SEQ_SHIFT_MIN || shift > SEQ_SHIFT_MAX || !cell_frame(rects, n, canvas_h, canvas_w, origin_x, origin_y, descs, a)) return RWH_E_INVALID;
+    if (shift < SEQ_SHIFT_MIN || shift > SEQ_SHIFT_MAX || !cell_frame(seq_frame(rects, n, canvas_h, canvas_w, origin_x, origin_y), descs, a)) return RWH_E_INVALID;
     return cell_slots(a, shift);
 }
 
@@ -284,29 +215,28 @@ extern "C" int64_t rwh_sequence_cell_stats_table_bytes(int canvas_h, int canvas_
 extern "C" int rwh_sequence_cell_stats(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                        int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int shift, int stride, int slots,
                                        uint32_t* d_tables, void* d_workspace, int64_t workspace_bytes, void* stream) {
-    return rwh::cell_device<false>(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, shift, stride, slots,
-                                   d_tables, d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr});
+    return rwh::cell_device(rwh::seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), shift, stride,
+                            slots, d_tables, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_sequence_cell_stats_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                             const double* d_col, const double* d_row, int canvas_h, int canvas_w, int shift, int stride,
                                             int slots, uint32_t* d_tables, void* d_workspace, int64_t workspace_bytes, void* stream) {
-    return rwh::cell_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, shift, stride, slots,
-                                  d_tables, d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
+    return rwh::cell_device(rwh::seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), shift, stride, slots, d_tables,
+                            d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_host_sequence_cell_stats(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                             int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int shift, int stride,
                                             int slots, uint32_t* tables) {
-    return rwh::cell_host<false>(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, shift, stride, slots, tables,
-                                 rwh::SeqRays{nullptr, nullptr});
+    return rwh::cell_host(rwh::seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), shift, stride, slots,
+                          tables);
 }
 
 extern "C" int rwh_host_sequence_cell_stats_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                  const double* col, const double* row, int canvas_h, int canvas_w, int shift, int stride,
                                                  int slots, uint32_t* tables) {
-    return rwh::cell_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, shift, stride, slots, tables,
-                                rwh::SeqRays{col, row});
+    return rwh::cell_host(rwh::seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), shift, stride, slots, tables);
 }
 
 // Cell gains, smoothing and maps of the block gain rule.  Host only, plain C++: the cell solves are seq_solve_gains, the solver of
@@ -318,7 +248,7 @@ extern "C" int rwh_host_sequence_block_gains(const uint32_t* tables, const int32
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SeqArgs a;
     if (!tables || !maps || shift < SEQ_SHIFT_MIN || shift > SEQ_SHIFT_MAX || smooth < 0 || smooth > 8) return RWH_E_INVALID;
-    if (!cell_frame(rects, n, canvas_h, canvas_w, origin_x, origin_y, descs, a) || slots != cell_slots(a, shift)) return RWH_E_INVALID;
+    if (!cell_frame(seq_frame(rects, n, canvas_h, canvas_w, origin_x, origin_y), descs, a) || slots != cell_slots(a, shift)) return RWH_E_INVALID;
     if (!(isfinite(sigma_n) && sigma_n > 0.0 && isfinite(sigma_g) && sigma_g > 0.0) || (base && !seq_gains_ok(base, n))) return RWH_E_INVALID;
     const double alpha = 1.0 / (sigma_n * sigma_n), beta = 1.0 / (sigma_g * sigma_g);
     const int gw = seq_cell_count(canvas_w, shift), gh = seq_cell_count(canvas_h, shift), K = slots, KK = K * K;
@@ -360,32 +290,3 @@ extern "C" int rwh_host_sequence_block_gains(const uint32_t* tables, const int32
     return RWH_OK;
 }
 
-extern "C" int rwh_stitch_sequence_maps(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
-                                        int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
-                                        int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
-                                        void* stream, const double* d_maps, int shift) {
-    return rwh::maps_device<false>(d_images, hw, inv_g, rects, n, anchor, order, blend, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                                   row_begin, row_end, d_workspace, workspace_bytes, stream, d_maps, shift, rwh::SeqRays{nullptr, nullptr});
-}
-
-extern "C" int rwh_stitch_sequence_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
-                                             const int32_t* order, int blend, const double* d_col, const double* d_row, void* d_canvas,
-                                             int canvas_h, int canvas_w, int row_begin, int row_end, void* d_workspace,
-                                             int64_t workspace_bytes, void* stream, const double* d_maps, int shift) {
-    return rwh::maps_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, d_canvas, canvas_h, canvas_w, 0, 0,
-                                  row_begin, row_end, d_workspace, workspace_bytes, stream, d_maps, shift, rwh::SeqRays{d_col, d_row});
-}
-
-extern "C" int rwh_host_stitch_sequence_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
-                                             int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
-                                             int origin_x, int origin_y, int row_begin, int row_end, const double* maps, int shift) {
-    return rwh::maps_host<false>(images, hw, inv_g, rects, n, anchor, order, blend, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                                 row_begin, row_end, maps, shift, rwh::SeqRays{nullptr, nullptr});
-}
-
-extern "C" int rwh_host_stitch_sequence_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
-                                                  const int32_t* order, int blend, const double* col, const double* row, void* canvas,
-                                                  int canvas_h, int canvas_w, int row_begin, int row_end, const double* maps, int shift) {
-    return rwh::maps_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, canvas, canvas_h, canvas_w, 0, 0,
-                                row_begin, row_end, maps, shift, rwh::SeqRays{col, row});
-}

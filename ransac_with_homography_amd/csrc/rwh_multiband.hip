@@ -249,9 +249,11 @@ __host__ __device__ __forceinline__ uint64_t mb_window_mask(const MbArgs& m, int
 }
 
 // ---- the kernels ----
+// The three head kernels take their launch record as L -- SeqWith<.., GAIN, PROJ>, or SeqWithMaps<.., PROJ> on the gain maps of the
+// block gain rule -- so each is one body for every state of the gain switch.
 // 256 lanes as 64 x 4, one pixel of the padded canvas each; the tile is tested once against the n rectangles (block-uniform).
-template <bool GAIN, bool PROJ = false, bool RING = false>
-__global__ __launch_bounds__(256) void mb_winner_kernel(const SeqWith<MbArgs, GAIN, PROJ> l) {
+template <bool GAIN, bool PROJ, bool RING, class L>
+__global__ __launch_bounds__(256) void mb_winner_kernel(const L l) {
     const MbArgs& m = l.a;
     const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
     const uint64_t cand = seq_tile_mask<RING>(m.a, bx0, bx0 + 64, by0, by0 + 4);
@@ -263,8 +265,9 @@ __global__ __launch_bounds__(256) void mb_winner_kernel(const SeqWith<MbArgs, GA
 
 // mb_winner_kernel under a label plane (the seam rule, "Using labels"): the pixel's label names the winner where that image covers
 // the pixel, the multi-band rule's own Winner stands everywhere else.  A kernel of its own: the unlabelled pass stays the code it was.
-template <bool GAIN, bool PROJ = false>
-__global__ __launch_bounds__(256) void mb_label_winner_kernel(const SeqWith<MbLabelArgs, GAIN, PROJ> l) {
+// L is a record on MbLabelArgs.  No ring form.
+template <bool GAIN, bool PROJ, class L>
+__global__ __launch_bounds__(256) void mb_label_winner_kernel(const L l) {
     const MbArgs& m = l.a.m;
     const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
     const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
@@ -277,8 +280,8 @@ __global__ __launch_bounds__(256) void mb_label_winner_kernel(const SeqWith<MbLa
 
 // blockIdx.z is the image; a block takes 64 x 4 pixels of its level-0 window (blocks beyond the window leave at once).
 // RING: the window's columns are taken modulo the period (PW).
-template <bool GAIN, bool PROJ = false, bool RING = false>
-__global__ __launch_bounds__(256) void mb_level0_kernel(const SeqWith<MbArgs, GAIN, PROJ> l) {
+template <bool GAIN, bool PROJ, bool RING, class L>
+__global__ __launch_bounds__(256) void mb_level0_kernel(const L l) {
     const MbArgs& m = l.a;
     const int i = blockIdx.z;
     const MbWin w = m.win[(size_t)i * (m.K + 1)];
@@ -286,42 +289,6 @@ __global__ __launch_bounds__(256) void mb_level0_kernel(const SeqWith<MbArgs, GA
     if (lx >= w.w || ly >= w.h) return;
     const int x = RING ? mb_mod(w.x0 + lx, m.PW) : w.x0 + lx, y = w.y0 + ly;
     m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<GAIN, PROJ, RING>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l), seq_rays(l));
-}
-
-// The three head kernels on the gain maps of the block gain rule (include/rwh.h): the bodies above with the gain read from the
-// maps.  Kernels of their own: the forms above keep their argument types, their names and their code.  No ring form.
-template <bool PROJ>
-__global__ __launch_bounds__(256) void mb_maps_winner_kernel(const SeqWithMaps<MbArgs, PROJ> l) {
-    const MbArgs& m = l.a;
-    const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
-    const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
-    const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
-    if (x >= m.PW || y >= m.PH) return;
-    const bool on = x < m.a.fw && y < m.a.fh;
-    m.pw[(int64_t)y * m.PW + x] = on ? mb_winner_pixel<true, PROJ, false>(m.a, cand, x, y, seq_gains(l), seq_rays(l)) : MB_NONE << 24;
-}
-
-template <bool PROJ>
-__global__ __launch_bounds__(256) void mb_maps_label_winner_kernel(const SeqWithMaps<MbLabelArgs, PROJ> l) {
-    const MbArgs& m = l.a.m;
-    const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
-    const uint64_t cand = seq_tile_mask(m.a, bx0, bx0 + 64, by0, by0 + 4);
-    const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
-    if (x >= m.PW || y >= m.PH) return;
-    uint32_t out = MB_NONE << 24;
-    if (x < m.a.fw && y < m.a.fh) out = seq_label_winner_pixel<true, PROJ>(m.a, cand, x, y, l.a.labels[(int64_t)y * m.a.fw + x], seq_gains(l), seq_rays(l));
-    m.pw[(int64_t)y * m.PW + x] = out;
-}
-
-template <bool PROJ>
-__global__ __launch_bounds__(256) void mb_maps_level0_kernel(const SeqWithMaps<MbArgs, PROJ> l) {
-    const MbArgs& m = l.a;
-    const int i = blockIdx.z;
-    const MbWin w = m.win[(size_t)i * (m.K + 1)];
-    const int lx = blockIdx.x * 64 + (threadIdx.x & 63), ly = blockIdx.y * 4 + seq_wave_row<PROJ>(threadIdx.x >> 6);
-    if (lx >= w.w || ly >= w.h) return;
-    const int x = w.x0 + lx, y = w.y0 + ly;
-    m.g[w.off + (int64_t)ly * w.w + lx] = mb_level0_pixel<true, PROJ, false>(m.a, i, m.pw[(int64_t)y * m.PW + x], x, y, seq_gains(l), seq_rays(l));
 }
 
 // The reduce from level l to l + 1 of image blockIdx.z.  A block makes MB_TW x MB_TH outputs from a (2 MB_TW + 3) x (2 MB_TH + 3)
@@ -420,9 +387,11 @@ static void mb_axis(int a, int b, int P, int K, int* lo, int* hi, bool ring = fa
 static int64_t mb_align(int64_t v) { return (v + 127) & ~(int64_t)127; }
 
 // What the size function and both entry points check of the geometry, and the plan.
-// ring: the ring rule -- canvas_w is the period (PW = canvas_w), a rectangle may pass the canvas's edge.
-static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y, int bands, MbPlan& p,
-                   bool ring = false) {
+// SEQ_RING: the ring rule -- canvas_w is the period (PW = canvas_w), a rectangle may pass the canvas's edge.
+static int mb_plan(const SeqCall& c, int bands, MbPlan& p) {
+    const int32_t* rects = c.rects;
+    const int n = c.n, canvas_h = c.canvas_h, canvas_w = c.canvas_w, origin_x = c.origin_x, origin_y = c.origin_y;
+    const bool ring = c.form == SEQ_RING;
     if (!rects || n < 1 || n > RWH_SEQ_MAX_IMAGES || bands < 1 || bands > RWH_SEQ_MAX_BANDS) return RWH_E_INVALID;
     if (!seq_canvas_ok(canvas_h, canvas_w) || (ring && !seq_period_ok(canvas_w))) return RWH_E_INVALID;
     const int K = bands, mask = (1 << K) - 1;
@@ -457,14 +426,16 @@ static int mb_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int 
     return RWH_OK;
 }
 
-// Everything both entry points check, the descriptors and the plan.
-static int mb_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor, int bands,
-                      const double* gains, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, MbArgs& m,
-                      MbPlan& p, bool proj = false, bool ring = false) {
-    int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m.a, proj, ring);
+// Everything both entry points check, the descriptors and the plan.  labelled: the call is one of the seam rule's, which has a
+// label plane and no ring form; the calls on maps may have a plane.
+static int mb_prepare(const SeqCall& c, int bands, SeqGain& gain, const unsigned char* labels, bool labelled, void* canvas, SeqDesc* descs,
+                      MbArgs& m, MbPlan& p, bool device) {
+    if (labelled && !labels) return RWH_E_INVALID;
+    if (labels && c.form == SEQ_RING) return RWH_E_INVALID;        // labels on the ring: no such form (include/rwh.h)
+    int st = seq_prepare_indexed(c, canvas, descs, m.a, device);
     if (st != RWH_OK) return st;
-    if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
-    st = mb_plan(rects, n, canvas_h, canvas_w, origin_x, origin_y, bands, p, ring);
+    if (!seq_gain_ok(gain, c, !device)) return RWH_E_INVALID;
+    st = mb_plan(c, bands, p);
     if (st != RWH_OK) return st;
     m.K = p.K; m.PW = p.PW; m.PH = p.PH;
     return RWH_OK;
@@ -480,29 +451,23 @@ static void mb_bind(MbArgs& m, const MbPlan& p, char* base) {
     for (int l = 1; l < MB_LEVELS; ++l) m.r[l] = l <= p.K ? reinterpret_cast<MbPx*>(base + p.r_at[l]) : nullptr;
 }
 
-template <bool GAIN, bool PROJ, bool RING>
-static void mb_launch_head(const MbArgs& m, const MbPlan& p, const double* gains, SeqRays rays, hipStream_t s, const unsigned char* labels) {
-    const SeqWith<MbArgs, GAIN, PROJ> l = seq_with<GAIN, PROJ>(m, gains, m.a.n, rays);
-    if constexpr (!RING) {
-        if (labels) hipLaunchKernelGGL((mb_label_winner_kernel<GAIN, PROJ>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s,
-                                       seq_with<GAIN, PROJ>(MbLabelArgs{m, labels}, gains, m.a.n, rays));
-        else hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ, RING>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
-    } else {
-        hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ, RING>), dim3((p.PW + 63) / 64, (p.PH + 3) / 4), dim3(256), 0, s, l);
-    }
-    hipLaunchKernelGGL((mb_level0_kernel<GAIN, PROJ, RING>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
-}
-
-template <bool PROJ>
-static void mb_launch_head_maps(const MbArgs& m, const MbPlan& p, const SeqMaps& maps, SeqRays rays, hipStream_t s, const unsigned char* labels) {
+// The winner pass (labelled where the call has a label plane; never on the ring: mb_prepare) and level 0.  gains: the gain switch's
+// value as seq_gain_dispatch hands it out.
+template <bool GAIN, bool PROJ, bool RING, class G>
+static void mb_launch_head(const MbArgs& m, const MbPlan& p, G gains, SeqRays rays, hipStream_t s, const unsigned char* labels) {
+    auto l = seq_with<GAIN, PROJ>(m, gains, m.a.n, rays);
     const dim3 grid((p.PW + 63) / 64, (p.PH + 3) / 4);
-    if (labels) hipLaunchKernelGGL((mb_maps_label_winner_kernel<PROJ>), grid, dim3(256), 0, s, seq_with_maps<PROJ>(MbLabelArgs{m, labels}, maps, rays));
-    else hipLaunchKernelGGL((mb_maps_winner_kernel<PROJ>), grid, dim3(256), 0, s, seq_with_maps<PROJ>(m, maps, rays));
-    hipLaunchKernelGGL((mb_maps_level0_kernel<PROJ>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s,
-                       seq_with_maps<PROJ>(m, maps, rays));
+    if constexpr (!RING) {
+        if (labels) {
+            auto ll = seq_with<GAIN, PROJ>(MbLabelArgs{m, labels}, gains, m.a.n, rays);
+            hipLaunchKernelGGL((mb_label_winner_kernel<GAIN, PROJ, decltype(ll)>), grid, dim3(256), 0, s, ll);
+        }
+    }
+    if (RING || !labels) hipLaunchKernelGGL((mb_winner_kernel<GAIN, PROJ, RING, decltype(l)>), grid, dim3(256), 0, s, l);
+    hipLaunchKernelGGL((mb_level0_kernel<GAIN, PROJ, RING, decltype(l)>), dim3((p.maxw[0] + 63) / 64, (p.maxh[0] + 3) / 4, m.a.n), dim3(256), 0, s, l);
 }
 
-template <bool GAIN, bool PROJ, bool RING, class G = const double*>
+template <bool GAIN, bool PROJ, bool RING, class G>
 static void mb_host_run(const MbArgs& m, const MbPlan& p, G gains, SeqRays rays, const unsigned char* labels) {
     const int n = m.a.n, K = p.K;
     const uint64_t all = seq_all(n);
@@ -512,10 +477,8 @@ static void mb_host_run(const MbArgs& m, const MbPlan& p, G gains, SeqRays rays,
             if (x < m.a.fw && y < m.a.fh) {
                 if constexpr (!RING) {
                     if (labels) out = seq_label_winner_pixel<GAIN, PROJ>(m.a, all, x, y, labels[(int64_t)y * m.a.fw + x], gains, rays);
-                    else out = mb_winner_pixel<GAIN, PROJ, RING>(m.a, all, x, y, gains, rays);
-                } else {
-                    out = mb_winner_pixel<GAIN, PROJ, RING>(m.a, all, x, y, gains, rays);
                 }
+                if (RING || !labels) out = mb_winner_pixel<GAIN, PROJ, RING>(m.a, all, x, y, gains, rays);
             }
             m.pw[(int64_t)y * p.PW + x] = out;
         }
@@ -543,95 +506,112 @@ static void mb_host_run(const MbArgs& m, const MbPlan& p, G gains, SeqRays rays,
             }
 }
 
-}  // namespace rwh
-
-extern "C" int64_t rwh_stitch_multiband_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                                                        int bands) {
-    rwh::MbPlan p;
-    const int st = rwh::mb_plan(rects, n, canvas_h, canvas_w, origin_x, origin_y, bands, p);
-    return st == RWH_OK ? p.bytes : (int64_t)st;
-}
-
-// The device call behind rwh_stitch_multiband (PROJ false: rays unused) and rwh_stitch_multiband_proj (PROJ true: mats holds the
-// M_i, no anchor, origin (0, 0)).  The reduce and collapse passes work on canvas planes and are the same for both.
-template <bool PROJ, bool RING = false>
-static int mb_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
-                     int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
-                     int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays,
-                     const unsigned char* d_labels = nullptr, bool labelled = false, const rwh::SeqMaps* maps = nullptr) {
-    using namespace rwh;
+// The device call behind every rwh_stitch_multiband* entry point.  The head passes are instantiated on the form and the gain switch;
+// the reduce and collapse passes work on canvas planes and know only the ring.
+static int mb_device(const SeqCall& c, int bands, SeqGain gain, const unsigned char* d_labels, bool labelled, void* d_canvas,
+                     void* d_workspace, int64_t workspace_bytes, void* stream) {
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     MbArgs m;
     MbPlan p;
-    if (labelled && !d_labels) return RWH_E_INVALID;
-    const int st = mb_prepare(d_images, hw, mats, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ, RING);
+    const int n = c.n;
+    const int st = mb_prepare(c, bands, gain, d_labels, labelled, d_canvas, descs, m, p, true);
     if (st != RWH_OK) return st;
     if (!d_workspace || workspace_bytes < p.bytes || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(d_workspace);
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
     seq_put(p.win, (size_t)n * (p.K + 1) * (sizeof(MbWin) / 8), reinterpret_cast<uint64_t*>(base + p.win_at), s);
     mb_bind(m, p, base);
-    if (maps) { if constexpr (!RING) mb_launch_head_maps<PROJ>(m, p, *maps, rays, s, d_labels); }
-    else if (gains) mb_launch_head<true, PROJ, RING>(m, p, gains, rays, s, d_labels); else mb_launch_head<false, PROJ, RING>(m, p, nullptr, rays, s, d_labels);
-    for (int l = 0; l < p.K; ++l)
-        hipLaunchKernelGGL(mb_down_kernel<RING>, dim3((p.maxw[l + 1] + MB_TW - 1) / MB_TW, (p.maxh[l + 1] + MB_TH - 1) / MB_TH, n), dim3(256), 0, s, m, l);
-    for (int l = p.K; l >= 0; --l)
-        hipLaunchKernelGGL(mb_collapse_kernel<RING>, dim3(((p.PW >> l) + 63) / 64, ((p.PH >> l) + 3) / 4), dim3(256), 0, s, m, l);
+    seq_form_dispatch(c.form, [&](auto form) {
+        constexpr bool PROJ = decltype(form)::proj, RING = decltype(form)::ring;
+        seq_gain_dispatch<!RING>(gain, [&](auto on, auto value) { mb_launch_head<decltype(on)::value, PROJ, RING>(m, p, value, c.rays, s, d_labels); });
+        for (int l = 0; l < p.K; ++l)
+            hipLaunchKernelGGL(mb_down_kernel<RING>, dim3((p.maxw[l + 1] + MB_TW - 1) / MB_TW, (p.maxh[l + 1] + MB_TH - 1) / MB_TH, n), dim3(256), 0, s, m, l);
+        for (int l = p.K; l >= 0; --l)
+            hipLaunchKernelGGL(mb_collapse_kernel<RING>, dim3(((p.PW >> l) + 63) / 64, ((p.PH >> l) + 3) / 4), dim3(256), 0, s, m, l);
+    });
     return check_launch();
 }
 
+static int mb_host(const SeqCall& c, int bands, SeqGain gain, const unsigned char* labels, bool labelled, void* canvas) {
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    MbArgs m;
+    MbPlan p;
+    const int st = mb_prepare(c, bands, gain, labels, labelled, canvas, descs, m, p, false);
+    if (st != RWH_OK) return st;
+    char* base = static_cast<char*>(malloc((size_t)p.bytes));
+    if (!base) return RWH_E_LAUNCH;
+    memcpy(base + p.desc_at, descs, (size_t)c.n * sizeof(SeqDesc));
+    memcpy(base + p.win_at, p.win, (size_t)c.n * (p.K + 1) * sizeof(MbWin));
+    mb_bind(m, p, base);
+    seq_form_dispatch(c.form, [&](auto form) {
+        constexpr bool PROJ = decltype(form)::proj, RING = decltype(form)::ring;
+        seq_gain_dispatch<!RING>(gain, [&](auto on, auto value) { mb_host_run<decltype(on)::value, PROJ, RING>(m, p, value, c.rays, labels); });
+    });
+    free(base);
+    return RWH_OK;
+}
+
+}  // namespace rwh
+
+using rwh::seq_curved;
+using rwh::seq_gain_maps;
+using rwh::seq_gain_n;
+using rwh::seq_plane;
+
+extern "C" int64_t rwh_stitch_multiband_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y,
+                                                        int bands) {
+    rwh::MbPlan p;
+    const int st = rwh::mb_plan(rwh::seq_frame(rects, n, canvas_h, canvas_w, origin_x, origin_y), bands, p);
+    return st == RWH_OK ? p.bytes : (int64_t)st;
+}
+
+extern "C" int64_t rwh_stitch_multiband_ring_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int bands) {
+    rwh::MbPlan p;
+    const int st = rwh::mb_plan(rwh::seq_frame(rects, n, canvas_h, canvas_w, 0, 0, true), bands, p);
+    return st == RWH_OK ? p.bytes : (int64_t)st;
+}
+
+// Every entry point below: the geometry record of its form, then the driver.
 extern "C" int rwh_stitch_multiband(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                     int anchor, int bands, const double* gains, void* d_canvas, int canvas_h, int canvas_w,
                                     int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream) {
-    return mb_device<false>(d_images, hw, inv_g, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                            d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr});
+    return rwh::mb_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), bands, seq_gain_n(gains),
+                          nullptr, false, d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_stitch_multiband_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                          int bands, const double* gains, const double* d_col, const double* d_row, void* d_canvas,
                                          int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes, void* stream) {
-    return mb_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, d_canvas, canvas_h, canvas_w, 0, 0,
-                           d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
+    return rwh::mb_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), bands, seq_gain_n(gains), nullptr, false,
+                          d_canvas, d_workspace, workspace_bytes, stream);
 }
 
-template <bool PROJ, bool RING = false>
-static int mb_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
-                   int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
-                   int origin_x, int origin_y, rwh::SeqRays rays, const unsigned char* labels = nullptr, bool labelled = false,
-                   const rwh::SeqMaps* maps = nullptr) {
-    using namespace rwh;
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    MbArgs m;
-    MbPlan p;
-    if (labelled && !labels) return RWH_E_INVALID;
-    const int st = mb_prepare(images, hw, mats, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m, p, PROJ, RING);
-    if (st != RWH_OK) return st;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
-    char* base = static_cast<char*>(malloc((size_t)p.bytes));
-    if (!base) return RWH_E_LAUNCH;
-    memcpy(base + p.desc_at, descs, (size_t)n * sizeof(SeqDesc));
-    memcpy(base + p.win_at, p.win, (size_t)n * (p.K + 1) * sizeof(MbWin));
-    mb_bind(m, p, base);
-    if (maps) { if constexpr (!RING) mb_host_run<true, PROJ, false>(m, p, *maps, rays, labels); }
-    else if (gains) mb_host_run<true, PROJ, RING>(m, p, gains, rays, labels); else mb_host_run<false, PROJ, RING>(m, p, nullptr, rays, labels);
-    free(base);
-    return RWH_OK;
+extern "C" int rwh_stitch_multiband_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                         int bands, const double* gains, const double* d_col, const double* d_row, void* d_canvas,
+                                         int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes, void* stream) {
+    return rwh::mb_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w, true), bands, seq_gain_n(gains), nullptr,
+                          false, d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_host_stitch_multiband(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                          int anchor, int bands, const double* gains, void* canvas, int canvas_h, int canvas_w,
                                          int origin_x, int origin_y) {
-    return mb_host<false>(images, hw, inv_g, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                          rwh::SeqRays{nullptr, nullptr});
+    return rwh::mb_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), bands, seq_gain_n(gains),
+                        nullptr, false, canvas);
 }
 
 extern "C" int rwh_host_stitch_multiband_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                               int bands, const double* gains, const double* col, const double* row, void* canvas,
                                               int canvas_h, int canvas_w) {
-    return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
-                         rwh::SeqRays{col, row});
+    return rwh::mb_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), bands, seq_gain_n(gains), nullptr, false, canvas);
+}
+
+extern "C" int rwh_host_stitch_multiband_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                              int bands, const double* gains, const double* col, const double* row, void* canvas,
+                                              int canvas_h, int canvas_w) {
+    return rwh::mb_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w, true), bands, seq_gain_n(gains), nullptr, false,
+                        canvas);
 }
 
 // The multi-band rule with the seam rule's Winner (include/rwh.h, "Using labels"): the calls above with a label plane.
@@ -639,30 +619,29 @@ extern "C" int rwh_stitch_multiband_labels(const void* const* d_images, const in
                                            int anchor, int bands, const double* gains, const unsigned char* d_labels, void* d_canvas,
                                            int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
                                            int64_t workspace_bytes, void* stream) {
-    return mb_device<false>(d_images, hw, inv_g, rects, n, anchor, bands, gains, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                            d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr}, d_labels, true);
+    return rwh::mb_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), bands, seq_gain_n(gains),
+                          d_labels, true, d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_stitch_multiband_labels_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                 int bands, const double* gains, const unsigned char* d_labels, const double* d_col,
                                                 const double* d_row, void* d_canvas, int canvas_h, int canvas_w, void* d_workspace,
                                                 int64_t workspace_bytes, void* stream) {
-    return mb_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, d_canvas, canvas_h, canvas_w, 0, 0,
-                           d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row}, d_labels, true);
+    return rwh::mb_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), bands, seq_gain_n(gains), d_labels, true,
+                          d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_host_stitch_multiband_labels(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                                 int anchor, int bands, const double* gains, const unsigned char* labels, void* canvas,
                                                 int canvas_h, int canvas_w, int origin_x, int origin_y) {
-    return mb_host<false>(images, hw, inv_g, rects, n, anchor, bands, gains, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                          rwh::SeqRays{nullptr, nullptr}, labels, true);
+    return rwh::mb_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), bands, seq_gain_n(gains),
+                        labels, true, canvas);
 }
 
 extern "C" int rwh_host_stitch_multiband_labels_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                      int bands, const double* gains, const unsigned char* labels, const double* col,
                                                      const double* row, void* canvas, int canvas_h, int canvas_w) {
-    return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
-                         rwh::SeqRays{col, row}, labels, true);
+    return rwh::mb_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), bands, seq_gain_n(gains), labels, true, canvas);
 }
 
 // The multi-band rule on the gain maps of the block gain rule: d_maps / maps and shift where the calls above take gains; labels may
@@ -671,56 +650,28 @@ extern "C" int rwh_stitch_multiband_maps(const void* const* d_images, const int3
                                          int anchor, int bands, const double* d_maps, int shift, const unsigned char* d_labels,
                                          void* d_canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
                                          int64_t workspace_bytes, void* stream) {
-    rwh::SeqMaps maps;
-    if (!rwh::seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
-    return mb_device<false>(d_images, hw, inv_g, rects, n, anchor, bands, nullptr, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                            d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr}, d_labels, false, &maps);
+    return rwh::mb_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), bands,
+                          seq_gain_maps(d_maps, shift), d_labels, false, d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_stitch_multiband_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                               int bands, const double* d_maps, int shift, const unsigned char* d_labels,
                                               const double* d_col, const double* d_row, void* d_canvas, int canvas_h, int canvas_w,
                                               void* d_workspace, int64_t workspace_bytes, void* stream) {
-    rwh::SeqMaps maps;
-    if (!rwh::seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
-    return mb_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, nullptr, d_canvas, canvas_h, canvas_w, 0, 0,
-                           d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row}, d_labels, false, &maps);
+    return rwh::mb_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), bands, seq_gain_maps(d_maps, shift),
+                          d_labels, false, d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_host_stitch_multiband_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                               int anchor, int bands, const double* maps_in, int shift, const unsigned char* labels,
                                               void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y) {
-    rwh::SeqMaps maps;
-    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || !rwh::seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !rwh::seq_maps_ok(maps, n)) return RWH_E_INVALID;
-    return mb_host<false>(images, hw, inv_g, rects, n, anchor, bands, nullptr, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                          rwh::SeqRays{nullptr, nullptr}, labels, false, &maps);
+    return rwh::mb_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), bands,
+                        seq_gain_maps(maps_in, shift), labels, false, canvas);
 }
 
 extern "C" int rwh_host_stitch_multiband_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                    int bands, const double* maps_in, int shift, const unsigned char* labels,
                                                    const double* col, const double* row, void* canvas, int canvas_h, int canvas_w) {
-    rwh::SeqMaps maps;
-    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || !rwh::seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !rwh::seq_maps_ok(maps, n)) return RWH_E_INVALID;
-    return mb_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, nullptr, canvas, canvas_h, canvas_w, 0, 0,
-                         rwh::SeqRays{col, row}, labels, false, &maps);
-}
-
-extern "C" int64_t rwh_stitch_multiband_ring_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int bands) {
-    rwh::MbPlan p;
-    const int st = rwh::mb_plan(rects, n, canvas_h, canvas_w, 0, 0, bands, p, true);
-    return st == RWH_OK ? p.bytes : (int64_t)st;
-}
-
-extern "C" int rwh_stitch_multiband_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
-                                         int bands, const double* gains, const double* d_col, const double* d_row, void* d_canvas,
-                                         int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes, void* stream) {
-    return mb_device<true, true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, d_canvas, canvas_h, canvas_w, 0, 0,
-                                 d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
-}
-
-extern "C" int rwh_host_stitch_multiband_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
-                                              int bands, const double* gains, const double* col, const double* row, void* canvas,
-                                              int canvas_h, int canvas_w) {
-    return mb_host<true, true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, bands, gains, canvas, canvas_h, canvas_w, 0, 0,
-                               rwh::SeqRays{col, row});
+    return rwh::mb_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), bands, seq_gain_maps(maps_in, shift), labels,
+                        false, canvas);
 }

@@ -225,26 +225,15 @@ __host__ __device__ __forceinline__ void sm_paste_store(const SeqArgs& a, int x,
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[k] = (unsigned char)(px >> (8 * k));
 }
-template <bool GAIN, bool PROJ>
-__global__ __launch_bounds__(256) void sm_paste_kernel(const SeqWith<SmPasteArgs, GAIN, PROJ> l) {
+// L: the launch record on SmPasteArgs, SeqWith or (on the gain maps of the block gain rule) SeqWithMaps.
+template <bool GAIN, bool PROJ, class L>
+__global__ __launch_bounds__(256) void sm_paste_kernel(const L l) {
     const SeqArgs& a = l.a.a;
     const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
     const uint64_t cand = seq_tile_mask(a, bx0, bx0 + 64, by0, by0 + 4);
     const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
     if (x >= a.fw || y >= a.fh) return;
     const uint32_t px = seq_label_winner_pixel<GAIN, PROJ>(a, cand, x, y, l.a.labels[(int64_t)y * a.fw + x], seq_gains(l), seq_rays(l));
-    sm_paste_store(a, x, y, px & 0xffffffu);
-}
-
-// sm_paste_kernel on the gain maps of the block gain rule (include/rwh.h): a kernel of its own, the forms above stay the code they were.
-template <bool PROJ>
-__global__ __launch_bounds__(256) void sm_maps_paste_kernel(const SeqWithMaps<SmPasteArgs, PROJ> l) {
-    const SeqArgs& a = l.a.a;
-    const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4;
-    const uint64_t cand = seq_tile_mask(a, bx0, bx0 + 64, by0, by0 + 4);
-    const int x = bx0 + (threadIdx.x & 63), y = by0 + seq_wave_row<PROJ>(threadIdx.x >> 6);
-    if (x >= a.fw || y >= a.fh) return;
-    const uint32_t px = seq_label_winner_pixel<true, PROJ>(a, cand, x, y, l.a.labels[(int64_t)y * a.fw + x], seq_gains(l), seq_rays(l));
     sm_paste_store(a, x, y, px & 0xffffffu);
 }
 
@@ -259,7 +248,9 @@ static int64_t sm_align(int64_t v) { return (v + 127) & ~(int64_t)127; }
 
 // What the size function and both entry points check of the geometry, and the plan.  tau: the main calls' (the size function
 // passes 1): wt * ht * tau <= 2^32 - 3 for every image, so that no distance reaches SM_UNREACHED and no sum wraps.
-static int sm_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y, int tau, SmPlan& p) {
+static int sm_plan(const SeqCall& c, int tau, SmPlan& p) {
+    const int32_t* rects = c.rects;
+    const int n = c.n, canvas_h = c.canvas_h, canvas_w = c.canvas_w, origin_x = c.origin_x, origin_y = c.origin_y;
     if (!rects || n < 1 || n > RWH_SEQ_MAX_IMAGES || !seq_canvas_ok(canvas_h, canvas_w)) return RWH_E_INVALID;
     p.maxw = p.maxh = p.maxtx = p.maxty = 0;
     int64_t px = 0, tiles = 0;
@@ -294,15 +285,15 @@ static int sm_plan(const int32_t* rects, int n, int canvas_h, int canvas_w, int 
     return RWH_OK;
 }
 
-// Everything both entry points check, the descriptors and the plan.
-static int sm_prepare(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                      const double* gains, double margin, int tau, void* labels, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                      SeqDesc* descs, SmArgs& m, SmPlan& p, bool proj) {
-    int st = seq_prepare_indexed(images, hw, mats, rects, n, anchor, labels, canvas_h, canvas_w, origin_x, origin_y, descs, m.a, proj);
+// Everything both entry points check, the descriptors and the plan.  The seam rule has no ring form.
+static int sm_prepare(const SeqCall& c, const double* gains, double margin, int tau, void* labels, SeqDesc* descs, SmArgs& m, SmPlan& p,
+                      bool device) {
+    if (c.form == SEQ_RING) return RWH_E_INVALID;
+    int st = seq_prepare_indexed(c, labels, descs, m.a, device);
     if (st != RWH_OK) return st;
-    if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
+    if (gains && !seq_gains_ok(gains, c.n)) return RWH_E_INVALID;
     if (!(margin >= 0.0) || tau < 1 || tau > 766) return RWH_E_INVALID;          // (a NaN margin is not >= 0)
-    st = sm_plan(rects, n, canvas_h, canvas_w, origin_x, origin_y, tau, p);
+    st = sm_plan(c, tau, p);
     if (st != RWH_OK) return st;
     m.margin = margin; m.tau = tau; m.tiles = p.tiles;
     return RWH_OK;
@@ -316,12 +307,6 @@ static void sm_bind(SmArgs& m, const SmPlan& p, char* base) {
     m.sv = reinterpret_cast<uint32_t*>(base + p.sv_at);
     m.dist = reinterpret_cast<uint32_t*>(base + p.dist_at);
     m.dirty = reinterpret_cast<unsigned char*>(base + p.dirty_at);
-}
-
-template <bool GAIN, bool PROJ>
-static void sm_launch_survey(const SmArgs& m, const double* gains, SeqRays rays, hipStream_t s) {
-    hipLaunchKernelGGL((sm_survey_kernel<GAIN, PROJ>), dim3((m.a.fw + 63) / 64, (m.a.fh + 3) / 4), dim3(256), 0, s,
-                       seq_with<GAIN, PROJ>(m, gains, m.a.n, rays));
 }
 
 // The host twin's distances of one image: Dijkstra with a binary heap over the image's window -- on purpose not the device's
@@ -366,30 +351,17 @@ static void sm_host_run(const SmArgs& m, const double* gains, SeqRays rays) {
         for (int x = 0; x < m.a.fw; ++x) m.a.dst[(int64_t)y * m.a.fw + x] = sm_label_pixel(m, x, y);
 }
 
-}  // namespace rwh
-
-extern "C" int64_t rwh_sequence_seams_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y) {
-    rwh::SmPlan p;
-    const int st = rwh::sm_plan(rects, n, canvas_h, canvas_w, origin_x, origin_y, 1, p);
-    return st == RWH_OK ? p.bytes : (int64_t)st;
-}
-
-// The device call behind rwh_sequence_seams (PROJ false) and rwh_sequence_seams_proj (PROJ true: mats holds the M_i, no anchor,
-// origin (0, 0)).  The host loop reads the flag after every SM_BATCH passes and so synchronises the stream.
-template <bool PROJ>
-static int sm_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                     const double* gains, double margin, int tau, unsigned char* d_labels, int canvas_h, int canvas_w,
-                     int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays,
-                     int32_t* passes) {
-    using namespace rwh;
+// The device call behind rwh_sequence_seams and rwh_sequence_seams_proj.  The seam rule's gain switch has two states (no maps).
+// The host loop reads the flag after every SM_BATCH passes and so synchronises the stream.
+static int sm_device(const SeqCall& c, const double* gains, double margin, int tau, unsigned char* d_labels, void* d_workspace,
+                     int64_t workspace_bytes, void* stream, int32_t* passes) {
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SmArgs m;
     SmPlan p;
-    const int st = sm_prepare(d_images, hw, mats, rects, n, anchor, gains, margin, tau, d_labels, canvas_h, canvas_w, origin_x, origin_y,
-                              descs, m, p, PROJ);
+    const int n = c.n;
+    const int st = sm_prepare(c, gains, margin, tau, d_labels, descs, m, p, true);
     if (st != RWH_OK) return st;
     if (!d_workspace || workspace_bytes < p.bytes || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* base = static_cast<char*>(d_workspace);
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
@@ -397,7 +369,13 @@ static int sm_device(const void* const* d_images, const int32_t* hw, const doubl
     sm_bind(m, p, base);
     if (hipMemsetAsync(m.flag, 0, 8, s) != hipSuccess) return RWH_E_LAUNCH;
     if (hipMemsetAsync(m.dirty, 1, (size_t)p.tiles, s) != hipSuccess) return RWH_E_LAUNCH;      // pass 1 reads array 0: every tile live
-    if (gains) sm_launch_survey<true, PROJ>(m, gains, rays, s); else sm_launch_survey<false, PROJ>(m, nullptr, rays, s);
+    seq_form_dispatch<false>(c.form, [&](auto form) {
+        seq_gain_dispatch<false>(seq_gain_n(gains), [&](auto on, const double* value) {
+            constexpr bool GAIN = decltype(on)::value, PROJ = decltype(form)::proj;
+            hipLaunchKernelGGL((sm_survey_kernel<GAIN, PROJ>), dim3((m.a.fw + 63) / 64, (m.a.fh + 3) / 4), dim3(256), 0, s,
+                               seq_with<GAIN, PROJ>(m, value, n, c.rays));
+        });
+    });
     hipLaunchKernelGGL(sm_init_kernel, dim3((p.maxw + 63) / 64, (p.maxh + 3) / 4, n), dim3(256), 0, s, m);
     uint32_t last = 0;
     int launched = 0;
@@ -408,46 +386,28 @@ static int sm_device(const void* const* d_images, const int32_t* hw, const doubl
         if (hipStreamSynchronize(s) != hipSuccess) return RWH_E_LAUNCH;
     } while ((int64_t)last >= (int64_t)launched);                   // the last pass launched still changed something
     if (passes) *passes = (int32_t)last;
-    hipLaunchKernelGGL(sm_label_kernel, dim3((canvas_w + 63) / 64, (canvas_h + 3) / 4), dim3(256), 0, s, m);
+    hipLaunchKernelGGL(sm_label_kernel, dim3((c.canvas_w + 63) / 64, (c.canvas_h + 3) / 4), dim3(256), 0, s, m);
     return check_launch();
 }
 
-extern "C" int rwh_sequence_seams(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
-                                  int anchor, const double* gains, double margin, int tau, unsigned char* d_labels, int canvas_h,
-                                  int canvas_w, int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream,
-                                  int32_t* passes) {
-    return sm_device<false>(d_images, hw, inv_g, rects, n, anchor, gains, margin, tau, d_labels, canvas_h, canvas_w, origin_x, origin_y,
-                            d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr}, passes);
-}
-
-extern "C" int rwh_sequence_seams_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
-                                       const double* gains, double margin, int tau, const double* d_col, const double* d_row,
-                                       unsigned char* d_labels, int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes,
-                                       void* stream, int32_t* passes) {
-    return sm_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, gains, margin, tau, d_labels, canvas_h, canvas_w, 0, 0,
-                           d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row}, passes);
-}
-
-template <bool PROJ>
-static int sm_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                   const double* gains, double margin, int tau, unsigned char* labels, int canvas_h, int canvas_w, int origin_x,
-                   int origin_y, rwh::SeqRays rays) {
-    using namespace rwh;
+static int sm_host(const SeqCall& c, const double* gains, double margin, int tau, unsigned char* labels) {
     SeqDesc descs[RWH_SEQ_MAX_IMAGES];
     SmArgs m;
     SmPlan p;
-    const int st = sm_prepare(images, hw, mats, rects, n, anchor, gains, margin, tau, labels, canvas_h, canvas_w, origin_x, origin_y,
-                              descs, m, p, PROJ);
+    const int st = sm_prepare(c, gains, margin, tau, labels, descs, m, p, false);
     if (st != RWH_OK) return st;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
     char* base = static_cast<char*>(malloc((size_t)p.bytes));
     if (!base) return RWH_E_LAUNCH;
-    memcpy(base + p.desc_at, descs, (size_t)n * sizeof(SeqDesc));
-    memcpy(base + p.win_at, p.win, (size_t)n * sizeof(SmWin));
+    memcpy(base + p.desc_at, descs, (size_t)c.n * sizeof(SeqDesc));
+    memcpy(base + p.win_at, p.win, (size_t)c.n * sizeof(SmWin));
     sm_bind(m, p, base);
     int out = RWH_OK;
     try {
-        if (gains) sm_host_run<true, PROJ>(m, gains, rays); else sm_host_run<false, PROJ>(m, nullptr, rays);
+        seq_form_dispatch<false>(c.form, [&](auto form) {
+            seq_gain_dispatch<false>(seq_gain_n(gains), [&](auto on, const double* value) {
+                sm_host_run<decltype(on)::value, decltype(form)::proj>(m, value, c.rays);
+            });
+        });
     } catch (const std::bad_alloc&) {
         out = RWH_E_LAUNCH;
     }
@@ -455,98 +415,125 @@ static int sm_host(const void* const* images, const int32_t* hw, const double* m
     return out;
 }
 
+// ---- label paste ----
+// What both label-paste entry points check, and their arguments.  Label paste has no ring form.
+static int sm_paste_prepare(const SeqCall& c, SeqGain& gain, const unsigned char* labels, void* canvas, SeqDesc* descs, SeqArgs& a, bool device) {
+    if (!labels || c.form == SEQ_RING) return RWH_E_INVALID;
+    const int st = seq_prepare_indexed(c, canvas, descs, a, device);
+    if (st != RWH_OK) return st;
+    return seq_gain_ok(gain, c, !device) ? RWH_OK : RWH_E_INVALID;
+}
+
+static int sm_paste_device(const SeqCall& c, SeqGain gain, const unsigned char* d_labels, void* d_canvas, void* d_workspace,
+                           int64_t workspace_bytes, void* stream) {
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    SmPasteArgs m;
+    const int st = sm_paste_prepare(c, gain, d_labels, d_canvas, descs, m.a, true);
+    if (st != RWH_OK) return st;
+    if (!d_workspace || workspace_bytes < (int64_t)c.n * (int64_t)sizeof(SeqDesc) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    seq_put(descs, (size_t)c.n * SEQ_DESC_WORDS, static_cast<uint64_t*>(d_workspace), s);
+    m.a.desc = static_cast<const SeqDesc*>(d_workspace);
+    m.labels = d_labels;
+    const dim3 grid((c.canvas_w + 63) / 64, (c.canvas_h + 3) / 4);
+    seq_form_dispatch<false>(c.form, [&](auto form) {
+        seq_gain_dispatch(gain, [&](auto on, auto value) {
+            constexpr bool GAIN = decltype(on)::value, PROJ = decltype(form)::proj;
+            auto l = seq_with<GAIN, PROJ>(m, value, c.n, c.rays);
+            hipLaunchKernelGGL((sm_paste_kernel<GAIN, PROJ, decltype(l)>), grid, dim3(256), 0, s, l);
+        });
+    });
+    return check_launch();
+}
+
+static int sm_paste_host(const SeqCall& c, SeqGain gain, const unsigned char* labels, void* canvas) {
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    SeqArgs a;
+    const int st = sm_paste_prepare(c, gain, labels, canvas, descs, a, false);
+    if (st != RWH_OK) return st;
+    const uint64_t all = seq_all(c.n);
+    seq_form_dispatch<false>(c.form, [&](auto form) {
+        seq_gain_dispatch(gain, [&](auto on, auto value) {
+            for (int y = 0; y < c.canvas_h; ++y)
+                for (int x = 0; x < c.canvas_w; ++x) {
+                    const uint32_t lab = labels[(int64_t)y * c.canvas_w + x];
+                    const uint32_t px = seq_label_winner_pixel<decltype(on)::value, decltype(form)::proj>(a, all, x, y, lab, value, c.rays);
+                    sm_paste_store(a, x, y, px & 0xffffffu);
+                }
+        });
+    });
+    return RWH_OK;
+}
+
+}  // namespace rwh
+
+using rwh::seq_curved;
+using rwh::seq_gain_maps;
+using rwh::seq_gain_n;
+using rwh::seq_plane;
+
+extern "C" int64_t rwh_sequence_seams_workspace_bytes(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y) {
+    rwh::SmPlan p;
+    const int st = rwh::sm_plan(rwh::seq_frame(rects, n, canvas_h, canvas_w, origin_x, origin_y), 1, p);
+    return st == RWH_OK ? p.bytes : (int64_t)st;
+}
+
+// Every entry point below: the geometry record of its form, then the driver.
+extern "C" int rwh_sequence_seams(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                  int anchor, const double* gains, double margin, int tau, unsigned char* d_labels, int canvas_h,
+                                  int canvas_w, int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream,
+                                  int32_t* passes) {
+    return rwh::sm_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), gains, margin, tau,
+                          d_labels, d_workspace, workspace_bytes, stream, passes);
+}
+
+extern "C" int rwh_sequence_seams_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                       const double* gains, double margin, int tau, const double* d_col, const double* d_row,
+                                       unsigned char* d_labels, int canvas_h, int canvas_w, void* d_workspace, int64_t workspace_bytes,
+                                       void* stream, int32_t* passes) {
+    return rwh::sm_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), gains, margin, tau, d_labels,
+                          d_workspace, workspace_bytes, stream, passes);
+}
+
 extern "C" int rwh_host_sequence_seams(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                        int anchor, const double* gains, double margin, int tau, unsigned char* labels, int canvas_h,
                                        int canvas_w, int origin_x, int origin_y) {
-    return sm_host<false>(images, hw, inv_g, rects, n, anchor, gains, margin, tau, labels, canvas_h, canvas_w, origin_x, origin_y,
-                          rwh::SeqRays{nullptr, nullptr});
+    return rwh::sm_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), gains, margin, tau, labels);
 }
 
 extern "C" int rwh_host_sequence_seams_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                             const double* gains, double margin, int tau, const double* col, const double* row,
                                             unsigned char* labels, int canvas_h, int canvas_w) {
-    return sm_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, gains, margin, tau, labels, canvas_h, canvas_w, 0, 0,
-                         rwh::SeqRays{col, row});
-}
-
-// ---- label paste ----
-template <bool PROJ>
-static int sm_paste_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                           const double* gains, const unsigned char* d_labels, void* d_canvas, int canvas_h, int canvas_w,
-                           int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays,
-                           const rwh::SeqMaps* maps = nullptr) {
-    using namespace rwh;
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    SmPasteArgs m;
-    if (!d_labels) return RWH_E_INVALID;
-    const int st = seq_prepare_indexed(d_images, hw, mats, rects, n, anchor, d_canvas, canvas_h, canvas_w, origin_x, origin_y, descs, m.a, PROJ);
-    if (st != RWH_OK) return st;
-    if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
-    if (!d_workspace || workspace_bytes < (int64_t)n * (int64_t)sizeof(SeqDesc) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, static_cast<uint64_t*>(d_workspace), s);
-    m.a.desc = static_cast<const SeqDesc*>(d_workspace);
-    m.labels = d_labels;
-    const dim3 grid((canvas_w + 63) / 64, (canvas_h + 3) / 4);
-    if (maps) hipLaunchKernelGGL((sm_maps_paste_kernel<PROJ>), grid, dim3(256), 0, s, seq_with_maps<PROJ>(m, *maps, rays));
-    else if (gains) hipLaunchKernelGGL((sm_paste_kernel<true, PROJ>), grid, dim3(256), 0, s, seq_with<true, PROJ>(m, gains, n, rays));
-    else hipLaunchKernelGGL((sm_paste_kernel<false, PROJ>), grid, dim3(256), 0, s, seq_with<false, PROJ>(m, nullptr, n, rays));
-    return check_launch();
-}
-
-template <bool PROJ>
-static int sm_paste_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                         const double* gains, const unsigned char* labels, void* canvas, int canvas_h, int canvas_w, int origin_x,
-                         int origin_y, rwh::SeqRays rays, const rwh::SeqMaps* maps = nullptr) {
-    using namespace rwh;
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    SeqArgs a;
-    if (!labels) return RWH_E_INVALID;
-    const int st = seq_prepare_indexed(images, hw, mats, rects, n, anchor, canvas, canvas_h, canvas_w, origin_x, origin_y, descs, a, PROJ);
-    if (st != RWH_OK) return st;
-    if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
-    const uint64_t all = seq_all(n);
-    for (int y = 0; y < canvas_h; ++y)
-        for (int x = 0; x < canvas_w; ++x) {
-            const uint32_t lab = labels[(int64_t)y * canvas_w + x];
-            const uint32_t px = maps ? seq_label_winner_pixel<true, PROJ>(a, all, x, y, lab, *maps, rays)
-                                : gains ? seq_label_winner_pixel<true, PROJ>(a, all, x, y, lab, gains, rays)
-                                      : seq_label_winner_pixel<false, PROJ>(a, all, x, y, lab, nullptr, rays);
-            sm_paste_store(a, x, y, px & 0xffffffu);
-        }
-    return RWH_OK;
+    return rwh::sm_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), gains, margin, tau, labels);
 }
 
 extern "C" int rwh_stitch_sequence_labels(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                           int anchor, const double* gains, const unsigned char* d_labels, void* d_canvas, int canvas_h,
                                           int canvas_w, int origin_x, int origin_y, void* d_workspace, int64_t workspace_bytes,
                                           void* stream) {
-    return sm_paste_device<false>(d_images, hw, inv_g, rects, n, anchor, gains, d_labels, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                                  d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr});
+    return rwh::sm_paste_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), seq_gain_n(gains),
+                                d_labels, d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_stitch_sequence_labels_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                const double* gains, const unsigned char* d_labels, const double* d_col,
                                                const double* d_row, void* d_canvas, int canvas_h, int canvas_w, void* d_workspace,
                                                int64_t workspace_bytes, void* stream) {
-    return sm_paste_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, gains, d_labels, d_canvas, canvas_h, canvas_w, 0, 0,
-                                 d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
+    return rwh::sm_paste_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), seq_gain_n(gains), d_labels,
+                                d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_host_stitch_sequence_labels(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects,
                                                int n, int anchor, const double* gains, const unsigned char* labels, void* canvas,
                                                int canvas_h, int canvas_w, int origin_x, int origin_y) {
-    return sm_paste_host<false>(images, hw, inv_g, rects, n, anchor, gains, labels, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                                rwh::SeqRays{nullptr, nullptr});
+    return rwh::sm_paste_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), seq_gain_n(gains),
+                              labels, canvas);
 }
 
 extern "C" int rwh_host_stitch_sequence_labels_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects,
                                                     int n, const double* gains, const unsigned char* labels, const double* col,
                                                     const double* row, void* canvas, int canvas_h, int canvas_w) {
-    return sm_paste_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, gains, labels, canvas, canvas_h, canvas_w, 0, 0,
-                               rwh::SeqRays{col, row});
+    return rwh::sm_paste_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), seq_gain_n(gains), labels, canvas);
 }
 
 // Label paste on the gain maps of the block gain rule: d_maps / maps and shift where the calls above take gains.  The host twins
@@ -555,36 +542,27 @@ extern "C" int rwh_stitch_sequence_labels_maps(const void* const* d_images, cons
                                                int anchor, const double* d_maps, int shift, const unsigned char* d_labels, void* d_canvas,
                                                int canvas_h, int canvas_w, int origin_x, int origin_y, void* d_workspace,
                                                int64_t workspace_bytes, void* stream) {
-    rwh::SeqMaps maps;
-    if (!rwh::seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
-    return sm_paste_device<false>(d_images, hw, inv_g, rects, n, anchor, nullptr, d_labels, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                                  d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr}, &maps);
+    return rwh::sm_paste_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y),
+                                seq_gain_maps(d_maps, shift), d_labels, d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_stitch_sequence_labels_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                     const double* d_maps, int shift, const unsigned char* d_labels, const double* d_col,
                                                     const double* d_row, void* d_canvas, int canvas_h, int canvas_w, void* d_workspace,
                                                     int64_t workspace_bytes, void* stream) {
-    rwh::SeqMaps maps;
-    if (!rwh::seq_maps_of(d_maps, shift, canvas_h, canvas_w, maps)) return RWH_E_INVALID;
-    return sm_paste_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, nullptr, d_labels, d_canvas, canvas_h, canvas_w, 0, 0,
-                                 d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row}, &maps);
+    return rwh::sm_paste_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), seq_gain_maps(d_maps, shift),
+                                d_labels, d_canvas, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_host_stitch_sequence_labels_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects,
                                                     int n, int anchor, const double* maps_in, int shift, const unsigned char* labels,
                                                     void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y) {
-    rwh::SeqMaps maps;
-    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || !rwh::seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !rwh::seq_maps_ok(maps, n)) return RWH_E_INVALID;
-    return sm_paste_host<false>(images, hw, inv_g, rects, n, anchor, nullptr, labels, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                                rwh::SeqRays{nullptr, nullptr}, &maps);
+    return rwh::sm_paste_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y),
+                              seq_gain_maps(maps_in, shift), labels, canvas);
 }
 
 extern "C" int rwh_host_stitch_sequence_labels_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects,
                                                          int n, const double* maps_in, int shift, const unsigned char* labels,
                                                          const double* col, const double* row, void* canvas, int canvas_h, int canvas_w) {
-    rwh::SeqMaps maps;
-    if (n < 1 || n > RWH_SEQ_MAX_IMAGES || !rwh::seq_maps_of(maps_in, shift, canvas_h, canvas_w, maps) || !rwh::seq_maps_ok(maps, n)) return RWH_E_INVALID;
-    return sm_paste_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, nullptr, labels, canvas, canvas_h, canvas_w, 0, 0,
-                               rwh::SeqRays{col, row}, &maps);
+    return rwh::sm_paste_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), seq_gain_maps(maps_in, shift), labels, canvas);
 }

@@ -1,6 +1,8 @@
 // The sequence rule's shared pieces (include/rwh.h, "The sequence rule"): the image descriptor, the sampling recipe, the pixel
-// function and the argument checks.  rwh_sequence.hip (paste, feather, overlap statistics) and rwh_multiband.hip (the multi-band
-// rule) both include this, so every compositor samples an image with one arithmetic, on the device and in the host twins.
+// function and the argument checks.  rwh_sequence.hip (paste, feather, overlap statistics), rwh_multiband.hip (the multi-band
+// rule), rwh_seams.hip (the seam rule) and rwh_blockgains.hip (the block gain rule) include this, so every compositor samples an
+// image with one arithmetic, on the device and in the host twins.  The host side of a call is three records: its geometry
+// (SeqCall), its gain switch (SeqGain) and the launch record made of them (SeqWith / SeqWithMaps).
 #ifndef RWH_SEQUENCE_H
 #define RWH_SEQUENCE_H
 #include <math.h>
@@ -46,8 +48,8 @@ template <class A, bool GAIN, bool PROJ> __host__ __device__ __forceinline__ con
 template <class A, bool GAIN, bool PROJ> __host__ __device__ __forceinline__ SeqRays seq_rays(const SeqWith<A, GAIN, PROJ>& l) {
     if constexpr (PROJ) return l.rays; else return SeqRays{nullptr, nullptr};
 }
-template <bool GAIN, bool PROJ = false, class A> static SeqWith<A, GAIN, PROJ> seq_with(const A& a, const double* gains, int n,
-                                                                                        SeqRays rays = SeqRays{nullptr, nullptr}) {
+template <bool GAIN, bool PROJ = false, class A>
+static SeqWith<A, GAIN, PROJ> seq_with(const A& a, const double* gains, int n, SeqRays rays = SeqRays{nullptr, nullptr}) {
     SeqWith<A, GAIN, PROJ> l;
     l.a = a;
     if constexpr (GAIN) {
@@ -60,7 +62,9 @@ template <bool GAIN, bool PROJ = false, class A> static SeqWith<A, GAIN, PROJ> s
 
 // The third state of the gain switch (include/rwh.h, the block gain rule): gain MAPS instead of N gains.  m: float64 [n][gh][gw] (a
 // device pointer in a launch, host memory in the host twins), cells of 2^shift canvas pixels.  The pointer and three ints travel
-// where gains[64] travels; the forms above keep their types, so their kernels keep their names and their code.
+// where gains[64] travels, in a record of their own, so the arguments of the other two states lie where they lay.  A head kernel
+// takes its record as a template parameter L and reads it through seq_gains(l) and seq_rays(l): one body per role, instantiated
+// on SeqWith or SeqWithMaps.
 struct SeqMaps { const double* m; int gw, gh, shift; };
 template <class A, bool PROJ = false> struct SeqWithMaps { A a; SeqMaps maps; };
 template <class A> struct SeqWithMaps<A, true> { A a; SeqMaps maps; SeqRays rays; };
@@ -68,7 +72,9 @@ template <class A, bool PROJ> __host__ __device__ __forceinline__ SeqMaps seq_ga
 template <class A, bool PROJ> __host__ __device__ __forceinline__ SeqRays seq_rays(const SeqWithMaps<A, PROJ>& l) {
     if constexpr (PROJ) return l.rays; else return SeqRays{nullptr, nullptr};
 }
-template <bool PROJ, class A> static SeqWithMaps<A, PROJ> seq_with_maps(const A& a, const SeqMaps& maps, SeqRays rays = SeqRays{nullptr, nullptr}) {
+template <bool GAIN, bool PROJ = false, class A>
+static SeqWithMaps<A, PROJ> seq_with(const A& a, const SeqMaps& maps, int, SeqRays rays = SeqRays{nullptr, nullptr}) {
+    static_assert(GAIN, "maps are gains");
     SeqWithMaps<A, PROJ> l;
     l.a = a;
     l.maps = maps;
@@ -321,15 +327,54 @@ static bool seq_rays_ok(const double* col, const double* row, bool device) {
     return col && row && !((uintptr_t)col & mask) && !((uintptr_t)row & mask);
 }
 
+// The geometry of one call, as the Python layer's SeqGeometry holds it: the images with their matrices and rectangles, the canvas
+// and the form.  Every driver of the family takes one, and every entry point makes it with seq_plane or seq_curved.
+//   SEQ_PLANE: mats holds the inv(G_i), the anchor enters unwarped, no rays.
+//   SEQ_CURVED (the projection rule): mats holds the M_i, anchor is SEQ_NO_ANCHOR and the origin (0, 0).
+//   SEQ_RING (the ring rule, on the projection rule): canvas_w is the period, a multiple of SEQ_RING_TILE; a rectangle starts on
+//   the canvas, is at most one period wide and may pass the canvas's edge.
+enum SeqForm { SEQ_PLANE, SEQ_CURVED, SEQ_RING };
+struct SeqCall {
+    const void* const* images; const int32_t* hw; const double* mats; const int32_t* rects;
+    int n, anchor, canvas_h, canvas_w, origin_x, origin_y;
+    SeqRays rays;
+    SeqForm form;
+};
+static SeqCall seq_plane(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
+                         int canvas_h, int canvas_w, int origin_x, int origin_y) {
+    return SeqCall{images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, SeqRays{nullptr, nullptr}, SEQ_PLANE};
+}
+static SeqCall seq_curved(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n, const double* col,
+                          const double* row, int canvas_h, int canvas_w, bool ring = false) {
+    return SeqCall{images, hw, m, rects, n, SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, SeqRays{col, row}, ring ? SEQ_RING : SEQ_CURVED};
+}
+// The rectangles alone, for the functions that are given no images (the size functions, the cells of the block gain rule).
+static SeqCall seq_frame(const int32_t* rects, int n, int canvas_h, int canvas_w, int origin_x, int origin_y, bool ring = false) {
+    SeqCall c = seq_plane(nullptr, nullptr, nullptr, rects, n, 0, canvas_h, canvas_w, origin_x, origin_y);
+    if (ring) c.form = SEQ_RING;
+    return c;
+}
+
+// f(form), form a SeqFormOf: where PROJ and RING have to be compile-time.  RINGS false: an operation that has no ring form (its
+// prepare refuses SEQ_RING), so none is instantiated.
+template <bool PROJ, bool RING> struct SeqFormOf { static constexpr bool proj = PROJ, ring = RING; };
+template <bool RINGS = true, class F> static void seq_form_dispatch(SeqForm form, const F& f) {
+    if (form == SEQ_PLANE) f(SeqFormOf<false, false>{});
+    else if (form == SEQ_CURVED) f(SeqFormOf<true, false>{});
+    else if constexpr (RINGS) f(SeqFormOf<true, true>{});
+}
+
 // Everything both entry points check, and the descriptors / arguments they share.  descs: room for RWH_SEQ_MAX_IMAGES.
-// proj: a projected call -- inv_g holds the M_i, anchor is SEQ_NO_ANCHOR and the origin (0, 0).
-// ring: a call of the ring rule (with proj) -- canvas_w is the period, a multiple of SEQ_RING_TILE; a rectangle starts on the canvas,
-// is at most one period wide and may pass the canvas's edge.
-static int seq_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
-                       const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                       int row_begin, int row_end, SeqDesc* descs, SeqArgs& a, bool proj = false, bool ring = false) {
-    if (!images || !hw || !inv_g || !rects || !order || !canvas) return RWH_E_INVALID;
+// device: the images, the canvas and the ray tables are the device's (the tables 16-byte aligned).
+static int seq_prepare(const SeqCall& c, const int32_t* order, int blend, void* canvas, int row_begin, int row_end, SeqDesc* descs,
+                       SeqArgs& a, bool device) {
+    const void* const* images = c.images;
+    const int32_t *hw = c.hw, *rects = c.rects;
+    const int n = c.n, anchor = c.anchor, canvas_h = c.canvas_h, canvas_w = c.canvas_w, origin_x = c.origin_x, origin_y = c.origin_y;
+    const bool proj = c.form != SEQ_PLANE, ring = c.form == SEQ_RING;
+    if (!images || !hw || !c.mats || !rects || !order || !canvas) return RWH_E_INVALID;
     if (proj ? (anchor != SEQ_NO_ANCHOR || origin_x || origin_y) : (anchor < 0 || anchor >= n)) return RWH_E_INVALID;
+    if (proj && !seq_rays_ok(c.rays.col, c.rays.row, device)) return RWH_E_INVALID;
     if (n < 1 || n > RWH_SEQ_MAX_IMAGES || (blend != RWH_SEQ_PASTE && blend != RWH_SEQ_FEATHER)) return RWH_E_INVALID;
     if (!seq_canvas_ok(canvas_h, canvas_w) || (ring && !seq_period_ok(canvas_w))) return RWH_E_INVALID;
     if (row_begin < 0 || row_end > canvas_h || row_begin > row_end) return RWH_E_INVALID;
@@ -350,7 +395,7 @@ static int seq_prepare(const void* const* images, const int32_t* hw, const doubl
         if (ring ? (rx >= canvas_w || d.wt > canvas_w) : (rx + d.wt > canvas_w)) return RWH_E_INVALID;
         if (i == anchor && (d.mx != 0 || d.my != 0 || d.wt != d.w || d.ht != d.h)) return RWH_E_INVALID;
         for (int j = 0; j < 9; ++j) {
-            d.ih[j] = inv_g[9 * i + j];
+            d.ih[j] = c.mats[9 * i + j];
             if (i != anchor && !isfinite(d.ih[j])) return RWH_E_INVALID;
         }
     }
@@ -364,20 +409,11 @@ static int seq_prepare(const void* const* images, const int32_t* hw, const doubl
 }
 
 // seq_prepare for the rules that take the images in index order over the whole canvas: the identity order, feather, all rows.
-static int seq_prepare_indexed(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
-                               void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y, SeqDesc* descs, SeqArgs& a,
-                               bool proj = false, bool ring = false) {
-    if (n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;     // (before order[] is filled)
+static int seq_prepare_indexed(const SeqCall& c, void* canvas, SeqDesc* descs, SeqArgs& a, bool device) {
+    if (c.n < 1 || c.n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;     // (before order[] is filled)
     int32_t order[RWH_SEQ_MAX_IMAGES];
-    for (int k = 0; k < n; ++k) order[k] = k;
-    return seq_prepare(images, hw, inv_g, rects, n, anchor, order, RWH_SEQ_FEATHER, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                       0, canvas_h, descs, a, proj, ring);
-}
-
-// f(feather, gain), the two flags as std::true_type / std::false_type: the four forms of the compositor, device and host.
-template <class F> static void seq_dispatch(bool feather, bool gain, const F& f) {
-    if (gain) { if (feather) f(std::true_type{}, std::true_type{}); else f(std::false_type{}, std::true_type{}); }
-    else { if (feather) f(std::true_type{}, std::false_type{}); else f(std::false_type{}, std::false_type{}); }
+    for (int k = 0; k < c.n; ++k) order[k] = k;
+    return seq_prepare(c, order, RWH_SEQ_FEATHER, canvas, 0, c.canvas_h, descs, a, device);
 }
 
 // The gains of the gain rule: N values, each finite and > 0.
@@ -385,6 +421,41 @@ static bool seq_gains_ok(const double* gains, int n) {
     for (int i = 0; i < n; ++i)
         if (!(isfinite(gains[i]) && gains[i] > 0.0)) return false;
     return true;
+}
+
+// The gain switch of one call, host side: no gains, the N gains of the gain rule, or the maps of the block gain rule with their
+// shift (gw and gh come from the canvas in seq_gain_ok).
+struct SeqGain {
+    enum Kind { NONE, GAINS, MAPS } kind;
+    const double* gains;
+    SeqMaps maps;
+};
+static SeqGain seq_gain_n(const double* gains) { return SeqGain{gains ? SeqGain::GAINS : SeqGain::NONE, gains, SeqMaps{nullptr, 0, 0, 0}}; }
+static SeqGain seq_gain_maps(const double* maps, int shift) { return SeqGain{SeqGain::MAPS, nullptr, SeqMaps{maps, 0, 0, shift}}; }
+
+// What a call checks of its gains, after its geometry (n and the canvas are in range).  host: the maps are host memory and read
+// here, as the N gains always are.  Maps on the ring: there is no such form (include/rwh.h), and this is where it is refused.
+static bool seq_gain_ok(SeqGain& g, const SeqCall& c, bool host) {
+    if (g.kind == SeqGain::GAINS) return seq_gains_ok(g.gains, c.n);
+    if (g.kind == SeqGain::NONE) return true;
+    if (c.form == SEQ_RING || !seq_maps_of(g.maps.m, g.maps.shift, c.canvas_h, c.canvas_w, g.maps)) return false;
+    return !host || seq_maps_ok(g.maps, c.n);
+}
+
+// f(gain, value): gain is std::false_type with a null pointer, or std::true_type with the N gains (const double*) or the maps
+// (SeqMaps) -- what seq_with and the pixel functions take.  MAPS false: the call's form has no maps (the ring, refused in
+// seq_gain_ok), so none is instantiated.
+template <bool MAPS = true, class F> static void seq_gain_dispatch(const SeqGain& g, const F& f) {
+    if (g.kind == SeqGain::NONE) f(std::false_type{}, (const double*)nullptr);
+    else if (g.kind == SeqGain::GAINS) f(std::true_type{}, g.gains);
+    else if constexpr (MAPS) f(std::true_type{}, g.maps);
+}
+
+// f(feather, gain, value): the forms of the compositor over the blend and the gain switch, device and host.
+template <bool MAPS = true, class F> static void seq_dispatch(bool feather, const SeqGain& g, const F& f) {
+    seq_gain_dispatch<MAPS>(g, [&](auto gain, auto value) {
+        if (feather) f(std::true_type{}, gain, value); else f(std::false_type{}, gain, value);
+    });
 }
 
 // The compositor's shape -- stitch_kernel's (rwh_stitch.hip): 256 lanes as 64 x 4, four consecutive pixels per lane, the 12 output

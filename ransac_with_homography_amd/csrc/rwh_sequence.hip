@@ -12,8 +12,9 @@ namespace rwh {
 // so the test and the descriptor reads of the pixel loop stay on the scalar side.
 // RING: the canvas is a whole number of tiles wide (checked before the launch), so every lane has its four pixels and there is no
 // tail path.
-template <bool FEATHER, bool GAIN = false, bool PROJ = false, bool RING = false>
-__global__ __launch_bounds__(256) void seq_kernel(const SeqWith<SeqArgs, GAIN, PROJ> l) {
+// L: the launch record, SeqWith<SeqArgs, GAIN, PROJ> or SeqWithMaps<SeqArgs, PROJ> -- one body for every state of the gain switch.
+template <bool FEATHER, bool GAIN, bool PROJ, bool RING, class L>
+__global__ __launch_bounds__(256) void seq_kernel(const L l) {
     static_assert(SEQ_RING_TILE == 64 * SEQ_PX, "a ring canvas is made of whole tiles");
     const SeqArgs& a = l.a;
     const int bx0 = blockIdx.x * 64 * SEQ_PX, by0 = a.row_begin + blockIdx.y * 4;
@@ -151,96 +152,149 @@ __global__ __launch_bounds__(256) void seq_stats_sum_kernel(const unsigned long 
 
 // What both statistics entry points check, and their arguments: rwh_stitch_sequence's checks (with the index order, no canvas
 // buffer and all rows) plus the stride range.
-static int seq_stat_prepare(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n, int anchor,
-                            int canvas_h, int canvas_w, int origin_x, int origin_y, int stride, uint64_t* count, uint64_t* sum,
-                            SeqDesc* descs, StatArgs& s, bool proj = false, bool ring = false) {
+static int seq_stat_prepare(const SeqCall& c, int stride, uint64_t* count, uint64_t* sum, SeqDesc* descs, StatArgs& s, bool device) {
     if (!count || !sum || stride < 1 || stride > 255) return RWH_E_INVALID;
-    const int st = seq_prepare_indexed(images, hw, inv_g, rects, n, anchor, count, canvas_h, canvas_w, origin_x, origin_y, descs, s.a, proj, ring);
+    const int st = seq_prepare_indexed(c, count, descs, s.a, device);
     if (st != RWH_OK) return st;
     s.a.dst = nullptr;
     s.stride = stride;
-    s.nsx = (canvas_w + stride - 1) / stride;
-    s.nsy = (canvas_h + stride - 1) / stride;
+    s.nsx = (c.canvas_w + stride - 1) / stride;
+    s.nsy = (c.canvas_h + stride - 1) / stride;
     s.slabs = nullptr;
-    s.slab_words = seq_slab_words(n);
+    s.slab_words = seq_slab_words(c.n);
+    return RWH_OK;
+}
+
+// The device compositor behind every rwh_stitch_sequence* entry point: the three forms, the two blends and the three states of
+// the gain switch.
+static int seq_device(const SeqCall& c, const int32_t* order, int blend, void* d_canvas, int row_begin, int row_end, void* d_workspace,
+                      int64_t workspace_bytes, void* stream, SeqGain gain) {
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    SeqArgs a;
+    const int st = seq_prepare(c, order, blend, d_canvas, row_begin, row_end, descs, a, true);
+    if (st != RWH_OK) return st;
+    if (!seq_gain_ok(gain, c, false)) return RWH_E_INVALID;
+    if (!d_workspace || workspace_bytes < rwh_stitch_sequence_workspace_bytes(c.n) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
+    if (row_begin == row_end) return RWH_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint64_t* table = static_cast<uint64_t*>(d_workspace);
+    seq_put(descs, (size_t)c.n * SEQ_DESC_WORDS, table, s);
+    a.desc = reinterpret_cast<const SeqDesc*>(table);
+    const dim3 grid((c.canvas_w + 64 * SEQ_PX - 1) / (64 * SEQ_PX), (row_end - row_begin + 3) / 4);
+    seq_form_dispatch(c.form, [&](auto form) {
+        constexpr bool PROJ = decltype(form)::proj, RING = decltype(form)::ring;
+        seq_dispatch<!RING>(blend == RWH_SEQ_FEATHER, gain, [&](auto feather, auto on, auto value) {
+            auto l = seq_with<decltype(on)::value, PROJ>(a, value, c.n, c.rays);
+            hipLaunchKernelGGL((seq_kernel<decltype(feather)::value, decltype(on)::value, PROJ, RING, decltype(l)>), grid, dim3(256), 0, s, l);
+        });
+    });
+    return check_launch();
+}
+
+static int seq_host(const SeqCall& c, const int32_t* order, int blend, void* canvas, int row_begin, int row_end, SeqGain gain) {
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    SeqArgs a;
+    const int st = seq_prepare(c, order, blend, canvas, row_begin, row_end, descs, a, false);
+    if (st != RWH_OK) return st;
+    if (!seq_gain_ok(gain, c, true)) return RWH_E_INVALID;
+    seq_form_dispatch(c.form, [&](auto form) {
+        constexpr bool PROJ = decltype(form)::proj, RING = decltype(form)::ring;
+        seq_dispatch<!RING>(blend == RWH_SEQ_FEATHER, gain, [&](auto feather, auto on, auto value) {
+            seq_host_rows<decltype(feather)::value, decltype(on)::value, PROJ, RING>(a, value, c.rays);
+        });
+    });
+    return RWH_OK;
+}
+
+static int seq_stat_device(const SeqCall& c, int stride, uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes,
+                           void* stream) {
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    StatArgs a;
+    const int n = c.n;
+    const int st = seq_stat_prepare(c, stride, d_count, d_sum, descs, a, true);
+    if (st != RWH_OK) return st;
+    if (!d_workspace || workspace_bytes < rwh_sequence_overlap_stats_workspace_bytes(n, c.canvas_h, c.canvas_w, stride) ||
+        ((uintptr_t)d_workspace & 7u) || ((uintptr_t)d_count & 7u) || ((uintptr_t)d_sum & 7u)) return RWH_E_INVALID;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint64_t* table = static_cast<uint64_t*>(d_workspace);
+    a.slabs = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_workspace) + seq_stat_table_bytes(n));
+    if (hipMemsetAsync(a.slabs, 0, (size_t)STAT_SLABS * a.slab_words * sizeof(uint64_t), s) != hipSuccess) return RWH_E_LAUNCH;
+    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
+    a.a.desc = reinterpret_cast<const SeqDesc*>(table);
+    const dim3 grid((a.nsx + STAT_W - 1) / STAT_W, (a.nsy + STAT_H - 1) / STAT_H);
+    seq_form_dispatch(c.form, [&](auto form) {
+        constexpr bool PROJ = decltype(form)::proj, RING = decltype(form)::ring;
+        hipLaunchKernelGGL((seq_stats_kernel<PROJ, RING>), grid, dim3(256), 0, s, (seq_with<false, PROJ>(a, nullptr, n, c.rays)));
+    });
+    hipLaunchKernelGGL(seq_stats_sum_kernel, dim3((2 * n * n + 255) / 256), dim3(256), 0, s, a.slabs, a.slab_words, n * n,
+                       reinterpret_cast<unsigned long long*>(d_count), reinterpret_cast<unsigned long long*>(d_sum));
+    return check_launch();
+}
+
+static int seq_stat_host(const SeqCall& c, int stride, uint64_t* count, uint64_t* sum) {
+    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
+    StatArgs a;
+    const int n = c.n;
+    const int st = seq_stat_prepare(c, stride, count, sum, descs, a, false);
+    if (st != RWH_OK) return st;
+    memset(count, 0, (size_t)n * n * sizeof(uint64_t));
+    memset(sum, 0, (size_t)n * n * sizeof(uint64_t));
+    const uint64_t all = seq_all(n);
+    seq_form_dispatch(c.form, [&](auto form) {
+        constexpr bool PROJ = decltype(form)::proj, RING = decltype(form)::ring;
+        for (int v = 0; v < a.nsy; ++v)
+            for (int u = 0; u < a.nsx; ++u) {
+                const int cx = u * stride, cy = v * stride;
+                const uint64_t cov = seq_cover<PROJ, RING>(a.a, all, cx, cy, c.rays);
+                for (uint64_t mi = cov; mi; mi &= mi - 1) {
+                    const int i = __builtin_ctzll(mi);
+                    const uint64_t l = seq_byte_sum<PROJ, RING>(a.a, i, cx, cy, c.rays);
+                    for (uint64_t mj = cov; mj; mj &= mj - 1) {
+                        const int j = __builtin_ctzll(mj);
+                        count[(size_t)i * n + j] += 1;
+                        sum[(size_t)i * n + j] += l;
+                    }
+                }
+            }
+    });
     return RWH_OK;
 }
 
 }  // namespace rwh
+
+using rwh::seq_curved;
+using rwh::seq_gain_maps;
+using rwh::seq_gain_n;
+using rwh::seq_plane;
 
 extern "C" int64_t rwh_stitch_sequence_workspace_bytes(int n) {
     if (n < 1 || n > RWH_SEQ_MAX_IMAGES) return RWH_E_INVALID;
     return (int64_t)n * (int64_t)sizeof(rwh::SeqDesc);
 }
 
-// The device compositor behind rwh_stitch_sequence_ex (PROJ false: rays unused) and rwh_stitch_sequence_proj (PROJ true: mats holds
-// the M_i, no anchor, origin (0, 0)) and rwh_stitch_sequence_ring (RING with PROJ: canvas_w is the period).
-template <bool PROJ, bool RING = false>
-static int seq_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                      const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                      int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes, void* stream, const double* gains,
-                      rwh::SeqRays rays) {
-    using namespace rwh;
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    SeqArgs a;
-    const int st = seq_prepare(d_images, hw, mats, rects, n, anchor, order, blend, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                               row_begin, row_end, descs, a, PROJ, RING);
-    if (st != RWH_OK) return st;
-    if (!d_workspace || workspace_bytes < rwh_stitch_sequence_workspace_bytes(n) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
-    if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
-    if (row_begin == row_end) return RWH_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint64_t* table = static_cast<uint64_t*>(d_workspace);
-    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
-    a.desc = reinterpret_cast<const SeqDesc*>(table);
-    const dim3 grid((canvas_w + 64 * SEQ_PX - 1) / (64 * SEQ_PX), (row_end - row_begin + 3) / 4);
-    seq_dispatch(blend == RWH_SEQ_FEATHER, gains != nullptr, [&](auto feather, auto gain) {
-        hipLaunchKernelGGL((seq_kernel<decltype(feather)::value, decltype(gain)::value, PROJ, RING>), grid, dim3(256), 0, s,
-                           (seq_with<decltype(gain)::value, PROJ>(a, gains, n, rays)));
-    });
-    return check_launch();
-}
-
-template <bool PROJ, bool RING = false>
-static int seq_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n, int anchor,
-                    const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w, int origin_x, int origin_y,
-                    int row_begin, int row_end, const double* gains, rwh::SeqRays rays) {
-    using namespace rwh;
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    SeqArgs a;
-    const int st = seq_prepare(images, hw, mats, rects, n, anchor, order, blend, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                               row_begin, row_end, descs, a, PROJ, RING);
-    if (st != RWH_OK) return st;
-    if (gains && !seq_gains_ok(gains, n)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
-    seq_dispatch(blend == RWH_SEQ_FEATHER, gains != nullptr,
-                 [&](auto feather, auto gain) { seq_host_rows<decltype(feather)::value, decltype(gain)::value, PROJ, RING>(a, gains, rays); });
-    return RWH_OK;
-}
-
+// Every entry point below: the geometry record of its form, then the driver.
 extern "C" int rwh_stitch_sequence_ex(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                       int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
                                       int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
                                       void* stream, const double* gains) {
-    return seq_device<false>(d_images, hw, inv_g, rects, n, anchor, order, blend, d_canvas, canvas_h, canvas_w, origin_x, origin_y,
-                             row_begin, row_end, d_workspace, workspace_bytes, stream, gains, rwh::SeqRays{nullptr, nullptr});
+    return rwh::seq_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), order, blend, d_canvas,
+                           row_begin, row_end, d_workspace, workspace_bytes, stream, seq_gain_n(gains));
 }
 
 extern "C" int rwh_stitch_sequence_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                         const int32_t* order, int blend, const double* d_col, const double* d_row, void* d_canvas,
                                         int canvas_h, int canvas_w, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
                                         void* stream, const double* gains) {
-    return seq_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, d_canvas, canvas_h, canvas_w, 0, 0,
-                            row_begin, row_end, d_workspace, workspace_bytes, stream, gains, rwh::SeqRays{d_col, d_row});
+    return rwh::seq_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), order, blend, d_canvas,
+                           row_begin, row_end, d_workspace, workspace_bytes, stream, seq_gain_n(gains));
 }
 
 extern "C" int rwh_stitch_sequence_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                         const int32_t* order, int blend, const double* d_col, const double* d_row, void* d_canvas,
                                         int canvas_h, int canvas_w, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
                                         void* stream, const double* gains) {
-    return seq_device<true, true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, d_canvas, canvas_h, canvas_w, 0, 0,
-                                  row_begin, row_end, d_workspace, workspace_bytes, stream, gains, rwh::SeqRays{d_col, d_row});
+    return rwh::seq_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w, true), order, blend, d_canvas,
+                           row_begin, row_end, d_workspace, workspace_bytes, stream, seq_gain_n(gains));
 }
 
 extern "C" int rwh_stitch_sequence(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
@@ -251,25 +305,43 @@ extern "C" int rwh_stitch_sequence(const void* const* d_images, const int32_t* h
                                   row_begin, row_end, d_workspace, workspace_bytes, stream, nullptr);
 }
 
+// The compositor on the gain maps of the block gain rule (rwh_blockgains.hip makes them): d_maps / maps and shift where the calls
+// above take gains.  The host twins read the maps: every entry finite and > 0.
+extern "C" int rwh_stitch_sequence_maps(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                        int anchor, const int32_t* order, int blend, void* d_canvas, int canvas_h, int canvas_w,
+                                        int origin_x, int origin_y, int row_begin, int row_end, void* d_workspace, int64_t workspace_bytes,
+                                        void* stream, const double* d_maps, int shift) {
+    return rwh::seq_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), order, blend, d_canvas,
+                           row_begin, row_end, d_workspace, workspace_bytes, stream, seq_gain_maps(d_maps, shift));
+}
+
+extern "C" int rwh_stitch_sequence_maps_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                             const int32_t* order, int blend, const double* d_col, const double* d_row, void* d_canvas,
+                                             int canvas_h, int canvas_w, int row_begin, int row_end, void* d_workspace,
+                                             int64_t workspace_bytes, void* stream, const double* d_maps, int shift) {
+    return rwh::seq_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), order, blend, d_canvas,
+                           row_begin, row_end, d_workspace, workspace_bytes, stream, seq_gain_maps(d_maps, shift));
+}
+
 extern "C" int rwh_host_stitch_sequence_ex(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                            int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
                                            int origin_x, int origin_y, int row_begin, int row_end, const double* gains) {
-    return seq_host<false>(images, hw, inv_g, rects, n, anchor, order, blend, canvas, canvas_h, canvas_w, origin_x, origin_y,
-                           row_begin, row_end, gains, rwh::SeqRays{nullptr, nullptr});
+    return rwh::seq_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), order, blend, canvas,
+                         row_begin, row_end, seq_gain_n(gains));
 }
 
 extern "C" int rwh_host_stitch_sequence_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                              const int32_t* order, int blend, const double* col, const double* row, void* canvas,
                                              int canvas_h, int canvas_w, int row_begin, int row_end, const double* gains) {
-    return seq_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, canvas, canvas_h, canvas_w, 0, 0,
-                          row_begin, row_end, gains, rwh::SeqRays{col, row});
+    return rwh::seq_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), order, blend, canvas, row_begin, row_end,
+                         seq_gain_n(gains));
 }
 
 extern "C" int rwh_host_stitch_sequence_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                              const int32_t* order, int blend, const double* col, const double* row, void* canvas,
                                              int canvas_h, int canvas_w, int row_begin, int row_end, const double* gains) {
-    return seq_host<true, true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, order, blend, canvas, canvas_h, canvas_w, 0, 0,
-                                row_begin, row_end, gains, rwh::SeqRays{col, row});
+    return rwh::seq_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w, true), order, blend, canvas, row_begin, row_end,
+                         seq_gain_n(gains));
 }
 
 extern "C" int rwh_host_stitch_sequence(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
@@ -279,110 +351,63 @@ extern "C" int rwh_host_stitch_sequence(const void* const* images, const int32_t
                                        row_begin, row_end, nullptr);
 }
 
+extern "C" int rwh_host_stitch_sequence_maps(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
+                                             int anchor, const int32_t* order, int blend, void* canvas, int canvas_h, int canvas_w,
+                                             int origin_x, int origin_y, int row_begin, int row_end, const double* maps, int shift) {
+    return rwh::seq_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), order, blend, canvas,
+                         row_begin, row_end, seq_gain_maps(maps, shift));
+}
+
+extern "C" int rwh_host_stitch_sequence_maps_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                  const int32_t* order, int blend, const double* col, const double* row, void* canvas,
+                                                  int canvas_h, int canvas_w, int row_begin, int row_end, const double* maps, int shift) {
+    return rwh::seq_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), order, blend, canvas, row_begin, row_end,
+                         seq_gain_maps(maps, shift));
+}
+
 extern "C" int64_t rwh_sequence_overlap_stats_workspace_bytes(int n, int canvas_h, int canvas_w, int stride) {
     if (n < 1 || n > RWH_SEQ_MAX_IMAGES || stride < 1 || stride > 255) return RWH_E_INVALID;
     if (!rwh::seq_canvas_ok(canvas_h, canvas_w)) return RWH_E_INVALID;
     return rwh::seq_stat_table_bytes(n) + (int64_t)rwh::STAT_SLABS * rwh::seq_slab_words(n) * (int64_t)sizeof(uint64_t);
 }
 
-template <bool PROJ, bool RING = false>
-static int seq_stat_device(const void* const* d_images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
-                           int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
-                           uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream, rwh::SeqRays rays) {
-    using namespace rwh;
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    StatArgs a;
-    const int st = seq_stat_prepare(d_images, hw, mats, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, d_count, d_sum,
-                                    descs, a, PROJ, RING);
-    if (st != RWH_OK) return st;
-    if (!d_workspace || workspace_bytes < rwh_sequence_overlap_stats_workspace_bytes(n, canvas_h, canvas_w, stride) ||
-        ((uintptr_t)d_workspace & 7u) || ((uintptr_t)d_count & 7u) || ((uintptr_t)d_sum & 7u)) return RWH_E_INVALID;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, true)) return RWH_E_INVALID;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint64_t* table = static_cast<uint64_t*>(d_workspace);
-    a.slabs = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_workspace) + seq_stat_table_bytes(n));
-    if (hipMemsetAsync(a.slabs, 0, (size_t)STAT_SLABS * a.slab_words * sizeof(uint64_t), s) != hipSuccess) return RWH_E_LAUNCH;
-    seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
-    a.a.desc = reinterpret_cast<const SeqDesc*>(table);
-    const dim3 grid((a.nsx + STAT_W - 1) / STAT_W, (a.nsy + STAT_H - 1) / STAT_H);
-    hipLaunchKernelGGL((seq_stats_kernel<PROJ, RING>), grid, dim3(256), 0, s, (seq_with<false, PROJ>(a, nullptr, n, rays)));
-    hipLaunchKernelGGL(seq_stats_sum_kernel, dim3((2 * n * n + 255) / 256), dim3(256), 0, s, a.slabs, a.slab_words, n * n,
-                       reinterpret_cast<unsigned long long*>(d_count), reinterpret_cast<unsigned long long*>(d_sum));
-    return check_launch();
-}
-
 extern "C" int rwh_sequence_overlap_stats(const void* const* d_images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                           int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
                                           uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream) {
-    return seq_stat_device<false>(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, d_count, d_sum,
-                                  d_workspace, workspace_bytes, stream, rwh::SeqRays{nullptr, nullptr});
+    return rwh::seq_stat_device(seq_plane(d_images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), stride, d_count,
+                                d_sum, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_sequence_overlap_stats_proj(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                const double* d_col, const double* d_row, int canvas_h, int canvas_w, int stride,
                                                uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream) {
-    return seq_stat_device<true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, stride, d_count, d_sum,
-                                 d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
-}
-
-template <bool PROJ, bool RING = false>
-static int seq_stat_host(const void* const* images, const int32_t* hw, const double* mats, const int32_t* rects, int n,
-                         int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
-                         uint64_t* count, uint64_t* sum, rwh::SeqRays rays) {
-    using namespace rwh;
-    SeqDesc descs[RWH_SEQ_MAX_IMAGES];
-    StatArgs a;
-    const int st = seq_stat_prepare(images, hw, mats, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, count, sum, descs, a, PROJ, RING);
-    if (st != RWH_OK) return st;
-    if (PROJ && !seq_rays_ok(rays.col, rays.row, false)) return RWH_E_INVALID;
-    uint64_t* cnt = count;
-    uint64_t* sm = sum;
-    memset(cnt, 0, (size_t)n * n * sizeof(uint64_t));
-    memset(sm, 0, (size_t)n * n * sizeof(uint64_t));
-    const uint64_t all = seq_all(n);
-    for (int v = 0; v < a.nsy; ++v)
-        for (int u = 0; u < a.nsx; ++u) {
-            const int cx = u * stride, cy = v * stride;
-            const uint64_t cov = seq_cover<PROJ, RING>(a.a, all, cx, cy, rays);
-            for (uint64_t mi = cov; mi; mi &= mi - 1) {
-                const int i = __builtin_ctzll(mi);
-                const uint64_t l = seq_byte_sum<PROJ, RING>(a.a, i, cx, cy, rays);
-                for (uint64_t mj = cov; mj; mj &= mj - 1) {
-                    const int j = __builtin_ctzll(mj);
-                    cnt[(size_t)i * n + j] += 1;
-                    sm[(size_t)i * n + j] += l;
-                }
-            }
-        }
-    return RWH_OK;
+    return rwh::seq_stat_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w), stride, d_count, d_sum,
+                                d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_sequence_overlap_stats_ring(const void* const* d_images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                const double* d_col, const double* d_row, int canvas_h, int canvas_w, int stride,
                                                uint64_t* d_count, uint64_t* d_sum, void* d_workspace, int64_t workspace_bytes, void* stream) {
-    return seq_stat_device<true, true>(d_images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, stride, d_count, d_sum,
-                                       d_workspace, workspace_bytes, stream, rwh::SeqRays{d_col, d_row});
-}
-
-extern "C" int rwh_host_sequence_overlap_stats_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
-                                                    const double* col, const double* row, int canvas_h, int canvas_w, int stride,
-                                                    uint64_t* count, uint64_t* sum) {
-    return seq_stat_host<true, true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, stride, count, sum,
-                                     rwh::SeqRays{col, row});
+    return rwh::seq_stat_device(seq_curved(d_images, hw, m, rects, n, d_col, d_row, canvas_h, canvas_w, true), stride, d_count, d_sum,
+                                d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int rwh_host_sequence_overlap_stats(const void* const* images, const int32_t* hw, const double* inv_g, const int32_t* rects, int n,
                                                int anchor, int canvas_h, int canvas_w, int origin_x, int origin_y, int stride,
                                                uint64_t* count, uint64_t* sum) {
-    return seq_stat_host<false>(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y, stride, count, sum,
-                                rwh::SeqRays{nullptr, nullptr});
+    return rwh::seq_stat_host(seq_plane(images, hw, inv_g, rects, n, anchor, canvas_h, canvas_w, origin_x, origin_y), stride, count, sum);
 }
 
 extern "C" int rwh_host_sequence_overlap_stats_proj(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
                                                     const double* col, const double* row, int canvas_h, int canvas_w, int stride,
                                                     uint64_t* count, uint64_t* sum) {
-    return seq_stat_host<true>(images, hw, m, rects, n, rwh::SEQ_NO_ANCHOR, canvas_h, canvas_w, 0, 0, stride, count, sum,
-                               rwh::SeqRays{col, row});
+    return rwh::seq_stat_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w), stride, count, sum);
+}
+
+extern "C" int rwh_host_sequence_overlap_stats_ring(const void* const* images, const int32_t* hw, const double* m, const int32_t* rects, int n,
+                                                    const double* col, const double* row, int canvas_h, int canvas_w, int stride,
+                                                    uint64_t* count, uint64_t* sum) {
+    return rwh::seq_stat_host(seq_curved(images, hw, m, rects, n, col, row, canvas_h, canvas_w, true), stride, count, sum);
 }
 
 // The gains of the gain rule from the two tables: seq_solve_gains (rwh_sequence.h) on them.
