@@ -7,7 +7,8 @@
  * Each entry point below names the reference lines it replaces.  All pointers
  * named `d_*` are DEVICE pointers; everything else is host memory read before
  * the function returns.  `stream` is a hipStream_t (NULL = default stream).
- * Functions enqueue work and return without synchronising; they allocate
+ * Functions enqueue work and return without synchronising, except where an entry
+ * point says otherwise (rwh_ransac_run, rwh_sequence_seams*); they allocate
  * nothing and keep no state, so they may be captured into a hipGraph.
  *
  * Return value: 0 on success, a negative RWH_E_* code otherwise (never throws).
@@ -220,7 +221,7 @@ RWH_API int rwh_dlt4_batched(const float* d_pts_a, const float* d_pts_b, int m,
  * and the accept rules of ransac.py:186-202 in order-independent form.
  * One wavefront scores a run of consecutive hypotheses: lanes stride over the M
  * correspondences (kept in registers; M > 256: one wavefront per chunk of 256, counts
- * accumulated with integer atomic adds after a memset node), `err < th` is ballotted and
+ * accumulated with integer atomic adds after a fill kernel), `err < th` is ballotted and
  * popcounted.  A pair whose distance clears `th` by a proven error band is decided from a
  * reciprocal; a hypothesis with any pair inside the band (or a NaN) is redone with the
  * reference's two IEEE float32 divisions: counts and masks are bit-identical to the
@@ -504,7 +505,7 @@ RWH_API int rwh_host_match_ratio(const uint8_t* desc_a, int na, const uint8_t* d
  *   32) / 2) always holds every keypoint, since no two keypoints are neighbours).  Unused entries of a row are RWH_ORB_KEY_NONE, above every key as signed and as unsigned words;
  *   d_workspace: workspace_bytes >= rwh_orb_workspace_bytes(n_images) = 8 (n_images + 1) bytes of device memory, 8-byte aligned.
  * Work: one block of 256 lanes per tile of RWH_ORB_TILE_W x RWH_ORB_TILE_H pixels, staged with a halo of 4 as gray bytes in LDS; one
- * atomic per wave that found a keypoint.  Two launches and two memsets, whatever n_images.
+ * atomic per wave that found a keypoint.  Two launches and two fill kernels, whatever n_images.
  * RWH_E_INVALID (before any device is touched): NULL pointer, n_images <= 0, capacity <= 0, negative sizes, threshold outside 0 ..
  * 254, a workspace that is too small or misaligned.
  * rwh_orb_describe_batched: rules 4 and 5 for the first min(d_counts[i], n_features, key_stride) keys of row i of d_keys (n_images
@@ -558,7 +559,7 @@ RWH_API int rwh_host_match_ratio(const uint8_t* desc_a, int na, const uint8_t* d
  *   built on the device as for the detector; the source window (at most 258 x 66 at s = 1024) is staged as gray bytes in LDS, the
  *   row sums go to a second LDS plane, a lane sums four adjacent columns and stores them as one word where the address is aligned.
  *   Two launches (none for n_levels == 1), whatever n_images; the whole pyramid extractor is then: pyramid (2 launches), detect (2
- *   launches, 2 memsets), the caller's sort, describe (1 launch).
+ *   launches, 2 fill kernels), the caller's sort, describe (1 launch).
  *   RWH_E_INVALID (before any device is touched): NULL pointer, n_images <= 0, a bad scales table, planes_offset outside 0 ..
  *   images_bytes, n_images n_levels >= 2^31, a workspace that is too small or misaligned.
  * rwh_host_orb_pyramid: rule 6 on the HOST for one image: planes (planes_bytes >= rwh_orb_pyramid_bytes) receives levels 1 ..

@@ -83,6 +83,31 @@ inline bool orb_scales_ok(const int32_t* scales, int n_levels) {
     return true;
 }
 
+// A fill of device memory enqueued as a kernel; every driver that clears device memory on its stream uses it, none uses
+// hipMemsetAsync.  What was observed (tests/test_stream_contract_gpu.py, ROCm 7 under torch, one MI355X): a call captured alone, on
+// a side stream, into a torch.cuda.CUDAGraph and replayed through torch left other values in the words its hipMemsetAsync was
+// asked to clear -- on the first or second replay, never eagerly -- in seq_stat_device (the slabs), the chunked scorer (the counts)
+// and the detector (keys and counts); with this kernel in their place the same records replay to the reference.  The cause
+// inside the runtime was not looked for, and nothing is claimed about memset nodes in general.
+static __global__ void fill_words_kernel(uint32_t* p, uint32_t v, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
+static __global__ void fill_bytes_kernel(uint8_t* p, uint8_t v, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
+// `bytes` bytes at p set to `byte` on stream s: whole 32-bit words where p and bytes are multiples of four, else byte by byte.
+inline hipError_t fill_async(void* p, int byte, size_t bytes, hipStream_t s) {
+    if (bytes == 0) return hipSuccess;
+    const bool words = (((uintptr_t)p | bytes) & 3u) == 0;
+    const size_t n = words ? bytes / 4 : bytes;
+    const unsigned blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    if (words) hipLaunchKernelGGL(fill_words_kernel, dim3(blocks), dim3(256), 0, s, static_cast<uint32_t*>(p), 0x01010101u * (uint32_t)(byte & 0xFF), n);
+    else hipLaunchKernelGGL(fill_bytes_kernel, dim3(blocks), dim3(256), 0, s, static_cast<uint8_t*>(p), (uint8_t)(byte & 0xFF), n);
+    return hipGetLastError();
+}
+
 inline int check_launch() {
     return hipGetLastError() == hipSuccess ? RWH_OK : RWH_E_LAUNCH;
 }

@@ -453,8 +453,8 @@ extern "C" int rwh_orb_detect_batched(const uint8_t* d_images, int64_t images_by
     if (workspace_bytes < rwh_orb_workspace_bytes(n_images) || ((uintptr_t)d_workspace & 7u)) return RWH_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned long long* prefix = static_cast<unsigned long long*>(d_workspace);
-    if (hipMemsetAsync(d_keys, (int)(RWH_ORB_KEY_NONE & 0xFF), 8ull * (size_t)n_images * (size_t)capacity, s) != hipSuccess) return RWH_E_LAUNCH;
-    if (hipMemsetAsync(d_counts, 0, 4ull * (size_t)n_images, s) != hipSuccess) return RWH_E_LAUNCH;
+    if (rwh::fill_async(d_keys, (int)(RWH_ORB_KEY_NONE & 0xFF), 8ull * (size_t)n_images * (size_t)capacity, s) != hipSuccess) return RWH_E_LAUNCH;
+    if (rwh::fill_async(d_counts, 0, 4ull * (size_t)n_images, s) != hipSuccess) return RWH_E_LAUNCH;
     hipLaunchKernelGGL(orb_setup_kernel, dim3(1), dim3(256), 0, s, d_table, n_images, (long long)images_bytes, (long long)gray_bytes, prefix);
     // the gray planes hold one byte per pixel, so gray_bytes bounds the pixels; an image adds at most one partial tile per tile row and
     // column it has -- the grid walks the tile list with a stride, so any size is correct

@@ -858,7 +858,7 @@ void launch_score(int words, dim3 grid, hipStream_t s, const float* d_h, const f
         hc = hc < 1 ? 1 : (hc > 14 ? 14 : hc);
         if (g_force_score_hpw) hc = g_force_score_hpw;
         const dim3 cgrid((unsigned)(((k + hc - 1) / hc + 3) / 4), (unsigned)chunks);
-        if (chunks <= 65535 && hipMemsetAsync(d_counts, 0, sizeof(int32_t) * (size_t)k, s) == hipSuccess) {
+        if (chunks <= 65535 && fill_async(d_counts, 0, sizeof(int32_t) * (size_t)k, s) == hipSuccess) {
             if (d_masks) hipLaunchKernelGGL((score_filter_kernel<LOSS, 4, true, true>), cgrid, block, 0, s, d_h, d_pts_a, d_pts_b, m, k, hc, th,
                                             sq_limit, d_counts, d_masks, nullptr, 0, mask_stride, nullptr, nullptr, thf, d_hinv);
             else hipLaunchKernelGGL((score_filter_kernel<LOSS, 4, false, true>), cgrid, block, 0, s, d_h, d_pts_a, d_pts_b, m, k, hc, th,

@@ -367,8 +367,8 @@ static int sm_device(const SeqCall& c, const double* gains, double margin, int t
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, reinterpret_cast<uint64_t*>(base + p.desc_at), s);
     seq_put(p.win, (size_t)n * (sizeof(SmWin) / 8), reinterpret_cast<uint64_t*>(base + p.win_at), s);
     sm_bind(m, p, base);
-    if (hipMemsetAsync(m.flag, 0, 8, s) != hipSuccess) return RWH_E_LAUNCH;
-    if (hipMemsetAsync(m.dirty, 1, (size_t)p.tiles, s) != hipSuccess) return RWH_E_LAUNCH;      // pass 1 reads array 0: every tile live
+    if (fill_async(m.flag, 0, 8, s) != hipSuccess) return RWH_E_LAUNCH;
+    if (fill_async(m.dirty, 1, (size_t)p.tiles, s) != hipSuccess) return RWH_E_LAUNCH;      // pass 1 reads array 0: every tile live
     seq_form_dispatch<false>(c.form, [&](auto form) {
         seq_gain_dispatch<false>(seq_gain_n(gains), [&](auto on, const double* value) {
             constexpr bool GAIN = decltype(on)::value, PROJ = decltype(form)::proj;

@@ -218,7 +218,7 @@ static int seq_stat_device(const SeqCall& c, int stride, uint64_t* d_count, uint
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint64_t* table = static_cast<uint64_t*>(d_workspace);
     a.slabs = reinterpret_cast<unsigned long long*>(static_cast<char*>(d_workspace) + seq_stat_table_bytes(n));
-    if (hipMemsetAsync(a.slabs, 0, (size_t)STAT_SLABS * a.slab_words * sizeof(uint64_t), s) != hipSuccess) return RWH_E_LAUNCH;
+    if (fill_async(a.slabs, 0, (size_t)STAT_SLABS * a.slab_words * sizeof(uint64_t), s) != hipSuccess) return RWH_E_LAUNCH;
     seq_put(descs, (size_t)n * SEQ_DESC_WORDS, table, s);
     a.a.desc = reinterpret_cast<const SeqDesc*>(table);
     const dim3 grid((a.nsx + STAT_W - 1) / STAT_W, (a.nsy + STAT_H - 1) / STAT_H);

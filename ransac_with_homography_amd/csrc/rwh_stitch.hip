@@ -161,7 +161,7 @@ extern "C" int rwh_stitch_panorama_rows(const void* d_img_t, int t_h, int t_w, c
     if (t_h < 2 || t_w < 2 || q_h <= 0 || q_w <= 0 || warp_w <= 0 || warp_h <= 0 || canvas_h <= 0 || canvas_w <= 0) return RWH_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (flags & RWH_WARP_ZERO_ORIGIN) {
-        if (hipMemsetAsync(const_cast<void*>(d_img_t), 0, 3, s) != hipSuccess) return RWH_E_LAUNCH;
+        if (rwh::fill_async(const_cast<void*>(d_img_t), 0, 3, s) != hipSuccess) return RWH_E_LAUNCH;
     }
     if (blend < 0 || blend > 3) return RWH_E_INVALID;
     if (row_begin == row_end) return RWH_OK;

@@ -216,7 +216,7 @@ extern "C" int rwh_stitch_panorama_ex(const void* d_img_t, int t_h, int t_w, int
     if (blend ? canvas_c != 3 : (canvas_c != t_c || (q_c != t_c && q_c != 1))) return RWH_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if ((flags & RWH_WARP_ZERO_ORIGIN) && !blend) {      // bilinear() on the caller's imgT: texel (0,0), every channel (C_T 3 or 4)
-        if (hipMemsetAsync(const_cast<void*>(d_img_t), 0, (size_t)t_esz * t_c, s) != hipSuccess) return RWH_E_LAUNCH;
+        if (rwh::fill_async(const_cast<void*>(d_img_t), 0, (size_t)t_esz * t_c, s) != hipSuccess) return RWH_E_LAUNCH;
     }
     if (row_begin == row_end) return RWH_OK;
     AnyArgs a;

@@ -1032,7 +1032,7 @@ extern "C" int rwh_warp_index_check(int src_h, int src_w, const double* inv_h, d
     const WarpArgs a = make_warp_args(nullptr, src_h, src_w, 0, inv_h, x0, step_x, x_last, y0, step_y, y_last, out_h, out_w, bound_h, bound_w,
                                       nullptr, 0, 0, 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipMemsetAsync(d_flag, 0, sizeof(int), s) != hipSuccess) return RWH_E_LAUNCH;
+    if (rwh::fill_async(d_flag, 0, sizeof(int), s) != hipSuccess) return RWH_E_LAUNCH;
     const long long n = (long long)out_h * out_w;
     if ((n + 255) / 256 >= (1ll << 31)) return RWH_E_UNSUPPORTED;
     hipLaunchKernelGGL(index_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, interp, d_flag);

@@ -113,6 +113,46 @@ def test_on_a_second_stream(lib):
     assert np.array_equal(sm.device(lib, images, Gs, 0, stream=torch.cuda.Stream()), sm.host(lib, images, Gs, 0))
 
 
+def test_both_forms_on_a_second_stream_after_a_dirty_workspace(lib):
+    """The two seam entry points synchronise and cannot be captured (tests/stream_contract_cases.py exempts them); what can be held:
+    on a side stream, into a workspace that holds another fill and then their own leftovers, the labels are the host twin's."""
+    import ctypes
+    import torch
+    import projection_cases as pc
+    side = torch.cuda.Stream()
+    images, Gs = sm.three_way()
+    need = sm.workspace_bytes(lib, sc.tables(images, Gs, 0))
+    ws = torch.full((need + 4096,), 0x3C, dtype=torch.uint8, device="cuda")
+    ws[need:].fill_(0xA5)
+    torch.cuda.synchronize()
+    for _ in range(2):
+        assert np.array_equal(sm.device(lib, images, Gs, 0, workspace=ws[:need], stream=side), sm.host(lib, images, Gs, 0))
+    assert (ws[need:].cpu().numpy() == 0xA5).all(), "a byte beyond the workspace's stated size was written"
+    images, Hs = pc.sweep(3, 3)
+    Gs = sc.chain(Hs, 0)
+    t = pc.tables(images, Gs, 0, "cylindrical", 40.0)
+    fh, fw = t["size"]
+    want = sm.host_proj(lib, images, Gs, 0)
+    need = lib.rwh_sequence_seams_workspace_bytes(t["rects"].ctypes.data, t["n"], fh, fw, 0, 0)
+    assert need > 0
+    ws = torch.full((need + 4096,), 0x3C, dtype=torch.uint8, device="cuda")
+    ws[need:].fill_(0xA5)
+    dev = sc.upload(images)
+    ptrs = np.array([d.data_ptr() for d in dev], dtype=np.uint64)
+    col, row = pc.device_tables(t)
+    for _ in range(2):
+        lab, fetch = sm.guarded_device_plane(fh, fw)
+        passes = ctypes.c_int32(0)
+        torch.cuda.synchronize()
+        st = lib.rwh_sequence_seams_proj(ptrs.ctypes.data, t["hw"].ctypes.data, t["m"].ctypes.data, t["rects"].ctypes.data, t["n"], None,
+                                         float(sm.MARGIN), int(sm.TAU), col.data_ptr(), row.data_ptr(), lab.data_ptr(), fh, fw,
+                                         ws.data_ptr(), need, side.cuda_stream, ctypes.addressof(passes))
+        assert st == 0
+        side.synchronize()
+        assert np.array_equal(fetch(), want) and passes.value >= 1
+    assert (ws[need:].cpu().numpy() == 0xA5).all(), "a byte beyond the workspace's stated size was written"
+
+
 def test_a_bad_workspace_or_option_is_refused_and_nothing_written(lib):
     import torch
     images, Gs = sc.translated_strip(3)
