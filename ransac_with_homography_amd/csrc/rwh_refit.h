@@ -4,6 +4,13 @@
 //   row 1 = [x, y, 1, 0, 0, 0, -x x', -y x' | x'],  row 2 = [0, 0, 0, x, y, 1, -x y', -y y' | y'],
 // every entry a float32 input or the float64 product of two of them (exact: 24 + 24 bits).  A^T A is symmetric with two equal
 // 3 x 3 blocks and a zero block, so A^T A and A^T b together are N_MOMENTS = 23 distinct sums.
+// The normal equations alone lose the square of cond(A): with G the equilibrated A^T A their relative error is of the order of
+// 2^-53 |G^-1|, on four inliers of a narrow strip far from the origin 1e-4 px, more than an SVD of A loses.  Where they may have
+// lost more than half of the 53 bits -- trace(G^-1) >= CORRECT_ABOVE = 2^27; the trace is |G^-1|_2 to within a factor 8 and comes
+// from the Cholesky factor -- the solution is corrected once (Bjorck's corrected normal equations): the residual b - A h is taken
+// from the correspondences themselves, its N_RESIDUALS = 8 sums A^T (b - A h) go through the factor already at hand, and the
+// result is added to h; the error left is of the order of cond(A) 2^-53, not its square.  Below the threshold the first solution
+// stands, and the second pass over the correspondences is not made.
 #pragma once
 #include <stdint.h>
 
@@ -16,6 +23,7 @@
 namespace rwh_refit {
 
 static constexpr int N_MOMENTS = 23;
+static constexpr int N_RESIDUALS = 8;
 static constexpr int THREADS = 256;     // lanes of one problem's workgroup; the host twin sums in the same 256 strided partials
 static constexpr int WAVES = THREADS / 64;
 
@@ -32,6 +40,41 @@ RWH_HD void moment_update(double* s, float xf, float yf, float xpf, float ypf) {
     s[19] += xp;  s[20] += yp;  s[21] += a * xp + c * yp;  s[22] += b * xp + d * yp;
 }
 
+// t += A^T (b - A h) of one correspondence, h = the eight unknowns of a solution with h33 == 1
+RWH_HD void residual_update(double* t, const double* h, float xf, float yf, float xpf, float ypf) {
+    const double x = xf, y = yf, xp = xpf, yp = ypf;
+    const double a = x * xp, b = y * xp, c = x * yp, d = y * yp;
+    const double r1 = xp - ((((x * h[0] + y * h[1]) + h[2]) - a * h[6]) - b * h[7]);
+    const double r2 = yp - ((((x * h[3] + y * h[4]) + h[5]) - c * h[6]) - d * h[7]);
+    t[0] += x * r1;  t[1] += y * r1;  t[2] += r1;  t[3] += x * r2;  t[4] += y * r2;  t[5] += r2;
+    t[6] -= a * r1 + c * r2;  t[7] -= b * r1 + d * r2;
+}
+
+// what solve() leaves for correct(): L (lower triangle) of the equilibrated A^T A, and the equilibration D
+struct Factor {
+    double l[8][8], dd[8];
+};
+
+static constexpr double CORRECT_ABOVE = 134217728.0;    // 2^27
+
+// trace(G^-1) = |L^-1|_F^2 for G = L L^T: L^-1 column by column
+RWH_HD double inverse_trace(const Factor& f) {
+    double sum = 0.0;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        double x[8];
+#pragma unroll
+        for (int i = c; i < 8; ++i) {
+            double v = i == c ? 1.0 : 0.0;
+#pragma unroll
+            for (int k = c; k < i; ++k) v -= f.l[i][k] * x[k];
+            x[i] = v / f.l[i][i];
+            sum += x[i] * x[i];
+        }
+    }
+    return sum;
+}
+
 RWH_HD void fill_nan(double* h9) {
     for (int i = 0; i < 9; ++i) h9[i] = __builtin_nan("");
 }
@@ -40,9 +83,12 @@ RWH_HD void fill_nan(double* h9) {
 // diagonal, the solution D^-1 h of the scaled system scaled back, so h is unchanged in exact arithmetic), Cholesky, two triangular
 // solves.  h9 = row-major 3 x 3 with h9[8] == 1.  Returns RWH_REFIT_OK, RWH_REFIT_FEW (fewer than 4 inliers) or RWH_REFIT_SINGULAR
 // (a diagonal entry or Cholesky pivot that is not a positive finite number, or a non-finite solution); h9 is all NaN unless OK.
-RWH_HD int solve(const double* s, double* h9) {
+// f holds the factor when the status is OK.
+RWH_HD int solve(const double* s, Factor& f, double* h9) {
     if (!(s[5] >= 4.0)) { fill_nan(h9); return RWH_REFIT_FEW; }
-    double g[8][8], r[8], dd[8];
+    double (&g)[8][8] = f.l;
+    double (&dd)[8] = f.dd;
+    double r[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -105,6 +151,34 @@ RWH_HD int solve(const double* s, double* h9) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) h9[i] = r[i];
     h9[8] = 1.0;
+    return RWH_REFIT_OK;
+}
+
+// The corrected step: h9 += D L^-T L^-1 D t for t = A^T (b - A h9) summed over the inliers (residual_update).  Returns
+// RWH_REFIT_OK, or RWH_REFIT_SINGULAR with h9 all NaN when the corrected solution is not finite.
+RWH_HD int correct(const Factor& f, const double* t, double* h9) {
+    double r[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {       // L z = D t
+        double v = t[i] * f.dd[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v -= f.l[i][k] * r[k];
+        r[i] = v / f.l[i][i];
+    }
+#pragma unroll
+    for (int i = 7; i >= 0; --i) {      // L^T y = z
+        double v = r[i];
+#pragma unroll
+        for (int k = i + 1; k < 8; ++k) v -= f.l[k][i] * r[k];
+        r[i] = v / f.l[i][i];
+    }
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        h9[i] += r[i] * f.dd[i];
+        ok = ok && __builtin_isfinite(h9[i]);
+    }
+    if (!ok) { fill_nan(h9); return RWH_REFIT_SINGULAR; }
     return RWH_REFIT_OK;
 }
 
